@@ -22,6 +22,9 @@ exist.  Rank 0 prints ONE JSON line.
   * roofline: algorithmic bytes (20 432 B per QP at this shape) x QPs per launch / the kernel's average
     launch duration, measured with HIP events on the launch stream over the timed region, against 8.0 TB/s.
   * cpu_baseline: the CPU oracle (oracle/, a port: CPLEX cannot exist here) on the same batch, rank 0, N = 1 only.
+  * A plain run sets up, warms up, times the --steps steps and prints the headline (metric, value, ms_per_step, the workload, the
+    solver's counts).  Everything else above -- roofline, latency, cpu_baseline and parity, the spread, the other configs and
+    workloads -- is measured only with `--full`.  `--dump-outputs DIR` writes the last timed step's results as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -644,6 +647,26 @@ def single_process_main(args, torch):
         step()
     comm.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": np.concatenate([T["x"][g].cpu().numpy()[: counts[g] * nv] for g in range(G)]).reshape(n_glob, nv),
+                                         "obj": np.concatenate([T["obj"][g].cpu().numpy()[: counts[g]] for g in range(G)]),
+                                         "status": np.concatenate([T["st"][g].cpu().numpy()[: counts[g]] for g in range(G)]),
+                                         "x_all_ranks": T["all"][0].cpu().numpy().reshape(G * per, nv)})
+    head = {"metric": "qp_solves_per_sec", "value": n_glob * args.steps / elapsed, "unit": "QP/s", "n_gpus": G, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "f64" if args.precision == "f64" else "f64 iterate and residuals, f32 factorisation", "data": "synthetic",
+            "config": {"workload": "%s -- ONE batch of %d agents cut into blocks of <= %d per GPU x M=%d x %d LSC neighbours (dim=%d, %s swarm "
+                                   "after 3 warm-up replans), solve + all-gather of the plans per step" % (CONFIGS[args.config]["what"], n_glob, per, M, n_obs_eff, dim, args.style),
+                       "baseline_config": args.config, "precision": args.precision, "row_format": args.rows,
+                       "collective_backend": comm.backend, "launch": "single process, lscqp_comm (one stream + one RCCL communicator per device)",
+                       "agents_per_gpu": per, "agents_total": n_glob, "ranks": 1, "distinct_devices": G,
+                       "devices_by_crossover_rule": int(max(1, min(G, n_glob // 256))), "allgather": True,
+                       "allgather_bytes_per_rank_per_step": int(per * nv * 8), "segments": M, "lsc_neighbours": n_obs_eff, "dim": dim,
+                       "parallelism": "agents sharded over %d GPU(s), one RCCL all-gather of the plans per step" % G}}
+    if not args.full:
+        print(json.dumps(head))
+        comm.close()
+        return
     # the solve kernel alone, HIP events on device 0's communicator stream (the stream the kernel is launched on)
     s0 = torch.cuda.ExternalStream(comm.stream(0), device=torch.device("cuda", 0))
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -686,23 +709,14 @@ def single_process_main(args, torch):
         parity = {"max_abs_dx": dxm, "max_rel_dobj": dom, "compared": cmp_n, "devices": G}
     bq = sol.algorithmic_bytes(n_obs_eff)
     achieved = bq * counts[0] / (kernel_ms * 1e-3)
-    out = {"metric": "qp_solves_per_sec", "value": n_glob * args.steps / elapsed, "unit": "QP/s", "n_gpus": G, "steps": args.steps,
-           "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
-           "vs_baseline": None, "dtype": "f64" if args.precision == "f64" else "f64 iterate and residuals, f32 factorisation", "data": "synthetic",
-           "config": {"workload": "%s -- ONE batch of %d agents cut into blocks of <= %d per GPU x M=%d x %d LSC neighbours (dim=%d, %s swarm "
-                                  "after 3 warm-up replans), solve + all-gather of the plans per step" % (CONFIGS[args.config]["what"], n_glob, per, M, n_obs_eff, dim, args.style),
-                      "baseline_config": args.config, "precision": args.precision, "row_format": args.rows,
-                      "collective_backend": comm.backend, "launch": "single process, lscqp_comm (one stream + one RCCL communicator per device)",
-                      "agents_per_gpu": per, "agents_total": n_glob, "ranks": 1, "distinct_devices": G,
-                      "devices_by_crossover_rule": int(max(1, min(G, n_glob // 256))), "allgather": True,
-                      "allgather_bytes_per_rank_per_step": int(per * nv * 8), "segments": M, "lsc_neighbours": n_obs_eff, "dim": dim,
-                      "parallelism": "agents sharded over %d GPU(s), one RCCL all-gather of the plans per step" % G},
+    out = dict(head)
+    out.update({
            "roofline": {"bound": "hbm", "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": achieved / HBM_PEAK,
                         "traffic": None, "kernel": "lscqp_pdip_kernel<%d,%d,true,NSLOT,W,%s>" % (M, dim, "float" if args.precision == "mixed" else "double"),
                         "kernel_ms": kernel_ms, "algorithmic_bytes_per_qp": bq, "qps_per_launch": counts[0]},
            "latency_ms": {"sharded_step": {"p50": float(np.percentile(lat, 50)), "p99": float(np.percentile(lat, 99)), "calls": int(len(lat)),
                                            "what": "solve of every block + all-gather, enqueue -> all streams synchronised"}},
-           "solver": {"non_optimal": int((st != 0).sum()), "iters_mean": float(it.mean()), "iters_max": int(it.max())}}
+           "solver": {"non_optimal": int((st != 0).sum()), "iters_mean": float(it.mean()), "iters_max": int(it.max())}})
     if parity is not None:
         out["parity_all_ranks"] = parity
     print(json.dumps(out))
@@ -949,10 +963,18 @@ def timed_workload(ctx, a):
     t1 = time.perf_counter()
     elapsed = t1 - t0
     kernel_ms = ev0.elapsed_time(ev1) / a.steps  # average launch duration on the launch stream
+    outputs = None
+    if a.dump_outputs:
+        # what the caller of the timed path holds after its last step (under --cold: the buffers of the copy that step solved)
+        k_ = (cold_i[0] - 1) % len(cold_calls) if cold_calls is not None else None
+        o_x, o_obj, o_st = (d_x, d_obj, d_st) if k_ is None else (cX[k_], cOB[k_], cST[k_])
+        outputs = {"x": o_x[: N * nv].cpu().numpy().reshape(N, nv), "obj": o_obj.cpu().numpy(), "status": o_st.cpu().numpy()}
+        if d_all is not None:
+            outputs["x_all_ranks"] = d_all.cpu().numpy().reshape(world * n_pad, nv)
     # the run's spread: the same K-step region six more times (barrier + synchronize on both sides each time; `value` stays the FIRST region's,
     # the contract's); max over ranks per repeat
     repeats = [elapsed / a.steps * 1e3]
-    for _ in range(0 if a.no_spread else 6):
+    for _ in range(6 if (a.full and not a.no_spread) else 0):
         ctx.barrier()
         torch.cuda.synchronize()
         t_r = time.perf_counter()
@@ -963,7 +985,7 @@ def timed_workload(ctx, a):
         repeats.append((time.perf_counter() - t_r) / a.steps * 1e3)
     repeats = [ctx.reduce([r], "max")[0] for r in repeats]
 
-    if d_all is not None and not a.pipeline:
+    if a.full and d_all is not None and not a.pipeline:
         # roofline.kernel_ms is the SOLVE kernel's launch duration: time it without the exchange that shares the step's stream
         ek0, ek1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ek0.record()
@@ -987,7 +1009,7 @@ def timed_workload(ctx, a):
         paths[k] = paths[k] / max(ctx.world, 1)
     das_ms = active_set_kernel_ms(torch, api, dict(M=M, dim=dim, world_min=sw.world_min, world_max=sw.world_max,
                                                    **{k_: v_ for k_, v_ in solver_kw.items() if k_ == "row_format"}), N, n_obs_eff,
-                                  (d_hdr, d_rows, d_off, d_sfc, d_xinit))
+                                  (d_hdr, d_rows, d_off, d_sfc, d_xinit)) if a.full else None
     if das_ms is not None:
         das_ms, = ctx.reduce([das_ms], "max")
     n_bad = int(ctx.reduce([float((status != 0).sum())], "sum")[0])
@@ -1009,7 +1031,7 @@ def timed_workload(ctx, a):
             mine = d_all.view(world, n_pad * nv)[rank][: N * nv]
             if not torch.equal(mine, d_x[: N * nv]):
                 raise SystemExit("bench.py: rank %d: the all-gathered plans do not contain this rank's block" % rank)
-        if not a.no_rank_parity and not a.no_cpu_baseline and a.rows == "f64":
+        if a.full and not a.no_rank_parity and not a.no_cpu_baseline and a.rows == "f64":
             # every rank checks its OWN block against the oracle (a bounded sample: the oracle is a dense CPU solver)
             from oracle import oracle as O
 
@@ -1022,7 +1044,7 @@ def timed_workload(ctx, a):
             dxm, dom = ctx.reduce([dxm, dom], "max")
             rank_parity = {"max_abs_dx": dxm, "max_rel_dobj": dom, "compared_per_rank": int(k), "ranks": world,
                            "compared": int(ctx.reduce([float(ok.sum())], "sum")[0])}
-        if strong and not a.no_latency:
+        if a.full and strong and not a.no_latency:
             # per-step latency of the sharded step (solve of the block + the all-gather), every rank taking part: max over ranks
             ls = []
             for _ in range(260):
@@ -1034,7 +1056,7 @@ def timed_workload(ctx, a):
             p50, p99 = ctx.reduce([float(np.percentile(ls, 50)), float(np.percentile(ls, 99))], "max")
             step_lat = {"p50": p50, "p99": p99, "calls": int(len(ls)), "what": "solve of the rank's block + all-gather, enqueue -> readable, max over ranks"}
     one_gpu = None
-    if whole is not None and not a.no_one_gpu_reference:
+    if whole is not None and a.full and not a.no_one_gpu_reference:
         # the SAME global batch solved whole by rank 0's GPU alone (the other ranks wait at the barrier): the one-GPU figure of this very
         # workload, so that the line carries its own strong-scaling reference
         w_h, w_o, w_s = (to_dev(torch, x, dev) for x in (whole.hdr, whole.off, whole.sfc))
@@ -1071,7 +1093,7 @@ def timed_workload(ctx, a):
                            n_bad=n_bad, n_floor=n_floor, iters_mean=it_sum / max(n_agents_seen, 1), iters_max=int(it_max), n_ranks_seen=n_ranks_seen,
                            n_devices_seen=n_devices_seen, n_agents_seen=n_agents_seen, rank_parity=rank_parity, step_lat=step_lat, one_gpu=one_gpu,
                            solve_only=solve_only, ordered=d_order[0] is not None, paths=paths, das_ms=das_ms, repeats=repeats, clock_warm_steps=clock_warm_steps,
-                           solver_kw=solver_kw)
+                           solver_kw=solver_kw, outputs=outputs)
 
 
 def check_ran_as_asked(ctx, a, S):
@@ -1153,6 +1175,24 @@ def compact_block(ctx, a, S):
     return out
 
 
+DUMP_BYTES = 64 * 1024 * 1024  # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float64.  Over DUMP_BYTES in all, the same fixed, seeded sample of agents
+    (rows) is kept of every array and its indices are written as sample_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BYTES:
+        n = min(v.shape[0] for v in arrays.values())
+        keep = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * DUMP_BYTES // total)), replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        arrays["sample_rows"] = keep.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1200,9 +1240,19 @@ def main():
                     help="profiling aid: launch the known-byte streaming kernels (lscqp_calib) once before the warm-up, for a rocprofv3 --pmc session to see")
     ap.add_argument("--no-one-gpu-reference", action="store_true",
                     help="strong scaling: skip rank 0's solve of the WHOLE batch on its own GPU (config.one_gpu_same_workload)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: spread repeats, roofline and cold-HBM figures, latency loops, the phase-off kernel, CPU "
+                         "baseline and oracle parity, every BASELINE config at its own shape, the generic kernel, the replan chain (N > 1: the "
+                         "other workloads, per-rank parity, the one-GPU reference).  Without it a run sets up, warms up, times --steps steps "
+                         "and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last timed step (rank 0: x, obj, status; with an all-gather also "
+                         "x_all_ranks) as DIR/<name>.npy in float64")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     # what a bare `--gpus N` measures (north_star / BASELINE configs[2..4]): N = 1 the configs[1] headline; N > 1 the sharded
     # configs[3] batch + all-gather as the line's value, then the other multi-GPU configs and the weak-c1 block
     multi_default = args.gpus > 1 and args.config is None and args.scaling is None and not (args.single_process or args.pipeline or args.graph)
@@ -1279,9 +1329,11 @@ def main():
     S = timed_workload(ctx, args)
     # the other workloads of a bare multi-GPU run: every rank takes part, rank 0 keeps the blocks
     more = []
-    if multi_default and not args.no_extra:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, S.outputs)
+    if args.full and multi_default and not args.no_extra:
         for key, scal in (("c4_f64", "strong"), ("c2", "strong"), ("c1", "weak")):
-            a2 = workload_args(args, key, scaling=scal, allgather=False, no_latency=True)
+            a2 = workload_args(args, key, scaling=scal, allgather=False, no_latency=True, dump_outputs=None)
             try:
                 more.append(compact_block(ctx, a2, timed_workload(ctx, a2)))
             except Exception as ex:  # (a collective failure takes every rank here; a SystemExit ends the job, as it must)
@@ -1291,6 +1343,17 @@ def main():
             dist.destroy_process_group()
         return
     check_ran_as_asked(ctx, args, S)
+    if not args.full:
+        # the headline alone: what the timed steps measured, the workload and the solver's own counts of them
+        print(json.dumps({
+            "metric": "qp_solves_per_sec", "value": S.n_glob * args.steps / S.elapsed, "unit": "QP/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": S.elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling,
+            "vs_baseline": None, "dtype": "f64" if args.precision == "f64" else "f64 iterate and residuals, f32 factorisation", "data": "synthetic",
+            "config": workload_config(ctx, args, S),
+            "solver": {"non_optimal": S.n_bad, "floor_accepted": S.n_floor, "iters_mean": S.iters_mean, "iters_max": S.iters_max, "paths": S.paths}}))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     sol, N, M, dim, nv, n_obs_eff, n_glob = S.sol, S.N, S.M, S.dim, S.nv, S.n_obs_eff, S.n_glob
     d_hdr, d_rows, d_off, d_sfc, d_x, d_obj, d_st, d_info, d_xinit = S.d_hdr, S.d_rows, S.d_off, S.d_sfc, S.d_x, S.d_obj, S.d_st, S.d_info, S.d_xinit

@@ -4,14 +4,39 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline alone; --dump-outputs writes what the last timed step
+    computed, and a second build of the same arguments gets the same inputs: the --full run of the same batch dumps the same solution."""
+    plain, full = tmp_path / "plain", tmp_path / "full"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(plain)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
+    assert len(lines) == 1
+    b = json.loads(lines[0])
+    assert b["metric"] == "qp_solves_per_sec" and b["unit"] == "QP/s" and b["higher_is_better"] is True and b["dtype"] == "f64"
+    assert b["steps"] == 7 and b["warmup"] == 2 and b["ms_per_step"] > 0 and abs(b["value"] - 64 * 1e3 / b["ms_per_step"]) <= 1e-6 * b["value"]
+    assert b["config"]["baseline_config"] == "c1" and b["solver"]["non_optimal"] == 0
+    for k in ("roofline", "latency_ms", "cpu_baseline", "parity", "spread", "configs", "replan_chain"):  # the --full legs did not run
+        assert k not in b, k
+    x, obj, st = (np.load(plain / (n + ".npy")) for n in ("x", "obj", "status"))
+    assert x.dtype == np.float64 and x.shape[0] == 64 and obj.shape == (64,) and (st == 0).all() and np.isfinite(x).all()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3", "--no-extra", "--full",
+                          "--dump-outputs", str(full)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert np.array_equal(np.load(full / "x.npy"), x) and np.array_equal(np.load(full / "obj.npy"), obj)
+
+
+@pytest.mark.gpu
 def test_bench_prints_one_contract_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3", "--no-extra"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3", "--no-extra", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -46,7 +71,7 @@ def test_bench_line_covers_every_baseline_config_at_its_own_shape():
     """Next to the configs[1] headline, every other BASELINE config is measured at its own shape on this GPU -- QP/s, HBM fraction,
     iterations, oracle parity and CPU baseline.  (--no-latency: the 1000-call percentile loops are the driver's bench run, not a test;
     nothing here asserts a duration -- timings are recorded in the line, never judged by the correctness suite.)"""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--no-latency"], capture_output=True, text=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--no-latency", "--full"], capture_output=True, text=True,
                          timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     b = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][0])
@@ -124,7 +149,7 @@ def test_bare_gpus_2_measures_the_sharded_config_with_the_allgather():
     one device, collectives over gloo -- LSCQP_BENCH_BACKEND=gloo exists for this test) on what BASELINE's multi-GPU configs name: configs[3]
     (1024 agents x M10 x 40) as ONE batch in contiguous blocks, the plans all-gathered every step; followed by the configs[4] shape, configs[2]
     and the weak configs[1] block.  Every rank's block is checked against the oracle."""
-    out = _run_bench(["--gpus", "2", "--steps", "5", "--warmup", "2"], {"LSCQP_BENCH_BACKEND": "gloo"}, timeout=1500)
+    out = _run_bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--full"], {"LSCQP_BENCH_BACKEND": "gloo"}, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -154,7 +179,7 @@ def test_bare_gpus_2_measures_the_sharded_config_with_the_allgather():
 @pytest.mark.gpu
 def test_weak_scaling_of_the_headline_config_stays_available():
     """`--config c1 --scaling weak`: every rank owns its own 64-agent swarm, no data-path collective (the N = 1 headline replicated)."""
-    out = _run_bench(["--gpus", "2", "--config", "c1", "--scaling", "weak", "--steps", "10", "--warmup", "3", "--no-extra", "--no-latency"], {"LSCQP_BENCH_BACKEND": "gloo"})
+    out = _run_bench(["--gpus", "2", "--config", "c1", "--scaling", "weak", "--steps", "10", "--warmup", "3", "--no-extra", "--no-latency", "--full"], {"LSCQP_BENCH_BACKEND": "gloo"})
     assert out.returncode == 0, out.stderr[-3000:]
     b = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][0])
     c = b["config"]
@@ -175,7 +200,7 @@ def test_weak_scaling_of_the_headline_config_stays_available():
 def test_strong_scaling_splits_one_batch_and_gathers_the_plans():
     """BASELINE configs[2]'s mode: 512 agents as ONE batch over 2 ranks (256 each), the plans all-gathered every step; each rank's
     block against the oracle; the gathered buffer holds the rank's own block."""
-    out = _run_bench(["--gpus", "2", "--scaling", "strong", "--config", "c2", "--steps", "10", "--warmup", "3", "--no-extra"],
+    out = _run_bench(["--gpus", "2", "--scaling", "strong", "--config", "c2", "--steps", "10", "--warmup", "3", "--no-extra", "--full"],
                      {"LSCQP_BENCH_BACKEND": "gloo"})
     assert out.returncode == 0, out.stderr[-3000:]
     b = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][0])
@@ -189,7 +214,7 @@ def test_strong_scaling_splits_one_batch_and_gathers_the_plans():
     assert pr["compared"] == 32 and pr["max_abs_dx"] <= 1e-6 and pr["max_rel_dobj"] <= 1e-8
     assert b["latency_ms"]["sharded_step"]["calls"] >= 200 and b["solver"]["non_optimal"] == 0
     # a ragged split: 10 agents over 3 ranks (4 + 4 + 2), the last block padded for the collective, never solved
-    out = _run_bench(["--gpus", "3", "--scaling", "strong", "--config", "c0", "--steps", "5", "--warmup", "2", "--no-extra", "--no-latency"],
+    out = _run_bench(["--gpus", "3", "--scaling", "strong", "--config", "c0", "--steps", "5", "--warmup", "2", "--no-extra", "--no-latency", "--full"],
                      {"LSCQP_BENCH_BACKEND": "gloo"})
     assert out.returncode == 0, out.stderr[-3000:]
     b = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][0])
@@ -201,7 +226,7 @@ def test_strong_scaling_splits_one_batch_and_gathers_the_plans():
 def test_single_process_communicator_bench():
     """--single-process: the same split driven by ONE process through lscqp_comm (ncclCommInitAll + lscqp_solve_batch_sharded_device +
     lscqp_allgather); one device here, the code path is the one G devices take."""
-    out = _run_bench(["--single-process", "--gpus", "1", "--config", "c2", "--steps", "10", "--warmup", "3", "--no-latency"])
+    out = _run_bench(["--single-process", "--gpus", "1", "--config", "c2", "--steps", "10", "--warmup", "3", "--no-latency", "--full"])
     assert out.returncode == 0, out.stderr[-3000:]
     b = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][0])
     assert b["n_gpus"] == 1 and b["scaling"] == "strong" and b["config"]["agents_total"] == 512 and "rccl" in b["config"]["collective_backend"]

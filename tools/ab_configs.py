@@ -23,7 +23,7 @@ for c in configs:
         for k, lib in libs.items():
             env = dict(os.environ, LSCQP_LIB=lib)
             r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", c, "--steps", str(STEPS.get(c, 50)), "--warmup", "10",
-                                "--no-cpu-baseline", "--no-extra", "--no-latency"], env=env, capture_output=True, text=True)
+                                "--no-cpu-baseline", "--no-extra", "--no-latency", "--full"], env=env, capture_output=True, text=True)
             line = [l for l in r.stdout.splitlines() if l.startswith("{")]
             if r.returncode != 0 or not line:
                 print(c, k, "FAILED", r.stderr[-400:])

@@ -9,7 +9,7 @@ LSC / Box / Trajectory does not have, or used it with another type, this fails t
 
 ROS, octomap, dynamicEDT3D and Eigen do not exist in this image; tools/dropin_stubs/ declares just their NAMES so that the reference
 headers parse (its README says what that is and is not).  Build container only: it reads /root/reference, so nothing on the GPU box or
-in the -m gpu tests may call it; tests/test_dropin_check.py runs it when the reference checkout is present.
+in the -m gpu tests may call it; it is run by hand where a reference checkout exists (LSC_REFERENCE names it), not by the suite.
 
 usage: python tools/check_dropin.py [-v]      exit code 0 = both files type-check against the reference's headers
 """

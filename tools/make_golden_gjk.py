@@ -5,7 +5,10 @@ src/openGJK/openGJK.cpp (oracle/Makefile, target `ref`) and records its outputs 
 LSC generation meets (generic, planar = 2-D missions, repeated points = hovering agents, float32-rounded coordinates,
 origin inside the hull).  The fixture is data only: inputs and the reference's outputs.
 
-    python tools/make_golden_gjk.py  ->  tests/golden/gjk_hulls.json
+    python tools/make_golden_gjk.py  ->  tests/golden/gjk_hulls.json, tests/golden/gjk_hulls_3000.npz
+
+gjk_hulls_3000.npz holds 3000 further hulls (seed 7: generic, planar every 4th, two repeated points every 9th) with the
+reference's distance and closest point of each, for tests/test_lscgen.py's broader sweep.
 """
 import json
 import os
@@ -42,3 +45,17 @@ out = {"source": "reference src/openGJK/openGJK.cpp (gjk) called as in include/g
        "cases": cases}
 json.dump(out, open(os.path.join(ROOT, "tests", "golden", "gjk_hulls.json"), "w"))
 print(len(cases), "cases;", sum(c["dist"] == 0 for c in cases), "with the origin inside the hull")
+
+rng = np.random.default_rng(7)
+hulls, dist, closest = np.zeros((3000, 6, 3)), np.zeros(3000), np.zeros((3000, 3))
+for t in range(3000):
+    c = rng.normal(size=3) * rng.uniform(0.2, 3)
+    pts = c + rng.normal(size=(6, 3)) * rng.uniform(0.01, 1.0)
+    if t % 4 == 0:
+        pts[:, 2] = 0
+    if t % 9 == 0:
+        pts[4:] = pts[:2]
+    hulls[t] = pts
+    dist[t], closest[t] = O.ref_gjk(pts)
+np.savez_compressed(os.path.join(ROOT, "tests", "golden", "gjk_hulls_3000.npz"), hull=hulls, dist=dist, closest=closest)
+print(len(hulls), "further hulls")

@@ -32,7 +32,7 @@ STEPS = {"c1": 400, "c0": 200, "c2": 100, "c3s": 60, "c3": 20, "c4": 60, "c4_f64
 
 def bench_cmd(c, cold=False, calibrate=False):
     return [sys.executable, os.path.join(ROOT, "bench.py"), "--config", c, "--steps", str(STEPS.get(c, 50)), "--warmup", "10",
-            "--no-cpu-baseline", "--no-extra", "--no-latency", "--no-spread", "--no-cold", "--no-clock-warm"] + (  # no side loops: the trace averages the timed launches alone
+            "--no-cpu-baseline", "--no-extra", "--no-latency", "--no-spread", "--no-cold", "--no-clock-warm", "--full"] + (  # no side loops: the trace averages the timed launches alone
         ["--cold"] if cold else []) + (["--calibrate-counters"] if calibrate else [])
 
 
@@ -181,7 +181,7 @@ def profile_config(c):
 
 summary = {}
 if "nobench" not in os.environ.get("PROFILE_SKIP", ""):
-    run([sys.executable, os.path.join(ROOT, "bench.py")], tag + "_bench.log")
+    run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"], tag + "_bench.log")
     b = last_json(os.path.join(OUT, tag + "_bench.log"))
     json.dump(b, open(os.path.join(OUT, tag + "_bench.json"), "w"))
     summary["bench"] = b and {k: b[k] for k in ("value", "ms_per_step")}
