@@ -29,6 +29,13 @@ def instances():
     return [tuple(int(v) for v in m) for m in re.findall(r"X\((\d+),\s*(\d+),\s*(\d+),\s*(\d+),\s*(\d+),\s*(\d+)\)", body)]
 
 
+def fused_instances():
+    txt = open(os.path.join(CSRC, "lscqp_launch.hpp")).read()
+    body = txt[txt.index("#define LSCQP_FUSED_INSTANCES"):]
+    body = body[:body.index("\n")]
+    return [tuple(int(v) for v in m) for m in re.findall(r"X\((\d+),\s*(\d+),\s*(\d+),\s*(\d+),\s*(\d+)\)", body)]
+
+
 def _newer(target, deps):
     if not os.path.exists(target):
         return True
@@ -56,6 +63,22 @@ def build(force=False, verbose=False, jobs=None):
         if force or _newer(o, hdrs + [src]):
             extra = os.environ.get("LSCQP_EXTRA_MIXED_FLAGS", "").split() if X else os.environ.get("LSCQP_EXTRA_F64_FLAGS", "").split()
             tasks.append([HIPCC] + FLAGS + extra + ["-DLSCQP_M=%d" % M, "-DLSCQP_DIM=%d" % D, "-DLSCQP_ES=%d" % E, "-DLSCQP_NSLOT=%d" % S, "-DLSCQP_W=%d" % W, "-DLSCQP_MIXED=%d" % X, "-c", src, "-o", o])
+    # the fused forms (csrc/lscqp_fused.hip): phase + first interior-point pass in one launch; built like the instances (the phase's half keeps
+    # its own fp contraction through lscqp_das.hpp's pragma), and a second time from the race test's twin of the phase for liblscqp_sync.so
+    das_hdr = [os.path.join(CSRC, "lscqp_das.hpp"), os.path.join(CSRC, "lscqp_das_body.inc")]
+    fused_src = os.path.join(CSRC, "lscqp_fused.hip")
+    fused_pairs = []  # (product object, twin object)
+    for (M, D, E, S, W) in fused_instances():
+        defs = ["-DLSCQP_M=%d" % M, "-DLSCQP_DIM=%d" % D, "-DLSCQP_ES=%d" % E, "-DLSCQP_NSLOT=%d" % S, "-DLSCQP_W=%d" % W]
+        fo = os.path.join(OBJ, "fused_%d_%d_%d_%d_%d.o" % (M, D, E, S, W))
+        fs = os.path.join(OBJ, "fused_%d_%d_%d_%d_%d_sync.o" % (M, D, E, S, W))
+        fused_pairs.append((fo, fs))
+        objs.append(fo)
+        extra = os.environ.get("LSCQP_EXTRA_F64_FLAGS", "").split()
+        if force or _newer(fo, hdrs + das_hdr + [fused_src]):
+            tasks.append([HIPCC] + FLAGS + extra + defs + ["-c", fused_src, "-o", fo])
+        if force or _newer(fs, hdrs + das_hdr + [fused_src]):
+            tasks.append([HIPCC] + FLAGS + extra + defs + ["-DLSCQP_DAS_FULL_SYNC", "-c", fused_src, "-o", fs])
     api_o = os.path.join(OBJ, "api.o")
     objs.append(api_o)
     api_src = os.path.join(CSRC, "lscqp_api.hip")
@@ -104,7 +127,7 @@ def build(force=False, verbose=False, jobs=None):
     das_o = os.path.join(OBJ, "lscqp_das.o")
     objs.append(das_o)
     das_src = os.path.join(CSRC, "lscqp_das.hip")
-    if force or _newer(das_o, hdrs + [das_src]):
+    if force or _newer(das_o, hdrs + das_hdr + [das_src]):
         # -ffp-contract=on: a multiply-add is fused where the SOURCE writes a * b + c in one expression and nowhere else.  The default (fast) lets
         # the backend fuse across statements as the surrounding code happens to allow -- the kernel's instantiations (row formats, wavefronts
         # per QP, launch forms) then differ in the last bit, and the phase's results are required to be identical across all of them
@@ -112,7 +135,7 @@ def build(force=False, verbose=False, jobs=None):
     # the race test's twin of the dual active-set kernel (csrc/lscqp_das.hip: LSCQP_DAS_FULL_SYNC) -> liblscqp_sync.so, linked below from the
     # product's own objects with this one in place of lscqp_das.o (tests/test_race_twin.py)
     das_sync_o = os.path.join(OBJ, "lscqp_das_sync.o")
-    if force or _newer(das_sync_o, hdrs + [das_src]):
+    if force or _newer(das_sync_o, hdrs + das_hdr + [das_src]):
         tasks.append([HIPCC] + FLAGS + ["-ffp-contract=on", "-DLSCQP_DAS_FULL_SYNC", "-c", das_src, "-o", das_sync_o])
     diag_o = os.path.join(OBJ, "lscqp_diag.o")
     objs.append(diag_o)
@@ -134,7 +157,9 @@ def build(force=False, verbose=False, jobs=None):
     if tasks or not os.path.exists(LIB):
         _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl", "-lpthread"])
     if tasks or not os.path.exists(SYNC_LIB):
-        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SYNC_LIB] + [das_sync_o if o == das_o else o for o in objs] + ["-ldl", "-lpthread"])
+        twin = dict(fused_pairs)
+        twin[das_o] = das_sync_o
+        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SYNC_LIB] + [twin.get(o, o) for o in objs] + ["-ldl", "-lpthread"])
     return LIB
 
 

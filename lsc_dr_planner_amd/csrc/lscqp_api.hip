@@ -40,6 +40,15 @@ extern "C" hipError_t lscqp_launch_das(const lscqp::DevClass* cls, int M, int di
                                        int stage_rows, int screen, const double* d_tab, int64_t n, const lscqp_header* hdr, const lscqp_row* rows, const uint64_t* row_offsets,
                                        const lscqp_box* sfc, const double* x_init, double* x_out, double* obj_out, int32_t* status_out,
                                        lscqp_info* info_out, hipStream_t stream);
+// the phase and the first interior-point pass in one launch (lscqp_fused.hip), per instance of LSCQP_FUSED_INSTANCES
+using fused_fn = hipError_t (*)(const lscqp::DevClass*, int, int, int, int, int, const double*, int64_t, const lscqp_header*, const lscqp_row*,
+                                const uint64_t*, const lscqp_box*, const double*, double*, double*, int32_t*, lscqp_info*, hipStream_t);
+#define LSCQP_FUSED_DECL(M, D, E, S, W)                                                                                                       \
+    extern "C" hipError_t lscqp_launch_fused_##M##_##D##_##E##_##S##_##W(const lscqp::DevClass*, int, int, int, int, int, const double*, int64_t, \
+                                                                         const lscqp_header*, const lscqp_row*, const uint64_t*, const lscqp_box*,  \
+                                                                         const double*, double*, double*, int32_t*, lscqp_info*, hipStream_t);
+LSCQP_FUSED_INSTANCES(LSCQP_FUSED_DECL)
+#undef LSCQP_FUSED_DECL
 extern "C" int lscqp_generate_lsc_raw_(int mode, int M, int dim, int64_t n_agents, int32_t n_obs, int64_t first_agent,
                                        const double* d_traj, const double* d_own_traj, const int32_t* d_neighbours, const double* d_radius,
                                        const double* d_downwash, const double* d_goal, const double* d_goal_all, int rows_f32,
@@ -95,6 +104,7 @@ struct Knobs {
     // 50.6, 64 QPs (1.4 MB) 110 -> 85; beyond a few MB the DMA engines' bandwidth wins back what their fixed cost loses.
     int zero_copy_bytes = 4 * 1024 * 1024;
     int defer_behind = 1;    // host-pointer entries: the interior-point pass behind the phase only when the phase left something (0: always enqueued)
+    int das_fused = 1;       // LSCQP_DAS_FUSED=0: the phase and the first interior-point pass as two launches also where a fused form exists
     int das_threads = -1, das_kmax = -1, das_steps = -1, das_cache = -1, das_stage = -1, das_screen = -1, das_loop = -1;  // -1: the launch policy's value
 };
 void load_knobs(Knobs& k) {
@@ -111,6 +121,8 @@ void load_knobs(Knobs& k) {
     k.defer_behind = db ? db[0] != '0' : 1;
     const char* zc = getenv("LSCQP_ZERO_COPY_BYTES");
     if (zc) k.zero_copy_bytes = atoi(zc);
+    const char* df = getenv("LSCQP_DAS_FUSED");
+    k.das_fused = df ? df[0] != '0' : 1;
 }
 
 struct Inst {
@@ -165,6 +177,19 @@ const Inst* find_instance(const Knobs& kn, int M, int dim, int es, int mixed, in
         if (better) best = &i;
     }
     return best;
+}
+// The fused form of an fp64 instance (lscqp_fused.hip); nullptr if it has none.
+fused_fn find_fused(const Inst* i) {
+    struct F { int M, D, E, S, W; fused_fn fn; };
+    static const F kFused[] = {
+#define LSCQP_FUSED_ROW(M, D, E, S, W) {M, D, E, S, W, lscqp_launch_fused_##M##_##D##_##E##_##S##_##W},
+        LSCQP_FUSED_INSTANCES(LSCQP_FUSED_ROW)
+#undef LSCQP_FUSED_ROW
+    };
+    if (!i || i->mixed) return nullptr;
+    for (const F& f : kFused)
+        if (f.M == i->M && f.D == i->dim && f.E == i->es && f.W == i->waves && max_obs_of(f.M, f.S, f.W) == i->max_obs) return f.fn;
+    return nullptr;
 }
 // An fp64 instance of the same shape that eliminates in the OTHER order (natural vs nested dissection), smallest capacity that holds
 // n_obs; nullptr if the shape has none.  A pivot that cancels to <= 0 in one order late in the iteration usually survives in the other
@@ -609,7 +634,7 @@ int lscqp_debug_set_knob_(lscqp_handle h, const char* name, int value) {
               : n == "check_order" ? &k.check_order : n == "no_queue" ? &k.no_queue : n == "defer_behind" ? &k.defer_behind : n == "zero_copy_bytes" ? &k.zero_copy_bytes : n == "behind_scan" ? &k.behind_scan
               : n == "das_threads" ? &k.das_threads : n == "das_kmax" ? &k.das_kmax : n == "das_steps" ? &k.das_steps
               : n == "das_cache" ? &k.das_cache : n == "das_stage" ? &k.das_stage : n == "das_screen" ? &k.das_screen
-              : n == "das_loop" ? &k.das_loop : nullptr;
+              : n == "das_loop" ? &k.das_loop : n == "das_fused" ? &k.das_fused : nullptr;
     if (!slot) return fail(LSCQP_ERR_INVALID_ARGUMENT, "unknown knob: " + n);
     *slot = value;
     return LSCQP_OK;
@@ -1154,6 +1179,7 @@ int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_
     // that fills it gets one wavefront per QP and a small LDS footprint (occupancy is what hides the row reads), and the few instances
     // with more active rows than that fall to the interior-point kernel.
     bool das_ran = behind_only;
+    bool fused_ran = false;  // the first interior-point pass ran inside the phase's launch (lscqp_fused.hip)
     if (retry >= 0 && !behind_only && h->desc.active_set != LSCQP_ACTIVE_SET_OFF) {
         const bool off = kn.active_set_off && h->desc.active_set != LSCQP_ACTIVE_SET_ONLY;
         int why = 0;
@@ -1208,7 +1234,26 @@ int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_
                 if (lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) > lscqp::kMaxLdsBytes) cacheC = 0;
             }
             while (kmax > 4 && lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) > lscqp::kMaxLdsBytes) kmax -= 4;
-            if (lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) <= lscqp::kMaxLdsBytes) {
+            // FUSED (lscqp_fused.hip): a batch of at most one instance per CU whose phase runs in its small-batch form on fp64 rows, in front of
+            // an fp64 instance that has a fused form, gets ONE launch -- a workgroup that hands its instance over solves it itself, with the
+            // pass's own class (repair = 3).  The separate pass behind the phase was a launch of n workgroups that almost all load a status and
+            // leave: 64 x M5, 14.25 -> 11.82 us per call fused (profiles/r07_fused.txt).  Not for calls that look at the statuses before they
+            // enqueue the pass (`deferred`), nor behind the scan form.
+            const fused_fn fused = (kn.das_fused && tiny && !mixed && !kn.behind_scan && h->desc.active_set != LSCQP_ACTIVE_SET_ONLY && !deferred &&
+                                    threads == 256 && screen == 2 && !cls.rows_f32)
+                                       ? find_fused(inst)
+                                       : nullptr;
+            if (fused && lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) <= lscqp::kMaxLdsBytes) {
+                lscqp::DevClass fc = cls;
+                fc.repair = 3;
+                fc.queue = nullptr;
+                fc.scan = 0;
+                e = fused(&fc, cap, kmax, steps, cacheC, stage, d_tab, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_x_init, d_x_out, d_obj_out, d_status_out,
+                          d_info_out, (hipStream_t)stream);
+                if (e == hipSuccess) das_ran = fused_ran = true;
+                else if (e != hipErrorNotSupported) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (fused active-set phase): ") + hipGetErrorString(e));
+            }
+            if (!fused_ran && lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) <= lscqp::kMaxLdsBytes) {
                 e = lscqp_launch_das(&cls, Mx, dx, h->es, cap, threads, kmax, steps, cacheC, stage, screen, d_tab, n, d_hdr, d_rows, d_row_offsets, d_sfc,
                                      d_x_init, d_x_out, d_obj_out, d_status_out, d_info_out, (hipStream_t)stream);
                 if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (dual active-set phase): ") + hipGetErrorString(e));
@@ -1308,11 +1353,14 @@ int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_
         }
         cls.scan = (first->persist && !first->mixed) ? 1 : 0;
     }
-    with_queue(cls, first);
+    if (!fused_ran) {
+        with_queue(cls, first);
+        das_in_front = false;
+        e = first->fn(&cls, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_x_init, d_x_out, d_obj_out, d_status_out, d_info_out, (hipStream_t)stream);
+        cls.scan = 0;
+        if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed: ") + hipGetErrorString(e));
+    }
     das_in_front = false;
-    e = first->fn(&cls, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_x_init, d_x_out, d_obj_out, d_status_out, d_info_out, (hipStream_t)stream);
-    cls.scan = 0;
-    if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed: ") + hipGetErrorString(e));
     // Second pass over the batch, same stream, no host round trip: a workgroup whose instance is already OPTIMAL (or was
     // refused for capacity) returns at once.  Mixed precision: the fp64 kernel re-solves what the float32 factorisation could
     // not finish (same start).  retry: the fp64 kernel re-solves from the DEFAULT start what a warm start did not bring to

@@ -1,0 +1,93 @@
+// The dual active-set phase and the first interior-point pass behind it in ONE launch, for batches of at most one instance per CU.
+// Built like lscqp_inst.hip, once per instance of LSCQP_FUSED_INSTANCES (lscqp_launch.hpp), with -DLSCQP_M=<M> -DLSCQP_DIM=<dim>
+// -DLSCQP_ES=<0|1> -DLSCQP_NSLOT=<slots> -DLSCQP_W=<wavefronts per QP>; exports lscqp_launch_fused_<M>_<dim>_<ES>_<NSLOT>_<W>.
+//
+// Why: behind the phase the pass usually finds nothing to do -- every workgroup loads one status, sees OPTIMAL and leaves -- and on a batch
+// of 64 that near-empty launch was 9 - 12 % of the call (profiles/r06_*).  The device entries cannot skip it (the host learns nothing of the
+// statuses before it enqueues), so here the workgroup that handed its instance over solves it itself, right behind the phase.
+#include <atomic>
+
+#include "lscqp_kernel.hpp"
+#include "lscqp_launch.hpp"
+// (last: its fp-contraction pragma holds to the end of this file -- lscqp_pdip_one above keeps the instances' own setting)
+#include "lscqp_das.hpp"
+
+#define LSCQP_FCAT_(a, b, c, d, e, f) a##b##_##c##_##d##_##e##_##f
+#define LSCQP_FCAT(a, b, c, d, e, f) LSCQP_FCAT_(a, b, c, d, e, f)
+#define LSCQP_FUSED_FN LSCQP_FCAT(lscqp_launch_fused_, LSCQP_M, LSCQP_DIM, LSCQP_ES, LSCQP_NSLOT, LSCQP_W)
+
+namespace lscqp_das {
+
+// One workgroup of four wavefronts per instance: the phase's small-batch form (das_kernel<4, false, false, false>), then -- for an instance
+// it handed over -- the first W wavefronts run the interior-point instance on it with cls.repair = 3, exactly as the separate launch would.
+template <int M, int DIM, bool ES, int NSLOT, int W>
+__global__ __launch_bounds__(256, 1) void das_pdip_kernel(DevClass cls, int cap, int kmax, int max_steps, int cacheC, int stage_rows,
+                                                          const double* __restrict__ tab, int64_t n, const lscqp_header* __restrict__ hdr,
+                                                          const lscqp_row* __restrict__ rows, const uint64_t* __restrict__ row_offsets,
+                                                          const lscqp_box* __restrict__ sfc, const double* __restrict__ x_init,
+                                                          double* __restrict__ x_out, double* __restrict__ obj_out, int32_t* __restrict__ status_out,
+                                                          lscqp_info* __restrict__ info_out) {
+    static_assert(W >= 1 && W <= 4, "the interior-point instance runs on the first W of the workgroup's four wavefronts");
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int64_t k0 = blockIdx.x;
+    if (k0 >= n) return;
+    const int64_t q = cls.order ? (int64_t)cls.order[k0] : k0;
+    int verdict = kDasSolved;
+    {  // the phase: das_kernel<4, false, false, false>'s body (lscqp_das_body.inc) with the class's shape as constants and nothing in front
+        constexpr int NW = 4, T = 64 * NW, kU = 4;
+        constexpr bool F32 = false, SCREEN = false, PEEL = false;
+        const int dim = DIM, es = ES ? 1 : 0, behind = 0;
+#define LSCQP_DAS_END(verdict_)   \
+    do {                          \
+        verdict = (verdict_);     \
+        goto phase_done;          \
+    } while (0)
+#include "lscqp_das_body.inc"
+#undef LSCQP_DAS_END
+    }
+phase_done:
+    // (the verdict is the same in every thread: each exit of the phase is taken by the whole workgroup)
+    verdict = __builtin_amdgcn_readfirstlane(verdict);
+    if (verdict != kDasHandedOver) return;
+    // Every wavefront is done with the phase's LDS before the interior-point instance lays out its own over it, and the status thread 0
+    // stored (ITER_LIMIT) is visible to the lanes of lscqp_pdip_one, which read it again: __syncthreads() is a workgroup-scope release, the
+    // barrier, a workgroup-scope acquire.
+    __syncthreads();
+    // The wavefronts beyond W leave.  The barriers of lscqp_pdip_one then wait for the W that remain: S_BARRIER waits only for the waves of
+    // the workgroup that have not ended (CDNA4 ISA, S_BARRIER).  (readfirstlane: a wave-uniform exit, one s_endpgm per leaving wavefront.)
+    if constexpr (W < 4) {
+        if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) >= W) return;
+    }
+    lscqp::lscqp_pdip_one<M, DIM, ES, NSLOT, W, double>(cls, q, smem, hdr, rows, row_offsets, sfc, x_init, x_out, obj_out, status_out, info_out);
+}
+
+}  // namespace lscqp_das
+
+// cls: the class of the interior-point pass (repair = 3, no queue, no scan; the phase reads none of those fields).  The phase's launch
+// parameters are those of lscqp_launch_das with threads = 256, the first look inside the loop of steps, fp64 rows, nothing in front.
+// Returns hipErrorNotSupported -- and launches nothing -- when the two LDS footprints do not fit one CU or the instance cannot hold the batch;
+// the caller then launches the two kernels.
+extern "C" hipError_t LSCQP_FUSED_FN(const lscqp::DevClass* cls, int cap, int kmax, int max_steps, int cacheC, int stage_rows, const double* d_tab,
+                                     int64_t n, const lscqp_header* hdr, const lscqp_row* rows, const uint64_t* row_offsets, const lscqp_box* sfc,
+                                     const double* x_init, double* x_out, double* obj_out, int32_t* status_out, lscqp_info* info_out,
+                                     hipStream_t stream) {
+    using C = lscqp::Cfg<LSCQP_M, LSCQP_DIM, (LSCQP_ES != 0), LSCQP_NSLOT, LSCQP_W, (int)sizeof(double)>;
+    auto kern = lscqp_das::das_pdip_kernel<LSCQP_M, LSCQP_DIM, (LSCQP_ES != 0), LSCQP_NSLOT, LSCQP_W>;
+    if (kmax < 1 || kmax > lscqp_das::kMaxK || cls->rows_f32 || cls->queue || cls->scan || cls->repair != 3) return hipErrorInvalidValue;
+    if (cls->n_obs_max > C::MAX_OBS) return hipErrorNotSupported;
+    const size_t lds_das = sizeof(double) * (size_t)lscqp_das::Layout::make(LSCQP_M, LSCQP_DIM, kmax, cacheC, stage_rows).total;
+    const size_t lds = lds_das > C::lds_bytes() ? lds_das : C::lds_bytes();
+    if (lds > lscqp::kMaxLdsBytes) return hipErrorNotSupported;
+    static std::atomic<bool> attr_set[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+    if (!attr_set[dev].load(std::memory_order_acquire)) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lscqp::kMaxLdsBytes);
+        if (e != hipSuccess) return e;
+        attr_set[dev].store(true, std::memory_order_release);
+    }
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(256), lds, stream, *cls, cap, kmax, max_steps, cacheC, stage_rows, d_tab, n, hdr, rows, row_offsets, sfc,
+                       x_init, x_out, obj_out, status_out, info_out);
+    return hipGetLastError();
+}

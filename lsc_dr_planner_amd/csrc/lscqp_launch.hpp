@@ -35,3 +35,9 @@ using launch_fn = hipError_t (*)(const DevClass*, int64_t, const lscqp_header*, 
     X(10, 3, 0, 7, 2, 0) X(10, 3, 0, 9, 4, 0) X(9, 3, 0, 7, 2, 0) X(9, 3, 0, 8, 4, 0) X(9, 3, 1, 7, 2, 0) X(9, 3, 1, 8, 4, 0) X(8, 3, 0, 7, 2, 0) X(8, 3, 0, 8, 4, 0) \
     X(10, 3, 1, 20, 2, 0) X(10, 2, 1, 20, 2, 0) X(5, 3, 1, 5, 2, 0) X(5, 3, 1, 12, 2, 0) X(6, 3, 1, 7, 2, 0) X(10, 2, 1, 5, 2, 0) X(10, 3, 1, 10, 4, 0) X(10, 2, 1, 10, 4, 0) \
     X(5, 3, 1, 10, 1, 1) X(5, 3, 1, 24, 1, 1) X(6, 3, 1, 20, 1, 1) X(10, 2, 1, 10, 1, 1)
+
+// The fused forms (lscqp_fused.hip), X(M, DIM, ES, NSLOT, W): the dual active-set phase and the first interior-point pass on that fp64
+// instance in one launch, for batches of at most one instance per CU.  Compiled for the instances that serve the BASELINE shapes of such
+// batches (configs[1] 64 x M5: <5,3,1,5,2>; the forest10 replica, configs[0]: <10,2,1,5,2>; the 128-QP shard of configs[3]: <10,3,1,10,4>);
+// every other batch runs the two kernels as before.
+#define LSCQP_FUSED_INSTANCES(X) X(5, 3, 1, 5, 2) X(10, 2, 1, 5, 2) X(10, 3, 1, 10, 4)

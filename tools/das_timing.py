@@ -19,7 +19,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 if "--build-only" in sys.argv:
     o = "/tmp/lscqp_das_timing.o"
     subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + ["-DLSCQP_DAS_TIMING=0xffff", "-DLSCQP_DAS_TIMING_MIN_STEPS=%s" % os.environ.get("DAS_TIMING_MIN_STEPS", "0"), "-c", os.path.join(CSRC, "lscqp_das.hip"), "-o", o])
-    objs = [f for f in glob.glob(os.path.join(CSRC, "_obj", "*.o")) if os.path.basename(f) != "lscqp_das.o"] + [o]
+    objs = [f for f in glob.glob(os.path.join(CSRC, "_obj", "*.o")) if os.path.basename(f) != "lscqp_das.o" and not f.endswith("_sync.o")] + [o]
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + objs + ["-ldl", "-lpthread"])
     print(OUT)
     sys.exit(0)
