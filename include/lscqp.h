@@ -112,9 +112,12 @@ typedef struct lscqp_class_desc {
  * the same bar as an interior-point result (1e-9 m on every row, 1e-9 scaled stationarity, multipliers >= 0, exact complementarity);
  * what it does not finish inside its budget (active rows, steps) -- or cannot judge: dependent active rows, capacity, row systems whose
  * emptiness it cannot prove -- is solved by the interior-point kernel behind it in the same call, on the same stream, exactly as without
- * the phase.  Round 6: a row system the phase PROVES empty -- an empty interval, or a violated row (by more than 1e-6 m, the interior-point
- * kernel's own bar) whose normal lies in the span of the active rows' with no multiplier to give way: a Farkas certificate -- is returned
- * LSCQP_STATUS_INFEASIBLE by the phase itself (LSCQP_INFO_ACTIVE_SET set, res_primal = the violation) and the kernel behind skips it.
+ * the phase.  Round 6: two verdicts of the phase are final -- LSCQP_STATUS_INFEASIBLE from the phase itself (LSCQP_INFO_ACTIVE_SET set),
+ * and the kernel behind skips the instance.  (1) An empty interval, lo > hi on one control point: exact; res_primal = the largest overlap
+ * lo - hi.  (2) A violated row with no step left: its normal lies in the span of the active rows' up to a residual part of relative size
+ * sqrt(curv / spp) (curv <= 1e-12 spp, in the metric of the class's inverse Hessian), no multiplier gives way, and the violation exceeds
+ * 1e-6 m plus what that residual part could buy over the world box's diameter; res_primal = the violation.  That is a Farkas certificate
+ * up to the rounding of curv and the metric: row systems that are empty by less are handed over (LSCQP_DAS_WHY_NO_STEP).
  *   LSCQP_ACTIVE_SET_DEFAULT  on
  *   LSCQP_ACTIVE_SET_OFF      the interior-point kernel alone (rounds 1-4; also: LSCQP_ACTIVE_SET=0 in the environment when the handle is
  *                             CREATED -- the library reads its environment in lscqp_create and nowhere else)

@@ -82,8 +82,9 @@
         }
     };
     // An instance whose row system has no point, PROVEN inside the phase (an empty interval; a violated row whose normal lies in the span of
-    // the active rows' with no multiplier to give way: a Farkas certificate, taken only where the violation is beyond doubt -- the same
-    // 1e-6 m the interior-point kernel judges by): LSCQP_STATUS_INFEASIBLE here and now, nothing left for the kernel behind.  The
+    // the active rows' with no multiplier to give way: a Farkas certificate, taken only where the violation exceeds 1e-6 m plus what the
+    // normal's part outside that span could buy across the world box -- see kind 3): LSCQP_STATUS_INFEASIBLE here and now, nothing left
+    // for the kernel behind.  The
     // reference's caller keeps initial_traj for any failure (src/traj_planner.cpp:767-797); x_out is the handed-over start, as above.
     auto infeasible_out = [&](int steps, double violation) {
         for (int e = tid; e < NX; e += T) x_out[q * NX + e] = x_init ? x_init[q * NX + e] : Hd->p0[fdiv(e, 1.0f / (float)P)];
@@ -237,8 +238,14 @@
     LSCQP_DAS_BARRIER();
     if (empty) ctl_[4] = 1.0;  // (benign race: every writer stores 1)
     LSCQP_DAS_BARRIER();
-    if (ctl_[4] != 0.0) {  // an empty interval (lo > hi on one control point: exact)
-        infeasible_out(0, 1.0);
+    if (ctl_[4] != 0.0) {  // an empty interval (lo > hi on one control point: exact); its violation is the largest overlap lo - hi
+        double ov = 0.0;
+        if (wv == 0) {  // (the two-sided rows of the other families have lo = -hs <= hi = hs: they never raise it)
+            for (int r = lane; r < NPAIR; r += 64)
+                if ((pix_[r] >> 24) != 0) ov = fmax(ov, plo_[r] - phi_[r]);
+            ov = wave_max(ov);
+        }
+        infeasible_out(0, ov);
         LSCQP_DAS_END(kDasInfeasible);
     }
     DAS_T(1);  // tables, two-sided rows, unconstrained optimum
@@ -788,8 +795,8 @@
                 int l = lane;
                 wave_argmin(t1, l);
                 const double t = fmin(t1, t2);
-                int kind;  // 0: no step exists (hand over); 1: p joins; 2: row l leaves; 3: no step exists and the row is violated beyond doubt: no point satisfies the rows
-                if (!(t < 1e299)) kind = (sp < -1e-6) ? 3 : 0;
+                int kind;  // 0: no step exists (hand over); 1: p joins; 2: row l leaves; 3: no step exists and the row is violated beyond what the rest of its normal can repair: no point satisfies the rows
+                if (!(t < 1e299)) kind = (sp < -1e-6) ? 3 : 0;  // (3 is a candidate proof: checked after the loop)
                 else if (t2 <= t1) kind = 1;
                 else kind = 2;
                 DAS_T(15);
@@ -893,6 +900,19 @@
         if (stop) break;
     }
     if (!solved) {
+        if (proven) {
+            // A proof only if the violation exceeds what the candidate's part outside the active rows' span could still buy: about
+            // sqrt(curv / spp) |a_p| per metre travelled, over at most the world box's diameter.  curv = a_p'C a_p - v'r as the last step's
+            // decision had it, again from what LDS holds -- the candidate's descriptors (slot kmax), W and r_ -- by every thread alike.
+            const int* const pe = &aint_[4 * kmax + 1];
+            const double* const pc = &acoef_[3 * kmax];
+            double vr = 0.0;
+            for (int j = 0; j < k; j++) vr += r_[j] * row_dot(pe, pc, W_ + (size_t)j * NX);
+            const double spp = cdot(pe, pc, pe, pc, Cm, P);
+            const double d0 = wb_[3] - wb_[0], d1 = wb_[4] - wb_[1], d2 = wb_[5] - wb_[2];
+            const double reach = sqrt(fmax(spp - vr, 0.0) / spp * (pc[0] * pc[0] + pc[1] * pc[1] + pc[2] * pc[2]) * (d0 * d0 + d1 * d1 + d2 * d2));
+            proven = ctl_[7] > 1e-6 + reach;  // (otherwise: handed over, LSCQP_DAS_WHY_NO_STEP)
+        }
         if (proven) infeasible_out(steps, ctl_[7]);
         else hand_over(steps, why);
         DAS_T_FLUSH();

@@ -382,13 +382,13 @@ __global__ __launch_bounds__(kT) void pdip_generic_kernel(DevClass cls, int M_, 
     const double mu_scale = fmin(1e3, fmax(1.0, 0.25 * pull));
     const double MU0 = (x_init ? cls.warm_mu0 : LSCQP_COLD_MU0) * mu_scale, S0MIN = x_init ? cls.warm_s0 : 0.1;
     int status = LSCQP_STATUS_ITER_LIMIT;
-    auto centre_rows = [&](double mu_c, double s_c, double& cnt, bool& bad) {
+    auto centre_rows = [&](double mu_c, double s_c, double& cnt, double& bad) {
 #pragma unroll
         for (int u = 0; u < kR2; u++) {
             double sl0 = 1.0, sh0 = 1.0, l0 = 0.0;
             if (t_on[u]) {
                 const double y = row_val(c_, u);
-                if (t_lo[u] > t_hi[u]) bad = true;
+                if (t_lo[u] > t_hi[u]) bad = fmax(bad, t_lo[u] - t_hi[u]);
                 sl0 = fmax(y - t_lo[u], s_c);
                 sh0 = fmax(t_hi[u] - y, s_c);
                 l0 = 1.0;
@@ -409,13 +409,14 @@ __global__ __launch_bounds__(kT) void pdip_generic_kernel(DevClass cls, int M_, 
             Rs_[o * CP + lcp] = s_init, Rl_[o * CP + lcp] = l_init;
         }
     };
-    double m_tot = 0;
+    double m_tot = 0, empty_ov = 0;
     {
         double cnt = 0;
-        bool bad = false;
+        double bad = 0.0;
         centre_rows(MU0, S0MIN, cnt, bad);
         m_tot = block_sum(cnt);
-        if (block_max(bad ? 1.0 : 0.0) > 0.0) status = LSCQP_STATUS_INFEASIBLE;
+        empty_ov = block_max(bad);
+        if (empty_ov > 0.0) status = LSCQP_STATUS_INFEASIBLE;  // (res_primal: the largest overlap lo - hi)
     }
     const double inv_m = 1.0 / m_tot;
 
@@ -488,7 +489,7 @@ __global__ __launch_bounds__(kT) void pdip_generic_kernel(DevClass cls, int M_, 
         return v;
     };
 
-    double res_p = 0, res_d = 0, res_gap = 0, snap_p = 0, snap_d = 0, snap_gap = 0, obj_abs = 0;
+    double res_p = empty_ov, res_d = 0, res_gap = 0, snap_p = 0, snap_d = 0, snap_gap = 0, obj_abs = 0;
     bool restore = false;
     int it = 0, near_cnt = 0, floor_cnt = 0;
     float rp_ref = 3.0e38f;
@@ -663,7 +664,7 @@ __global__ __launch_bounds__(kT) void pdip_generic_kernel(DevClass cls, int M_, 
             const bool net = cls.warm_net > 0 && x_init != nullptr && it == 1 && !net_done && (double)alpha_first < cls.warm_net;
             if (net || (!recentred && jam_since >= 6 && floor_cnt == 0)) {
                 double cnt_ = 0;
-                bool bad_ = false;
+                double bad_ = 0.0;
                 centre_rows(1e-3 * mu_scale, 0.03, cnt_, bad_);
                 if (net) net_done = true; else recentred = true;
                 rp_ref = 3.0e38f;
@@ -1055,8 +1056,11 @@ __global__ __launch_bounds__(kT) void pdip_generic_kernel(DevClass cls, int M_, 
         status = LSCQP_STATUS_OPTIMAL;
         restore = true;
     }
-    if (status == LSCQP_STATUS_ITER_LIMIT && res_p > 1e-6) status = LSCQP_STATUS_INFEASIBLE;
-    if (status == LSCQP_STATUS_NUMERIC && res_p > 1e-6) status = LSCQP_STATUS_INFEASIBLE;
+    // An iteration that ran out (or broke down) with its primal residual still open is called INFEASIBLE only at the stall test's own
+    // scale, 1e-4 m: a feasible row pair 1e-6 m apart along a near-antiparallel direction ends here with ~1.5e-6 m and is no proof of
+    // anything (tests/test_infeasible_verdicts.py) -- it stays ITER_LIMIT / NUMERIC, a failure all the same for the caller.
+    if (status == LSCQP_STATUS_ITER_LIMIT && res_p > 1e-4) status = LSCQP_STATUS_INFEASIBLE;
+    if (status == LSCQP_STATUS_NUMERIC && res_p > 1e-4) status = LSCQP_STATUS_INFEASIBLE;
     if (restore) {
         __syncthreads();
         for (int zi = tid; zi < NZ; zi += kT) z_[zi] = zs_[zi];

@@ -195,8 +195,9 @@ def test_budget_exhausted_instances_are_solved_by_the_interior_point_kernel(api,
 
 @pytest.mark.gpu
 def test_infeasible_and_refused_instances_keep_the_interior_point_kernels_statuses(api, oracle, torch_cuda, solver_path):
-    """The phase never answers INFEASIBLE or CAPACITY itself: an instance whose rows admit no point and one with more obstacles than the
-    launch's kernel instance holds get exactly the statuses they get without the phase, and their neighbours in the batch are solved."""
+    """An instance whose rows admit no point and one with more obstacles than the launch's kernel instance holds get exactly the statuses they
+    get without the phase (INFEASIBLE -- proven by the phase or found by the interior-point kernel -- and CAPACITY, which only the kernel
+    gives), and their neighbours in the batch are solved."""
     import torch
 
     from lsc_dr_planner_amd import synth
