@@ -59,15 +59,17 @@ constexpr double kTolD = 1e-9;      // accepted stationarity (scaled like lscqp_
 constexpr int kMaxK = 32;           // active rows the phase can hold (lanes of one wavefront own the rows of the small factor)
 
 // ---- tables, per number of terminal segments ts = 1 .. M:  [U1 (P) | U2 (P) | G1 (P) | C (P x P, symmetric)] --------------------------
-__host__ __device__ inline size_t table_stride(int M) { return (size_t)(3 + 6 * M) * (size_t)(6 * M); }
-__host__ __device__ inline int num_pairs(int M, int dim) { return dim * (6 * M + 5 * M + 4 * M + M * (M - 1) / 2); }
+__host__ __device__ constexpr size_t table_stride(int M) { return (size_t)(3 + 6 * M) * (size_t)(6 * M); }
+__host__ __device__ constexpr int num_pairs(int M, int dim) { return dim * (6 * M + 5 * M + 4 * M + M * (M - 1) / 2); }
 
-// LDS carve of one QP, in doubles.
+// LDS carve of one QP, in doubles.  kmax and n_stage are the CAPACITIES the carve holds (active rows; LSC rows staged per instance); the
+// budgets a launch runs with may be smaller.  das_kernel carves at run time from its arguments; the fused kernel (lscqp_fused.hip) carves
+// at compile time from its instance's maxima, so that every offset is an immediate and no scalar register holds one.
 struct Layout {
     int P, NX, kmax, NPAIR;
     int o_hdr, o_sfc, o_c, o_cu, o_lam, o_plo, o_phi, o_pix, o_W, o_L, o_u, o_r, o_arhs, o_acoef, o_aint, o_red, o_ctl, o_wb, o_dq, o_C, o_rows, o_tl, n_stage, total;
-    __host__ __device__ static Layout make(int M, int dim, int kmax, int cacheC, int stage_rows = 0) {
-        Layout s;
+    __host__ __device__ static constexpr Layout make(int M, int dim, int kmax, int cacheC, int stage_rows = 0) {
+        Layout s{};
         s.P = 6 * M, s.NX = dim * s.P, s.kmax = kmax, s.NPAIR = num_pairs(M, dim);
         int o = 0;
         auto take = [&](int n) { const int at = o; o += (n + 1) & ~1; return at; };
@@ -159,11 +161,14 @@ __device__ __forceinline__ int fdiv(int a, float inv_b) { return (int)(((float)a
 
 // Development aid: per-phase cycle totals, compiled in only with -DLSCQP_DAS_TIMING (tools/das_timing.py)
 #ifdef LSCQP_DAS_TIMING
-__device__ unsigned long long das_cycles[16];
+#ifndef LSCQP_DAS_CYCLES
+#define LSCQP_DAS_CYCLES das_cycles  // (the fused translation unit keeps its totals under a name of its own: das_fused_cycles)
+#endif
+__device__ unsigned long long LSCQP_DAS_CYCLES[16];
 // (thread 0 accumulates in LDS and adds to the global totals once, at the end: an atomic behind every probe would be waited for by the next
 // wait on vector memory -- a round trip of microseconds booked on whatever phase comes next)
 #define DAS_T_DECL()                                                                                                                  \
-    unsigned long long* const das_tl_ = reinterpret_cast<unsigned long long*>(smem + Layout::make(M, dim, kmax, cacheC, stage_rows).o_tl); \
+    unsigned long long* const das_tl_ = reinterpret_cast<unsigned long long*>(smem + L.o_tl);                                         \
     if (threadIdx.x == 0)                                                                                                             \
         for (int i_ = 0; i_ < 16; i_++) das_tl_[i_] = 0;                                                                              \
     unsigned long long tprev_ = __builtin_readcyclecounter()
@@ -178,10 +183,10 @@ __device__ unsigned long long das_cycles[16];
 #ifndef LSCQP_DAS_TIMING_MIN_STEPS
 #define LSCQP_DAS_TIMING_MIN_STEPS 0  /* only instances with at least that many steps are booked */
 #endif
-#define DAS_T_FLUSH()                                                                  \
-    do {                                                                               \
-        if (tid == 0 && steps >= LSCQP_DAS_TIMING_MIN_STEPS)                           \
-            for (int i_ = 0; i_ < 16; i_++) atomicAdd(&das_cycles[i_], das_tl_[i_]);   \
+#define DAS_T_FLUSH()                                                                    \
+    do {                                                                                 \
+        if (tid == 0 && steps >= LSCQP_DAS_TIMING_MIN_STEPS)                             \
+            for (int i_ = 0; i_ < 16; i_++) atomicAdd(&LSCQP_DAS_CYCLES[i_], das_tl_[i_]);   \
     } while (0)
 #else
 #define DAS_T_DECL() \
@@ -255,6 +260,7 @@ __global__ __launch_bounds__(64 * NW, (SCREEN ? LSCQP_DAS_WPES : NW == 1 ? LSCQP
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int T = 64 * NW;
     constexpr int kU = SCREEN ? 4 : (NW == 1) ? LSCQP_DAS_KU1 : 4;  // LSC rows in flight per thread (the one-wavefront full form trades them for a third wavefront per SIMD)
+    constexpr int kMaxNL = 0x7fffffff;  // (LSC rows per instance: bounded by `cap` at run time only)
     const int64_t k0 = blockIdx.x;
     if (k0 >= n) return;
     const int64_t q = cls.order ? (int64_t)cls.order[k0] : k0;

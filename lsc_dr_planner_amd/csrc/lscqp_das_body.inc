@@ -1,15 +1,24 @@
 // lscqp_das_body.inc — the dual active-set phase on ONE instance q, by the workgroup of 64 * NW threads (lscqp_das.hpp).
 // Included textually into the body of a kernel -- das_kernel, and lscqp_fused.hip's das_pdip_kernel -- where these are in scope:
-//   NW, F32, SCREEN, PEEL, T = 64 * NW, kU (constants); cls, M, dim, es, cap, kmax, max_steps, cacheC, stage_rows, behind, tab, q, hdr, rows,
-//   row_offsets, sfc, x_init, x_out, obj_out, status_out, info_out; smem (the dynamic LDS, lscqp_das_lds_bytes(M, dim, kmax, cacheC, stage_rows));
-//   LSCQP_DAS_END(verdict): leaves the phase with a DasVerdict, taken by the whole workgroup at once.
+//   NW, F32, SCREEN, PEEL, T = 64 * NW, kU, kMaxNL (constants; kMaxNL bounds an instance's LSC rows); cls, M, dim, es, cap, kmax, max_steps,
+//   cacheC, stage_rows, behind, tab, q, hdr, rows, row_offsets, sfc, x_init, x_out, obj_out, status_out, info_out; smem (the dynamic LDS,
+//   lscqp_das_lds_bytes(M, dim, kmax, cacheC, stage_rows), or the carve of LSCQP_DAS_LAYOUT);
+//   LSCQP_DAS_END(verdict): leaves the phase with a DasVerdict, taken by the whole workgroup at once;
+//   LSCQP_DAS_LAYOUT (optional): the LDS carve as a constant expression, with room for at least kmax active rows, the class's table and
+//   stage_rows staged rows; without it the carve is made at run time from kmax, cacheC and stage_rows.  kmax, max_steps, cacheC and
+//   stage_rows are the launch's BUDGETS either way: the carve's capacities (L.kmax, L.n_stage) only place the arrays.
 // (Text, not a function: the kernel's own code then is exactly what it was as one function -- a __forceinline__ device function holding this
 // body was simplified before it was inlined, through a generic LDS pointer, and das_kernel came out 2 VGPRs and some SGPR spills different
 // and the 512-QP batches 2 % slower, measured.)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    DAS_T_DECL();
+#ifdef LSCQP_DAS_LAYOUT
+    constexpr Layout L = LSCQP_DAS_LAYOUT;
+#else
     const Layout L = Layout::make(M, dim, kmax, cacheC, stage_rows);
+#endif
+    DAS_T_DECL();
     const int P = L.P, NX = L.NX, NPAIR = L.NPAIR;
+    const int kcap = L.kmax;  // active rows the carve holds (>= the budget kmax); slot kcap of the descriptors is the candidate's
     double* const H_ = smem + L.o_hdr;
     double* const sfc_ = smem + L.o_sfc;
     double* const c_ = smem + L.o_c;
@@ -18,23 +27,23 @@
     double* const plo_ = smem + L.o_plo;
     double* const phi_ = smem + L.o_phi;
     int* const pix_ = reinterpret_cast<int*>(smem + L.o_pix);  // packed stencil of a two-sided row: type << 24 | first entry index (in 0 .. NX-1) << 12 | second
-    double* const W_ = smem + L.o_W;   // [kmax + 1][NX]
-    double* const Jm_ = smem + L.o_L;  // [kmax][kmax + 1] J = L^-1, S = A'C A = L L' over the active rows
+    double* const W_ = smem + L.o_W;   // [kcap + 1][NX]
+    double* const Jm_ = smem + L.o_L;  // [kcap][kcap + 1] J = L^-1, S = A'C A = L L' over the active rows
     double* const u_ = smem + L.o_u;
     double* const r_ = smem + L.o_r;
-    double* const arhs_ = smem + L.o_arhs;    // [kmax + 1]: slot kmax = the candidate row
-    double* const acoef_ = smem + L.o_acoef;  // [kmax + 1][3]
-    int* const aint_ = reinterpret_cast<int*>(smem + L.o_aint);  // [kmax + 1][4]: id, entry0, entry1, entry2
+    double* const arhs_ = smem + L.o_arhs;    // [kcap + 1]: slot kcap = the candidate row
+    double* const acoef_ = smem + L.o_acoef;  // [kcap + 1][3]
+    int* const aint_ = reinterpret_cast<int*>(smem + L.o_aint);  // [kcap + 1][4]: id, entry0, entry1, entry2
     double* const red_ = smem + L.o_red;      // [2][16]
     double* const ctl_ = smem + L.o_ctl;      // step decision of wavefront 0: t, kind, leaving row, accumulated multiplier of the candidate
     double* const wb_ = smem + L.o_wb;
     double* const dq_ = smem + L.o_dq;        // world_min[3], world_max[3]
     double* const Cc_ = smem + L.o_C;
     double* const Sx_ = smem + L.o_rows;      // staged LSC rows: [nx | ny | nz | b] x stage_rows
-    double* const Sy_ = Sx_ + stage_rows;
-    double* const Sz_ = Sy_ + stage_rows;
-    double* const Sb_ = Sz_ + stage_rows;
-    const int LDL = kmax + 1;
+    double* const Sy_ = Sx_ + L.n_stage;
+    double* const Sz_ = Sy_ + L.n_stage;
+    double* const Sb_ = Sz_ + L.n_stage;
+    const int LDL = kcap + 1;
     int par = 0;  // which half of red_ the next cross-wavefront reduction uses (double buffered: one barrier per reduction)
 
     if (!SCREEN && behind) {  // (uniform) behind the lean form: what it finished is skipped before anything is fetched
@@ -299,15 +308,16 @@
         const int type = pk >> 24, e0 = (pk >> 12) & 0xfff, e1 = pk & 0xfff;
         const double sg = (s & 1) ? -1.0 : 1.0;
         R.rhs = (s & 1) ? -phi_[r] : plo_[r];
-        if (type == 1) {
-            R.ent[0] = ent_of(e0), R.coef[0] = sg;
-        } else if (type == 2) {
-            R.ent[0] = ent_of(e0 + 1), R.ent[1] = ent_of(e0), R.coef[0] = sg, R.coef[1] = -sg;
-        } else if (type == 3) {
-            R.ent[0] = ent_of(e0 + 2), R.ent[1] = ent_of(e0 + 1), R.ent[2] = ent_of(e0), R.coef[0] = sg, R.coef[1] = -2.0 * sg, R.coef[2] = sg;
-        } else {
-            R.ent[0] = ent_of(e1), R.ent[1] = ent_of(e0), R.coef[0] = sg, R.coef[1] = -sg;
-        }
+        // 1: c[e0]   2: c[e0+1] - c[e0]   3: c[e0+2] - 2 c[e0+1] + c[e0]   else (4): c[e1] - c[e0].  Selects, not a chain of branches: with
+        // the fused kernel's compile-time carve, the compiler merged the branches so that a pair row (type 4) left the phase with coef[1]
+        // undefined (0 in practice) -- a different row, found on c1_infeasible_1pct (NOTES.md section 16).  The values are the branches' own.
+        const bool t1 = type == 1, t2 = type == 2, t3 = type == 3;
+        R.ent[0] = ent_of(t1 ? e0 : t2 ? e0 + 1 : t3 ? e0 + 2 : e1);
+        R.ent[1] = t1 ? 0 : ent_of(t3 ? e0 + 1 : e0);
+        R.ent[2] = t3 ? ent_of(e0) : 0;
+        R.coef[0] = sg;
+        R.coef[1] = t1 ? 0.0 : t3 ? -2.0 * sg : -sg;
+        R.coef[2] = t3 ? sg : 0.0;
     };
     auto row_dot = [&](const int* ent, const double* coef, const double* vec) -> double {  // a'vec for a vector in c_ layout
         return coef[0] * vec[ent_axis(ent[0]) * P + ent_cp(ent[0])] + coef[1] * vec[ent_axis(ent[1]) * P + ent_cp(ent[1])] +
@@ -361,7 +371,7 @@
             prep(tid, px, py, pz, pw, rx, ry, rz, rb);
             if (staged) stage(tid, rx, ry, rz, rb);
             eval(tid, rx, ry, rz, rb);
-            for (int j0 = tid + kU * T; j0 < nL; j0 += kU * T) {
+            for (int j0 = tid + kU * T; kMaxNL > kU * T && j0 < nL; j0 += kU * T) {  // (no trip where the class's rows fit one block)
                 double x[kU], y[kU], z[kU], w[kU];
 #pragma unroll
                 for (int u = 0; u < kU; u++) fetch_row(j0 + u * T < nL ? j0 + u * T : 0, x[u], y[u], z[u], w[u]);
@@ -478,13 +488,13 @@
     auto solve_factor = [&](int k_, double vi, double* yy) -> double {
         const int k = __builtin_amdgcn_readfirstlane(k_);
         const bool mine = lane < k;
-        const int ll = min(lane, kmax - 1);
+        const int ll = min(lane, kcap - 1);
         vi = mine ? vi : 0.0;
         double yi = 0.0, ri = 0.0;
         for (int j0 = 0; j0 < k; j0 += 8) {  // y = J v (row ll of J)
             double Jr[8];
 #pragma unroll
-            for (int t_ = 0; t_ < 8; t_++) Jr[t_] = Jm_[ll * LDL + min(j0 + t_, kmax)];  // (column kmax: always zero)
+            for (int t_ = 0; t_ < 8; t_++) Jr[t_] = Jm_[ll * LDL + min(j0 + t_, kcap)];  // (column kcap: always zero)
 #pragma unroll
             for (int t_ = 0; t_ < 8; t_++) yi += Jr[t_] * lscqp::bcast(vi, j0 + t_);  // (k <= 32: the lane index stays below 64; lanes >= k hold 0)
         }
@@ -493,12 +503,12 @@
         for (int j0 = 0; j0 < k; j0 += 8) {  // r = J'y (column ll of J)
             double Jc[8];
 #pragma unroll
-            for (int t_ = 0; t_ < 8; t_++) Jc[t_] = Jm_[min(j0 + t_, kmax - 1) * LDL + ll];  // (a clamped row meets y = 0)
+            for (int t_ = 0; t_ < 8; t_++) Jc[t_] = Jm_[min(j0 + t_, kcap - 1) * LDL + ll];  // (a clamped row meets y = 0)
 #pragma unroll
             for (int t_ = 0; t_ < 8; t_++) ri += Jc[t_] * lscqp::bcast(yi, j0 + t_);
         }
         ri = mine ? ri : 0.0;
-        if (lane < kmax + 4) r_[lane] = ri;  // (zeros behind the active rows: the update of c reads a window of four without a test)
+        if (lane < kcap + 4) r_[lane] = ri;  // (zeros behind the active rows: the update of c reads a window of four without a test)
         return ri;
     };
     // c_[e] = base[e] (or c_[e]) + sum_j wts[j] W_j[e] over the active rows
@@ -713,7 +723,7 @@
         }
         if (!haveJ) {  // (before the first step; by wavefront 0, the only one that touches J: in order with its own use)
             if (wv == 0)
-                for (int e = lane; e < kmax * LDL; e += 64) Jm_[e] = 0.0;
+                for (int e = lane; e < kcap * LDL; e += 64) Jm_[e] = 0.0;
             haveJ = true;
         }
         if (cacheC && !haveC) {  // the table of this instance's ts in LDS from the first step on (every step reads a few of its columns)
@@ -734,13 +744,13 @@
             Cm = Cc_;
             LSCQP_DAS_BARRIER();  // (every thread reads columns other threads copied)
         }
-        // ---- the candidate row p = bid, slot kmax of the descriptors ----
+        // ---- the candidate row p = bid, slot kcap of the descriptors ----
         Row Rp;
         decode(bid, Rp);
         if (tid == 0) {
-            aint_[4 * kmax] = bid;
-            for (int t = 0; t < 3; t++) aint_[4 * kmax + 1 + t] = Rp.ent[t], acoef_[3 * kmax + t] = Rp.coef[t];
-            arhs_[kmax] = Rp.rhs;
+            aint_[4 * kcap] = bid;
+            for (int t = 0; t < 3; t++) aint_[4 * kcap + 1 + t] = Rp.ent[t], acoef_[3 * kcap + t] = Rp.coef[t];
+            arhs_[kcap] = Rp.rhs;
             ctl_[3] = 0.0;  // the candidate's multiplier so far
         }
         // w_p = C a_p goes into slot k of W.  Wavefront 0's decision of the first partial step does not read it -- a_p'C a_p comes straight from
@@ -856,9 +866,9 @@
             DAS_T(11);  // the step itself: c, W
             if (kind == 1) {
                 if (tid == 0) {
-                    for (int t_ = 0; t_ < 4; t_++) aint_[4 * k + t_] = aint_[4 * kmax + t_];
-                    for (int t_ = 0; t_ < 3; t_++) acoef_[3 * k + t_] = acoef_[3 * kmax + t_];
-                    arhs_[k] = arhs_[kmax];
+                    for (int t_ = 0; t_ < 4; t_++) aint_[4 * k + t_] = aint_[4 * kcap + t_];
+                    for (int t_ = 0; t_ < 3; t_++) acoef_[3 * k + t_] = acoef_[3 * kcap + t_];
+                    arhs_[k] = arhs_[kcap];
                 }
                 k++;
                 LSCQP_DAS_BARRIER();
@@ -903,9 +913,9 @@
         if (proven) {
             // A proof only if the violation exceeds what the candidate's part outside the active rows' span could still buy: about
             // sqrt(curv / spp) |a_p| per metre travelled, over at most the world box's diameter.  curv = a_p'C a_p - v'r as the last step's
-            // decision had it, again from what LDS holds -- the candidate's descriptors (slot kmax), W and r_ -- by every thread alike.
-            const int* const pe = &aint_[4 * kmax + 1];
-            const double* const pc = &acoef_[3 * kmax];
+            // decision had it, again from what LDS holds -- the candidate's descriptors (slot kcap), W and r_ -- by every thread alike.
+            const int* const pe = &aint_[4 * kcap + 1];
+            const double* const pc = &acoef_[3 * kcap];
             double vr = 0.0;
             for (int j = 0; j < k; j++) vr += r_[j] * row_dot(pe, pc, W_ + (size_t)j * NX);
             const double spp = cdot(pe, pc, pe, pc, Cm, P);

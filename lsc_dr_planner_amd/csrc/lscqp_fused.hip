@@ -10,6 +10,7 @@
 #include "lscqp_kernel.hpp"
 #include "lscqp_launch.hpp"
 // (last: its fp-contraction pragma holds to the end of this file -- lscqp_pdip_one above keeps the instances' own setting)
+#define LSCQP_DAS_CYCLES das_fused_cycles  // (-DLSCQP_DAS_TIMING, tools/das_timing.py: beside lscqp_das.hip's own totals in one library)
 #include "lscqp_das.hpp"
 
 #define LSCQP_FCAT_(a, b, c, d, e, f) a##b##_##c##_##d##_##e##_##f
@@ -17,6 +18,22 @@
 #define LSCQP_FUSED_FN LSCQP_FCAT(lscqp_launch_fused_, LSCQP_M, LSCQP_DIM, LSCQP_ES, LSCQP_NSLOT, LSCQP_W)
 
 namespace lscqp_das {
+
+// The phase's LDS carve of a fused instance, fixed at compile time: the class's shape, the table copy, room for the staged rows of
+// MAX_OBS obstacles, and 32 active rows -- or 20 where 32 would not fit beside those (M = 10 in 3-D, MAX_OBS = 40).  Every LDS offset of
+// the phase is then an immediate.  A launch asks for budgets at or below these capacities; one that asks for more is refused (two
+// launches).  The host gives a batch of at most one instance per CU 32 active rows whenever they fit beside ITS staged rows and the table
+// (lscqp_api.hip): for the M = 10, 3-D instance that is a batch of at most 30 obstacles, which this carve therefore refuses -- such a batch
+// runs the two launches of the parent form (NOTES.md section 16); the configs[3] shard (40 obstacles) gets 20 from the host and is fused.
+constexpr bool carve_fits(int M, int dim, int kmax, int stage_rows) {
+    return sizeof(double) * (size_t)Layout::make(M, dim, kmax, 1, stage_rows).total <= lscqp::kMaxLdsBytes;
+}
+template <int M, int DIM, bool ES, int NSLOT, int W>
+struct FusedCarve {
+    static constexpr int kStage = lscqp::Cfg<M, DIM, ES, NSLOT, W, (int)sizeof(double)>::MAX_OBS * 6 * M;  // LSC rows of a full instance
+    static constexpr int KMAX = carve_fits(M, DIM, kMaxK, kStage) ? kMaxK : 20;
+    static_assert(carve_fits(M, DIM, KMAX, kStage), "the fused phase's carve does not fit the CU's LDS");
+};
 
 // One workgroup of four wavefronts per instance: the phase's small-batch form (das_kernel<4, false, false, false>), then -- for an instance
 // it handed over -- the first W wavefronts run the interior-point instance on it with cls.repair = 3, exactly as the separate launch would.
@@ -36,13 +53,17 @@ __global__ __launch_bounds__(256, 1) void das_pdip_kernel(DevClass cls, int cap,
     {  // the phase: das_kernel<4, false, false, false>'s body (lscqp_das_body.inc) with the class's shape as constants and nothing in front
         constexpr int NW = 4, T = 64 * NW, kU = 4;
         constexpr bool F32 = false, SCREEN = false, PEEL = false;
-        const int dim = DIM, es = ES ? 1 : 0, behind = 0;
+        constexpr int dim = DIM, es = ES ? 1 : 0, behind = 0;
+        using FC = FusedCarve<M, DIM, ES, NSLOT, W>;
+        constexpr int kMaxNL = FC::kStage;  // (an instance beyond the launch's cap <= MAX_OBS is handed over before its rows are read)
 #define LSCQP_DAS_END(verdict_)   \
     do {                          \
         verdict = (verdict_);     \
         goto phase_done;          \
     } while (0)
+#define LSCQP_DAS_LAYOUT Layout::make(M, DIM, FC::KMAX, 1, FC::kStage)
 #include "lscqp_das_body.inc"
+#undef LSCQP_DAS_LAYOUT
 #undef LSCQP_DAS_END
     }
 phase_done:
@@ -65,17 +86,19 @@ phase_done:
 
 // cls: the class of the interior-point pass (repair = 3, no queue, no scan; the phase reads none of those fields).  The phase's launch
 // parameters are those of lscqp_launch_das with threads = 256, the first look inside the loop of steps, fp64 rows, nothing in front.
-// Returns hipErrorNotSupported -- and launches nothing -- when the two LDS footprints do not fit one CU or the instance cannot hold the batch;
-// the caller then launches the two kernels.
+// Returns hipErrorNotSupported -- and launches nothing -- when the budgets exceed the phase's compiled carve (FusedCarve: kmax, stage_rows),
+// the two LDS footprints do not fit one CU or the instance cannot hold the batch; the caller then launches the two kernels.
 extern "C" hipError_t LSCQP_FUSED_FN(const lscqp::DevClass* cls, int cap, int kmax, int max_steps, int cacheC, int stage_rows, const double* d_tab,
                                      int64_t n, const lscqp_header* hdr, const lscqp_row* rows, const uint64_t* row_offsets, const lscqp_box* sfc,
                                      const double* x_init, double* x_out, double* obj_out, int32_t* status_out, lscqp_info* info_out,
                                      hipStream_t stream) {
     using C = lscqp::Cfg<LSCQP_M, LSCQP_DIM, (LSCQP_ES != 0), LSCQP_NSLOT, LSCQP_W, (int)sizeof(double)>;
+    using FC = lscqp_das::FusedCarve<LSCQP_M, LSCQP_DIM, (LSCQP_ES != 0), LSCQP_NSLOT, LSCQP_W>;
     auto kern = lscqp_das::das_pdip_kernel<LSCQP_M, LSCQP_DIM, (LSCQP_ES != 0), LSCQP_NSLOT, LSCQP_W>;
     if (kmax < 1 || kmax > lscqp_das::kMaxK || cls->rows_f32 || cls->queue || cls->scan || cls->repair != 3) return hipErrorInvalidValue;
-    if (cls->n_obs_max > C::MAX_OBS) return hipErrorNotSupported;
-    const size_t lds_das = sizeof(double) * (size_t)lscqp_das::Layout::make(LSCQP_M, LSCQP_DIM, kmax, cacheC, stage_rows).total;
+    if (cls->n_obs_max > C::MAX_OBS || cap > C::MAX_OBS) return hipErrorNotSupported;
+    if (kmax > FC::KMAX || stage_rows > FC::kStage) return hipErrorNotSupported;  // (beyond the compiled carve)
+    const size_t lds_das = sizeof(double) * (size_t)lscqp_das::Layout::make(LSCQP_M, LSCQP_DIM, FC::KMAX, 1, FC::kStage).total;
     const size_t lds = lds_das > C::lds_bytes() ? lds_das : C::lds_bytes();
     if (lds > lscqp::kMaxLdsBytes) return hipErrorNotSupported;
     static std::atomic<bool> attr_set[64];
@@ -91,3 +114,15 @@ extern "C" hipError_t LSCQP_FUSED_FN(const lscqp::DevClass* cls, int cap, int km
                        x_init, x_out, obj_out, status_out, info_out);
     return hipGetLastError();
 }
+
+#ifdef LSCQP_DAS_TIMING
+// the phase's cycle totals of this fused instance (one instance per library: tools/das_timing.py builds the twin of one)
+extern "C" int lscqp_das_fused_cycles(unsigned long long* out, int reset) {
+    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(lscqp_das::das_fused_cycles), sizeof(unsigned long long) * 16);
+    if (reset) {
+        unsigned long long z[16] = {0};
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(lscqp_das::das_fused_cycles), z, sizeof z);
+    }
+    return 0;
+}
+#endif
