@@ -694,6 +694,80 @@ int lscqp_construct_sfc_device_ordered(lscqp_handle h, lscqp_map map, int32_t mo
 int lscqp_construct_sfc(lscqp_map map, int32_t mode, int32_t M, int64_t n, const double* points, const double* radius,
                         lscqp_box* sfc, int32_t* status_out);
 
+/* ---- the grid planner / MAPF layer (last row): each agent's next waypoint, on the device -------------------
+ *
+ * Device analogue of MultiSyncSimulator::decentralizedMAPP (reference src/multi_sync_simulator.cpp:160-303) in the default configuration
+ * mode/goal = grid_based_planner, mode/mapf = pibt: the 0.5 m grid of GridBasedPlanner (src/grid_based_planner.cpp), one distance
+ * table per agent (Solver::createDistanceTable, src/mapf/solver.cpp:270-289), ONE timestep of PIBT (src/mapf/pibt.cpp) per group of
+ * agents in communication range, and the simulator's filter that decides which agents take their new waypoint.  2-D missions only.
+ *   lscqp_grid_shape          GridBasedPlanner::updateGridInfo (:86-100): grid_min snaps the world box to multiples of the resolution
+ *                             (SP_EPSILON = 1e-9), a 2-D mission has one plane at z_2d.  Host arithmetic only, no device call.
+ *   lscqp_grid_create         the grid over the map's world box and updateGridMap (:102-140): a node is occupied when the L-infinity
+ *                             distance to the nearest occupied voxel CELL is below radius - 1e-5, evaluated by a kernel from the map's
+ *                             nearest-cell field with the corridor kernel's query -- a node without a cell within max_dist is measured
+ *                             against a cell at the world origin, like lscqp_construct_sfc_device.  grid/margin is read by the reference
+ *                             and used nowhere.  world_dimension != 2: LSCQP_ERR_UNSUPPORTED (the reference's MAPF graph is x-y only and
+ *                             its 3-D waypoints come out at the floor of the world).
+ *   lscqp_grid_info / _download   grid_min[3], dims[3]; the static occupancy, uint8 [dims[1]][dims[0]].  _download_mission: the occupancy
+ *                             the last lscqp_grid_fields_device left (start and goal nodes cleared), which the waypoint decision reads.
+ *   lscqp_grid_fields_device  updateGridMission (:255-283) + createDistanceTable for n agents: d_field [n][dims[1]][dims[0]] int32, the
+ *                             number of 4-connected steps (left x-1, right x+1, up y-1, down y+1: Grid::Grid) from the node to the
+ *                             agent's goal node, LSCQP_GRID_UNREACHABLE on occupied and unreachable nodes; d_init_d [n] = the field at
+ *                             the agent's START node (PIBT's init_d).  One workgroup per agent relaxes its field in sweeps in LDS
+ *                             (16 bits per node) up to 65 000 nodes, in HBM beyond.  d_start_points, d_goal_points [n][3].
+ *     DIFFERENCE 1: the reference rebuilds every table in every replan and clears the current and goal nodes of the agents of ONE group
+ *     at a time.  Goals and map do not change during a mission and a waypoint is always a free node except possibly the start, so here
+ *     the start and goal nodes of EVERY agent passed in are cleared, once, and the fields are computed once per mission (lscqp_plan:
+ *     per lscqp_plan_reset, and again when the map's generation counter moves).  The two rules differ only where a start or goal node
+ *     lies inside an inflated cell AND the swarm is split into groups.  No replan then pays for n graph searches.
+ *   lscqp_waypoints_device    one replan's decision for all n agents of the mission, asynchronous on `stream`:
+ *       groups     connected components of "L-infinity distance of the current POSITIONS (d_state) < communication_range" (:162-193;
+ *                  range < 0: one group; range == 0: every agent alone, and like range < 0 no range test in the filter; NaN is refused).  d_group_out [n]: the least agent id of the agent's group.
+ *       PIBT       per group, first timestep (the simulator keeps path[1] only, :219-220; every `elapsed` is 0): priority init_d, then
+ *                  tie_breaker = id / n, larger first; funcPIBT with priority inheritance and backtracking, chooseNode with vertex and
+ *                  swap conflicts.  An agent's node is the node of its present WAYPOINT (:205).  Agents of other groups are invisible.
+ *                  DIFFERENCE 2: std::shuffle in chooseNode is replaced by the identity order -- the candidates are visited as left,
+ *                  right, up, down, stay and the first one wins a tie.  That is one of the orders the reference can draw, so every
+ *                  result is one the reference could have produced.  d_desired_out [n]: the node taken, y * dims[0] + x.
+ *       filter     (:222-296) a desired waypoint is taken only if (a) it lies within range / 2 - 1e-5 (L-infinity) of every segment start
+ *                  point and of the last point of the agent's plan (d_plan [n][dim*M*6], the plans as the last replan left them; NULL:
+ *                  of the agent's position -- no trajectory yet), (b) it differs from the present waypoint, (c) the agent's current goal
+ *                  point (d_current_goal [n][3]) has reached the present waypoint, (d) no member of its group that keeps its waypoint
+ *                  holds that node.  d_waypoint [n][3] is updated in place, d_updated_out [n] = 1 where it changed.
+ *                  DIFFERENCE 3: the reference drops repeated leading configurations of the PIBT plan (:355-374) and treats an empty
+ *                  plan as "MAPF failed"; with one timestep neither exists: a replan in which nobody can move leaves every waypoint.
+ *     Precondition (PIBT's own): the agents of one group hold distinct waypoint nodes.  Where two do, the one with the larger id is the
+ *     node's holder, as in PIBT::run.  An agent's own node counts as free for it whatever the map says.
+ *     The decision loop has a hard bound of 4 n + 16 passes (funcPIBT is entered at most once per agent: 3 n suffice); reaching it
+ *     leaves every waypoint as it was and sets the status word lscqp_grid_status reads (0 = fine, 1 = bound reached).  The word is sticky:
+ *     later decisions do not clear it; lscqp_grid_fields_device (hence lscqp_plan_reset) does.  The grid keeps nothing of the map after
+ *     lscqp_grid_create: it may outlive it.
+ *     The launch uses work arrays owned by the grid: one decision at a time per grid.  They grow on demand, which synchronises and
+ *     allocates -- a caller that captures the launch in a graph calls lscqp_grid_reserve(grid, n) first. */
+typedef struct lscqp_grid_s* lscqp_grid;
+typedef struct lscqp_grid_desc {
+    double resolution;       /* grid/resolution, 0.5 m in the launch files */
+    double radius;           /* agent_radius of updateGridMap (the reference passes mission.agents[0].radius) */
+    double z_2d;             /* world_z_2d */
+    int32_t world_dimension; /* 2 */
+    int32_t reserved_;
+} lscqp_grid_desc;
+#define LSCQP_GRID_UNREACHABLE 0x3fffffff /* larger than any path */
+int lscqp_grid_shape(const double* world_min, const double* world_max, double resolution, int32_t world_dimension, double z_2d,
+                     double* grid_min, int32_t* dims);
+int lscqp_grid_create(lscqp_map map, const lscqp_grid_desc* desc, lscqp_grid* out);
+void lscqp_grid_destroy(lscqp_grid grid);
+int lscqp_grid_info(lscqp_grid grid, double* grid_min, int32_t* dims);
+int lscqp_grid_download(lscqp_grid grid, uint8_t* occ);
+int lscqp_grid_download_mission(lscqp_grid grid, uint8_t* occ);
+int lscqp_grid_reserve(lscqp_grid grid, int64_t n);
+int lscqp_grid_status(lscqp_grid grid, int32_t* status_out); /* waits for the device */
+int lscqp_grid_fields_device(lscqp_grid grid, int64_t n, const double* d_start_points, const double* d_goal_points, int32_t* d_field,
+                             int32_t* d_init_d, void* stream);
+int lscqp_waypoints_device(lscqp_grid grid, double communication_range, int32_t M, int32_t dim, int64_t n, const double* d_state,
+                           const double* d_plan, const double* d_current_goal, const int32_t* d_field, const int32_t* d_init_d,
+                           double* d_waypoint, int32_t* d_group_out, int32_t* d_desired_out, int32_t* d_updated_out, void* stream);
+
 /* ---- the caller of the path: one replan of a batch of agents as one chain of device work ----------
  *
  * Device analogue of TrajPlanner::plan / planImpl (reference src/traj_planner.cpp:33-60, 117-139) run for every local agent of
@@ -719,8 +793,11 @@ int lscqp_construct_sfc(lscqp_map map, int32_t mode, int32_t M, int64_t n, const
  *                                                                                     it in DLSC mode only, :763-766)
  * on ONE stream, with no host synchronisation, allocation or copy in between.  lscqp_plan_step_graph captures that chain once in
  * a hipGraph and replays it: one graph launch per replan instead of ten kernel launches.
- * Host work that remains is what the survey leaves out of scope: the grid planner / MAPF layer writes each local agent's next
- * waypoint into LSCQP_PLAN_BUF_WAYPOINT before the step (and, unless closed_loop is set, the simulator writes the agents' states).
+ * Where the waypoints come from is the plan's waypoint_mode: LSCQP_WAYPOINT_FROM_CALLER -- the caller's grid planner / MAPF layer writes each
+ * local agent's next waypoint into LSCQP_PLAN_BUF_WAYPOINT before the step -- or LSCQP_WAYPOINT_GRID_PIBT: the chain starts with
+ * lscqp_waypoints_device (decentralizedMAPP precedes the planning loop in the simulator too) and a mission flies from start points and
+ * goal points alone: lscqp_plan_reset, then lscqp_plan_step_graph in a loop, with no host work between replans.  (Unless closed_loop is
+ * set, the simulator writes the agents' states.)
  * Dynamic (non-agent) obstacles are not part of the chain (lscqp_generate_lsc_obstacles_device is available separately).
  * Sharding (section 8e): rank r owns the agents [first_agent, first_agent + n_agents) of n_total; its plan needs every agent's
  * previous plan, state and goal point, so the owners' slices of LSCQP_PLAN_BUF_PLAN / _STATE / _GOAL are all-gathered between
@@ -757,7 +834,11 @@ typedef struct lscqp_plan_desc {
                                  they stay where they are) or _FROM_VELOCITY (circle_test: Trajectory::planConstVelTraj from the
                                  current state) */
     int32_t initial_traj_mode; /* the planning agent's own initial trajectory (initialTrajPlanning, :360-423): same three values */
-    int32_t reserved_;
+    int32_t waypoint_mode;     /* LSCQP_WAYPOINT_FROM_CALLER (0): LSCQP_PLAN_BUF_WAYPOINT is the caller's to write.  LSCQP_WAYPOINT_GRID_PIBT (1):
+                                  the plan owns a lscqp_grid over its map (resolution 0.5 m, lscqp_plan_set_grid changes it; radius of agent 0,
+                                  as the reference passes it) and every replan starts with lscqp_waypoints_device over the plans, states and
+                                  goal points the last replan left.  Needs a map, a 2-D class and every agent's waypoint and plan on this
+                                  device: n_agents == n_total (LSCQP_ERR_INVALID_ARGUMENT otherwise, the rule of safety_samples) */
     double reset_threshold;   /* checkObstacleDisturbance (:312-319, plan/reset_threshold, 0.1 in the launch files): an agent whose predicted
                                  trajectory starts further than this from its current position is predicted to stay where it is
                                  (a disturbed or externally moved robot; only with closed_loop == 0 can that happen).  <= 0: no check */
@@ -765,6 +846,8 @@ typedef struct lscqp_plan_desc {
 #define LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION 0
 #define LSCQP_TRAJ_FROM_POSITION 1
 #define LSCQP_TRAJ_FROM_VELOCITY 2
+#define LSCQP_WAYPOINT_FROM_CALLER 0
+#define LSCQP_WAYPOINT_GRID_PIBT 1
 /* Buffers of a plan (device pointers through lscqp_plan_buffer; lscqp_plan_upload / _download copy synchronously).
  * "all": [n_total] entries indexed by global id; "local": [n_agents] entries. */
 #define LSCQP_PLAN_BUF_STATE 0        /* in   all    double[9]: position, velocity, acceleration (float32 values, as State holds them) */
@@ -784,7 +867,11 @@ typedef struct lscqp_plan_desc {
 #define LSCQP_PLAN_BUF_OBJECTIVE 13   /* out  local  double */
 #define LSCQP_PLAN_BUF_INFO 14        /* out  local  lscqp_info */
 #define LSCQP_PLAN_BUF_SAFETY 15      /* out  local  lscqp_safety (safety_samples > 0) */
-#define LSCQP_PLAN_BUF_COUNT 16
+/* waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT only (no such buffer otherwise: lscqp_plan_buffer returns NULL and 0 bytes) */
+#define LSCQP_PLAN_BUF_DESIRED_GOAL 16     /* in   all    double[3]: the mission's goal points (Agent::desired_goal_point), set by lscqp_plan_reset */
+#define LSCQP_PLAN_BUF_WAYPOINT_UPDATED 17 /* out  local  int32: 1 = the last replan moved the agent's waypoint */
+#define LSCQP_PLAN_BUF_GROUP 18            /* out  local  int32: least agent id of the agent's communication group in the last replan */
+#define LSCQP_PLAN_BUF_COUNT 19
 /* agents [n_total] (host).  map: required exactly when the class uses corridors.  The class's row_format must be LSCQP_ROWS_F64. */
 int lscqp_plan_create(lscqp_handle h, lscqp_map map, const lscqp_plan_desc* desc, const lscqp_agent_param* agents, lscqp_plan* out);
 void lscqp_plan_destroy(lscqp_plan plan);
@@ -792,6 +879,12 @@ void lscqp_plan_destroy(lscqp_plan plan);
  * planners start from, planner_seq < 2), goal points := goal_points, or the start positions if NULL (AgentManager's constructor),
  * waypoints := the goal points; the next step is a FIRST replan (initializeSFC). */
 int lscqp_plan_reset(lscqp_plan plan, const double* start_positions, const double* goal_points);
+/* waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: goal_points are the mission's DESIRED goal points (required); the current goal points and the
+ * waypoints := the start positions (AgentManager's constructor, src/agent_manager.cpp:8-10) and the distance fields of the mission are
+ * computed (lscqp_grid_fields_device).  lscqp_plan_set_grid replaces the plan's grid by one of another resolution; call it before
+ * lscqp_plan_reset.  lscqp_plan_grid: the plan's grid (NULL in mode 0), for lscqp_grid_info / _download / _status. */
+int lscqp_plan_set_grid(lscqp_plan plan, double resolution);
+lscqp_grid lscqp_plan_grid(lscqp_plan plan);
 void* lscqp_plan_buffer(lscqp_plan plan, int32_t which, uint64_t* bytes_out);
 int lscqp_plan_upload(lscqp_plan plan, int32_t which, const void* host, uint64_t offset, uint64_t bytes);
 int lscqp_plan_download(lscqp_plan plan, int32_t which, void* host, uint64_t offset, uint64_t bytes);

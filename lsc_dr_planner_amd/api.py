@@ -227,6 +227,28 @@ def lib():
         L.lscqp_plan_graph_nodes.argtypes = [vp]
         L.lscqp_plan_group_step.restype = C.c_int
         L.lscqp_plan_group_step.argtypes = [vp, vp, C.c_int32]
+        L.lscqp_plan_set_grid.restype = C.c_int
+        L.lscqp_plan_set_grid.argtypes = [vp, C.c_double]
+        L.lscqp_plan_grid.restype = C.c_void_p
+        L.lscqp_plan_grid.argtypes = [vp]
+        L.lscqp_grid_shape.restype = C.c_int
+        L.lscqp_grid_shape.argtypes = [vp, vp, C.c_double, C.c_int32, C.c_double, vp, vp]
+        L.lscqp_grid_create.restype = C.c_int
+        L.lscqp_grid_create.argtypes = [vp, vp, C.POINTER(C.c_void_p)]
+        L.lscqp_grid_destroy.restype = None
+        L.lscqp_grid_destroy.argtypes = [vp]
+        for name in ("lscqp_grid_info", "lscqp_grid_download", "lscqp_grid_download_mission", "lscqp_grid_status"):
+            getattr(L, name).restype = C.c_int
+        L.lscqp_grid_info.argtypes = [vp, vp, vp]
+        L.lscqp_grid_download.argtypes = [vp, vp]
+        L.lscqp_grid_download_mission.argtypes = [vp, vp]
+        L.lscqp_grid_status.argtypes = [vp, vp]
+        L.lscqp_grid_reserve.restype = C.c_int
+        L.lscqp_grid_reserve.argtypes = [vp, C.c_int64]
+        L.lscqp_grid_fields_device.restype = C.c_int
+        L.lscqp_grid_fields_device.argtypes = [vp, C.c_int64] + [vp] * 5
+        L.lscqp_waypoints_device.restype = C.c_int
+        L.lscqp_waypoints_device.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_int64] + [vp] * 10
         L.lscqp_last_error.restype = C.c_char_p
         L.lscqp_version.restype = C.c_char_p
         L.lscqp_instance_work.restype = C.c_int
@@ -253,7 +275,9 @@ EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_
                     "lscqp_generate_lsc_obstacles_device", "lscqp_generate_lsc_bytes", "lscqp_optimize_goal_device", "lscqp_optimize_goal", "lscqp_validate_step_device", "lscqp_map_create", "lscqp_map_create_from_csv", "lscqp_map_destroy", "lscqp_map_info",
                     "lscqp_map_download", "lscqp_map_prepare", "lscqp_construct_sfc_device", "lscqp_construct_sfc", "lscqp_safety_metrics_device", "lscqp_safety_obstacles_device",
                     "lscqp_plan_create", "lscqp_plan_destroy", "lscqp_plan_reset", "lscqp_plan_buffer", "lscqp_plan_upload", "lscqp_plan_download",
-                    "lscqp_plan_step", "lscqp_plan_step_graph", "lscqp_plan_graph_nodes", "lscqp_plan_group_step",
+                    "lscqp_plan_step", "lscqp_plan_step_graph", "lscqp_plan_graph_nodes", "lscqp_plan_group_step", "lscqp_plan_set_grid", "lscqp_plan_grid",
+                    "lscqp_grid_shape", "lscqp_grid_create", "lscqp_grid_destroy", "lscqp_grid_info", "lscqp_grid_download", "lscqp_grid_download_mission",
+                    "lscqp_grid_reserve", "lscqp_grid_status", "lscqp_grid_fields_device", "lscqp_waypoints_device",
                     "lscqp_instance_work", "lscqp_diagnose", "lscqp_diagnose_device", "lscqp_dump_instance", "lscqp_row_family_name",
                     "lscqp_last_error", "lscqp_version"]
 
@@ -335,6 +359,106 @@ class WorldMap:
             pass
 
 
+GRID_UNREACHABLE = 0x3FFFFFFF  # LSCQP_GRID_UNREACHABLE
+
+
+class GridDesc(C.Structure):  # lscqp_grid_desc
+    _fields_ = [("resolution", C.c_double), ("radius", C.c_double), ("z_2d", C.c_double), ("world_dimension", C.c_int32), ("reserved_", C.c_int32)]
+
+
+def grid_shape(world_min, world_max, resolution=0.5, world_dimension=2, z_2d=1.0):
+    """lscqp_grid_shape (GridBasedPlanner::updateGridInfo): (grid_min float64[3], dims int32[3]).  No device call."""
+    wmin, wmax = np.ascontiguousarray(world_min, dtype=np.float64), np.ascontiguousarray(world_max, dtype=np.float64)
+    gmin, dims = np.zeros(3, np.float64), np.zeros(3, np.int32)
+    rc = lib().lscqp_grid_shape(wmin.ctypes.data_as(C.c_void_p), wmax.ctypes.data_as(C.c_void_p), float(resolution), int(world_dimension), float(z_2d),
+                                gmin.ctypes.data_as(C.c_void_p), dims.ctypes.data_as(C.c_void_p))
+    if rc != OK:
+        raise LscqpError(rc, lib().lscqp_last_error().decode())
+    return gmin, dims
+
+
+def _dptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class Grid:
+    """lscqp_grid: the grid planner's grid over a WorldMap (include/lscqp.h, "the grid planner / MAPF layer"): occupancy, per-agent
+    distance fields, and one replan's PIBT waypoint decision.  2-D.  `handle`: a grid owned by a Plan (not destroyed here)."""
+
+    def __init__(self, world_map, resolution=0.5, radius=0.15, z_2d=1.0, world_dimension=2, handle=None):
+        self._own = handle is None
+        self._map = world_map
+        if handle is None:
+            d = GridDesc(float(resolution), float(radius), float(z_2d), int(world_dimension), 0)
+            h = C.c_void_p()
+            rc = lib().lscqp_grid_create(world_map._h, C.byref(d), C.byref(h))
+            if rc != OK:
+                raise LscqpError(rc, lib().lscqp_last_error().decode())
+            handle = h
+        self._h = handle
+        self.grid_min, self.dims = np.zeros(3, np.float64), np.zeros(3, np.int32)
+        lib().lscqp_grid_info(self._h, self.grid_min.ctypes.data_as(C.c_void_p), self.dims.ctypes.data_as(C.c_void_p))
+        self.resolution = float(resolution)
+
+    def _check(self, rc):
+        if rc != OK:
+            raise LscqpError(rc, lib().lscqp_last_error().decode())
+
+    def close(self):
+        if self._h and self._own:
+            lib().lscqp_grid_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def download(self, mission=False):
+        """Occupancy, uint8 (dims[1], dims[0]); mission=True: with the start and goal nodes of the last `fields` call cleared."""
+        occ = np.zeros((int(self.dims[1]), int(self.dims[0])), np.uint8)
+        self._check((lib().lscqp_grid_download_mission if mission else lib().lscqp_grid_download)(self._h, occ.ctypes.data_as(C.c_void_p)))
+        return occ
+
+    def status(self):
+        st = np.zeros(1, np.int32)
+        self._check(lib().lscqp_grid_status(self._h, st.ctypes.data_as(C.c_void_p)))
+        return int(st[0])
+
+    def reserve(self, n):
+        self._check(lib().lscqp_grid_reserve(self._h, int(n)))
+
+    def fields(self, d_start_points, d_goal_points, d_field=None, d_init_d=None, stream=None):
+        """lscqp_grid_fields_device: (d_field int32 (n, dims[1], dims[0]), d_init_d int32 (n,)), torch tensors on the device."""
+        import torch
+
+        n = d_start_points.numel() // 3
+        if d_field is None:
+            d_field = torch.empty((n, int(self.dims[1]), int(self.dims[0])), dtype=torch.int32, device=d_start_points.device)
+        if d_init_d is None:
+            d_init_d = torch.empty(n, dtype=torch.int32, device=d_start_points.device)
+        s = stream if stream is not None else torch.cuda.current_stream()
+        self._check(lib().lscqp_grid_fields_device(self._h, n, _dptr(d_start_points), _dptr(d_goal_points), _dptr(d_field), _dptr(d_init_d), C.c_void_p(s.cuda_stream)))
+        return d_field, d_init_d
+
+    def waypoints(self, communication_range, M, dim, d_state, d_plan, d_current_goal, d_field, d_init_d, d_waypoint, stream=None):
+        """lscqp_waypoints_device: d_waypoint (float64 (n, 3)) is updated in place; returns (group, desired node, updated), int32 (n,) tensors."""
+        import torch
+
+        n = d_waypoint.numel() // 3
+        out = [torch.empty(n, dtype=torch.int32, device=d_waypoint.device) for _ in range(3)]
+        s = stream if stream is not None else torch.cuda.current_stream()
+        self._check(lib().lscqp_waypoints_device(self._h, float(communication_range), int(M), int(dim), n, _dptr(d_state), _dptr(d_plan), _dptr(d_current_goal),
+                                                 _dptr(d_field), _dptr(d_init_d), _dptr(d_waypoint), _dptr(out[0]), _dptr(out[1]), _dptr(out[2]), C.c_void_p(s.cuda_stream)))
+        return tuple(out)
+
+
+def waypoints(grid, communication_range, M, dim, d_state, d_plan, d_current_goal, d_field, d_init_d, d_waypoint, stream=None):
+    """lscqp_waypoints_device (see Grid.waypoints)."""
+    return grid.waypoints(communication_range, M, dim, d_state, d_plan, d_current_goal, d_field, d_init_d, d_waypoint, stream=stream)
+
+
 AGENT_PARAM_DTYPE = np.dtype([("radius", "f8"), ("downwash", "f8"), ("max_vel", "f8", 3), ("max_acc", "f8", 3), ("nominal_velocity", "f8")])
 
 
@@ -342,14 +466,15 @@ class PlanDesc(C.Structure):  # lscqp_plan_desc
     _fields_ = [("n_agents", C.c_int64), ("n_total", C.c_int64), ("first_agent", C.c_int64), ("n_obs", C.c_int32), ("constraint_mode", C.c_int32),
                 ("sfc_mode", C.c_int32), ("optimize_goal", C.c_int32), ("closed_loop", C.c_int32), ("safety_samples", C.c_int32),
                 ("time_step", C.c_double), ("z_2d", C.c_double), ("record_time_step", C.c_double), ("tight_warm_start", C.c_int32),
-                ("prediction_mode", C.c_int32), ("initial_traj_mode", C.c_int32), ("reserved_", C.c_int32), ("reset_threshold", C.c_double)]
+                ("prediction_mode", C.c_int32), ("initial_traj_mode", C.c_int32), ("waypoint_mode", C.c_int32), ("reset_threshold", C.c_double)]
 
 
 TRAJ_FROM_PREVIOUS_SOLUTION, TRAJ_FROM_POSITION, TRAJ_FROM_VELOCITY = 0, 1, 2
+WAYPOINT_FROM_CALLER, WAYPOINT_GRID_PIBT = 0, 1
 
 
 (PLAN_STATE, PLAN_WAYPOINT, PLAN_PLAN, PLAN_GOAL, PLAN_HEADER, PLAN_ROWS, PLAN_SFC, PLAN_STATUS, PLAN_GOAL_STATUS, PLAN_SFC_STATUS, PLAN_VALID,
- PLAN_IN_RANGE, PLAN_NEXT_STATE, PLAN_OBJECTIVE, PLAN_INFO, PLAN_SAFETY) = range(16)
+ PLAN_IN_RANGE, PLAN_NEXT_STATE, PLAN_OBJECTIVE, PLAN_INFO, PLAN_SAFETY, PLAN_DESIRED_GOAL, PLAN_WAYPOINT_UPDATED, PLAN_GROUP) = range(19)
 
 
 class Plan:
@@ -359,11 +484,12 @@ class Plan:
 
     _DT = {PLAN_STATE: np.float64, PLAN_WAYPOINT: np.float64, PLAN_PLAN: np.float64, PLAN_GOAL: np.float64, PLAN_STATUS: np.int32,
            PLAN_GOAL_STATUS: np.int32, PLAN_SFC_STATUS: np.int32, PLAN_VALID: np.int32, PLAN_IN_RANGE: np.int32, PLAN_NEXT_STATE: np.float64,
-           PLAN_OBJECTIVE: np.float64}
+           PLAN_OBJECTIVE: np.float64, PLAN_DESIRED_GOAL: np.float64, PLAN_WAYPOINT_UPDATED: np.int32, PLAN_GROUP: np.int32}
 
     def __init__(self, solver, world_map, n_agents, n_obs, agents, n_total=None, first_agent=0, constraint_mode=1, sfc_mode=1,
                  optimize_goal=True, closed_loop=False, time_step=None, z_2d=1.0, safety_samples=0, record_time_step=0.1, tight_warm_start=False,
-                 prediction_mode=TRAJ_FROM_PREVIOUS_SOLUTION, initial_traj_mode=TRAJ_FROM_PREVIOUS_SOLUTION, reset_threshold=0.1):
+                 prediction_mode=TRAJ_FROM_PREVIOUS_SOLUTION, initial_traj_mode=TRAJ_FROM_PREVIOUS_SOLUTION, reset_threshold=0.1,
+                 waypoint_mode=WAYPOINT_FROM_CALLER, grid_resolution=0.5):
         self._p = None
         n_total = n_agents if n_total is None else n_total
         d = PlanDesc()
@@ -374,6 +500,7 @@ class Plan:
         d.safety_samples, d.record_time_step = int(safety_samples), float(record_time_step)
         d.tight_warm_start = int(tight_warm_start)
         d.prediction_mode, d.initial_traj_mode, d.reset_threshold = int(prediction_mode), int(initial_traj_mode), float(reset_threshold)
+        d.waypoint_mode = int(waypoint_mode)
         ag = np.ascontiguousarray(agents, dtype=AGENT_PARAM_DTYPE)
         if ag.shape != (n_total,):
             raise ValueError("agents: one AGENT_PARAM_DTYPE record per agent of the mission")
@@ -385,6 +512,14 @@ class Plan:
         self.n_agents, self.n_total, self.first_agent, self.n_obs, self.M, self.nv = n_agents, n_total, first_agent, n_obs, solver.desc.M, solver.nv
         self._dt = dict(self._DT)
         self._dt.update({PLAN_HEADER: HEADER_DTYPE, PLAN_ROWS: ROW_DTYPE, PLAN_SFC: BOX_DTYPE, PLAN_INFO: INFO_DTYPE, PLAN_SAFETY: SAFETY_DTYPE})
+        self.waypoint_mode, self.grid_resolution = int(waypoint_mode), float(grid_resolution)
+        if self.waypoint_mode == WAYPOINT_GRID_PIBT and float(grid_resolution) != 0.5:
+            self._check(lib().lscqp_plan_set_grid(self._p, float(grid_resolution)))
+
+    def grid(self):
+        """The plan's own Grid (waypoint_mode = WAYPOINT_GRID_PIBT), for inspection; owned by the plan."""
+        h = lib().lscqp_plan_grid(self._p)
+        return None if not h else Grid(self._map, resolution=self.grid_resolution, handle=C.c_void_p(h))
 
     def close(self):
         if self._p:

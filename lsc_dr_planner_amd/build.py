@@ -114,6 +114,11 @@ def build(force=False, verbose=False, jobs=None):
     plan_src = os.path.join(CSRC, "lscplan.hip")
     if force or _newer(plan_o, hdrs + [plan_src]):
         tasks.append([HIPCC] + FLAGS + ["-c", plan_src, "-o", plan_o])
+    grid_o = os.path.join(OBJ, "lscgrid.o")
+    objs.append(grid_o)
+    grid_src = os.path.join(CSRC, "lscgrid.hip")
+    if force or _newer(grid_o, hdrs + [grid_src]):
+        tasks.append([HIPCC] + FLAGS + ["-c", grid_src, "-o", grid_o])
     gen_o = os.path.join(OBJ, "lscgen.o")
     objs.append(gen_o)
     gen_src = os.path.join(CSRC, "lscgen.hip")

@@ -1,0 +1,665 @@
+// lscgrid.hip — the grid planner / MAPF layer of the reference on the device, gfx950 only: where each agent's NEXT WAYPOINT comes from.
+//   GridBasedPlanner::updateGridInfo / updateGridMap / updateGridMission   reference src/grid_based_planner.cpp:86-140, 255-283
+//   Grid::Grid (x-y, 4-connected: left, right, up, down)                    third_party/grid-pathfinding/graph/src/graph.cpp:371-400
+//   Solver::createDistanceTable                                             src/mapf/solver.cpp:270-289
+//   PIBT::run / funcPIBT / planOneStep / chooseNode, FIRST timestep only    src/mapf/pibt.cpp
+//   MultiSyncSimulator::decentralizedMAPP (groups, update filter)           src/multi_sync_simulator.cpp:160-303
+// Three pieces:
+//   occupancy   one lane per grid node, from the voxel map's nearest-occupied-cell field (the corridor kernel's own query, quirk included)
+//   fields      one workgroup per agent: the distance-to-goal field of the agent relaxed in sweeps -- d = min(d, min over the 4 neighbours + 1)
+//               until a sweep changes nothing (a workgroup-wide vote) -- in LDS where the field fits, in its place in HBM otherwise
+//   waypoints   one replan's decision: candidates gathered by all lanes, then ONE workgroup: groups by min-label propagation, agents ordered by
+//               priority, the PIBT walk (sequential by nature: priority inheritance and backtracking) by one wavefront with an explicit
+//               stack, and the simulator's update filter by all lanes again
+// Everything here is integers and exact grid points, and the float32 / double arithmetic of the reference where a comparison is made.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/lscqp.h"
+
+extern "C" int lscqp_set_error_(int code, const char* msg);
+extern "C" int lscqp_map_raw_(lscqp_map mp, double* res, float* world_min, float* world_max, int* key0, int* dims, const int32_t** d_nearest, int* device);
+
+namespace lscgrid {
+
+constexpr int kUnreach = LSCQP_GRID_UNREACHABLE;
+constexpr int kBlocked = kUnreach + 1;    // an occupied node while a field is relaxed in HBM (written out as kUnreach)
+constexpr unsigned kUnreach16 = 0xFFFEu;  // the same pair where the field is relaxed in LDS (16 bits per node)
+constexpr unsigned kBlocked16 = 0xFFFFu;
+constexpr int kLdsNodes = 65000;          // padded nodes a 16-bit LDS field holds: paths stay below kUnreach16, 130 KB of the CU's 160 KB
+constexpr double kEpsFloat = 1e-5;        // SP_EPSILON_FLOAT
+constexpr int kDecideThreads = 1024;
+constexpr int kTableLdsBytes = 60 * 1024;  // occupied_now / occupied_next live in LDS up to this size, in HBM beyond
+
+struct View {  // the grid as the kernels see it
+    double gmin0, gmin1, res, z_2d;
+    int W, H;
+};
+
+struct MapRaw {
+    double res;
+    int key00, key01, key02, dims0, dims1, dims2;
+    const int32_t* nearest;
+};
+
+// gridNodeToPoint3D (:386-399): grid_min + index * resolution in double, held as point3d (float32)
+__device__ __forceinline__ float node_coord(double gmin, int i, double res) {
+#pragma clang fp contract(off)
+    return (float)(gmin + (double)i * res);
+}
+
+// point3DToGridVector (:429-441): round((point - grid_min) / resolution), clamped into the grid
+__device__ __forceinline__ int coord_node(float p, double gmin, double res, int dim) {
+#pragma clang fp contract(off)
+    int v = (int)round(((double)p - gmin) / res);
+    return v < 0 ? 0 : (v > dim - 1 ? dim - 1 : v);
+}
+
+__device__ __forceinline__ int point_node(const View& g, const double* p) {
+    return coord_node((float)p[1], g.gmin1, g.res, g.H) * g.W + coord_node((float)p[0], g.gmin0, g.res, g.W);
+}
+
+// updateGridMap (:102-140): a node is occupied when the L-infinity distance from it to the nearest occupied voxel CELL is below
+// agent_radius - SP_EPSILON_FLOAT.  The query is the corridor kernel's (lscsfc.hip obstacle_in): no cell within max_dist, or a node outside the
+// distance map, leaves the reference's closest_point default-constructed -- a cell at the world origin.
+__global__ __launch_bounds__(256) void occupancy_kernel(View g, MapRaw m, double radius, uint8_t* __restrict__ occ) {
+#pragma clang fp contract(off)
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    if (id >= g.W * g.H) return;
+    const int j = id / g.W, i = id - j * g.W;
+    const float p[3] = {node_coord(g.gmin0, i, g.res), node_coord(g.gmin1, j, g.res), (float)g.z_2d};
+    const int key0[3] = {m.key00, m.key01, m.key02}, dims[3] = {m.dims0, m.dims1, m.dims2};
+    int v[3];
+    bool inside = true;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        v[k] = (int)floor((1.0 / m.res) * (double)p[k]) - key0[k];
+        inside = inside && v[k] >= 0 && v[k] < dims[k];
+    }
+    const int code = inside ? m.nearest[((int64_t)v[2] * dims[1] + v[1]) * dims[0] + v[0]] : 0;
+    const bool have = (code >> 24) != 0;
+    const int off[3] = {(code & 255) - 128, ((code >> 8) & 255) - 128, ((code >> 16) & 255) - 128};
+    const float delta = (float)(0.5 * m.res);
+    double dist = 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float c = have ? (float)(((double)(v[k] + off[k] + key0[k]) + 0.5) * m.res) : 0.0f;
+        const float cmin = c - delta, cmax = c + delta;
+        const float q = p[k] < cmin ? cmin : (p[k] > cmax ? cmax : p[k]);
+        const double dk = fabs((double)(q - p[k]));
+        dist = dist < dk ? dk : dist;
+    }
+    occ[id] = dist < radius - kEpsFloat ? 1 : 0;
+}
+
+// updateGridMission (:255-283), once per mission instead of once per group and replan (include/lscqp.h): start and goal nodes are free
+__global__ __launch_bounds__(256) void clear_nodes_kernel(View g, int64_t n, const double* __restrict__ start, const double* __restrict__ goal,
+                                                          uint8_t* occ) {
+    const int64_t a = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (a >= n) return;
+    occ[point_node(g, start + a * 3)] = 0;
+    occ[point_node(g, goal + a * 3)] = 0;
+}
+
+// createDistanceTable as a relaxation.  One workgroup per agent.  LDS form: the field carries a border of blocked nodes, so a node's four
+// neighbours are at -1, +1, -pitch, +pitch with no bounds to test; HBM form: the same sweeps over the agent's slice of `field` itself.
+// Lanes read their neighbours while other lanes lower them: every value ever stored is the length of SOME path to the goal, values only
+// fall, and a sweep in which nothing changed saw constant values -- the fixed point, which is the BFS distance.
+template <bool LDS>
+__global__ __launch_bounds__(1024) void fields_kernel(View g, const uint8_t* __restrict__ occ, const double* __restrict__ start,
+                                                      const double* __restrict__ goal, int32_t* field, int32_t* __restrict__ init_d) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int64_t a = blockIdx.x;
+    const int T = blockDim.x, tid = threadIdx.x, W = g.W, H = g.H, nodes = W * H;
+    const int gnode = point_node(g, goal + a * 3), snode = point_node(g, start + a * 3);
+    int32_t* out = field + a * (int64_t)nodes;
+    if (LDS) {
+        uint16_t* f = (uint16_t*)smem;
+        const int P = W + 2, padded = P * (H + 2);
+        for (int id = tid; id < padded; id += T) f[id] = (uint16_t)kBlocked16;
+        __syncthreads();
+        for (int id = tid; id < nodes; id += T) {
+            const int y = id / W, x = id - y * W;
+            f[(y + 1) * P + x + 1] = (uint16_t)(id == gnode ? 0u : (occ[id] ? kBlocked16 : kUnreach16));
+        }
+        __syncthreads();
+        for (int sweep = 0; sweep <= nodes; sweep++) {  // (a path has fewer than `nodes` edges: the vote ends the loop long before)
+            int changed = 0;
+            for (int id = P + 1 + tid; id < padded - P - 1; id += T) {
+                const unsigned d = f[id];
+                if (d == kBlocked16 || d == 0u) continue;
+                const unsigned l = f[id - 1], r = f[id + 1], u = f[id - P], dn = f[id + P];
+                const unsigned m = min(min(l, r), min(u, dn)) + 1u;
+                if (m < d) {
+                    f[id] = (uint16_t)m;
+                    changed = 1;
+                }
+            }
+            if (!__syncthreads_or(changed)) break;
+        }
+        for (int id = tid; id < nodes; id += T) {
+            const int y = id / W, x = id - y * W;
+            const unsigned d = f[(y + 1) * P + x + 1];
+            out[id] = d >= kUnreach16 ? kUnreach : (int)d;
+        }
+        if (tid == 0) {
+            const int y = snode / W, x = snode - y * W;
+            const unsigned d = f[(y + 1) * P + x + 1];
+            init_d[a] = d >= kUnreach16 ? kUnreach : (int)d;
+        }
+    } else {
+        for (int id = tid; id < nodes; id += T) out[id] = id == gnode ? 0 : (occ[id] ? kBlocked : kUnreach);
+        __syncthreads();
+        for (int sweep = 0; sweep <= nodes; sweep++) {
+            int changed = 0;
+            for (int id = tid; id < nodes; id += T) {
+                const int d = out[id];
+                if (d == kBlocked || d == 0) continue;
+                const int y = id / W, x = id - y * W;
+                int m = kBlocked;
+                if (x > 0) m = min(m, out[id - 1]);
+                if (x + 1 < W) m = min(m, out[id + 1]);
+                if (y > 0) m = min(m, out[id - W]);
+                if (y + 1 < H) m = min(m, out[id + W]);
+                if (m + 1 < d) {
+                    out[id] = m + 1;
+                    changed = 1;
+                }
+            }
+            if (!__syncthreads_or(changed)) break;
+        }
+        for (int id = tid; id < nodes; id += T)
+            if (out[id] == kBlocked) out[id] = kUnreach;
+        __syncthreads();
+        if (tid == 0) init_d[a] = out[snode];
+    }
+}
+
+// ---- one replan's waypoint decision --------------------------------------------------------------------------------------------------------
+struct Scratch {  // per-agent work arrays of a decision (lscqp_grid_reserve) and the two node tables of the HBM form
+    int32_t *cur, *cand, *cost, *vnext, *order, *stack, *label, *blocker, *keep, *onnode, *gsize;
+    int32_t *now, *next;  // [nodes] each, all zero between launches
+    int32_t* status;
+};
+
+// Words the ONE workgroup of the decision kernel changes while other lanes read them: relaxed atomics at workgroup scope -- plain loads and
+// stores to the hardware (a workgroup's wavefronts share their CU's L1), but never kept in a register by the compiler
+__device__ __forceinline__ int ldv(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void stv(int32_t* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+// every lane: an agent's PIBT node (the node of its present WAYPOINT, multi_sync_simulator.cpp:205), its five candidates in the identity
+// order left, right, up, down, stay with their distances to the agent's goal, and the start of the group labels
+__global__ __launch_bounds__(256) void gather_kernel(View g, int64_t n, double range, const uint8_t* __restrict__ occ,
+                                                     const double* __restrict__ waypoint, const int32_t* __restrict__ field, Scratch s) {
+#pragma clang fp contract(off)
+    const int64_t a = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (a >= n) return;
+    const int W = g.W, H = g.H;
+    const float wx = (float)waypoint[a * 3 + 0], wy = (float)waypoint[a * 3 + 1], wz = (float)waypoint[a * 3 + 2];
+    const int cx = coord_node(wx, g.gmin0, g.res, W), cy = coord_node(wy, g.gmin1, g.res, H);
+    const int cur = cy * W + cx;
+    const float dx = wx - node_coord(g.gmin0, cx, g.res), dy = wy - node_coord(g.gmin1, cy, g.res), dz = wz - (float)g.z_2d;
+    s.onnode[a] = sqrt((double)(dx * dx + dy * dy + dz * dz)) < kEpsFloat ? 1 : 0;  // (the waypoint IS its node's point, to Vector3::distance)
+    s.cur[a] = cur;
+    const int32_t* f = field + a * (int64_t)W * H;
+    const int ox[5] = {-1, 1, 0, 0, 0}, oy[5] = {0, 0, -1, 1, 0};
+#pragma unroll
+    for (int c = 0; c < 5; c++) {
+        const int x = cx + ox[c], y = cy + oy[c];
+        int u = -1;
+        if (x >= 0 && x < W && y >= 0 && y < H) {
+            u = y * W + x;
+            if (c < 4 && occ[u]) u = -1;  // (the agent's own node is a node of its graph whatever the map says)
+        }
+        s.cand[a * 5 + c] = u;
+        s.cost[a * 5 + c] = u >= 0 ? f[u] : kUnreach;
+    }
+    s.vnext[a] = -1;
+    s.blocker[a] = -1;
+    s.gsize[a] = 0;
+    s.label[a] = range < 0 ? 0 : (int)a;
+}
+
+// PIBT::chooseNode for an agent nobody else can see (a group of one): the goal if it is a candidate, else the first candidate of the least
+// distance (the stay node is the only one occupied now and the last one visited, so the occupied-now tie rule never fires)
+__device__ __forceinline__ int choose_alone(const Scratch& s, int64_t a) {
+    int v = -1, cv = 0;
+    for (int c = 0; c < 5; c++) {
+        const int u = s.cand[a * 5 + c], cu = s.cost[a * 5 + c];
+        if (u < 0) continue;
+        if (cu == 0) return u;
+        if (v < 0 || cu < cv) v = u, cv = cu;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(kDecideThreads) void decide_kernel(View g, int64_t n64, double range, int M, int dim, int tables_in_lds,
+                                                                const double* __restrict__ state, const double* __restrict__ plan,
+                                                                const double* __restrict__ cur_goal, const int32_t* __restrict__ init_d,
+                                                                double* waypoint, Scratch s, int32_t* __restrict__ group_out,
+                                                                int32_t* __restrict__ desired_out, int32_t* __restrict__ updated_out) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ int n_multi_sh, fail_sh;
+    const int n = (int)n64, tid = threadIdx.x, T = kDecideThreads, nodes = g.W * g.H;
+    int32_t *now = s.now, *next = s.next;
+    if (tables_in_lds) {
+        now = (int32_t*)smem;
+        next = now + nodes;
+        for (int id = tid; id < 2 * nodes; id += T) now[id] = 0;
+    }
+    if (tid == 0) n_multi_sh = 0, fail_sh = 0;
+    __syncthreads();
+    // -- groups (decentralizedMAPP :162-193): connected components of "L-infinity distance of the current POSITIONS < range", as the least id of
+    // the component.  Every label ever stored is the id of a member of the agent's own component and labels only fall, so reading them while other
+    // lanes lower them (and jumping label -> label[label]) is safe; a round in which nothing changed is the fixed point.
+    if (range > 0) {  // (range 0: nobody is within it, every agent keeps its own label)
+        for (int round = 0; round <= n; round++) {
+            int changed = 0;
+            for (int a = tid; a < n; a += T) {
+                const float px = (float)state[(int64_t)a * 9], py = (float)state[(int64_t)a * 9 + 1], pz = (float)state[(int64_t)a * 9 + 2];
+                const int la = ldv(s.label + a);
+                int m = la;
+                for (int j = 0; j < n; j++) {
+                    const int lj = ldv(s.label + j);
+                    if (lj >= m) continue;
+                    const double d0 = fabs((double)(px - (float)state[(int64_t)j * 9])), d1 = fabs((double)(py - (float)state[(int64_t)j * 9 + 1])),
+                                 d2 = fabs((double)(pz - (float)state[(int64_t)j * 9 + 2]));
+                    if (fmax(d0, fmax(d1, d2)) < range) m = lj;
+                }
+                const int mm = ldv(s.label + m);
+                if (mm < m) m = mm;
+                if (m < la) {
+                    stv(s.label + a, m);
+                    changed = 1;
+                }
+            }
+            if (!__syncthreads_or(changed)) break;
+        }
+    }
+    for (int a = tid; a < n; a += T) atomicAdd(s.gsize + ldv(s.label + a), 1);
+    __syncthreads();
+    // -- agents of a group of one decide by themselves; the others are ordered: group by group, within a group by PIBT's priority (elapsed is 0 at
+    // the first timestep; larger init_d first, then the larger tie_breaker = id / n)
+    for (int a = tid; a < n; a += T) {
+        const int la = ldv(s.label + a);
+        if (ldv(s.gsize + la) == 1) {
+            const int v = choose_alone(s, a);
+            stv(s.vnext + a, v < 0 ? s.cur[a] : v);
+            continue;
+        }
+        atomicAdd(&n_multi_sh, 1);
+        const int da = init_d[a];
+        int rank = 0;
+        for (int b = 0; b < n; b++) {
+            const int lb = ldv(s.label + b);
+            if (b == a || ldv(s.gsize + lb) == 1) continue;
+            const int db = init_d[b];
+            const bool before = lb != la ? lb < la : (db != da ? db > da : b > a);
+            rank += before ? 1 : 0;
+        }
+        stv(s.order + rank, a);
+    }
+    __syncthreads();
+    const int n_multi = n_multi_sh;
+    // -- PIBT::run's planning loop for the first timestep, one group after the other, by ONE wavefront.  Every lane runs the same control flow
+    // and issues the same stores (a lane then reads back what it wrote itself); lanes 0..4 look at one candidate each in chooseNode.
+    if (tid < 64) {
+        const int lane = tid;
+        // funcPIBT is entered at most once per agent and every entry plans once, plus once more after each child that failed (a child fails at
+        // most once): <= 2 n plans and <= n returns that carry "true" upwards -- 3 n passes of the loop below.  Reaching the bound means the
+        // tables were corrupt; the waypoints are then left alone and the status word says so.
+        const int bound = 4 * n + 16;
+        int passes = 0, fail = 0;
+        for (int gs = 0; gs < n_multi && !fail;) {
+            const int ge = gs + ldv(s.gsize + ldv(s.label + ldv(s.order + gs)));
+            for (int idx = gs + lane; idx < ge; idx += 64) {  // occupied_now: the last id wins
+                const int a = ldv(s.order + idx);
+                atomicMax(now + s.cur[a], a + 1);
+            }
+            __threadfence_block();
+            __builtin_amdgcn_wave_barrier();
+            for (int idx = gs; idx < ge && !fail; idx++) {
+                const int a0 = ldv(s.order + idx);
+                if (ldv(s.vnext + a0) != -1) continue;
+                int sp = 0, mode = 0;  // mode 0: call or "the child failed" (plan a step), 1: the callee returned true
+                stv(s.stack, a0);
+                while (sp >= 0) {
+                    if (++passes > bound) {
+                        fail = 1;
+                        break;
+                    }
+                    if (mode == 1) {
+                        sp--;
+                        continue;
+                    }
+                    const int ai = ldv(s.stack + sp), cur_i = s.cur[ai];
+                    // chooseNode, candidates in the identity order (one of the orders std::shuffle can draw)
+                    int u = -1, cu = 0, held = 0, ok = 0, aj = -1;
+                    if (lane < 5) {
+                        u = s.cand[(int64_t)ai * 5 + lane];
+                        cu = s.cost[(int64_t)ai * 5 + lane];
+                        if (u >= 0) {
+                            aj = ldv(now + u) - 1;
+                            held = aj >= 0;
+                            ok = ldv(next + u) == 0;                           // vertex conflict
+                            if (ok && aj >= 0) ok = ldv(s.vnext + aj) != cur_i;  // swap conflict
+                        }
+                    }
+                    int v = -1, cv = 0, hv = 0, jv = -1;
+                    for (int c = 0; c < 5; c++) {
+                        const int uc = __shfl(u, c), cc = __shfl(cu, c), hc = __shfl(held, c), oc = __shfl(ok, c), jc = __shfl(aj, c);
+                        if (!oc) continue;
+                        if (cc == 0) {  // the goal: taken at once
+                            v = uc, jv = jc;
+                            break;
+                        }
+                        if (v < 0 || cc < cv || (cc == cv && hv && !hc)) v = uc, cv = cc, hv = hc, jv = jc;
+                    }
+                    if (v < 0) {  // failed to secure a node: stay, and tell the caller
+                        stv(next + cur_i, ai + 1);
+                        stv(s.vnext + ai, cur_i);
+                        stv(s.blocker + ai, -1);
+                        sp--;
+                        mode = 0;
+                        continue;
+                    }
+                    stv(next + v, ai + 1);
+                    stv(s.vnext + ai, v);
+                    stv(s.blocker + ai, (jv != ai && v != cur_i) ? jv : -1);
+                    if (jv >= 0 && jv != ai && ldv(s.vnext + jv) == -1) {  // priority inheritance
+                        sp++;
+                        stv(s.stack + sp, jv);
+                        mode = 0;
+                        continue;
+                    }
+                    sp--;
+                    mode = 1;
+                }
+            }
+            __threadfence_block();
+            __builtin_amdgcn_wave_barrier();
+            for (int idx = gs + lane; idx < ge; idx += 64) {  // leave the tables empty for the next group
+                const int a = ldv(s.order + idx), vn = ldv(s.vnext + a);
+                stv(now + s.cur[a], 0);
+                if (vn >= 0) stv(next + vn, 0);
+            }
+            __threadfence_block();
+            __builtin_amdgcn_wave_barrier();
+            gs = ge;
+        }
+        if (fail) {
+            if (!tables_in_lds)
+                for (int id = lane; id < 2 * nodes; id += 64) stv(id < nodes ? now + id : next + (id - nodes), 0);
+            if (lane == 0) fail_sh = 1;
+        }
+    }
+    __syncthreads();
+    const int fail = fail_sh;
+    // -- the update filter (:222-264): (a) the desired waypoint within range / 2 of every segment start and of the last point of the agent's
+    // plan, (b) it differs from the present waypoint, (c) the current goal point has reached the present waypoint
+    const float zf = (float)g.z_2d;
+    for (int a = tid; a < n; a += T) {
+        const int vn = ldv(s.vnext + a), d = vn < 0 ? s.cur[a] : vn;
+        const int dy_ = d / g.W, dx_ = d - dy_ * g.W;
+        const float des[3] = {node_coord(g.gmin0, dx_, g.res), node_coord(g.gmin1, dy_, g.res), zf};
+        bool in_range = true;
+        if (range > 0) {
+            for (int m = 0; m <= M && in_range; m++) {
+                double dist = 0;
+                for (int k = 0; k < 3; k++) {
+                    float q;
+                    if (plan == nullptr) q = (float)state[(int64_t)a * 9 + k];
+                    else if (k >= dim) q = zf;
+                    else q = (float)plan[(int64_t)a * dim * M * 6 + ((int64_t)k * M + (m < M ? m : M - 1)) * 6 + (m < M ? 0 : 5)];
+                    const double dk = fabs((double)(des[k] - q));
+                    dist = dist < dk ? dk : dist;
+                }
+                if (dist > 0.5 * range - kEpsFloat) in_range = false;
+            }
+        }
+        float nw = 0, ng = 0;
+        for (int k = 0; k < 3; k++) {
+            const float w = (float)waypoint[(int64_t)a * 3 + k], e = des[k] - w, h = (float)cur_goal[(int64_t)a * 3 + k] - w;
+            nw += e * e;
+            ng += h * h;
+        }
+        stv(s.keep + a, (in_range && sqrt((double)nw) > kEpsFloat && sqrt((double)ng) < kEpsFloat) ? 1 : 0);
+        desired_out[a] = d;
+        group_out[a] = ldv(s.label + a);
+    }
+    __syncthreads();
+    // (d) "find valid update" (:266-296): a candidate whose desired node is the present waypoint of a group member that is not (or no longer) a
+    // candidate itself is dropped, until nothing is.  Within a group PIBT hands out distinct nodes, so the only agent that can hold a
+    // candidate's desired node is the one PIBT found there -- `blocker` -- and dropping candidates only ever adds holders: the loop's result
+    // does not depend on the order in which the reference visits its std::set.
+    for (int round = 0; round <= n; round++) {
+        int changed = 0;
+        for (int a = tid; a < n; a += T) {
+            if (!ldv(s.keep + a)) continue;
+            const int j = ldv(s.blocker + a);
+            if (j >= 0 && s.onnode[j] && !ldv(s.keep + j)) {
+                stv(s.keep + a, 0);
+                changed = 1;
+            }
+        }
+        if (!__syncthreads_or(changed)) break;
+    }
+    for (int a = tid; a < n; a += T) {
+        const int up = !fail && ldv(s.keep + a);
+        if (up) {
+            const int d = desired_out[a], dy_ = d / g.W, dx_ = d - dy_ * g.W;
+            waypoint[(int64_t)a * 3 + 0] = (double)node_coord(g.gmin0, dx_, g.res);
+            waypoint[(int64_t)a * 3 + 1] = (double)node_coord(g.gmin1, dy_, g.res);
+            waypoint[(int64_t)a * 3 + 2] = (double)zf;
+        }
+        updated_out[a] = up;
+    }
+    if (tid == 0 && fail) *s.status = 1;
+}
+
+}  // namespace lscgrid
+
+struct lscqp_grid_s {
+    lscgrid::View v;
+    double radius = 0, gmin[3] = {0, 0, 0};
+    int dims[3] = {0, 0, 0};
+    int device = 0;
+    uint8_t *d_occ = nullptr, *d_occ_mission = nullptr;
+    int64_t reserved = 0;
+    int32_t* d_agent_scratch = nullptr;  // 11 arrays, the candidate ones five wide
+    int32_t* d_tables = nullptr;         // now, next, status
+    lscgrid::Scratch s;
+};
+
+namespace {
+
+int grid_hip_fail(hipError_t e, const char* what) {
+    return lscqp_set_error_(LSCQP_ERR_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
+}
+#define GRID_HIP(call)                                     \
+    do {                                                   \
+        const hipError_t e_ = (call);                      \
+        if (e_ != hipSuccess) return grid_hip_fail(e_, #call); \
+    } while (0)
+
+constexpr int64_t kPerAgentInts = 9 + 2 * 5;  // cur, vnext, order, stack, label, blocker, keep, onnode, gsize + cand[5], cost[5]
+
+}  // namespace
+
+extern "C" {
+
+int lscqp_grid_shape(const double* world_min, const double* world_max, double resolution, int32_t world_dimension, double z_2d, double* grid_min,
+                     int32_t* dims) {
+    if (!world_min || !world_max || !grid_min || !dims) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    if (!(resolution > 0)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "grid resolution must be positive");
+    if (world_dimension != 2 && world_dimension != 3) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "world_dimension must be 2 or 3");
+    double gmax[3];
+    for (int i = 0; i < 3; i++) {  // updateGridInfo (src/grid_based_planner.cpp:86-100), SP_EPSILON = 1e-9
+        const double lo = floor((-world_min[i] + 1e-9) / resolution), hi = floor((world_max[i] + 1e-9) / resolution);
+        grid_min[i] = -lo * resolution;
+        gmax[i] = hi * resolution;
+    }
+    if (world_dimension == 2) grid_min[2] = gmax[2] = z_2d;
+    for (int i = 0; i < 3; i++) {
+        const double span = (gmax[i] - grid_min[i]) / resolution;
+        if (!(span >= 0) || span > 1e6) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the world box is empty or the grid has more than 1e6 nodes per axis");
+        dims[i] = (int32_t)round(span) + 1;
+    }
+    return LSCQP_OK;
+}
+
+int lscqp_grid_create(lscqp_map map, const lscqp_grid_desc* desc, lscqp_grid* out) {
+    if (!map || !desc || !out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    if (desc->world_dimension != 2)
+        return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED,
+                                "lscqp_grid is 2-D only: the reference's MAPF graph is x-y (Grid::Grid) and its 3-D waypoints come out at the floor of the world");
+    if (!(desc->resolution > 0) || !(desc->radius >= 0)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "grid resolution must be positive and radius non-negative");
+    double res = 0;
+    float wmin[3], wmax[3];
+    int key0[3], mdims[3], mdev = 0;
+    const int32_t* nearest = nullptr;
+    lscqp_map_raw_(map, &res, wmin, wmax, key0, mdims, &nearest, &mdev);
+    int cur_dev = 0;
+    if (hipGetDevice(&cur_dev) != hipSuccess) return lscqp_set_error_(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (mdev != cur_dev) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the map lives on another device than the current one");
+    const double wmin_d[3] = {wmin[0], wmin[1], wmin[2]}, wmax_d[3] = {wmax[0], wmax[1], wmax[2]};  // (mission.world_min / _max are point3d)
+    lscqp_grid_s* g = new lscqp_grid_s();
+    int rc = lscqp_grid_shape(wmin_d, wmax_d, desc->resolution, 2, desc->z_2d, g->gmin, g->dims);
+    if (rc == LSCQP_OK && (int64_t)g->dims[0] * g->dims[1] > (int64_t)1 << 26) rc = lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "more than 2^26 grid nodes");
+    if (rc != LSCQP_OK) {
+        delete g;
+        return rc;
+    }
+    g->device = cur_dev;
+    g->radius = desc->radius;
+    g->v = lscgrid::View{g->gmin[0], g->gmin[1], desc->resolution, desc->z_2d, g->dims[0], g->dims[1]};
+    const lscgrid::MapRaw mraw{res, key0[0], key0[1], key0[2], mdims[0], mdims[1], mdims[2], nearest};  // (read by the occupancy kernel below and not kept: the grid outlives its map)
+    const int nodes = g->dims[0] * g->dims[1];
+    hipError_t e = hipMalloc((void**)&g->d_occ, (size_t)nodes);
+    if (e == hipSuccess) e = hipMalloc((void**)&g->d_occ_mission, (size_t)nodes);
+    if (e == hipSuccess) e = hipMalloc((void**)&g->d_tables, ((size_t)2 * nodes + 4) * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemset(g->d_tables, 0, ((size_t)2 * nodes + 4) * sizeof(int32_t));
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(lscgrid::occupancy_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, (hipStream_t)0, g->v, mraw, g->radius, g->d_occ);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(g->d_occ_mission, g->d_occ, (size_t)nodes, hipMemcpyDeviceToDevice);
+    // (the LDS form of the field kernel may ask for more than the 64 KB a kernel gets by default)
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lscgrid::fields_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lscgrid::kLdsNodes * 2);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        lscqp_grid_destroy(g);
+        return grid_hip_fail(e, "lscqp_grid_create");
+    }
+    *out = g;
+    return LSCQP_OK;
+}
+
+void lscqp_grid_destroy(lscqp_grid g) {
+    if (!g) return;
+    int prev = -1;
+    if (hipGetDevice(&prev) == hipSuccess && prev != g->device) (void)hipSetDevice(g->device);
+    (void)hipDeviceSynchronize();
+    for (void* p : {(void*)g->d_occ, (void*)g->d_occ_mission, (void*)g->d_agent_scratch, (void*)g->d_tables})
+        if (p) (void)hipFree(p);
+    if (prev >= 0 && prev != g->device) (void)hipSetDevice(prev);
+    delete g;
+}
+
+int lscqp_grid_info(lscqp_grid g, double* grid_min, int32_t* dims) {
+    if (!g || !grid_min || !dims) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    for (int k = 0; k < 3; k++) grid_min[k] = g->gmin[k], dims[k] = g->dims[k];
+    return LSCQP_OK;
+}
+
+int lscqp_grid_download(lscqp_grid g, uint8_t* occ) {
+    if (!g || !occ) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    GRID_HIP(hipMemcpy(occ, g->d_occ, (size_t)g->dims[0] * g->dims[1], hipMemcpyDeviceToHost));
+    return LSCQP_OK;
+}
+
+int lscqp_grid_download_mission(lscqp_grid g, uint8_t* occ) {
+    if (!g || !occ) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    GRID_HIP(hipMemcpy(occ, g->d_occ_mission, (size_t)g->dims[0] * g->dims[1], hipMemcpyDeviceToHost));
+    return LSCQP_OK;
+}
+
+int lscqp_grid_status(lscqp_grid g, int32_t* status_out) {
+    if (!g || !status_out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    GRID_HIP(hipMemcpy(status_out, g->d_tables + (size_t)2 * g->dims[0] * g->dims[1], sizeof(int32_t), hipMemcpyDeviceToHost));
+    return LSCQP_OK;
+}
+
+int lscqp_grid_reserve(lscqp_grid g, int64_t n) {
+    if (!g || n < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (n > ((int64_t)1 << 24)) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "more than 2^24 agents");
+    if (n > g->reserved) {
+        GRID_HIP(hipDeviceSynchronize());
+        if (g->d_agent_scratch) GRID_HIP(hipFree(g->d_agent_scratch));
+        g->d_agent_scratch = nullptr;
+        g->reserved = 0;
+        GRID_HIP(hipMalloc((void**)&g->d_agent_scratch, (size_t)n * kPerAgentInts * sizeof(int32_t)));
+        g->reserved = n;
+    }
+    int32_t* b = g->d_agent_scratch;
+    const int64_t r = g->reserved;
+    lscgrid::Scratch& s = g->s;
+    s.cur = b, s.vnext = b + r, s.order = b + 2 * r, s.stack = b + 3 * r, s.label = b + 4 * r, s.blocker = b + 5 * r, s.keep = b + 6 * r;
+    s.onnode = b + 7 * r, s.gsize = b + 8 * r, s.cand = b + 9 * r, s.cost = b + 14 * r;
+    const int64_t nodes = (int64_t)g->dims[0] * g->dims[1];
+    s.now = g->d_tables, s.next = g->d_tables + nodes, s.status = g->d_tables + 2 * nodes;
+    return LSCQP_OK;
+}
+
+int lscqp_grid_fields_device(lscqp_grid g, int64_t n, const double* d_start_points, const double* d_goal_points, int32_t* d_field, int32_t* d_init_d,
+                             void* stream) {
+    if (!g || n < 0 || (n > 0 && (!d_start_points || !d_goal_points || !d_field || !d_init_d)))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (n == 0) return LSCQP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int W = g->dims[0], H = g->dims[1], nodes = W * H;
+    GRID_HIP(hipMemcpyAsync(g->d_occ_mission, g->d_occ, (size_t)nodes, hipMemcpyDeviceToDevice, st));
+    GRID_HIP(hipMemsetAsync(g->d_tables + (size_t)2 * nodes, 0, 4 * sizeof(int32_t), st));  // a new mission: the status word starts at 0
+    hipLaunchKernelGGL(lscgrid::clear_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, d_start_points, d_goal_points, g->d_occ_mission);
+    const int64_t padded = (int64_t)(W + 2) * (H + 2);
+    if (padded <= lscgrid::kLdsNodes) {
+        const int threads = padded <= 2048 ? 256 : 1024;
+        const size_t lds = (size_t)((padded * 2 + 15) / 16 * 16);
+        hipLaunchKernelGGL(lscgrid::fields_kernel<true>, dim3((unsigned)n), dim3(threads), lds, st, g->v, g->d_occ_mission, d_start_points, d_goal_points, d_field, d_init_d);
+    } else {
+        hipLaunchKernelGGL(lscgrid::fields_kernel<false>, dim3((unsigned)n), dim3(1024), 0, st, g->v, g->d_occ_mission, d_start_points, d_goal_points, d_field, d_init_d);
+    }
+    GRID_HIP(hipGetLastError());
+    return LSCQP_OK;
+}
+
+int lscqp_waypoints_device(lscqp_grid g, double communication_range, int32_t M, int32_t dim, int64_t n, const double* d_state, const double* d_plan,
+                           const double* d_current_goal, const int32_t* d_field, const int32_t* d_init_d, double* d_waypoint, int32_t* d_group_out,
+                           int32_t* d_desired_out, int32_t* d_updated_out, void* stream) {
+    if (!g || n < 0 || (n > 0 && (!d_state || !d_current_goal || !d_field || !d_init_d || !d_waypoint || !d_group_out || !d_desired_out || !d_updated_out)))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (dim != 2) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_waypoints_device is 2-D only");
+    if (d_plan && M < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "M must be positive");
+    if (!(communication_range == communication_range)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "communication_range is NaN");
+    if (n == 0) return LSCQP_OK;
+    if (n > g->reserved) {  // (synchronises and allocates: a caller that captures the launch reserves beforehand)
+        const int rc = lscqp_grid_reserve(g, n);
+        if (rc != LSCQP_OK) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int nodes = g->dims[0] * g->dims[1];
+    hipLaunchKernelGGL(lscgrid::gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, communication_range, g->d_occ_mission, d_waypoint, d_field, g->s);
+    const size_t table_bytes = (size_t)2 * nodes * sizeof(int32_t);
+    const int in_lds = table_bytes <= (size_t)lscgrid::kTableLdsBytes;
+    hipLaunchKernelGGL(lscgrid::decide_kernel, dim3(1), dim3(lscgrid::kDecideThreads), in_lds ? (table_bytes + 15) / 16 * 16 : 0, st, g->v, n, communication_range,
+                       (int)M, (int)dim, in_lds, d_state, d_plan, d_current_goal, d_init_d, d_waypoint, g->s, d_group_out, d_desired_out, d_updated_out);
+    GRID_HIP(hipGetLastError());
+    return LSCQP_OK;
+}
+
+}  // extern "C"

@@ -13,8 +13,9 @@
 // Two small kernels of this file glue them: `prepare` (headers, corridor seed points, the initial trajectory in the solver's
 // layout) and `commit` (failsafe, goal point).  Because nothing in the chain synchronises, allocates or copies through the
 // host, the whole replan can be captured once in a hipGraph and replayed (lscqp_plan_step_graph): one graph launch instead of
-// ten kernel launches per replan.  What stays on the host is what is out of scope: the waypoints of the
-// grid planner / MAPF layer, written into the plan's waypoint buffer before each step.
+// ten kernel launches per replan.  The waypoints of the grid planner / MAPF layer are either written into the plan's waypoint buffer by
+// the caller before each step (waypoint_mode 0) or decided at the head of the chain by lscqp_waypoints_device (waypoint_mode 1, lscgrid.hip):
+//   MultiSyncSimulator::decentralizedMAPP               -> lscqp_waypoints_device over the state, plans and goal points of the last replan
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -212,6 +213,12 @@ struct lscqp_plan_s {
     // what the captured graph (and the tight-warm-start clone) was derived from: a later lscqp_update / lscqp_map_prepare bumps these
     uint64_t h_gen = 0, map_gen = 0;
     std::vector<void*> owned;
+    // waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: the grid, the mission's distance fields (one per agent, made by lscqp_plan_reset) and start points
+    lscqp_grid grid = nullptr;
+    double grid_resolution = 0.5, grid_radius = 0;
+    int32_t *field = nullptr, *init_d = nullptr, *desired_node = nullptr;
+    double* start_pts = nullptr;
+    bool fields_valid = false;
 };
 
 namespace {
@@ -270,6 +277,13 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     double* obj = (double*)p->buf[LSCQP_PLAN_BUF_OBJECTIVE];
     lscqp_info* info = (lscqp_info*)p->buf[LSCQP_PLAN_BUF_INFO];
     const double fraction = p->d.time_step / s.dt;
+    // decentralizedMAPP precedes the planning loop (src/multi_sync_simulator.cpp:101-120): the waypoints of this replan, from the plans as the
+    // last replan left them (AgentManager::getTraj is desired_traj, un-shifted)
+    if (p->grid) {
+        if (!p->fields_valid) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: lscqp_plan_reset must come before the first step");
+        PLAN_TRY(lscqp_waypoints_device(p->grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, state, x_plan, goal, p->field, p->init_d,
+                                        waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], p->desired_node, (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
+    }
     // obstaclePredictionWithPrevSol / initialTrajPlanningPrevSol for every agent of the mission (:273-310, 399-423)
     const bool from_plans = !first_replan && (s.prediction_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION || s.initial_traj_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION);
     const bool whole_shift = from_plans && fraction >= 1.0 - 1e-9;  // (done by prepare_kernel itself)
@@ -332,6 +346,42 @@ void drop_graph(lscqp_plan_s* p) {
     p->graph = nullptr;
 }
 
+// the plan's grid and the buffers sized by it (waypoint_mode 1): made at lscqp_plan_create, again by lscqp_plan_set_grid
+int make_grid(lscqp_plan_s* p, double resolution) {
+    lscqp_grid_desc gd;
+    memset(&gd, 0, sizeof gd);
+    gd.resolution = resolution, gd.radius = p->grid_radius, gd.z_2d = p->d.z_2d, gd.world_dimension = p->s.dim;
+    lscqp_grid gnew = nullptr;
+    PLAN_TRY(lscqp_grid_create(p->map, &gd, &gnew));
+    double gmin[3];
+    int32_t dims[3];
+    lscqp_grid_info(gnew, gmin, dims);
+    void* f = nullptr;
+    const hipError_t e = hipMalloc(&f, (size_t)p->s.n_total * dims[0] * dims[1] * sizeof(int32_t));
+    int rc = e == hipSuccess ? lscqp_grid_reserve(gnew, p->s.n_total) : hip_fail(e, "hipMalloc(distance fields)");
+    if (rc != LSCQP_OK) {
+        if (f) (void)hipFree(f);
+        lscqp_grid_destroy(gnew);
+        return rc;
+    }
+    if (p->grid) lscqp_grid_destroy(p->grid);
+    if (p->field) (void)hipFree(p->field);
+    p->grid = gnew;
+    p->field = (int32_t*)f;
+    p->grid_resolution = resolution;
+    p->fields_valid = false;
+    return LSCQP_OK;
+}
+
+// updateGridMission + createDistanceTable for the whole mission (include/lscqp.h, DIFFERENCE 1); synchronous
+int make_fields(lscqp_plan_s* p) {
+    PLAN_TRY(lscqp_grid_fields_device(p->grid, p->s.n_total, p->start_pts, (const double*)p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], p->field, p->init_d, nullptr));
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "distance fields");
+    p->fields_valid = true;
+    return LSCQP_OK;
+}
+
 // The class constants travel to the kernels BY VALUE and the map view (table pointer + margin) likewise, so a captured graph -- and
 // the private WARM_TIGHT clone of the handle -- are snapshots.  lscqp_update(h) (TrajOptimizer::updateParam, src/traj_optimizer.cpp:158-160)
 // or lscqp_map_prepare after the capture would be silently ignored by the replayed graph while the eager chain sees the new values:
@@ -370,6 +420,12 @@ int refresh(lscqp_plan_s* p) {
             const int rc = lscqp_update(p->hq, &cd);
             if (rc != LSCQP_OK) return rc;
         }
+    }
+    if (mg != p->map_gen && p->grid && p->fields_valid) {  // the map moved under the mission: its grid and fields are made again
+        const int rc = make_grid(p, p->grid_resolution);
+        if (rc != LSCQP_OK) return rc;
+        const int rc2 = make_fields(p);
+        if (rc2 != LSCQP_OK) return rc2;
     }
     p->h_gen = hg;
     p->map_gen = mg;
@@ -421,6 +477,14 @@ int lscqp_plan_create(lscqp_handle h, lscqp_map map, const lscqp_plan_desc* desc
                                 "safety_samples needs every agent's new plan on this device (n_agents == n_total) and record_time_step > 0");
     if (lscqp_row_bytes(h) != (int)sizeof(lscqp_row))
         return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "the plan chain uses 32-byte rows (row_format = LSCQP_ROWS_F64)");
+    if (desc->waypoint_mode != LSCQP_WAYPOINT_FROM_CALLER && desc->waypoint_mode != LSCQP_WAYPOINT_GRID_PIBT)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode must be LSCQP_WAYPOINT_FROM_CALLER or LSCQP_WAYPOINT_GRID_PIBT");
+    if (desc->waypoint_mode == LSCQP_WAYPOINT_GRID_PIBT) {
+        if (desc->n_agents != desc->n_total)
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT needs every agent's waypoint and plan on this device (n_agents == n_total)");
+        if (!map) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT needs a map");
+        if (nv / (6 * M) != 2) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT needs a 2-D class (the reference's MAPF graph is x-y only)");
+    }
     if (map) {  // the corridor kernel's free-space table for the agents of this mission (no-op if the map already has one that serves them)
         double rmax = 0;
         for (int64_t i = 0; i < desc->n_total; i++) rmax = agents[i].radius > rmax ? agents[i].radius : rmax;
@@ -483,6 +547,12 @@ int lscqp_plan_create(lscqp_handle h, lscqp_map map, const lscqp_plan_desc* desc
         ok(dalloc(p, &p->points, n * 9)) && ok(dalloc(p, &p->own, n * P * 3)) && ok(dalloc(p, &p->x_init, n * nv)) && ok(dalloc(p, &p->x_new, n * nv)) &&
         ok(dalloc(p, &p->nbr, n * no)) && ok(dalloc(p, &p->off, n + 1)) && ((int64_t)n > lscqp_launch_capacity(h, (int64_t)n, desc->n_obs) ? ok(dalloc(p, &p->order, n)) : true) &&
         ((map && n > lscplan::kSfcOrderMin) ? (ok(dalloc(p, &p->sfc_order, n)) && ok(dalloc(p, &p->sfc_cost, n))) : true);
+    if (desc->waypoint_mode == LSCQP_WAYPOINT_GRID_PIBT) {
+        ok(dalloc_pub<double>(p, LSCQP_PLAN_BUF_DESIRED_GOAL, nt * 3)) && ok(dalloc_pub<int32_t>(p, LSCQP_PLAN_BUF_WAYPOINT_UPDATED, n)) &&
+            ok(dalloc_pub<int32_t>(p, LSCQP_PLAN_BUF_GROUP, n)) && ok(dalloc(p, &p->init_d, nt)) && ok(dalloc(p, &p->desired_node, nt)) && ok(dalloc(p, &p->start_pts, nt * 3));
+        p->grid_radius = agents[0].radius;  // (planMAPF is handed mission.agents[0].radius, src/multi_sync_simulator.cpp:211-214)
+        if (rc == LSCQP_OK) rc = make_grid(p, 0.5);
+    }
     if (rc == LSCQP_OK) {
         p->bytes[LSCQP_PLAN_BUF_STATE] = nt * 9 * sizeof(double);
         p->bytes[LSCQP_PLAN_BUF_PLAN] = nt * nv * sizeof(double);
@@ -522,22 +592,26 @@ void lscqp_plan_destroy(lscqp_plan p) {
     drop_graph(p);
     if (p->cap) (void)hipStreamDestroy(p->cap);
     for (void* q : p->owned) (void)hipFree(q);
+    if (p->grid) lscqp_grid_destroy(p->grid);
+    if (p->field) (void)hipFree(p->field);
     if (p->own_hq) lscqp_destroy(p->hq);
     delete p;
 }
 
 int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* goal_points) {
     if (!p || !start_positions) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    if (p->grid && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: the mission's goal points are required");
     DeviceGuard g(p->device);
     const lscplan::Shape& s = p->s;
     const size_t nt = (size_t)s.n_total, P = (size_t)s.M * 6;
-    std::vector<double> st(nt * 9, 0.0), x(nt * s.nv), gl(nt * 3);
+    std::vector<double> st(nt * 9, 0.0), x(nt * s.nv), gl(nt * 3), dg(p->grid ? nt * 3 : 0);
     for (size_t a = 0; a < nt; a++) {
         for (int k = 0; k < 3; k++) {
             // State holds point3d; a 2-D mission flies at z = world_z_2d (src/agent_manager.cpp:40-42)
             const double v = (k < s.dim) ? (double)(float)start_positions[a * 3 + k] : (double)(float)s.z_2d;
             st[a * 9 + k] = v;
-            gl[a * 3 + k] = goal_points ? (double)(float)goal_points[a * 3 + k] : v;  // AgentManager ctor: current_goal_point = start
+            gl[a * 3 + k] = (goal_points && !p->grid) ? (double)(float)goal_points[a * 3 + k] : v;  // AgentManager ctor: current_goal_point = start
+            if (p->grid) dg[a * 3 + k] = (k < s.dim) ? (double)(float)goal_points[a * 3 + k] : v;  // Agent::desired_goal_point, in the mission's plane
         }
         for (int k = 0; k < s.dim; k++)
             for (size_t j = 0; j < P; j++) x[a * s.nv + k * P + j] = st[a * 9 + k];
@@ -547,7 +621,12 @@ int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* 
     if (e == hipSuccess) e = hipMemcpy(p->buf[LSCQP_PLAN_BUF_PLAN], x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p->buf[LSCQP_PLAN_BUF_GOAL], gl.data(), gl.size() * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p->buf[LSCQP_PLAN_BUF_WAYPOINT], gl.data() + s.first_agent * 3, (size_t)s.n_agents * 3 * sizeof(double), hipMemcpyHostToDevice);
+    if (p->grid) {  // (gl holds the start positions here: the waypoints above start there, src/agent_manager.cpp:10)
+        if (e == hipSuccess) e = hipMemcpy(p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], dg.data(), dg.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(p->start_pts, gl.data(), gl.size() * sizeof(double), hipMemcpyHostToDevice);
+    }
     if (e != hipSuccess) return hip_fail(e, "plan reset");
+    if (p->grid) PLAN_TRY(make_fields(p));
     p->first = true;
     p->steps = 0;
     return LSCQP_OK;
@@ -622,6 +701,18 @@ int lscqp_plan_step_graph(lscqp_plan p, void* stream) {
     p->steps++;
     return LSCQP_OK;
 }
+
+int lscqp_plan_set_grid(lscqp_plan p, double resolution) {
+    if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
+    if (!p->grid) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the plan has no grid (waypoint_mode = LSCQP_WAYPOINT_FROM_CALLER)");
+    DeviceGuard g(p->device);
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_grid");
+    drop_graph(p);  // (a captured chain holds the old grid's buffers)
+    return make_grid(p, resolution);
+}
+
+lscqp_grid lscqp_plan_grid(lscqp_plan p) { return p ? p->grid : nullptr; }
 
 const lscqp_plan_desc* lscqp_plan_desc_of_(lscqp_plan p) { return &p->d; }  // (library-internal: lscqp_comm.hip)
 int lscqp_plan_device_(lscqp_plan p) { return p->device; }

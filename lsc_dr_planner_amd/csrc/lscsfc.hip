@@ -55,6 +55,14 @@ struct lscqp_map_s {
 #ifndef LSCSFC_VARIANT_ONLY
 extern "C" int lscqp_map_device_(lscqp_map mp) { return mp->device; }
 extern "C" uint64_t lscqp_map_generation_(lscqp_map mp) { return mp->generation; }
+// (library-internal: lscgrid.hip evaluates the grid planner's occupancy from the same nearest-occupied-cell field)
+extern "C" int lscqp_map_raw_(lscqp_map mp, double* res, float* world_min, float* world_max, int* key0, int* dims, const int32_t** d_nearest, int* device) {
+    *res = mp->res;
+    for (int k = 0; k < 3; k++) world_min[k] = mp->world_min[k], world_max[k] = mp->world_max[k], key0[k] = mp->key0[k], dims[k] = mp->dims[k];
+    *d_nearest = mp->d_nearest;
+    *device = mp->device;
+    return 0;
+}
 #endif
 
 namespace lscsfc {

@@ -6,9 +6,10 @@
 
     python tools/closed_loop.py [--steps 40] [--world tests/golden/forest10_world.json]
 
-The host does only what the out-of-scope parts of the reference do: it picks each agent's next waypoint (the grid-based
-planner / MAPF stand-in: 0.5 m towards the desired goal from the end of the current plan) and keeps the per-agent
-headers.  Agents whose QP fails or whose solution is invalid keep their shifted previous plan, like the reference
+The host keeps the per-agent headers and, with --router host (the default), picks each agent's next waypoint with a stand-in
+for the grid-based planner (8-connected shortest paths, no conflict handling between agents).  --router device replaces
+the stand-in by lscqp_waypoints_device: the reference's own rule (4-connected grid, one PIBT step per communication
+group, the simulator's update filter), so its paths differ from the stand-in's.  Agents whose QP fails or whose solution is invalid keep their shifted previous plan, like the reference
 (src/traj_planner.cpp:767-797).  Prints one JSON summary; tests/test_closed_loop.py runs it.
 """
 import argparse
@@ -104,10 +105,13 @@ def random_forest_world(n_agents=64, side=24.0, n_boxes=150, seed=0, clearance=0
             "z_2d": z, "radius": 0.15, "starts": [[p[0], p[1], z] for p in starts], "goals": [[p[0], p[1], z] for p in goals]}
 
 
-def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None):
+def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None, router="host"):
     """script (optional): {"waypoint": (K, N, 3), "state": (K, N, 9)} -- replay of a recorded mission: replan k takes every agent's
     state and waypoint from the script instead of the loop's own step / router (the plans, goal points, corridors and neighbour sets are
-    still the loop's own), and the result carries every replan's solution (`x`, (K, N, nv)) and goal point (`goal`, (K, N, 3))."""
+    still the loop's own), and the result carries every replan's solution (`x`, (K, N, nv)) and goal point (`goal`, (K, N, 3)).
+    router: "host" (GridRouter) or "device" (lscqp_waypoints_device over the previous plans, states and goal points)."""
+    if router not in ("host", "device"):
+        raise ValueError("router must be 'host' or 'device'")
     import torch
 
     from lsc_dr_planner_amd import api
@@ -164,7 +168,13 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
     torch.cuda.synchronize()
     assert (d_sst.cpu().numpy() == 1).all(), "a start point lies inside an inflated obstacle"
 
-    router = GridRouter(g, wmap.download()[0], wmap.key0) if script is None else None
+    use_device_router = router == "device" and script is None
+    grid_router = GridRouter(g, wmap.download()[0], wmap.key0) if script is None and not use_device_router else None
+    if use_device_router:  # the grid planner's grid and the mission's distance fields, once
+        grid = api.Grid(wmap, 0.5, radius, z2d)
+        d_field, d_init_d = grid.fields(up(starts), up(desired))
+        d_way = up(np.float32(starts).astype(np.float64))
+        updated_total = 0
     waypoint = starts.copy()  # first waypoint: the start node itself; it advances in the loop
     goal_pt = starts.copy()   # agent.current_goal_point
     log = {"steps": steps, "agents": N, "qp_failed": 0, "invalid": 0, "sfc_kept": 0, "goal_infeasible": 0, "min_safety_ratio": np.inf,
@@ -182,10 +192,15 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
         # satisfiable); the current goal point is the outcome of the previous goal LP (src/traj_planner.cpp:545-549)
         if script is not None:
             state, waypoint = np.array(script["state"][step], dtype=np.float64), np.array(script["waypoint"][step], dtype=np.float64)
+        elif use_device_router:
+            # decentralizedMAPP: one PIBT step per communication group from the plans as the last replan left them, then the update filter
+            _, _, d_upd = grid.waypoints(comm_range, M, dim, up(state), d_xprev, up(goal_pt), d_field, d_init_d, d_way)
+            waypoint = d_way.cpu().numpy().reshape(N, 3)
+            updated_total += int(d_upd.sum().item())
         else:
             for a in range(N):
                 if np.abs(state[a, :2] - waypoint[a, :2]).max() < 0.3:
-                    waypoint[a, :2] = router.next_waypoint(waypoint[a], desired[a])[0]
+                    waypoint[a, :2] = grid_router.next_waypoint(waypoint[a], desired[a])[0]
         waypoint = np.float32(waypoint).astype(np.float64)
         if step > 0:
             P = np.stack([last, goal_pt, waypoint], axis=1)
@@ -272,6 +287,11 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
     log["max_iters"] = int(max(log["iters"]))
     del log["iters"]
     # occupancy check of the flown positions: the agents (L-infinity radius) never touch an occupied cell
+    log["router"] = router
+    if use_device_router:
+        log["waypoints_updated"] = updated_total
+        assert grid.status() == 0
+        grid.close()
     wmap.close()
     return log
 
@@ -284,6 +304,7 @@ if __name__ == "__main__":
     ap.add_argument("--forest", type=int, default=0, help="N > 0: a synthetic forest with N agents instead of --world")
     ap.add_argument("--obs", type=int, default=None, help="neighbour capacity per agent")
     ap.add_argument("--dump", default=None, help="npz path: inputs of the first replan with a failed QP")
+    ap.add_argument("--router", default="host", choices=("host", "device"), help="where the waypoints come from: the host stand-in or lscqp_waypoints_device")
     a = ap.parse_args()
     world = random_forest_world(a.forest) if a.forest > 0 else a.world
-    print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs)))
+    print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router)))
