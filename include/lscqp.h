@@ -908,6 +908,60 @@ int64_t lscqp_plan_graph_nodes(lscqp_plan plan); /* nodes of the captured graph,
  * written per plan before the call, as for lscqp_plan_step. */
 int lscqp_plan_group_step(lscqp_comm c, const lscqp_plan* plans, int32_t use_graph);
 
+/* ---- many missions over one map: a mission partition of a plan's agents --------------------------------------------------------------
+ *
+ * The reference is evaluated on sets of missions over ONE world (launch/test_all_*.launch: missions/<set>/<set>_1..30.json, one result
+ * line per mission).  A partition lets one plan fly K such missions in one chain per replan.  Missions are contiguous ranges of global
+ * agent ids, [mission_offsets[k], mission_offsets[k + 1]), the list strictly increasing from 0 to n_total (no empty mission).  Agents of
+ * different missions share the map and the solver class and nothing else: they are never each other's neighbours (no LSC / BVC rows for
+ * each other), never in one communication group, never compete for a grid node, never enter each other's safety figures, and their start
+ * and goal nodes are cleared in their own mission's occupancy only.  Everything else in the chain is per agent and unchanged.
+ *   lscqp_plan_set_missions   host offsets [n_missions + 1].  Call it before lscqp_plan_reset, like lscqp_plan_set_grid: it waits for the
+ *                             device, drops a captured graph and invalidates the distance fields, and a step before the next
+ *                             lscqp_plan_reset is refused (LSCQP_ERR_INVALID_ARGUMENT).  n_missions <= 1 or NULL offsets: back to the single
+ *                             mission, whose chain is the one a plan without this call runs, launch for launch.  A bad offset list and a
+ *                             sharded plan (n_agents != n_total, the rule of safety_samples and waypoint_mode 1) are refused and leave the
+ *                             plan as it was.  Out of scope: different maps, classes or n_obs per mission; missions across devices.
+ *   lscqp_plan_missions       the partition read back: *n_missions_out (1 without a partition) and, if offsets_out != NULL, its
+ *                             n_missions + 1 offsets.
+ *   lscqp_plan_mission_status status_out [n_missions], host; waits for the device.  The word of each mission's waypoint walk: 0 = fine,
+ *                             1 = the bound of 4 n_k + 16 passes was reached (n_k: the mission's agents), which leaves the waypoints of THAT
+ *                             mission alone.  Sticky like lscqp_grid_status, cleared by lscqp_plan_reset; all zero in waypoint_mode 0.
+ *                             LSCQP_PLAN_BUF_GROUP keeps reporting the least GLOBAL id of the agent's group.
+ * The mission-aware twins of the entry points in which agents see each other.  Each takes the partition twice: mission_offsets on the
+ * host (checked before the device is touched; the safety launch is shaped by the largest mission) and d_mission_offsets, the same
+ * n_missions + 1 values on the device, which the kernels read.  All n agents are local (no first_agent); ids in and out are global.
+ *   lscqp_select_neighbours_missions_device   lscqp_select_neighbours_device with the agent's own mission as its candidates; the cut to the
+ *                             n_obs nearest and the in-range count keep their meaning.
+ *   lscqp_safety_metrics_missions_device      lscqp_safety_metrics_device over the pairs within a mission; closest_agent is a global id,
+ *                             -1 and an infinite ratio for a mission of one.
+ *   lscqp_grid_fields_missions_device         lscqp_grid_fields_device with one occupancy copy per mission: an agent's start and goal nodes
+ *                             are cleared in its mission's copy, and its field is relaxed over that copy.  Clears the status words.
+ *   lscqp_waypoints_missions_device           lscqp_waypoints_device as one workgroup per mission over its slice: groups, priorities, the
+ *                             PIBT walk with node tables of its own (LDS up to 60 KB, a slab of an HBM buffer per mission beyond) and the
+ *                             filter.  d_group_out: least global id of the group.  lscqp_grid_fields_missions_device over the SAME
+ *                             partition must have come last on this grid (it makes the copies and clears them for the agents of its
+ *                             partition): any other offset list is refused.  One decision at a time per grid.
+ *   lscqp_grid_mission_status status_out [n_missions], host; waits: the words lscqp_plan_mission_status reports. */
+int lscqp_plan_set_missions(lscqp_plan plan, int32_t n_missions, const int64_t* mission_offsets);
+int lscqp_plan_missions(lscqp_plan plan, int32_t* n_missions_out, int64_t* offsets_out);
+int lscqp_plan_mission_status(lscqp_plan plan, int32_t* status_out);
+int lscqp_select_neighbours_missions_device(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
+                                            const int64_t* d_mission_offsets, int32_t n_obs, double communication_range,
+                                            const double* d_positions, int32_t* d_neighbours_out, int32_t* d_count_out, void* stream);
+int lscqp_safety_metrics_missions_device(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
+                                         const int64_t* d_mission_offsets, int32_t n_samples, double record_time_step, double z_2d,
+                                         const double* d_x_all, const double* d_radius, const double* d_downwash, const lscqp_header* d_hdr,
+                                         lscqp_safety* d_out, void* stream);
+int lscqp_grid_fields_missions_device(lscqp_grid grid, int64_t n, int32_t n_missions, const int64_t* mission_offsets,
+                                      const int64_t* d_mission_offsets, const double* d_start_points, const double* d_goal_points,
+                                      int32_t* d_field, int32_t* d_init_d, void* stream);
+int lscqp_waypoints_missions_device(lscqp_grid grid, double communication_range, int32_t M, int32_t dim, int64_t n, int32_t n_missions,
+                                    const int64_t* mission_offsets, const int64_t* d_mission_offsets, const double* d_state,
+                                    const double* d_plan, const double* d_current_goal, const int32_t* d_field, const int32_t* d_init_d,
+                                    double* d_waypoint, int32_t* d_group_out, int32_t* d_desired_out, int32_t* d_updated_out, void* stream);
+int lscqp_grid_mission_status(lscqp_grid grid, int32_t n_missions, int32_t* status_out);
+
 /* ---- work counters of a launch (the fp64-VALU figure next to the HBM one) -----------------------------
  *
  * The kernel is bound by fp64 vector issue, not by HBM; the figure that goes with that roof is

@@ -249,6 +249,23 @@ def lib():
         L.lscqp_grid_fields_device.argtypes = [vp, C.c_int64] + [vp] * 5
         L.lscqp_waypoints_device.restype = C.c_int
         L.lscqp_waypoints_device.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_int64] + [vp] * 10
+        i64, i32 = C.c_int64, C.c_int32
+        L.lscqp_plan_set_missions.restype = C.c_int
+        L.lscqp_plan_set_missions.argtypes = [vp, i32, vp]
+        L.lscqp_plan_missions.restype = C.c_int
+        L.lscqp_plan_missions.argtypes = [vp, vp, vp]
+        L.lscqp_plan_mission_status.restype = C.c_int
+        L.lscqp_plan_mission_status.argtypes = [vp, vp]
+        L.lscqp_select_neighbours_missions_device.restype = C.c_int
+        L.lscqp_select_neighbours_missions_device.argtypes = [vp, i64, i32, vp, vp, i32, C.c_double, vp, vp, vp, vp]
+        L.lscqp_safety_metrics_missions_device.restype = C.c_int
+        L.lscqp_safety_metrics_missions_device.argtypes = [vp, i64, i32, vp, vp, i32, C.c_double, C.c_double] + [vp] * 6
+        L.lscqp_grid_fields_missions_device.restype = C.c_int
+        L.lscqp_grid_fields_missions_device.argtypes = [vp, i64, i32, vp, vp] + [vp] * 5
+        L.lscqp_waypoints_missions_device.restype = C.c_int
+        L.lscqp_waypoints_missions_device.argtypes = [vp, C.c_double, i32, i32, i64, i32, vp, vp] + [vp] * 10
+        L.lscqp_grid_mission_status.restype = C.c_int
+        L.lscqp_grid_mission_status.argtypes = [vp, i32, vp]
         L.lscqp_last_error.restype = C.c_char_p
         L.lscqp_version.restype = C.c_char_p
         L.lscqp_instance_work.restype = C.c_int
@@ -278,6 +295,8 @@ EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_
                     "lscqp_plan_step", "lscqp_plan_step_graph", "lscqp_plan_graph_nodes", "lscqp_plan_group_step", "lscqp_plan_set_grid", "lscqp_plan_grid",
                     "lscqp_grid_shape", "lscqp_grid_create", "lscqp_grid_destroy", "lscqp_grid_info", "lscqp_grid_download", "lscqp_grid_download_mission",
                     "lscqp_grid_reserve", "lscqp_grid_status", "lscqp_grid_fields_device", "lscqp_waypoints_device",
+                    "lscqp_plan_set_missions", "lscqp_plan_missions", "lscqp_plan_mission_status", "lscqp_select_neighbours_missions_device",
+                    "lscqp_safety_metrics_missions_device", "lscqp_grid_fields_missions_device", "lscqp_waypoints_missions_device", "lscqp_grid_mission_status",
                     "lscqp_instance_work", "lscqp_diagnose", "lscqp_diagnose_device", "lscqp_dump_instance", "lscqp_row_family_name",
                     "lscqp_last_error", "lscqp_version"]
 
@@ -381,6 +400,20 @@ def _dptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def mission_offsets_arg(offsets, device=None, d_offsets=None):
+    """A mission partition as the entry points take it: (K, host int64 array, its device copy or None).  offsets[0..K], see
+    include/lscqp.h, "many missions over one map".  d_offsets: the caller's own device copy (an int64 tensor), kept by the caller."""
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    if off.size < 2:
+        raise ValueError("mission offsets: at least [0, n_total]")
+    d_off = d_offsets
+    if device is not None and d_off is None:
+        import torch
+
+        d_off = torch.from_numpy(off).to(device)
+    return off.size - 1, off, d_off
+
+
 class Grid:
     """lscqp_grid: the grid planner's grid over a WorldMap (include/lscqp.h, "the grid planner / MAPF layer"): occupancy, per-agent
     distance fields, and one replan's PIBT waypoint decision.  2-D.  `handle`: a grid owned by a Plan (not destroyed here)."""
@@ -453,6 +486,47 @@ class Grid:
                                                  _dptr(d_field), _dptr(d_init_d), _dptr(d_waypoint), _dptr(out[0]), _dptr(out[1]), _dptr(out[2]), C.c_void_p(s.cuda_stream)))
         return tuple(out)
 
+    def mission_status(self, n_missions):
+        """lscqp_grid_mission_status: int32 (n_missions,), the word of each mission's waypoint walk."""
+        st = np.zeros(int(n_missions), np.int32)
+        self._check(lib().lscqp_grid_mission_status(self._h, int(n_missions), st.ctypes.data_as(C.c_void_p)))
+        return st
+
+    def fields_missions(self, offsets, d_start_points, d_goal_points, d_field=None, d_init_d=None, stream=None, d_offsets=None):
+        """lscqp_grid_fields_missions_device: `fields` with one occupancy copy per mission of the partition `offsets` (host, [K + 1]).
+        Without d_offsets (the caller's device copy of the offsets) the call makes its own and waits for the stream before it returns."""
+        import torch
+
+        n = d_start_points.numel() // 3
+        K, off, d_off = mission_offsets_arg(offsets, d_start_points.device, d_offsets)
+        if d_field is None:
+            d_field = torch.empty((n, int(self.dims[1]), int(self.dims[0])), dtype=torch.int32, device=d_start_points.device)
+        if d_init_d is None:
+            d_init_d = torch.empty(n, dtype=torch.int32, device=d_start_points.device)
+        s = stream if stream is not None else torch.cuda.current_stream()
+        self._check(lib().lscqp_grid_fields_missions_device(self._h, n, K, off.ctypes.data_as(C.c_void_p), _dptr(d_off), _dptr(d_start_points), _dptr(d_goal_points),
+                                                            _dptr(d_field), _dptr(d_init_d), C.c_void_p(s.cuda_stream)))
+        if d_offsets is None:
+            s.synchronize()  # (d_off is this call's own)
+        return d_field, d_init_d
+
+    def waypoints_missions(self, offsets, communication_range, M, dim, d_state, d_plan, d_current_goal, d_field, d_init_d, d_waypoint, stream=None,
+                           d_offsets=None):
+        """lscqp_waypoints_missions_device: `waypoints` as one decision per mission of the partition `offsets` (host, [K + 1]); d_offsets as
+        for `fields_missions`."""
+        import torch
+
+        n = d_waypoint.numel() // 3
+        K, off, d_off = mission_offsets_arg(offsets, d_waypoint.device, d_offsets)
+        out = [torch.empty(n, dtype=torch.int32, device=d_waypoint.device) for _ in range(3)]
+        s = stream if stream is not None else torch.cuda.current_stream()
+        self._check(lib().lscqp_waypoints_missions_device(self._h, float(communication_range), int(M), int(dim), n, K, off.ctypes.data_as(C.c_void_p), _dptr(d_off),
+                                                          _dptr(d_state), _dptr(d_plan), _dptr(d_current_goal), _dptr(d_field), _dptr(d_init_d), _dptr(d_waypoint),
+                                                          _dptr(out[0]), _dptr(out[1]), _dptr(out[2]), C.c_void_p(s.cuda_stream)))
+        if d_offsets is None:
+            s.synchronize()
+        return tuple(out)
+
 
 def waypoints(grid, communication_range, M, dim, d_state, d_plan, d_current_goal, d_field, d_init_d, d_waypoint, stream=None):
     """lscqp_waypoints_device (see Grid.waypoints)."""
@@ -489,7 +563,7 @@ class Plan:
     def __init__(self, solver, world_map, n_agents, n_obs, agents, n_total=None, first_agent=0, constraint_mode=1, sfc_mode=1,
                  optimize_goal=True, closed_loop=False, time_step=None, z_2d=1.0, safety_samples=0, record_time_step=0.1, tight_warm_start=False,
                  prediction_mode=TRAJ_FROM_PREVIOUS_SOLUTION, initial_traj_mode=TRAJ_FROM_PREVIOUS_SOLUTION, reset_threshold=0.1,
-                 waypoint_mode=WAYPOINT_FROM_CALLER, grid_resolution=0.5):
+                 waypoint_mode=WAYPOINT_FROM_CALLER, grid_resolution=0.5, mission_offsets=None):
         self._p = None
         n_total = n_agents if n_total is None else n_total
         d = PlanDesc()
@@ -515,6 +589,35 @@ class Plan:
         self.waypoint_mode, self.grid_resolution = int(waypoint_mode), float(grid_resolution)
         if self.waypoint_mode == WAYPOINT_GRID_PIBT and float(grid_resolution) != 0.5:
             self._check(lib().lscqp_plan_set_grid(self._p, float(grid_resolution)))
+        if mission_offsets is not None:
+            try:
+                self.set_missions(mission_offsets)
+            except Exception:
+                self.close()  # (a refused partition: the native plan does not wait for __del__)
+                raise
+
+    def set_missions(self, offsets):
+        """lscqp_plan_set_missions: offsets[0..K] cut the agents into K independent missions over the plan's map (None or K <= 1: one
+        mission).  Call it before `reset`."""
+        if offsets is None:
+            self._check(lib().lscqp_plan_set_missions(self._p, 0, None))
+            return
+        K, off, _ = mission_offsets_arg(offsets)
+        self._check(lib().lscqp_plan_set_missions(self._p, K, off.ctypes.data_as(C.c_void_p)))
+
+    def missions(self):
+        """lscqp_plan_missions: the partition's offsets, int64 (K + 1,); [0, n_total] without one."""
+        K = C.c_int32()
+        self._check(lib().lscqp_plan_missions(self._p, C.byref(K), None))
+        off = np.zeros(K.value + 1, np.int64)
+        self._check(lib().lscqp_plan_missions(self._p, C.byref(K), off.ctypes.data_as(C.c_void_p)))
+        return off
+
+    def mission_status(self):
+        """lscqp_plan_mission_status: int32 (K,), 1 where a mission's waypoint walk reached its bound."""
+        st = np.zeros(len(self.missions()) - 1, np.int32)
+        self._check(lib().lscqp_plan_mission_status(self._p, st.ctypes.data_as(C.c_void_p)))
+        return st
 
     def grid(self):
         """The plan's own Grid (waypoint_mode = WAYPOINT_GRID_PIBT), for inspection; owned by the plan."""
@@ -1076,6 +1179,31 @@ class Solver:
                                                   C.c_void_p(d_count.data_ptr()), C.c_void_p(s.cuda_stream))
         if rc != OK:
             raise LscqpError(rc, lib().lscqp_last_error().decode())
+
+    def select_neighbours_missions_device(self, offsets, n_obs, comm_range, d_positions, d_neighbours, d_count, stream=None):
+        """select_neighbours_device with the agent's own mission of the partition `offsets` (host, [K + 1]) as its candidates."""
+        import torch
+
+        s = stream if stream is not None else torch.cuda.current_stream()
+        K, off, d_off = mission_offsets_arg(offsets, d_positions.device)
+        rc = lib().lscqp_select_neighbours_missions_device(self._h, int(off[-1]), K, off.ctypes.data_as(C.c_void_p), _dptr(d_off), int(n_obs), float(comm_range),
+                                                           _dptr(d_positions), _dptr(d_neighbours), _dptr(d_count), C.c_void_p(s.cuda_stream))
+        if rc != OK:
+            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        s.synchronize()  # (d_off is this call's own)
+
+    def safety_metrics_missions_device(self, offsets, n_samples, record_time_step, d_x_all, d_radius, d_downwash, d_hdr, d_out, z_2d=1.0, stream=None):
+        """safety_metrics_device over the pairs within each mission of the partition `offsets` (host, [K + 1])."""
+        import torch
+
+        s = stream if stream is not None else torch.cuda.current_stream()
+        K, off, d_off = mission_offsets_arg(offsets, d_x_all.device)
+        rc = lib().lscqp_safety_metrics_missions_device(self._h, int(off[-1]), K, off.ctypes.data_as(C.c_void_p), _dptr(d_off), int(n_samples), float(record_time_step),
+                                                        float(z_2d), _dptr(d_x_all), _dptr(d_radius), _dptr(d_downwash), _dptr(d_hdr), _dptr(d_out),
+                                                        C.c_void_p(s.cuda_stream))
+        if rc != OK:
+            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        s.synchronize()
 
     def shift_traj_device(self, n, d_x_prev, d_traj, z_2d=1.0, shift=1, stream=None):
         """initialTrajPlanningPrevSol: solver output [n][dim*M*6] -> initial trajectories [n][M][6][3] (float32 values)."""

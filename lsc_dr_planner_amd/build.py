@@ -52,7 +52,7 @@ def _run(cmd):
 
 def build(force=False, verbose=False, jobs=None):
     os.makedirs(OBJ, exist_ok=True)
-    hdrs = [os.path.join(CSRC, f) for f in ("lscqp_kernel.hpp", "lscqp_launch.hpp", "lscqp_staging.hpp")] + [
+    hdrs = [os.path.join(CSRC, f) for f in ("lscqp_kernel.hpp", "lscqp_launch.hpp", "lscqp_staging.hpp", "lscqp_missions.hpp")] + [
         os.path.join(HERE, "..", "include", "lscqp.h"), os.path.abspath(__file__)]
     tasks = []
     objs = []

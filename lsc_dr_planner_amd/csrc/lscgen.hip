@@ -19,6 +19,7 @@
 #include <string>
 
 #include "../../include/lscqp.h"
+#include "lscqp_missions.hpp"
 
 namespace lscgen {
 
@@ -620,13 +621,22 @@ __global__ __launch_bounds__(kThreads) void generate_lsc_obstacle_kernel(int M, 
 // wavefront per local agent: the lanes test 64 candidates at a time, and a ballot + prefix population count compacts the
 // accepted ids in order.  The row buffers have room for n_obs neighbours per agent; when more are in range the n_obs
 // nearest are kept (L-infinity distance, then id; still listed in id order) and count_out tells the caller.
+// MIS: the agents are partitioned into missions off[0..K] (include/lscqp.h, "many missions over one map") and the candidates of an agent
+// are the agents [m_lo, m_hi) of its own mission instead of [0, n_total); ids stay global.
+template <bool MIS>
 __global__ __launch_bounds__(64) void select_neighbours_kernel(int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_obs,
                                                                double range, const double* __restrict__ pos,
-                                                               int32_t* __restrict__ nbr, int32_t* __restrict__ count) {
+                                                               int32_t* __restrict__ nbr, int32_t* __restrict__ count,
+                                                               const int64_t* __restrict__ off, int K) {
     const int64_t a = blockIdx.x;
     if (a >= n_agents) return;
     const int lane = threadIdx.x;
     const int64_t gi = first_agent + a;
+    int64_t m_lo = 0, m_hi = n_total;  // the candidates: [m_lo, m_hi)
+    if (MIS) {
+        const int k = lscqp_missions::mission_of(off, K, gi);
+        m_lo = off[k], m_hi = off[k + 1];
+    }
     // positions are point3d (float) in the reference; LInfinityDistance widens the float differences (include/util.hpp:122-131)
     const float px = (float)pos[3 * gi], py = (float)pos[3 * gi + 1], pz = (float)pos[3 * gi + 2];
     auto dist_of = [&](int64_t j) -> double {
@@ -634,16 +644,16 @@ __global__ __launch_bounds__(64) void select_neighbours_kernel(int64_t n_agents,
         return fmax(fmax(fabs((double)dx), fabs((double)dy)), fabs((double)dz));
     };
     auto in_range = [&](int64_t j, double limit) -> bool {
-        return j < n_total && j != gi && !(range > 0 && dist_of(j) > limit);
+        return j < m_hi && j != gi && !(range > 0 && dist_of(j) > limit);
     };
     // pass 1: count the agents in range and keep them (distance, id; id order) in LDS while they fit
     constexpr int kCap = 1024;
     __shared__ double cand_d[kCap];
     __shared__ int32_t cand_j[kCap];
     int total = 0;
-    for (int64_t base = 0; base < n_total; base += 64) {
+    for (int64_t base = m_lo; base < m_hi; base += 64) {
         const int64_t j = base + lane;
-        const bool valid = j < n_total && j != gi;
+        const bool valid = j < m_hi && j != gi;
         const double d = valid ? dist_of(j) : 0.0;
         const bool in = valid && !(range > 0 && d > range);
         const unsigned long long m = __ballot(in);
@@ -690,9 +700,9 @@ __global__ __launch_bounds__(64) void select_neighbours_kernel(int64_t n_agents,
         double lo = 0, hi = range > 0 ? range : 3.0e38;
         if (!(range > 0)) {
             double mx = 0;
-            for (int64_t base = 0; base < n_total; base += 64) {
+            for (int64_t base = m_lo; base < m_hi; base += 64) {
                 const int64_t j = base + lane;
-                double d = (j < n_total && j != gi) ? dist_of(j) : 0.0;
+                double d = (j < m_hi && j != gi) ? dist_of(j) : 0.0;
                 for (int o = 32; o > 0; o >>= 1) d = fmax(d, __shfl_xor(d, o));
                 mx = fmax(mx, d);
             }
@@ -702,9 +712,9 @@ __global__ __launch_bounds__(64) void select_neighbours_kernel(int64_t n_agents,
             const double mid = 0.5 * (lo + hi);
             if (mid <= lo || mid >= hi) break;
             int c = 0;
-            for (int64_t base = 0; base < n_total; base += 64) {
+            for (int64_t base = m_lo; base < m_hi; base += 64) {
                 const int64_t j = base + lane;
-                c += __popcll(__ballot(j < n_total && j != gi && dist_of(j) <= mid));
+                c += __popcll(__ballot(j < m_hi && j != gi && dist_of(j) <= mid));
             }
             if (c >= n_obs)
                 hi = mid;
@@ -712,20 +722,20 @@ __global__ __launch_bounds__(64) void select_neighbours_kernel(int64_t n_agents,
                 lo = mid;
         }
         limit = hi;  // smallest distance value with at least n_obs agents at or below it
-        for (int64_t base = 0; base < n_total; base += 64) {
+        for (int64_t base = m_lo; base < m_hi; base += 64) {
             const int64_t j = base + lane;
-            n_strict += __popcll(__ballot(j < n_total && j != gi && dist_of(j) < limit));
+            n_strict += __popcll(__ballot(j < m_hi && j != gi && dist_of(j) < limit));
         }
         capped = true;
     }
     int written = 0, ties_left = capped ? n_obs - n_strict : 0;
-    for (int64_t base = 0; base < n_total && written < n_obs; base += 64) {
+    for (int64_t base = m_lo; base < m_hi && written < n_obs; base += 64) {
         const int64_t j = base + lane;
         bool take;
         if (!capped) {
             take = in_range(j, range);
         } else {
-            const bool valid = j < n_total && j != gi;
+            const bool valid = j < m_hi && j != gi;
             const double d = valid ? dist_of(j) : 0.0;
             const bool tie = valid && d == limit;
             const unsigned long long tm = __ballot(tie);
@@ -751,8 +761,18 @@ extern "C" int lscqp_set_error_(int code, const char* msg);  // lscqp_api.hip
 extern "C" int lscqp_select_neighbours_raw_(int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_obs, double range,
                                             const double* d_pos, int32_t* d_nbr, int32_t* d_count, void* stream) {
     if (n_agents == 0) return LSCQP_OK;
-    hipLaunchKernelGGL(lscgen::select_neighbours_kernel, dim3((unsigned)n_agents), dim3(64), 0, (hipStream_t)stream, n_agents, first_agent,
-                       n_total, n_obs, range, d_pos, d_nbr, d_count);
+    hipLaunchKernelGGL(lscgen::select_neighbours_kernel<false>, dim3((unsigned)n_agents), dim3(64), 0, (hipStream_t)stream, n_agents, first_agent,
+                       n_total, n_obs, range, d_pos, d_nbr, d_count, (const int64_t*)nullptr, 0);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
+    return LSCQP_OK;
+}
+
+extern "C" int lscqp_select_neighbours_missions_raw_(int64_t n_total, int32_t n_missions, const int64_t* d_off, int32_t n_obs, double range,
+                                                     const double* d_pos, int32_t* d_nbr, int32_t* d_count, void* stream) {
+    if (n_total == 0) return LSCQP_OK;
+    hipLaunchKernelGGL(lscgen::select_neighbours_kernel<true>, dim3((unsigned)n_total), dim3(64), 0, (hipStream_t)stream, n_total, (int64_t)0, n_total,
+                       n_obs, range, d_pos, d_nbr, d_count, d_off, (int)n_missions);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
     return LSCQP_OK;

@@ -11,20 +11,27 @@
 //   waypoints   one replan's decision: candidates gathered by all lanes, then ONE workgroup: groups by min-label propagation, agents ordered by
 //               priority, the PIBT walk (sequential by nature: priority inheritance and backtracking) by one wavefront with an explicit
 //               stack, and the simulator's update filter by all lanes again
+// A MISSION PARTITION (include/lscqp.h, "many missions over one map") cuts the agents into contiguous slices that share the map and nothing
+// else: one occupancy copy per mission (start and goal nodes are cleared in the agent's own copy only), and the decision as one workgroup per
+// mission over its slice, with node tables, order, stack, fail flag and walk bound of its own.
 // Everything here is integers and exact grid points, and the float32 / double arithmetic of the reference where a comparison is made.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
+#include <vector>
 
 #include "../../include/lscqp.h"
+#include "lscqp_missions.hpp"
 
 extern "C" int lscqp_set_error_(int code, const char* msg);
 extern "C" int lscqp_map_raw_(lscqp_map mp, double* res, float* world_min, float* world_max, int* key0, int* dims, const int32_t** d_nearest, int* device);
 
 namespace lscgrid {
 
+using lscqp_missions::mission_of;
 constexpr int kUnreach = LSCQP_GRID_UNREACHABLE;
 constexpr int kBlocked = kUnreach + 1;    // an occupied node while a field is relaxed in HBM (written out as kUnreach)
 constexpr unsigned kUnreach16 = 0xFFFEu;  // the same pair where the field is relaxed in LDS (16 bits per node)
@@ -95,11 +102,20 @@ __global__ __launch_bounds__(256) void occupancy_kernel(View g, MapRaw m, double
     occ[id] = dist < radius - kEpsFloat ? 1 : 0;
 }
 
-// updateGridMission (:255-283), once per mission instead of once per group and replan (include/lscqp.h): start and goal nodes are free
+// one copy of the base occupancy per mission
+__global__ __launch_bounds__(256) void spread_occupancy_kernel(int nodes, int K, const uint8_t* __restrict__ base, uint8_t* __restrict__ copies) {
+    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (id >= (int64_t)nodes * K) return;
+    copies[id] = base[id % nodes];
+}
+
+// updateGridMission (:255-283), once per mission instead of once per group and replan (include/lscqp.h): start and goal nodes are free.
+// off != NULL: occ holds one copy per mission of the partition and an agent clears its nodes in the copy of its own mission only
 __global__ __launch_bounds__(256) void clear_nodes_kernel(View g, int64_t n, const double* __restrict__ start, const double* __restrict__ goal,
-                                                          uint8_t* occ) {
+                                                          uint8_t* occ, const int64_t* __restrict__ off, int K) {
     const int64_t a = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (a >= n) return;
+    if (off) occ += (int64_t)mission_of(off, K, a) * g.W * g.H;
     occ[point_node(g, start + a * 3)] = 0;
     occ[point_node(g, goal + a * 3)] = 0;
 }
@@ -110,10 +126,12 @@ __global__ __launch_bounds__(256) void clear_nodes_kernel(View g, int64_t n, con
 // fall, and a sweep in which nothing changed saw constant values -- the fixed point, which is the BFS distance.
 template <bool LDS>
 __global__ __launch_bounds__(1024) void fields_kernel(View g, const uint8_t* __restrict__ occ, const double* __restrict__ start,
-                                                      const double* __restrict__ goal, int32_t* field, int32_t* __restrict__ init_d) {
+                                                      const double* __restrict__ goal, int32_t* field, int32_t* __restrict__ init_d,
+                                                      const int64_t* __restrict__ off, int K) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int64_t a = blockIdx.x;
     const int T = blockDim.x, tid = threadIdx.x, W = g.W, H = g.H, nodes = W * H;
+    if (off) occ += (int64_t)mission_of(off, K, a) * nodes;  // (the copy of the agent's mission)
     const int gnode = point_node(g, goal + a * 3), snode = point_node(g, start + a * 3);
     int32_t* out = field + a * (int64_t)nodes;
     if (LDS) {
@@ -192,12 +210,21 @@ __device__ __forceinline__ void stv(int32_t* p, int v) { __hip_atomic_store(p, v
 
 // every lane: an agent's PIBT node (the node of its present WAYPOINT, multi_sync_simulator.cpp:205), its five candidates in the identity
 // order left, right, up, down, stay with their distances to the agent's goal, and the start of the group labels
+// MIS: the agents are partitioned into missions off[0..K]; occ holds one copy per mission and the labels are local to the mission's slice
+template <bool MIS>
 __global__ __launch_bounds__(256) void gather_kernel(View g, int64_t n, double range, const uint8_t* __restrict__ occ,
-                                                     const double* __restrict__ waypoint, const int32_t* __restrict__ field, Scratch s) {
+                                                     const double* __restrict__ waypoint, const int32_t* __restrict__ field, Scratch s,
+                                                     const int64_t* __restrict__ off, int K) {
 #pragma clang fp contract(off)
     const int64_t a = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (a >= n) return;
     const int W = g.W, H = g.H;
+    int64_t base = 0;
+    if (MIS) {
+        const int k = mission_of(off, K, a);
+        base = off[k];
+        occ += (int64_t)k * W * H;
+    }
     const float wx = (float)waypoint[a * 3 + 0], wy = (float)waypoint[a * 3 + 1], wz = (float)waypoint[a * 3 + 2];
     const int cx = coord_node(wx, g.gmin0, g.res, W), cy = coord_node(wy, g.gmin1, g.res, H);
     const int cur = cy * W + cx;
@@ -220,7 +247,7 @@ __global__ __launch_bounds__(256) void gather_kernel(View g, int64_t n, double r
     s.vnext[a] = -1;
     s.blocker[a] = -1;
     s.gsize[a] = 0;
-    s.label[a] = range < 0 ? 0 : (int)a;
+    s.label[a] = range < 0 ? 0 : (int)(a - base);
 }
 
 // PIBT::chooseNode for an agent nobody else can see (a group of one): the goal if it is a candidate, else the first candidate of the least
@@ -236,14 +263,33 @@ __device__ __forceinline__ int choose_alone(const Scratch& s, int64_t a) {
     return v;
 }
 
+// MIS: one workgroup per mission of the partition off[0..gridDim.x].  The workgroup sees its slice as a swarm of its own: every per-agent
+// array is entered at the slice's first agent and agent ids are LOCAL to the slice from here on (labels, order, stack, the ids in the node
+// tables; tie_breaker = id / n orders a contiguous slice the same either way), the node tables are the workgroup's own (LDS, or the
+// mission's slab of the HBM tables) and so are the fail flag, the walk bound and the status word.  Only group_out speaks global ids.
+template <bool MIS>
 __global__ __launch_bounds__(kDecideThreads) void decide_kernel(View g, int64_t n64, double range, int M, int dim, int tables_in_lds,
                                                                 const double* __restrict__ state, const double* __restrict__ plan,
                                                                 const double* __restrict__ cur_goal, const int32_t* __restrict__ init_d,
                                                                 double* waypoint, Scratch s, int32_t* __restrict__ group_out,
-                                                                int32_t* __restrict__ desired_out, int32_t* __restrict__ updated_out) {
+                                                                int32_t* __restrict__ desired_out, int32_t* __restrict__ updated_out,
+                                                                const int64_t* __restrict__ off) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int n_multi_sh, fail_sh;
+    int64_t base = 0;
+    if (MIS) {
+        const int64_t k = blockIdx.x;
+        base = off[k];
+        n64 = off[k + 1] - base;
+        state += base * 9, cur_goal += base * 3, init_d += base, waypoint += base * 3;
+        if (plan != nullptr) plan += base * dim * M * 6;
+        group_out += base, desired_out += base, updated_out += base;
+        s.cur += base, s.vnext += base, s.order += base, s.stack += base, s.label += base, s.blocker += base, s.keep += base, s.onnode += base;
+        s.gsize += base, s.cand += base * 5, s.cost += base * 5;
+        s.now += k * 2 * (int64_t)g.W * g.H, s.next += k * 2 * (int64_t)g.W * g.H;
+        s.status += k;
+    }
     const int n = (int)n64, tid = threadIdx.x, T = kDecideThreads, nodes = g.W * g.H;
     int32_t *now = s.now, *next = s.next;
     if (tables_in_lds) {
@@ -429,7 +475,7 @@ __global__ __launch_bounds__(kDecideThreads) void decide_kernel(View g, int64_t 
         }
         stv(s.keep + a, (in_range && sqrt((double)nw) > kEpsFloat && sqrt((double)ng) < kEpsFloat) ? 1 : 0);
         desired_out[a] = d;
-        group_out[a] = ldv(s.label + a);
+        group_out[a] = (int)base + ldv(s.label + a);
     }
     __syncthreads();
     // (d) "find valid update" (:266-296): a candidate whose desired node is the present waypoint of a group member that is not (or no longer) a
@@ -473,6 +519,13 @@ struct lscqp_grid_s {
     int32_t* d_agent_scratch = nullptr;  // 11 arrays, the candidate ones five wide
     int32_t* d_tables = nullptr;         // now, next, status
     lscgrid::Scratch s;
+    // a mission partition (lscqp_grid_reserve_missions_): one occupancy copy and one status word per mission, and where the node tables do
+    // not fit in LDS one slab of them per mission
+    int missions = 0;
+    uint8_t* d_occ_k = nullptr;     // [missions][nodes]
+    int32_t* d_status_k = nullptr;  // [missions]
+    int32_t* d_tables_k = nullptr;  // [missions][2][nodes], all zero between launches
+    std::vector<int64_t> fields_off;  // the partition of the last lscqp_grid_fields_missions_device: the one the copies were cleared for
 };
 
 namespace {
@@ -488,7 +541,13 @@ int grid_hip_fail(hipError_t e, const char* what) {
 
 constexpr int64_t kPerAgentInts = 9 + 2 * 5;  // cur, vnext, order, stack, label, blocker, keep, onnode, gsize + cand[5], cost[5]
 
+bool tables_fit_lds(const lscqp_grid_s* g) {
+    return (size_t)2 * g->dims[0] * g->dims[1] * sizeof(int32_t) <= (size_t)lscgrid::kTableLdsBytes;
+}
+
 }  // namespace
+
+extern "C" int lscqp_check_missions_(int64_t n_total, int32_t n_missions, const int64_t* mission_offsets);  // lscqp_api.hip
 
 extern "C" {
 
@@ -565,7 +624,7 @@ void lscqp_grid_destroy(lscqp_grid g) {
     int prev = -1;
     if (hipGetDevice(&prev) == hipSuccess && prev != g->device) (void)hipSetDevice(g->device);
     (void)hipDeviceSynchronize();
-    for (void* p : {(void*)g->d_occ, (void*)g->d_occ_mission, (void*)g->d_agent_scratch, (void*)g->d_tables})
+    for (void* p : {(void*)g->d_occ, (void*)g->d_occ_mission, (void*)g->d_agent_scratch, (void*)g->d_tables, (void*)g->d_occ_k, (void*)g->d_status_k, (void*)g->d_tables_k})
         if (p) (void)hipFree(p);
     if (prev >= 0 && prev != g->device) (void)hipSetDevice(prev);
     delete g;
@@ -625,14 +684,17 @@ int lscqp_grid_fields_device(lscqp_grid g, int64_t n, const double* d_start_poin
     const int W = g->dims[0], H = g->dims[1], nodes = W * H;
     GRID_HIP(hipMemcpyAsync(g->d_occ_mission, g->d_occ, (size_t)nodes, hipMemcpyDeviceToDevice, st));
     GRID_HIP(hipMemsetAsync(g->d_tables + (size_t)2 * nodes, 0, 4 * sizeof(int32_t), st));  // a new mission: the status word starts at 0
-    hipLaunchKernelGGL(lscgrid::clear_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, d_start_points, d_goal_points, g->d_occ_mission);
+    hipLaunchKernelGGL(lscgrid::clear_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, d_start_points, d_goal_points, g->d_occ_mission,
+                       (const int64_t*)nullptr, 0);
     const int64_t padded = (int64_t)(W + 2) * (H + 2);
     if (padded <= lscgrid::kLdsNodes) {
         const int threads = padded <= 2048 ? 256 : 1024;
         const size_t lds = (size_t)((padded * 2 + 15) / 16 * 16);
-        hipLaunchKernelGGL(lscgrid::fields_kernel<true>, dim3((unsigned)n), dim3(threads), lds, st, g->v, g->d_occ_mission, d_start_points, d_goal_points, d_field, d_init_d);
+        hipLaunchKernelGGL(lscgrid::fields_kernel<true>, dim3((unsigned)n), dim3(threads), lds, st, g->v, g->d_occ_mission, d_start_points, d_goal_points, d_field, d_init_d,
+                           (const int64_t*)nullptr, 0);
     } else {
-        hipLaunchKernelGGL(lscgrid::fields_kernel<false>, dim3((unsigned)n), dim3(1024), 0, st, g->v, g->d_occ_mission, d_start_points, d_goal_points, d_field, d_init_d);
+        hipLaunchKernelGGL(lscgrid::fields_kernel<false>, dim3((unsigned)n), dim3(1024), 0, st, g->v, g->d_occ_mission, d_start_points, d_goal_points, d_field, d_init_d,
+                           (const int64_t*)nullptr, 0);
     }
     GRID_HIP(hipGetLastError());
     return LSCQP_OK;
@@ -653,11 +715,115 @@ int lscqp_waypoints_device(lscqp_grid g, double communication_range, int32_t M, 
     }
     hipStream_t st = (hipStream_t)stream;
     const int nodes = g->dims[0] * g->dims[1];
-    hipLaunchKernelGGL(lscgrid::gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, communication_range, g->d_occ_mission, d_waypoint, d_field, g->s);
+    hipLaunchKernelGGL(lscgrid::gather_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, communication_range, g->d_occ_mission, d_waypoint, d_field, g->s,
+                       (const int64_t*)nullptr, 0);
     const size_t table_bytes = (size_t)2 * nodes * sizeof(int32_t);
     const int in_lds = table_bytes <= (size_t)lscgrid::kTableLdsBytes;
-    hipLaunchKernelGGL(lscgrid::decide_kernel, dim3(1), dim3(lscgrid::kDecideThreads), in_lds ? (table_bytes + 15) / 16 * 16 : 0, st, g->v, n, communication_range,
-                       (int)M, (int)dim, in_lds, d_state, d_plan, d_current_goal, d_init_d, d_waypoint, g->s, d_group_out, d_desired_out, d_updated_out);
+    hipLaunchKernelGGL(lscgrid::decide_kernel<false>, dim3(1), dim3(lscgrid::kDecideThreads), in_lds ? (table_bytes + 15) / 16 * 16 : 0, st, g->v, n, communication_range,
+                       (int)M, (int)dim, in_lds, d_state, d_plan, d_current_goal, d_init_d, d_waypoint, g->s, d_group_out, d_desired_out, d_updated_out,
+                       (const int64_t*)nullptr);
+    GRID_HIP(hipGetLastError());
+    return LSCQP_OK;
+}
+
+// (library-internal, also lscplan.hip) work arrays for n agents in n_missions missions; grows on demand, which synchronises and allocates
+int lscqp_grid_reserve_missions_(lscqp_grid g, int64_t n, int32_t n_missions) {
+    if (!g || n < 0 || n_missions < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
+    const int rc = lscqp_grid_reserve(g, n);
+    if (rc != LSCQP_OK) return rc;
+    if (n_missions <= g->missions) return LSCQP_OK;
+    const size_t nodes = (size_t)g->dims[0] * g->dims[1], K = (size_t)n_missions;
+    GRID_HIP(hipDeviceSynchronize());
+    for (void** p : {(void**)&g->d_occ_k, (void**)&g->d_status_k, (void**)&g->d_tables_k}) {
+        if (*p) GRID_HIP(hipFree(*p));
+        *p = nullptr;
+    }
+    g->missions = 0;
+    g->fields_off.clear();  // (the copies are gone)
+    GRID_HIP(hipMalloc((void**)&g->d_occ_k, K * nodes));
+    GRID_HIP(hipMalloc((void**)&g->d_status_k, K * sizeof(int32_t)));
+    GRID_HIP(hipMemset(g->d_status_k, 0, K * sizeof(int32_t)));
+    if (!tables_fit_lds(g)) {
+        GRID_HIP(hipMalloc((void**)&g->d_tables_k, K * 2 * nodes * sizeof(int32_t)));
+        GRID_HIP(hipMemset(g->d_tables_k, 0, K * 2 * nodes * sizeof(int32_t)));
+    }
+    g->missions = n_missions;
+    return LSCQP_OK;
+}
+
+int lscqp_grid_mission_status(lscqp_grid g, int32_t n_missions, int32_t* status_out) {
+    if (!g || !status_out || n_missions < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (n_missions > g->missions) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the grid has seen no partition of that many missions");
+    GRID_HIP(hipMemcpy(status_out, g->d_status_k, (size_t)n_missions * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return LSCQP_OK;
+}
+
+int lscqp_grid_fields_missions_device(lscqp_grid g, int64_t n, int32_t n_missions, const int64_t* mission_offsets, const int64_t* d_mission_offsets,
+                                      const double* d_start_points, const double* d_goal_points, int32_t* d_field, int32_t* d_init_d, void* stream) {
+    if (!g || n < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
+    {
+        const int rc = lscqp_check_missions_(n, n_missions, mission_offsets);
+        if (rc != LSCQP_OK) return rc;
+    }
+    if (!d_mission_offsets || !d_start_points || !d_goal_points || !d_field || !d_init_d) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (n_missions > g->missions || n > g->reserved) {  // (synchronises and allocates)
+        const int rc = lscqp_grid_reserve_missions_(g, n, n_missions);
+        if (rc != LSCQP_OK) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int W = g->dims[0], H = g->dims[1], nodes = W * H, K = n_missions;
+    g->fields_off.assign(mission_offsets, mission_offsets + K + 1);
+    hipLaunchKernelGGL(lscgrid::spread_occupancy_kernel, dim3((unsigned)(((int64_t)nodes * K + 255) / 256)), dim3(256), 0, st, nodes, K, g->d_occ, g->d_occ_k);
+    GRID_HIP(hipMemsetAsync(g->d_status_k, 0, (size_t)K * sizeof(int32_t), st));  // new missions: their status words start at 0
+    hipLaunchKernelGGL(lscgrid::clear_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, d_start_points, d_goal_points, g->d_occ_k,
+                       d_mission_offsets, K);
+    const int64_t padded = (int64_t)(W + 2) * (H + 2);
+    if (padded <= lscgrid::kLdsNodes) {
+        const int threads = padded <= 2048 ? 256 : 1024;
+        const size_t lds = (size_t)((padded * 2 + 15) / 16 * 16);
+        hipLaunchKernelGGL(lscgrid::fields_kernel<true>, dim3((unsigned)n), dim3(threads), lds, st, g->v, g->d_occ_k, d_start_points, d_goal_points, d_field, d_init_d,
+                           d_mission_offsets, K);
+    } else {
+        hipLaunchKernelGGL(lscgrid::fields_kernel<false>, dim3((unsigned)n), dim3(1024), 0, st, g->v, g->d_occ_k, d_start_points, d_goal_points, d_field, d_init_d,
+                           d_mission_offsets, K);
+    }
+    GRID_HIP(hipGetLastError());
+    return LSCQP_OK;
+}
+
+int lscqp_waypoints_missions_device(lscqp_grid g, double communication_range, int32_t M, int32_t dim, int64_t n, int32_t n_missions,
+                                    const int64_t* mission_offsets, const int64_t* d_mission_offsets, const double* d_state, const double* d_plan,
+                                    const double* d_current_goal, const int32_t* d_field, const int32_t* d_init_d, double* d_waypoint,
+                                    int32_t* d_group_out, int32_t* d_desired_out, int32_t* d_updated_out, void* stream) {
+    if (!g || n < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
+    {
+        const int rc = lscqp_check_missions_(n, n_missions, mission_offsets);
+        if (rc != LSCQP_OK) return rc;
+    }
+    if (!d_mission_offsets || !d_state || !d_current_goal || !d_field || !d_init_d || !d_waypoint || !d_group_out || !d_desired_out || !d_updated_out)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (dim != 2) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_waypoints_missions_device is 2-D only");
+    if (d_plan && M < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "M must be positive");
+    if (!(communication_range == communication_range)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "communication_range is NaN");
+    // (the occupancy copies are lscqp_grid_fields_missions_device's, cleared for the agents of ITS partition)
+    if (g->fields_off.size() != (size_t)n_missions + 1 || !std::equal(g->fields_off.begin(), g->fields_off.end(), mission_offsets))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_grid_fields_missions_device over this same partition must come first");
+    if (n > g->reserved) {  // (synchronises and allocates)
+        const int rc = lscqp_grid_reserve(g, n);
+        if (rc != LSCQP_OK) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int nodes = g->dims[0] * g->dims[1], K = n_missions;
+    hipLaunchKernelGGL(lscgrid::gather_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, communication_range, g->d_occ_k, d_waypoint, d_field, g->s,
+                       d_mission_offsets, K);
+    const size_t table_bytes = (size_t)2 * nodes * sizeof(int32_t);
+    const int in_lds = tables_fit_lds(g);
+    lscgrid::Scratch s = g->s;
+    if (!in_lds) s.now = g->d_tables_k, s.next = g->d_tables_k + nodes;
+    s.status = g->d_status_k;
+    hipLaunchKernelGGL(lscgrid::decide_kernel<true>, dim3((unsigned)K), dim3(lscgrid::kDecideThreads), in_lds ? (table_bytes + 15) / 16 * 16 : 0, st, g->v, n,
+                       communication_range, (int)M, (int)dim, in_lds, d_state, d_plan, d_current_goal, d_init_d, d_waypoint, s, d_group_out, d_desired_out,
+                       d_updated_out, d_mission_offsets);
     GRID_HIP(hipGetLastError());
     return LSCQP_OK;
 }

@@ -16,6 +16,9 @@
 // ten kernel launches per replan.  The waypoints of the grid planner / MAPF layer are either written into the plan's waypoint buffer by
 // the caller before each step (waypoint_mode 0) or decided at the head of the chain by lscqp_waypoints_device (waypoint_mode 1, lscgrid.hip):
 //   MultiSyncSimulator::decentralizedMAPP               -> lscqp_waypoints_device over the state, plans and goal points of the last replan
+// A plan with a mission partition (lscqp_plan_set_missions) flies many independent missions over one map in the same chain: the three
+// steps in which agents see each other -- the waypoint decision, the range filter, the safety figures -- run as their mission-aware twins,
+// every other step is per agent and does not know.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -35,6 +38,8 @@ extern "C" int lscqp_commit_validate_raw_(int M, int dim, int use_sfc, double dt
 extern "C" int lscqp_optimize_goal_fin_device_(lscqp_handle h, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows, const uint64_t* d_row_offsets,
                                                const lscqp_box* d_sfc, int32_t* d_status_out, double fin_dt, void* stream);
 extern "C" uint64_t lscqp_map_generation_(lscqp_map mp);
+extern "C" int lscqp_check_missions_(int64_t n_total, int32_t n_missions, const int64_t* mission_offsets);
+extern "C" int lscqp_grid_reserve_missions_(lscqp_grid g, int64_t n, int32_t n_missions);
 extern "C" int lscqp_generate_constraints_own_(lscqp_handle h, int32_t mode, int64_t n_agents, int32_t n_obs, int64_t first_agent,
                                                const double* d_traj, const double* d_own_traj, const int32_t* d_neighbours, const double* d_radius,
                                                const double* d_downwash, const double* d_goal_all, lscqp_row* d_rows_out, int32_t n_obs_total,
@@ -219,6 +224,11 @@ struct lscqp_plan_s {
     int32_t *field = nullptr, *init_d = nullptr, *desired_node = nullptr;
     double* start_pts = nullptr;
     bool fields_valid = false;
+    // a mission partition (lscqp_plan_set_missions): empty = one mission, the chain as it always was
+    std::vector<int64_t> moff;  // [K + 1]
+    int64_t* d_moff = nullptr;
+    bool missions_pending = false;  // the partition changed and lscqp_plan_reset has not come yet
+    int n_missions() const { return moff.empty() ? 1 : (int)moff.size() - 1; }
 };
 
 namespace {
@@ -277,12 +287,19 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     double* obj = (double*)p->buf[LSCQP_PLAN_BUF_OBJECTIVE];
     lscqp_info* info = (lscqp_info*)p->buf[LSCQP_PLAN_BUF_INFO];
     const double fraction = p->d.time_step / s.dt;
+    const int K = p->n_missions();
+    if (p->missions_pending) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_missions: lscqp_plan_reset must come before the next step");
     // decentralizedMAPP precedes the planning loop (src/multi_sync_simulator.cpp:101-120): the waypoints of this replan, from the plans as the
     // last replan left them (AgentManager::getTraj is desired_traj, un-shifted)
     if (p->grid) {
         if (!p->fields_valid) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: lscqp_plan_reset must come before the first step");
-        PLAN_TRY(lscqp_waypoints_device(p->grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, state, x_plan, goal, p->field, p->init_d,
-                                        waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], p->desired_node, (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
+        if (K > 1)
+            PLAN_TRY(lscqp_waypoints_missions_device(p->grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, K, p->moff.data(), p->d_moff,
+                                                     state, x_plan, goal, p->field, p->init_d, waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], p->desired_node,
+                                                     (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
+        else
+            PLAN_TRY(lscqp_waypoints_device(p->grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, state, x_plan, goal, p->field, p->init_d,
+                                            waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], p->desired_node, (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
     }
     // obstaclePredictionWithPrevSol / initialTrajPlanningPrevSol for every agent of the mission (:273-310, 399-423)
     const bool from_plans = !first_replan && (s.prediction_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION || s.initial_traj_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION);
@@ -300,8 +317,12 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
         PLAN_TRY(lscqp_construct_sfc_device_ordered(h, p->map, first_replan ? LSCQP_SFC_INIT : p->d.sfc_mode, s.n_agents, p->points,
                                                     p->radius + s.first_agent, sfc, sfc_status, sfc_order, p->sfc_cost, stream));
     }
-    PLAN_TRY(lscqp_select_neighbours_device(h, s.n_agents, s.first_agent, s.n_total, s.n_obs, lscqp_class_desc_of_(h)->communication_range, p->pos, p->nbr, count,
-                                            stream));
+    if (K > 1)
+        PLAN_TRY(lscqp_select_neighbours_missions_device(h, s.n_total, K, p->moff.data(), p->d_moff, s.n_obs, lscqp_class_desc_of_(h)->communication_range, p->pos,
+                                                         p->nbr, count, stream));
+    else
+        PLAN_TRY(lscqp_select_neighbours_device(h, s.n_agents, s.first_agent, s.n_total, s.n_obs, lscqp_class_desc_of_(h)->communication_range, p->pos, p->nbr, count,
+                                                stream));
     if (s.n_obs > 0)
         PLAN_TRY(lscqp_generate_constraints_own_(h, p->d.constraint_mode, s.n_agents, s.n_obs, s.first_agent, p->traj, p->own, p->nbr, p->radius,
                                                  p->downwash, goal, rows, s.n_obs, 0, stream));
@@ -329,7 +350,10 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
         PLAN_TRY(lscqp_commit_validate_raw_(s.M, s.dim, cd->use_sfc, s.dt, s.n_agents, p->d.time_step, s.z_2d, status, p->x_new, p->x_init,
                                             x_plan + s.first_agent * s.nv, goal + s.first_agent * 3, hdr, p->map ? sfc : nullptr, valid, state_out, stream));
     }
-    if (p->d.safety_samples > 0)  // MultiSyncSimulator::update's safety ratio / excess ratios over the step just planned (:486-577)
+    if (p->d.safety_samples > 0 && K > 1)
+        PLAN_TRY(lscqp_safety_metrics_missions_device(h, s.n_total, K, p->moff.data(), p->d_moff, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan,
+                                                      p->radius, p->downwash, hdr, (lscqp_safety*)p->buf[LSCQP_PLAN_BUF_SAFETY], stream));
+    else if (p->d.safety_samples > 0)  // MultiSyncSimulator::update's safety ratio / excess ratios over the step just planned (:486-577)
         PLAN_TRY(lscqp_safety_metrics_device(h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan,
                                              p->radius, p->downwash, hdr, (lscqp_safety*)p->buf[LSCQP_PLAN_BUF_SAFETY], stream));
     // (closed loop: LSCQP_PLAN_BUF_NEXT_STATE is the local agents' slice of the state buffer itself, so doStep's result is the next
@@ -358,7 +382,8 @@ int make_grid(lscqp_plan_s* p, double resolution) {
     lscqp_grid_info(gnew, gmin, dims);
     void* f = nullptr;
     const hipError_t e = hipMalloc(&f, (size_t)p->s.n_total * dims[0] * dims[1] * sizeof(int32_t));
-    int rc = e == hipSuccess ? lscqp_grid_reserve(gnew, p->s.n_total) : hip_fail(e, "hipMalloc(distance fields)");
+    int rc = e != hipSuccess ? hip_fail(e, "hipMalloc(distance fields)")
+                             : (p->n_missions() > 1 ? lscqp_grid_reserve_missions_(gnew, p->s.n_total, p->n_missions()) : lscqp_grid_reserve(gnew, p->s.n_total));
     if (rc != LSCQP_OK) {
         if (f) (void)hipFree(f);
         lscqp_grid_destroy(gnew);
@@ -375,7 +400,11 @@ int make_grid(lscqp_plan_s* p, double resolution) {
 
 // updateGridMission + createDistanceTable for the whole mission (include/lscqp.h, DIFFERENCE 1); synchronous
 int make_fields(lscqp_plan_s* p) {
-    PLAN_TRY(lscqp_grid_fields_device(p->grid, p->s.n_total, p->start_pts, (const double*)p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], p->field, p->init_d, nullptr));
+    if (p->n_missions() > 1)
+        PLAN_TRY(lscqp_grid_fields_missions_device(p->grid, p->s.n_total, p->n_missions(), p->moff.data(), p->d_moff, p->start_pts,
+                                                   (const double*)p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], p->field, p->init_d, nullptr));
+    else
+        PLAN_TRY(lscqp_grid_fields_device(p->grid, p->s.n_total, p->start_pts, (const double*)p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], p->field, p->init_d, nullptr));
     const hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "distance fields");
     p->fields_valid = true;
@@ -594,6 +623,7 @@ void lscqp_plan_destroy(lscqp_plan p) {
     for (void* q : p->owned) (void)hipFree(q);
     if (p->grid) lscqp_grid_destroy(p->grid);
     if (p->field) (void)hipFree(p->field);
+    if (p->d_moff) (void)hipFree(p->d_moff);
     if (p->own_hq) lscqp_destroy(p->hq);
     delete p;
 }
@@ -627,6 +657,7 @@ int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* 
     }
     if (e != hipSuccess) return hip_fail(e, "plan reset");
     if (p->grid) PLAN_TRY(make_fields(p));
+    p->missions_pending = false;
     p->first = true;
     p->steps = 0;
     return LSCQP_OK;
@@ -713,6 +744,62 @@ int lscqp_plan_set_grid(lscqp_plan p, double resolution) {
 }
 
 lscqp_grid lscqp_plan_grid(lscqp_plan p) { return p ? p->grid : nullptr; }
+
+int lscqp_plan_set_missions(lscqp_plan p, int32_t n_missions, const int64_t* mission_offsets) {
+    if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
+    const bool single = n_missions <= 1 || !mission_offsets;
+    if (!single) {
+        if (p->s.n_agents != p->s.n_total)
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "a mission partition needs every agent on this device (n_agents == n_total): a sharded plan flies one mission");
+        PLAN_TRY(lscqp_check_missions_(p->s.n_total, n_missions, mission_offsets));
+    }
+    DeviceGuard g(p->device);
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_missions");
+    if (!single) {  // (everything that can fail comes before the plan changes)
+        int64_t* d = nullptr;
+        e = hipMalloc((void**)&d, (size_t)(n_missions + 1) * sizeof(int64_t));
+        if (e == hipSuccess) e = hipMemcpy(d, mission_offsets, (size_t)(n_missions + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
+        const int rc = e != hipSuccess ? hip_fail(e, "lscqp_plan_set_missions") : (p->grid ? lscqp_grid_reserve_missions_(p->grid, p->s.n_total, n_missions) : LSCQP_OK);
+        if (rc != LSCQP_OK) {
+            if (d) (void)hipFree(d);
+            return rc;
+        }
+        if (p->d_moff) (void)hipFree(p->d_moff);
+        p->d_moff = d;
+        p->moff.assign(mission_offsets, mission_offsets + n_missions + 1);
+    } else {
+        if (p->d_moff) (void)hipFree(p->d_moff);
+        p->d_moff = nullptr;
+        p->moff.clear();
+    }
+    drop_graph(p);  // (a captured chain holds the old partition's launches)
+    p->fields_valid = false;
+    p->missions_pending = true;
+    return LSCQP_OK;
+}
+
+int lscqp_plan_missions(lscqp_plan p, int32_t* n_missions_out, int64_t* offsets_out) {
+    if (!p || !n_missions_out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    const int K = p->n_missions();
+    *n_missions_out = K;
+    if (offsets_out) {
+        if (K > 1) memcpy(offsets_out, p->moff.data(), (size_t)(K + 1) * sizeof(int64_t));
+        else offsets_out[0] = 0, offsets_out[1] = p->s.n_total;
+    }
+    return LSCQP_OK;
+}
+
+int lscqp_plan_mission_status(lscqp_plan p, int32_t* status_out) {
+    if (!p || !status_out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    const int K = p->n_missions();
+    if (!p->grid) {  // (no waypoint walk in this plan: nothing to report)
+        for (int k = 0; k < K; k++) status_out[k] = 0;
+        return LSCQP_OK;
+    }
+    DeviceGuard g(p->device);
+    return K > 1 ? lscqp_grid_mission_status(p->grid, K, status_out) : lscqp_grid_status(p->grid, status_out);
+}
 
 const lscqp_plan_desc* lscqp_plan_desc_of_(lscqp_plan p) { return &p->d; }  // (library-internal: lscqp_comm.hip)
 int lscqp_plan_device_(lscqp_plan p) { return p->device; }

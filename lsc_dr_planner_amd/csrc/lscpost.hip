@@ -171,19 +171,34 @@ __device__ __forceinline__ void position_at(int M, int dim, double dt, double t,
     }
 }
 
+// MIS: the agents (all of them local: first_agent = 0) are partitioned into missions off[0..K] (include/lscqp.h, "many missions over one
+// map"); a workgroup serves kSafI agents of ONE mission -- mission blockIdx.x / per_mission, chunk blockIdx.x % per_mission of it, with
+// per_mission sized by the largest mission -- and the other agents j run over [lo, hi) of that mission instead of [0, n_total).  Ids and
+// keys stay global.
+template <bool MIS>
 __global__ __launch_bounds__(kSafT) void safety_metrics_kernel(int M, int dim, double dt, int64_t n_agents, int64_t first_agent,
                                                                int64_t n_total, int n_samples, double record_time_step, double z_2d,
                                                                const double* __restrict__ x_all, const double* __restrict__ radius,
                                                                const double* __restrict__ downwash,
-                                                               const lscqp_header* __restrict__ hdr, lscqp_safety* __restrict__ out) {
+                                                               const lscqp_header* __restrict__ hdr, lscqp_safety* __restrict__ out,
+                                                               const int64_t* __restrict__ off, unsigned per_mission) {
     __shared__ float tp[kSafT][3];
     __shared__ double tr[kSafT], tdr[kSafT];  // r_j, downwash_j * r_j
     __shared__ double red_v[kSafT];
     __shared__ int64_t red_k[kSafT];
     const int li = threadIdx.x % kSafI, slice = threadIdx.x / kSafI;
-    const int64_t a = (int64_t)blockIdx.x * kSafI + li;
+    int64_t lo = 0, hi = n_total;
+    unsigned chunk = blockIdx.x;
+    if (MIS) {
+        const unsigned k = blockIdx.x / per_mission;
+        chunk = blockIdx.x - k * per_mission;
+        lo = off[k], hi = off[k + 1];
+        if (lo + (int64_t)chunk * kSafI >= hi) return;  // (the whole workgroup: the grid is sized by the largest mission)
+        n_agents = hi;
+    }
+    const int64_t a = lo + (int64_t)chunk * kSafI + li;
     const bool live = a < n_agents;
-    const int64_t gi = first_agent + (live ? a : 0);
+    const int64_t gi = first_agent + (live ? a : lo);
     const int nv = dim * 6 * M;
     const double ri = radius[gi], dri = downwash[gi] * ri;
     double best = 1e300;
@@ -217,10 +232,10 @@ __global__ __launch_bounds__(kSafT) void safety_metrics_kernel(int M, int dim, d
                 aex[k] = (ae > 0 && ae > aex[k]) ? ae : aex[k];
             }
         }
-        for (int64_t tile = 0; tile < n_total; tile += kSafT) {
+        for (int64_t tile = lo; tile < hi; tile += kSafT) {
             __syncthreads();
             const int64_t gj = tile + threadIdx.x;
-            if (gj < n_total) {
+            if (gj < hi) {
                 float pj[3];
                 position_at(M, dim, dt, t, z_2d, x_all + gj * nv, pj);
                 tp[threadIdx.x][0] = pj[0], tp[threadIdx.x][1] = pj[1], tp[threadIdx.x][2] = pj[2];
@@ -228,7 +243,7 @@ __global__ __launch_bounds__(kSafT) void safety_metrics_kernel(int M, int dim, d
                 tdr[threadIdx.x] = downwash[gj] * tr[threadIdx.x];
             }
             __syncthreads();
-            const int cnt = (int)((n_total - tile < kSafT) ? n_total - tile : kSafT);
+            const int cnt = (int)((hi - tile < kSafT) ? hi - tile : kSafT);
             for (int jj = slice; jj < cnt; jj += kSafS) {
                 const int64_t j = tile + jj;
                 // 16.8 M pairs at 4096 agents: the two divisions and the square root per pair go through v_rcp_f64 / v_rsq_f64
@@ -343,8 +358,25 @@ extern "C" int lscqp_safety_metrics_raw_(int M, int dim, double dt, int64_t n_ag
                                          const double* d_downwash, const lscqp_header* d_hdr, lscqp_safety* d_out, void* stream) {
     if (n_agents == 0) return LSCQP_OK;
     const unsigned blocks = (unsigned)((n_agents + lscpost::kSafI - 1) / lscpost::kSafI);
-    hipLaunchKernelGGL(lscpost::safety_metrics_kernel, dim3(blocks), dim3(lscpost::kSafT), 0, (hipStream_t)stream, M, dim, dt, n_agents,
-                       first_agent, n_total, n_samples, record_time_step, z_2d, d_x_all, d_radius, d_downwash, d_hdr, d_out);
+    hipLaunchKernelGGL(lscpost::safety_metrics_kernel<false>, dim3(blocks), dim3(lscpost::kSafT), 0, (hipStream_t)stream, M, dim, dt, n_agents,
+                       first_agent, n_total, n_samples, record_time_step, z_2d, d_x_all, d_radius, d_downwash, d_hdr, d_out, (const int64_t*)nullptr, 1u);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
+    return LSCQP_OK;
+}
+
+// largest_mission: the agents of the largest mission of the partition (sizes the grid: every mission gets that many workgroups)
+extern "C" int lscqp_safety_metrics_missions_raw_(int M, int dim, double dt, int64_t n_total, int32_t n_missions, int64_t largest_mission,
+                                                  const int64_t* d_off, int n_samples, double record_time_step, double z_2d, const double* d_x_all,
+                                                  const double* d_radius, const double* d_downwash, const lscqp_header* d_hdr, lscqp_safety* d_out,
+                                                  void* stream) {
+    if (n_total == 0) return LSCQP_OK;
+    const int64_t per_mission = (largest_mission + lscpost::kSafI - 1) / lscpost::kSafI;
+    if (per_mission * n_missions > 0x7fffffff)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the partition needs more than 2^31 workgroups (missions x the largest mission's agents / 32)");
+    hipLaunchKernelGGL(lscpost::safety_metrics_kernel<true>, dim3((unsigned)(per_mission * n_missions)), dim3(lscpost::kSafT), 0, (hipStream_t)stream, M, dim, dt,
+                       n_total, (int64_t)0, n_total, n_samples, record_time_step, z_2d, d_x_all, d_radius, d_downwash, d_hdr, d_out, d_off,
+                       (unsigned)per_mission);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
     return LSCQP_OK;

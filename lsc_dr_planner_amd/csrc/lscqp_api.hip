@@ -73,6 +73,12 @@ extern "C" int lscqp_select_neighbours_raw_(int64_t n_agents, int64_t first_agen
 extern "C" int lscqp_validate_step_raw_(int M, int dim, int use_sfc, double dt, int64_t n, double time_step, double z_2d, const double* d_x,
                                         const lscqp_header* d_hdr, const lscqp_box* d_sfc, int32_t* d_valid, double* d_state,
                                         void* stream);
+extern "C" int lscqp_select_neighbours_missions_raw_(int64_t n_total, int32_t n_missions, const int64_t* d_off, int32_t n_obs, double range,
+                                                     const double* d_pos, int32_t* d_nbr, int32_t* d_count, void* stream);
+extern "C" int lscqp_safety_metrics_missions_raw_(int M, int dim, double dt, int64_t n_total, int32_t n_missions, int64_t largest_mission,
+                                                  const int64_t* d_off, int n_samples, double record_time_step, double z_2d, const double* d_x_all,
+                                                  const double* d_radius, const double* d_downwash, const lscqp_header* d_hdr, lscqp_safety* d_out,
+                                                  void* stream);
 extern "C" int lscqp_shift_traj_raw_(int M, int dim, int64_t n, int shift, double z_2d, const double* d_x_prev, double* d_traj,
                                      void* stream);
 
@@ -1056,6 +1062,49 @@ int lscqp_select_neighbours_device(lscqp_handle h, int64_t n_agents, int64_t fir
     if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     return lscqp_select_neighbours_raw_(n_agents, first_agent, n_total, n_obs, communication_range, d_positions, d_neighbours_out,
                                         d_count_out, stream);
+}
+
+// (library-internal: every entry point that takes a mission partition) mission_offsets[0..n_missions], host: strictly increasing from 0 to n_total
+int lscqp_check_missions_(int64_t n_total, int32_t n_missions, const int64_t* mission_offsets) {
+    if (n_missions < 1 || !mission_offsets) return fail(LSCQP_ERR_INVALID_ARGUMENT, "a mission partition needs n_missions >= 1 and its offset list");
+    if (mission_offsets[0] != 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "mission_offsets[0] must be 0");
+    for (int32_t k = 0; k < n_missions; k++)
+        if (mission_offsets[k + 1] <= mission_offsets[k]) return fail(LSCQP_ERR_INVALID_ARGUMENT, "mission_offsets must be strictly increasing (no empty mission)");
+    if (mission_offsets[n_missions] != n_total) return fail(LSCQP_ERR_INVALID_ARGUMENT, "mission_offsets[n_missions] must be the number of agents");
+    return LSCQP_OK;
+}
+
+int lscqp_select_neighbours_missions_device(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
+                                            const int64_t* d_mission_offsets, int32_t n_obs, double communication_range,
+                                            const double* d_positions, int32_t* d_neighbours_out, int32_t* d_count_out, void* stream) {
+    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_total < 0 || n_obs < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
+    const int rc = lscqp_check_missions_(n_total, n_missions, mission_offsets);
+    if (rc != LSCQP_OK) return rc;
+    if (!d_mission_offsets || !d_positions || !d_count_out || (n_obs > 0 && !d_neighbours_out)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    int ndev = 0;
+    const hipError_t de = hipGetDeviceCount(&ndev);
+    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    return lscqp_select_neighbours_missions_raw_(n_total, n_missions, d_mission_offsets, n_obs, communication_range, d_positions, d_neighbours_out,
+                                                 d_count_out, stream);
+}
+
+int lscqp_safety_metrics_missions_device(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
+                                         const int64_t* d_mission_offsets, int32_t n_samples, double record_time_step, double z_2d,
+                                         const double* d_x_all, const double* d_radius, const double* d_downwash, const lscqp_header* d_hdr,
+                                         lscqp_safety* d_out, void* stream) {
+    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_total < 0 || n_samples < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
+    const int rc = lscqp_check_missions_(n_total, n_missions, mission_offsets);
+    if (rc != LSCQP_OK) return rc;
+    if (!d_mission_offsets || !d_x_all || !d_radius || !d_downwash || !d_hdr || !d_out) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    int ndev = 0;
+    const hipError_t de = hipGetDeviceCount(&ndev);
+    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    int64_t largest = 0;
+    for (int32_t k = 0; k < n_missions; k++) largest = std::max(largest, mission_offsets[k + 1] - mission_offsets[k]);
+    return lscqp_safety_metrics_missions_raw_(h->desc.M, h->desc.dim, h->desc.dt, n_total, n_missions, largest, d_mission_offsets, n_samples,
+                                              record_time_step, z_2d, d_x_all, d_radius, d_downwash, d_hdr, d_out, stream);
 }
 
 int lscqp_validate_step_device(lscqp_handle h, int64_t n, double time_step, double z_2d, const double* d_x,

@@ -105,13 +105,80 @@ def random_forest_world(n_agents=64, side=24.0, n_boxes=150, seed=0, clearance=0
             "z_2d": z, "radius": 0.15, "starts": [[p[0], p[1], z] for p in starts], "goals": [[p[0], p[1], z] for p in goals]}
 
 
-def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None, router="host"):
+def seeded_missions(world, occ, grid_min, missions, seed=0):
+    """K missions over one world: mission 0 is the world's own, mission k > 0 has as many agents on distinct free grid nodes and distinct
+    free goal nodes drawn from (seed, k).  Returns (offsets [K + 1], starts, goals)."""
+    starts, goals = [np.array(world["starts"], float)], [np.array(world["goals"], float)]
+    n = len(starts[0])
+    ys, xs = np.nonzero(~occ.astype(bool))
+    for k in range(1, missions):
+        pick = np.random.default_rng([seed, k]).choice(len(xs), size=2 * n, replace=False)
+        pts = np.c_[grid_min[0] + 0.5 * xs[pick], grid_min[1] + 0.5 * ys[pick], np.full(2 * n, float(world["z_2d"]))]
+        starts.append(pts[:n])
+        goals.append(pts[n:])
+    return np.arange(missions + 1) * n, np.concatenate(starts), np.concatenate(goals)
+
+
+def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=0, graph=True):
+    """`missions` seeded missions over one world flown by ONE lscqp_plan with a mission partition (include/lscqp.h, "many missions over one
+    map"): waypoint_mode 1, closed loop, one captured graph per replan.  The summary has the figures of `run` per mission."""
+    import torch
+
+    from lsc_dr_planner_amd import api
+
+    g = world_json if isinstance(world_json, dict) else json.load(open(world_json))
+    n = len(g["starts"])
+    sol = api.Solver(api.make_desc(M=M, dim=2, dt=dt, world_min=g["world_min"], world_max=g["world_max"]))
+    wmap = api.WorldMap(g["boxes"], g["world_min"], g["world_max"], g["resolution"], g["max_dist"])
+    probe = api.Grid(wmap, 0.5, float(g["radius"]), float(g["z_2d"]))
+    off, starts, goals = seeded_missions(g, probe.download(), probe.grid_min, missions, seed)
+    probe.close()
+    N = int(off[-1])
+    n_obs = max(1, min(n - 1 if n_obs is None else n_obs, sol.max_obstacles()))
+    ag = np.zeros(N, api.AGENT_PARAM_DTYPE)
+    ag["radius"], ag["downwash"], ag["max_vel"], ag["max_acc"], ag["nominal_velocity"] = g["radius"], 2.0, 1.0, 2.0, 1.0
+    plan = api.Plan(sol, wmap, N, n_obs, ag, constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, optimize_goal=True, closed_loop=True,
+                    z_2d=float(g["z_2d"]), safety_samples=2, record_time_step=0.1, waypoint_mode=api.WAYPOINT_GRID_PIBT, mission_offsets=off)
+    plan.reset(starts, goals)
+    per = [dict(mission=k, agents=n, qp_failed=0, invalid=0, min_safety_ratio=np.inf, max_vel_excess=0.0, max_acc_excess=0.0, waypoints_updated=0,
+                truncated_agent_steps=0) for k in range(missions)]
+    for _ in range(steps):
+        plan.step(graph=graph)
+        torch.cuda.synchronize()
+        st, valid, saf, upd, cnt = (plan.get(b) for b in (api.PLAN_STATUS, api.PLAN_VALID, api.PLAN_SAFETY, api.PLAN_WAYPOINT_UPDATED, api.PLAN_IN_RANGE))
+        for k, m in enumerate(per):
+            sl = slice(int(off[k]), int(off[k + 1]))
+            m["qp_failed"] += int((st[sl] != 0).sum())
+            m["invalid"] += int(((st[sl] == 0) & (valid[sl] != 1)).sum())
+            m["min_safety_ratio"] = float(min(m["min_safety_ratio"], saf["safety_ratio"][sl].min()))
+            m["max_vel_excess"] = float(max(m["max_vel_excess"], saf["vel_excess_ratio"][sl].max()))
+            m["max_acc_excess"] = float(max(m["max_acc_excess"], saf["acc_excess_ratio"][sl].max()))
+            m["waypoints_updated"] += int(upd[sl].sum())
+            m["truncated_agent_steps"] += int((cnt[sl] > n_obs).sum())
+    state = plan.get(api.PLAN_STATE).reshape(N, 9)
+    progress = np.linalg.norm(goals[:, :2] - starts[:, :2], axis=1) - np.linalg.norm(goals[:, :2] - state[:, :2], axis=1)
+    status = plan.mission_status()
+    for k, m in enumerate(per):
+        m["mean_progress_m"] = float(progress[int(off[k]):int(off[k + 1])].mean())
+        m["walk_bound_reached"] = int(status[k])
+    log = dict(steps=steps, missions=missions, agents=N, row_slots=n_obs, router="device", sim_time_s=steps * dt, graph_nodes=plan.graph_nodes(),
+               qp_failed=sum(m["qp_failed"] for m in per), invalid=sum(m["invalid"] for m in per),
+               min_safety_ratio=min(m["min_safety_ratio"] for m in per), per_mission=per)
+    plan.close()
+    wmap.close()
+    return log
+
+
+def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None, router="host", missions=None):
     """script (optional): {"waypoint": (K, N, 3), "state": (K, N, 9)} -- replay of a recorded mission: replan k takes every agent's
     state and waypoint from the script instead of the loop's own step / router (the plans, goal points, corridors and neighbour sets are
     still the loop's own), and the result carries every replan's solution (`x`, (K, N, nv)) and goal point (`goal`, (K, N, 3)).
-    router: "host" (GridRouter) or "device" (lscqp_waypoints_device over the previous plans, states and goal points)."""
+    router: "host" (GridRouter) or "device" (lscqp_waypoints_device over the previous plans, states and goal points).
+    missions: K > 0 flies K seeded missions over the world in one lscqp_plan (run_missions) and reports per-mission figures."""
     if router not in ("host", "device"):
         raise ValueError("router must be 'host' or 'device'")
+    if missions:
+        return run_missions(world_json, int(missions), steps=steps, M=M, dt=dt, n_obs=n_obs)
     import torch
 
     from lsc_dr_planner_amd import api
@@ -304,7 +371,8 @@ if __name__ == "__main__":
     ap.add_argument("--forest", type=int, default=0, help="N > 0: a synthetic forest with N agents instead of --world")
     ap.add_argument("--obs", type=int, default=None, help="neighbour capacity per agent")
     ap.add_argument("--dump", default=None, help="npz path: inputs of the first replan with a failed QP")
+    ap.add_argument("--missions", type=int, default=0, help="K > 0: K seeded missions over the world in ONE plan with a mission partition, figures per mission")
     ap.add_argument("--router", default="host", choices=("host", "device"), help="where the waypoints come from: the host stand-in or lscqp_waypoints_device")
     a = ap.parse_args()
     world = random_forest_world(a.forest) if a.forest > 0 else a.world
-    print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router)))
+    print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router, missions=a.missions)))

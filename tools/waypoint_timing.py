@@ -7,9 +7,16 @@
     python tools/waypoint_timing.py --part closed_loop              tools/closed_loop.py per replan with router=host and router=device
     python tools/waypoint_timing.py --part chains --agents 0|64 [--parent DIR] [--runs 5]
                                                                     the driver of `chain`: fresh child processes, parent mode 0 / mode 0 / mode 1
-                                                                    interleaved, medians and the run-to-run spread of each
+                                                                    (and parent mode 1) interleaved, medians and the run-to-run spread of each
+    python tools/waypoint_timing.py --part missions --missions K [--tree DIR]
+                                                                    one process: K copies of forest10 as K plans stepped one after another
+                                                                    and (this checkout) as ONE plan with K missions, graph replay
+    python tools/waypoint_timing.py --part missions_sweep [--missions-list 1,8,25] [--parent DIR] [--runs 5]
+                                                                    the driver of `missions`: fresh child processes, interleaved
+    python tools/waypoint_timing.py --part decision --missions K    the decision alone: one workgroup per mission against the single-workgroup
+                                                                    decision over the same 10 K agents
 
-Every part prints JSON lines; profiles/r09_waypoints.txt is a transcript."""
+Every part prints JSON lines; profiles/r09_waypoints.txt and profiles/r10_missions.txt are transcripts."""
 import argparse
 import json
 import os
@@ -151,7 +158,7 @@ def part_chains(a):
     me = os.path.abspath(__file__)
     variants = [("mode0", ["--mode", "0"]), ("mode1", ["--mode", "1"])]
     if a.parent:
-        variants.insert(0, ("parent_mode0", ["--mode", "0", "--tree", a.parent]))
+        variants = [("parent_mode0", ["--mode", "0", "--tree", a.parent]), variants[0], ("parent_mode1", ["--mode", "1", "--tree", a.parent]), variants[1]]
     res = {k: [] for k, _ in variants}
     for _ in range(a.runs):
         for name, extra in variants:  # interleaved: one run of each, then the next round
@@ -166,6 +173,119 @@ def part_chains(a):
             print(json.dumps(dict(what="chains", clock="host wall time around step + synchronize, median of %d replans per run" % (a.steps - 3), agents=rows[0]["agents"], variant=name, form=form, runs_us=[round(x, 1) for x in v], median_us=round(float(np.median(v)), 1),
                                   spread_us=round(max(v) - min(v), 1), graph_nodes=rows[0]["graph_nodes"], failed_qps=sum(r[form + "_failed_qps"] for r in rows),
                                   progress_m=round(rows[0][form + "_progress_m"], 2))), flush=True)
+
+
+def part_missions(a):
+    """K copies of forest10.  `separate`: K plans of ten agents (what a caller without the partition runs), every plan's graph launched
+    one after another, one wait at the end.  `batched`: one plan with K missions.  Host wall time per replan of ALL K missions."""
+    if a.tree:
+        sys.path.insert(0, os.path.abspath(a.tree))
+    import torch
+
+    from lsc_dr_planner_amd import api
+
+    W = json.load(open(os.path.join(ROOT, "tests", "golden", "forest10_world.json")))
+    K, n = a.missions, len(W["starts"])
+    starts, goals = np.array(W["starts"], dtype=np.float64), np.array(W["goals"], dtype=np.float64)
+    sol = api.Solver(api.make_desc(M=10, dim=2, dt=0.2, world_min=W["world_min"], world_max=W["world_max"]))
+    wmap = api.WorldMap(W["boxes"], W["world_min"], W["world_max"], W["resolution"], W["max_dist"])
+
+    def make(N, **kw):
+        ag = np.zeros(N, api.AGENT_PARAM_DTYPE)
+        ag["radius"], ag["downwash"], ag["max_vel"], ag["max_acc"], ag["nominal_velocity"] = W["radius"], 2.0, 1.0, 2.0, 1.0
+        return api.Plan(sol, wmap, N, n - 1, ag, constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, closed_loop=True, z_2d=W["z_2d"], waypoint_mode=1, **kw)
+
+    def fly(plans):
+        t, failed = [], 0
+        for k in range(a.steps):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for p in plans:
+                p.step(graph=True)
+            torch.cuda.synchronize()
+            if k >= 3:
+                t.append(time.perf_counter() - t1)
+            failed += sum(int((p.get(api.PLAN_STATUS) != 0).sum()) for p in plans)
+        return float(np.median(t) * 1e6), failed
+
+    out = dict(what="missions", clock="host wall time around the steps of all K missions + synchronize", missions=K, agents=K * n, lib=os.path.dirname(api.__file__),
+               steps=a.steps)
+    plans = [make(n) for _ in range(K)]
+    for p in plans:
+        p.reset(starts, goals)
+    out["separate_us"], out["separate_failed_qps"] = fly(plans)
+    for p in plans:
+        p.close()
+    if hasattr(api.Plan, "set_missions"):
+        plan = make(K * n, mission_offsets=np.arange(K + 1) * n)
+        plan.reset(np.tile(starts, (K, 1)), np.tile(goals, (K, 1)))
+        out["batched_us"], out["batched_failed_qps"] = fly([plan])
+        out["graph_nodes"] = plan.graph_nodes()
+        plan.close()
+    print(json.dumps(out), flush=True)
+
+
+def part_missions_sweep(a):
+    me = os.path.abspath(__file__)
+    for K in [int(v) for v in a.missions_list.split(",")]:
+        variants = [("this", [])] + ([("parent", ["--tree", a.parent])] if a.parent else [])
+        res = {k: [] for k, _ in variants}
+        for _ in range(a.runs):
+            for name, extra in variants:
+                r = subprocess.run([sys.executable, me, "--part", "missions", "--missions", str(K), "--steps", str(a.steps)] + extra, capture_output=True, text=True, timeout=600)
+                if r.returncode != 0:
+                    print(r.stdout[-2000:], r.stderr[-4000:], file=sys.stderr)
+                    raise SystemExit("child failed (%s, K = %d): nothing more is started" % (name, K))
+                res[name].append(json.loads(r.stdout.strip().splitlines()[-1]))
+        for name, rows in res.items():
+            for form in ("separate", "batched"):
+                if form + "_us" not in rows[0]:
+                    continue
+                v = [r[form + "_us"] for r in rows]
+                print(json.dumps(dict(what="missions_sweep", clock=rows[0]["clock"] + ", median of %d replans per run" % (a.steps - 3), missions=K, agents=rows[0]["agents"],
+                                      lib=name, form=form, runs_us=[round(x, 1) for x in v], median_us=round(float(np.median(v)), 1), spread_us=round(max(v) - min(v), 1),
+                                      failed_qps=sum(r[form + "_failed_qps"] for r in rows))), flush=True)
+
+
+def part_decision(a):
+    """The decision alone on a 40 m forest (81 x 81 nodes, tables in LDS): K missions of ten agents as one workgroup per mission, and the
+    same 10 K agents as one swarm in the single workgroup."""
+    import torch
+
+    from lsc_dr_planner_amd import api
+
+    dev = torch.device("cuda", 0)
+    up = lambda x, dt=np.float64: torch.from_numpy(np.ascontiguousarray(x, dtype=dt)).to(dev)  # noqa: E731
+    w = _forest(40.0, 300)
+    wmap = api.WorldMap(w["boxes"], w["world_min"], w["world_max"], w["resolution"], w["max_dist"])
+    grid = api.Grid(wmap, 0.5, w["radius"], w["z_2d"])
+    occ = grid.download()
+    K, per = a.missions, 10
+    n = K * per
+    off = np.arange(K + 1) * per
+    starts, goals = _free_nodes(occ, grid.grid_min, n, 1, True), _free_nodes(occ, grid.grid_min, n, 2, False)
+    d_s, d_g, d_off = up(starts), up(goals), up(off, np.int64)
+    st = np.zeros((n, 9))
+    st[:, :3] = starts
+    x = np.repeat(starts[:, :2, None], 60, axis=2).reshape(n, -1)  # hover plans
+    d_st, d_x, d_cg, d_way0 = up(st), up(x), up(np.float32(starts).astype(float)), up(np.float32(starts).astype(float))
+    d_way = d_way0.clone()
+    for rng_name, rng in (("one group per mission / swarm", -1.0), ("range 3 m", 3.0)):
+        d_field, d_init = grid.fields(d_s, d_g)
+        g, _, u = grid.waypoints(rng, 10, 2, d_st, d_x, d_cg, d_field, d_init, d_way)
+        torch.cuda.synchronize()
+        r = _events(torch, lambda: grid.waypoints(rng, 10, 2, d_st, d_x, d_cg, d_field, d_init, d_way), a.repeats, 20, before=lambda: d_way.copy_(d_way0))
+        print(json.dumps(dict(what="decision", form="one swarm, one workgroup", agents=n, range=rng_name, groups=int(torch.unique(g).numel()), waypoints_moved=int(u.sum().item()), **r)), flush=True)
+        d_field, d_init = grid.fields_missions(off, d_s, d_g, d_offsets=d_off)
+        d_way.copy_(d_way0)
+        g, _, u = grid.waypoints_missions(off, rng, 10, 2, d_st, d_x, d_cg, d_field, d_init, d_way, d_offsets=d_off)
+        torch.cuda.synchronize()
+        r = _events(torch, lambda: grid.waypoints_missions(off, rng, 10, 2, d_st, d_x, d_cg, d_field, d_init, d_way, d_offsets=d_off), a.repeats, 20,
+                    before=lambda: d_way.copy_(d_way0))
+        assert not grid.mission_status(K).any() and grid.status() == 0
+        print(json.dumps(dict(what="decision", form="%d missions, one workgroup each" % K, agents=n, range=rng_name, groups=int(torch.unique(g).numel()), waypoints_moved=int(u.sum().item()), **r)), flush=True)
+    grid.close()
+    wmap.close()
 
 
 def part_closed_loop(a):
@@ -186,7 +306,9 @@ def part_closed_loop(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", required=True, choices=("kernels", "chain", "chains", "closed_loop"))
+    ap.add_argument("--part", required=True, choices=("kernels", "chain", "chains", "closed_loop", "missions", "missions_sweep", "decision"))
+    ap.add_argument("--missions", type=int, default=25)
+    ap.add_argument("--missions-list", default="1,8,25")
     ap.add_argument("--agents", type=int, default=0)
     ap.add_argument("--mode", type=int, default=0)
     ap.add_argument("--steps", type=int, default=60)
@@ -195,10 +317,11 @@ def main():
     ap.add_argument("--tree", default=None)
     ap.add_argument("--parent", default=None)
     a = ap.parse_args()
-    if a.part != "chain" or not a.tree:
+    if a.part not in ("chain", "missions") or not a.tree:
         sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tools"))
-    {"kernels": part_kernels, "chain": part_chain, "chains": part_chains, "closed_loop": part_closed_loop}[a.part](a)
+    {"kernels": part_kernels, "chain": part_chain, "chains": part_chains, "closed_loop": part_closed_loop, "missions": part_missions,
+     "missions_sweep": part_missions_sweep, "decision": part_decision}[a.part](a)
 
 
 if __name__ == "__main__":
