@@ -54,7 +54,7 @@ namespace lscqp_das {
 using lscqp::DevClass;
 using lscqp::KQ;
 
-constexpr double kTolP = 1e-9;      // a row is violated below -1e-9 (normalised): the interior-point kernel's primal bar
+constexpr double kTolP = 1e-9;      // a row is violated below -1e-9 m of RAW slack (not divided by the row's norm): the interior-point kernel's primal bar
 constexpr double kTolD = 1e-9;      // accepted stationarity (scaled like lscqp_info.res_dual)
 constexpr int kMaxK = 32;           // active rows the phase can hold (lanes of one wavefront own the rows of the small factor)
 

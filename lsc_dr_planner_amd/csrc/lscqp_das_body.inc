@@ -324,7 +324,7 @@
                coef[2] * vec[ent_axis(ent[2]) * P + ent_cp(ent[2])];
     };
 
-    // ---- one pass over every row: the most violated one (normalised slack, lowest id on ties) and the largest raw violation ---------
+    // ---- one pass over every row: the most violated one (RAW slack, lowest id on ties); its slack is the largest raw violation -------
     // The FIRST pass consumes the rows requested in the prologue (HBM), asks for the rest four at a time and, in the staged form (small
     // batches: LDS to spare), leaves them translated in LDS; later passes read them from there, or from L2.
     bool first_pass = true;  // (uniform)
