@@ -743,7 +743,21 @@ int lscqp_construct_sfc(lscqp_map map, int32_t mode, int32_t M, int64_t n, const
  *     later decisions do not clear it; lscqp_grid_fields_device (hence lscqp_plan_reset) does.  The grid keeps nothing of the map after
  *     lscqp_grid_create: it may outlive it.
  *     The launch uses work arrays owned by the grid: one decision at a time per grid.  They grow on demand, which synchronises and
- *     allocates -- a caller that captures the launch in a graph calls lscqp_grid_reserve(grid, n) first. */
+ *     allocates -- a caller that captures the launch in a graph calls lscqp_grid_reserve(grid, n) first.
+ *   lscqp_waypoints_wide_device   the SAME decision -- same arguments, same contract, same status word, every output equal to
+ *     lscqp_waypoints_device's bit for bit -- spread over the device for a large swarm instead of run by one workgroup.  After the same
+ *     gather: groups from a cell list over the positions (a counting sort by x-y cell of side >= 1.0001 * range, enlarged until at most
+ *     2 n + 16 cells cover the grid's box; positions outside fall into the edge cells) and a lock-free union-find over the pairs of the
+ *     3 x 3 cells that pass the unchanged test, the root with the larger id hooked under the smaller -- O(n) work where agents are spread
+ *     out, against n^2 per round; agents alone in their group decide in parallel; the others are sorted group by group (init_d
+ *     descending, id descending) and ONE workgroup per group of more than one agent runs the PIBT walk by one of its wavefronts over
+ *     node tables of the group's own (open-addressed, 4 n_g to 8 n_g slots: O(n) memory in all), with a bound of 4 n_g + 16 passes of its
+ *     own, then the update filter for its members.  A last launch applies the updates; if ANY group reached its bound no waypoint of the
+ *     swarm changes and the status word becomes 1.  Asynchronous on `stream`: 6 launches (range <= 0) or 11, none of which waits for
+ *     another workgroup, no host round trip, capturable.  The walk inside one group stays sequential: a swarm that is one group
+ *     (range < 0) gains from the sort only.  Work arrays: lscqp_grid_reserve_wide(grid, n), which includes lscqp_grid_reserve(grid, n)
+ *     and adds about 150 bytes per agent; like the one-workgroup entry the wide entry allocates on demand (and synchronises) when nothing
+ *     was reserved.  lscqp_grid_reserve and lscqp_waypoints_device keep their footprint.  One decision at a time per grid, either form. */
 typedef struct lscqp_grid_s* lscqp_grid;
 typedef struct lscqp_grid_desc {
     double resolution;       /* grid/resolution, 0.5 m in the launch files */
@@ -767,6 +781,10 @@ int lscqp_grid_fields_device(lscqp_grid grid, int64_t n, const double* d_start_p
 int lscqp_waypoints_device(lscqp_grid grid, double communication_range, int32_t M, int32_t dim, int64_t n, const double* d_state,
                            const double* d_plan, const double* d_current_goal, const int32_t* d_field, const int32_t* d_init_d,
                            double* d_waypoint, int32_t* d_group_out, int32_t* d_desired_out, int32_t* d_updated_out, void* stream);
+int lscqp_grid_reserve_wide(lscqp_grid grid, int64_t n);
+int lscqp_waypoints_wide_device(lscqp_grid grid, double communication_range, int32_t M, int32_t dim, int64_t n, const double* d_state,
+                                const double* d_plan, const double* d_current_goal, const int32_t* d_field, const int32_t* d_init_d,
+                                double* d_waypoint, int32_t* d_group_out, int32_t* d_desired_out, int32_t* d_updated_out, void* stream);
 
 /* ---- the caller of the path: one replan of a batch of agents as one chain of device work ----------
  *
@@ -942,7 +960,22 @@ int lscqp_plan_group_step(lscqp_comm c, const lscqp_plan* plans, int32_t use_gra
  *                             filter.  d_group_out: least global id of the group.  lscqp_grid_fields_missions_device over the SAME
  *                             partition must have come last on this grid (it makes the copies and clears them for the agents of its
  *                             partition): any other offset list is refused.  One decision at a time per grid.
- *   lscqp_grid_mission_status status_out [n_missions], host; waits: the words lscqp_plan_mission_status reports. */
+ *   lscqp_grid_mission_status status_out [n_missions], host; waits: the words lscqp_plan_mission_status reports.
+ * Which form of the waypoint decision a plan's chain starts with (waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT only; any other plan:
+ * LSCQP_ERR_INVALID_ARGUMENT):
+ *   lscqp_plan_set_waypoint_decision   LSCQP_DECISION_ONE_WORKGROUP (the default: lscqp_waypoints_device, the chain node for node as it
+ *                             was), LSCQP_DECISION_WIDE (lscqp_waypoints_wide_device) or LSCQP_DECISION_AUTO (wide from
+ *                             LSCQP_DECISION_AUTO_MIN_AGENTS agents of the mission on; NOTES.md section 20 says where that figure comes from).  Every buffer of
+ *                             the plan is bit-identical whichever is chosen.  The call waits for the device, reserves the work arrays
+ *                             (lscqp_grid_reserve_wide) and drops a captured graph, like lscqp_plan_set_missions; no lscqp_plan_reset
+ *                             is needed after it.  A partition of more than one mission keeps one workgroup per mission: WIDE or AUTO on
+ *                             a plan that has one, and such a partition on a plan set to WIDE or AUTO, are LSCQP_ERR_UNSUPPORTED and
+ *                             leave the plan as it was. */
+#define LSCQP_DECISION_ONE_WORKGROUP 0
+#define LSCQP_DECISION_WIDE 1
+#define LSCQP_DECISION_AUTO 2
+#define LSCQP_DECISION_AUTO_MIN_AGENTS 512
+int lscqp_plan_set_waypoint_decision(lscqp_plan plan, int32_t which);
 int lscqp_plan_set_missions(lscqp_plan plan, int32_t n_missions, const int64_t* mission_offsets);
 int lscqp_plan_missions(lscqp_plan plan, int32_t* n_missions_out, int64_t* offsets_out);
 int lscqp_plan_mission_status(lscqp_plan plan, int32_t* status_out);

@@ -250,6 +250,12 @@ def lib():
         L.lscqp_waypoints_device.restype = C.c_int
         L.lscqp_waypoints_device.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_int64] + [vp] * 10
         i64, i32 = C.c_int64, C.c_int32
+        L.lscqp_grid_reserve_wide.restype = C.c_int
+        L.lscqp_grid_reserve_wide.argtypes = [vp, C.c_int64]
+        L.lscqp_waypoints_wide_device.restype = C.c_int
+        L.lscqp_waypoints_wide_device.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_int64] + [vp] * 10
+        L.lscqp_plan_set_waypoint_decision.restype = C.c_int
+        L.lscqp_plan_set_waypoint_decision.argtypes = [vp, C.c_int32]
         L.lscqp_plan_set_missions.restype = C.c_int
         L.lscqp_plan_set_missions.argtypes = [vp, i32, vp]
         L.lscqp_plan_missions.restype = C.c_int
@@ -295,6 +301,7 @@ EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_
                     "lscqp_plan_step", "lscqp_plan_step_graph", "lscqp_plan_graph_nodes", "lscqp_plan_group_step", "lscqp_plan_set_grid", "lscqp_plan_grid",
                     "lscqp_grid_shape", "lscqp_grid_create", "lscqp_grid_destroy", "lscqp_grid_info", "lscqp_grid_download", "lscqp_grid_download_mission",
                     "lscqp_grid_reserve", "lscqp_grid_status", "lscqp_grid_fields_device", "lscqp_waypoints_device",
+                    "lscqp_grid_reserve_wide", "lscqp_waypoints_wide_device", "lscqp_plan_set_waypoint_decision",
                     "lscqp_plan_set_missions", "lscqp_plan_missions", "lscqp_plan_mission_status", "lscqp_select_neighbours_missions_device",
                     "lscqp_safety_metrics_missions_device", "lscqp_grid_fields_missions_device", "lscqp_waypoints_missions_device", "lscqp_grid_mission_status",
                     "lscqp_instance_work", "lscqp_diagnose", "lscqp_diagnose_device", "lscqp_dump_instance", "lscqp_row_family_name",
@@ -486,6 +493,22 @@ class Grid:
                                                  _dptr(d_field), _dptr(d_init_d), _dptr(d_waypoint), _dptr(out[0]), _dptr(out[1]), _dptr(out[2]), C.c_void_p(s.cuda_stream)))
         return tuple(out)
 
+    def reserve_wide(self, n):
+        """lscqp_grid_reserve_wide: the work arrays of `waypoints_wide` for n agents (those of `waypoints` included)."""
+        self._check(lib().lscqp_grid_reserve_wide(self._h, int(n)))
+
+    def waypoints_wide(self, communication_range, M, dim, d_state, d_plan, d_current_goal, d_field, d_init_d, d_waypoint, stream=None):
+        """lscqp_waypoints_wide_device: `waypoints` spread over the device; same arguments, the same outputs bit for bit."""
+        import torch
+
+        n = d_waypoint.numel() // 3
+        out = [torch.empty(n, dtype=torch.int32, device=d_waypoint.device) for _ in range(3)]
+        s = stream if stream is not None else torch.cuda.current_stream()
+        self._check(lib().lscqp_waypoints_wide_device(self._h, float(communication_range), int(M), int(dim), n, _dptr(d_state), _dptr(d_plan), _dptr(d_current_goal),
+                                                      _dptr(d_field), _dptr(d_init_d), _dptr(d_waypoint), _dptr(out[0]), _dptr(out[1]), _dptr(out[2]),
+                                                      C.c_void_p(s.cuda_stream)))
+        return tuple(out)
+
     def mission_status(self, n_missions):
         """lscqp_grid_mission_status: int32 (n_missions,), the word of each mission's waypoint walk."""
         st = np.zeros(int(n_missions), np.int32)
@@ -545,6 +568,8 @@ class PlanDesc(C.Structure):  # lscqp_plan_desc
 
 TRAJ_FROM_PREVIOUS_SOLUTION, TRAJ_FROM_POSITION, TRAJ_FROM_VELOCITY = 0, 1, 2
 WAYPOINT_FROM_CALLER, WAYPOINT_GRID_PIBT = 0, 1
+DECISION_ONE_WORKGROUP, DECISION_WIDE, DECISION_AUTO = 0, 1, 2
+DECISION_AUTO_MIN_AGENTS = 512  # LSCQP_DECISION_AUTO_MIN_AGENTS
 
 
 (PLAN_STATE, PLAN_WAYPOINT, PLAN_PLAN, PLAN_GOAL, PLAN_HEADER, PLAN_ROWS, PLAN_SFC, PLAN_STATUS, PLAN_GOAL_STATUS, PLAN_SFC_STATUS, PLAN_VALID,
@@ -604,6 +629,10 @@ class Plan:
             return
         K, off, _ = mission_offsets_arg(offsets)
         self._check(lib().lscqp_plan_set_missions(self._p, K, off.ctypes.data_as(C.c_void_p)))
+
+    def set_waypoint_decision(self, which):
+        """lscqp_plan_set_waypoint_decision: DECISION_ONE_WORKGROUP (default), DECISION_WIDE or DECISION_AUTO; waypoint_mode 1 only."""
+        self._check(lib().lscqp_plan_set_waypoint_decision(self._p, int(which)))
 
     def missions(self):
         """lscqp_plan_missions: the partition's offsets, int64 (K + 1,); [0, n_total] without one."""

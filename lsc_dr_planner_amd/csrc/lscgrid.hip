@@ -507,6 +507,434 @@ __global__ __launch_bounds__(kDecideThreads) void decide_kernel(View g, int64_t 
     if (tid == 0 && fail) *s.status = 1;
 }
 
+// ---- the WIDE form of the decision (lscqp_waypoints_wide_device) ---------------------------------------------------------------------------
+// The same decision spread over the device, stage by stage, each stage a launch of its own that hands its results to the next at the kernel
+// boundary; no kernel waits for another workgroup and the number of launches depends on the sign of the range alone:
+//   gather (above)
+//   groups     range > 0 only: a cell list over the positions (zero, histogram, scan, scatter: a counting sort by x-y cell whose side is at
+//              least 1.0001 * range, so a pair the test accepts lies in the same or an adjacent cell), a lock-free union-find over the pairs of
+//              the 3 x 3 cells that pass the UNCHANGED test -- the root with the larger id is hooked under the smaller, so a component's root
+//              is its least id, the label of the one-workgroup kernel -- and a flatten pass, which also counts the members
+//   order      segment offsets per group of more than one agent (one scan over the roots); agents alone decide and filter by themselves,
+//              the others drop a key (init_d descending, id descending) into their group's segment
+//   walk       one workgroup per group of more than one agent: a bitonic sort of the segment by all lanes, then ONE wavefront runs the
+//              funcPIBT loop of decide_kernel over node tables of the group's own -- an open-addressed table of 4 n_g .. 8 n_g slots, in LDS
+//              for small groups and in the group's slab of an O(n) buffer otherwise -- with a bound of 4 n_g + 16 passes, then all lanes run
+//              the update filter and its fixed point for the members
+//   apply      the updates, unless some group reached its bound
+// Keys are distinct and every table answers the same whatever slot an entry landed in, so no result depends on the order in which atomics
+// arrive.  Every work array is written before it is read within the call: nothing has to be left clean.
+constexpr int kWideThreads = 256;
+constexpr int kWideLdsKeys = 1024;  // a segment of up to this many agents is sorted in LDS
+constexpr int kWideLdsCap = 1024;   // ... and a node table of up to this many slots (n_g <= 256) lives there
+
+struct Cells {  // the cell list's geometry, from the host
+    double side;
+    int ncx, ncy;
+};
+
+struct Wide {  // work arrays of the wide form (lscqp_grid_reserve_wide), every size a function of n alone
+    float4* sorted;       // [n]          position and id of the agents, cell by cell
+    uint64_t* keys;       // [n]          sort keys, one segment per group
+    int32_t *segstart, *fill, *grouplist;  // [n] each: a root's segment start and fill cursor; the roots of the groups to walk
+    int32_t *cell_count, *cell_fill, *cell_start;  // [2 n + 17] each
+    int32_t* table;       // [24 n]       a group's slab starts at 24 * segstart: key, now, next of up to 8 n_g slots
+    int32_t* misc;        // [0] groups to walk, [1] some group reached its bound
+};
+
+__device__ __forceinline__ int ald(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ int cell_of(const Cells& c, const View& g, float px, float py) {
+#pragma clang fp contract(off)
+    const double fx = floor(((double)px - g.gmin0) / c.side), fy = floor(((double)py - g.gmin1) / c.side);
+    const int cx = (int)fmin(fmax(fx, 0.0), (double)(c.ncx - 1)), cy = (int)fmin(fmax(fy, 0.0), (double)(c.ncy - 1));  // (outside the box, NaN: an edge cell)
+    return cy * c.ncx + cx;
+}
+
+// exclusive scan of one value per lane over a workgroup of T lanes; *total: the sum
+template <int T>
+__device__ __forceinline__ int block_scan(int v, int* sh, int* total) {
+    const int tid = threadIdx.x;
+    sh[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < T; off <<= 1) {
+        const int t = tid >= off ? sh[tid - off] : 0;
+        __syncthreads();
+        sh[tid] += t;
+        __syncthreads();
+    }
+    const int incl = sh[tid];
+    *total = sh[T - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+__global__ __launch_bounds__(256) void wide_zero_kernel(int count, int32_t* __restrict__ p, int32_t* __restrict__ q) {
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    if (id < count) p[id] = 0, q[id] = 0;
+}
+
+__global__ __launch_bounds__(256) void cell_count_kernel(View g, Cells c, int n, const double* __restrict__ state, Wide w) {
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= n) return;
+    atomicAdd(w.cell_count + cell_of(c, g, (float)state[(int64_t)a * 9], (float)state[(int64_t)a * 9 + 1]), 1);
+}
+
+// cell_start[0..ncell]: the exclusive scan of the counts, by one workgroup (ncell <= 2 n + 16)
+__global__ __launch_bounds__(1024) void cell_scan_kernel(int ncell, Wide w) {
+    __shared__ int sh[1024];
+    const int tid = threadIdx.x, per = (ncell + 1023) / 1024, lo = min(tid * per, ncell), hi = min(lo + per, ncell);
+    int sum = 0;
+    for (int i = lo; i < hi; i++) sum += w.cell_count[i];
+    int total;
+    int run = block_scan<1024>(sum, sh, &total);
+    for (int i = lo; i < hi; i++) {
+        w.cell_start[i] = run;
+        run += w.cell_count[i];
+    }
+    if (tid == 0) w.cell_start[ncell] = total;
+}
+
+__global__ __launch_bounds__(256) void cell_scatter_kernel(View g, Cells c, int n, const double* __restrict__ state, Wide w) {
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= n) return;
+    const float px = (float)state[(int64_t)a * 9], py = (float)state[(int64_t)a * 9 + 1], pz = (float)state[(int64_t)a * 9 + 2];
+    const int cell = cell_of(c, g, px, py);
+    const int slot = w.cell_start[cell] + atomicAdd(w.cell_fill + cell, 1);
+    if (slot >= 0 && slot < n) w.sorted[slot] = make_float4(px, py, pz, __int_as_float(a));
+}
+
+// union-find over the parent array `par` (the labels): every access is an agent-scope atomic, parents only fall and stay inside the component
+__device__ __forceinline__ int uf_find(int32_t* par, int x) {
+    for (;;) {
+        const int p = ald(par + x);
+        if (p == x) return x;
+        const int gp = ald(par + p);
+        if (gp < p) __hip_atomic_fetch_min(par + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (path halving)
+        x = p;
+    }
+}
+
+__global__ __launch_bounds__(256) void hook_kernel(View g, Cells c, int n, double range, Wide w, int32_t* par) {
+#pragma clang fp contract(off)
+    const int slot = blockIdx.x * 256 + threadIdx.x;
+    if (slot >= n) return;
+    const float4 me = w.sorted[slot];
+    const int a = __float_as_int(me.w);
+    if (a < 0 || a >= n) return;  // (never: the scatter filled every slot)
+    const int lo = cell_of(c, g, me.x, me.y);
+    const int cy = lo / c.ncx, cx = lo - cy * c.ncx;
+    for (int yy = max(cy - 1, 0); yy <= min(cy + 1, c.ncy - 1); yy++)
+        for (int xx = max(cx - 1, 0); xx <= min(cx + 1, c.ncx - 1); xx++) {
+            const int cell = yy * c.ncx + xx, b = max(w.cell_start[cell], 0), e = min(w.cell_start[cell + 1], n);
+            for (int t = b; t < e; t++) {
+                const float4 o = w.sorted[t];
+                const int j = __float_as_int(o.w);
+                if (j >= a || j < 0) continue;  // (every pair once, by its larger id)
+                const double d0 = fabs((double)(me.x - o.x)), d1 = fabs((double)(me.y - o.y)), d2 = fabs((double)(me.z - o.z));
+                if (!(fmax(d0, fmax(d1, d2)) < range)) continue;
+                int ra = uf_find(par, a), rb = uf_find(par, j);
+                while (ra != rb) {  // hook the root with the larger id under the smaller
+                    const int big = max(ra, rb), small = min(ra, rb);
+                    int expect = big;
+                    if (__hip_atomic_compare_exchange_strong(par + big, &expect, small, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+                    ra = uf_find(par, big), rb = uf_find(par, small);
+                }
+            }
+        }
+}
+
+// every agent's label becomes its root (roots do not move here: whatever a lane reads on the way is an ancestor); the roots count their members
+__global__ __launch_bounds__(256) void flatten_kernel(int n, Scratch s) {
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= n) return;
+    int x = a;
+    for (int p = ald(s.label + x); p != x; p = ald(s.label + x)) x = p;
+    __hip_atomic_store(s.label + a, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    atomicAdd(s.gsize + x, 1);
+}
+
+// one workgroup: the groups of more than one agent in the order of their roots -- segstart[root], grouplist[k] = root, misc[0] = their number
+__global__ __launch_bounds__(1024) void segments_kernel(int n, Scratch s, Wide w) {
+    __shared__ int sh[1024];
+    const int tid = threadIdx.x, per = (n + 1023) / 1024, lo = min(tid * per, n), hi = min(lo + per, n);
+    int members = 0, groups = 0;
+    for (int a = lo; a < hi; a++) {
+        const int sz = s.label[a] == a ? s.gsize[a] : 0;
+        if (sz > 1) members += sz, groups++;
+    }
+    int total_members, total_groups;
+    int run_m = block_scan<1024>(members, sh, &total_members), run_g = block_scan<1024>(groups, sh, &total_groups);
+    for (int a = lo; a < hi; a++) {
+        const int sz = s.label[a] == a ? s.gsize[a] : 0;
+        w.fill[a] = 0;
+        w.segstart[a] = run_m;
+        if (sz > 1) {
+            w.grouplist[run_g++] = a;
+            run_m += sz;
+        }
+    }
+    if (tid == 0) w.misc[0] = total_groups, w.misc[1] = 0;
+}
+
+// the update filter's tests (a)-(c) of decide_kernel for one agent whose desired node is d
+__device__ __forceinline__ int filter_abc(const View& g, double range, int M, int dim, const double* __restrict__ state, const double* __restrict__ plan,
+                                          const double* __restrict__ cur_goal, const double* waypoint, int64_t a, int d) {
+#pragma clang fp contract(off)
+    const float zf = (float)g.z_2d;
+    const int dy_ = d / g.W, dx_ = d - dy_ * g.W;
+    const float des[3] = {node_coord(g.gmin0, dx_, g.res), node_coord(g.gmin1, dy_, g.res), zf};
+    bool in_range = true;
+    if (range > 0) {
+        for (int m = 0; m <= M && in_range; m++) {
+            double dist = 0;
+            for (int k = 0; k < 3; k++) {
+                float q;
+                if (plan == nullptr) q = (float)state[a * 9 + k];
+                else if (k >= dim) q = zf;
+                else q = (float)plan[a * dim * M * 6 + ((int64_t)k * M + (m < M ? m : M - 1)) * 6 + (m < M ? 0 : 5)];
+                const double dk = fabs((double)(des[k] - q));
+                dist = dist < dk ? dk : dist;
+            }
+            if (dist > 0.5 * range - kEpsFloat) in_range = false;
+        }
+    }
+    float nw = 0, ng = 0;
+    for (int k = 0; k < 3; k++) {
+        const float wv = (float)waypoint[a * 3 + k], e = des[k] - wv, h = (float)cur_goal[a * 3 + k] - wv;
+        nw += e * e;
+        ng += h * h;
+    }
+    return (in_range && sqrt((double)nw) > kEpsFloat && sqrt((double)ng) < kEpsFloat) ? 1 : 0;
+}
+
+// agents alone in their group decide and filter by themselves (nobody can hold their node: blocker stays -1); the others drop their key --
+// ascending keys are init_d descending, then id descending, PIBT's priority at the first timestep -- into their group's segment
+__global__ __launch_bounds__(256) void place_kernel(View g, int n, double range, int M, int dim, const double* __restrict__ state,
+                                                    const double* __restrict__ plan, const double* __restrict__ cur_goal,
+                                                    const int32_t* __restrict__ init_d, const double* waypoint, Scratch s, Wide w,
+                                                    int32_t* __restrict__ group_out, int32_t* __restrict__ desired_out) {
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= n) return;
+    const int la = s.label[a];
+    if (s.gsize[la] == 1) {
+        const int v = choose_alone(s, a), d = v < 0 ? s.cur[a] : v;
+        s.vnext[a] = d;
+        s.keep[a] = filter_abc(g, range, M, dim, state, plan, cur_goal, waypoint, a, d);
+        desired_out[a] = d;
+        group_out[a] = la;
+        return;
+    }
+    const int slot = w.segstart[la] + atomicAdd(w.fill + la, 1);
+    if (slot >= 0 && slot < n) w.keys[slot] = ((uint64_t)(~((uint32_t)init_d[a] ^ 0x80000000u)) << 32) | (uint32_t)~(uint32_t)a;
+}
+
+__device__ __forceinline__ unsigned table_hash(int node, unsigned mask) { return ((unsigned)node * 2654435761u >> 7) & mask; }
+
+// the slot of `node` in a group's table, -1 where the table has none (both node tables then hold 0 there)
+__device__ __forceinline__ int table_find(const int32_t* tkey, unsigned mask, int node) {
+    for (unsigned h = table_hash(node, mask), probes = 0; probes <= mask; h = (h + 1) & mask, probes++) {
+        const int k = ldv(tkey + h);
+        if (k == node) return (int)h;
+        if (k < 0) return -1;
+    }
+    return -1;
+}
+
+__device__ __forceinline__ void key_swap(uint64_t* kk, int i, int j) {
+    const uint64_t x = kk[i], y = kk[j];
+    if (y < x) kk[i] = y, kk[j] = x;
+}
+
+// one workgroup per group of more than one agent; agent ids are global throughout
+__global__ __launch_bounds__(kWideThreads) void wide_walk_kernel(View g, int n, double range, int M, int dim, const double* __restrict__ state,
+                                                                 const double* __restrict__ plan, const double* __restrict__ cur_goal,
+                                                                 const double* waypoint, Scratch s, Wide w, int32_t* __restrict__ group_out,
+                                                                 int32_t* __restrict__ desired_out) {
+    __shared__ uint64_t keys_sh[kWideLdsKeys];
+    __shared__ int32_t table_sh[3 * kWideLdsCap];
+    __shared__ int fail_sh;
+    if ((int)blockIdx.x >= w.misc[0]) return;
+    const int tid = threadIdx.x, T = kWideThreads;
+    const int root = w.grouplist[blockIdx.x], gs = w.segstart[root], ng = s.gsize[root];
+    if (root < 0 || root >= n || ng < 2 || gs < 0 || gs > n - ng) return;  // (never: the segments are the scan of these sizes)
+    // -- the order: the segment's keys ascending, by a bitonic network whose comparators all point the same way -- the slots from ng up to the
+    // next power of two hold keys larger than any and never move, so a comparator that reaches one is skipped
+    uint64_t* kk = w.keys + gs;
+    if (ng <= kWideLdsKeys) {
+        for (int i = tid; i < ng; i += T) keys_sh[i] = kk[i];
+        kk = keys_sh;
+    }
+    if (tid == 0) fail_sh = 0;
+    __syncthreads();
+    int p2 = 1;
+    while (p2 < ng) p2 <<= 1;
+    for (int size = 2; size <= p2; size <<= 1) {
+        const int half = size >> 1;
+        for (int t = tid; t < (p2 >> 1); t += T) {
+            const int blk = t / half, off = t - blk * half, i = blk * size + off, j = blk * size + size - 1 - off;
+            if (j < ng) key_swap(kk, i, j);
+        }
+        __syncthreads();
+        for (int stride = half >> 1; stride >= 1; stride >>= 1) {
+            for (int t = tid; t < (p2 >> 1); t += T) {
+                const int i = 2 * stride * (t / stride) + t % stride, j = i + stride;
+                if (j < ng) key_swap(kk, i, j);
+            }
+            __syncthreads();
+        }
+    }
+    int32_t* order = s.order + gs;
+    for (int i = tid; i < ng; i += T) order[i] = (int)~(uint32_t)kk[i];
+    // -- the group's node tables: slots for the members' nodes and the nodes they take, at most half full
+    int cap = 8;
+    while (cap < 4 * ng) cap <<= 1;
+    const unsigned mask = (unsigned)cap - 1u;
+    int32_t* tkey = cap <= kWideLdsCap ? table_sh : w.table + 24 * (int64_t)gs;
+    int32_t *now = tkey + cap, *next = now + cap;
+    for (int i = tid; i < cap; i += T) tkey[i] = -1, now[i] = 0, next[i] = 0;
+    __syncthreads();
+    // -- PIBT::run's planning loop for the first timestep over this group, by ONE wavefront: decide_kernel's loop, the node tables looked up by key
+    if (tid < 64) {
+        const int lane = tid;
+        const int bound = 4 * ng + 16;
+        int passes = 0, fail = 0;
+        int32_t* stack = s.stack + gs;
+        for (int idx = lane; idx < ng; idx += 64) {  // occupied_now: the last id wins
+            const int a = order[idx], node = s.cur[a];
+            for (unsigned h = table_hash(node, mask), probes = 0; probes <= mask; h = (h + 1) & mask, probes++) {
+                const int was = atomicCAS(tkey + h, -1, node);
+                if (was == -1 || was == node) {
+                    atomicMax(now + h, a + 1);
+                    break;
+                }
+            }
+        }
+        __threadfence_block();
+        __builtin_amdgcn_wave_barrier();
+        for (int idx = 0; idx < ng && !fail; idx++) {
+            const int a0 = order[idx];
+            if (ldv(s.vnext + a0) != -1) continue;
+            int sp = 0, mode = 0;  // mode 0: call or "the child failed" (plan a step), 1: the callee returned true
+            stv(stack, a0);
+            while (sp >= 0) {
+                if (++passes > bound) {
+                    fail = 1;
+                    break;
+                }
+                if (mode == 1) {
+                    sp--;
+                    continue;
+                }
+                const int ai = ldv(stack + sp), cur_i = s.cur[ai];
+                // chooseNode, candidates in the identity order (one of the orders std::shuffle can draw)
+                int u = -1, cu = 0, held = 0, ok = 0, aj = -1;
+                if (lane < 5) {
+                    u = s.cand[(int64_t)ai * 5 + lane];
+                    cu = s.cost[(int64_t)ai * 5 + lane];
+                    if (u >= 0) {
+                        const int sl = table_find(tkey, mask, u);
+                        aj = sl >= 0 ? ldv(now + sl) - 1 : -1;
+                        held = aj >= 0;
+                        ok = sl < 0 || ldv(next + sl) == 0;                // vertex conflict
+                        if (ok && aj >= 0) ok = ldv(s.vnext + aj) != cur_i;  // swap conflict
+                    }
+                }
+                int v = -1, cv = 0, hv = 0, jv = -1;
+                for (int c = 0; c < 5; c++) {
+                    const int uc = __shfl(u, c), cc = __shfl(cu, c), hc = __shfl(held, c), oc = __shfl(ok, c), jc = __shfl(aj, c);
+                    if (!oc) continue;
+                    if (cc == 0) {  // the goal: taken at once
+                        v = uc, jv = jc;
+                        break;
+                    }
+                    if (v < 0 || cc < cv || (cc == cv && hv && !hc)) v = uc, cv = cc, hv = hc, jv = jc;
+                }
+                // (every lane finds or makes the slot of the node taken, the same one)
+                const int take = v < 0 ? cur_i : v;
+                int sl = -1;
+                for (unsigned h = table_hash(take, mask), probes = 0; probes <= mask; h = (h + 1) & mask, probes++) {
+                    const int k = ldv(tkey + h);
+                    if (k == take || k < 0) {
+                        if (k < 0) stv(tkey + h, take);
+                        sl = (int)h;
+                        break;
+                    }
+                }
+                if (sl < 0) {  // (never: the table is at most half full)
+                    fail = 1;
+                    break;
+                }
+                if (v < 0) {  // failed to secure a node: stay, and tell the caller
+                    stv(next + sl, ai + 1);
+                    stv(s.vnext + ai, cur_i);
+                    stv(s.blocker + ai, -1);
+                    sp--;
+                    mode = 0;
+                    continue;
+                }
+                stv(next + sl, ai + 1);
+                stv(s.vnext + ai, v);
+                stv(s.blocker + ai, (jv != ai && v != cur_i) ? jv : -1);
+                if (jv >= 0 && jv != ai && ldv(s.vnext + jv) == -1) {  // priority inheritance
+                    sp++;
+                    if (sp >= ng) {  // (never: an agent is entered once)
+                        fail = 1;
+                        break;
+                    }
+                    stv(stack + sp, jv);
+                    mode = 0;
+                    continue;
+                }
+                sp--;
+                mode = 1;
+            }
+        }
+        if (fail && lane == 0) {
+            fail_sh = 1;
+            __hip_atomic_store(w.misc + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    // -- the update filter for the members: (a)-(c), then "find valid update" -- `blocker` is a member, the fixed point stays in the group
+    for (int i = tid; i < ng; i += T) {
+        const int a = order[i], vn = ldv(s.vnext + a), d = vn < 0 ? s.cur[a] : vn;
+        stv(s.keep + a, filter_abc(g, range, M, dim, state, plan, cur_goal, waypoint, a, d));
+        desired_out[a] = d;
+        group_out[a] = root;
+    }
+    __syncthreads();
+    for (int round = 0; round <= ng; round++) {
+        int changed = 0;
+        for (int i = tid; i < ng; i += T) {
+            const int a = order[i];
+            if (!ldv(s.keep + a)) continue;
+            const int j = ldv(s.blocker + a);
+            if (j >= 0 && s.onnode[j] && !ldv(s.keep + j)) {
+                stv(s.keep + a, 0);
+                changed = 1;
+            }
+        }
+        if (!__syncthreads_or(changed)) break;
+    }
+}
+
+__global__ __launch_bounds__(256) void apply_kernel(View g, int n, Scratch s, Wide w, const int32_t* __restrict__ desired, double* __restrict__ waypoint,
+                                                    int32_t* __restrict__ updated_out) {
+#pragma clang fp contract(off)
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= n) return;
+    const int fail = w.misc[1], up = !fail && s.keep[a];
+    if (up) {
+        const int d = desired[a], dy_ = d / g.W, dx_ = d - dy_ * g.W;
+        waypoint[(int64_t)a * 3 + 0] = (double)node_coord(g.gmin0, dx_, g.res);
+        waypoint[(int64_t)a * 3 + 1] = (double)node_coord(g.gmin1, dy_, g.res);
+        waypoint[(int64_t)a * 3 + 2] = (double)(float)g.z_2d;
+    }
+    updated_out[a] = up;
+    if (a == 0 && fail) *s.status = 1;
+}
+
 }  // namespace lscgrid
 
 struct lscqp_grid_s {
@@ -526,6 +954,10 @@ struct lscqp_grid_s {
     int32_t* d_status_k = nullptr;  // [missions]
     int32_t* d_tables_k = nullptr;  // [missions][2][nodes], all zero between launches
     std::vector<int64_t> fields_off;  // the partition of the last lscqp_grid_fields_missions_device: the one the copies were cleared for
+    // the wide form of the decision (lscqp_grid_reserve_wide)
+    int64_t wide_reserved = 0;
+    void* d_wide = nullptr;
+    lscgrid::Wide w;
 };
 
 namespace {
@@ -624,7 +1056,7 @@ void lscqp_grid_destroy(lscqp_grid g) {
     int prev = -1;
     if (hipGetDevice(&prev) == hipSuccess && prev != g->device) (void)hipSetDevice(g->device);
     (void)hipDeviceSynchronize();
-    for (void* p : {(void*)g->d_occ, (void*)g->d_occ_mission, (void*)g->d_agent_scratch, (void*)g->d_tables, (void*)g->d_occ_k, (void*)g->d_status_k, (void*)g->d_tables_k})
+    for (void* p : {(void*)g->d_occ, (void*)g->d_occ_mission, (void*)g->d_agent_scratch, (void*)g->d_tables, (void*)g->d_occ_k, (void*)g->d_status_k, (void*)g->d_tables_k, g->d_wide})
         if (p) (void)hipFree(p);
     if (prev >= 0 && prev != g->device) (void)hipSetDevice(prev);
     delete g;
@@ -722,6 +1154,79 @@ int lscqp_waypoints_device(lscqp_grid g, double communication_range, int32_t M, 
     hipLaunchKernelGGL(lscgrid::decide_kernel<false>, dim3(1), dim3(lscgrid::kDecideThreads), in_lds ? (table_bytes + 15) / 16 * 16 : 0, st, g->v, n, communication_range,
                        (int)M, (int)dim, in_lds, d_state, d_plan, d_current_goal, d_init_d, d_waypoint, g->s, d_group_out, d_desired_out, d_updated_out,
                        (const int64_t*)nullptr);
+    GRID_HIP(hipGetLastError());
+    return LSCQP_OK;
+}
+
+int lscqp_grid_reserve_wide(lscqp_grid g, int64_t n) {
+    if (!g || n < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
+    {
+        const int rc = lscqp_grid_reserve(g, n);
+        if (rc != LSCQP_OK) return rc;
+    }
+    if (n <= g->wide_reserved) return LSCQP_OK;
+    GRID_HIP(hipDeviceSynchronize());
+    if (g->d_wide) GRID_HIP(hipFree(g->d_wide));
+    g->d_wide = nullptr;
+    g->wide_reserved = 0;
+    const size_t r = (size_t)n, cells = 2 * r + 17;
+    const size_t ints = 3 * r + 3 * cells + 24 * r + 4;
+    GRID_HIP(hipMalloc(&g->d_wide, r * sizeof(float4) + r * sizeof(uint64_t) + ints * sizeof(int32_t)));
+    lscgrid::Wide& w = g->w;
+    w.sorted = (float4*)g->d_wide;
+    w.keys = (uint64_t*)(w.sorted + r);
+    int32_t* b = (int32_t*)(w.keys + r);
+    w.segstart = b, w.fill = b + r, w.grouplist = b + 2 * r;
+    w.cell_count = b + 3 * r, w.cell_fill = w.cell_count + cells, w.cell_start = w.cell_fill + cells;
+    w.table = w.cell_start + cells;
+    w.misc = w.table + 24 * r;
+    g->wide_reserved = n;
+    return LSCQP_OK;
+}
+
+int lscqp_waypoints_wide_device(lscqp_grid g, double communication_range, int32_t M, int32_t dim, int64_t n, const double* d_state, const double* d_plan,
+                                const double* d_current_goal, const int32_t* d_field, const int32_t* d_init_d, double* d_waypoint, int32_t* d_group_out,
+                                int32_t* d_desired_out, int32_t* d_updated_out, void* stream) {
+    if (!g || n < 0 || (n > 0 && (!d_state || !d_current_goal || !d_field || !d_init_d || !d_waypoint || !d_group_out || !d_desired_out || !d_updated_out)))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (dim != 2) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_waypoints_wide_device is 2-D only");
+    if (d_plan && M < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "M must be positive");
+    if (!(communication_range == communication_range)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "communication_range is NaN");
+    if (n == 0) return LSCQP_OK;
+    if (n > g->wide_reserved || n > g->reserved) {  // (synchronises and allocates: a caller that captures the launch reserves beforehand)
+        const int rc = lscqp_grid_reserve_wide(g, n);
+        if (rc != LSCQP_OK) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const double range = communication_range;
+    const int ni = (int)n;
+    const dim3 per_agent((unsigned)((n + 255) / 256)), b256(256);
+    const lscgrid::Scratch& s = g->s;
+    const lscgrid::Wide& w = g->w;
+    hipLaunchKernelGGL(lscgrid::gather_kernel<false>, per_agent, b256, 0, st, g->v, n, range, g->d_occ_mission, d_waypoint, d_field, s, (const int64_t*)nullptr, 0);
+    if (range > 0) {
+        // the cell side: the range and a margin for the rounding of the float32 subtraction in the test, enlarged until 2 n + 16 cells cover the
+        // grid's box (positions outside fall into the edge cells)
+        const double lx = (g->dims[0] - 1) * g->v.res, ly = (g->dims[1] - 1) * g->v.res, limit = 2.0 * (double)n + 16.0;
+        lscgrid::Cells c;
+        c.side = 1.0001 * range;
+        while ((floor(lx / c.side) + 1.0) * (floor(ly / c.side) + 1.0) > limit) c.side *= 1.25;
+        c.ncx = (int)floor(lx / c.side) + 1, c.ncy = (int)floor(ly / c.side) + 1;
+        const int ncell = c.ncx * c.ncy;
+        hipLaunchKernelGGL(lscgrid::wide_zero_kernel, dim3((unsigned)((ncell + 1 + 255) / 256)), b256, 0, st, ncell + 1, w.cell_count, w.cell_fill);
+        hipLaunchKernelGGL(lscgrid::cell_count_kernel, per_agent, b256, 0, st, g->v, c, ni, d_state, w);
+        hipLaunchKernelGGL(lscgrid::cell_scan_kernel, dim3(1), dim3(1024), 0, st, ncell, w);
+        hipLaunchKernelGGL(lscgrid::cell_scatter_kernel, per_agent, b256, 0, st, g->v, c, ni, d_state, w);
+        hipLaunchKernelGGL(lscgrid::hook_kernel, per_agent, b256, 0, st, g->v, c, ni, range, w, s.label);
+    }
+    hipLaunchKernelGGL(lscgrid::flatten_kernel, per_agent, b256, 0, st, ni, s);
+    hipLaunchKernelGGL(lscgrid::segments_kernel, dim3(1), dim3(1024), 0, st, ni, s, w);
+    hipLaunchKernelGGL(lscgrid::place_kernel, per_agent, b256, 0, st, g->v, ni, range, (int)M, (int)dim, d_state, d_plan, d_current_goal, d_init_d,
+                       (const double*)d_waypoint, s, w, d_group_out, d_desired_out);
+    // (a group to walk has two members or more: n / 2 workgroups at the most, the ones beyond the number of groups return at once)
+    hipLaunchKernelGGL(lscgrid::wide_walk_kernel, dim3((unsigned)((n + 1) / 2)), dim3(lscgrid::kWideThreads), 0, st, g->v, ni, range, (int)M, (int)dim, d_state, d_plan,
+                       d_current_goal, (const double*)d_waypoint, s, w, d_group_out, d_desired_out);
+    hipLaunchKernelGGL(lscgrid::apply_kernel, per_agent, b256, 0, st, g->v, ni, s, w, (const int32_t*)d_desired_out, d_waypoint, d_updated_out);
     GRID_HIP(hipGetLastError());
     return LSCQP_OK;
 }

@@ -229,6 +229,9 @@ struct lscqp_plan_s {
     int64_t* d_moff = nullptr;
     bool missions_pending = false;  // the partition changed and lscqp_plan_reset has not come yet
     int n_missions() const { return moff.empty() ? 1 : (int)moff.size() - 1; }
+    // which form of the waypoint decision heads the chain (lscqp_plan_set_waypoint_decision)
+    int decision = LSCQP_DECISION_ONE_WORKGROUP;
+    bool wide() const { return decision == LSCQP_DECISION_WIDE || (decision == LSCQP_DECISION_AUTO && s.n_total >= LSCQP_DECISION_AUTO_MIN_AGENTS); }
 };
 
 namespace {
@@ -297,6 +300,9 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
             PLAN_TRY(lscqp_waypoints_missions_device(p->grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, K, p->moff.data(), p->d_moff,
                                                      state, x_plan, goal, p->field, p->init_d, waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], p->desired_node,
                                                      (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
+        else if (p->wide())
+            PLAN_TRY(lscqp_waypoints_wide_device(p->grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, state, x_plan, goal, p->field, p->init_d,
+                                                 waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], p->desired_node, (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
         else
             PLAN_TRY(lscqp_waypoints_device(p->grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, state, x_plan, goal, p->field, p->init_d,
                                             waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], p->desired_node, (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
@@ -384,6 +390,7 @@ int make_grid(lscqp_plan_s* p, double resolution) {
     const hipError_t e = hipMalloc(&f, (size_t)p->s.n_total * dims[0] * dims[1] * sizeof(int32_t));
     int rc = e != hipSuccess ? hip_fail(e, "hipMalloc(distance fields)")
                              : (p->n_missions() > 1 ? lscqp_grid_reserve_missions_(gnew, p->s.n_total, p->n_missions()) : lscqp_grid_reserve(gnew, p->s.n_total));
+    if (rc == LSCQP_OK && p->decision != LSCQP_DECISION_ONE_WORKGROUP) rc = lscqp_grid_reserve_wide(gnew, p->s.n_total);
     if (rc != LSCQP_OK) {
         if (f) (void)hipFree(f);
         lscqp_grid_destroy(gnew);
@@ -752,6 +759,8 @@ int lscqp_plan_set_missions(lscqp_plan p, int32_t n_missions, const int64_t* mis
         if (p->s.n_agents != p->s.n_total)
             return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "a mission partition needs every agent on this device (n_agents == n_total): a sharded plan flies one mission");
         PLAN_TRY(lscqp_check_missions_(p->s.n_total, n_missions, mission_offsets));
+        if (p->decision != LSCQP_DECISION_ONE_WORKGROUP)
+            return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "a partition of more than one mission keeps one workgroup per mission: set LSCQP_DECISION_ONE_WORKGROUP first");
     }
     DeviceGuard g(p->device);
     hipError_t e = hipDeviceSynchronize();
@@ -776,6 +785,22 @@ int lscqp_plan_set_missions(lscqp_plan p, int32_t n_missions, const int64_t* mis
     drop_graph(p);  // (a captured chain holds the old partition's launches)
     p->fields_valid = false;
     p->missions_pending = true;
+    return LSCQP_OK;
+}
+
+int lscqp_plan_set_waypoint_decision(lscqp_plan p, int32_t which) {
+    if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
+    if (which != LSCQP_DECISION_ONE_WORKGROUP && which != LSCQP_DECISION_WIDE && which != LSCQP_DECISION_AUTO)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "which must be LSCQP_DECISION_ONE_WORKGROUP, LSCQP_DECISION_WIDE or LSCQP_DECISION_AUTO");
+    if (!p->grid) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the plan decides no waypoints (waypoint_mode = LSCQP_WAYPOINT_FROM_CALLER)");
+    if (which != LSCQP_DECISION_ONE_WORKGROUP && p->n_missions() > 1)
+        return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "a partition of more than one mission keeps one workgroup per mission");
+    DeviceGuard g(p->device);
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_waypoint_decision");
+    if (which != LSCQP_DECISION_ONE_WORKGROUP) PLAN_TRY(lscqp_grid_reserve_wide(p->grid, p->s.n_total));  // (before the plan changes)
+    drop_graph(p);  // (a captured chain holds the other form's launches)
+    p->decision = which;
     return LSCQP_OK;
 }
 

@@ -169,14 +169,19 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     return log
 
 
-def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None, router="host", missions=None):
+def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None, router="host", missions=None,
+        decision="one"):
     """script (optional): {"waypoint": (K, N, 3), "state": (K, N, 9)} -- replay of a recorded mission: replan k takes every agent's
     state and waypoint from the script instead of the loop's own step / router (the plans, goal points, corridors and neighbour sets are
     still the loop's own), and the result carries every replan's solution (`x`, (K, N, nv)) and goal point (`goal`, (K, N, 3)).
     router: "host" (GridRouter) or "device" (lscqp_waypoints_device over the previous plans, states and goal points).
-    missions: K > 0 flies K seeded missions over the world in one lscqp_plan (run_missions) and reports per-mission figures."""
+    missions: K > 0 flies K seeded missions over the world in one lscqp_plan (run_missions) and reports per-mission figures.
+    decision (router "device"): "one" (lscqp_waypoints_device), "wide" (lscqp_waypoints_wide_device) or "auto" (wide from
+    DECISION_AUTO_MIN_AGENTS agents on); the flight is the same whichever is chosen."""
     if router not in ("host", "device"):
         raise ValueError("router must be 'host' or 'device'")
+    if decision not in ("one", "wide", "auto"):
+        raise ValueError("decision must be 'one', 'wide' or 'auto'")
     if missions:
         return run_missions(world_json, int(missions), steps=steps, M=M, dt=dt, n_obs=n_obs)
     import torch
@@ -242,6 +247,8 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
         d_field, d_init_d = grid.fields(up(starts), up(desired))
         d_way = up(np.float32(starts).astype(np.float64))
         updated_total = 0
+        use_wide = decision == "wide" or (decision == "auto" and N >= api.DECISION_AUTO_MIN_AGENTS)
+        decide = grid.waypoints_wide if use_wide else grid.waypoints
     waypoint = starts.copy()  # first waypoint: the start node itself; it advances in the loop
     goal_pt = starts.copy()   # agent.current_goal_point
     log = {"steps": steps, "agents": N, "qp_failed": 0, "invalid": 0, "sfc_kept": 0, "goal_infeasible": 0, "min_safety_ratio": np.inf,
@@ -261,7 +268,7 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
             state, waypoint = np.array(script["state"][step], dtype=np.float64), np.array(script["waypoint"][step], dtype=np.float64)
         elif use_device_router:
             # decentralizedMAPP: one PIBT step per communication group from the plans as the last replan left them, then the update filter
-            _, _, d_upd = grid.waypoints(comm_range, M, dim, up(state), d_xprev, up(goal_pt), d_field, d_init_d, d_way)
+            _, _, d_upd = decide(comm_range, M, dim, up(state), d_xprev, up(goal_pt), d_field, d_init_d, d_way)
             waypoint = d_way.cpu().numpy().reshape(N, 3)
             updated_total += int(d_upd.sum().item())
         else:
@@ -356,6 +363,7 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
     # occupancy check of the flown positions: the agents (L-infinity radius) never touch an occupied cell
     log["router"] = router
     if use_device_router:
+        log["decision"] = "wide" if use_wide else "one"
         log["waypoints_updated"] = updated_total
         assert grid.status() == 0
         grid.close()
@@ -372,7 +380,9 @@ if __name__ == "__main__":
     ap.add_argument("--obs", type=int, default=None, help="neighbour capacity per agent")
     ap.add_argument("--dump", default=None, help="npz path: inputs of the first replan with a failed QP")
     ap.add_argument("--missions", type=int, default=0, help="K > 0: K seeded missions over the world in ONE plan with a mission partition, figures per mission")
+    ap.add_argument("--decision", default="one", choices=("one", "wide", "auto"),
+                    help="with --router device: the one-workgroup decision, lscqp_waypoints_wide_device, or wide from DECISION_AUTO_MIN_AGENTS agents on")
     ap.add_argument("--router", default="host", choices=("host", "device"), help="where the waypoints come from: the host stand-in or lscqp_waypoints_device")
     a = ap.parse_args()
     world = random_forest_world(a.forest) if a.forest > 0 else a.world
-    print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router, missions=a.missions)))
+    print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router, missions=a.missions, decision=a.decision)))

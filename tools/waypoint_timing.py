@@ -15,8 +15,13 @@
                                                                     the driver of `missions`: fresh child processes, interleaved
     python tools/waypoint_timing.py --part decision --missions K    the decision alone: one workgroup per mission against the single-workgroup
                                                                     decision over the same 10 K agents
+    python tools/waypoint_timing.py --part decision_wide [--agents-list 10,64,512,4096]
+                                                                    lscqp_waypoints_device against lscqp_waypoints_wide_device on the 201 x 201
+                                                                    grid at ranges -1, 3, 2, 1 m: same inputs, outputs compared equal first,
+                                                                    then timed in the same process, interleaved
+    --decision 0|1|2 with --part chain / chains (mode 1)            the plan's lscqp_plan_set_waypoint_decision; chains adds a mode-1 WIDE variant
 
-Every part prints JSON lines; profiles/r09_waypoints.txt and profiles/r10_missions.txt are transcripts."""
+Every part prints JSON lines; profiles/r09_waypoints.txt, profiles/r10_missions.txt and profiles/r12_waypoints_wide.txt are transcripts."""
 import argparse
 import json
 import os
@@ -124,10 +129,12 @@ def part_chain(a):
     ag["radius"], ag["downwash"], ag["max_vel"], ag["max_acc"], ag["nominal_velocity"] = W["radius"], 2.0, 1.0, 2.0, 1.0
     kw = dict(waypoint_mode=1) if a.mode == 1 else {}
     plan = api.Plan(sol, wmap, N, n_obs, ag, constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, closed_loop=True, z_2d=W["z_2d"], **kw)
+    if a.decision:
+        plan.set_waypoint_decision(a.decision)
     router = closed_loop.GridRouter(W, wmap.download()[0], wmap.key0) if a.mode == 0 else None
     starts, desired = np.array(W["starts"], dtype=np.float64), np.array(W["goals"], dtype=np.float64)
     # (host wall time around step + synchronise, the figure a caller feels; the kernels part uses device events)
-    out = dict(what="chain", clock="host wall time around step + synchronize", agents=N, mode=a.mode, lib=os.path.dirname(api.__file__), steps=a.steps)
+    out = dict(what="chain", clock="host wall time around step + synchronize", agents=N, mode=a.mode, decision=a.decision, lib=os.path.dirname(api.__file__), steps=a.steps)
     for form in ("eager", "graph"):
         plan.reset(starts, desired) if a.mode == 1 else plan.reset(starts)
         way = starts.copy()
@@ -156,9 +163,9 @@ def part_chain(a):
 
 def part_chains(a):
     me = os.path.abspath(__file__)
-    variants = [("mode0", ["--mode", "0"]), ("mode1", ["--mode", "1"])]
+    variants = [("mode0", ["--mode", "0"]), ("mode1", ["--mode", "1"]), ("mode1_wide", ["--mode", "1", "--decision", "1"])]
     if a.parent:
-        variants = [("parent_mode0", ["--mode", "0", "--tree", a.parent]), variants[0], ("parent_mode1", ["--mode", "1", "--tree", a.parent]), variants[1]]
+        variants = [("parent_mode0", ["--mode", "0", "--tree", a.parent]), variants[0], ("parent_mode1", ["--mode", "1", "--tree", a.parent]), variants[1], variants[2]]
     res = {k: [] for k, _ in variants}
     for _ in range(a.runs):
         for name, extra in variants:  # interleaved: one run of each, then the next round
@@ -288,6 +295,59 @@ def part_decision(a):
     wmap.close()
 
 
+def part_decision_wide(a):
+    """The one-workgroup decision and the wide one on the 201 x 201 grid of `kernels`, same inputs: hover plans at distinct free nodes.  Per
+    agent count and range the outputs of the two are compared equal first; then `rounds` rounds of (repeats / rounds one-workgroup calls,
+    repeats / rounds wide calls) are timed with HIP events, and the medians are over all of a form's calls."""
+    import torch
+
+    from lsc_dr_planner_amd import api
+
+    dev = torch.device("cuda", 0)
+    up = lambda x, dt=np.float64: torch.from_numpy(np.ascontiguousarray(x, dtype=dt)).to(dev)  # noqa: E731
+    w = _forest(100.0, 3000)
+    wmap = api.WorldMap(w["boxes"], w["world_min"], w["world_max"], w["resolution"], w["max_dist"])
+    grid = api.Grid(wmap, 0.5, w["radius"], w["z_2d"])
+    occ = grid.download()
+    M, rounds = 10, 4
+    for n in [int(v) for v in a.agents_list.split(",")]:
+        starts, goals = _free_nodes(occ, grid.grid_min, n, 1, True), _free_nodes(occ, grid.grid_min, n, 2, False)
+        d_field, d_init = grid.fields(up(starts), up(goals))
+        st = np.zeros((n, 9))
+        st[:, :3] = starts
+        x = np.repeat(starts[:, :2, None], M * 6, axis=2).reshape(n, -1)  # hover plans
+        d_st, d_x, d_cg, d_way0 = up(st), up(x), up(np.float32(starts).astype(float)), up(np.float32(starts).astype(float))
+        d_way = d_way0.clone()
+        grid.reserve_wide(n)
+        forms = (("one_workgroup", grid.waypoints), ("wide", grid.waypoints_wide))
+        for rng in (-1.0, 3.0, 2.0, 1.0):
+            outs = {}
+            for name, fn in forms:
+                d_way.copy_(d_way0)
+                g, d, u = fn(rng, M, 2, d_st, d_x, d_cg, d_field, d_init, d_way)
+                torch.cuda.synchronize()
+                outs[name] = (g.clone(), d.clone(), u.clone(), d_way.clone())
+            assert grid.status() == 0
+            assert all(torch.equal(p, q) for p, q in zip(outs["one_workgroup"], outs["wide"])), "the two forms disagree: nothing is timed"
+            g, _, u, _ = outs["wide"]
+            sizes = torch.bincount(g.long())
+            t = {name: [] for name, _ in forms}
+            per = max(1, a.repeats // rounds)
+            for _ in range(rounds):  # interleaved
+                for name, fn in forms:
+                    r = _events(torch, lambda: fn(rng, M, 2, d_st, d_x, d_cg, d_field, d_init, d_way), per, 5, before=lambda: d_way.copy_(d_way0))
+                    t[name].append(r["median_us"])
+            row = dict(what="decision_wide", grid="201x201", agents=n, range=rng, groups=int((sizes > 0).sum().item()), groups_walked=int((sizes > 1).sum().item()),
+                       largest_group=int(sizes.max().item()), waypoints_moved=int(u.sum().item()), calls_per_form=per * rounds)
+            for name, _ in forms:
+                row[name + "_us"] = round(float(np.median(t[name])), 1)
+                row[name + "_rounds_us"] = [round(v, 1) for v in t[name]]
+            row["one_over_wide"] = round(row["one_workgroup_us"] / row["wide_us"], 2)
+            print(json.dumps(row), flush=True)
+    grid.close()
+    wmap.close()
+
+
 def part_closed_loop(a):
     import closed_loop
 
@@ -306,7 +366,9 @@ def part_closed_loop(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", required=True, choices=("kernels", "chain", "chains", "closed_loop", "missions", "missions_sweep", "decision"))
+    ap.add_argument("--part", required=True, choices=("kernels", "chain", "chains", "closed_loop", "missions", "missions_sweep", "decision", "decision_wide"))
+    ap.add_argument("--agents-list", default="10,64,512,4096")
+    ap.add_argument("--decision", type=int, default=0)
     ap.add_argument("--missions", type=int, default=25)
     ap.add_argument("--missions-list", default="1,8,25")
     ap.add_argument("--agents", type=int, default=0)
@@ -321,7 +383,7 @@ def main():
         sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     {"kernels": part_kernels, "chain": part_chain, "chains": part_chains, "closed_loop": part_closed_loop, "missions": part_missions,
-     "missions_sweep": part_missions_sweep, "decision": part_decision}[a.part](a)
+     "missions_sweep": part_missions_sweep, "decision": part_decision, "decision_wide": part_decision_wide}[a.part](a)
 
 
 if __name__ == "__main__":
