@@ -10,7 +10,10 @@
 //               until a sweep changes nothing (a workgroup-wide vote) -- in LDS where the field fits, in its place in HBM otherwise
 //   waypoints   one replan's decision: candidates gathered by all lanes, then ONE workgroup: groups by min-label propagation, agents ordered by
 //               priority, the PIBT walk (sequential by nature: priority inheritance and backtracking) by one wavefront with an explicit
-//               stack, and the simulator's update filter by all lanes again
+//               stack, and the simulator's update filter by all lanes again.  A second, WIDE form spreads the same decision over the device
+//               (below).  The two forms share ONE walk (pibt_walk, over a dense or a keyed node table), ONE set of filter tests
+//               (filter_abc), ONE fixed point (find_valid_update) and ONE waypoint write (write_update); what differs stays in the kernels:
+//               how occupied_now is seeded, how the tables are cleared, and what the pass bound counts
 // A MISSION PARTITION (include/lscqp.h, "many missions over one map") cuts the agents into contiguous slices that share the map and nothing
 // else: one occupancy copy per mission (start and goal nodes are cleared in the agent's own copy only), and the decision as one workgroup per
 // mission over its slice, with node tables, order, stack, fail flag and walk bound of its own.
@@ -20,6 +23,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -263,6 +267,175 @@ __device__ __forceinline__ int choose_alone(const Scratch& s, int64_t a) {
     return v;
 }
 
+// ---- what the two forms of the decision share: the walk of one group, the update filter, the waypoint write ----------------------------------
+// occupied_now / occupied_next behind a slot index.  Dense: slot = node, every node has a slot (the one-workgroup form: LDS or the HBM slab)
+struct DenseTables {
+    int32_t *now, *next;
+    __device__ __forceinline__ int find(int node) const { return node; }
+    __device__ __forceinline__ int claim(int node) const { return node; }
+};
+
+__device__ __forceinline__ unsigned table_hash(int node, unsigned mask) { return ((unsigned)node * 2654435761u >> 7) & mask; }
+
+// Keyed: a group's own open-addressed table of mask + 1 slots (the wide form); a node without a slot reads as 0 in both tables
+struct KeyedTables {
+    int32_t *tkey, *now, *next;
+    unsigned mask;
+    __device__ __forceinline__ int find(int node) const {  // the slot of `node`, -1 where the table has none
+        for (unsigned h = table_hash(node, mask), probes = 0; probes <= mask; h = (h + 1) & mask, probes++) {
+            const int k = ldv(tkey + h);
+            if (k == node) return (int)h;
+            if (k < 0) return -1;
+        }
+        return -1;
+    }
+    __device__ __forceinline__ int claim(int node) const {  // find or insert, by every lane of the walking wavefront alike; -1: the table is full
+        for (unsigned h = table_hash(node, mask), probes = 0; probes <= mask; h = (h + 1) & mask, probes++) {
+            const int k = ldv(tkey + h);
+            if (k == node || k < 0) {
+                if (k < 0) stv(tkey + h, node);
+                return (int)h;
+            }
+        }
+        return -1;
+    }
+};
+
+// PIBT::run's planning loop for the first timestep over the members order[0..count) of ONE group, by ONE wavefront; occupied_now is seeded
+// by the caller.  Every lane runs the same control flow and issues the same stores (a lane then reads back what it wrote itself); lanes 0..4
+// look at one candidate each in chooseNode.  funcPIBT is entered at most once per agent and every entry plans once, plus once more after each
+// child that failed (a child fails at most once): <= 2 n plans and <= n returns that carry "true" upwards -- 3 n passes of the loop below.
+// `passes` counts them against `bound`, both the caller's; returns 1 where the bound was reached (the tables were corrupt), 0 otherwise.
+template <class Tables>
+__device__ __forceinline__ int pibt_walk(const Scratch& s, const Tables& t, const int32_t* order, int count, int32_t* stack, int lane, int& passes,
+                                         int bound) {
+    for (int idx = 0; idx < count; idx++) {
+        const int a0 = ldv(order + idx);
+        if (ldv(s.vnext + a0) != -1) continue;
+        int sp = 0, mode = 0;  // mode 0: call or "the child failed" (plan a step), 1: the callee returned true
+        stv(stack, a0);
+        while (sp >= 0) {
+            if (++passes > bound) return 1;
+            if (mode == 1) {
+                sp--;
+                continue;
+            }
+            const int ai = ldv(stack + sp), cur_i = s.cur[ai];
+            // chooseNode, candidates in the identity order (one of the orders std::shuffle can draw)
+            int u = -1, cu = 0, held = 0, ok = 0, aj = -1;
+            if (lane < 5) {
+                u = s.cand[(int64_t)ai * 5 + lane];
+                cu = s.cost[(int64_t)ai * 5 + lane];
+                if (u >= 0) {
+                    const int sl = t.find(u);
+                    aj = sl >= 0 ? ldv(t.now + sl) - 1 : -1;
+                    held = aj >= 0;
+                    ok = sl < 0 || ldv(t.next + sl) == 0;              // vertex conflict
+                    if (ok && aj >= 0) ok = ldv(s.vnext + aj) != cur_i;  // swap conflict
+                }
+            }
+            int v = -1, cv = 0, hv = 0, jv = -1;
+            for (int c = 0; c < 5; c++) {
+                const int uc = __shfl(u, c), cc = __shfl(cu, c), hc = __shfl(held, c), oc = __shfl(ok, c), jc = __shfl(aj, c);
+                if (!oc) continue;
+                if (cc == 0) {  // the goal: taken at once
+                    v = uc, jv = jc;
+                    break;
+                }
+                if (v < 0 || cc < cv || (cc == cv && hv && !hc)) v = uc, cv = cc, hv = hc, jv = jc;
+            }
+            const int take = v < 0 ? cur_i : v;  // (failed to secure a node: stay, and tell the caller)
+            const int sl = t.claim(take);
+            if (sl < 0) return 1;  // (never: a dense table has every node, a keyed one is at most half full)
+            stv(t.next + sl, ai + 1);
+            stv(s.vnext + ai, take);
+            if (v < 0) {
+                stv(s.blocker + ai, -1);
+                sp--;
+                mode = 0;
+                continue;
+            }
+            stv(s.blocker + ai, (jv != ai && v != cur_i) ? jv : -1);
+            if (jv >= 0 && jv != ai && ldv(s.vnext + jv) == -1) {  // priority inheritance
+                sp++;
+                if (sp >= count) return 1;  // (never: an agent is entered once)
+                stv(stack + sp, jv);
+                mode = 0;
+                continue;
+            }
+            sp--;
+            mode = 1;
+        }
+    }
+    return 0;
+}
+
+// the update filter (:222-264) for one agent whose desired node is d: (a) the desired waypoint within range / 2 of every segment start and of
+// the last point of the agent's plan, (b) it differs from the present waypoint, (c) the current goal point has reached the present waypoint
+__device__ __forceinline__ int filter_abc(const View& g, double range, int M, int dim, const double* __restrict__ state, const double* __restrict__ plan,
+                                          const double* __restrict__ cur_goal, const double* waypoint, int64_t a, int d) {
+#pragma clang fp contract(off)
+    const float zf = (float)g.z_2d;
+    const int dy_ = d / g.W, dx_ = d - dy_ * g.W;
+    const float des[3] = {node_coord(g.gmin0, dx_, g.res), node_coord(g.gmin1, dy_, g.res), zf};
+    bool in_range = true;
+    if (range > 0) {
+        for (int m = 0; m <= M && in_range; m++) {
+            double dist = 0;
+            for (int k = 0; k < 3; k++) {
+                float q;
+                if (plan == nullptr) q = (float)state[a * 9 + k];
+                else if (k >= dim) q = zf;
+                else q = (float)plan[a * dim * M * 6 + ((int64_t)k * M + (m < M ? m : M - 1)) * 6 + (m < M ? 0 : 5)];
+                const double dk = fabs((double)(des[k] - q));
+                dist = dist < dk ? dk : dist;
+            }
+            if (dist > 0.5 * range - kEpsFloat) in_range = false;
+        }
+    }
+    float nw = 0, ng = 0;
+    for (int k = 0; k < 3; k++) {
+        const float wv = (float)waypoint[a * 3 + k], e = des[k] - wv, h = (float)cur_goal[a * 3 + k] - wv;
+        nw += e * e;
+        ng += h * h;
+    }
+    return (in_range && sqrt((double)nw) > kEpsFloat && sqrt((double)ng) < kEpsFloat) ? 1 : 0;
+}
+
+// (d) "find valid update" (:266-296) by every lane of the workgroup, over the members order[0..count) or, order == nullptr, the agents
+// 0..count: a candidate whose desired node is the present waypoint of a group member that is not (or no longer) a candidate itself is
+// dropped, until nothing is.  Within a group PIBT hands out distinct nodes, so the only agent that can hold a candidate's desired node is
+// the one PIBT found there -- `blocker`, a member of the same group -- and dropping candidates only ever adds holders: the loop's result
+// does not depend on the order in which the reference visits its std::set.
+template <int T>  // (the workgroup's size)
+__device__ __forceinline__ void find_valid_update(const Scratch& s, const int32_t* order, int count) {
+    for (int round = 0; round <= count; round++) {
+        int changed = 0;
+        for (int i = threadIdx.x; i < count; i += T) {
+            const int a = order ? order[i] : i;
+            if (!ldv(s.keep + a)) continue;
+            const int j = ldv(s.blocker + a);
+            if (j >= 0 && s.onnode[j] && !ldv(s.keep + j)) {
+                stv(s.keep + a, 0);
+                changed = 1;
+            }
+        }
+        if (!__syncthreads_or(changed)) break;
+    }
+}
+
+// an agent's verdict: where it updates, its waypoint becomes the desired node's grid point -- float32, as the reference holds it
+__device__ __forceinline__ void write_update(const View& g, int up, int d, double* waypoint, int32_t* updated) {
+#pragma clang fp contract(off)
+    if (up) {
+        const int dy_ = d / g.W, dx_ = d - dy_ * g.W;
+        waypoint[0] = (double)node_coord(g.gmin0, dx_, g.res);
+        waypoint[1] = (double)node_coord(g.gmin1, dy_, g.res);
+        waypoint[2] = (double)(float)g.z_2d;
+    }
+    *updated = up;
+}
+
 // MIS: one workgroup per mission of the partition off[0..gridDim.x].  The workgroup sees its slice as a swarm of its own: every per-agent
 // array is entered at the slice's first agent and agent ids are LOCAL to the slice from here on (labels, order, stack, the ids in the node
 // tables; tie_breaker = id / n orders a contiguous slice the same either way), the node tables are the workgroup's own (LDS, or the
@@ -351,13 +524,11 @@ __global__ __launch_bounds__(kDecideThreads) void decide_kernel(View g, int64_t 
     }
     __syncthreads();
     const int n_multi = n_multi_sh;
-    // -- PIBT::run's planning loop for the first timestep, one group after the other, by ONE wavefront.  Every lane runs the same control flow
-    // and issues the same stores (a lane then reads back what it wrote itself); lanes 0..4 look at one candidate each in chooseNode.
+    // -- PIBT::run's planning loop for the first timestep, one group after the other, by ONE wavefront (pibt_walk).  The passes of all groups
+    // count against ONE bound, 4 n + 16; reaching it means the tables were corrupt: the waypoints are then left alone and the status word says so.
     if (tid < 64) {
         const int lane = tid;
-        // funcPIBT is entered at most once per agent and every entry plans once, plus once more after each child that failed (a child fails at
-        // most once): <= 2 n plans and <= n returns that carry "true" upwards -- 3 n passes of the loop below.  Reaching the bound means the
-        // tables were corrupt; the waypoints are then left alone and the status word says so.
+        const DenseTables t{now, next};
         const int bound = 4 * n + 16;
         int passes = 0, fail = 0;
         for (int gs = 0; gs < n_multi && !fail;) {
@@ -368,64 +539,7 @@ __global__ __launch_bounds__(kDecideThreads) void decide_kernel(View g, int64_t 
             }
             __threadfence_block();
             __builtin_amdgcn_wave_barrier();
-            for (int idx = gs; idx < ge && !fail; idx++) {
-                const int a0 = ldv(s.order + idx);
-                if (ldv(s.vnext + a0) != -1) continue;
-                int sp = 0, mode = 0;  // mode 0: call or "the child failed" (plan a step), 1: the callee returned true
-                stv(s.stack, a0);
-                while (sp >= 0) {
-                    if (++passes > bound) {
-                        fail = 1;
-                        break;
-                    }
-                    if (mode == 1) {
-                        sp--;
-                        continue;
-                    }
-                    const int ai = ldv(s.stack + sp), cur_i = s.cur[ai];
-                    // chooseNode, candidates in the identity order (one of the orders std::shuffle can draw)
-                    int u = -1, cu = 0, held = 0, ok = 0, aj = -1;
-                    if (lane < 5) {
-                        u = s.cand[(int64_t)ai * 5 + lane];
-                        cu = s.cost[(int64_t)ai * 5 + lane];
-                        if (u >= 0) {
-                            aj = ldv(now + u) - 1;
-                            held = aj >= 0;
-                            ok = ldv(next + u) == 0;                           // vertex conflict
-                            if (ok && aj >= 0) ok = ldv(s.vnext + aj) != cur_i;  // swap conflict
-                        }
-                    }
-                    int v = -1, cv = 0, hv = 0, jv = -1;
-                    for (int c = 0; c < 5; c++) {
-                        const int uc = __shfl(u, c), cc = __shfl(cu, c), hc = __shfl(held, c), oc = __shfl(ok, c), jc = __shfl(aj, c);
-                        if (!oc) continue;
-                        if (cc == 0) {  // the goal: taken at once
-                            v = uc, jv = jc;
-                            break;
-                        }
-                        if (v < 0 || cc < cv || (cc == cv && hv && !hc)) v = uc, cv = cc, hv = hc, jv = jc;
-                    }
-                    if (v < 0) {  // failed to secure a node: stay, and tell the caller
-                        stv(next + cur_i, ai + 1);
-                        stv(s.vnext + ai, cur_i);
-                        stv(s.blocker + ai, -1);
-                        sp--;
-                        mode = 0;
-                        continue;
-                    }
-                    stv(next + v, ai + 1);
-                    stv(s.vnext + ai, v);
-                    stv(s.blocker + ai, (jv != ai && v != cur_i) ? jv : -1);
-                    if (jv >= 0 && jv != ai && ldv(s.vnext + jv) == -1) {  // priority inheritance
-                        sp++;
-                        stv(s.stack + sp, jv);
-                        mode = 0;
-                        continue;
-                    }
-                    sp--;
-                    mode = 1;
-                }
-            }
+            fail = pibt_walk(s, t, s.order + gs, ge - gs, s.stack, lane, passes, bound);
             __threadfence_block();
             __builtin_amdgcn_wave_barrier();
             for (int idx = gs + lane; idx < ge; idx += 64) {  // leave the tables empty for the next group
@@ -445,65 +559,16 @@ __global__ __launch_bounds__(kDecideThreads) void decide_kernel(View g, int64_t 
     }
     __syncthreads();
     const int fail = fail_sh;
-    // -- the update filter (:222-264): (a) the desired waypoint within range / 2 of every segment start and of the last point of the agent's
-    // plan, (b) it differs from the present waypoint, (c) the current goal point has reached the present waypoint
-    const float zf = (float)g.z_2d;
+    // -- the update filter: tests (a)-(c) per agent, then "find valid update" over the whole swarm (a blocker is a member of the agent's own group)
     for (int a = tid; a < n; a += T) {
         const int vn = ldv(s.vnext + a), d = vn < 0 ? s.cur[a] : vn;
-        const int dy_ = d / g.W, dx_ = d - dy_ * g.W;
-        const float des[3] = {node_coord(g.gmin0, dx_, g.res), node_coord(g.gmin1, dy_, g.res), zf};
-        bool in_range = true;
-        if (range > 0) {
-            for (int m = 0; m <= M && in_range; m++) {
-                double dist = 0;
-                for (int k = 0; k < 3; k++) {
-                    float q;
-                    if (plan == nullptr) q = (float)state[(int64_t)a * 9 + k];
-                    else if (k >= dim) q = zf;
-                    else q = (float)plan[(int64_t)a * dim * M * 6 + ((int64_t)k * M + (m < M ? m : M - 1)) * 6 + (m < M ? 0 : 5)];
-                    const double dk = fabs((double)(des[k] - q));
-                    dist = dist < dk ? dk : dist;
-                }
-                if (dist > 0.5 * range - kEpsFloat) in_range = false;
-            }
-        }
-        float nw = 0, ng = 0;
-        for (int k = 0; k < 3; k++) {
-            const float w = (float)waypoint[(int64_t)a * 3 + k], e = des[k] - w, h = (float)cur_goal[(int64_t)a * 3 + k] - w;
-            nw += e * e;
-            ng += h * h;
-        }
-        stv(s.keep + a, (in_range && sqrt((double)nw) > kEpsFloat && sqrt((double)ng) < kEpsFloat) ? 1 : 0);
+        stv(s.keep + a, filter_abc(g, range, M, dim, state, plan, cur_goal, waypoint, a, d));
         desired_out[a] = d;
         group_out[a] = (int)base + ldv(s.label + a);
     }
     __syncthreads();
-    // (d) "find valid update" (:266-296): a candidate whose desired node is the present waypoint of a group member that is not (or no longer) a
-    // candidate itself is dropped, until nothing is.  Within a group PIBT hands out distinct nodes, so the only agent that can hold a
-    // candidate's desired node is the one PIBT found there -- `blocker` -- and dropping candidates only ever adds holders: the loop's result
-    // does not depend on the order in which the reference visits its std::set.
-    for (int round = 0; round <= n; round++) {
-        int changed = 0;
-        for (int a = tid; a < n; a += T) {
-            if (!ldv(s.keep + a)) continue;
-            const int j = ldv(s.blocker + a);
-            if (j >= 0 && s.onnode[j] && !ldv(s.keep + j)) {
-                stv(s.keep + a, 0);
-                changed = 1;
-            }
-        }
-        if (!__syncthreads_or(changed)) break;
-    }
-    for (int a = tid; a < n; a += T) {
-        const int up = !fail && ldv(s.keep + a);
-        if (up) {
-            const int d = desired_out[a], dy_ = d / g.W, dx_ = d - dy_ * g.W;
-            waypoint[(int64_t)a * 3 + 0] = (double)node_coord(g.gmin0, dx_, g.res);
-            waypoint[(int64_t)a * 3 + 1] = (double)node_coord(g.gmin1, dy_, g.res);
-            waypoint[(int64_t)a * 3 + 2] = (double)zf;
-        }
-        updated_out[a] = up;
-    }
+    find_valid_update<kDecideThreads>(s, nullptr, n);
+    for (int a = tid; a < n; a += T) write_update(g, !fail && ldv(s.keep + a), desired_out[a], waypoint + (int64_t)a * 3, updated_out + a);
     if (tid == 0 && fail) *s.status = 1;
 }
 
@@ -517,9 +582,9 @@ __global__ __launch_bounds__(kDecideThreads) void decide_kernel(View g, int64_t 
 //              is its least id, the label of the one-workgroup kernel -- and a flatten pass, which also counts the members
 //   order      segment offsets per group of more than one agent (one scan over the roots); agents alone decide and filter by themselves,
 //              the others drop a key (init_d descending, id descending) into their group's segment
-//   walk       one workgroup per group of more than one agent: a bitonic sort of the segment by all lanes, then ONE wavefront runs the
-//              funcPIBT loop of decide_kernel over node tables of the group's own -- an open-addressed table of 4 n_g .. 8 n_g slots, in LDS
-//              for small groups and in the group's slab of an O(n) buffer otherwise -- with a bound of 4 n_g + 16 passes, then all lanes run
+//   walk       one workgroup per group of more than one agent: a bitonic sort of the segment by all lanes, then ONE wavefront runs
+//              pibt_walk over node tables of the group's own -- an open-addressed table of 4 n_g .. 8 n_g slots (KeyedTables), in LDS for
+//              small groups and in the group's slab of an O(n) buffer otherwise -- with a bound of 4 n_g + 16 passes, then all lanes run
 //              the update filter and its fixed point for the members
 //   apply      the updates, unless some group reached its bound
 // Keys are distinct and every table answers the same whatever slot an entry landed in, so no result depends on the order in which atomics
@@ -677,37 +742,6 @@ __global__ __launch_bounds__(1024) void segments_kernel(int n, Scratch s, Wide w
     if (tid == 0) w.misc[0] = total_groups, w.misc[1] = 0;
 }
 
-// the update filter's tests (a)-(c) of decide_kernel for one agent whose desired node is d
-__device__ __forceinline__ int filter_abc(const View& g, double range, int M, int dim, const double* __restrict__ state, const double* __restrict__ plan,
-                                          const double* __restrict__ cur_goal, const double* waypoint, int64_t a, int d) {
-#pragma clang fp contract(off)
-    const float zf = (float)g.z_2d;
-    const int dy_ = d / g.W, dx_ = d - dy_ * g.W;
-    const float des[3] = {node_coord(g.gmin0, dx_, g.res), node_coord(g.gmin1, dy_, g.res), zf};
-    bool in_range = true;
-    if (range > 0) {
-        for (int m = 0; m <= M && in_range; m++) {
-            double dist = 0;
-            for (int k = 0; k < 3; k++) {
-                float q;
-                if (plan == nullptr) q = (float)state[a * 9 + k];
-                else if (k >= dim) q = zf;
-                else q = (float)plan[a * dim * M * 6 + ((int64_t)k * M + (m < M ? m : M - 1)) * 6 + (m < M ? 0 : 5)];
-                const double dk = fabs((double)(des[k] - q));
-                dist = dist < dk ? dk : dist;
-            }
-            if (dist > 0.5 * range - kEpsFloat) in_range = false;
-        }
-    }
-    float nw = 0, ng = 0;
-    for (int k = 0; k < 3; k++) {
-        const float wv = (float)waypoint[a * 3 + k], e = des[k] - wv, h = (float)cur_goal[a * 3 + k] - wv;
-        nw += e * e;
-        ng += h * h;
-    }
-    return (in_range && sqrt((double)nw) > kEpsFloat && sqrt((double)ng) < kEpsFloat) ? 1 : 0;
-}
-
 // agents alone in their group decide and filter by themselves (nobody can hold their node: blocker stays -1); the others drop their key --
 // ascending keys are init_d descending, then id descending, PIBT's priority at the first timestep -- into their group's segment
 __global__ __launch_bounds__(256) void place_kernel(View g, int n, double range, int M, int dim, const double* __restrict__ state,
@@ -727,18 +761,6 @@ __global__ __launch_bounds__(256) void place_kernel(View g, int n, double range,
     }
     const int slot = w.segstart[la] + atomicAdd(w.fill + la, 1);
     if (slot >= 0 && slot < n) w.keys[slot] = ((uint64_t)(~((uint32_t)init_d[a] ^ 0x80000000u)) << 32) | (uint32_t)~(uint32_t)a;
-}
-
-__device__ __forceinline__ unsigned table_hash(int node, unsigned mask) { return ((unsigned)node * 2654435761u >> 7) & mask; }
-
-// the slot of `node` in a group's table, -1 where the table has none (both node tables then hold 0 there)
-__device__ __forceinline__ int table_find(const int32_t* tkey, unsigned mask, int node) {
-    for (unsigned h = table_hash(node, mask), probes = 0; probes <= mask; h = (h + 1) & mask, probes++) {
-        const int k = ldv(tkey + h);
-        if (k == node) return (int)h;
-        if (k < 0) return -1;
-    }
-    return -1;
 }
 
 __device__ __forceinline__ void key_swap(uint64_t* kk, int i, int j) {
@@ -794,12 +816,11 @@ __global__ __launch_bounds__(kWideThreads) void wide_walk_kernel(View g, int n, 
     int32_t *now = tkey + cap, *next = now + cap;
     for (int i = tid; i < cap; i += T) tkey[i] = -1, now[i] = 0, next[i] = 0;
     __syncthreads();
-    // -- PIBT::run's planning loop for the first timestep over this group, by ONE wavefront: decide_kernel's loop, the node tables looked up by key
+    // -- PIBT::run's planning loop for the first timestep over this group, by ONE wavefront: the walk of decide_kernel, the node tables looked up
+    // by key, with a bound of this group's own
     if (tid < 64) {
         const int lane = tid;
-        const int bound = 4 * ng + 16;
-        int passes = 0, fail = 0;
-        int32_t* stack = s.stack + gs;
+        const KeyedTables t{tkey, now, next, mask};
         for (int idx = lane; idx < ng; idx += 64) {  // occupied_now: the last id wins
             const int a = order[idx], node = s.cur[a];
             for (unsigned h = table_hash(node, mask), probes = 0; probes <= mask; h = (h + 1) & mask, probes++) {
@@ -812,84 +833,8 @@ __global__ __launch_bounds__(kWideThreads) void wide_walk_kernel(View g, int n, 
         }
         __threadfence_block();
         __builtin_amdgcn_wave_barrier();
-        for (int idx = 0; idx < ng && !fail; idx++) {
-            const int a0 = order[idx];
-            if (ldv(s.vnext + a0) != -1) continue;
-            int sp = 0, mode = 0;  // mode 0: call or "the child failed" (plan a step), 1: the callee returned true
-            stv(stack, a0);
-            while (sp >= 0) {
-                if (++passes > bound) {
-                    fail = 1;
-                    break;
-                }
-                if (mode == 1) {
-                    sp--;
-                    continue;
-                }
-                const int ai = ldv(stack + sp), cur_i = s.cur[ai];
-                // chooseNode, candidates in the identity order (one of the orders std::shuffle can draw)
-                int u = -1, cu = 0, held = 0, ok = 0, aj = -1;
-                if (lane < 5) {
-                    u = s.cand[(int64_t)ai * 5 + lane];
-                    cu = s.cost[(int64_t)ai * 5 + lane];
-                    if (u >= 0) {
-                        const int sl = table_find(tkey, mask, u);
-                        aj = sl >= 0 ? ldv(now + sl) - 1 : -1;
-                        held = aj >= 0;
-                        ok = sl < 0 || ldv(next + sl) == 0;                // vertex conflict
-                        if (ok && aj >= 0) ok = ldv(s.vnext + aj) != cur_i;  // swap conflict
-                    }
-                }
-                int v = -1, cv = 0, hv = 0, jv = -1;
-                for (int c = 0; c < 5; c++) {
-                    const int uc = __shfl(u, c), cc = __shfl(cu, c), hc = __shfl(held, c), oc = __shfl(ok, c), jc = __shfl(aj, c);
-                    if (!oc) continue;
-                    if (cc == 0) {  // the goal: taken at once
-                        v = uc, jv = jc;
-                        break;
-                    }
-                    if (v < 0 || cc < cv || (cc == cv && hv && !hc)) v = uc, cv = cc, hv = hc, jv = jc;
-                }
-                // (every lane finds or makes the slot of the node taken, the same one)
-                const int take = v < 0 ? cur_i : v;
-                int sl = -1;
-                for (unsigned h = table_hash(take, mask), probes = 0; probes <= mask; h = (h + 1) & mask, probes++) {
-                    const int k = ldv(tkey + h);
-                    if (k == take || k < 0) {
-                        if (k < 0) stv(tkey + h, take);
-                        sl = (int)h;
-                        break;
-                    }
-                }
-                if (sl < 0) {  // (never: the table is at most half full)
-                    fail = 1;
-                    break;
-                }
-                if (v < 0) {  // failed to secure a node: stay, and tell the caller
-                    stv(next + sl, ai + 1);
-                    stv(s.vnext + ai, cur_i);
-                    stv(s.blocker + ai, -1);
-                    sp--;
-                    mode = 0;
-                    continue;
-                }
-                stv(next + sl, ai + 1);
-                stv(s.vnext + ai, v);
-                stv(s.blocker + ai, (jv != ai && v != cur_i) ? jv : -1);
-                if (jv >= 0 && jv != ai && ldv(s.vnext + jv) == -1) {  // priority inheritance
-                    sp++;
-                    if (sp >= ng) {  // (never: an agent is entered once)
-                        fail = 1;
-                        break;
-                    }
-                    stv(stack + sp, jv);
-                    mode = 0;
-                    continue;
-                }
-                sp--;
-                mode = 1;
-            }
-        }
+        int passes = 0;
+        const int fail = pibt_walk(s, t, order, ng, s.stack + gs, lane, passes, 4 * ng + 16);
         if (fail && lane == 0) {
             fail_sh = 1;
             __hip_atomic_store(w.misc + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -904,19 +849,7 @@ __global__ __launch_bounds__(kWideThreads) void wide_walk_kernel(View g, int n, 
         group_out[a] = root;
     }
     __syncthreads();
-    for (int round = 0; round <= ng; round++) {
-        int changed = 0;
-        for (int i = tid; i < ng; i += T) {
-            const int a = order[i];
-            if (!ldv(s.keep + a)) continue;
-            const int j = ldv(s.blocker + a);
-            if (j >= 0 && s.onnode[j] && !ldv(s.keep + j)) {
-                stv(s.keep + a, 0);
-                changed = 1;
-            }
-        }
-        if (!__syncthreads_or(changed)) break;
-    }
+    find_valid_update<kWideThreads>(s, order, ng);
 }
 
 __global__ __launch_bounds__(256) void apply_kernel(View g, int n, Scratch s, Wide w, const int32_t* __restrict__ desired, double* __restrict__ waypoint,
@@ -924,14 +857,8 @@ __global__ __launch_bounds__(256) void apply_kernel(View g, int n, Scratch s, Wi
 #pragma clang fp contract(off)
     const int a = blockIdx.x * 256 + threadIdx.x;
     if (a >= n) return;
-    const int fail = w.misc[1], up = !fail && s.keep[a];
-    if (up) {
-        const int d = desired[a], dy_ = d / g.W, dx_ = d - dy_ * g.W;
-        waypoint[(int64_t)a * 3 + 0] = (double)node_coord(g.gmin0, dx_, g.res);
-        waypoint[(int64_t)a * 3 + 1] = (double)node_coord(g.gmin1, dy_, g.res);
-        waypoint[(int64_t)a * 3 + 2] = (double)(float)g.z_2d;
-    }
-    updated_out[a] = up;
+    const int fail = w.misc[1];
+    write_update(g, !fail && s.keep[a], desired[a], waypoint + (int64_t)a * 3, updated_out + a);
     if (a == 0 && fail) *s.status = 1;
 }
 
@@ -975,6 +902,33 @@ constexpr int64_t kPerAgentInts = 9 + 2 * 5;  // cur, vnext, order, stack, label
 
 bool tables_fit_lds(const lscqp_grid_s* g) {
     return (size_t)2 * g->dims[0] * g->dims[1] * sizeof(int32_t) <= (size_t)lscgrid::kTableLdsBytes;
+}
+
+// the argument checks the three lscqp_waypoints_* entries share.  `entry`: the caller's own name; `buffers`: the device pointers that must
+// not be null -- where `need_buffers` says so (the single-swarm entries take null buffers with no agents) -- refused with `null_msg`
+int check_waypoint_args(const char* entry, lscqp_grid g, int64_t n, bool need_buffers, std::initializer_list<const void*> buffers, const char* null_msg,
+                        double communication_range, int32_t M, int32_t dim, const double* d_plan) {
+    if (!g || n < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (need_buffers)
+        for (const void* p : buffers)
+            if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, null_msg);
+    if (dim != 2) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, (std::string(entry) + " is 2-D only").c_str());
+    if (d_plan && M < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "M must be positive");
+    if (!(communication_range == communication_range)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "communication_range is NaN");
+    return LSCQP_OK;
+}
+
+// one workgroup per agent relaxes its field: in LDS where the padded grid fits, in HBM otherwise (d_off: the mission partition, or null)
+void launch_fields(const lscqp_grid_s* g, int64_t n, const uint8_t* occ, const double* d_start_points, const double* d_goal_points, int32_t* d_field,
+                   int32_t* d_init_d, const int64_t* d_off, int K, hipStream_t st) {
+    const int64_t padded = (int64_t)(g->dims[0] + 2) * (g->dims[1] + 2);
+    if (padded <= lscgrid::kLdsNodes) {
+        const int threads = padded <= 2048 ? 256 : 1024;
+        const size_t lds = (size_t)((padded * 2 + 15) / 16 * 16);
+        hipLaunchKernelGGL(lscgrid::fields_kernel<true>, dim3((unsigned)n), dim3(threads), lds, st, g->v, occ, d_start_points, d_goal_points, d_field, d_init_d, d_off, K);
+    } else {
+        hipLaunchKernelGGL(lscgrid::fields_kernel<false>, dim3((unsigned)n), dim3(1024), 0, st, g->v, occ, d_start_points, d_goal_points, d_field, d_init_d, d_off, K);
+    }
 }
 
 }  // namespace
@@ -1113,21 +1067,12 @@ int lscqp_grid_fields_device(lscqp_grid g, int64_t n, const double* d_start_poin
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
     if (n == 0) return LSCQP_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int W = g->dims[0], H = g->dims[1], nodes = W * H;
+    const int nodes = g->dims[0] * g->dims[1];
     GRID_HIP(hipMemcpyAsync(g->d_occ_mission, g->d_occ, (size_t)nodes, hipMemcpyDeviceToDevice, st));
     GRID_HIP(hipMemsetAsync(g->d_tables + (size_t)2 * nodes, 0, 4 * sizeof(int32_t), st));  // a new mission: the status word starts at 0
     hipLaunchKernelGGL(lscgrid::clear_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, d_start_points, d_goal_points, g->d_occ_mission,
                        (const int64_t*)nullptr, 0);
-    const int64_t padded = (int64_t)(W + 2) * (H + 2);
-    if (padded <= lscgrid::kLdsNodes) {
-        const int threads = padded <= 2048 ? 256 : 1024;
-        const size_t lds = (size_t)((padded * 2 + 15) / 16 * 16);
-        hipLaunchKernelGGL(lscgrid::fields_kernel<true>, dim3((unsigned)n), dim3(threads), lds, st, g->v, g->d_occ_mission, d_start_points, d_goal_points, d_field, d_init_d,
-                           (const int64_t*)nullptr, 0);
-    } else {
-        hipLaunchKernelGGL(lscgrid::fields_kernel<false>, dim3((unsigned)n), dim3(1024), 0, st, g->v, g->d_occ_mission, d_start_points, d_goal_points, d_field, d_init_d,
-                           (const int64_t*)nullptr, 0);
-    }
+    launch_fields(g, n, g->d_occ_mission, d_start_points, d_goal_points, d_field, d_init_d, nullptr, 0, st);
     GRID_HIP(hipGetLastError());
     return LSCQP_OK;
 }
@@ -1135,11 +1080,11 @@ int lscqp_grid_fields_device(lscqp_grid g, int64_t n, const double* d_start_poin
 int lscqp_waypoints_device(lscqp_grid g, double communication_range, int32_t M, int32_t dim, int64_t n, const double* d_state, const double* d_plan,
                            const double* d_current_goal, const int32_t* d_field, const int32_t* d_init_d, double* d_waypoint, int32_t* d_group_out,
                            int32_t* d_desired_out, int32_t* d_updated_out, void* stream) {
-    if (!g || n < 0 || (n > 0 && (!d_state || !d_current_goal || !d_field || !d_init_d || !d_waypoint || !d_group_out || !d_desired_out || !d_updated_out)))
-        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (dim != 2) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_waypoints_device is 2-D only");
-    if (d_plan && M < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "M must be positive");
-    if (!(communication_range == communication_range)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "communication_range is NaN");
+    {
+        const int rc = check_waypoint_args("lscqp_waypoints_device", g, n, n > 0, {d_state, d_current_goal, d_field, d_init_d, d_waypoint, d_group_out, d_desired_out, d_updated_out},
+                                           "bad argument", communication_range, M, dim, d_plan);
+        if (rc != LSCQP_OK) return rc;
+    }
     if (n == 0) return LSCQP_OK;
     if (n > g->reserved) {  // (synchronises and allocates: a caller that captures the launch reserves beforehand)
         const int rc = lscqp_grid_reserve(g, n);
@@ -1187,11 +1132,11 @@ int lscqp_grid_reserve_wide(lscqp_grid g, int64_t n) {
 int lscqp_waypoints_wide_device(lscqp_grid g, double communication_range, int32_t M, int32_t dim, int64_t n, const double* d_state, const double* d_plan,
                                 const double* d_current_goal, const int32_t* d_field, const int32_t* d_init_d, double* d_waypoint, int32_t* d_group_out,
                                 int32_t* d_desired_out, int32_t* d_updated_out, void* stream) {
-    if (!g || n < 0 || (n > 0 && (!d_state || !d_current_goal || !d_field || !d_init_d || !d_waypoint || !d_group_out || !d_desired_out || !d_updated_out)))
-        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (dim != 2) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_waypoints_wide_device is 2-D only");
-    if (d_plan && M < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "M must be positive");
-    if (!(communication_range == communication_range)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "communication_range is NaN");
+    {
+        const int rc = check_waypoint_args("lscqp_waypoints_wide_device", g, n, n > 0, {d_state, d_current_goal, d_field, d_init_d, d_waypoint, d_group_out, d_desired_out, d_updated_out},
+                                           "bad argument", communication_range, M, dim, d_plan);
+        if (rc != LSCQP_OK) return rc;
+    }
     if (n == 0) return LSCQP_OK;
     if (n > g->wide_reserved || n > g->reserved) {  // (synchronises and allocates: a caller that captures the launch reserves beforehand)
         const int rc = lscqp_grid_reserve_wide(g, n);
@@ -1276,22 +1221,13 @@ int lscqp_grid_fields_missions_device(lscqp_grid g, int64_t n, int32_t n_mission
         if (rc != LSCQP_OK) return rc;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int W = g->dims[0], H = g->dims[1], nodes = W * H, K = n_missions;
+    const int nodes = g->dims[0] * g->dims[1], K = n_missions;
     g->fields_off.assign(mission_offsets, mission_offsets + K + 1);
     hipLaunchKernelGGL(lscgrid::spread_occupancy_kernel, dim3((unsigned)(((int64_t)nodes * K + 255) / 256)), dim3(256), 0, st, nodes, K, g->d_occ, g->d_occ_k);
     GRID_HIP(hipMemsetAsync(g->d_status_k, 0, (size_t)K * sizeof(int32_t), st));  // new missions: their status words start at 0
     hipLaunchKernelGGL(lscgrid::clear_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, d_start_points, d_goal_points, g->d_occ_k,
                        d_mission_offsets, K);
-    const int64_t padded = (int64_t)(W + 2) * (H + 2);
-    if (padded <= lscgrid::kLdsNodes) {
-        const int threads = padded <= 2048 ? 256 : 1024;
-        const size_t lds = (size_t)((padded * 2 + 15) / 16 * 16);
-        hipLaunchKernelGGL(lscgrid::fields_kernel<true>, dim3((unsigned)n), dim3(threads), lds, st, g->v, g->d_occ_k, d_start_points, d_goal_points, d_field, d_init_d,
-                           d_mission_offsets, K);
-    } else {
-        hipLaunchKernelGGL(lscgrid::fields_kernel<false>, dim3((unsigned)n), dim3(1024), 0, st, g->v, g->d_occ_k, d_start_points, d_goal_points, d_field, d_init_d,
-                           d_mission_offsets, K);
-    }
+    launch_fields(g, n, g->d_occ_k, d_start_points, d_goal_points, d_field, d_init_d, d_mission_offsets, K, st);
     GRID_HIP(hipGetLastError());
     return LSCQP_OK;
 }
@@ -1305,11 +1241,12 @@ int lscqp_waypoints_missions_device(lscqp_grid g, double communication_range, in
         const int rc = lscqp_check_missions_(n, n_missions, mission_offsets);
         if (rc != LSCQP_OK) return rc;
     }
-    if (!d_mission_offsets || !d_state || !d_current_goal || !d_field || !d_init_d || !d_waypoint || !d_group_out || !d_desired_out || !d_updated_out)
-        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (dim != 2) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_waypoints_missions_device is 2-D only");
-    if (d_plan && M < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "M must be positive");
-    if (!(communication_range == communication_range)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "communication_range is NaN");
+    {
+        const int rc = check_waypoint_args("lscqp_waypoints_missions_device", g, n, true,
+                                           {d_mission_offsets, d_state, d_current_goal, d_field, d_init_d, d_waypoint, d_group_out, d_desired_out, d_updated_out}, "null buffer",
+                                           communication_range, M, dim, d_plan);
+        if (rc != LSCQP_OK) return rc;
+    }
     // (the occupancy copies are lscqp_grid_fields_missions_device's, cleared for the agents of ITS partition)
     if (g->fields_off.size() != (size_t)n_missions + 1 || !std::equal(g->fields_off.begin(), g->fields_off.end(), mission_offsets))
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_grid_fields_missions_device over this same partition must come first");

@@ -9,35 +9,19 @@ import pytest
 from tests import grid_reference as R
 from tests import mission_cases as MC
 from tests import waypoint_cases as WC
+from tests import waypoint_device as WD
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
-def _dev(torch, a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to("cuda")
-
-
-def _device_grid(api, w, resolution=0.5):
-    wmap = api.WorldMap(w["boxes"], w["world_min"], w["world_max"], w["resolution"], w["max_dist"])
-    return wmap, api.Grid(wmap, resolution, w["radius"], w["z_2d"])
-
-
-def _device_step(api, torch, grid, off, rng, s, d_field, d_init_d, M=10):
-    n = len(s["waypoints"])
-    st = np.zeros((n, 9))
-    st[:, :3] = s["positions"]
-    d_way = _dev(torch, s["waypoints"], np.float64)
-    d_plan = None if s["plans"] is None else _dev(torch, WC.plan_from_points(np.asarray(s["plans"])), np.float64)
-    g, d, u = grid.waypoints_missions(off, rng, M, 2, _dev(torch, st), d_plan, _dev(torch, s["current_goals"], np.float64), d_field, d_init_d, d_way)
-    torch.cuda.synchronize()
-    assert not grid.mission_status(len(off) - 1).any()
-    return g.cpu().numpy(), d.cpu().numpy(), u.cpu().numpy(), d_way.cpu().numpy().reshape(n, 3)
+def _device_step(torch, grid, off, rng, s, d_field, d_init_d):
+    return WD.decision_step(torch, grid, rng, s, d_field, d_init_d, off=off)
 
 
 def _compare_rollouts(api, torch, grid, G, world, off, starts, goals, ranges, steps, seed):
     F, init_d, free = MC.mission_fields(G, off, starts, goals)
-    d_field, d_init_d = grid.fields_missions(off, _dev(torch, starts, np.float64), _dev(torch, goals, np.float64))
+    d_field, d_init_d = grid.fields_missions(off, WD.dev(torch, starts, np.float64), WD.dev(torch, goals, np.float64))
     torch.cuda.synchronize()
     assert np.array_equal(d_field.cpu().numpy(), F)
     assert np.array_equal(d_init_d.cpu().numpy(), init_d)
@@ -45,7 +29,7 @@ def _compare_rollouts(api, torch, grid, G, world, off, starts, goals, ranges, st
     for rng in ranges:
         for s in MC.seeded_states(G, free, off, world, starts, F, init_d, steps, rng, seed):
             label, desired, updated, new = MC.waypoint_step(G, free, off, rng, s["positions"], s["plans"], s["current_goals"], s["waypoints"], F, init_d)
-            g, d, u, w = _device_step(api, torch, grid, off, rng, s, d_field, d_init_d)
+            g, d, u, w = _device_step(torch, grid, off, rng, s, d_field, d_init_d)
             assert np.array_equal(d, desired), (rng, np.nonzero(d != desired))
             assert np.array_equal(g, label), (rng, np.nonzero(g != label))  # (= offset + the slice's own least id)
             assert np.array_equal(u, updated), (rng, np.nonzero(u != updated))
@@ -74,7 +58,7 @@ def test_waypoint_twins_equal_the_per_mission_restatement_lds_tables(api, oracle
     import torch
 
     world, off, starts, goals = MC.forest_missions(K, n=10, side=40.0, n_boxes=300, seed=0)
-    wmap, grid = _device_grid(api, world)
+    wmap, grid = WD.device_grid(api, world)
     G = _forest_grid(oracle, world)
     assert grid.dims.tolist() == G.dims and np.array_equal(grid.download().astype(bool), G.occ)
     assert 2 * G.W * G.H * 4 <= 60 * 1024
@@ -93,7 +77,7 @@ def test_waypoint_twins_equal_the_per_mission_restatement_hbm_tables(api, oracle
     import torch
 
     w = WC.walled_world(400)
-    wmap, grid = _device_grid(api, w)
+    wmap, grid = WD.device_grid(api, w)
     assert grid.dims.tolist() == [400, 400, 1]
     G = R.Grid(w["world_min"], w["world_max"], w["z_2d"], 0.5, w["radius"], occ=grid.download().astype(bool))
     A_start, A_goal, B_start, B_goal = [10.0, 5.0, 0.6], [12.0, 5.0, 0.6], [10.5, 5.0, 0.6], [8.0, 5.0, 0.6]
@@ -105,7 +89,7 @@ def test_waypoint_twins_equal_the_per_mission_restatement_hbm_tables(api, oracle
     assert c["init_d"][3] == 4 and c["init_d"][4] == 5
     # the head-on pair at its start, one group per mission: the walk of mission 1 runs in ITS slab, with a conflict in it
     s = dict(positions=starts, plans=None, current_goals=starts, waypoints=starts)
-    g, d, u, way = _device_step(api, torch, grid, off, -1, s, c["d_field"], c["d_init_d"])
+    g, d, u, way = _device_step(torch, grid, off, -1, s, c["d_field"], c["d_init_d"])
     ref = MC.waypoint_step(G, c["free"], off, -1, starts, None, starts, starts, c["F"], c["init_d"])
     assert all(np.array_equal(x, y) for x, y in zip((g, d, u, way), ref))
     assert g.tolist() == [0, 0, 0, 3, 3, 3]
@@ -114,7 +98,7 @@ def test_waypoint_twins_equal_the_per_mission_restatement_hbm_tables(api, oracle
     assert d[3] not in (ay * G.W + ax, by * G.W + bx)  # ... A neither stays nor swaps:
     assert c["F"][3].reshape(-1)[d[3]] == 5            # it steps back, one step further from its goal than it was
     # the same decision again: the slabs were left empty by the walk before
-    g2, d2, _, _ = _device_step(api, torch, grid, off, -1, s, c["d_field"], c["d_init_d"])
+    g2, d2, _, _ = _device_step(torch, grid, off, -1, s, c["d_field"], c["d_init_d"])
     assert np.array_equal(g2, g) and np.array_equal(d2, d)
     grid.close()
     wmap.close()
@@ -134,24 +118,24 @@ def test_start_and_goal_nodes_are_cleared_in_their_own_mission_only(api, oracle,
     A_start, A_goal, B_start, B_goal = WC.P(0, 0), WC.P(2, 1), WC.P(2, 0), WC.P(2, 2)
     starts, goals = np.array([A_start, B_start], float), np.array([A_goal, B_goal], float)
     off = np.array([0, 1, 2])
-    wmap, grid = _device_grid(api, world)
+    wmap, grid = WD.device_grid(api, world)
     assert np.array_equal(grid.download().astype(bool), world["occ"])
     G = WC.reference_grid(oracle, world)
     F, init_d, free = MC.mission_fields(G, off, starts, goals)
     gi, gj = G.node(A_goal)
     assert G.occ[gj, gi] and free[0][gj, gi] and not free[1][gj, gi]
-    d_field, d_init_d = grid.fields_missions(off, _dev(torch, starts, np.float64), _dev(torch, goals, np.float64))
+    d_field, d_init_d = grid.fields_missions(off, WD.dev(torch, starts, np.float64), WD.dev(torch, goals, np.float64))
     got, got_d = d_field.cpu().numpy(), d_init_d.cpu().numpy()
     assert np.array_equal(got, F) and np.array_equal(got_d, init_d)
     assert got[0, gj, gi] == 0 and got_d[0] == 3            # A: (0,0) -> (1,0) -> (2,0) -> G
     assert got[1, gj, gi] == api.GRID_UNREACHABLE and got_d[1] == 6  # B: round the wall through (4, 1)
     s = dict(positions=starts, plans=None, current_goals=starts, waypoints=starts)
-    g, d, u, w = _device_step(api, torch, grid, off, -1, s, d_field, d_init_d)
+    g, d, u, w = _device_step(torch, grid, off, -1, s, d_field, d_init_d)
     ref = MC.waypoint_step(G, free, off, -1, starts, None, starts, starts, F, init_d)
     assert all(np.array_equal(x, y) for x, y in zip((g, d, u, w), ref))
     assert d.tolist() == [WC.N(1, 0, Wd), WC.N(3, 0, Wd)] and g.tolist() == [0, 1]  # B steps right, not down into G
     # the same two agents as ONE mission: G is free for both and B goes through it
-    f1, d1 = grid.fields(_dev(torch, starts, np.float64), _dev(torch, goals, np.float64))
+    f1, d1 = grid.fields(WD.dev(torch, starts, np.float64), WD.dev(torch, goals, np.float64))
     torch.cuda.synchronize()
     assert d1.cpu().numpy().tolist() == [3, 2]
     grid.close()
@@ -173,7 +157,7 @@ def test_neighbour_twin_equals_the_single_entry_point_on_each_slice(api, torch_c
     off = np.array([0, 7, 40, 41, 1141])
     n = int(off[-1])
     pos = _positions(np.random.default_rng(3), off, 6.0)
-    d_pos = _dev(torch, pos)
+    d_pos = WD.dev(torch, pos)
     for n_obs, rng in ((8, 3.0), (8, -1.0), (40, 1.5), (0, 3.0)):
         d_nbr = torch.full((n * max(n_obs, 1),), -7, dtype=torch.int32, device="cuda")
         d_cnt = torch.full((n,), -7, dtype=torch.int32, device="cuda")
@@ -184,7 +168,7 @@ def test_neighbour_twin_equals_the_single_entry_point_on_each_slice(api, torch_c
             nk = sl.stop - sl.start
             s_nbr = torch.full((nk * max(n_obs, 1),), -7, dtype=torch.int32, device="cuda")
             s_cnt = torch.full((nk,), -7, dtype=torch.int32, device="cuda")
-            sol.select_neighbours_device(nk, 0, nk, n_obs, rng, _dev(torch, pos[sl]), s_nbr, s_cnt)
+            sol.select_neighbours_device(nk, 0, nk, n_obs, rng, WD.dev(torch, pos[sl]), s_nbr, s_cnt)
             torch.cuda.synchronize()
             want = s_nbr.cpu().numpy()[:nk * n_obs].reshape(nk, n_obs)
             want = np.where(want >= 0, want + off[k], want)
@@ -211,13 +195,13 @@ def test_safety_twin_equals_the_single_entry_point_on_each_slice(api, torch_cuda
     hdr["vmax"], hdr["amax"] = 0.3, 1.0
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to("cuda")  # noqa: E731
     d_out = torch.zeros(n * api.SAFETY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-    sol.safety_metrics_missions_device(off, 3, 0.07, _dev(torch, x), _dev(torch, rad), _dev(torch, dwv), up(hdr), d_out, z_2d=0.6)
+    sol.safety_metrics_missions_device(off, 3, 0.07, WD.dev(torch, x), WD.dev(torch, rad), WD.dev(torch, dwv), up(hdr), d_out, z_2d=0.6)
     torch.cuda.synchronize()
     got = d_out.cpu().numpy().view(api.SAFETY_DTYPE)
     for k, sl in enumerate(MC.slices(off)):
         nk = sl.stop - sl.start
         s_out = torch.zeros(nk * api.SAFETY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-        sol.safety_metrics_device(nk, 0, nk, 3, 0.07, _dev(torch, x[sl]), _dev(torch, rad[sl]), _dev(torch, dwv[sl]), up(hdr[sl]), s_out, z_2d=0.6)
+        sol.safety_metrics_device(nk, 0, nk, 3, 0.07, WD.dev(torch, x[sl]), WD.dev(torch, rad[sl]), WD.dev(torch, dwv[sl]), up(hdr[sl]), s_out, z_2d=0.6)
         torch.cuda.synchronize()
         want = s_out.cpu().numpy().view(api.SAFETY_DTYPE).copy()
         want["closest_agent"] = np.where(want["closest_agent"] >= 0, want["closest_agent"] + off[k], want["closest_agent"])
@@ -227,14 +211,8 @@ def test_safety_twin_equals_the_single_entry_point_on_each_slice(api, torch_cuda
     sol.close()
 
 
-def _agents(api, radius, N):
-    ag = np.zeros(N, api.AGENT_PARAM_DTYPE)
-    ag["radius"], ag["downwash"], ag["max_vel"], ag["max_acc"], ag["nominal_velocity"] = radius, 2.0, 1.0, 2.0, 1.0
-    return ag
-
-
 def _plan(api, sol, wmap, W, N, **kw):
-    return api.Plan(sol, wmap, N, 9, _agents(api, W["radius"], N), constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, optimize_goal=True,
+    return api.Plan(sol, wmap, N, 9, WD.agents(api, W["radius"], N), constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, optimize_goal=True,
                     closed_loop=True, z_2d=W["z_2d"], safety_samples=2, record_time_step=0.1, waypoint_mode=api.WAYPOINT_GRID_PIBT, **kw)
 
 
@@ -393,7 +371,7 @@ def test_refusals_and_the_single_mission_plan(api, torch_cuda):
         assert plan.mission_status().tolist() == [0]
     plan.close()
     # a sharded plan flies one mission
-    shard = api.Plan(sol, wmap, 5, 9, _agents(api, W["radius"], n), n_total=n, first_agent=0, constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL,
+    shard = api.Plan(sol, wmap, 5, 9, WD.agents(api, W["radius"], n), n_total=n, first_agent=0, constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL,
                      z_2d=W["z_2d"])
     with pytest.raises(api.LscqpError) as e:
         shard.set_missions([0, 4, 10])
@@ -402,13 +380,13 @@ def test_refusals_and_the_single_mission_plan(api, torch_cuda):
     shard.close()
     # the grid twins: a bad partition, and a decision before the fields of its partition
     grid = api.Grid(wmap, 0.5, W["radius"], W["z_2d"])
-    d_s, d_g = _dev(torch, starts, np.float64), _dev(torch, goals, np.float64)
+    d_s, d_g = WD.dev(torch, starts, np.float64), WD.dev(torch, goals, np.float64)
     with pytest.raises(api.LscqpError) as e:
         grid.fields_missions([0, 6, 4, 10], d_s, d_g)
     assert e.value.code == api.ERR_INVALID_ARGUMENT
     d_way = d_s.clone()
     with pytest.raises(api.LscqpError) as e:
-        grid.waypoints_missions([0, 4, 10], 3.0, 10, 2, _dev(torch, np.zeros((n, 9))), None, d_s, torch.zeros(n, dtype=torch.int32, device="cuda"),
+        grid.waypoints_missions([0, 4, 10], 3.0, 10, 2, WD.dev(torch, np.zeros((n, 9))), None, d_s, torch.zeros(n, dtype=torch.int32, device="cuda"),
                                 torch.zeros(n, dtype=torch.int32, device="cuda"), d_way)
     assert e.value.code == api.ERR_INVALID_ARGUMENT and "lscqp_grid_fields_missions_device" in str(e.value)
     with pytest.raises(api.LscqpError):
@@ -417,9 +395,9 @@ def test_refusals_and_the_single_mission_plan(api, torch_cuda):
     d_f, d_i = grid.fields_missions([0, 4, 10], d_s, d_g)
     for other in ([0, 5, 10], [0, 10], [0, 4, 7, 10]):
         with pytest.raises(api.LscqpError) as e:
-            grid.waypoints_missions(other, 3.0, 10, 2, _dev(torch, np.zeros((n, 9))), None, d_s, d_f, d_i, d_way)
+            grid.waypoints_missions(other, 3.0, 10, 2, WD.dev(torch, np.zeros((n, 9))), None, d_s, d_f, d_i, d_way)
         assert e.value.code == api.ERR_INVALID_ARGUMENT and "same partition" in str(e.value), other
-    grid.waypoints_missions([0, 4, 10], 3.0, 10, 2, _dev(torch, np.zeros((n, 9))), None, d_s, d_f, d_i, d_way)
+    grid.waypoints_missions([0, 4, 10], 3.0, 10, 2, WD.dev(torch, np.zeros((n, 9))), None, d_s, d_f, d_i, d_way)
     torch.cuda.synchronize()
     assert grid.mission_status(2).tolist() == [0, 0]
     grid.close()

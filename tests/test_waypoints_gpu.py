@@ -2,51 +2,16 @@
 restatement of the reference (tests/grid_reference.py).  Everything compared is integers or exact grid points: every comparison is exact
 equality.  Invariants of a PIBT step are asserted separately from equality."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
 from tests import grid_reference as R
 from tests import waypoint_cases as WC
+from tests import waypoint_device as WD
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-
-
-def _closed_loop():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import closed_loop
-
-    return closed_loop
-
-
-def _dev(torch, a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to("cuda")
-
-
-def _device_grid(api, w, resolution=0.5):
-    wmap = api.WorldMap(w["boxes"], w["world_min"], w["world_max"], w["resolution"], w["max_dist"])
-    return wmap, api.Grid(wmap, resolution, w["radius"], w["z_2d"])
-
-
-def _device_fields(api, torch, grid, starts, goals):
-    f, d = grid.fields(_dev(torch, starts, np.float64), _dev(torch, goals, np.float64))
-    torch.cuda.synchronize()
-    return f, d
-
-
-def _device_step(api, torch, grid, rng, state, current_goals, way, d_field, d_init_d, plans=None, M=10):
-    """(group, desired, updated, new waypoints) of one lscqp_waypoints_device; positions ride in a state record."""
-    n = len(way)
-    st = np.zeros((n, 9))
-    st[:, :3] = state
-    d_way = _dev(torch, way, np.float64)
-    d_plan = None if plans is None else _dev(torch, WC.plan_from_points(np.asarray(plans)), np.float64)
-    g, d, u = grid.waypoints(rng, M, 2, _dev(torch, st), d_plan, _dev(torch, current_goals, np.float64), d_field, d_init_d, d_way)
-    torch.cuda.synchronize()
-    assert grid.status() == 0
-    return g.cpu().numpy(), d.cpu().numpy(), u.cpu().numpy(), d_way.cpu().numpy().reshape(n, 3)
 
 
 def _check_invariants(G, label, desired, way):
@@ -75,7 +40,7 @@ def _same_partition(a, b):
 def _compare_step(api, torch, grid, G, rng, s, F, init_d, d_field, d_init_d):
     label, desired, updated, new = R.waypoint_step(G, rng, s["positions"], None if s["plans"] is None else list(s["plans"]), s["current_goals"],
                                                    s["waypoints"], F, init_d)
-    g, d, u, w = _device_step(api, torch, grid, rng, s["positions"], s["current_goals"], s["waypoints"], d_field, d_init_d, s["plans"])
+    g, d, u, w = WD.decision_step(torch, grid, rng, s, d_field, d_init_d)
     _check_invariants(G, g, d, s["waypoints"])
     assert np.array_equal(d, desired), np.nonzero(d != desired)
     assert _same_partition(g, label) and np.array_equal(g, label)  # (both name a group by its least id)
@@ -85,8 +50,8 @@ def _compare_step(api, torch, grid, G, rng, s, F, init_d, d_field, d_init_d):
 
 
 def test_grid_occupancy_equals_the_restatement(api, oracle, torch_cuda):
-    for w in (WC.forest10(), _closed_loop().random_forest_world(64)):
-        wmap, grid = _device_grid(api, w)
+    for w in (WC.forest10(), WD.closed_loop().random_forest_world(64)):
+        wmap, grid = WD.device_grid(api, w)
         G = WC.reference_grid(oracle, w)
         assert grid.dims.tolist() == G.dims and grid.grid_min.tolist() == G.gmin
         occ = grid.download()
@@ -99,11 +64,11 @@ def test_grid_occupancy_equals_the_restatement(api, oracle, torch_cuda):
 def test_fields_equal_the_restatement(api, oracle, torch_cuda):
     import torch
 
-    for w in (WC.forest10(), _closed_loop().random_forest_world(64)):
-        wmap, grid = _device_grid(api, w)
+    for w in (WC.forest10(), WD.closed_loop().random_forest_world(64)):
+        wmap, grid = WD.device_grid(api, w)
         G = WC.reference_grid(oracle, w)
         F, init_d = R.mission_fields(G, w["starts"], w["goals"])
-        d_field, d_init_d = _device_fields(api, torch, grid, w["starts"], w["goals"])
+        d_field, d_init_d = WD.device_fields(torch, grid, w["starts"], w["goals"])
         assert np.array_equal(grid.download(mission=True).astype(bool), ~G.free)
         assert np.array_equal(d_field.cpu().numpy(), F)
         assert np.array_equal(d_init_d.cpu().numpy(), init_d)
@@ -117,13 +82,13 @@ def test_fields_of_a_grid_too_large_for_lds(api, oracle, torch_cuda):
     import torch
 
     w = WC.walled_world(400)
-    wmap, grid = _device_grid(api, w)
+    wmap, grid = WD.device_grid(api, w)
     assert grid.dims.tolist() == [400, 400, 1]
     occ = grid.download().astype(bool)
     assert 1000 < occ.sum() < 4000
     G = R.Grid(w["world_min"], w["world_max"], w["z_2d"], 0.5, w["radius"], occ=occ)
     F, init_d = R.mission_fields(G, w["starts"], w["goals"])
-    d_field, d_init_d = _device_fields(api, torch, grid, w["starts"], w["goals"])
+    d_field, d_init_d = WD.device_fields(torch, grid, w["starts"], w["goals"])
     got = d_field.cpu().numpy()
     assert np.array_equal(got, F)
     assert np.array_equal(d_init_d.cpu().numpy(), init_d)
@@ -139,10 +104,10 @@ def test_waypoints_on_forest10_along_a_rollout(api, oracle, torch_cuda):
     import torch
 
     w = WC.forest10()
-    wmap, grid = _device_grid(api, w)
+    wmap, grid = WD.device_grid(api, w)
     G = WC.reference_grid(oracle, w)
     F, init_d = R.mission_fields(G, w["starts"], w["goals"])
-    d_field, d_init_d = _device_fields(api, torch, grid, w["starts"], w["goals"])
+    d_field, d_init_d = WD.device_fields(torch, grid, w["starts"], w["goals"])
     n_updated, n_groups = 0, set()
     for s in WC.seeded_states(G, w, F, init_d, 30, 3.0, seed=3):
         label, updated = _compare_step(api, torch, grid, G, 3.0, s, F, init_d, d_field, d_init_d)
@@ -159,11 +124,11 @@ def test_waypoints_on_random_forests(api, oracle, torch_cuda, n_agents):
     circle and on 512 agents between random nodes of a denser forest."""
     import torch
 
-    w = _closed_loop().random_forest_world(64) if n_agents == 64 else WC.random_mission(512)
-    wmap, grid = _device_grid(api, w)
+    w = WD.closed_loop().random_forest_world(64) if n_agents == 64 else WC.random_mission(512)
+    wmap, grid = WD.device_grid(api, w)
     G = WC.reference_grid(oracle, w)
     F, init_d = R.mission_fields(G, w["starts"], w["goals"])
-    d_field, d_init_d = _device_fields(api, torch, grid, w["starts"], w["goals"])
+    d_field, d_init_d = WD.device_fields(torch, grid, w["starts"], w["goals"])
     assert np.array_equal(d_init_d.cpu().numpy(), init_d)
     seen = {}
     for rng in (-1, 3.0, 2.0, 1.0):
@@ -181,36 +146,21 @@ def test_waypoints_on_toy_cases(api, oracle, torch_cuda, name):
     import torch
 
     c = WC.toy_case(name)
-    wmap, grid = _device_grid(api, c["world"])
+    wmap, grid = WD.device_grid(api, c["world"])
     assert np.array_equal(grid.download().astype(bool), c["world"]["occ"])
     G = WC.reference_grid(oracle, c["world"])
     F, init_d = R.mission_fields(G, c["starts"], c["goals"])
-    d_field, d_init_d = _device_fields(api, torch, grid, c["starts"], c["goals"])
+    d_field, d_init_d = WD.device_fields(torch, grid, c["starts"], c["goals"])
     assert np.array_equal(d_field.cpu().numpy(), F) and np.array_equal(d_init_d.cpu().numpy(), init_d)
     if c["init_d"] is not None:
         init_d = np.array(c["init_d"])
-        d_init_d = _dev(torch, init_d, np.int32)
+        d_init_d = WD.dev(torch, init_d, np.int32)
     s = dict(positions=c["positions"], plans=None, current_goals=c["current_goals"], waypoints=c["waypoints"])
     _compare_step(api, torch, grid, G, c["range"], s, F, init_d, d_field, d_init_d)
-    _, d, _, _ = _device_step(api, torch, grid, c["range"], c["positions"], c["current_goals"], c["waypoints"], d_field, d_init_d)
+    _, d, _, _ = WD.decision_step(torch, grid, c["range"], s, d_field, d_init_d)
     assert d.tolist() == c["expect"]
     grid.close()
     wmap.close()
-
-
-def _agents(api, W, N):
-    ag = np.zeros(N, api.AGENT_PARAM_DTYPE)
-    ag["radius"], ag["downwash"], ag["max_vel"], ag["max_acc"], ag["nominal_velocity"] = W["radius"], 2.0, 1.0, 2.0, 1.0
-    return ag
-
-
-def _forest10_plan(api, W, waypoint_mode, **kw):
-    N = len(W["starts"])
-    sol = api.Solver(api.make_desc(M=10, dim=2, dt=0.2, world_min=W["world_min"], world_max=W["world_max"]))
-    wmap = api.WorldMap(W["boxes"], W["world_min"], W["world_max"], W["resolution"], W["max_dist"])
-    plan = api.Plan(sol, wmap, N, N - 1, _agents(api, W, N), constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, optimize_goal=True, closed_loop=True,
-                    z_2d=W["z_2d"], safety_samples=2, record_time_step=0.1, waypoint_mode=waypoint_mode, **kw)
-    return sol, wmap, plan
 
 
 def _plan_points(x, N, M, z):
@@ -237,7 +187,7 @@ def test_forest10_flies_from_starts_and_goals_alone(api, oracle, torch_cuda):
     RAW = (api.PLAN_HEADER, api.PLAN_ROWS, api.PLAN_SFC, api.PLAN_INFO, api.PLAN_SAFETY)
     flights = {}
     for graph in (False, True):
-        sol, wmap, plan = _forest10_plan(api, W, api.WAYPOINT_GRID_PIBT)
+        sol, wmap, plan = WD.forest10_plan(api, W, api.WAYPOINT_GRID_PIBT)
         plan.reset(starts, goals)
         assert np.array_equal(plan.get(api.PLAN_WAYPOINT).reshape(N, 3), np.float32(starts).astype(float))
         assert np.array_equal(plan.get(api.PLAN_DESIRED_GOAL).reshape(N, 3), np.float32(goals).astype(float))
@@ -290,11 +240,11 @@ def test_fields_either_side_of_the_lds_limit(api, oracle, torch_cuda, nodes):
     import torch
 
     w = WC.walled_world(nodes)
-    wmap, grid = _device_grid(api, w)
+    wmap, grid = WD.device_grid(api, w)
     assert grid.dims.tolist() == [nodes, nodes, 1]
     G = R.Grid(w["world_min"], w["world_max"], w["z_2d"], 0.5, w["radius"], occ=grid.download().astype(bool))
     F, init_d = R.mission_fields(G, w["starts"], w["goals"])
-    d_field, d_init_d = _device_fields(api, torch, grid, w["starts"], w["goals"])
+    d_field, d_init_d = WD.device_fields(torch, grid, w["starts"], w["goals"])
     assert np.array_equal(d_field.cpu().numpy(), F)
     assert np.array_equal(d_init_d.cpu().numpy(), init_d)
     assert init_d[2] == api.GRID_UNREACHABLE and 0 < init_d[0] < 2000
@@ -308,7 +258,7 @@ def test_closed_loop_tool_with_either_router(router):
     lscqp_waypoints_device in place of the host stand-in holds the bars of test_closed_loop.py."""
     import json
 
-    log = _closed_loop().run(os.path.join(ROOT, "tests", "golden", "forest10_world.json"), steps=60, router=router)
+    log = WD.closed_loop().run(os.path.join(ROOT, "tests", "golden", "forest10_world.json"), steps=60, router=router)
     back = json.loads(json.dumps(log))
     assert back["router"] == router == log["router"]
     assert log["qp_failed"] == 0 and log["invalid"] == 0 and log["sfc_kept"] == 0, log
@@ -318,7 +268,7 @@ def test_closed_loop_tool_with_either_router(router):
     if router == "device":
         assert log["waypoints_updated"] > 50, log
     with pytest.raises(ValueError):
-        _closed_loop().run(os.path.join(ROOT, "tests", "golden", "forest10_world.json"), steps=1, router="elsewhere")
+        WD.closed_loop().run(os.path.join(ROOT, "tests", "golden", "forest10_world.json"), steps=1, router="elsewhere")
 
 
 def test_range_zero_leaves_every_agent_alone(api, torch_cuda):
@@ -329,7 +279,7 @@ def test_range_zero_leaves_every_agent_alone(api, torch_cuda):
     N = 10
     sol = api.Solver(api.make_desc(M=10, dim=2, dt=0.2, comm_range=0.0, world_min=W["world_min"], world_max=W["world_max"]))
     wmap = api.WorldMap(W["boxes"], W["world_min"], W["world_max"], W["resolution"], W["max_dist"])
-    plan = api.Plan(sol, wmap, N, N - 1, _agents(api, W, N), constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, closed_loop=True, z_2d=W["z_2d"],
+    plan = api.Plan(sol, wmap, N, N - 1, WD.agents(api, W["radius"], N), constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, closed_loop=True, z_2d=W["z_2d"],
                     waypoint_mode=api.WAYPOINT_GRID_PIBT)
     plan.reset(np.array(W["starts"], float), np.array(W["goals"], float))
     for _ in range(3):
@@ -351,7 +301,7 @@ def test_waypoint_mode_0_is_unchanged(api, torch_cuda):
     starts, goals = np.array(W["starts"], float), np.array(W["goals"], float)
     nodes = {}
     for mode in (api.WAYPOINT_FROM_CALLER, api.WAYPOINT_GRID_PIBT):
-        sol, wmap, plan = _forest10_plan(api, W, mode)
+        sol, wmap, plan = WD.forest10_plan(api, W, mode)
         if mode == api.WAYPOINT_FROM_CALLER:
             for b in (api.PLAN_DESIRED_GOAL, api.PLAN_WAYPOINT_UPDATED, api.PLAN_GROUP):
                 assert plan.pointer(b) == (None, 0)
@@ -384,17 +334,17 @@ def test_argument_errors(api, torch_cuda):
     kw = dict(constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, z_2d=W["z_2d"], waypoint_mode=api.WAYPOINT_GRID_PIBT)
     sol2 = api.Solver(api.make_desc(M=10, dim=2, dt=0.2, world_min=W["world_min"], world_max=W["world_max"]))
     with pytest.raises(api.LscqpError) as e:  # a shard: not every agent's waypoint and plan is here
-        api.Plan(sol2, wmap, 5, 9, _agents(api, W, N), n_total=N, first_agent=0, **kw)
+        api.Plan(sol2, wmap, 5, 9, WD.agents(api, W["radius"], N), n_total=N, first_agent=0, **kw)
     assert e.value.code == api.ERR_INVALID_ARGUMENT and "n_agents == n_total" in str(e.value)
     sol3 = api.Solver(api.make_desc(M=5, dim=3, dt=0.2, world_min=W["world_min"], world_max=W["world_max"]))
     with pytest.raises(api.LscqpError) as e:  # a 3-D class
-        api.Plan(sol3, wmap, N, 9, _agents(api, W, N), **kw)
+        api.Plan(sol3, wmap, N, 9, WD.agents(api, W["radius"], N), **kw)
     assert e.value.code == api.ERR_INVALID_ARGUMENT and "2-D" in str(e.value)
     nosfc = api.Solver(api.make_desc(M=10, dim=2, dt=0.2, use_sfc=False, world_min=W["world_min"], world_max=W["world_max"]))
     with pytest.raises(api.LscqpError) as e:  # no map
-        api.Plan(nosfc, None, N, 9, _agents(api, W, N), **kw)
+        api.Plan(nosfc, None, N, 9, WD.agents(api, W["radius"], N), **kw)
     assert e.value.code == api.ERR_INVALID_ARGUMENT and "needs a map" in str(e.value)
-    sol, wmap2, plan = _forest10_plan(api, W, api.WAYPOINT_GRID_PIBT)
+    sol, wmap2, plan = WD.forest10_plan(api, W, api.WAYPOINT_GRID_PIBT)
     with pytest.raises(api.LscqpError) as e:  # the mission's goal points are what the fields are made from
         plan.reset(np.array(W["starts"], float))
     assert e.value.code == api.ERR_INVALID_ARGUMENT

@@ -2,54 +2,19 @@
 Python restatement of the reference (tests/grid_reference.py).  Each case goes through all three and every comparison is exact equality of
 the group, the desired node, the updated flag and the waypoint buffer.  Where a case breaks PIBT's precondition (two members of a group on
 one waypoint node) the restatement is undefined and the two device entries are compared alone; the case says so."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
 from tests import grid_reference as R
 from tests import waypoint_cases as WC
+from tests import waypoint_device as WD
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 
 
-def _closed_loop():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import closed_loop
-
-    return closed_loop
-
-
-def _dev(torch, a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to("cuda")
-
-
-def _device_grid(api, w, resolution=0.5):
-    wmap = api.WorldMap(w["boxes"], w["world_min"], w["world_max"], w["resolution"], w["max_dist"])
-    return wmap, api.Grid(wmap, resolution, w["radius"], w["z_2d"])
-
-
-def _device_fields(torch, grid, starts, goals):
-    f, d = grid.fields(_dev(torch, starts, np.float64), _dev(torch, goals, np.float64))
-    torch.cuda.synchronize()
-    return f, d
-
-
-def _step(torch, grid, wide, rng, s, d_field, d_init_d, M=10):
-    """(group, desired, updated, new waypoints) of one decision by the wide entry or the one-workgroup entry."""
-    n = len(s["waypoints"])
-    st = np.zeros((n, 9))
-    st[:, :3] = s["positions"]
-    d_way = _dev(torch, s["waypoints"], np.float64)
-    d_plan = None if s["plans"] is None else _dev(torch, WC.plan_from_points(np.asarray(s["plans"])), np.float64)
-    fn = grid.waypoints_wide if wide else grid.waypoints
-    g, d, u = fn(rng, M, 2, _dev(torch, st), d_plan, _dev(torch, s["current_goals"], np.float64), d_field, d_init_d, d_way)
-    torch.cuda.synchronize()
-    assert grid.status() == 0
-    return g.cpu().numpy(), d.cpu().numpy(), u.cpu().numpy(), d_way.cpu().numpy().reshape(n, 3)
+def _step(torch, grid, wide, rng, s, d_field, d_init_d):
+    return WD.decision_step(torch, grid, rng, s, d_field, d_init_d, wide=wide)
 
 
 def _compare(torch, grid, G, rng, s, F, init_d, d_field, d_init_d, restatement=True):
@@ -70,13 +35,13 @@ def test_wide_on_toy_cases(api, oracle, torch_cuda, name):
     import torch
 
     c = WC.toy_case(name)
-    wmap, grid = _device_grid(api, c["world"])
+    wmap, grid = WD.device_grid(api, c["world"])
     G = WC.reference_grid(oracle, c["world"])
     F, init_d = R.mission_fields(G, c["starts"], c["goals"])
-    d_field, d_init_d = _device_fields(torch, grid, c["starts"], c["goals"])
+    d_field, d_init_d = WD.device_fields(torch, grid, c["starts"], c["goals"])
     if c["init_d"] is not None:
         init_d = np.array(c["init_d"])
-        d_init_d = _dev(torch, init_d, np.int32)
+        d_init_d = WD.dev(torch, init_d, np.int32)
     s = dict(positions=c["positions"], plans=None, current_goals=c["current_goals"], waypoints=c["waypoints"])
     _, d, _, _ = _compare(torch, grid, G, c["range"], s, F, init_d, d_field, d_init_d)
     assert d.tolist() == c["expect"]
@@ -88,10 +53,10 @@ def test_wide_on_forest10_along_a_rollout(api, oracle, torch_cuda):
     import torch
 
     w = WC.forest10()
-    wmap, grid = _device_grid(api, w)
+    wmap, grid = WD.device_grid(api, w)
     G = WC.reference_grid(oracle, w)
     F, init_d = R.mission_fields(G, w["starts"], w["goals"])
-    d_field, d_init_d = _device_fields(torch, grid, w["starts"], w["goals"])
+    d_field, d_init_d = WD.device_fields(torch, grid, w["starts"], w["goals"])
     n_updated, n_groups = 0, set()
     for s in WC.seeded_states(G, w, F, init_d, 30, 3.0, seed=3):
         g, _, u, _ = _compare(torch, grid, G, 3.0, s, F, init_d, d_field, d_init_d)
@@ -108,11 +73,11 @@ def test_wide_on_random_forests(api, oracle, torch_cuda, n_agents):
     tests/test_waypoints_gpu.py asserts, so "one group" and "hundreds of groups" are both known to be exercised."""
     import torch
 
-    w = _closed_loop().random_forest_world(64) if n_agents == 64 else WC.random_mission(512)
-    wmap, grid = _device_grid(api, w)
+    w = WD.closed_loop().random_forest_world(64) if n_agents == 64 else WC.random_mission(512)
+    wmap, grid = WD.device_grid(api, w)
     G = WC.reference_grid(oracle, w)
     F, init_d = R.mission_fields(G, w["starts"], w["goals"])
-    d_field, d_init_d = _device_fields(torch, grid, w["starts"], w["goals"])
+    d_field, d_init_d = WD.device_fields(torch, grid, w["starts"], w["goals"])
     seen = {}
     for rng in (-1, 3.0, 2.0, 1.0):
         for s in WC.seeded_states(G, w, F, init_d, 4 if n_agents == 64 else 2, rng, seed=11):
@@ -135,7 +100,7 @@ class _Open:
 
     def __init__(self, api, torch):
         self.torch = torch
-        self.wmap, self.grid = _device_grid(api, OPEN)
+        self.wmap, self.grid = WD.device_grid(api, OPEN)
         self.G = R.Grid(OPEN["world_min"], OPEN["world_max"], OPEN["z_2d"], 0.5, OPEN["radius"], occ=self.grid.download().astype(bool))
         assert self.G.dims[:2] == [41, 41] and 0 < self.G.occ.sum() < 20
         ys, xs = np.nonzero(~self.G.occ)
@@ -148,7 +113,7 @@ class _Open:
         way = self.free[rnd.permutation(len(self.free))[:n]] if waypoints is None else np.array(waypoints, float)
         goals = np.array([list(GOALS[k]) + [OPEN["z_2d"]] for k in rnd.integers(0, len(GOALS), n)])
         F, init_d = R.mission_fields(self.G, list(way), list(goals))
-        d_field, d_init_d = _device_fields(self.torch, self.grid, way, goals)
+        d_field, d_init_d = WD.device_fields(self.torch, self.grid, way, goals)
         assert np.array_equal(d_init_d.cpu().numpy(), init_d)
         way = f32(way).astype(float)
         return dict(plans=None, current_goals=way.copy(), waypoints=way), F, init_d, d_field, d_init_d
@@ -255,6 +220,16 @@ def test_one_group_of_1000(open_world):
     assert (g == 0).all() and len(set(d.tolist())) == 1000 and u.sum() > 0
 
 
+def test_one_group_of_1100(open_world):
+    """More members than a segment that is sorted in LDS holds (1024): the group's keys are sorted in their place in HBM."""
+    o = open_world
+    assert len(o.free) > 1660
+    s, F, init_d, d_field, d_init_d = o.swarm(1100, seed=22)
+    s["positions"] = s["waypoints"].copy()
+    g, d, u, _ = _compare(o.torch, o.grid, o.G, -1.0, s, F, init_d, d_field, d_init_d)
+    assert (g == 0).all() and len(set(d.tolist())) == 1100 and u.sum() > 0
+
+
 def test_two_members_on_one_node(open_world):
     """PIBT's precondition broken: agents 0 and 2 of one group hold the same waypoint node.  The restatement is undefined there, so this
     case compares the two device entries only: the larger id is the node's holder in both."""
@@ -291,7 +266,7 @@ def test_wide_argument_errors(api, open_world):
     o = open_world
     s, F, init_d, d_field, d_init_d = o.swarm(4, seed=2)
     st = torch.zeros((4, 9), dtype=torch.float64, device="cuda")
-    way = _dev(torch, s["waypoints"], np.float64)
+    way = WD.dev(torch, s["waypoints"], np.float64)
     plan = torch.zeros((4, 120), dtype=torch.float64, device="cuda")
     with pytest.raises(api.LscqpError) as e:
         o.grid.waypoints_wide(3.0, 10, 3, st, None, way, d_field, d_init_d, way.clone())
@@ -318,10 +293,10 @@ def forest512(api, oracle, torch_cuda):
     import torch
 
     w = WC.random_mission(512)
-    wmap, grid = _device_grid(api, w)
+    wmap, grid = WD.device_grid(api, w)
     G = WC.reference_grid(oracle, w)
     F, init_d = R.mission_fields(G, w["starts"], w["goals"])
-    d_field, d_init_d = _device_fields(torch, grid, w["starts"], w["goals"])
+    d_field, d_init_d = WD.device_fields(torch, grid, w["starts"], w["goals"])
     s = WC.seeded_states(G, w, F, init_d, 2, 2.0, seed=11)[1]
     yield dict(grid=grid, s=s, d_field=d_field, d_init_d=d_init_d)
     grid.close()
@@ -360,8 +335,8 @@ def test_captured_in_a_graph(forest512):
     grid.reserve_wide(n)
     st = np.zeros((n, 9))
     st[:, :3] = s["positions"]
-    d_st, d_plan, d_cg = _dev(torch, st), _dev(torch, WC.plan_from_points(np.asarray(s["plans"])), np.float64), _dev(torch, s["current_goals"], np.float64)
-    d_way0 = _dev(torch, s["waypoints"], np.float64)
+    d_st, d_plan, d_cg = WD.dev(torch, st), WD.dev(torch, WC.plan_from_points(np.asarray(s["plans"])), np.float64), WD.dev(torch, s["current_goals"], np.float64)
+    d_way0 = WD.dev(torch, s["waypoints"], np.float64)
     d_way = d_way0.clone()
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()

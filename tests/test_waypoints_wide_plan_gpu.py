@@ -4,23 +4,9 @@ import numpy as np
 import pytest
 
 from tests import waypoint_cases as WC
+from tests import waypoint_device as WD
 
 pytestmark = pytest.mark.gpu
-
-
-def _agents(api, W, N):
-    ag = np.zeros(N, api.AGENT_PARAM_DTYPE)
-    ag["radius"], ag["downwash"], ag["max_vel"], ag["max_acc"], ag["nominal_velocity"] = W["radius"], 2.0, 1.0, 2.0, 1.0
-    return ag
-
-
-def _forest10_plan(api, W, waypoint_mode=1, **kw):
-    N = len(W["starts"])
-    sol = api.Solver(api.make_desc(M=10, dim=2, dt=0.2, world_min=W["world_min"], world_max=W["world_max"]))
-    wmap = api.WorldMap(W["boxes"], W["world_min"], W["world_max"], W["resolution"], W["max_dist"])
-    plan = api.Plan(sol, wmap, N, N - 1, _agents(api, W, N), constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, optimize_goal=True, closed_loop=True,
-                    z_2d=W["z_2d"], safety_samples=2, record_time_step=0.1, waypoint_mode=waypoint_mode, **kw)
-    return sol, wmap, plan
 
 
 def _snapshot(api, plan):
@@ -42,7 +28,7 @@ def test_forest10_flies_the_same_with_the_wide_decision(api, torch_cuda):
     flights, nodes = {}, {}
     for decision in (api.DECISION_ONE_WORKGROUP, api.DECISION_WIDE):
         for graph in (False, True):
-            sol, wmap, plan = _forest10_plan(api, W)
+            sol, wmap, plan = WD.forest10_plan(api, W)
             if decision != api.DECISION_ONE_WORKGROUP:
                 plan.set_waypoint_decision(decision)
             plan.reset(starts, goals)
@@ -70,7 +56,7 @@ def test_graph_node_count_survives_resets(api, torch_cuda):
 
     W = WC.forest10()
     starts, goals = np.array(W["starts"], float), np.array(W["goals"], float)
-    sol, wmap, plan = _forest10_plan(api, W)
+    sol, wmap, plan = WD.forest10_plan(api, W)
     plan.set_waypoint_decision(api.DECISION_WIDE)
     counts = []
     for g in (goals, goals[::-1].copy(), np.roll(goals, 3, axis=0)):
@@ -94,7 +80,7 @@ def test_auto_picks_the_form_by_agent_count(api, torch_cuda):
     starts, goals = np.array(W["starts"], float), np.array(W["goals"], float)
     nodes = {}
     for decision in (api.DECISION_ONE_WORKGROUP, api.DECISION_AUTO):
-        sol, wmap, plan = _forest10_plan(api, W)
+        sol, wmap, plan = WD.forest10_plan(api, W)
         plan.set_waypoint_decision(decision)
         plan.reset(starts, goals)
         for _ in range(2):
@@ -108,13 +94,13 @@ def test_auto_picks_the_form_by_agent_count(api, torch_cuda):
 
 def test_setter_is_refused_without_the_grid_planner(api, torch_cuda):
     W = WC.forest10()
-    sol, wmap, plan = _forest10_plan(api, W, waypoint_mode=api.WAYPOINT_FROM_CALLER)
+    sol, wmap, plan = WD.forest10_plan(api, W, waypoint_mode=api.WAYPOINT_FROM_CALLER)
     for decision in (api.DECISION_ONE_WORKGROUP, api.DECISION_WIDE, api.DECISION_AUTO):
         with pytest.raises(api.LscqpError) as e:
             plan.set_waypoint_decision(decision)
         assert e.value.code == api.ERR_INVALID_ARGUMENT and "LSCQP_WAYPOINT_FROM_CALLER" in str(e.value)
     plan.close()
-    sol, wmap2, plan = _forest10_plan(api, W)
+    sol, wmap2, plan = WD.forest10_plan(api, W)
     with pytest.raises(api.LscqpError) as e:
         plan.set_waypoint_decision(7)
     assert e.value.code == api.ERR_INVALID_ARGUMENT
@@ -132,7 +118,7 @@ def test_setter_and_a_partition_refuse_each_other(api, torch_cuda, first):
     W = WC.forest10()
     starts, goals = np.array(W["starts"], float), np.array(W["goals"], float)
     kw = dict(mission_offsets=[0, 5, 10]) if first == "partition" else {}
-    plans = [_forest10_plan(api, W, **kw) for _ in range(2)]
+    plans = [WD.forest10_plan(api, W, **kw) for _ in range(2)]
     a, b = plans[0][2], plans[1][2]
     if first == "decision":
         b.set_waypoint_decision(api.DECISION_WIDE)
@@ -171,7 +157,7 @@ def test_setter_works_with_a_single_mission_partition(api, torch_cuda):
 
     W = WC.forest10()
     starts, goals = np.array(W["starts"], float), np.array(W["goals"], float)
-    plans = [_forest10_plan(api, W) for _ in range(2)]
+    plans = [WD.forest10_plan(api, W) for _ in range(2)]
     a, b = plans[0][2], plans[1][2]
     b.set_missions([0, 10])
     b.set_waypoint_decision(api.DECISION_WIDE)
