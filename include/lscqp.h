@@ -1065,6 +1065,54 @@ int lscqp_diagnose(lscqp_handle h, int64_t n, const lscqp_header* hdr, const lsc
 int lscqp_dump_instance(lscqp_handle h, const lscqp_header* hdr, const lscqp_row* rows, const lscqp_box* sfc, const char* path);
 const char* lscqp_row_family_name(int32_t family);
 
+/* ---- the PRESCREEN (round 14): per-control-point infeasibility, proven in one pass in front of the solve ----------------------
+ *
+ * The reference learns that a QP has no point from CPLEX's presolve and falls back at once (src/traj_optimizer.cpp:103-144: status
+ * Infeasible / InfeasibleOrUnbounded -> QPFAILED; src/traj_planner.cpp:767-797: the caller keeps initial_traj).  The dual active-set phase
+ * reaches the same verdict only after ~70 steps.  An LSC row (:413-429), a corridor face (:372-397) and a world face (:252-253) each touch
+ * ONE control point: if the rows of one control point have no common point, the QP has none.  The prescreen (csrc/lscqp_prescreen.hip)
+ * tests that per control point, one lane each: Goldfarb-Idnani in three variables on the point's LSC rows and its interval (world box,
+ * corridor of its segment), and FIRES only with a certificate it has checked itself on the normalised rows n^_i.c >= b^_i, coordinates
+ * relative to the agent's position p0:
+ *     lambda >= 0, sum lambda = 1 over at most dim + 1 rows;  rho = sum lambda_i n^_i,  v = sum lambda_i b^_i;
+ *     D = the largest distance from p0 to a corner of the world box (over the class's `dim` axes);
+ *     violation = v - |rho|_1 D >= 1e-6 m  -- every point of the world box violates one of the rows by that much.
+ * A control point whose rows are empty by 1e-5 m or more fires; one whose rows have a point to within 0.9e-6 m never does; in between either
+ * answer is right.  Not tested: the fixed control points c0, c1, c2 of segment 0 (the reference puts no LSC row on them, :404-406), rows
+ * that couple control points, RSFC classes, and an instance with n_obs < 0 or n_obs > n_obs_max.  One verdict per instance: the lowest
+ * firing control point m*6 + i.
+ *
+ *   lscqp_prescreen_batch_device  the test alone: one certificate per instance, nothing else is written.  DEVICE pointers, asynchronous on
+ *                            `stream`, capturable; arguments validated like lscqp_solve_batch_device's; LSCQP_ERR_NO_DEVICE without a device.
+ *   lscqp_set_prescreen      LSCQP_PRESCREEN_OFF (default) / LSCQP_PRESCREEN_ON.  Waits for the device, and moves the handle's generation as
+ *                            lscqp_update does: a plan drops its captured graph and re-captures.  lscqp_prescreen reads the mode back.
+ * With the prescreen ON every solve entry that runs on one device (host-pointer, device, _ex, ordered, bound; through them lscqp_plan's
+ * chain) enqueues the prescreen first on the same stream.  A fired instance gets what the phase's own INFEASIBLE verdict writes -- x_out =
+ * the start (x_init, or hover at p0), obj 0, LSCQP_STATUS_INFEASIBLE, info {0, LSCQP_INFO_ACTIVE_SET | LSCQP_INFO_PRESCREENED, res_primal =
+ * the proven violation, 0, 0} -- and every kernel behind skips it (the phase through a bit of its `behind` argument, the interior-point
+ * passes by the ACTIVE_SET flag as for the phase's own verdict; as there, a caller that passes no info array leaves the later passes nothing to
+ * recognise the verdict by, and they look at the instance again).  Every other instance is marked LSCQP_STATUS_ITER_LIMIT and solved exactly as
+ * without the prescreen, bit for bit.  The one-launch fused form is not used while the prescreen is on (two launches, as with das_fused = 0);
+ * with the phase off the first interior-point pass takes only what is marked ITER_LIMIT.  The sharded multi-device entries
+ * call the device entry once per device and inherit the mode; nothing of theirs was changed for it.
+ * OFF: nothing of this happens -- same launches, same arguments, same graph nodes. */
+#define LSCQP_PRESCREEN_OFF 0
+#define LSCQP_PRESCREEN_ON 1
+#define LSCQP_INFO_PRESCREENED 128  /* lscqp_info.flags: LSCQP_STATUS_INFEASIBLE by the prescreen; res_primal = the proven violation */
+typedef struct lscqp_prescreen_cert { /* 72 bytes */
+    int32_t fired;         /* 0 / 1 */
+    int32_t control_point; /* m*6 + i, -1 if not fired */
+    int32_t n_rows;        /* 1..4, 0 if not fired */
+    int32_t reserved;
+    int32_t row[4];        /* >= 0: index into the instance's row list (oi * 6 M + control_point); -1-(2*axis+side): interval face, side 0 = lower */
+    double lambda[4];      /* >= 0, sum 1 */
+    double violation;      /* proven, metres (>= 1e-6 when fired) */
+} lscqp_prescreen_cert;
+int lscqp_prescreen_batch_device(lscqp_handle h, int64_t n, int32_t n_obs_max, const lscqp_header* d_hdr, const lscqp_row* d_rows,
+                                 const uint64_t* d_row_offsets, const lscqp_box* d_sfc, lscqp_prescreen_cert* d_cert_out, void* stream);
+int lscqp_set_prescreen(lscqp_handle h, int32_t mode);
+int lscqp_prescreen(lscqp_handle h);
+
 /* Number of inequality rows populatebyrow adds for an agent with n_obs obstacles (SFC + LSC + velocity +
  * acceleration + communication, src/traj_optimizer.cpp:370-500), not counting rows dropped for tiny normals. */
 int lscqp_num_inequalities(lscqp_handle h, int32_t n_obs);

@@ -16,6 +16,8 @@ STATUS_OPTIMAL, STATUS_INFEASIBLE, STATUS_ITER_LIMIT, STATUS_NUMERIC, STATUS_CAP
 PRECISION_F64, PRECISION_MIXED = 0, 1  # lscqp_class_desc.precision
 WARM_DEFAULT, WARM_TIGHT = 0, 1  # lscqp_class_desc.warm_start
 INFO_FLOOR_ACCEPTED, INFO_REPAIRED, INFO_RECENTRED, INFO_REMEMBERED, INFO_SHIFTED, INFO_RESCUED, INFO_ACTIVE_SET = 1, 2, 4, 8, 16, 32, 64  # lscqp_info.flags
+INFO_PRESCREENED = 128  # lscqp_info.flags: INFEASIBLE by the prescreen (lscqp_set_prescreen)
+PRESCREEN_OFF, PRESCREEN_ON = 0, 1  # lscqp_set_prescreen
 ACTIVE_SET_DEFAULT, ACTIVE_SET_OFF, ACTIVE_SET_ONLY = 0, 1, 2  # lscqp_class_desc.active_set
 (DAS_WHY_CAPACITY, DAS_WHY_EMPTY_INTERVAL, DAS_WHY_ROWS, DAS_WHY_STEPS, DAS_WHY_NO_STEP, DAS_WHY_PIVOT, DAS_WHY_VERIFICATION,
  DAS_WHY_MULTIPLIER) = range(1, 9)
@@ -52,6 +54,8 @@ assert HEADER_DTYPE.itemsize == 256 and ROW_DTYPE.itemsize == 32 and BOX_DTYPE.i
 assert INFO_DTYPE.itemsize == 32
 # lscqp_diag (failure diagnostics): per row family the largest violation / count, and the most violated row by name
 ROW_BOUND, ROW_SFC, ROW_LSC, ROW_VEL, ROW_ACC, ROW_COMM_PAIR, ROW_COMM_WAYPOINT, ROW_EQUALITY, ROW_FAMILIES = range(9)
+PRESCREEN_CERT_DTYPE = np.dtype([("fired", "i4"), ("control_point", "i4"), ("n_rows", "i4"), ("reserved", "i4"), ("row", "i4", 4),
+                                 ("lambda", "f8", 4), ("violation", "f8")])  # lscqp_prescreen_cert, 72 bytes
 DIAG_DTYPE = np.dtype([("worst", "f8", 8), ("violated", "i4", 8), ("violation", "f8"), ("family", "i4"), ("obstacle", "i4"),
                        ("segment", "i4"), ("point", "i4"), ("axis", "i4"), ("reserved", "i4")])
 assert DIAG_DTYPE.itemsize == 128
@@ -284,6 +288,15 @@ def lib():
         L.lscqp_dump_instance.argtypes = [vp, vp, vp, vp, C.c_char_p]
         L.lscqp_row_family_name.restype = C.c_char_p
         L.lscqp_row_family_name.argtypes = [C.c_int32]
+        if hasattr(L, "lscqp_set_prescreen"):  # (LSCQP_LIB may name an A/B build that predates the prescreen: tools/prescreen_timing.py)
+            L.lscqp_prescreen_batch_device.restype = C.c_int
+            L.lscqp_prescreen_batch_device.argtypes = [vp, C.c_int64, C.c_int32] + [vp] * 6
+            L.lscqp_set_prescreen.restype = C.c_int
+            L.lscqp_set_prescreen.argtypes = [vp, C.c_int32]
+            L.lscqp_prescreen.restype = C.c_int
+            L.lscqp_prescreen.argtypes = [vp]
+            L.lscqp_debug_prescreen_twin_.restype = C.c_int
+            L.lscqp_debug_prescreen_twin_.argtypes = [vp, C.c_int64, C.c_int32] + [vp] * 5
         _lib = L
     return _lib
 
@@ -305,6 +318,7 @@ EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_
                     "lscqp_plan_set_missions", "lscqp_plan_missions", "lscqp_plan_mission_status", "lscqp_select_neighbours_missions_device",
                     "lscqp_safety_metrics_missions_device", "lscqp_grid_fields_missions_device", "lscqp_waypoints_missions_device", "lscqp_grid_mission_status",
                     "lscqp_instance_work", "lscqp_diagnose", "lscqp_diagnose_device", "lscqp_dump_instance", "lscqp_row_family_name",
+                    "lscqp_prescreen_batch_device", "lscqp_set_prescreen", "lscqp_prescreen",
                     "lscqp_last_error", "lscqp_version"]
 
 
@@ -1055,6 +1069,72 @@ class Solver:
                                                     p(d_obj), p(d_status), p(d_info), int(retry), p(d_order), C.c_void_p(s.cuda_stream))
         if rc != OK:
             raise LscqpError(rc, lib().lscqp_last_error().decode())
+
+    # ---- the prescreen (include/lscqp.h) --------------------------------------------------------------------
+    def set_prescreen(self, mode):
+        """lscqp_set_prescreen: PRESCREEN_ON / PRESCREEN_OFF -- the per-control-point infeasibility test in front of every solve of this handle."""
+        rc = lib().lscqp_set_prescreen(self._h, int(mode))
+        if rc != OK:
+            raise LscqpError(rc, lib().lscqp_last_error().decode())
+
+    def prescreen(self):
+        return lib().lscqp_prescreen(self._h)
+
+    def prescreen_device(self, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, d_cert, stream=None):
+        """lscqp_prescreen_batch_device: the test alone, one PRESCREEN_CERT_DTYPE record per instance into d_cert (72 n bytes).  Torch CUDA
+        tensors (only data_ptr() is used) or None; asynchronous on `stream` or torch's current stream."""
+        import torch
+
+        s = stream if stream is not None else torch.cuda.current_stream()
+
+        def p(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+
+        rc = lib().lscqp_prescreen_batch_device(self._h, n, n_obs_max, p(d_hdr), p(d_rows), p(d_off), p(d_sfc), p(d_cert), C.c_void_p(s.cuda_stream))
+        if rc != OK:
+            raise LscqpError(rc, lib().lscqp_last_error().decode())
+
+    def prescreen_host(self, hdr, rows, row_offsets, sfc):
+        """The prescreen on host arrays: staged to the current device, tested there, the certificates (PRESCREEN_CERT_DTYPE[n]) fetched back."""
+        import torch
+
+        n = len(hdr)
+        hdr = np.ascontiguousarray(hdr, dtype=HEADER_DTYPE)
+        n_obs_max = int(hdr["n_obs"].max()) if n else 0
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+
+        def up(a):
+            if a is None:
+                return None
+            t = torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy())
+            return t.to(dev) if dev is not None else t
+
+        d_rows = up(self.rows_in_format(rows)) if rows is not None else None
+        d_off = up(np.ascontiguousarray(row_offsets, dtype=np.uint64)) if row_offsets is not None else None
+        d_sfc = up(np.ascontiguousarray(sfc, dtype=BOX_DTYPE).reshape(-1)) if sfc is not None else None
+        d_hdr = up(hdr)
+        d_cert = torch.zeros(max(n, 1) * PRESCREEN_CERT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.prescreen_device(n, max(n_obs_max, 0), d_hdr, d_rows, d_off, d_sfc, d_cert)
+        torch.cuda.synchronize()
+        return d_cert.cpu().numpy()[:n * PRESCREEN_CERT_DTYPE.itemsize].view(PRESCREEN_CERT_DTYPE).copy()
+
+    def prescreen_twin(self, hdr, rows, row_offsets, sfc, n_obs_max=None):
+        """(library-internal, tests) the prescreen kernel's per-control-point arithmetic on the host: lscqp_debug_prescreen_twin_."""
+        n = len(hdr)
+        hdr = np.ascontiguousarray(hdr, dtype=HEADER_DTYPE)
+        rows = self.rows_in_format(rows) if rows is not None else None
+        row_offsets = np.ascontiguousarray(row_offsets, dtype=np.uint64) if row_offsets is not None else None
+        sfc = np.ascontiguousarray(sfc, dtype=BOX_DTYPE).reshape(-1) if sfc is not None else None
+        out = np.zeros(n, PRESCREEN_CERT_DTYPE)
+
+        def p(a):
+            return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+        cap = int(hdr["n_obs"].max()) if n_obs_max is None else int(n_obs_max)
+        rc = lib().lscqp_debug_prescreen_twin_(self._h, n, max(cap, 0), p(hdr), p(rows), p(row_offsets), p(sfc), p(out))
+        if rc != OK:
+            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        return out
 
     def device_fill(self, n, n_obs_max):
         """lscqp_device_fill: instances one device works on at once in the first kernel of a solve of this class."""

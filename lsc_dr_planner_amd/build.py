@@ -142,6 +142,12 @@ def build(force=False, verbose=False, jobs=None):
     das_sync_o = os.path.join(OBJ, "lscqp_das_sync.o")
     if force or _newer(das_sync_o, hdrs + das_hdr + [das_src]):
         tasks.append([HIPCC] + FLAGS + ["-ffp-contract=on", "-DLSCQP_DAS_FULL_SYNC", "-c", das_src, "-o", das_sync_o])
+    pre_o = os.path.join(OBJ, "lscqp_prescreen.o")
+    objs.append(pre_o)
+    pre_src = os.path.join(CSRC, "lscqp_prescreen.hip")
+    if force or _newer(pre_o, hdrs + [pre_src]):
+        # (-ffp-contract=on as the phase: the row formats' instantiations and the host twin then round alike wherever the source writes one expression)
+        tasks.append([HIPCC] + FLAGS + ["-ffp-contract=on", "-c", pre_src, "-o", pre_o])
     diag_o = os.path.join(OBJ, "lscqp_diag.o")
     objs.append(diag_o)
     diag_src = os.path.join(CSRC, "lscqp_diag.hip")

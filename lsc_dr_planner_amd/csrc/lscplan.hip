@@ -456,6 +456,10 @@ int refresh(lscqp_plan_s* p) {
             const int rc = lscqp_update(p->hq, &cd);
             if (rc != LSCQP_OK) return rc;
         }
+        if (p->own_hq && lscqp_prescreen(p->hq) != lscqp_prescreen(p->h)) {  // (lscqp_set_prescreen moves the generation too: the clone follows the mode)
+            const int rc = lscqp_set_prescreen(p->hq, lscqp_prescreen(p->h));
+            if (rc != LSCQP_OK) return rc;
+        }
     }
     if (mg != p->map_gen && p->grid && p->fields_valid) {  // the map moved under the mission: its grid and fields are made again
         const int rc = make_grid(p, p->grid_resolution);
@@ -547,6 +551,7 @@ int lscqp_plan_create(lscqp_handle h, lscqp_map map, const lscqp_plan_desc* desc
             return rc_clone;  // (lscqp_create has set the message)
         }
         p->own_hq = true;
+        if (lscqp_prescreen(h) != LSCQP_PRESCREEN_OFF) (void)lscqp_set_prescreen(p->hq, lscqp_prescreen(h));
     }
     p->h_gen = lscqp_handle_generation_(h);
     p->map_gen = map ? lscqp_map_generation_(map) : 0;

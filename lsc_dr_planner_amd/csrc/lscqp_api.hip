@@ -40,6 +40,10 @@ extern "C" hipError_t lscqp_launch_das(const lscqp::DevClass* cls, int M, int di
                                        int stage_rows, int screen, const double* d_tab, int64_t n, const lscqp_header* hdr, const lscqp_row* rows, const uint64_t* row_offsets,
                                        const lscqp_box* sfc, const double* x_init, double* x_out, double* obj_out, int32_t* status_out,
                                        lscqp_info* info_out, hipStream_t stream);
+// the prescreen (lscqp_prescreen.hip): cert_out for the standalone entry, the solve's outputs in front of a solve
+extern "C" hipError_t lscqp_launch_prescreen(const lscqp::DevClass* cls, int M, int dim, int cap, int64_t n, const lscqp_header* hdr, const lscqp_row* rows,
+                                             const uint64_t* row_offsets, const lscqp_box* sfc, const double* x_init, lscqp_prescreen_cert* cert_out,
+                                             double* x_out, double* obj_out, int32_t* status_out, lscqp_info* info_out, hipStream_t stream);
 // the phase and the first interior-point pass in one launch (lscqp_fused.hip), per instance of LSCQP_FUSED_INSTANCES
 using fused_fn = hipError_t (*)(const lscqp::DevClass*, int, int, int, int, int, const double*, int64_t, const lscqp_header*, const lscqp_row*,
                                 const uint64_t*, const lscqp_box*, const double*, double*, double*, int32_t*, lscqp_info*, hipStream_t);
@@ -419,6 +423,7 @@ struct lscqp_solver {
     Knobs knobs;              // read from the environment at lscqp_create, never afterwards (lscqp_debug_reload_knobs_ for the tests)
     std::atomic<int>* behind_needed = nullptr;  // host-pointer entries: did the last call's phase leave work for the interior-point kernel?
     uint64_t generation = 0;  // bumped by lscqp_update: holders of state derived from the class (a captured plan graph) re-derive it
+    int prescreen = LSCQP_PRESCREEN_OFF;  // lscqp_set_prescreen: the per-control-point infeasibility test in front of every single-device solve
 };
 
 static int derive(lscqp_solver* s, const lscqp_class_desc* d) {
@@ -1229,6 +1234,16 @@ int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_
     // with more active rows than that fall to the interior-point kernel.
     bool das_ran = behind_only;
     bool fused_ran = false;  // the first interior-point pass ran inside the phase's launch (lscqp_fused.hip)
+    // ---- the PRESCREEN (lscqp_prescreen.hip), in front of everything: what it proves infeasible is final (LSCQP_INFO_ACTIVE_SET |
+    // LSCQP_INFO_PRESCREENED), everything else is marked ITER_LIMIT -- the phase skips the former through bit 1 of `behind`, and a first
+    // interior-point pass without the phase in front runs the way the pass behind the phase does (repair = 3: only what is marked)
+    const bool prescreened = h->prescreen == LSCQP_PRESCREEN_ON && (retry >= 0 || behind_only);
+    if (prescreened && kn.das_screen > 0) return fail(LSCQP_ERR_UNSUPPORTED, "the lean form of the phase (knob das_screen) is not available with the prescreen on");
+    if (prescreened && !behind_only) {
+        e = lscqp_launch_prescreen(&cls, h->desc.M, h->desc.dim, n_obs_max, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_x_init, nullptr, d_x_out, d_obj_out,
+                                   d_status_out, d_info_out, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (prescreen): ") + hipGetErrorString(e));
+    }
     if (retry >= 0 && !behind_only && h->desc.active_set != LSCQP_ACTIVE_SET_OFF) {
         const bool off = kn.active_set_off && h->desc.active_set != LSCQP_ACTIVE_SET_ONLY;
         int why = 0;
@@ -1270,6 +1285,7 @@ int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_
             // form: bit 0 the lean form in front (built and measured, no gain: the phase is bound by instruction issue, not occupancy); bit 1 the
             // first look inside the loop of steps (one copy of that code: batches of at most two workgroups per CU; lscqp_das.hip, PEEL)
             const int screen = (knob(kn.das_screen, 0) ? 1 : 0) | (knob(kn.das_loop, small ? 1 : 0) ? 2 : 0);
+            const int skip_proven = prescreened ? 4 : 0;  // (lscqp_launch_das: the phase skips what the prescreen marked INFEASIBLE)
             const int Mx = h->desc.M, dx = h->desc.dim;
             // what does not fit the CU's LDS is given up in this order: staged rows, the table copy, active rows
             if (lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) > lscqp::kMaxLdsBytes) stage = 0;
@@ -1288,7 +1304,7 @@ int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_
             // pass's own class (repair = 3).  The separate pass behind the phase was a launch of n workgroups that almost all load a status and
             // leave: 64 x M5, 14.25 -> 11.82 us per call fused (profiles/r07_fused.txt).  Not for calls that look at the statuses before they
             // enqueue the pass (`deferred`), nor behind the scan form.
-            const fused_fn fused = (kn.das_fused && tiny && !mixed && !kn.behind_scan && h->desc.active_set != LSCQP_ACTIVE_SET_ONLY && !deferred &&
+            const fused_fn fused = (kn.das_fused && !prescreened && tiny && !mixed && !kn.behind_scan && h->desc.active_set != LSCQP_ACTIVE_SET_ONLY && !deferred &&
                                     threads == 256 && screen == 2 && !cls.rows_f32)
                                        ? find_fused(inst)
                                        : nullptr;
@@ -1303,7 +1319,7 @@ int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_
                 else if (e != hipErrorNotSupported) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (fused active-set phase): ") + hipGetErrorString(e));
             }
             if (!fused_ran && lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) <= lscqp::kMaxLdsBytes) {
-                e = lscqp_launch_das(&cls, Mx, dx, h->es, cap, threads, kmax, steps, cacheC, stage, screen, d_tab, n, d_hdr, d_rows, d_row_offsets, d_sfc,
+                e = lscqp_launch_das(&cls, Mx, dx, h->es, cap, threads, kmax, steps, cacheC, stage, screen | skip_proven, d_tab, n, d_hdr, d_rows, d_row_offsets, d_sfc,
                                      d_x_init, d_x_out, d_obj_out, d_status_out, d_info_out, (hipStream_t)stream);
                 if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (dual active-set phase): ") + hipGetErrorString(e));
                 das_ran = true;
@@ -1318,7 +1334,7 @@ int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_
             return LSCQP_OK;
         }
     }
-    const int first_repair = das_ran ? 3 : 0;
+    const int first_repair = (das_ran || prescreened) ? 3 : 0;
     if (!inst || !inst64) {
         // no compiled instance serves this launch (shape without one, or more obstacles than its register slots hold): the
         // run-time-shaped kernel, fp64.  Same statuses, same second pass.
@@ -1432,6 +1448,56 @@ int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_
     }
     if (retry == 2 || retry == 3) return rescue();
     return LSCQP_OK;
+}
+
+// The prescreen alone (include/lscqp.h): one certificate per instance.  The reference's counterpart is CPLEX's presolve verdict
+// (src/traj_optimizer.cpp:103-144).
+int lscqp_prescreen_batch_device(lscqp_handle h, int64_t n, int32_t n_obs_max, const lscqp_header* d_hdr, const lscqp_row* d_rows,
+                                 const uint64_t* d_row_offsets, const lscqp_box* d_sfc, lscqp_prescreen_cert* d_cert_out, void* stream) {
+    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n < 0 || n_obs_max < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
+    if (n == 0) return LSCQP_OK;
+    if (!d_hdr || !d_cert_out || (n_obs_max > 0 && (!d_rows || !d_row_offsets)) || (h->desc.use_sfc && !d_sfc))
+        return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    int ndev = 0;
+    const hipError_t de = hipGetDeviceCount(&ndev);
+    if (de != hipSuccess || ndev == 0)
+        return fail(LSCQP_ERR_NO_DEVICE, std::string("no HIP device: lscqp has no CPU fallback (hipGetDeviceCount: ") + hipGetErrorString(de) + ", " +
+                                             std::to_string(ndev) + " devices)");
+    lscqp::DevClass cls = h->dev;
+    cls.n_obs_max = n_obs_max;
+    const hipError_t e = lscqp_launch_prescreen(&cls, h->desc.M, h->desc.dim, n_obs_max, n, d_hdr, d_rows, d_row_offsets, d_sfc, nullptr, d_cert_out, nullptr,
+                                                nullptr, nullptr, nullptr, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (prescreen): ") + hipGetErrorString(e));
+    return LSCQP_OK;
+}
+
+// The prescreen in front of every single-device solve of the handle, on / off.  Like lscqp_update a host synchronisation point for holders of
+// derived state: the generation moves, and a plan (lscplan.hip) drops its captured graph and captures the new chain.
+int lscqp_set_prescreen(lscqp_handle h, int32_t mode) {
+    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (mode != LSCQP_PRESCREEN_OFF && mode != LSCQP_PRESCREEN_ON) return fail(LSCQP_ERR_INVALID_ARGUMENT, "mode must be LSCQP_PRESCREEN_OFF or LSCQP_PRESCREEN_ON");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {  // (launches in flight keep the chain they were enqueued with; wait for them)
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("hipDeviceSynchronize: ") + hipGetErrorString(e));
+    } else {
+        (void)hipGetLastError();
+    }
+    h->prescreen = mode;
+    h->generation++;
+    return LSCQP_OK;
+}
+int lscqp_prescreen(lscqp_handle h) { return h ? h->prescreen : -1; }
+// (library-internal, tests only) the prescreen's per-control-point arithmetic on HOST arrays (lscqp_prescreen.hip: lscqp_prescreen_host_twin_) -- holds the
+// certificate contract to the referee on a machine without a device.  No entry point of the ABI calls it; the product path has no CPU fallback.
+extern "C" int lscqp_prescreen_host_twin_(const lscqp::DevClass* cls, int M, int dim, int cap, int64_t n, const lscqp_header* hdr, const void* rows,
+                                          const uint64_t* row_offsets, const lscqp_box* sfc, lscqp_prescreen_cert* cert_out);
+int lscqp_debug_prescreen_twin_(lscqp_handle h, int64_t n, int32_t n_obs_max, const lscqp_header* hdr, const lscqp_row* rows, const uint64_t* row_offsets,
+                                const lscqp_box* sfc, lscqp_prescreen_cert* cert_out) {
+    if (!h || n < 0 || n_obs_max < 0 || !hdr || !cert_out || (n_obs_max > 0 && (!rows || !row_offsets)) || (h->desc.use_sfc && !sfc))
+        return fail(LSCQP_ERR_INVALID_ARGUMENT, "invalid argument");
+    return lscqp_prescreen_host_twin_(&h->dev, h->desc.M, h->desc.dim, n_obs_max, n, hdr, rows, row_offsets, sfc, cert_out);
 }
 
 int lscqp_solve_batch_device(lscqp_handle h, int64_t n, int32_t n_obs_max, const lscqp_header* d_hdr,

@@ -172,6 +172,7 @@ extern "C" int lscqp_das_blocks_per_cu(int M, int dim, int kmax, int rows_f32) {
 // capacity of the kernel instance that runs behind the phase (an instance beyond it is left to that kernel's LSCQP_STATUS_CAPACITY).
 // screen bit 1: the first look inside the loop of steps (PEEL = false; four wavefronts only).  screen bit 0: the lean one-wavefront form first (unconstrained minimiser + one pass + verification at twice the occupancy), then the
 // full form over what it left -- for batches that fill the chip, where most instances hold no active row at all.
+// screen bit 2: the prescreen (lscqp_prescreen.hip) ran in front of this launch; instances it marked LSCQP_STATUS_INFEASIBLE are skipped.
 extern "C" hipError_t lscqp_launch_das(const lscqp::DevClass* cls, int M, int dim, int es, int cap, int threads, int kmax, int max_steps, int cacheC,
                                        int stage_rows, int screen, const double* d_tab, int64_t n, const lscqp_header* hdr, const lscqp_row* rows,
                                        const uint64_t* row_offsets, const lscqp_box* sfc, const double* x_init, double* x_out, double* obj_out,
@@ -195,7 +196,7 @@ extern "C" hipError_t lscqp_launch_das(const lscqp::DevClass* cls, int M, int di
     }
     if (n <= 0) return hipSuccess;
     const bool f32 = cls->rows_f32 != 0;
-    int behind = 0;
+    int behind = (screen & 4) ? 2 : 0;  // (bit 1: the prescreen ran in front -- what it marked LSCQP_STATUS_INFEASIBLE is skipped)
     const bool loop_form = (screen & 2) != 0;  // (the first look inside the loop of steps: the four-wavefront form of small batches)
     if (screen & 1) {
         const size_t lds_s = lscqp_das_lds_bytes(M, dim, 1, 0, 0);  // (no active rows, no table copy, no staged rows)
@@ -206,7 +207,7 @@ extern "C" hipError_t lscqp_launch_das(const lscqp::DevClass* cls, int M, int di
 #undef LSCQP_DAS_SCREEN
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        behind = 1;
+        behind |= 1;
     }
 #define LSCQP_DAS_LAUNCH(NW_, F_, PEEL_)                                                                                                                       \
     hipLaunchKernelGGL((lscqp_das::das_kernel<NW_, F_, false, PEEL_>), dim3((unsigned)n), dim3(64 * NW_), lds, stream, *cls, M, dim, es, cap, kmax, max_steps, cacheC, \

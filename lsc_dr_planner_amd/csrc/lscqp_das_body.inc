@@ -46,8 +46,10 @@
     const int LDL = kcap + 1;
     int par = 0;  // which half of red_ the next cross-wavefront reduction uses (double buffered: one barrier per reduction)
 
-    if (!SCREEN && behind) {  // (uniform) behind the lean form: what it finished is skipped before anything is fetched
-        if (status_out[q] == LSCQP_STATUS_OPTIMAL) LSCQP_DAS_END(kDasSolved);
+    if (!SCREEN && behind) {  // (uniform) behind the lean form (bit 0): what it finished is skipped before anything is fetched; behind the
+        const int st_early = status_out[q];  // prescreen (bit 1, lscqp_prescreen.hip): so is what it proved infeasible
+        if ((behind & 1) && st_early == LSCQP_STATUS_OPTIMAL) LSCQP_DAS_END(kDasSolved);
+        if ((behind & 2) && st_early == LSCQP_STATUS_INFEASIBLE) LSCQP_DAS_END(kDasInfeasible);
     }
     // ---- header, corridor boxes (and the instance's row offset: one memory round trip for all three) -------------------------------
     const uint64_t roff = row_offsets ? row_offsets[q] : 0;
@@ -263,7 +265,10 @@
     // LSC row j, translated to the agent's position; false: the reference drops it (:404-406: first three control points, :409-411: zero normal)
     auto translate = [&](int j, double x, double y, double z, double w, double& nx, double& ny, double& nz, double& b) -> bool {
         nx = x, ny = y, nz = (dim == 3) ? z : 0.0;
-        b = w - (x * org0 + y * org1 + (dim == 3 ? z * org2 : 0.0));
+        // (the whole sum per arm, not `... + (dim == 3 ? z * org2 : 0.0)`: where dim is a compile-time constant -- the fused kernel -- the compiler
+        // drops the dead arm and contracts z * org2 into the sum; where it is a run-time value it could not, and the two forms of the phase differed
+        // in the last bit of b on instances with active LSC rows.  Each arm below is what the fused kernel compiles for its dim: its code is unchanged.)
+        b = (dim == 3) ? w - (x * org0 + y * org1 + z * org2) : w - (x * org0 + y * org1 + 0.0);
         return !(x * x + y * y + z * z < 1e-10) && (j - P * fdiv(j, iP)) >= 3;
     };
     auto load_row = [&](int j, double& nx, double& ny, double& nz, double& b) -> bool {  // (single rows: the candidate's)
