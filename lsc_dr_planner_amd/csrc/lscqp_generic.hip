@@ -3,9 +3,9 @@
 //
 // The reference builds its QP for whatever param.M and constraints.getObsSize() are (src/traj_optimizer.cpp:4-16, 399-437;
 // src/param.cpp:71, 128-163); the register-resident kernel of lscqp_kernel.hpp exists as a table of compiled (M, dim, end stop,
-// slots, wavefronts) instances, chosen for speed.  THIS kernel serves everything the table does not: horizons without a compiled
-// instance (M = 9; the end-stop-free DLSC / BVC / RSFC classes at M != 5, 10; reduced systems of more than 64 rows without the
-// two equal blocks the nested dissection needs), and neighbour counts beyond a compiled instance's capacity.  Same model, same
+// slots, wavefronts) instances, chosen for speed.  THIS kernel serves everything the table does not: the horizons without a compiled
+// instance (M = 11, 12: the table holds one for every (M <= 10, dim, end stop)), neighbour counts beyond a compiled instance's
+// capacity, and the rescue pass of every shape.  Same model, same
 // interior-point iteration, same stopping rules and statuses as lscqp_kernel.hpp (its header comment and DESIGN.md section 2 describe
 // them; the numbered steps below cite it) -- organised for generality instead of issue rate:
 //   * one workgroup of 256 threads per QP, M / dim / end stop / n_obs are run-time values;

@@ -353,7 +353,10 @@ def family_c(hdr, rows, sfc, n_obs, M, dim, seed, reps=2):
     return out
 
 
-SHAPES = {"c1": (5, 3, 8), "c0": (10, 2, 8), "generic": (9, 3, 8)}  # (M, dim, n_obs); M = 9 in 3-D has no compiled instance
+# (M, dim, n_obs).  "generic": the shape kept its name from round 3, when M = 9 in 3-D had no compiled instance; it has one since (14
+# neighbours), so only the forced path of tests/test_infeasible_verdicts.py runs it on the run-time-shaped kernel.  "m12": no compiled
+# instance at all -- every path that reaches an interior-point kernel ends in the run-time-shaped one.
+SHAPES = {"c1": (5, 3, 8), "c0": (10, 2, 8), "generic": (9, 3, 8), "m12": (12, 3, 8)}
 
 
 class Group:

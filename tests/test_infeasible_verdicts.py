@@ -1,12 +1,15 @@
 """The solver's INFEASIBLE verdicts against the exact feasibility referee (tests/feasibility.py), on every path that can give one.
 
 Families A (near-antiparallel pairs), B (graded slabs) and C (empty and zero-width corridor intervals) on the c1 shape (M = 5, 3-D), the c0
-shape (M = 10, 2-D) and M = 9 in 3-D, which has no compiled instance (the run-time-shaped kernel answers).  Paths:
+shape (M = 10, 2-D), M = 9 in 3-D, and M = 12 in 3-D, which has no compiled instance: there paths a, b, c and e end in the run-time-shaped
+kernel (csrc/lscqp_generic.hip), whose early-stop rules are an implementation of their own.  Paths:
   a  the default small batch through the device entry (at most one instance per CU: the fused launch);
   b  the same instances replicated past the CU count (two launches, the large-batch phase budget);
   c  knob das_fused = 0;
   d  LSCQP_ACTIVE_SET_ONLY (the phase alone: a verdict or a hand-over);
-  e  knob active_set_off = 1 through the device entry (the interior-point kernel alone).
+  e  knob active_set_off = 1 through the device entry (the interior-point kernel alone);
+  g  knobs force_generic = 1 and active_set_off = 1 through the device entry: the run-time-shaped kernel alone, its own verdict on every shape
+     (held to rules 1 - 4 like path e).
 Rules: 1. FEASIBLE is never INFEASIBLE.  2. INFEASIBLE is never OPTIMAL.  3. t_hi <= -1e-4 is OPTIMAL on every path but d, at polish_primal's
 point to 1e-8 m (the phase's answer) or 1e-6 m (the interior-point kernel's).  4. An empty corridor interval is INFEASIBLE with its overlap
 (bmin - bmax) in res_primal.  5. Outside GREY, the phase on (a) and off (e) agree on OPTIMAL or not -- except that a FEASIBLE instance
@@ -19,7 +22,7 @@ import pytest
 from tests import feasibility as F
 from tests import helpers as H
 
-PATHS = ("a", "b", "c", "d", "e")
+PATHS = ("a", "b", "c", "d", "e", "g")
 
 
 def _device(torch, sol, arrays, n_obs):
@@ -39,6 +42,14 @@ def api_info():
     from lsc_dr_planner_amd import api
 
     return api.INFO_DTYPE
+
+
+def _assert_run_time_shaped(api, sol, n, n_obs):
+    """The handle's next launch of n instances goes to the run-time-shaped kernel: lscqp_instance_work selects through the launch's own
+    find_instance() call and switches, and answers ERR_UNSUPPORTED exactly when that finds no compiled instance."""
+    with pytest.raises(api.LscqpError) as e:
+        sol.instance_work(n, n_obs)
+    assert e.value.code == api.ERR_UNSUPPORTED and "run-time-shaped kernel carries no instruction counts" in str(e.value), e.value
 
 
 def _run_paths(api, torch, g, ncu):
@@ -65,6 +76,13 @@ def _run_paths(api, torch, g, ncu):
         sol.set_knob("active_set_off", 1)
         out["e"].append(_device(torch, sol, arrays, g.n_obs))
         sol.set_knob("active_set_off", 0)
+        gen = api.Solver(g.desc(api))
+        if g.M > 10:  # no compiled instance: what paths a, b, c and e ran behind the phase was the run-time-shaped kernel already
+            _assert_run_time_shaped(api, gen, n, g.n_obs)
+        gen.set_knob("force_generic", 1)
+        gen.set_knob("active_set_off", 1)
+        _assert_run_time_shaped(api, gen, n, g.n_obs)
+        out["g"].append(_device(torch, gen, arrays, g.n_obs))
     return {p: {k: np.concatenate([r[k] for r in out[p]]) for k in ("x", "status", "info")} for p in PATHS}
 
 
@@ -104,7 +122,7 @@ def test_infeasible_verdicts_against_the_referee(api, oracle, torch_cuda, shape)
             if i.verdict.t_hi <= -1e-4:
                 ag, lsc, sfc = F.oracle_inputs(oracle, i.hdr, i.rows, i.sfc)
                 xr, ok = H.polish_primal(oracle, cls, ag, lsc, sfc)
-                for p in ("a", "b", "c", "e"):
+                for p in ("a", "b", "c", "e", "g"):
                     if st[p] != api.STATUS_OPTIMAL:
                         fail(3, p)
                         continue
