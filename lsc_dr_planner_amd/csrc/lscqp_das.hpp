@@ -82,9 +82,9 @@ struct Layout {
         s.o_u = take(kmax + 1), s.o_r = take(kmax + 4), s.o_arhs = take(kmax + 1);
         s.o_acoef = take(3 * (kmax + 1));
         s.o_aint = take(2 * (kmax + 1) + 2);  // ints: per active row {id, entry0, entry1, entry2} (+ the candidate); entry = axis << 16 | control point
-        s.o_red = take(2 * 24);               // cross-wavefront reductions, double buffered
-        s.o_ctl = take(8);
-        s.o_wb = take(8);  // world box of the class (a kernel argument indexed with a run-time axis would be fetched through vector memory)
+        s.o_red = take(2 * 24);               // cross-wavefront reductions, double buffered; [20, 24): the wavefronts' empty-interval ballots, [44]: w_c
+        s.o_ctl = take(8);                    // the step's decision; [4]: w_t
+        s.o_wb = take(8);  // world box of the class, then dt and q2s (a kernel argument indexed with a run-time axis would be fetched through vector memory)
         s.o_dq = take(36);  // the objective's coefficient-rounding term (36 doubles as a kernel argument live in 72 scalar registers the kernel does not have)
         s.o_C = take(cacheC ? s.P * s.P : 0);
         s.n_stage = stage_rows;  // LSC rows of the instance kept in LDS after the first pass (SoA nx | ny | nz | b), 0: re-read from L2
@@ -200,6 +200,30 @@ __device__ unsigned long long LSCQP_DAS_CYCLES[16];
     } while (0)
 #endif
 
+// The kernel-argument block of a kernel that holds the phase with LSCQP_DAS_PROLOGUE 1 (the fused forms): every pointer and class scalar the phase reads before its first pass, asked
+// for at kernel entry and waited for ONCE -- in front of the exit test, the order indirection and every branch.  Left where they are used,
+// the compiler sinks these reads behind the tests around their uses (a scalar load and a wait of its own per use: seven dependent waits
+// up to the first barrier, the world box through a tree of divergent branches), and it re-reads a class scalar from the kernel-argument
+// segment rather than keep it in a register -- with a wait on the counter the LDS reads share, in the middle of those reads.  The empty
+// statement takes the pointers as scalar-register inputs (they must be there at this point; they stay what they are to the optimiser)
+// and hands the class scalars, the row offsets' pointer and the boxes' back as values of unknown origin: nothing behind it can be read
+// again from the segment.
+// (a pointer of unknown origin is a generic one, and a load through it waits on both counters: these two say "global memory" themselves)
+#define LSCQP_DAS_GLOBAL __attribute__((address_space(1)))
+#define LSCQP_DAS_KERNARGS()                                                                                                            \
+    double ka_wb0 = cls.world_min[0], ka_wb1 = cls.world_min[1], ka_wb2 = cls.world_min[2];                                            \
+    double ka_wb3 = cls.world_max[0], ka_wb4 = cls.world_max[1], ka_wb5 = cls.world_max[2];                                            \
+    double ka_dt = cls.dt, ka_q2s = cls.q2s, ka_w_t = cls.w_t, ka_w_c = cls.w_c, ka_comm_range = cls.comm_range;                               \
+    int ka_use_sfc = cls.use_sfc, ka_rsfc = cls.rsfc;                                                                                  \
+    const int32_t* const ka_order = cls.order;                                                                                        \
+    LSCQP_DAS_GLOBAL const uint64_t* ka_roffs = (LSCQP_DAS_GLOBAL const uint64_t*)row_offsets;                                         \
+    LSCQP_DAS_GLOBAL const double* ka_sfc = (LSCQP_DAS_GLOBAL const double*)sfc;                                                       \
+    asm volatile(""                                                                                                                    \
+                 : "+s"(ka_wb0), "+s"(ka_wb1), "+s"(ka_wb2), "+s"(ka_wb3), "+s"(ka_wb4), "+s"(ka_wb5), "+s"(ka_dt), "+s"(ka_q2s),      \
+                   "+s"(ka_w_t), "+s"(ka_w_c), "+s"(ka_comm_range), "+s"(ka_use_sfc), "+s"(ka_rsfc), "+s"(ka_roffs), "+s"(ka_sfc)                   \
+                 : "s"(ka_order), "s"(tab), "s"(hdr), "s"(rows), "s"(n), "s"(cap), "s"(kmax), "s"(max_steps),        \
+                   "s"(cacheC), "s"(stage_rows), "s"(x_init), "s"(x_out), "s"(obj_out), "s"(status_out), "s"(info_out))
+
 // One row of the model as (<= 3 entries, right-hand side): a'c >= h.  An entry names (axis, control point) as axis << 16 | cp.
 struct Row {
     int ent[3];
@@ -264,9 +288,13 @@ __global__ __launch_bounds__(64 * NW, (SCREEN ? LSCQP_DAS_WPES : NW == 1 ? LSCQP
     const int64_t k0 = blockIdx.x;
     if (k0 >= n) return;
     const int64_t q = cls.order ? (int64_t)cls.order[k0] : k0;
+    // (the prologue as it was before the kernel-argument block: with the block every one-wavefront form moved in vector registers, and three
+    // forms spilled more scalar registers -- NOTES section 23; these forms run the batches that fill the chip, and their code is unchanged)
+#define LSCQP_DAS_PROLOGUE 0
 #define LSCQP_DAS_END(verdict_) return
 #include "lscqp_das_body.inc"
 #undef LSCQP_DAS_END
+#undef LSCQP_DAS_PROLOGUE
 }
 
 }  // namespace lscqp_das

@@ -3,6 +3,11 @@
 //   NW, F32, SCREEN, PEEL, T = 64 * NW, kU, kMaxNL (constants; kMaxNL bounds an instance's LSC rows); cls, M, dim, es, cap, kmax, max_steps,
 //   cacheC, stage_rows, behind, tab, q, hdr, rows, row_offsets, sfc, x_init, x_out, obj_out, status_out, info_out; smem (the dynamic LDS,
 //   lscqp_das_lds_bytes(M, dim, kmax, cacheC, stage_rows), or the carve of LSCQP_DAS_LAYOUT);
+//   LSCQP_DAS_PROLOGUE: 1 -- the prologue (everything above DAS_T(1)) scheduled around the kernel-argument block of LSCQP_DAS_KERNARGS
+//   (lscqp_das.hpp: ka_dt, ka_q2s, ka_w_t, ka_w_c, ka_comm_range, ka_use_sfc, ka_rsfc, ka_wb0 .. 5, ka_roffs, ka_sfc), which the kernel has placed
+//   in front of its exit test: the phase then reads no field of cls and neither row_offsets nor sfc by name (the fused forms);
+//   0 -- the prologue as it was, every value read where it is used (das_kernel).  The two differ in WHEN a value is asked for and waited
+//   for, in no expression that rounds: every form of the phase returns the same bytes (tests/test_das_prologue.py);
 //   LSCQP_DAS_END(verdict): leaves the phase with a DasVerdict, taken by the whole workgroup at once;
 //   LSCQP_DAS_LAYOUT (optional): the LDS carve as a constant expression, with room for at least kmax active rows, the class's table and
 //   stage_rows staged rows; without it the carve is made at run time from kmax, cacheC and stage_rows.  kmax, max_steps, cacheC and
@@ -10,6 +15,11 @@
 // (Text, not a function: the kernel's own code then is exactly what it was as one function -- a __forceinline__ device function holding this
 // body was simplified before it was inlined, through a generic LDS pointer, and das_kernel came out 2 VGPRs and some SGPR spills different
 // and the 512-QP batches 2 % slower, measured.)
+#if LSCQP_DAS_PROLOGUE
+#define DAS_CLS(f) ka_##f  // a scalar of the class: the kernel-argument block's register
+#else
+#define DAS_CLS(f) cls.f  // a scalar of the class: the kernel argument, read where it is used
+#endif
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 #ifdef LSCQP_DAS_LAYOUT
     constexpr Layout L = LSCQP_DAS_LAYOUT;
@@ -51,6 +61,79 @@
         if ((behind & 1) && st_early == LSCQP_STATUS_OPTIMAL) LSCQP_DAS_END(kDasSolved);
         if ((behind & 2) && st_early == LSCQP_STATUS_INFEASIBLE) LSCQP_DAS_END(kDasInfeasible);
     }
+#if LSCQP_DAS_PROLOGUE
+    // ---- ONE wave of requests: the instance's row offset and obstacle count, the class's two-sided rows, the header, the corridor
+    // boxes and the objective's rounding terms -- straight-line code, every address clamped into memory the instance owns, no test around
+    // any load (a branch around a load makes the compiler wait for every load right behind it: the loads have to be in flight TOGETHER).
+    // Vector loads return in the order they were asked for, so the LSC rows are asked for LAST, as soon as offset and count are there: the
+    // wait for the header then leaves them in flight, across the barrier and under everything up to the first pass.
+    // (offset and count are per-thread vector loads of one address, not scalar loads: they stand FIRST in the machine code, and the wait
+    // in front of the rows' addresses is for these two alone -- the other four stay in flight.  n_obs, in_cap, nL and roff therefore live in
+    // vector registers and are divergent to the compiler, uniform in fact: NOTES section 23.)
+    const lscqp_header* const hq = hdr + q;
+    const bool use_sfc = ka_use_sfc != 0;  // (uniform)
+    constexpr int kNS = (72 + T - 1) / T;  // corridor-box words per thread (6 M <= 72)
+    LSCQP_DAS_GLOBAL const double* const hsrc = (LSCQP_DAS_GLOBAL const double*)hq;
+    LSCQP_DAS_GLOBAL const double* const ssrc = use_sfc ? ka_sfc + q * 6 * M : hsrc;  // (no boxes: the header again, unused)
+    double hw = hsrc[tid & 31];
+    double sw[kNS];
+#pragma unroll
+    for (int i = 0; i < kNS; i++) sw[i] = ssrc[(use_sfc && tid + i * T < 6 * M) ? tid + i * T : 0];
+    const double* const tab_end = tab + (size_t)M * table_stride(M);  // (behind the tables: lscqp_api.hip, das_refresh)
+    double dqw = tab_end[min(tid, 35)];
+    // the class's two-sided rows (lscqp_das_build_pairs, behind the tables and the 36 rounding terms): the first four of this thread
+    constexpr int kPB = 4;
+    const int2* const pairs_g = reinterpret_cast<const int2*>(tab_end + 36);
+    int2 pwr[kPB];
+#pragma unroll
+    for (int u = 0; u < kPB; u++) pwr[u] = pairs_g[min(tid + u * T, NPAIR - 1)];
+    // (offset and count: the compiler moves these two to the head of the wave)
+    const uint64_t roff_raw = *(ka_roffs ? ka_roffs + q : (LSCQP_DAS_GLOBAL const uint64_t*)hq);  // (no offsets: a word of the header, unused)
+    const int n_obs = hq->n_obs;
+    // the first LSC rows of this thread, raw.  An instance beyond the launch's capacity is handed over below and NO row of it is asked for;
+    // neither is one where the instance has none: those loads read the head of the instance's own header and their values are dropped.
+    __builtin_amdgcn_sched_barrier(0);  // (everything above is asked for before the first wait below)
+    const uint64_t roff = ka_roffs ? roff_raw : 0;
+    const bool in_cap = !(n_obs > cap || n_obs < 0);
+    const int nL = in_cap ? n_obs * P : 0;
+    auto fetch_row = [&](int j, double& x, double& y, double& z, double& w) {  // raw row j of this instance
+        if constexpr (F32) {
+            const float4 f = reinterpret_cast<const float4*>(rows)[roff + (uint64_t)j];
+            x = f.x, y = f.y, z = f.z, w = f.w;
+        } else {
+            const double4 d = *reinterpret_cast<const double4*>(&rows[roff + (uint64_t)j]);
+            x = d.x, y = d.y, z = d.z, w = d.w;
+        }
+    };
+    double px[kU], py[kU], pz[kU], pw[kU];
+    {
+        using RowT = std::conditional_t<F32, float4, double4>;
+        const RowT* const rbase = nL > 0 ? reinterpret_cast<const RowT*>(rows) + roff : reinterpret_cast<const RowT*>(hq);
+#pragma unroll
+        for (int u = 0; u < kU; u++) {
+            const int j = tid + u * T;
+            const RowT d = rbase[j < nL ? j : 0];
+            px[u] = nL > 0 ? (double)d.x : 0.0, py[u] = nL > 0 ? (double)d.y : 0.0, pz[u] = nL > 0 ? (double)d.z : 0.0, pw[u] = nL > 0 ? (double)d.w : -1.0;
+        }
+    }
+    // ONE wait for the wave, with the rows left in flight (the values are taken here: left alone, the compiler moves a load into the test
+    // around its store, with a wait for everything behind it)
+    asm volatile("" : "+v"(hw), "+v"(dqw));
+#pragma unroll
+    for (int i = 0; i < kNS; i++) asm volatile("" : "+v"(sw[i]));
+    if (tid < 32) H_[tid] = hw;
+#pragma unroll
+    for (int i = 0; i < kNS; i++)
+        if (use_sfc && tid + i * T < 6 * M) sfc_[tid + i * T] = sw[i];
+    if (tid < 36) dq_[tid] = dqw;
+    if (tid == 0) {  // (registers of the kernel-argument block)
+        wb_[0] = ka_wb0, wb_[1] = ka_wb1, wb_[2] = ka_wb2, wb_[3] = ka_wb3, wb_[4] = ka_wb4, wb_[5] = ka_wb5;
+        // four class scalars for the verification, which reads them from here instead of holding eight scalar registers across the loop of
+        // steps (or reading them again from the kernel-argument segment, with a wait the LDS reads around it share): slots nothing else uses
+        wb_[6] = ka_dt, wb_[7] = ka_q2s, ctl_[4] = ka_w_t, red_[44] = ka_w_c;
+    }
+    LSCQP_DAS_BARRIER();
+#else
     // ---- header, corridor boxes (and the instance's row offset: one memory round trip for all three) -------------------------------
     const uint64_t roff = row_offsets ? row_offsets[q] : 0;
     // the class's two-sided rows (lscqp_das_build_pairs, behind the tables and the 36 rounding terms): the first four of this thread are asked
@@ -71,10 +154,13 @@
         }
     }
     __syncthreads();
+#endif
     DAS_T(0);  // header, boxes, row offset
     const lscqp_header* Hd = reinterpret_cast<const lscqp_header*>(H_);
     const lscqp_box* sfcl = reinterpret_cast<const lscqp_box*>(sfc_);
+#if !LSCQP_DAS_PROLOGUE
     const int n_obs = Hd->n_obs;
+#endif
     // Handing an instance over: the interior-point kernel behind this phase solves whatever is not OPTIMAL (cls.repair == 3 there).
     // (why: LSCQP_DAS_WHY_* of include/lscqp.h, left in lscqp_info.res_dual of an instance nobody solves afterwards -- LSCQP_ACTIVE_SET_ONLY,
     // tests and tools/loaded_probe.py; the pass that solves the instance overwrites the record)
@@ -111,11 +197,16 @@
             }
         }
     };
-    if (n_obs > cap || n_obs < 0) {  // the kernel instance behind this phase refuses it (LSCQP_STATUS_CAPACITY): its verdict, not ours
+#if LSCQP_DAS_PROLOGUE
+    if (!in_cap)
+#else
+    if (n_obs > cap || n_obs < 0)
+#endif
+    {  // the kernel instance behind this phase refuses it (LSCQP_STATUS_CAPACITY): its verdict, not ours
         hand_over(0, LSCQP_DAS_WHY_CAPACITY);
         LSCQP_DAS_END(kDasHandedOver);
     }
-    const double dt = cls.dt;
+    const double dt = DAS_CLS(dt);
     const double org0 = Hd->p0[0], org1 = Hd->p0[1], org2 = Hd->p0[2];
     const double* const org = Hd->p0;  // (LDS: indexed with a run-time axis; a register array would be materialised in scratch memory)
     int ts = Hd->terminal_segments;
@@ -125,17 +216,30 @@
         if (ts < 1) ts = 1;
     }
     if (ts > M) ts = M;
-    const double q2s = cls.q2s, wt2 = 2.0 * cls.w_t;
+    const double q2s = DAS_CLS(q2s), wt2 = 2.0 * DAS_CLS(w_t);
     const double* const tb = tab + (size_t)(ts - 1) * table_stride(M);
     const double* const U1 = tb, * const U2 = tb + P, * const G1 = tb + 2 * P, * const Cg = tb + 3 * P;
-    const bool comm_on = cls.comm_range > 0;
-    const double rho_pair = 0.5 * cls.comm_range - Hd->radius;  // :484
-    const double rho_wp = 0.5 * cls.comm_range - 1e-5;          // :495
+    const bool comm_on = DAS_CLS(comm_range) > 0;
+    const double rho_pair = 0.5 * DAS_CLS(comm_range) - Hd->radius;  // :484
+    const double rho_wp = 0.5 * DAS_CLS(comm_range) - 1e-5;          // :495
+#if !LSCQP_DAS_PROLOGUE
     const int nL = n_obs * P;
+#endif
     const float iP = 1.0f / (float)P;
     const bool staged = stage_rows > 0 && nL <= stage_rows;  // (uniform)
     bool rows_in_lds = false;                                // set by the first pass
 
+#if LSCQP_DAS_PROLOGUE
+    // ---- behind the rows, and under their trip: the table vectors of this thread's control points (they need ts), clamped, no test ----
+    constexpr int NE = 4;  // control-point entries per thread the prologue handles in registers (NX <= 4 T for every shape: 216 at M = 12 in 3-D)
+    double tu1[NE], tu2[NE], tg1[NE];
+#pragma unroll
+    for (int i = 0; i < NE; i++) {
+        const int e = tid + i * T < NX ? tid + i * T : 0;
+        const int cp = e - P * fdiv(e, iP);
+        tu1[i] = U1[cp], tu2[i] = U2[cp], tg1[i] = G1[cp];
+    }
+#else
     // ---- memory first: the table vectors of this thread's control points and its first LSC rows are requested before anything is computed --
     // (the row format is a template parameter and the index is clamped instead of guarded: a branch around a load makes the compiler wait
     // for every load right behind it -- the loads of a thread have to be in flight TOGETHER)
@@ -168,14 +272,21 @@
             fetch_row(j < nL ? j : 0, px[u], py[u], pz[u], pw[u]);
         }
     }
+#endif
 
     // The small-batch form asks for the class's table NOW as well (an instance with a step would otherwise wait a memory round trip for it at
     // its first step -- and in a batch of 64 that one instance is the launch's time); a quiet instance never waits for these loads.
     constexpr int kCPre = (NW == 4 && !PEEL && !SCREEN) ? 6 : 0;  // table entries per thread held in registers (6 x 256 >= 36 M^2 up to M = 6)
     double cpre[kCPre > 0 ? kCPre : 1];
+#if LSCQP_DAS_PROLOGUE
+    const bool c_fits = kCPre > 0 && P * P <= kCPre * T;  // (uniform; a constant of the shape: the loads then stand in straight-line code)
+    const bool c_prefetched = c_fits && cacheC;           // (uniform; the fused forms always keep the table)
+#else
     const bool c_prefetched = kCPre > 0 && cacheC && P * P <= kCPre * T;  // (uniform)
+    const bool c_fits = c_prefetched;
+#endif
     if constexpr (kCPre > 0) {
-        if (c_prefetched) {
+        if (c_fits) {
 #pragma unroll
             for (int i = 0; i < kCPre; i++) {
                 const int e = tid + i * T;
@@ -208,11 +319,11 @@
             const double ok_ = org[k], wlo = wb_[k], whi = wb_[3 + k], wpk = Hd->next_waypoint[k] - ok_;
             const double hv = Hd->vmax[k] * hv_c, ha = Hd->amax[k] * ha_c;
             double lo = wlo - ok_, hi = whi - ok_;  // :252-253,260-265
-            if (cls.rsfc && rs) {                  // :255-258
+            if (DAS_CLS(rsfc) && rs) {          // :255-258
                 lo = -100.0 - ok_;
                 hi = 100.0 - ok_;
             }
-            if (cls.use_sfc) {  // (uniform) :372-397
+            if (DAS_CLS(use_sfc)) {  // (uniform) :372-397
                 lo = fmax(lo, sfcl[m].bmin[k] - ok_);
                 hi = fmin(hi, sfcl[m].bmax[k] - ok_);
             }
@@ -245,11 +356,32 @@
     }
     if (dim == 2)
         for (int e = tid; e < P; e += T) c_[2 * P + e] = 0.0;
+#if LSCQP_DAS_PROLOGUE
+    // the workgroup's verdict on `empty` with ONE barrier: every wavefront leaves its own ballot in a slot of red_ no reduction uses
+    // ([20, 24) of the first half), every thread reads all of them behind the barrier that also publishes c_ and the two-sided rows
+    const bool empty_w = __ballot(empty) != 0;  // (wave-uniform)
+    if constexpr (NW > 1) {
+        if (lane == 0) red_[20 + wv] = empty_w ? 1.0 : 0.0;
+    }
+    LSCQP_DAS_BARRIER();
+    bool empty_g = empty_w;
+    if constexpr (NW > 1) {
+        empty_g = false;
+#pragma unroll
+        for (int w = 0; w < NW; w++) empty_g = empty_g || red_[20 + w] != 0.0;
+    }
+#else
     if (tid == 0) ctl_[4] = 0.0;
     LSCQP_DAS_BARRIER();
     if (empty) ctl_[4] = 1.0;  // (benign race: every writer stores 1)
     LSCQP_DAS_BARRIER();
-    if (ctl_[4] != 0.0) {  // an empty interval (lo > hi on one control point: exact); its violation is the largest overlap lo - hi
+#endif
+#if LSCQP_DAS_PROLOGUE
+    if (empty_g)
+#else
+    if (ctl_[4] != 0.0)
+#endif
+    {  // an empty interval (lo > hi on one control point: exact); its violation is the largest overlap lo - hi
         double ov = 0.0;
         if (wv == 0) {  // (the two-sided rows of the other families have lo = -hs <= hi = hs: they never raise it)
             for (int r = lane; r < NPAIR; r += 64)
@@ -529,6 +661,10 @@
     // as cplex.getObjValue() reports it (as lscqp_kernel.hpp).  Every z thread evaluates the <= 4 control-point rows of Hx it needs itself.
     const int NZA = 3 * (M - 1) + (es ? 1 : 3);
     auto finish_local = [&](int k, double& rd, double& gs, double& part) {
+#if LSCQP_DAS_PROLOGUE
+        // (the class's, left in LDS by the prologue; the two ka_ names stand in front of the block's registers for DAS_CLS below)
+        const double dt = wb_[6], q2s = wb_[7], ka_w_t = ctl_[4], ka_w_c = red_[44], wt2 = 2.0 * ka_w_t;
+#endif
         if (k > 0) {  // A'u, per control point
             for (int e = tid; e < NX; e += T) lam_[e] = 0.0;
             LSCQP_DAS_BARRIER();
@@ -605,9 +741,9 @@
                 r += dr[0] * s0, r += dr[1] * s1, r += dr[2] * s2, r += dr[3] * s3, r += dr[4] * s4, r += dr[5] * s5;
                 corr += r * (cc[i] + ok_);
             }
-            pp += cls.w_c * corr;
+            pp += DAS_CLS(w_c) * corr;
             const double dgoal = cc[5] - (Hd->goal[kx] - ok_);
-            pp += (m >= M - ts) ? cls.w_t * dgoal * dgoal : 0.0;
+            pp += (m >= M - ts) ? DAS_CLS(w_t) * dgoal * dgoal : 0.0;
             part += pp;
         }
     };
@@ -938,3 +1074,4 @@
     DAS_T(7);  // epilogue
     DAS_T_FLUSH();
     LSCQP_DAS_END(kDasSolved);
+#undef DAS_CLS

@@ -28,6 +28,14 @@ namespace lscqp_das {
 constexpr bool carve_fits(int M, int dim, int kmax, int stage_rows) {
     return sizeof(double) * (size_t)Layout::make(M, dim, kmax, 1, stage_rows).total <= lscqp::kMaxLdsBytes;
 }
+// Which prologue the phase runs here (lscqp_das_body.inc, LSCQP_DAS_PROLOGUE): the rescheduled one on the kernel-argument block, except in
+// the M = 10, 3-D instance -- there the block costs scalar registers (306 SGPR spills against 292) and the form keeps the prologue it had.
+// (this unit is compiled once per instance: the shape is the preprocessor's as well as the template's)
+#if LSCQP_M == 10 && LSCQP_DIM == 3
+#define LSCQP_FUSED_PROLOGUE 0
+#else
+#define LSCQP_FUSED_PROLOGUE 1
+#endif
 template <int M, int DIM, bool ES, int NSLOT, int W>
 struct FusedCarve {
     static constexpr int kStage = lscqp::Cfg<M, DIM, ES, NSLOT, W, (int)sizeof(double)>::MAX_OBS * 6 * M;  // LSC rows of a full instance
@@ -46,9 +54,16 @@ __global__ __launch_bounds__(256, 1) void das_pdip_kernel(DevClass cls, int cap,
                                                           lscqp_info* __restrict__ info_out) {
     static_assert(W >= 1 && W <= 4, "the interior-point instance runs on the first W of the workgroup's four wavefronts");
     extern __shared__ __attribute__((aligned(16))) double smem[];
+#if LSCQP_FUSED_PROLOGUE
+    LSCQP_DAS_KERNARGS();  // (one block of kernel-argument reads, one wait: lscqp_das.hpp)
+    const int64_t k0 = blockIdx.x;
+    if (k0 >= n) return;
+    const int64_t q = ka_order ? (int64_t)ka_order[k0] : k0;
+#else
     const int64_t k0 = blockIdx.x;
     if (k0 >= n) return;
     const int64_t q = cls.order ? (int64_t)cls.order[k0] : k0;
+#endif
     int verdict = kDasSolved;
     {  // the phase: das_kernel<4, false, false, false>'s body (lscqp_das_body.inc) with the class's shape as constants and nothing in front
         constexpr int NW = 4, T = 64 * NW, kU = 4;
@@ -62,7 +77,9 @@ __global__ __launch_bounds__(256, 1) void das_pdip_kernel(DevClass cls, int cap,
         goto phase_done;          \
     } while (0)
 #define LSCQP_DAS_LAYOUT Layout::make(M, DIM, FC::KMAX, 1, FC::kStage)
+#define LSCQP_DAS_PROLOGUE LSCQP_FUSED_PROLOGUE
 #include "lscqp_das_body.inc"
+#undef LSCQP_DAS_PROLOGUE
 #undef LSCQP_DAS_LAYOUT
 #undef LSCQP_DAS_END
     }
