@@ -291,9 +291,11 @@ __global__ __launch_bounds__(64 * NW, (SCREEN ? LSCQP_DAS_WPES : NW == 1 ? LSCQP
     // (the prologue as it was before the kernel-argument block: with the block every one-wavefront form moved in vector registers, and three
     // forms spilled more scalar registers -- NOTES section 23; these forms run the batches that fill the chip, and their code is unchanged)
 #define LSCQP_DAS_PROLOGUE 0
+#define LSCQP_DAS_STEP_PATH 0  // (likewise the stepping instance's path: a quiet instance of a full chip must not pay for step setup)
 #define LSCQP_DAS_END(verdict_) return
 #include "lscqp_das_body.inc"
 #undef LSCQP_DAS_END
+#undef LSCQP_DAS_STEP_PATH
 #undef LSCQP_DAS_PROLOGUE
 }
 

@@ -8,6 +8,12 @@
 //   in front of its exit test: the phase then reads no field of cls and neither row_offsets nor sfc by name (the fused forms);
 //   0 -- the prologue as it was, every value read where it is used (das_kernel).  The two differ in WHEN a value is asked for and waited
 //   for, in no expression that rounds: every form of the phase returns the same bytes (tests/test_das_prologue.py);
+//   LSCQP_DAS_STEP_PATH: a set of bits, one per change to the path of an instance that takes steps (0: the text as it was -- das_kernel, whose
+//   forms serve the batches that fill the chip, where a quiet instance must not pay for step setup).  1: the later passes read the
+//   staged rows with clamped, untested loads, all in flight at once.  2: what the first step needs and only the header decides is done
+//   ahead of it -- the factor zeroed in the prologue, the class's table left in LDS by the first pass (needs LSCQP_DAS_LAYOUT and more than
+//   one wavefront).  4: a joining row's descriptors are stored from registers, not copied from the candidate's slot.  As the prologues,
+//   the settings differ in when and by which thread a value is moved, in no expression that rounds (tests/test_das_step_path.py);
 //   LSCQP_DAS_END(verdict): leaves the phase with a DasVerdict, taken by the whole workgroup at once;
 //   LSCQP_DAS_LAYOUT (optional): the LDS carve as a constant expression, with room for at least kmax active rows, the class's table and
 //   stage_rows staged rows; without it the carve is made at run time from kmax, cacheC and stage_rows.  kmax, max_steps, cacheC and
@@ -294,6 +300,22 @@
             }
         }
     }
+#if LSCQP_DAS_STEP_PATH & 2
+    // What the first step needs and only the header decides, done under the rows' trip instead of on the stepping instance's path: the
+    // factor zeroed by every thread (below, behind c_u; it was wavefront 0's, 17 stores per lane, in front of the first candidate), and --
+    // where the table fits the registers asked for above -- the table left in LDS by the first pass (in front of that pass's barrier,
+    // which publishes it) whatever cacheC says: the compile-time carve has the room, and the values are the table's own either way.
+    // A quiet instance now waits for the table's loads; in a batch of at most one instance per CU its time is not the launch's.
+#ifndef LSCQP_DAS_LAYOUT
+#error "LSCQP_DAS_STEP_PATH & 2 needs the compile-time carve"
+#endif
+    static_assert(NW > 1, "the first pass's barrier publishes the table");
+    constexpr bool kTableEarly = kCPre > 0 && L.P * L.P <= kCPre * T;
+    // (only the rescheduled prologue asks for the table whatever cacheC says: the other one would leave cpre[] unset at cacheC == 0)
+    static_assert(!kTableEarly || LSCQP_DAS_PROLOGUE, "the table is stored from cpre[]: it needs the prologue that always loads it");
+#else
+    constexpr bool kTableEarly = false;
+#endif
 
     // ---- the two-sided rows, one table for all four families (ids nL + 2 r + side; side 0: stencil - lo >= 0, side 1: hi - stencil >= 0) ----
     //   r in [0, NX)                    interval of one control point: world box, corridor, communication rows on c[m][5]  (:252-265, 372-397, 482-497)
@@ -356,6 +378,12 @@
     }
     if (dim == 2)
         for (int e = tid; e < P; e += T) c_[2 * P + e] = 0.0;
+#if LSCQP_DAS_STEP_PATH & 2
+    {  // the factor, zeroed behind the section's own LDS traffic, two entries a store (k (k + 1) is even, the carve aligns to 16 bytes)
+        double2* const J2 = reinterpret_cast<double2*>(Jm_);
+        for (int e = tid; e < kcap * LDL / 2; e += T) J2[e] = make_double2(0.0, 0.0);
+    }
+#endif
 #if LSCQP_DAS_PROLOGUE
     // the workgroup's verdict on `empty` with ONE barrier: every wavefront leaves its own ballot in a slot of red_ no reduction uses
     // ([20, 24) of the first half), every thread reads all of them behind the barrier that also publishes c_ and the two-sided rows
@@ -517,6 +545,25 @@
                 eval(j0, rx, ry, rz, rb);
             }
         } else if (rows_in_lds) {
+#if LSCQP_DAS_STEP_PATH & 1
+            // every staged row of this thread asked for at once, the index clamped into the staged arrays and no test around a load; a slot
+            // past the end becomes the harmless row by selects on the loaded values (a test around a load serialises the loads: each slot
+            // then is an LDS round trip of its own, and the reads of c_ in eval come behind the last of them)
+            for (int j0 = tid; j0 < nL; j0 += kU * T) {
+                double lx[kU], ly[kU], lz[kU], lb[kU];
+#pragma unroll
+                for (int u = 0; u < kU; u++) {
+                    const int j = j0 + u * T, jc = j < nL ? j : 0;
+                    lx[u] = Sx_[jc], ly[u] = Sy_[jc], lz[u] = Sz_[jc], lb[u] = Sb_[jc];
+                }
+#pragma unroll
+                for (int u = 0; u < kU; u++) {
+                    const bool in = j0 + u * T < nL;
+                    rx[u] = in ? lx[u] : 0.0, ry[u] = in ? ly[u] : 0.0, rz[u] = in ? lz[u] : 0.0, rb[u] = in ? lb[u] : -1.0;
+                }
+                eval(j0, rx, ry, rz, rb);
+            }
+#else
             for (int j0 = tid; j0 < nL; j0 += kU * T) {
 #pragma unroll
                 for (int u = 0; u < kU; u++) {
@@ -526,6 +573,7 @@
                 }
                 eval(j0, rx, ry, rz, rb);
             }
+#endif
         } else {
             for (int j0 = tid; j0 < nL; j0 += kU * T) {
                 double x[kU], y[kU], z[kU], w[kU];
@@ -565,6 +613,17 @@
         double bv;
         int bi;
         pass_local(bv, bi);
+#if LSCQP_DAS_STEP_PATH & 2
+        if constexpr (kTableEarly) {
+            if (was_first) {  // the class's table, from the registers the prologue asked for; the barrier below publishes it
+#pragma unroll
+                for (int i = 0; i < kCPre; i++) {
+                    const int e = tid + i * T;
+                    if (e < P * P) Cc_[e] = cpre[i];
+                }
+            }
+        }
+#endif
         wave_argmin(bv, bi);
         if constexpr (NW > 1) {
             double* const rb_ = red_ + 24 * par;
@@ -583,7 +642,7 @@
     };
 
     // ---- the small factor: S = A'C A (k x k, SPD), S = Lm Lm', rows owned by the lanes of wavefront 0 -------------------------------------
-    const double* Cm = Cg;  // column cp = Cm + cp * P (symmetric); the LDS copy once a step needs it
+    const double* Cm = kTableEarly ? Cc_ : Cg;  // column cp = Cm + cp * P (symmetric); the LDS copy once a step needs it (or from the first pass on)
     // The small system S = A'C A of the active rows is carried as J = L^-1, the INVERSE of its Cholesky factor (lower triangular, zeros kept
     // above the diagonal): S^-1 = J'J, so r = S^-1 v is two matrix-vector products without a dependent chain (a substitution through L is
     // 2k dependent broadcast-multiply-subtract steps), a joining row appends the row (-r' , 1) / sqrt(a_p'w_p - v'r) -- r is this step's --
@@ -862,12 +921,17 @@
             why = LSCQP_DAS_WHY_ROWS;
             break;
         }
+#if LSCQP_DAS_STEP_PATH & 2
+        (void)haveJ, (void)haveC;  // (the first-step setup is done: nothing to remember)
+#else
         if (!haveJ) {  // (before the first step; by wavefront 0, the only one that touches J: in order with its own use)
             if (wv == 0)
                 for (int e = lane; e < kcap * LDL; e += 64) Jm_[e] = 0.0;
             haveJ = true;
         }
-        if (cacheC && !haveC) {  // the table of this instance's ts in LDS from the first step on (every step reads a few of its columns)
+#endif
+        // (kTableEarly: the first pass has left the table in LDS)
+        if (!kTableEarly && cacheC && !haveC) {  // the table of this instance's ts in LDS from the first step on (every step reads a few of its columns)
             bool copied = false;
             if constexpr (kCPre > 0) {
                 if (c_prefetched) {
@@ -1006,11 +1070,22 @@
             }
             DAS_T(11);  // the step itself: c, W
             if (kind == 1) {
+#if LSCQP_DAS_STEP_PATH & 4
+                // the joining row's descriptors, from the registers every thread holds (slot kcap keeps the copy the candidate left there --
+                // nothing has written it since -- and is not read here: eight LDS round trips of one thread in front of the barrier)
+                if (tid == 0) {
+                    aint_[4 * k] = bid;
+#pragma unroll
+                    for (int t_ = 0; t_ < 3; t_++) aint_[4 * k + 1 + t_] = Rp.ent[t_], acoef_[3 * k + t_] = Rp.coef[t_];
+                    arhs_[k] = Rp.rhs;
+                }
+#else
                 if (tid == 0) {
                     for (int t_ = 0; t_ < 4; t_++) aint_[4 * k + t_] = aint_[4 * kcap + t_];
                     for (int t_ = 0; t_ < 3; t_++) acoef_[3 * k + t_] = acoef_[3 * kcap + t_];
                     arhs_[k] = arhs_[kcap];
                 }
+#endif
                 k++;
                 LSCQP_DAS_BARRIER();
                 break;

@@ -36,6 +36,17 @@ constexpr bool carve_fits(int M, int dim, int kmax, int stage_rows) {
 #else
 #define LSCQP_FUSED_PROLOGUE 1
 #endif
+// Which changes to the stepping instance's path the phase runs here (lscqp_das_body.inc, LSCQP_DAS_STEP_PATH: a set of bits, one per
+// change): the M = 5 form runs all three.  The M = 10 forms keep the text they had: with the changes the 2-D one spills one scalar
+// register more (252 against 251) and has no timing that would pay for it, the 3-D one 301 - 312 against 292 (NOTES section 24).
+// (-DLSCQP_FUSED_STEP_PATH=<bits> builds a subset: the timing twins of one change.)
+#ifndef LSCQP_FUSED_STEP_PATH
+#if LSCQP_M == 5
+#define LSCQP_FUSED_STEP_PATH 7
+#else
+#define LSCQP_FUSED_STEP_PATH 0
+#endif
+#endif
 template <int M, int DIM, bool ES, int NSLOT, int W>
 struct FusedCarve {
     static constexpr int kStage = lscqp::Cfg<M, DIM, ES, NSLOT, W, (int)sizeof(double)>::MAX_OBS * 6 * M;  // LSC rows of a full instance
@@ -78,7 +89,9 @@ __global__ __launch_bounds__(256, 1) void das_pdip_kernel(DevClass cls, int cap,
     } while (0)
 #define LSCQP_DAS_LAYOUT Layout::make(M, DIM, FC::KMAX, 1, FC::kStage)
 #define LSCQP_DAS_PROLOGUE LSCQP_FUSED_PROLOGUE
+#define LSCQP_DAS_STEP_PATH LSCQP_FUSED_STEP_PATH
 #include "lscqp_das_body.inc"
+#undef LSCQP_DAS_STEP_PATH
 #undef LSCQP_DAS_PROLOGUE
 #undef LSCQP_DAS_LAYOUT
 #undef LSCQP_DAS_END
