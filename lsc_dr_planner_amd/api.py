@@ -211,6 +211,11 @@ def lib():
         L.lscqp_construct_sfc_device.argtypes = [vp, vp, C.c_int32, C.c_int64] + [vp] * 5
         L.lscqp_validate_step_device.restype = C.c_int
         L.lscqp_validate_step_device.argtypes = [vp, C.c_int64, C.c_double, C.c_double] + [vp] * 6
+        # library-internal entries of the replan chain (csrc/lscplan.hip), wrapped for the tests like the lscqp_debug_*_ symbols below
+        L.lscqp_optimize_goal_fin_device_.restype = C.c_int
+        L.lscqp_optimize_goal_fin_device_.argtypes = [vp, C.c_int64] + [vp] * 5 + [C.c_double, vp]
+        L.lscqp_commit_validate_raw_.restype = C.c_int
+        L.lscqp_commit_validate_raw_.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int64, C.c_double, C.c_double] + [vp] * 10
         L.lscqp_plan_create.restype = C.c_int
         L.lscqp_plan_create.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_void_p)]
         L.lscqp_plan_destroy.restype = None
@@ -1199,6 +1204,17 @@ class Solver:
         if rc != OK:
             raise LscqpError(rc, lib().lscqp_last_error().decode())
 
+    def optimize_goal_fin_device(self, n, d_hdr, d_rows, d_off, d_sfc, d_status, fin_dt, stream=None):
+        """(library-internal, tests) lscqp_optimize_goal_fin_device_: the goal LP as the replan chain runs it -- the goal left as a point3d
+        (float32 values) and terminal_segments written from it (fin_dt = the class's dt)."""
+        import torch
+
+        s = stream if stream is not None else torch.cuda.current_stream()
+        rc = lib().lscqp_optimize_goal_fin_device_(self._h, n, _dptr(d_hdr), _dptr(d_rows), _dptr(d_off), _dptr(d_sfc), _dptr(d_status), float(fin_dt),
+                                                   C.c_void_p(s.cuda_stream))
+        if rc != OK:
+            raise LscqpError(rc, lib().lscqp_last_error().decode())
+
     # ---- isSolValid + getStateAt + doStep (SURVEY.md section 8f-3) -------------------------------------------
     def safety_metrics_device(self, n_agents, first_agent, n_total, n_samples, record_time_step, d_x_all, d_radius, d_downwash, d_hdr,
                               d_out, z_2d=1.0, stream=None):
@@ -1247,6 +1263,20 @@ class Solver:
 
         rc = lib().lscqp_validate_step_device(self._h, n, float(time_step), float(z_2d), p(d_x), p(d_hdr), p(d_sfc), p(d_valid),
                                               p(d_state), C.c_void_p(s.cuda_stream))
+        if rc != OK:
+            raise LscqpError(rc, lib().lscqp_last_error().decode())
+
+    def commit_validate_device(self, n, time_step, d_qp_status, d_x_new, d_x_init, d_x_plan, d_goal, d_hdr, d_sfc, d_valid, d_state, z_2d=1.0,
+                               stream=None):
+        """(library-internal, tests) lscqp_commit_validate_raw_: the replan chain's commit (x_plan = x_new where the QP is OPTIMAL, else
+        x_init; goal = hdr.goal) with isSolValid + doStep on the plan it chose, in one launch."""
+        import torch
+
+        s = stream if stream is not None else torch.cuda.current_stream()
+        d = self.desc
+        rc = lib().lscqp_commit_validate_raw_(int(d.M), int(d.dim), int(d.use_sfc), float(d.dt), n, float(time_step), float(z_2d), _dptr(d_qp_status),
+                                              _dptr(d_x_new), _dptr(d_x_init), _dptr(d_x_plan), _dptr(d_goal), _dptr(d_hdr), _dptr(d_sfc),
+                                              _dptr(d_valid), _dptr(d_state), C.c_void_p(s.cuda_stream))
         if rc != OK:
             raise LscqpError(rc, lib().lscqp_last_error().decode())
 
