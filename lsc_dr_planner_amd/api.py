@@ -78,6 +78,25 @@ class Work(C.Structure):  # lscqp_work
                 ("lds_bytes", C.c_int32), ("kernel", C.c_char * 96)]
 
 
+class _PlanPhase(C.Structure):  # csrc/lscqp_solve_plan.hpp: PhaseShape, Pass, SolvePlan -- what lscqp_debug_solve_plan_ fills
+    _fields_ = [(k, C.c_int32) for k in ("cap", "threads", "kmax", "steps", "cacheC", "stage_rows", "screen", "tiny", "lds_bytes")]
+
+
+class _PlanPass(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("kind", "repair", "scan", "queue", "x_init", "M", "dim", "es", "slots", "waves", "mixed")] + [
+        ("inst", C.c_void_p), ("what", C.c_char_p)]
+
+
+class _Plan(C.Structure):
+    _fields_ = [("n_pass", C.c_int32), ("deferred", C.c_int32), ("error", C.c_int32), ("capacity", C.c_int32), ("phase", _PlanPhase),
+                ("fused", C.c_void_p), ("passes", _PlanPass * 6)]
+
+
+PLAN_WHOLE, PLAN_BEHIND_PHASE, PLAN_OTHER_ORDER, PLAN_RESCUE = 0, 1, 2, 3  # which part of a call (csrc/lscqp_solve_plan.hpp: SolvePart)
+PLAN_PASS_KINDS = ("prescreen", "phase", "fused", "instance", "generic")    # PassKind
+PLAN_ERRORS = (None, "lean_with_prescreen", "only_without_phase", "no_kernel")  # PlanError
+
+
 class LscqpError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("lscqp error %d: %s" % (code, msg))
@@ -302,6 +321,9 @@ def lib():
             L.lscqp_prescreen.argtypes = [vp]
             L.lscqp_debug_prescreen_twin_.restype = C.c_int
             L.lscqp_debug_prescreen_twin_.argtypes = [vp, C.c_int64, C.c_int32] + [vp] * 5
+        if hasattr(L, "lscqp_debug_solve_plan_"):  # (an A/B build may predate the solve plan: tools/solve_plan_ab.py)
+            L.lscqp_debug_solve_plan_.restype = C.c_int
+            L.lscqp_debug_solve_plan_.argtypes = [vp, C.c_int64, C.c_int32] + [C.c_int32] * 7 + [C.POINTER(_Plan)]
         _lib = L
     return _lib
 
@@ -1140,6 +1162,25 @@ class Solver:
         if rc != OK:
             raise LscqpError(rc, lib().lscqp_last_error().decode())
         return out
+
+    def solve_plan(self, n, n_obs_max, retry=0, part=PLAN_WHOLE, has_x_init=False, has_order=False, deferred=False, n_cu=256, tables_available=True):
+        """(library-internal, tests) what a solve call of this handle WOULD launch: lscqp_debug_solve_plan_, the very planner the solve worker
+        runs, on no device.  {"passes": [...], "deferred", "error", "capacity"}; a pass of kind "fused" is followed by the "phase" and the
+        "instance" pass that run in its place when the fused launcher refuses the budgets."""
+        self._sync_knobs()
+        out = _Plan()
+        rc = lib().lscqp_debug_solve_plan_(self._h, int(n), int(n_obs_max), int(retry), int(part), int(has_x_init), int(has_order), int(deferred),
+                                           int(n_cu), int(tables_available), C.byref(out))
+        if rc != OK:
+            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        passes = []
+        for ps in out.passes[:out.n_pass]:
+            d = {k: getattr(ps, k) for k, _ in _PlanPass._fields_ if k != "inst"}
+            d["kind"], d["what"] = PLAN_PASS_KINDS[ps.kind], ps.what.decode()
+            if d["kind"] in ("phase", "fused"):  # the launch shape of the phase
+                d.update({k: getattr(out.phase, k) for k, _ in _PlanPhase._fields_})
+            passes.append(d)
+        return {"passes": passes, "deferred": bool(out.deferred), "error": PLAN_ERRORS[out.error], "capacity": out.capacity}
 
     def device_fill(self, n, n_obs_max):
         """lscqp_device_fill: instances one device works on at once in the first kernel of a solve of this class."""

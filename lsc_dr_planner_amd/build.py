@@ -82,7 +82,7 @@ def build(force=False, verbose=False, jobs=None):
     api_o = os.path.join(OBJ, "api.o")
     objs.append(api_o)
     api_src = os.path.join(CSRC, "lscqp_api.hip")
-    if force or _newer(api_o, hdrs + [api_src]):
+    if force or _newer(api_o, hdrs + [api_src, os.path.join(CSRC, "lscqp_solve_plan.hpp")]):
         tasks.append([HIPCC] + FLAGS + os.environ.get("LSCQP_EXTRA_F64_FLAGS", "").split() + ["-c", api_src, "-o", api_o])
     post_o = os.path.join(OBJ, "lscpost.o")
     objs.append(post_o)

@@ -93,6 +93,22 @@ int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
+// There is no CPU fallback: an entry that needs a device fails with LSCQP_ERR_NO_DEVICE -- most with one fixed text (have_device), the solve and
+// prescreen entries with what the runtime said (need_device_say_why: LSCQP_OK, or the failure)
+bool have_device(hipError_t* err = nullptr, int* count = nullptr) {
+    int ndev = 0;
+    const hipError_t de = hipGetDeviceCount(&ndev);
+    if (err) *err = de;
+    if (count) *count = ndev;
+    return de == hipSuccess && ndev > 0;
+}
+int need_device_say_why() {
+    hipError_t de;
+    int ndev;
+    if (have_device(&de, &ndev)) return LSCQP_OK;
+    return fail(LSCQP_ERR_NO_DEVICE, std::string("no HIP device: lscqp has no CPU fallback (hipGetDeviceCount: ") + hipGetErrorString(de) + ", " +
+                                         std::to_string(ndev) + " devices)");
+}
 
 }  // namespace
 extern "C" int lscqp_set_error_(int code, const char* msg) { return fail(code, msg); }
@@ -153,6 +169,7 @@ const Inst kInst[] = {
     LSCQP_INSTANCES(LSCQP_ROW)
 #undef LSCQP_ROW
 };
+int slots_of(const Inst& i) { return i.max_obs / max_obs_of(i.M, 1, i.waves); }  // LSC row slots per lane (NSLOT of its row of LSCQP_INSTANCES)
 
 // Instance of the shape that accommodates n_obs obstacles per agent; nullptr if none.
 // Launch policy: a batch small enough to leave SIMDs idle (n <= 2 x CUs: at most two QPs per CU) takes the instance
@@ -389,6 +406,8 @@ const double kQInt[36] = {720, -1800, 1200, 0,     0,     -120, -1800, 4800, -36
 
 }  // namespace
 
+#include "lscqp_solve_plan.hpp"  // (behind Knobs, Inst, find_instance, find_fused and other_order_instance: the planner calls them)
+
 // Tables of the dual active-set phase: one host copy per class generation, one device copy per device that has solved with the handle
 // (a communicator drives several devices through one handle).  Shared by the copies lscqp_update makes of the handle.
 // A device buffer is IMMUTABLE once a launch may have seen it: an update that changes the tables gives every device a FRESH buffer and
@@ -607,10 +626,7 @@ int lscqp_create(const lscqp_class_desc* desc, lscqp_handle* out) {
     s->behind_needed = new std::atomic<int>(0);
     load_knobs(s->knobs);  // the ONLY place the product reads its environment
     das_refresh(s);
-    {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) (void)das_device_table(s, nullptr);  // (a host without a device still creates handles: lscqp_dump_instance)
-    }
+    if (have_device()) (void)das_device_table(s, nullptr);  // (a host without a device still creates handles: lscqp_dump_instance)
     *out = s;
     return LSCQP_OK;
 }
@@ -619,9 +635,7 @@ int lscqp_create(const lscqp_class_desc* desc, lscqp_handle* out) {
 // inside a stream capture.  lscqp_create does it for the device that is current then, lscqp_comm_create for every device of the communicator.
 int lscqp_prepare_device(lscqp_handle h) {
     if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     int why = 0;
     if (!das_device_table(h, nullptr, &why) && why != 0)
         return fail(LSCQP_ERR_HIP, why == 2 ? "lscqp_prepare_device inside a stream capture" : "active-set tables: device allocation or copy failed");
@@ -659,10 +673,7 @@ int lscqp_update(lscqp_handle h, const lscqp_class_desc* desc) {
     tmp.generation = h->generation + 1;
     *h = tmp;  // (the staging pool pointer and the active-set tables travel with the copy)
     das_refresh(h);
-    {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) (void)das_device_table(h, nullptr);
-    }
+    if (have_device()) (void)das_device_table(h, nullptr);
     return LSCQP_OK;
 }
 
@@ -721,7 +732,9 @@ int64_t lscqp_device_fill(lscqp_handle h, int64_t n, int32_t n_obs_max) {
     // passes behind it -- a hard stretch of the mission, mixed precision on a loaded swarm -- the slower kernel is the one that fills the device)
     const bool ip_busy = h->behind_needed && h->behind_needed->load(std::memory_order_relaxed) != 0;
     if (!ip_busy && h->desc.active_set != LSCQP_ACTIVE_SET_OFF && !(h->knobs.active_set_off && h->desc.active_set != LSCQP_ACTIVE_SET_ONLY) && h->das && !h->das->host.empty()) {
-        const int per_cu = lscqp_das_blocks_per_cu(h->desc.M, h->desc.dim, 8, h->dev.rows_f32);
+        // (the active rows of the policy's one-wavefront form: a batch beyond 8 x CUs, whatever overrides the handle carries)
+        const int kmax = das_phase_shape(Knobs{}, h->desc.M, h->desc.dim, 8 * (int64_t)n_cu + 1, n_obs_max, n_cu).kmax;
+        const int per_cu = lscqp_das_blocks_per_cu(h->desc.M, h->desc.dim, kmax, h->dev.rows_f32);
         if (per_cu > 0) return (int64_t)n_cu * per_cu;
     }
     return lscqp_launch_capacity(h, n, n_obs_max);
@@ -738,8 +751,7 @@ int lscqp_instance_work(lscqp_handle h, int64_t n, int32_t n_obs_max, lscqp_work
     if (n_cu <= 0) n_cu = 256;  // (no device in this process: MI355X's CU count decides the small-batch policy)
     const Inst* inst = find_instance(h->knobs, h->desc.M, h->desc.dim, h->es, mixed, n_obs_max, n, n_cu);
     if (!inst) return fail(LSCQP_ERR_UNSUPPORTED, "no compiled kernel instance for this launch (the run-time-shaped kernel carries no instruction counts)");
-    const int G = 64 * inst->waves / (6 * inst->M - 3) > 0 ? 64 * inst->waves / (6 * inst->M - 3) : 1;
-    const int nslot = inst->max_obs / G;
+    const int nslot = slots_of(*inst);
     double t[24];
     if (lscqp_work_table_(inst->M, inst->dim, inst->es, nslot, inst->waves, inst->mixed, t) != 0)
         return fail(LSCQP_ERR_UNSUPPORTED, "the build holds no instruction counts for this kernel instance");
@@ -773,9 +785,7 @@ int lscqp_generate_lsc_device(lscqp_handle h, int64_t n_agents, int32_t n_obs, i
     if (n_agents == 0 || n_obs == 0) return LSCQP_OK;
     if (!d_traj || !d_neighbours || !d_radius || !d_downwash || !d_goal || !d_rows_out)
         return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     return lscqp_generate_lsc_raw_(LSCQP_GEN_LSC, h->desc.M, h->desc.dim, n_agents, n_obs, first_agent, d_traj, nullptr, d_neighbours, d_radius,
                                    d_downwash, d_goal, nullptr, h->dev.rows_f32, n_obs, 0, d_rows_out, stream);
 }
@@ -815,9 +825,7 @@ int lscqp_generate_lsc_obstacles_device(lscqp_handle h, const lscqp_obstacle_par
     if (n_agents == 0 || n_dyn == 0) return LSCQP_OK;
     if (!d_traj || !d_obstacle_ids || !d_obstacles || !d_radius || !d_goal || !d_hdr || !d_rows_out)
         return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     const double* binv3 = device_binv3();
     if (!binv3) return fail(LSCQP_ERR_HIP, "constant upload failed");
     return lscqp_generate_lsc_obstacles_raw_(h->desc.M, h->desc.dim, h->desc.dt, param, n_agents, n_dyn, first_agent, d_traj, d_obstacle_ids,
@@ -831,9 +839,7 @@ int lscqp_shift_traj_partial_device(lscqp_handle h, int64_t n, double fraction, 
     if (!(fraction > 0.0 && fraction < 1.0)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "fraction = multisim_time_step / dt must lie in (0, 1)");
     if (n == 0) return LSCQP_OK;
     if (!d_x_prev || !d_traj) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     // W = B A B^-1 (src/trajectory.cpp:24-38): B Bernstein -> monomial (include/polynomial.hpp:281-294), A(i,j) = C(i,j) a^j b^(i-j) for
     // t -> a t + b with b = fraction, a = 1 - fraction, B^-1 in closed form
     auto Cn = [](int n_, int k_) { double r = 1; for (int i = 1; i <= k_; i++) r = r * (n_ - k_ + i) / i; return k_ > n_ ? 0.0 : r; };
@@ -886,9 +892,7 @@ int lscqp_generate_constraints_own_(lscqp_handle h, int32_t mode, int64_t n_agen
     if (n_agents == 0 || n_obs == 0) return LSCQP_OK;
     if (!d_traj || !d_neighbours || !d_radius || !d_downwash || !d_goal_all || !d_rows_out)
         return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     return lscqp_generate_lsc_raw_(mode, h->desc.M, h->desc.dim, n_agents, n_obs, first_agent, d_traj, d_own_traj, d_neighbours, d_radius,
                                    d_downwash, d_goal_all + 3 * first_agent, d_goal_all, h->dev.rows_f32, n_obs_total, slot0, d_rows_out, stream);
 }
@@ -900,9 +904,7 @@ int lscqp_shift_traj_device(lscqp_handle h, int64_t n, int32_t shift_segments, d
     if (shift_segments < 0 || shift_segments > 1) return fail(LSCQP_ERR_INVALID_ARGUMENT, "shift_segments must be 0 or 1");
     if (n == 0) return LSCQP_OK;
     if (!d_x_prev || !d_traj) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     return lscqp_shift_traj_raw_(h->desc.M, h->desc.dim, n, shift_segments, z_2d, d_x_prev, d_traj, stream);
 }
 
@@ -927,9 +929,7 @@ int lscqp_optimize_goal_fin_device_(lscqp_handle h, int64_t n, lscqp_header* d_h
     if (n < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
     if (n == 0) return LSCQP_OK;
     if (!d_hdr || !d_status_out || (h->desc.use_sfc && !d_sfc)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     return lscqp_goal_fin_raw_(h->desc.M, h->desc.dim, h->desc.use_sfc, h->dev.rows_f32, fin_dt, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_status_out, stream);
 }
 
@@ -939,9 +939,7 @@ int lscqp_optimize_goal(lscqp_handle h, int64_t n, lscqp_header* hdr, const lscq
     if (n < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
     if (n == 0) return LSCQP_OK;
     if (!hdr || !status_out) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     int n_obs_max = 0;
     for (int64_t q = 0; q < n; q++) {
         if (hdr[q].n_obs < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative n_obs");
@@ -991,9 +989,7 @@ int lscqp_safety_metrics_device(lscqp_handle h, int64_t n_agents, int64_t first_
         return fail(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
     if (n_agents == 0) return LSCQP_OK;
     if (!d_x_all || !d_radius || !d_downwash || !d_hdr || !d_out) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     return lscqp_safety_metrics_raw_(h->desc.M, h->desc.dim, h->desc.dt, n_agents, first_agent, n_total, n_samples, record_time_step, z_2d,
                                      d_x_all, d_radius, d_downwash, d_hdr, d_out, stream);
 }
@@ -1011,9 +1007,7 @@ int lscqp_safety_obstacles_device(lscqp_handle h, int64_t n_agents, int64_t firs
         return fail(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
     if (n_agents == 0) return LSCQP_OK;
     if (!d_x_all || !d_radius || !d_downwash || !d_out || (n_obstacles > 0 && !d_obstacles)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     return lscqp_safety_obstacles_raw_(h->desc.M, h->desc.dim, h->desc.dt, n_agents, first_agent, n_samples, record_time_step, z_2d, d_x_all,
                                        d_radius, d_downwash, n_obstacles, d_obstacles, d_out, stream);
 }
@@ -1030,9 +1024,7 @@ int lscqp_order_by_cost_device(int64_t n, const uint32_t* d_cost_prev, int32_t* 
     if (n < 0 || n > 0x7fffffff) return fail(LSCQP_ERR_INVALID_ARGUMENT, "0 <= n < 2^31 required");
     if (n == 0) return LSCQP_OK;
     if (!d_cost_prev || !d_order_out) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     hipLaunchKernelGGL(order_by_cost_kernel, dim3(1), dim3(kOrdT), 0, (hipStream_t)stream, n, d_cost_prev, d_order_out);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (order_by_cost): ") + hipGetErrorString(e));
@@ -1048,9 +1040,7 @@ int lscqp_construct_sfc_device_ordered(lscqp_handle h, lscqp_map mp, int32_t mod
     if (n == 0) return LSCQP_OK;
     if (!d_points || !d_radius || !d_sfc || !d_status_out) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
     if (h->desc.M > 21) return fail(LSCQP_ERR_UNSUPPORTED, "corridor shift supports M <= 21");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     return lscqp_construct_sfc_raw_ex_(mp, mode, h->desc.M, n, d_points, d_radius, d_sfc, d_status_out, d_order, d_cost_out, stream);
 }
 
@@ -1062,9 +1052,7 @@ int lscqp_select_neighbours_device(lscqp_handle h, int64_t n_agents, int64_t fir
         return fail(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
     if (n_agents == 0) return LSCQP_OK;
     if (!d_positions || !d_count_out || (n_obs > 0 && !d_neighbours_out)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     return lscqp_select_neighbours_raw_(n_agents, first_agent, n_total, n_obs, communication_range, d_positions, d_neighbours_out,
                                         d_count_out, stream);
 }
@@ -1087,9 +1075,7 @@ int lscqp_select_neighbours_missions_device(lscqp_handle h, int64_t n_total, int
     const int rc = lscqp_check_missions_(n_total, n_missions, mission_offsets);
     if (rc != LSCQP_OK) return rc;
     if (!d_mission_offsets || !d_positions || !d_count_out || (n_obs > 0 && !d_neighbours_out)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     return lscqp_select_neighbours_missions_raw_(n_total, n_missions, d_mission_offsets, n_obs, communication_range, d_positions, d_neighbours_out,
                                                  d_count_out, stream);
 }
@@ -1103,9 +1089,7 @@ int lscqp_safety_metrics_missions_device(lscqp_handle h, int64_t n_total, int32_
     const int rc = lscqp_check_missions_(n_total, n_missions, mission_offsets);
     if (rc != LSCQP_OK) return rc;
     if (!d_mission_offsets || !d_x_all || !d_radius || !d_downwash || !d_hdr || !d_out) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     int64_t largest = 0;
     for (int32_t k = 0; k < n_missions; k++) largest = std::max(largest, mission_offsets[k + 1] - mission_offsets[k]);
     return lscqp_safety_metrics_missions_raw_(h->desc.M, h->desc.dim, h->desc.dt, n_total, n_missions, largest, d_mission_offsets, n_samples,
@@ -1119,9 +1103,7 @@ int lscqp_validate_step_device(lscqp_handle h, int64_t n, double time_step, doub
     if (n < 0 || !(time_step >= 0)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size or time");
     if (n == 0) return LSCQP_OK;
     if (!d_x || !d_hdr || !d_valid_out || !d_state_out || (h->desc.use_sfc && !d_sfc)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     return lscqp_validate_step_raw_(h->desc.M, h->desc.dim, h->desc.use_sfc, h->desc.dt, n, time_step, z_2d, d_x, d_hdr, d_sfc, d_valid_out,
                                     d_state_out, stream);
 }
@@ -1146,18 +1128,100 @@ int lscqp_order_by_work_device(int64_t n, const lscqp_info* d_info_prev, int32_t
     if (n < 0 || n > 0x7fffffff) return fail(LSCQP_ERR_INVALID_ARGUMENT, "0 <= n < 2^31 required");
     if (n == 0) return LSCQP_OK;
     if (!d_info_prev || !d_order_out) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     hipLaunchKernelGGL(order_by_work_kernel, dim3(1), dim3(kOrdT), 0, (hipStream_t)stream, n, d_info_prev, d_order_out);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (order_by_work): ") + hipGetErrorString(e));
     return LSCQP_OK;
 }
 
-int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_max, const lscqp_header* d_hdr, const lscqp_row* d_rows,
-                                       const uint64_t* d_row_offsets, const lscqp_box* d_sfc, const double* d_x_init, double* d_x_out, double* d_obj_out,
-                                       int32_t* d_status_out, lscqp_info* d_info_out, int32_t retry, const int32_t* d_order, void* stream, int* deferred);
+// The worker behind the public device entries: validate, resolve the device and the tables, plan (lscqp_solve_plan.hpp: every rule about WHAT is
+// launched lives there), run the plan.  part: a SolvePart -- the host-pointer entries and lscqp_comm.hip run the parts behind the first after
+// looking at the statuses.  deferred != NULL (the host-pointer entries): when the dual active-set phase runs, the call returns right behind it
+// with *deferred = 1 and the interior-point passes are NOT enqueued -- the caller reads the statuses with the results and enqueues them
+// (PART_BEHIND_PHASE, same retry) only if the phase left an instance: on the bench's batches it never does, and a near-empty launch costs
+// 2 - 4 us of every call.
+int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_max, const lscqp_header* d_hdr,
+                                       const lscqp_row* d_rows, const uint64_t* d_row_offsets, const lscqp_box* d_sfc,
+                                       const double* d_x_init, double* d_x_out, double* d_obj_out, int32_t* d_status_out,
+                                       lscqp_info* d_info_out, int32_t retry, int32_t part, const int32_t* d_order, void* stream, int* deferred) {
+    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (deferred) *deferred = 0;
+    if (retry < 0 || retry > 3 || part < PART_WHOLE || part > PART_RESCUE) return fail(LSCQP_ERR_INVALID_ARGUMENT, "invalid pass code");
+    if (n < 0 || n_obs_max < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
+    if (n == 0) return LSCQP_OK;
+    if (!d_hdr || !d_x_out || !d_obj_out || !d_status_out || (n_obs_max > 0 && (!d_rows || !d_row_offsets)) ||
+        (h->desc.use_sfc && !d_sfc))
+        return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (int rc = need_device_say_why()) return rc;
+    const Knobs& kn = h->knobs;
+    const hipStream_t st = (hipStream_t)stream;
+    if (d_order && kn.check_order && order_is_permutation(n, d_order, st) == 0)
+        return fail(LSCQP_ERR_INVALID_ARGUMENT, "d_order is not a permutation of 0 .. n-1 (LSCQP_CHECK_ORDER)");
+    const int M = h->desc.M, dim = h->desc.dim;
+    const double* d_tab = nullptr;
+    if (phase_asked(h->desc, kn, (SolvePart)part)) {
+        int why = 0;
+        d_tab = das_device_table(h, st, &why);
+        // (no tables on this device and none can be made right now: running without the phase would differ from an eager run in the last
+        // bits -- silently, for the whole lifetime of a captured graph.  Say so instead.)
+        if (!d_tab && why == 2)
+            return fail(LSCQP_ERR_HIP, "the class's active-set tables are not on this device and the launch sits inside a stream capture: call "
+                                       "lscqp_prepare_device(handle) on this device before capturing");
+        if (!d_tab && why == 1) return fail(LSCQP_ERR_HIP, "active-set tables: device allocation or copy failed");
+    }
+    const SolvePlan plan = plan_solve(h->desc, h->es, kn, h->prescreen, n, n_obs_max, retry, (SolvePart)part, d_x_init != nullptr, deferred != nullptr,
+                                      cu_count(), d_tab != nullptr);
+    if (plan.error == PLAN_LEAN_WITH_PRESCREEN)
+        return fail(LSCQP_ERR_UNSUPPORTED, "the lean form of the phase (knob das_screen) is not available with the prescreen on");
+    if (plan.error == PLAN_ONLY_WITHOUT_PHASE)
+        return fail(LSCQP_ERR_UNSUPPORTED, "LSCQP_ACTIVE_SET_ONLY: the active-set phase could not run (no tables on this device, or capacity)");
+    if (plan.error == PLAN_NO_KERNEL) {
+        const bool mixed = h->desc.precision == LSCQP_PRECISION_MIXED;
+        char buf[240];
+        snprintf(buf, sizeof buf, "no kernel of M=%d dim=%d%s holds %d obstacles per agent (compiled instances and the run-time-shaped kernel: %d)",
+                 M, dim, mixed ? " (mixed precision)" : "", n_obs_max, lscqp_max_obstacles(h));
+        return fail(LSCQP_ERR_UNSUPPORTED, buf);
+    }
+    const PhaseShape& ph = plan.phase;
+    for (int k = 0; k < plan.n_pass; k++) {
+        const Pass& ps = plan.pass[k];
+        lscqp::DevClass cls = h->dev;
+        cls.n_obs_max = n_obs_max;
+        cls.order = d_order;
+        cls.repair = ps.repair;
+        cls.scan = ps.scan;
+        cls.queue = ps.queue ? next_queue_counter(st) : nullptr;
+        const double* x_init = ps.x_init ? d_x_init : nullptr;
+        hipError_t e = hipSuccess;
+        switch (ps.kind) {
+        case PASS_PRESCREEN:
+            e = lscqp_launch_prescreen(&cls, M, dim, n_obs_max, n, d_hdr, d_rows, d_row_offsets, d_sfc, x_init, nullptr, d_x_out, d_obj_out, d_status_out,
+                                       d_info_out, st);
+            break;
+        case PASS_FUSED:
+            e = plan.fused(&cls, ph.cap, ph.kmax, ph.steps, ph.cacheC, ph.stage_rows, d_tab, n, d_hdr, d_rows, d_row_offsets, d_sfc, x_init, d_x_out, d_obj_out,
+                           d_status_out, d_info_out, st);
+            if (e == hipSuccess) k += 2;  // (it did the work of the phase and the first pass, which follow it in the plan)
+            else if (e == hipErrorNotSupported) e = hipSuccess;  // (budgets beyond the compiled carve: those two launches, then)
+            break;
+        case PASS_PHASE:
+            e = lscqp_launch_das(&cls, M, dim, h->es, ph.cap, ph.threads, ph.kmax, ph.steps, ph.cacheC, ph.stage_rows, ph.screen, d_tab, n, d_hdr, d_rows,
+                                 d_row_offsets, d_sfc, x_init, d_x_out, d_obj_out, d_status_out, d_info_out, st);
+            break;
+        case PASS_INSTANCE:
+            e = ps.inst->fn(&cls, n, d_hdr, d_rows, d_row_offsets, d_sfc, x_init, d_x_out, d_obj_out, d_status_out, d_info_out, st);
+            break;
+        case PASS_GENERIC:
+            e = lscqp_launch_generic(&cls, M, dim, h->es, n, d_hdr, d_rows, d_row_offsets, d_sfc, x_init, d_x_out, d_obj_out, d_status_out, d_info_out, st);
+            break;
+        }
+        if (e != hipSuccess)
+            return fail(LSCQP_ERR_HIP, std::string("HIP launch failed") + (ps.what[0] ? " (" + std::string(ps.what) + ")" : "") + ": " + hipGetErrorString(e));
+    }
+    if (deferred) *deferred = plan.deferred;
+    return LSCQP_OK;
+}
 
 int lscqp_solve_batch_device_ex(lscqp_handle h, int64_t n, int32_t n_obs_max, const lscqp_header* d_hdr,
                                 const lscqp_row* d_rows, const uint64_t* d_row_offsets, const lscqp_box* d_sfc,
@@ -1173,280 +1237,17 @@ int lscqp_solve_batch_device_ordered(lscqp_handle h, int64_t n, int32_t n_obs_ma
                                      lscqp_info* d_info_out, int32_t retry, const int32_t* d_order, void* stream) {
     if (retry < 0 || retry > 3) return fail(LSCQP_ERR_INVALID_ARGUMENT, "retry must be 0, 1, 2 or 3");
     return lscqp_solve_batch_device_internal_(h, n, n_obs_max, d_hdr, d_rows, d_row_offsets, d_sfc, d_x_init, d_x_out, d_obj_out, d_status_out, d_info_out,
-                                              retry, d_order, stream, nullptr);
+                                              retry, PART_WHOLE, d_order, stream, nullptr);
 }
 
-// The worker behind the public device entries.  retry also takes the library's own pass codes: -2 = only the repair pass on the instance of
-// the other elimination order, -3 = only the rescue pass (the host-pointer entries and lscqp_comm.hip run them after looking at the statuses),
-// -10 - r = the interior-point passes of a call with retry = r whose dual active-set phase has ALREADY run (see `deferred`).
-// deferred != NULL (the host-pointer entries): when the dual active-set phase runs, the call returns right behind it with *deferred = 1 and
-// the interior-point passes are NOT enqueued -- the caller reads the statuses with the results and enqueues them (pass code -10 - retry)
-// only if the phase left an instance: on the bench's batches it never does, and a near-empty launch costs 2 - 4 us of every call.
-int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_max, const lscqp_header* d_hdr,
-                                       const lscqp_row* d_rows, const uint64_t* d_row_offsets, const lscqp_box* d_sfc,
-                                       const double* d_x_init, double* d_x_out, double* d_obj_out, int32_t* d_status_out,
-                                       lscqp_info* d_info_out, int32_t retry, const int32_t* d_order, void* stream, int* deferred) {
-    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (deferred) *deferred = 0;
-    bool behind_only = false;  // the phase of this call ran in an earlier invocation
-    if (retry <= -10 && retry >= -13) {
-        behind_only = true;
-        retry = -10 - retry;
-    }
-    if (retry < -3 || retry > 3 || retry == -1) return fail(LSCQP_ERR_INVALID_ARGUMENT, "invalid pass code");
-    if (n < 0 || n_obs_max < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
-    if (n == 0) return LSCQP_OK;
-    if (!d_hdr || !d_x_out || !d_obj_out || !d_status_out || (n_obs_max > 0 && (!d_rows || !d_row_offsets)) ||
-        (h->desc.use_sfc && !d_sfc))
-        return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    {
-        const hipError_t de = hipGetDeviceCount(&ndev);
-        if (de != hipSuccess || ndev == 0)
-            return fail(LSCQP_ERR_NO_DEVICE, std::string("no HIP device: lscqp has no CPU fallback (hipGetDeviceCount: ") +
-                                                 hipGetErrorString(de) + ", " + std::to_string(ndev) + " devices)");
-    }
-    const Knobs& kn = h->knobs;
-    if (d_order && kn.check_order && order_is_permutation(n, d_order, (hipStream_t)stream) == 0)
-        return fail(LSCQP_ERR_INVALID_ARGUMENT, "d_order is not a permutation of 0 .. n-1 (LSCQP_CHECK_ORDER)");
-    const int mixed = h->desc.precision == LSCQP_PRECISION_MIXED ? 1 : 0;
-    const Inst* inst = find_instance(h->knobs, h->desc.M, h->desc.dim, h->es, mixed, n_obs_max, n, cu_count());
-    const Inst* inst64 = mixed ? find_instance(h->knobs, h->desc.M, h->desc.dim, h->es, 0, n_obs_max, n, cu_count()) : inst;
-    lscqp::DevClass cls = h->dev;
-    cls.n_obs_max = n_obs_max;
-    cls.order = d_order;
-    // a launch of more instances than the device has CUs MAY exceed what the chip holds at once: it gets a zeroed work-queue counter and
-    // the instance's launcher decides (lscqp_inst.hip: persistent workgroups over the queue, or one instance per workgroup)
-    const bool queued = !kn.no_queue && n > (int64_t)cu_count();  // (no_queue: tools/lpt_probe.py tells the queue and the order apart)
-    // (a counter -- a memset on the stream, a slot of the ring -- only for a launch that can use it: the instance has a persistent form, and
-    // the pass is not the near-empty one behind the dual active-set phase, where almost every workgroup returns at once)
-    bool das_in_front = false;
-    auto with_queue = [&](lscqp::DevClass& c, const Inst* i) {
-        c.queue = (queued && i && i->persist && !das_in_front) ? next_queue_counter((hipStream_t)stream) : nullptr;
-    };
-    hipError_t e = hipSuccess;
-    if (retry < 0 && h->desc.active_set == LSCQP_ACTIVE_SET_ONLY) return LSCQP_OK;  // (the host-pointer entries' extra passes are interior-point passes)
-    // ---- the DUAL ACTIVE SET phase (lscqp_das.hip) in front of the first interior-point pass ----------------------------------------
-    // One launch over the batch; what it finishes is OPTIMAL (LSCQP_INFO_ACTIVE_SET), everything else is marked for the interior-point
-    // kernel, whose first pass then runs with cls.repair = 3 (skip what is OPTIMAL, nothing was "repaired").  Launch shape: a batch that
-    // leaves the chip idle gets four wavefronts per QP, the whole budget of active rows and the class's table in LDS (latency); a batch
-    // that fills it gets one wavefront per QP and a small LDS footprint (occupancy is what hides the row reads), and the few instances
-    // with more active rows than that fall to the interior-point kernel.
-    bool das_ran = behind_only;
-    bool fused_ran = false;  // the first interior-point pass ran inside the phase's launch (lscqp_fused.hip)
-    // ---- the PRESCREEN (lscqp_prescreen.hip), in front of everything: what it proves infeasible is final (LSCQP_INFO_ACTIVE_SET |
-    // LSCQP_INFO_PRESCREENED), everything else is marked ITER_LIMIT -- the phase skips the former through bit 1 of `behind`, and a first
-    // interior-point pass without the phase in front runs the way the pass behind the phase does (repair = 3: only what is marked)
-    const bool prescreened = h->prescreen == LSCQP_PRESCREEN_ON && (retry >= 0 || behind_only);
-    if (prescreened && kn.das_screen > 0) return fail(LSCQP_ERR_UNSUPPORTED, "the lean form of the phase (knob das_screen) is not available with the prescreen on");
-    if (prescreened && !behind_only) {
-        e = lscqp_launch_prescreen(&cls, h->desc.M, h->desc.dim, n_obs_max, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_x_init, nullptr, d_x_out, d_obj_out,
-                                   d_status_out, d_info_out, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (prescreen): ") + hipGetErrorString(e));
-    }
-    if (retry >= 0 && !behind_only && h->desc.active_set != LSCQP_ACTIVE_SET_OFF) {
-        const bool off = kn.active_set_off && h->desc.active_set != LSCQP_ACTIVE_SET_ONLY;
-        int why = 0;
-        const double* d_tab = off ? nullptr : das_device_table(h, (hipStream_t)stream, &why);
-        // (no tables on this device and none can be made right now: running without the phase would differ from an eager run in the last
-        // bits -- silently, for the whole lifetime of a captured graph.  Say so instead.)
-        if (!off && !d_tab && why == 2)
-            return fail(LSCQP_ERR_HIP, "the class's active-set tables are not on this device and the launch sits inside a stream capture: call "
-                                       "lscqp_prepare_device(handle) on this device before capturing");
-        if (!off && !d_tab && why == 1) return fail(LSCQP_ERR_HIP, "active-set tables: device allocation or copy failed");
-        int cap = 0;
-        if (!inst || !inst64) cap = (mixed || n_obs_max > lscqp_generic_max_obstacles(h->desc.M, h->desc.dim, h->es)) ? -1 : n_obs_max;
-        else cap = std::min(inst->max_obs, inst64->max_obs);
-        if (d_tab && cap >= 0) {
-            // Launch shape (measured, profiles/r05_das_launch_shapes.txt): up to two QPs per CU the launch is about latency -- four
-            // wavefronts per QP, the whole budget of active rows, the class's table and the instance's rows in LDS; up to eight per CU
-            // the launch still lasts as long as its slowest QP (1024 x M10 x 40: 0.28 ms with one wavefront per QP, 0.19 ms with four) but
-            // LDS is what limits the resident workgroups -- four wavefronts, a small footprint; beyond that one wavefront per QP.
-            const int64_t ncu = cu_count() > 0 ? cu_count() : 256;
-            const bool small = n <= 2 * ncu, medium = n <= 8 * ncu;
-            auto knob = [](int v, int dflt) { return v >= 0 ? v : dflt; };  // (overrides: lscqp_debug_set_knob_, tests and sweeps only)
-            int threads = knob(kn.das_threads, medium ? 256 : 64);
-            // (20 active rows, not the 32 the kernel could hold: the footprint decides how many workgroups a CU holds at once and whether the
-            // instance's rows fit in LDS beside the rest -- 512 x M6: 43.0 -> 33.9 us, 128 x M10 x 40: 92.2 -> 84.3, 64 x M5: 12.9 -> 12.5; 24 would
-            // already cost the M = 10 class its staged rows.  No feasible instance of a 6 000-instance sweep of the harder swarms needs more than
-            // 12; ONE of the ~50 000 of the stress sweep needs 17-20, and at 16 it went to the interior-point kernel, which accepted it at its
-            // rounding floor (stationarity 1.9e-7): profiles/r05_kmax_sweep.txt, NOTES.md section 13)
-            // round 6 (tools/loaded_probe.py, swarms 8 - 30 replans into their exchange): a batch that leaves most CUs idle (n <= CUs) gets every
-            // active row the kernel can hold -- the forest10 class mid-exchange holds > 20 rows at one agent's optimum for several replans, and
-            // handing that ONE instance over cost the call 0.16 ms of phase + 0.34 ms of interior point against 0.34 ms without the phase; the
-            // step budget of the other small batches is halved: a feasible instance of the loaded sweeps needs <= 50 steps (<= 33 beyond 64 agents),
-            // an instance that keeps adding and dropping beyond that is, on those sweeps, one whose rows admit no point -- the kernel behind
-            // says so in 14 iterations, and every step spent here before that is added to the call
-            const bool tiny = n <= ncu;
-            int kmax = knob(kn.das_kmax, tiny ? 32 : small ? 20 : 8);
-            int steps = knob(kn.das_steps, tiny ? 96 : small ? 48 : 24);
-            int cacheC = knob(kn.das_cache, small ? 1 : 0);
-            int stage = knob(kn.das_stage, small ? 1 : 0) ? n_obs_max * 6 * h->desc.M : 0;
-            // form: bit 0 the lean form in front (built and measured, no gain: the phase is bound by instruction issue, not occupancy); bit 1 the
-            // first look inside the loop of steps (one copy of that code: batches of at most two workgroups per CU; lscqp_das.hip, PEEL)
-            const int screen = (knob(kn.das_screen, 0) ? 1 : 0) | (knob(kn.das_loop, small ? 1 : 0) ? 2 : 0);
-            const int skip_proven = prescreened ? 4 : 0;  // (lscqp_launch_das: the phase skips what the prescreen marked INFEASIBLE)
-            const int Mx = h->desc.M, dx = h->desc.dim;
-            // what does not fit the CU's LDS is given up in this order: staged rows, the table copy, active rows
-            if (lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) > lscqp::kMaxLdsBytes) stage = 0;
-            if (lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) > lscqp::kMaxLdsBytes) cacheC = 0;
-            if (tiny && kn.das_kmax < 0 && kmax > 20 && lscqp_das_lds_bytes(Mx, dx, kmax, knob(kn.das_cache, 1), knob(kn.das_stage, 1) ? n_obs_max * 6 * Mx : 0) > lscqp::kMaxLdsBytes) {
-                // (the larger budget never at the price of the staged rows or the table copy: 128 x M10 x 40 runs 8 % slower without them)
-                kmax = 20;
-                cacheC = knob(kn.das_cache, 1);
-                stage = knob(kn.das_stage, 1) ? n_obs_max * 6 * Mx : 0;
-                if (lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) > lscqp::kMaxLdsBytes) stage = 0;
-                if (lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) > lscqp::kMaxLdsBytes) cacheC = 0;
-            }
-            while (kmax > 4 && lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) > lscqp::kMaxLdsBytes) kmax -= 4;
-            // FUSED (lscqp_fused.hip): a batch of at most one instance per CU whose phase runs in its small-batch form on fp64 rows, in front of
-            // an fp64 instance that has a fused form, gets ONE launch -- a workgroup that hands its instance over solves it itself, with the
-            // pass's own class (repair = 3).  The separate pass behind the phase was a launch of n workgroups that almost all load a status and
-            // leave: 64 x M5, 14.25 -> 11.82 us per call fused (profiles/r07_fused.txt).  Not for calls that look at the statuses before they
-            // enqueue the pass (`deferred`), nor behind the scan form.
-            const fused_fn fused = (kn.das_fused && !prescreened && tiny && !mixed && !kn.behind_scan && h->desc.active_set != LSCQP_ACTIVE_SET_ONLY && !deferred &&
-                                    threads == 256 && screen == 2 && !cls.rows_f32)
-                                       ? find_fused(inst)
-                                       : nullptr;
-            if (fused && lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) <= lscqp::kMaxLdsBytes) {
-                lscqp::DevClass fc = cls;
-                fc.repair = 3;
-                fc.queue = nullptr;
-                fc.scan = 0;
-                e = fused(&fc, cap, kmax, steps, cacheC, stage, d_tab, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_x_init, d_x_out, d_obj_out, d_status_out,
-                          d_info_out, (hipStream_t)stream);
-                if (e == hipSuccess) das_ran = fused_ran = true;
-                else if (e != hipErrorNotSupported) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (fused active-set phase): ") + hipGetErrorString(e));
-            }
-            if (!fused_ran && lscqp_das_lds_bytes(Mx, dx, kmax, cacheC, stage) <= lscqp::kMaxLdsBytes) {
-                e = lscqp_launch_das(&cls, Mx, dx, h->es, cap, threads, kmax, steps, cacheC, stage, screen | skip_proven, d_tab, n, d_hdr, d_rows, d_row_offsets, d_sfc,
-                                     d_x_init, d_x_out, d_obj_out, d_status_out, d_info_out, (hipStream_t)stream);
-                if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (dual active-set phase): ") + hipGetErrorString(e));
-                das_ran = true;
-            }
-        }
-        if (h->desc.active_set == LSCQP_ACTIVE_SET_ONLY) {
-            if (!das_ran) return fail(LSCQP_ERR_UNSUPPORTED, "LSCQP_ACTIVE_SET_ONLY: the active-set phase could not run (no tables on this device, or capacity)");
-            return LSCQP_OK;
-        }
-        if (das_ran && deferred) {  // the caller looks at the statuses first
-            *deferred = 1;
-            return LSCQP_OK;
-        }
-    }
-    const int first_repair = (das_ran || prescreened) ? 3 : 0;
-    if (!inst || !inst64) {
-        // no compiled instance serves this launch (shape without one, or more obstacles than its register slots hold): the
-        // run-time-shaped kernel, fp64.  Same statuses, same second pass.
-        if (mixed || n_obs_max > lscqp_generic_max_obstacles(h->desc.M, h->desc.dim, h->es)) {
-            char buf[240];
-            snprintf(buf, sizeof buf, "no kernel of M=%d dim=%d%s holds %d obstacles per agent (compiled instances and the run-time-shaped kernel: %d)",
-                     h->desc.M, h->desc.dim, mixed ? " (mixed precision)" : "", n_obs_max, lscqp_max_obstacles(h));
-            return fail(LSCQP_ERR_UNSUPPORTED, buf);
-        }
-        if (retry == -2) return LSCQP_OK;  // (no other elimination order to try)
-        if (retry == -3) {  // (internal) only the rescue pass
-            cls.repair = 2;
-            e = lscqp_launch_generic(&cls, h->desc.M, h->desc.dim, h->es, n, d_hdr, d_rows, d_row_offsets, d_sfc, nullptr, d_x_out, d_obj_out, d_status_out,
-                                     d_info_out, (hipStream_t)stream);
-            if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (rescue pass): ") + hipGetErrorString(e));
-            return LSCQP_OK;
-        }
-        cls.repair = first_repair;
-        e = lscqp_launch_generic(&cls, h->desc.M, h->desc.dim, h->es, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_x_init, d_x_out, d_obj_out, d_status_out,
-                                 d_info_out, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (run-time-shaped kernel): ") + hipGetErrorString(e));
-        if (retry && d_x_init) {
-            cls.repair = 1;
-            e = lscqp_launch_generic(&cls, h->desc.M, h->desc.dim, h->es, n, d_hdr, d_rows, d_row_offsets, d_sfc, nullptr, d_x_out, d_obj_out, d_status_out,
-                                     d_info_out, (hipStream_t)stream);
-            if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (run-time-shaped kernel, second pass): ") + hipGetErrorString(e));
-        }
-        if (retry == 2 || retry == 3) {
-            cls.repair = 2;
-            e = lscqp_launch_generic(&cls, h->desc.M, h->desc.dim, h->es, n, d_hdr, d_rows, d_row_offsets, d_sfc, nullptr, d_x_out, d_obj_out, d_status_out,
-                                     d_info_out, (hipStream_t)stream);
-            if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (rescue pass): ") + hipGetErrorString(e));
-        }
-        return LSCQP_OK;
-    }
-    // RESCUE pass (retry == -3: only it; retry == 2: after the other passes): what is still at the iteration limit or broke down
-    // numerically goes through the run-time-shaped kernel once more with cls.repair = 2 (lscqp_generic.hip: weighted corrector)
-    auto rescue = [&]() -> int {
-        if (n_obs_max > lscqp_generic_max_obstacles(h->desc.M, h->desc.dim, h->es)) return LSCQP_OK;  // (the kernel cannot hold the batch: nothing to try)
-        lscqp::DevClass rc_ = cls;
-        rc_.repair = 2;
-        rc_.queue = nullptr;
-        const hipError_t er = lscqp_launch_generic(&rc_, h->desc.M, h->desc.dim, h->es, n, d_hdr, d_rows, d_row_offsets, d_sfc, nullptr, d_x_out, d_obj_out,
-                                                   d_status_out, d_info_out, (hipStream_t)stream);
-        if (er != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (rescue pass): ") + hipGetErrorString(er));
-        return LSCQP_OK;
-    };
-    if (retry == -3) return rescue();
-    if (retry == -2) {  // (internal) only the repair pass, on the other-order instance: the statuses of a first pass are in d_status_out
-        const Inst* other = other_order_instance(inst64, n_obs_max);
-        if (!other) return LSCQP_OK;
-        cls.repair = 1;
-        with_queue(cls, other);
-        e = other->fn(&cls, n, d_hdr, d_rows, d_row_offsets, d_sfc, nullptr, d_x_out, d_obj_out, d_status_out, d_info_out, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (other-order pass): ") + hipGetErrorString(e));
-        return LSCQP_OK;
-    }
-    cls.repair = first_repair;
-    das_in_front = das_ran;
-    // Behind the phase the pass usually finds nothing to do, and what it costs then is its launch: n workgroups that load one status each and
-    // leave (4096 x M5: 4.5 us and 33 MB of fetches per call; a mixed-precision class: two such launches, float32 then fp64).  So behind the
-    // phase the pass runs on an fp64 instance of the same capacity that has the PERSIST form, in its scan mode (lscqp_kernel.hpp:
-    // DevClass::scan): at most as many workgroups as the chip holds, each looking through 64 statuses per round trip.  A mixed-precision class
-    // is served by that fp64 instance directly -- the float32 factorisation has nothing to add behind a phase that finishes the easy
-    // instances, and its own second pass would be a third launch.  Without such an instance: as before.
-    const Inst* first = inst;
-    if (das_ran && !kn.behind_scan) {
-        // MEASURED (round 6, profiles/r06_behind_scan.txt): the scan form LOSES -- 64 x M5 14.8 -> 17.3 us per call, 4096 x M5 41.0 -> 42.3 -- the
-        // persistent form of the kernel pays more before its first status load than n one-status workgroups cost.  Off by default (knob
-        // behind_scan); what stays is the mixed-precision class going straight to its fp64 instance behind the phase (one launch instead of two).
-        first = mixed ? inst64 : inst;
-    } else if (das_ran) {
-        const int want = std::min(inst->max_obs, inst64->max_obs);
-        if (!(inst->persist && !inst->mixed)) {
-            const Inst* b = nullptr;
-            for (const Inst& i : kInst)
-                if (i.M == h->desc.M && i.dim == h->desc.dim && i.es == h->es && !i.mixed && i.persist && i.max_obs == want && (!kn.pin_waves || i.waves == kn.pin_waves) &&
-                    (!b || i.waves < b->waves))
-                    b = &i;
-            first = b ? b : (mixed ? inst64 : inst);
-        }
-        cls.scan = (first->persist && !first->mixed) ? 1 : 0;
-    }
-    if (!fused_ran) {
-        with_queue(cls, first);
-        das_in_front = false;
-        e = first->fn(&cls, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_x_init, d_x_out, d_obj_out, d_status_out, d_info_out, (hipStream_t)stream);
-        cls.scan = 0;
-        if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed: ") + hipGetErrorString(e));
-    }
-    das_in_front = false;
-    // Second pass over the batch, same stream, no host round trip: a workgroup whose instance is already OPTIMAL (or was
-    // refused for capacity) returns at once.  Mixed precision: the fp64 kernel re-solves what the float32 factorisation could
-    // not finish (same start).  retry: the fp64 kernel re-solves from the DEFAULT start what a warm start did not bring to
-    // OPTIMAL -- a jammed or diverged warm start (ITER_LIMIT / NUMERIC, or relabelled INFEASIBLE on its primal residual) says
-    // nothing about the problem, a cold start proves infeasibility independently of x_init.
-    // retry = 2: the second pass on the instance of the other elimination order (also for cold batches).  Not the default of a retry:
-    // the natural-order instances of the shapes that have both spill to scratch, and a kernel with a private segment costs ~35 us to
-    // launch even when every workgroup returns at once (measured: 38.7 vs 4.6 us per call on the forest10 replica).
-    const Inst* alt = retry == 2 ? other_order_instance(inst64, n_obs_max) : nullptr;
-    if ((mixed && first->mixed) || (retry && (d_x_init || alt))) {
-        cls.repair = 1;
-        // (behind the phase the second pass, too, finds nothing on most batches: same instance, same scan form as the first)
-        const Inst* second = alt ? alt : ((das_ran && kn.behind_scan && first->persist && !first->mixed) ? first : inst64);
-        cls.scan = (das_ran && kn.behind_scan && second->persist) ? 1 : 0;
-        with_queue(cls, cls.scan ? nullptr : second);
-        e = second->fn(&cls, n, d_hdr, d_rows, d_row_offsets, d_sfc, (retry ? nullptr : d_x_init), d_x_out, d_obj_out, d_status_out,
-                       d_info_out, (hipStream_t)stream);
-        cls.scan = 0;
-        if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("HIP launch failed (second pass): ") + hipGetErrorString(e));
-    }
-    if (retry == 2 || retry == 3) return rescue();
+// (library-internal, tests) the plan of a call of this handle, from the planner the worker above runs -- on no device: the CU count and
+// whether the class's tables are on the device are arguments.  has_order: taken because a call has it; no rule reads it today.
+int lscqp_debug_solve_plan_(lscqp_handle h, int64_t n, int32_t n_obs_max, int32_t retry, int32_t part, int32_t has_x_init, int32_t has_order,
+                            int32_t deferred, int32_t n_cu, int32_t tables_available, SolvePlan* out) {
+    if (!h || !out || n < 0 || n_obs_max < 0 || retry < 0 || retry > 3 || part < PART_WHOLE || part > PART_RESCUE)
+        return fail(LSCQP_ERR_INVALID_ARGUMENT, "invalid argument");
+    (void)has_order;
+    *out = plan_solve(h->desc, h->es, h->knobs, h->prescreen, n, n_obs_max, retry, (SolvePart)part, has_x_init != 0, deferred != 0, n_cu, tables_available != 0);
     return LSCQP_OK;
 }
 
@@ -1459,11 +1260,7 @@ int lscqp_prescreen_batch_device(lscqp_handle h, int64_t n, int32_t n_obs_max, c
     if (n == 0) return LSCQP_OK;
     if (!d_hdr || !d_cert_out || (n_obs_max > 0 && (!d_rows || !d_row_offsets)) || (h->desc.use_sfc && !d_sfc))
         return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    const hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev == 0)
-        return fail(LSCQP_ERR_NO_DEVICE, std::string("no HIP device: lscqp has no CPU fallback (hipGetDeviceCount: ") + hipGetErrorString(de) + ", " +
-                                             std::to_string(ndev) + " devices)");
+    if (int rc = need_device_say_why()) return rc;
     lscqp::DevClass cls = h->dev;
     cls.n_obs_max = n_obs_max;
     const hipError_t e = lscqp_launch_prescreen(&cls, h->desc.M, h->desc.dim, n_obs_max, n, d_hdr, d_rows, d_row_offsets, d_sfc, nullptr, d_cert_out, nullptr,
@@ -1477,8 +1274,7 @@ int lscqp_prescreen_batch_device(lscqp_handle h, int64_t n, int32_t n_obs_max, c
 int lscqp_set_prescreen(lscqp_handle h, int32_t mode) {
     if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
     if (mode != LSCQP_PRESCREEN_OFF && mode != LSCQP_PRESCREEN_ON) return fail(LSCQP_ERR_INVALID_ARGUMENT, "mode must be LSCQP_PRESCREEN_OFF or LSCQP_PRESCREEN_ON");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {  // (launches in flight keep the chain they were enqueued with; wait for them)
+    if (have_device()) {  // (launches in flight keep the chain they were enqueued with; wait for them)
         const hipError_t e = hipDeviceSynchronize();
         if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("hipDeviceSynchronize: ") + hipGetErrorString(e));
     } else {
@@ -1521,13 +1317,7 @@ int lscqp_solve_batch_stream(lscqp_handle h, int64_t n, const lscqp_header* hdr,
     if (n < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
     if (n == 0) return LSCQP_OK;
     if (!hdr || !x_out || !obj_out || !status_out) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    int ndev = 0;
-    {
-        const hipError_t de = hipGetDeviceCount(&ndev);
-        if (de != hipSuccess || ndev == 0)
-            return fail(LSCQP_ERR_NO_DEVICE, std::string("no HIP device: lscqp has no CPU fallback (hipGetDeviceCount: ") +
-                                                 hipGetErrorString(de) + ", " + std::to_string(ndev) + " devices)");
-    }
+    if (int rc = need_device_say_why()) return rc;
     int n_obs_max = 0;
     for (int64_t q = 0; q < n; q++) {
         if (hdr[q].n_obs < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative n_obs");
@@ -1584,7 +1374,7 @@ int lscqp_solve_batch_stream(lscqp_handle h, int64_t n, const lscqp_header* hdr,
     // to do is 2 - 4 us of a 20 us call.
     int deferred = 0;
     const bool speculate = h->knobs.defer_behind && h->behind_needed && h->behind_needed->load(std::memory_order_relaxed) == 0;
-    int rc = lscqp_solve_batch_device_internal_(h, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, d_xi, d_x, d_obj, d_st, d_info, 1, nullptr, st,
+    int rc = lscqp_solve_batch_device_internal_(h, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, d_xi, d_x, d_obj, d_st, d_info, 1, PART_WHOLE, nullptr, st,
                                                 speculate ? &deferred : nullptr);
     if (rc != LSCQP_OK) return rc;
     if (!zero_copy) LSCQP_CK(hipMemcpyAsync(hbase + b_in, dbase + b_in, b_out, hipMemcpyDeviceToHost, st));
@@ -1595,7 +1385,7 @@ int lscqp_solve_batch_stream(lscqp_handle h, int64_t n, const lscqp_header* hdr,
         if (deferred) {
             for (int64_t q = 0; q < n && !left; q++) left = st_h[q] == LSCQP_STATUS_ITER_LIMIT;  // (OPTIMAL and a PROVEN INFEASIBLE are final)
             if (left) {
-                rc = lscqp_solve_batch_device_internal_(h, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, d_xi, d_x, d_obj, d_st, d_info, -11, nullptr, st, nullptr);
+                rc = lscqp_solve_batch_device_internal_(h, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, d_xi, d_x, d_obj, d_st, d_info, 1, PART_BEHIND_PHASE, nullptr, st, nullptr);
                 if (rc != LSCQP_OK) return rc;
                 if (!zero_copy) LSCQP_CK(hipMemcpyAsync(hbase + b_in, dbase + b_in, b_out, hipMemcpyDeviceToHost, st));
                 LSCQP_CK(hipStreamSynchronize(st));
@@ -1614,9 +1404,8 @@ int lscqp_solve_batch_stream(lscqp_handle h, int64_t n, const lscqp_header* hdr,
         const int32_t* st_h = (const int32_t*)(hbase + o_st);
         bool any = false;
         for (int64_t q = 0; q < n && !any; q++) any = st_h[q] != LSCQP_STATUS_OPTIMAL && st_h[q] != LSCQP_STATUS_CAPACITY;
-        const Inst* first = any ? find_instance(h->knobs, h->desc.M, h->desc.dim, h->es, 0, n_obs_max, n, cu_count()) : nullptr;
-        if (first && other_order_instance(first, n_obs_max)) {
-            rc = lscqp_solve_batch_device_internal_(h, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, nullptr, d_x, d_obj, d_st, d_info, -2, nullptr, st, nullptr);
+        if (any && lscqp_has_other_order_(h, n, n_obs_max)) {
+            rc = lscqp_solve_batch_device_internal_(h, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, nullptr, d_x, d_obj, d_st, d_info, 0, PART_OTHER_ORDER, nullptr, st, nullptr);
             if (rc != LSCQP_OK) return rc;
             if (!zero_copy) LSCQP_CK(hipMemcpyAsync(hbase + b_in, dbase + b_in, b_out, hipMemcpyDeviceToHost, st));
             LSCQP_CK(hipStreamSynchronize(st));
@@ -1626,7 +1415,7 @@ int lscqp_solve_batch_stream(lscqp_handle h, int64_t n, const lscqp_header* hdr,
         bool lim = false;
         for (int64_t q = 0; q < n && !lim; q++) lim = st_h[q] == LSCQP_STATUS_ITER_LIMIT || st_h[q] == LSCQP_STATUS_NUMERIC;
         if (lim && n_obs_max <= lscqp_generic_max_obstacles(h->desc.M, h->desc.dim, h->es)) {
-            rc = lscqp_solve_batch_device_internal_(h, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, nullptr, d_x, d_obj, d_st, d_info, -3, nullptr, st, nullptr);
+            rc = lscqp_solve_batch_device_internal_(h, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, nullptr, d_x, d_obj, d_st, d_info, 0, PART_RESCUE, nullptr, st, nullptr);
             if (rc != LSCQP_OK) return rc;
             if (!zero_copy) LSCQP_CK(hipMemcpyAsync(hbase + b_in, dbase + b_in, b_out, hipMemcpyDeviceToHost, st));
             LSCQP_CK(hipStreamSynchronize(st));

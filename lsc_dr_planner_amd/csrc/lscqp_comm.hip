@@ -29,7 +29,9 @@ extern "C" const lscqp_plan_desc* lscqp_plan_desc_of_(lscqp_plan p);  // lscplan
 extern "C" int lscqp_plan_device_(lscqp_plan p);
 extern "C" int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_max, const lscqp_header* d_hdr, const lscqp_row* d_rows,
                                                   const uint64_t* d_row_offsets, const lscqp_box* d_sfc, const double* d_x_init, double* d_x_out, double* d_obj_out,
-                                                  int32_t* d_status_out, lscqp_info* d_info_out, int32_t retry, const int32_t* d_order, void* stream, int* deferred);
+                                                  int32_t* d_status_out, lscqp_info* d_info_out, int32_t retry, int32_t part, const int32_t* d_order, void* stream,
+                                                  int* deferred);
+constexpr int32_t kPartOtherOrder = 2;  // lscqp_solve_plan.hpp: PART_OTHER_ORDER, only the repair pass on the instance of the other elimination order
 extern "C" int lscqp_has_other_order_(lscqp_handle h, int64_t n, int32_t n_obs_max);
 
 namespace {
@@ -425,6 +427,7 @@ int lscqp_solve_batch_sharded(lscqp_handle h, lscqp_comm c, int64_t n, const lsc
         if (rc == LSCQP_OK) {
             // what lscqp_solve_batch does for a single device: instances that are still not OPTIMAL get one more pass on the instance
             // with the other elimination order, where the shape has one -- so a sharded batch returns what the one-device call returns
+            // (up to that call's rescue pass, which is not run here)
             const int32_t* st_h = (const int32_t*)((const char*)S.slot->h + S.o_st);
             bool any = false;
             for (int64_t q = 0; q < S.cnt && !any; q++) any = st_h[q] != LSCQP_STATUS_OPTIMAL && st_h[q] != LSCQP_STATUS_CAPACITY;
@@ -438,7 +441,7 @@ int lscqp_solve_batch_sharded(lscqp_handle h, lscqp_comm c, int64_t n, const lsc
                 rc = lscqp_solve_batch_device_internal_(h, S.cnt, n_obs_max, (const lscqp_header*)db, (const lscqp_row*)(db + o_rows),
                                                  (const uint64_t*)(db + o_off), use_sfc ? (const lscqp_box*)(db + o_sfc) : nullptr, nullptr,
                                                  (double*)(db + S.o_x), (double*)(db + S.o_obj), (int32_t*)(db + S.o_st),
-                                                 (lscqp_info*)(db + S.o_info), -2, nullptr, c->stream[g], nullptr);
+                                                 (lscqp_info*)(db + S.o_info), 0, kPartOtherOrder, nullptr, c->stream[g], nullptr);
                 if (rc == LSCQP_OK && hipMemcpyAsync(hb2 + S.b_in, db + S.b_in, S.b_out, hipMemcpyDeviceToHost, c->stream[g]) != hipSuccess)
                     rc = fail(LSCQP_ERR_HIP, "hipMemcpyAsync (D2H) failed");
                 if (rc == LSCQP_OK && (e = hipStreamSynchronize(c->stream[g])) != hipSuccess)
