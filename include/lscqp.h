@@ -995,6 +995,86 @@ int lscqp_waypoints_missions_device(lscqp_grid grid, double communication_range,
                                     double* d_waypoint, int32_t* d_group_out, int32_t* d_desired_out, int32_t* d_updated_out, void* stream);
 int lscqp_grid_mission_status(lscqp_grid grid, int32_t n_missions, int32_t* status_out);
 
+/* ---- the mission record: each mission's summary figures kept on the device, and plans flown to the finish -----------------------------
+ *
+ * What the reference prints per mission is its summary line (MultiSyncSimulator::saveSummarizedResultAsCSV, src/multi_sync_simulator.cpp
+ * :658-709): flight time, flight distance, safety ratio, excess ratios.  A record keeps the running figures of that line per mission of a
+ * partition (or for the whole swarm), accumulated by ONE kernel at the end of each replan (csrc/lscrecord.hip: one workgroup per mission),
+ * and tells when a mission is over -- MultiSyncSimulator::isFinished (:401-424).  The host reads it when it likes.
+ * The replan index r of a mission counts from 0 at the reset and lives in the record on the device (`replans` is the next r): a captured
+ * graph carries constant arguments, so a host counter could not reach the kernel.  At the end of replan r, for every mission not finished:
+ *   1. replan r is accumulated.
+ *      - sample points: for every agent the n_samples points of its NEW plan at s * record_time_step -- the states the safety kernel
+ *        evaluates (Trajectory::getStateAt of the float32 control points, z := z_2d in 2-D; the same device function), written to the points
+ *        buffer.
+ *      - distance (getTotalDistance, :711-720): the agent's distance grows by the norm() of consecutive points, the segment from the previous
+ *        replan's last point to this replan's sample 0 included (none at r = 0), in octomath::Vector3's arithmetic: float differences, float
+ *        sum of squares (no fused multiply-add), sqrt of that value in double; the sum is a double per agent.  The mission's distance is the
+ *        sum of its agents' distances in id order, formed on the host at the download: a fixed order, bit-reproducible.
+ *      - safety and excess ratios from the replan's lscqp_safety records: the mission's minimum safety_ratio with the replan, agent and other
+ *        agent attaining it (strict < in the order replan, then agent id), per-axis maxima of the excess ratios (never below 0).
+ *      - counts: agent-replans with a QP status != LSCQP_STATUS_OPTIMAL and the first replan with one (-1: none; the reference's loop ends at
+ *        the first QPFAILED, here the flight goes on and the record names the replan), valid == 0, goal LP status != 0, sfc_status == 0,
+ *        waypoint updates (where that buffer exists), the largest in-range count, agent-replans with in_range > the header's n_obs.
+ *   2. the finish test, on the state replan r STARTED from (p0 of the headers): the mission has finished when no agent has
+ *      distance(p0, desired goal) > goal_threshold -- Vector3::distance on float32 values (the goal narrowed to float32), compared in double;
+ *      equality counts as finished.  Then finished = 1, replans = r + 1, flight_time = r * time_step: isFinished runs before doStep in the
+ *      reference's loop, so the replan that starts from a passing state has been flown and logged.  A finished mission's record is frozen
+ *      (its workgroup returns after loading one word; its agents go on being replanned: they hover) and never un-finishes.
+ * lscqp_record_create      n_missions / offsets as lscqp_plan_set_missions takes them (HOST offsets; NULL: one mission [0, n_total)); M, dim
+ *                          and dt are the class's.  time_step: the simulation step a replan stands for (flight_time's unit).
+ * lscqp_record_reset       host goal points [n_total][3] (narrowed to float32 as they are); clears every figure; synchronous.
+ * lscqp_record_step_device one accumulation, asynchronous on `stream`; DEVICE pointers indexed by global agent id: d_hdr [n_total], d_x_all
+ *                          [n_total][dim*M*6], the int32 status buffers of the chain, d_safety [n_total]; d_waypoint_updated may be NULL.
+ * lscqp_record_download    out [n_missions] and, if not NULL, agent_distance [n_total]; waits for the device.
+ * lscqp_record_points      device pointer of float[n_total][n_samples][3]: the points of the last step (agents of finished missions keep the
+ *                          points of the step that finished them).
+ * lscqp_record_unfinished  the number of missions not yet finished (one 4-byte copy); waits for the device.
+ * lscqp_plan_set_record    desc != NULL gives the plan a record of its own (NULL: takes it away), accumulated by the LAST node of the chain,
+ *                          eager and captured.  Needs safety_samples > 0 and n_agents == n_total (LSCQP_ERR_INVALID_ARGUMENT says which
+ *                          failed).  It may come before or after lscqp_plan_set_missions: the record is rebuilt for the partition in force
+ *                          at lscqp_plan_reset, which must follow (a step before it is refused), requires goal_points -- they are the
+ *                          desired goals, pinned to the mission's plane in 2-D like the states -- and clears the record.  A plan without a
+ *                          record enqueues the chain it always did, node for node.
+ * lscqp_plan_record        the plan's own record, NULL without one; owned by the plan.
+ * lscqp_plan_run           flies the plan until every mission has finished: replans are enqueued in batches of check_every >= 1 (through the
+ *                          graph if use_graph != 0), behind each batch the 4-byte count of unfinished missions is copied and waited for, and
+ *                          the call returns at 0 or after max_replans.  Needs a record, closed_loop != 0 and waypoint_mode =
+ *                          LSCQP_WAYPOINT_GRID_PIBT (nothing else flies without host writes between replans; LSCQP_ERR_INVALID_ARGUMENT
+ *                          otherwise).  Because records freeze, the records do not depend on check_every; *replans_enqueued does. */
+typedef struct lscqp_record_desc {
+    double goal_threshold; /* param.goal_threshold, 0.1 in the launch files */
+} lscqp_record_desc;
+typedef struct lscqp_mission_record { /* 160 bytes */
+    int32_t finished;               /* 1 = every agent was within goal_threshold of its goal at the start of replan `replans - 1` */
+    int32_t replans;                /* replans accumulated (r + 1 after replan r); frozen when finished */
+    int32_t first_qp_failed_replan; /* -1: none */
+    int32_t reserved;
+    double flight_time;             /* (replans - 1) * time_step once finished (total_flight_time), -1 until then */
+    double distance;                /* total_flight_distance: sum of the agents' distances in id order (formed at the download) */
+    double safety_ratio_agent;      /* +inf: nothing compared */
+    int32_t safety_replan, safety_agent, safety_other, reserved2; /* replan, agent and other agent (global ids) attaining it; -1 */
+    double vel_excess_ratio[3];     /* per-axis maxima; the summary prints their float norm() (:685-686) */
+    double acc_excess_ratio[3];
+    int64_t qp_failed, invalid, goal_failed, sfc_kept, waypoint_updates;
+    int64_t max_in_range;
+    int64_t truncated;
+} lscqp_mission_record;
+typedef struct lscqp_record_s* lscqp_record;
+int lscqp_record_create(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets, int32_t n_samples,
+                        double record_time_step, double time_step, double z_2d, const lscqp_record_desc* desc, lscqp_record* out);
+void lscqp_record_destroy(lscqp_record rec);
+int lscqp_record_reset(lscqp_record rec, const double* goal_points);
+int lscqp_record_step_device(lscqp_record rec, const lscqp_header* d_hdr, const double* d_x_all, const int32_t* d_status,
+                             const int32_t* d_goal_status, const int32_t* d_sfc_status, const int32_t* d_valid, const int32_t* d_in_range,
+                             const lscqp_safety* d_safety, const int32_t* d_waypoint_updated, void* stream);
+int lscqp_record_download(lscqp_record rec, lscqp_mission_record* out, double* agent_distance);
+void* lscqp_record_points(lscqp_record rec, uint64_t* bytes_out);
+int lscqp_record_unfinished(lscqp_record rec, int32_t* unfinished_out);
+int lscqp_plan_set_record(lscqp_plan plan, const lscqp_record_desc* desc);
+lscqp_record lscqp_plan_record(lscqp_plan plan);
+int lscqp_plan_run(lscqp_plan plan, int64_t max_replans, int32_t check_every, int32_t use_graph, void* stream, int64_t* replans_enqueued);
+
 /* ---- work counters of a launch (the fp64-VALU figure next to the HBM one) -----------------------------
  *
  * The kernel is bound by fp64 vector issue, not by HBM; the figure that goes with that roof is

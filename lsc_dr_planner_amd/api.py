@@ -300,6 +300,26 @@ def lib():
         L.lscqp_waypoints_missions_device.argtypes = [vp, C.c_double, i32, i32, i64, i32, vp, vp] + [vp] * 10
         L.lscqp_grid_mission_status.restype = C.c_int
         L.lscqp_grid_mission_status.argtypes = [vp, i32, vp]
+        L.lscqp_record_create.restype = C.c_int
+        L.lscqp_record_create.argtypes = [vp, i64, i32, vp, i32, C.c_double, C.c_double, C.c_double, vp, C.POINTER(C.c_void_p)]
+        L.lscqp_record_destroy.restype = None
+        L.lscqp_record_destroy.argtypes = [vp]
+        L.lscqp_record_reset.restype = C.c_int
+        L.lscqp_record_reset.argtypes = [vp, vp]
+        L.lscqp_record_step_device.restype = C.c_int
+        L.lscqp_record_step_device.argtypes = [vp] * 11
+        L.lscqp_record_download.restype = C.c_int
+        L.lscqp_record_download.argtypes = [vp, vp, vp]
+        L.lscqp_record_points.restype = C.c_void_p
+        L.lscqp_record_points.argtypes = [vp, vp]
+        L.lscqp_record_unfinished.restype = C.c_int
+        L.lscqp_record_unfinished.argtypes = [vp, vp]
+        L.lscqp_plan_set_record.restype = C.c_int
+        L.lscqp_plan_set_record.argtypes = [vp, vp]
+        L.lscqp_plan_record.restype = C.c_void_p
+        L.lscqp_plan_record.argtypes = [vp]
+        L.lscqp_plan_run.restype = C.c_int
+        L.lscqp_plan_run.argtypes = [vp, i64, i32, i32, vp, vp]
         L.lscqp_last_error.restype = C.c_char_p
         L.lscqp_version.restype = C.c_char_p
         L.lscqp_instance_work.restype = C.c_int
@@ -344,6 +364,8 @@ EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_
                     "lscqp_grid_reserve_wide", "lscqp_waypoints_wide_device", "lscqp_plan_set_waypoint_decision",
                     "lscqp_plan_set_missions", "lscqp_plan_missions", "lscqp_plan_mission_status", "lscqp_select_neighbours_missions_device",
                     "lscqp_safety_metrics_missions_device", "lscqp_grid_fields_missions_device", "lscqp_waypoints_missions_device", "lscqp_grid_mission_status",
+                    "lscqp_record_create", "lscqp_record_destroy", "lscqp_record_reset", "lscqp_record_step_device", "lscqp_record_download",
+                    "lscqp_record_points", "lscqp_record_unfinished", "lscqp_plan_set_record", "lscqp_plan_record", "lscqp_plan_run",
                     "lscqp_instance_work", "lscqp_diagnose", "lscqp_diagnose_device", "lscqp_dump_instance", "lscqp_row_family_name",
                     "lscqp_prescreen_batch_device", "lscqp_set_prescreen", "lscqp_prescreen",
                     "lscqp_last_error", "lscqp_version"]
@@ -597,6 +619,89 @@ def waypoints(grid, communication_range, M, dim, d_state, d_plan, d_current_goal
     return grid.waypoints(communication_range, M, dim, d_state, d_plan, d_current_goal, d_field, d_init_d, d_waypoint, stream=stream)
 
 
+# lscqp_mission_record (160 bytes)
+MISSION_RECORD_DTYPE = np.dtype([("finished", "i4"), ("replans", "i4"), ("first_qp_failed_replan", "i4"), ("reserved", "i4"), ("flight_time", "f8"),
+                                 ("distance", "f8"), ("safety_ratio_agent", "f8"), ("safety_replan", "i4"), ("safety_agent", "i4"), ("safety_other", "i4"),
+                                 ("reserved2", "i4"), ("vel_excess_ratio", "f8", 3), ("acc_excess_ratio", "f8", 3), ("qp_failed", "i8"), ("invalid", "i8"),
+                                 ("goal_failed", "i8"), ("sfc_kept", "i8"), ("waypoint_updates", "i8"), ("max_in_range", "i8"), ("truncated", "i8")])
+
+
+class RecordDesc(C.Structure):  # lscqp_record_desc
+    _fields_ = [("goal_threshold", C.c_double)]
+
+
+class Record:
+    """lscqp_record: per mission the running figures of the reference's summary line and the finish test, kept on the device
+    (include/lscqp.h, "the mission record").  `handle`: a record owned by a Plan (not destroyed here)."""
+
+    def __init__(self, solver=None, n_total=0, offsets=None, n_samples=2, record_time_step=0.1, time_step=0.2, z_2d=1.0, goal_threshold=0.1,
+                 handle=None, n_missions=None):
+        self._r, self._own = None, handle is None
+        self.n_total, self.n_samples = int(n_total), int(n_samples)
+        if handle is not None:
+            self._r, self.n_missions = handle, int(n_missions)
+            return
+        d = RecordDesc(float(goal_threshold))
+        K, off = 1, None
+        if offsets is not None:
+            K, off, _ = mission_offsets_arg(offsets)
+        h = C.c_void_p()
+        rc = lib().lscqp_record_create(solver._h, self.n_total, K, None if off is None else off.ctypes.data_as(C.c_void_p), self.n_samples,
+                                       float(record_time_step), float(time_step), float(z_2d), C.byref(d), C.byref(h))
+        if rc != OK:
+            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        self._r, self.n_missions, self._solver = h, K, solver
+
+    def _check(self, rc):
+        if rc != OK:
+            raise LscqpError(rc, lib().lscqp_last_error().decode())
+
+    def close(self):
+        if self._r and self._own:
+            lib().lscqp_record_destroy(self._r)
+        self._r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, goal_points):
+        gp = np.ascontiguousarray(goal_points, dtype=np.float64).reshape(self.n_total, 3)
+        self._check(lib().lscqp_record_reset(self._r, gp.ctypes.data_as(C.c_void_p)))
+
+    def step_device(self, d_hdr, d_x_all, d_status, d_goal_status, d_sfc_status, d_valid, d_in_range, d_safety, d_waypoint_updated=None, stream=None):
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._check(lib().lscqp_record_step_device(self._r, _dptr(d_hdr), _dptr(d_x_all), _dptr(d_status), _dptr(d_goal_status), _dptr(d_sfc_status),
+                                                   _dptr(d_valid), _dptr(d_in_range), _dptr(d_safety), _dptr(d_waypoint_updated), sp))
+
+    def download(self):
+        """(records (K,) MISSION_RECORD_DTYPE, agent distances (n_total,) float64); waits for the device."""
+        rec = np.zeros(self.n_missions, MISSION_RECORD_DTYPE)
+        dist = np.zeros(self.n_total, np.float64)
+        self._check(lib().lscqp_record_download(self._r, rec.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p)))
+        return rec, dist
+
+    def points(self):
+        """The sample points of the last step, float32 (n_total, n_samples, 3), copied to the host (waits for the device)."""
+        import torch
+
+        nb = C.c_uint64()
+        ptr = lib().lscqp_record_points(self._r, C.byref(nb))
+
+        class _View:
+            __cuda_array_interface__ = dict(shape=(nb.value // 4,), typestr="<f4", data=(ptr, False), version=2)
+
+        torch.cuda.synchronize()
+        return torch.as_tensor(_View(), device="cuda").cpu().numpy().reshape(self.n_total, self.n_samples, 3)
+
+    def unfinished(self):
+        w = C.c_int32()
+        self._check(lib().lscqp_record_unfinished(self._r, C.byref(w)))
+        return int(w.value)
+
+
 AGENT_PARAM_DTYPE = np.dtype([("radius", "f8"), ("downwash", "f8"), ("max_vel", "f8", 3), ("max_acc", "f8", 3), ("nominal_velocity", "f8")])
 
 
@@ -652,7 +757,7 @@ class Plan:
         self.n_agents, self.n_total, self.first_agent, self.n_obs, self.M, self.nv = n_agents, n_total, first_agent, n_obs, solver.desc.M, solver.nv
         self._dt = dict(self._DT)
         self._dt.update({PLAN_HEADER: HEADER_DTYPE, PLAN_ROWS: ROW_DTYPE, PLAN_SFC: BOX_DTYPE, PLAN_INFO: INFO_DTYPE, PLAN_SAFETY: SAFETY_DTYPE})
-        self.waypoint_mode, self.grid_resolution = int(waypoint_mode), float(grid_resolution)
+        self.waypoint_mode, self.grid_resolution, self._safety_samples = int(waypoint_mode), float(grid_resolution), int(safety_samples)
         if self.waypoint_mode == WAYPOINT_GRID_PIBT and float(grid_resolution) != 0.5:
             self._check(lib().lscqp_plan_set_grid(self._p, float(grid_resolution)))
         if mission_offsets is not None:
@@ -756,6 +861,30 @@ class Plan:
 
     def graph_nodes(self):
         return int(lib().lscqp_plan_graph_nodes(self._p))
+
+    def set_record(self, goal_threshold=0.1):
+        """lscqp_plan_set_record: the plan keeps a mission record, accumulated by the chain's last node (None: no record).  `reset` must follow."""
+        if goal_threshold is None:
+            self._check(lib().lscqp_plan_set_record(self._p, None))
+            return
+        d = RecordDesc(float(goal_threshold))
+        self._check(lib().lscqp_plan_set_record(self._p, C.byref(d)))
+
+    def record(self):
+        """The plan's own Record (owned by the plan), None without one."""
+        h = lib().lscqp_plan_record(self._p)
+        if not h:
+            return None
+        return Record(handle=C.c_void_p(h), n_total=self.n_total, n_samples=self._safety_samples, n_missions=len(self.missions()) - 1)
+
+    def run(self, max_replans, check_every=1, graph=True, stream=None):
+        """lscqp_plan_run: replans until every mission of the record has finished or max_replans; returns the replans enqueued."""
+        if getattr(self, "_solver", None) is not None:
+            self._solver._sync_knobs()
+        sp = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        n = C.c_int64()
+        self._check(lib().lscqp_plan_run(self._p, int(max_replans), int(check_every), int(bool(graph)), sp, C.byref(n)))
+        return int(n.value)
 
 
 def shard_range(n, n_used, g):

@@ -87,8 +87,16 @@ def build(force=False, verbose=False, jobs=None):
     post_o = os.path.join(OBJ, "lscpost.o")
     objs.append(post_o)
     post_src = os.path.join(CSRC, "lscpost.hip")
-    if force or _newer(post_o, hdrs + [post_src]):
+    traj_hdr = os.path.join(CSRC, "lscpost_traj.hpp")
+    if force or _newer(post_o, hdrs + [post_src, traj_hdr]):
         tasks.append([HIPCC] + FLAGS + ["-c", post_src, "-o", post_o])
+    # the mission record (csrc/lscrecord.hip).  -Rpass-analysis=kernel-resource-usage puts the kernel's registers, scratch and LDS into the
+    # build log (a verbose build prints it): the kernel is required to use no scratch
+    rec_o = os.path.join(OBJ, "lscrecord.o")
+    objs.append(rec_o)
+    rec_src = os.path.join(CSRC, "lscrecord.hip")
+    if force or _newer(rec_o, hdrs + [rec_src, traj_hdr]):
+        tasks.append([HIPCC] + FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", rec_src, "-o", rec_o])
     goal_o = os.path.join(OBJ, "lscgoal.o")
     objs.append(goal_o)
     goal_src = os.path.join(CSRC, "lscgoal.hip")

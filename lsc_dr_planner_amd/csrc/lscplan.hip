@@ -44,6 +44,10 @@ extern "C" int lscqp_generate_constraints_own_(lscqp_handle h, int32_t mode, int
                                                const double* d_traj, const double* d_own_traj, const int32_t* d_neighbours, const double* d_radius,
                                                const double* d_downwash, const double* d_goal_all, lscqp_row* d_rows_out, int32_t n_obs_total,
                                                int32_t slot0, void* stream);
+extern "C" int lscqp_record_create_(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
+                                    const int64_t* d_offsets_borrowed, int32_t n_samples, double record_time_step, double time_step, double z_2d,
+                                    const lscqp_record_desc* desc, lscqp_record* out);
+extern "C" int lscqp_record_unfinished_on_(lscqp_record r, void* stream, int32_t* unfinished_out);
 
 namespace lscplan {
 
@@ -231,6 +235,11 @@ struct lscqp_plan_s {
     int n_missions() const { return moff.empty() ? 1 : (int)moff.size() - 1; }
     // which form of the waypoint decision heads the chain (lscqp_plan_set_waypoint_decision)
     int decision = LSCQP_DECISION_ONE_WORKGROUP;
+    // a mission record (lscqp_plan_set_record): accumulated by the last node of the chain
+    bool rec_on = false;
+    lscqp_record_desc rec_desc = {0.0};
+    lscqp_record rec = nullptr;
+    bool record_pending = false;  // the record was set or its partition changed and lscqp_plan_reset has not come yet
     bool wide() const { return decision == LSCQP_DECISION_WIDE || (decision == LSCQP_DECISION_AUTO && s.n_total >= LSCQP_DECISION_AUTO_MIN_AGENTS); }
 };
 
@@ -292,6 +301,8 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     const double fraction = p->d.time_step / s.dt;
     const int K = p->n_missions();
     if (p->missions_pending) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_missions: lscqp_plan_reset must come before the next step");
+    if (p->rec_on && (p->record_pending || !p->rec))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: lscqp_plan_reset must come before the next step");
     // decentralizedMAPP precedes the planning loop (src/multi_sync_simulator.cpp:101-120): the waypoints of this replan, from the plans as the
     // last replan left them (AgentManager::getTraj is desired_traj, un-shifted)
     if (p->grid) {
@@ -362,6 +373,10 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     else if (p->d.safety_samples > 0)  // MultiSyncSimulator::update's safety ratio / excess ratios over the step just planned (:486-577)
         PLAN_TRY(lscqp_safety_metrics_device(h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan,
                                              p->radius, p->downwash, hdr, (lscqp_safety*)p->buf[LSCQP_PLAN_BUF_SAFETY], stream));
+    // the mission record: the figures of this replan and the finish test on the state it started from (hdr.p0), the chain's last node
+    if (p->rec_on)
+        PLAN_TRY(lscqp_record_step_device(p->rec, hdr, x_plan, status, goal_status, sfc_status, valid, count, (const lscqp_safety*)p->buf[LSCQP_PLAN_BUF_SAFETY],
+                                          (const int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
     // (closed loop: LSCQP_PLAN_BUF_NEXT_STATE is the local agents' slice of the state buffer itself, so doStep's result is the next
     // replan's current state without a copy)
     const hipError_t e = hipGetLastError();
@@ -415,6 +430,18 @@ int make_fields(lscqp_plan_s* p) {
     const hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "distance fields");
     p->fields_valid = true;
+    return LSCQP_OK;
+}
+
+// the plan's record for the partition in force (its offsets are the ones the partition already has on the device); the old one is dropped
+int make_record(lscqp_plan_s* p) {
+    lscqp_record rnew = nullptr;
+    const bool one = p->moff.empty();
+    PLAN_TRY(lscqp_record_create_(p->h, p->s.n_total, one ? 1 : p->n_missions(), one ? nullptr : p->moff.data(), one ? nullptr : p->d_moff,
+                                  p->d.safety_samples, p->d.record_time_step, p->d.time_step, p->s.z_2d, &p->rec_desc, &rnew));
+    drop_graph(p);  // (a captured chain holds the old record's buffers)
+    if (p->rec) lscqp_record_destroy(p->rec);
+    p->rec = rnew;
     return LSCQP_OK;
 }
 
@@ -635,6 +662,7 @@ void lscqp_plan_destroy(lscqp_plan p) {
     for (void* q : p->owned) (void)hipFree(q);
     if (p->grid) lscqp_grid_destroy(p->grid);
     if (p->field) (void)hipFree(p->field);
+    if (p->rec) lscqp_record_destroy(p->rec);
     if (p->d_moff) (void)hipFree(p->d_moff);
     if (p->own_hq) lscqp_destroy(p->hq);
     delete p;
@@ -643,6 +671,7 @@ void lscqp_plan_destroy(lscqp_plan p) {
 int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* goal_points) {
     if (!p || !start_positions) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
     if (p->grid && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: the mission's goal points are required");
+    if (p->rec_on && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: the mission's goal points are required (the desired goals of the finish test)");
     DeviceGuard g(p->device);
     const lscplan::Shape& s = p->s;
     const size_t nt = (size_t)s.n_total, P = (size_t)s.M * 6;
@@ -669,6 +698,14 @@ int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* 
     }
     if (e != hipSuccess) return hip_fail(e, "plan reset");
     if (p->grid) PLAN_TRY(make_fields(p));
+    if (p->rec_on) {  // the record of the partition in force, cleared; desired goals in the mission's plane like the states
+        if (!p->rec || p->record_pending || p->missions_pending) PLAN_TRY(make_record(p));
+        std::vector<double> want(nt * 3);
+        for (size_t a = 0; a < nt; a++)
+            for (int k = 0; k < 3; k++) want[a * 3 + k] = (k < s.dim) ? goal_points[a * 3 + k] : st[a * 9 + k];
+        PLAN_TRY(lscqp_record_reset(p->rec, want.data()));
+        p->record_pending = false;
+    }
     p->missions_pending = false;
     p->first = true;
     p->steps = 0;
@@ -790,6 +827,11 @@ int lscqp_plan_set_missions(lscqp_plan p, int32_t n_missions, const int64_t* mis
     drop_graph(p);  // (a captured chain holds the old partition's launches)
     p->fields_valid = false;
     p->missions_pending = true;
+    if (p->rec) {  // (the record was built for the old partition and reads its device offsets: made again at the reset)
+        lscqp_record_destroy(p->rec);
+        p->rec = nullptr;
+    }
+    p->record_pending = p->rec_on;
     return LSCQP_OK;
 }
 
@@ -829,6 +871,65 @@ int lscqp_plan_mission_status(lscqp_plan p, int32_t* status_out) {
     }
     DeviceGuard g(p->device);
     return K > 1 ? lscqp_grid_mission_status(p->grid, K, status_out) : lscqp_grid_status(p->grid, status_out);
+}
+
+int lscqp_plan_set_record(lscqp_plan p, const lscqp_record_desc* desc) {
+    if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
+    if (desc) {
+        if (p->d.safety_samples <= 0)
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: the record reads the safety figures of the chain (safety_samples > 0 required)");
+        if (p->s.n_agents != p->s.n_total)
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: the record needs every agent on this device (n_agents == n_total)");
+        if (!(desc->goal_threshold >= 0)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: goal_threshold must be >= 0");
+    }
+    DeviceGuard g(p->device);
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_record");
+    if (!desc) {
+        drop_graph(p);  // (a captured chain ends in the record's node)
+        if (p->rec) lscqp_record_destroy(p->rec);
+        p->rec = nullptr;
+        p->rec_on = p->record_pending = false;
+        return LSCQP_OK;
+    }
+    const lscqp_record_desc before = p->rec_desc;
+    p->rec_desc = *desc;
+    if (!p->missions_pending) {  // (otherwise the partition's device offsets are about to change: lscqp_plan_reset makes it)
+        const int rc = make_record(p);
+        if (rc != LSCQP_OK) {
+            p->rec_desc = before;
+            return rc;
+        }
+    }
+    drop_graph(p);
+    p->rec_on = p->record_pending = true;
+    return LSCQP_OK;
+}
+
+lscqp_record lscqp_plan_record(lscqp_plan p) { return p ? p->rec : nullptr; }
+
+int lscqp_plan_run(lscqp_plan p, int64_t max_replans, int32_t check_every, int32_t use_graph, void* stream, int64_t* replans_enqueued) {
+    if (replans_enqueued) *replans_enqueued = 0;
+    if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
+    if (!p->rec_on) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_run: the plan has no record (lscqp_plan_set_record): nothing tells when a mission is over");
+    if (!p->d.closed_loop || !p->grid)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
+                                "lscqp_plan_run: closed_loop != 0 and waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT required (nothing else flies without host writes between replans)");
+    if (max_replans < 1 || check_every < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_run: max_replans >= 1 and check_every >= 1 required");
+    int64_t done = 0;
+    while (done < max_replans) {
+        for (int32_t i = 0; i < check_every && done < max_replans; i++, done++) {
+            const int rc = use_graph ? lscqp_plan_step_graph(p, stream) : lscqp_plan_step(p, stream);
+            if (replans_enqueued) *replans_enqueued = done;
+            if (rc != LSCQP_OK) return rc;
+        }
+        if (replans_enqueued) *replans_enqueued = done;
+        int32_t left = 0;
+        DeviceGuard g(p->device);
+        PLAN_TRY(lscqp_record_unfinished_on_(p->rec, stream, &left));
+        if (left == 0) break;
+    }
+    return LSCQP_OK;
 }
 
 const lscqp_plan_desc* lscqp_plan_desc_of_(lscqp_plan p) { return &p->d; }  // (library-internal: lscqp_comm.hip)

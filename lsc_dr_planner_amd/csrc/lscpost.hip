@@ -16,28 +16,12 @@
 #include <string>
 
 #include "../../include/lscqp.h"
+#include "lscpost_traj.hpp"
 
 namespace lscpost {
 
 constexpr int kThreads = 64;
 constexpr double kEpsFloat = 1e-5;  // SP_EPSILON_FLOAT, Box::isPointInBox (src/collision_constraints.cpp:81-88)
-
-// sum_i cp[i] C(n,i) t^i (1-t)^(n-i)
-template <int N>
-__device__ __forceinline__ double bern(const double (&cp)[6], double t) {
-    constexpr int binom[6][6] = {{1, 0, 0, 0, 0, 0}, {1, 1, 0, 0, 0, 0}, {1, 2, 1, 0, 0, 0}, {1, 3, 3, 1, 0, 0}, {1, 4, 6, 4, 1, 0}, {1, 5, 10, 10, 5, 1}};
-    double s = 0, ti = 1;
-    double omt[6];
-    omt[0] = 1;
-#pragma unroll
-    for (int i = 1; i <= N; i++) omt[i] = omt[i - 1] * (1 - t);
-#pragma unroll
-    for (int i = 0; i <= N; i++) {
-        s += cp[i] * binom[N][i] * ti * omt[N - i];
-        ti *= t;
-    }
-    return s;
-}
 
 // one wavefront per agent: the lanes share the (segment, control point) pairs of the corridor test, lanes 0..2 evaluate one axis of the
 // state each (a lane per agent walked ~60 dependent loads: 19 us for 10 agents in the replan chain)
@@ -145,30 +129,6 @@ __device__ __forceinline__ double post_sqrt(double x) {  // sqrt(x), x >= 0: v_r
     g = fma(g, e, g);
     h = fma(h, e, h);
     return fma(fma(-g, g, x), h, g);  // final correction: g + (x - g^2) * h
-}
-
-// position (float32, as State holds it) of the trajectory xq at time t
-__device__ __forceinline__ void position_at(int M, int dim, double dt, double t, double z_2d, const double* xq, float (&pos)[3]) {
-    const int P = 6 * M;
-    int ms = -1;
-    double tn = 0, end = 0;
-    for (int idx = 0; idx < M; idx++) {  // getPointAt's segment search (src/trajectory.cpp:121-136)
-        end += dt;
-        if (t < end) {
-            ms = idx;
-            tn = 1 - (end - t) / dt;
-            break;
-        }
-    }
-    if (ms < 0) {
-        ms = M - 1;
-        tn = 1.0;
-    }
-    for (int k = 0; k < 3; k++) {
-        double c[6];
-        for (int i = 0; i < 6; i++) c[i] = (k < dim) ? (double)(float)xq[k * P + 6 * ms + i] : (double)(float)z_2d;
-        pos[k] = (float)bern<5>(c, tn);
-    }
 }
 
 // MIS: the agents (all of them local: first_agent = 0) are partitioned into missions off[0..K] (include/lscqp.h, "many missions over one

@@ -1,0 +1,407 @@
+// lscrecord.hip — the mission record (include/lscqp.h, "the mission record"), gfx950 only: the running figures of the reference's summary
+// line per mission, accumulated on the device at the end of each replan, and the test that tells when a mission is over.
+//   MultiSyncSimulator::isFinished          reference src/multi_sync_simulator.cpp:401-424
+//   MultiSyncSimulator::getTotalDistance    :711-720 (the polyline through the logged sample points)
+//   MultiSyncSimulator::update              :486-577 (minimum safety ratio, maximum excess ratios; per agent in lscpost.hip)
+//   saveSummarizedResultAsCSV               :658-709 (what becomes of the figures)
+// One workgroup per mission, its threads stride over the mission's agents: sample points, distance, and the partial figures of its agents,
+// then ONE reduction across the workgroup (DPP moves within a wavefront, LDS across the four wavefronts, combined in wavefront order).  Every
+// reduced figure is a sum of integers, a maximum, or a minimum whose ties go to the lowest agent id: the result does not depend on how the
+// agents fall onto lanes.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/lscqp.h"
+#include "lscpost_traj.hpp"
+
+extern "C" int lscqp_set_error_(int code, const char* msg);
+extern "C" const lscqp_class_desc* lscqp_class_desc_of_(lscqp_handle h);
+extern "C" int lscqp_check_missions_(int64_t n_total, int32_t n_missions, const int64_t* mission_offsets);
+
+namespace lscrecord {
+
+constexpr int kThreads = 256, kWaves = kThreads / 64;
+
+struct Args {
+    int M, dim, n_samples;
+    double dt, record_time_step, time_step, z_2d, goal_threshold;
+    int64_t n_total;
+    const int64_t* off;  // [K + 1] or NULL: one mission [0, n_total)
+    const lscqp_header* hdr;
+    const double* x_all;
+    const int32_t *status, *goal_status, *sfc_status, *valid, *in_range, *waypoint_updated;  // (waypoint_updated may be NULL)
+    const lscqp_safety* safety;
+    const float* goal;  // [n_total][3] desired goals, float32
+    float* points;      // [n_total][n_samples][3]
+    float* last;        // [n_total][3] the agent's last sample point of the previous replan
+    double* dist;       // [n_total]
+    lscqp_mission_record* rec;
+    int32_t* unfinished;
+};
+
+// what a lane, a wavefront and the workgroup hold of the mission's agents in one replan.  Scalar fields only, listed once: small arrays
+// indexed by loops stay in memory until the loops are unrolled, and by then the selects of `combine` have become selects of addresses
+// (scratch instead of registers).
+#define LSCREC_MAXIMA(X) X(vel_x) X(vel_y) X(vel_z) X(acc_x) X(acc_y) X(acc_z) /* excess ratios, never below 0 */
+#define LSCREC_COUNTS(X) X(qp_failed) X(invalid) X(goal_failed) X(sfc_kept) X(waypoint) X(truncated) X(far) /* far: agents beyond the threshold */
+struct Part {
+    double ratio;      // least safety ratio, +inf: none
+    int agent, other;  // ... the agent attaining it (lowest id on ties) and its closest agent; -1
+#define X(f) double f;
+    LSCREC_MAXIMA(X)
+#undef X
+#define X(f) int f;
+    LSCREC_COUNTS(X)
+#undef X
+    int max_in_range;
+};
+
+__device__ __forceinline__ Part empty_part() {
+    Part p;
+    p.ratio = INFINITY, p.agent = -1, p.other = -1;
+#define X(f) p.f = 0.0;
+    LSCREC_MAXIMA(X)
+#undef X
+#define X(f) p.f = 0;
+    LSCREC_COUNTS(X)
+#undef X
+    p.max_in_range = 0;
+    return p;
+}
+
+// (ids compare as unsigned: -1, "none", loses every tie)
+__device__ __forceinline__ void combine(Part& a, const Part& b) {
+    // (`if`, not `take ? b.f : a.f`: a conditional between two lvalues is a choice of ADDRESS, which keeps both structs in memory)
+    if (b.ratio < a.ratio || (b.ratio == a.ratio && (unsigned)b.agent < (unsigned)a.agent)) {
+        a.ratio = b.ratio;
+        a.agent = b.agent;
+        a.other = b.other;
+    }
+#define X(f) \
+    if (b.f > a.f) a.f = b.f;
+    LSCREC_MAXIMA(X)
+#undef X
+#define X(f) a.f += b.f;
+    LSCREC_COUNTS(X)
+#undef X
+    if (b.max_in_range > a.max_in_range) a.max_in_range = b.max_in_range;
+}
+
+// one DPP move of every field (lscqp_kernel.hpp: row_shr steps scan a row of 16 lanes, row_bcast:15 / :31 carry the rows' results across;
+// lanes without a source receive the identity) and the combination with it
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int dpp_i32(int idn, int v) {
+    return __builtin_amdgcn_update_dpp(idn, v, CTRL, ROW_MASK, 0xf, false);
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_f64(double idn, double v) {
+    const int lo = dpp_i32<CTRL, ROW_MASK>(__double2loint(idn), __double2loint(v));
+    const int hi = dpp_i32<CTRL, ROW_MASK>(__double2hiint(idn), __double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ void dpp_step(Part& p) {
+    Part q;
+    q.ratio = dpp_f64<CTRL, ROW_MASK>(INFINITY, p.ratio);
+    q.agent = dpp_i32<CTRL, ROW_MASK>(-1, p.agent);
+    q.other = dpp_i32<CTRL, ROW_MASK>(-1, p.other);
+#define X(f) q.f = dpp_f64<CTRL, ROW_MASK>(0.0, p.f);
+    LSCREC_MAXIMA(X)
+#undef X
+#define X(f) q.f = dpp_i32<CTRL, ROW_MASK>(0, p.f);
+    LSCREC_COUNTS(X)
+#undef X
+    q.max_in_range = dpp_i32<CTRL, ROW_MASK>(0, p.max_in_range);
+    combine(p, q);
+}
+// lane 63 ends up with the wavefront's figures
+__device__ __forceinline__ void wave_reduce(Part& p) {
+    dpp_step<0x111, 0xf>(p);  // row_shr:1
+    dpp_step<0x112, 0xf>(p);  // row_shr:2
+    dpp_step<0x114, 0xf>(p);  // row_shr:4
+    dpp_step<0x118, 0xf>(p);  // row_shr:8
+    dpp_step<0x142, 0xa>(p);  // row_bcast:15 into rows 1 and 3
+    dpp_step<0x143, 0xc>(p);  // row_bcast:31 into rows 2 and 3
+}
+
+// (a - b).norm() of octomath::Vector3: float differences, float sum of squares, the square root of that value in double
+__device__ __forceinline__ double norm_of_difference(const float (&a)[3], const float (&b)[3]) {
+#pragma clang fp contract(off)
+    const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+    const float nsq = dx * dx + dy * dy + dz * dz;
+    return sqrt((double)nsq);
+}
+
+__global__ __launch_bounds__(kThreads) void record_kernel(Args A) {
+    __shared__ Part s_part[kWaves];
+    const int k = blockIdx.x;
+    lscqp_mission_record* R = A.rec + k;
+    if (R->finished != 0) return;  // frozen (the whole workgroup: one word, the same for every lane)
+    const int r = R->replans;      // this replan's index
+    const int64_t lo = A.off ? A.off[k] : 0, hi = A.off ? A.off[k + 1] : A.n_total;
+    const int nv = A.dim * 6 * A.M;
+    Part p = empty_part();
+    for (int64_t a = lo + threadIdx.x; a < hi; a += kThreads) {
+        // sample points of the new plan, the polyline through them and the previous replan's last point
+        float prev[3] = {0, 0, 0};
+        if (r > 0) prev[0] = A.last[a * 3 + 0], prev[1] = A.last[a * 3 + 1], prev[2] = A.last[a * 3 + 2];
+        double d = A.dist[a];
+        float* pts = A.points + a * A.n_samples * 3;
+        for (int s = 0; s < A.n_samples; s++) {
+            float q[3];
+            lscpost::position_at(A.M, A.dim, A.dt, s * A.record_time_step, A.z_2d, A.x_all + a * nv, q);
+            pts[s * 3 + 0] = q[0], pts[s * 3 + 1] = q[1], pts[s * 3 + 2] = q[2];
+            if (r > 0 || s > 0) d += norm_of_difference(q, prev);
+            prev[0] = q[0], prev[1] = q[1], prev[2] = q[2];
+        }
+        A.dist[a] = d;
+        A.last[a * 3 + 0] = prev[0], A.last[a * 3 + 1] = prev[1], A.last[a * 3 + 2] = prev[2];
+        // the replan's figures of this agent (ascending ids within a lane: strict < keeps the lowest)
+        Part q = empty_part();
+        const lscqp_safety* S = A.safety + a;
+        const lscqp_header* H = A.hdr + a;
+        auto positive = [](double v) { return v > 0.0 ? v : 0.0; };
+        q.ratio = S->safety_ratio, q.agent = (int)a, q.other = S->closest_agent;
+        q.vel_x = positive(S->vel_excess_ratio[0]), q.vel_y = positive(S->vel_excess_ratio[1]), q.vel_z = positive(S->vel_excess_ratio[2]);
+        q.acc_x = positive(S->acc_excess_ratio[0]), q.acc_y = positive(S->acc_excess_ratio[1]), q.acc_z = positive(S->acc_excess_ratio[2]);
+        const int in_range = A.in_range[a];
+        q.qp_failed = A.status[a] != LSCQP_STATUS_OPTIMAL;
+        q.invalid = A.valid[a] == 0;
+        q.goal_failed = A.goal_status[a] != 0;
+        q.sfc_kept = A.sfc_status[a] == 0;
+        q.waypoint = A.waypoint_updated ? A.waypoint_updated[a] != 0 : 0;
+        q.truncated = in_range > H->n_obs;
+        q.max_in_range = in_range > 0 ? in_range : 0;
+        // isFinished: current_position.distance(desired_goal_point) > goal_threshold, on the state this replan started from
+        const float p0[3] = {(float)H->p0[0], (float)H->p0[1], (float)H->p0[2]};
+        const float g[3] = {A.goal[a * 3 + 0], A.goal[a * 3 + 1], A.goal[a * 3 + 2]};
+        q.far = norm_of_difference(p0, g) > A.goal_threshold;
+        combine(p, q);
+    }
+    wave_reduce(p);
+    if ((threadIdx.x & 63) == 63) s_part[threadIdx.x >> 6] = p;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    p = s_part[0];
+    for (int w = 1; w < kWaves; w++) combine(p, s_part[w]);
+    if (p.ratio < R->safety_ratio_agent) {  // strict <: an earlier replan keeps a tie
+        R->safety_ratio_agent = p.ratio;
+        R->safety_replan = r, R->safety_agent = p.agent, R->safety_other = p.other;
+    }
+    const double ex[6] = {p.vel_x, p.vel_y, p.vel_z, p.acc_x, p.acc_y, p.acc_z};
+    for (int i = 0; i < 3; i++) {
+        if (ex[i] > R->vel_excess_ratio[i]) R->vel_excess_ratio[i] = ex[i];
+        if (ex[3 + i] > R->acc_excess_ratio[i]) R->acc_excess_ratio[i] = ex[3 + i];
+    }
+    R->qp_failed += p.qp_failed;
+    if (p.qp_failed > 0 && R->first_qp_failed_replan < 0) R->first_qp_failed_replan = r;
+    R->invalid += p.invalid;
+    R->goal_failed += p.goal_failed;
+    R->sfc_kept += p.sfc_kept;
+    R->waypoint_updates += p.waypoint;
+    R->truncated += p.truncated;
+    if (p.max_in_range > R->max_in_range) R->max_in_range = p.max_in_range;
+    R->replans = r + 1;
+    if (p.far == 0) {
+        R->flight_time = r * A.time_step;
+        R->finished = 1;
+        __hip_atomic_fetch_sub(A.unfinished, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+}  // namespace lscrecord
+
+struct lscqp_record_s {
+    lscrecord::Args a;  // (the per-step pointers are filled by lscqp_record_step_device)
+    int K = 1;
+    int device = 0;
+    std::vector<int64_t> off;  // [K + 1]
+    int64_t* d_off = nullptr;  // own copy of the offsets, or NULL where the caller's device copy is borrowed
+    float *goal = nullptr, *points = nullptr, *last = nullptr;
+    double* dist = nullptr;
+    lscqp_mission_record* rec = nullptr;
+    int32_t* unfinished = nullptr;
+    int32_t* h_word = nullptr;  // pinned: where lscqp_plan_run's 4-byte copies land
+};
+
+namespace {
+
+int hip_fail(hipError_t e, const char* what) {
+    return lscqp_set_error_(LSCQP_ERR_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
+}
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+        else prev = -1;
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+}  // namespace
+
+// (library-internal, lscplan.hip) d_offsets_borrowed: the partition's offsets as the plan already has them on the device; NULL: an own copy
+extern "C" int lscqp_record_create_(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
+                                    const int64_t* d_offsets_borrowed, int32_t n_samples, double record_time_step, double time_step, double z_2d,
+                                    const lscqp_record_desc* desc, lscqp_record* out) {
+    if (!h || !desc || !out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_total <= 0 || n_total > 0x7fffffff) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_record_create: 0 < n_total < 2^31 required");
+    if (n_samples <= 0 || !(record_time_step > 0) || !(time_step > 0))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_record_create: n_samples > 0, record_time_step > 0 and time_step > 0 required");
+    if (!(desc->goal_threshold >= 0)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_record_create: goal_threshold must be >= 0");
+    const bool single = !mission_offsets;
+    if (!single) {
+        const int rc = lscqp_check_missions_(n_total, n_missions, mission_offsets);
+        if (rc != LSCQP_OK) return rc;
+    }
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return lscqp_set_error_(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+    lscqp_record_s* r = new lscqp_record_s();
+    memset(&r->a, 0, sizeof r->a);
+    r->device = dev;
+    r->K = single ? 1 : n_missions;
+    if (single) r->off = {0, n_total};
+    else r->off.assign(mission_offsets, mission_offsets + n_missions + 1);
+    const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
+    const int M = lscqp_num_segments(h);
+    r->a.M = M, r->a.dim = lscqp_num_variables(h) / (6 * M), r->a.n_samples = n_samples;
+    r->a.dt = cd->dt, r->a.record_time_step = record_time_step, r->a.time_step = time_step, r->a.z_2d = z_2d;
+    r->a.goal_threshold = desc->goal_threshold;
+    r->a.n_total = n_total;
+    const size_t nt = (size_t)n_total;
+    hipError_t e = hipSuccess;
+    if (!single && !d_offsets_borrowed) {
+        e = hipMalloc((void**)&r->d_off, (size_t)(n_missions + 1) * sizeof(int64_t));
+        if (e == hipSuccess) e = hipMemcpy(r->d_off, mission_offsets, (size_t)(n_missions + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMalloc((void**)&r->goal, nt * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&r->points, nt * (size_t)n_samples * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&r->last, nt * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&r->dist, nt * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r->rec, (size_t)r->K * sizeof(lscqp_mission_record));
+    if (e == hipSuccess) e = hipMalloc((void**)&r->unfinished, sizeof(int32_t));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&r->h_word, sizeof(int32_t), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        lscqp_record_destroy(r);
+        return hip_fail(e, "lscqp_record_create");
+    }
+    r->a.off = single ? nullptr : (d_offsets_borrowed ? d_offsets_borrowed : r->d_off);
+    r->a.goal = r->goal, r->a.points = r->points, r->a.last = r->last, r->a.dist = r->dist, r->a.rec = r->rec, r->a.unfinished = r->unfinished;
+    std::vector<double> zero(nt * 3, 0.0);
+    const int rc = lscqp_record_reset(r, zero.data());
+    if (rc != LSCQP_OK) {
+        lscqp_record_destroy(r);
+        return rc;
+    }
+    *out = r;
+    return LSCQP_OK;
+}
+
+extern "C" {
+
+int lscqp_record_create(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets, int32_t n_samples,
+                        double record_time_step, double time_step, double z_2d, const lscqp_record_desc* desc, lscqp_record* out) {
+    return lscqp_record_create_(h, n_total, n_missions, mission_offsets, nullptr, n_samples, record_time_step, time_step, z_2d, desc, out);
+}
+
+void lscqp_record_destroy(lscqp_record r) {
+    if (!r) return;
+    DeviceGuard g(r->device);
+    (void)hipDeviceSynchronize();
+    for (void* q : {(void*)r->d_off, (void*)r->goal, (void*)r->points, (void*)r->last, (void*)r->dist, (void*)r->rec, (void*)r->unfinished})
+        if (q) (void)hipFree(q);
+    if (r->h_word) (void)hipHostFree(r->h_word);
+    delete r;
+}
+
+int lscqp_record_reset(lscqp_record r, const double* goal_points) {
+    if (!r || !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    DeviceGuard g(r->device);
+    const size_t nt = (size_t)r->a.n_total;
+    std::vector<float> gl(nt * 3);
+    for (size_t i = 0; i < nt * 3; i++) gl[i] = (float)goal_points[i];
+    std::vector<lscqp_mission_record> rec((size_t)r->K);
+    for (lscqp_mission_record& m : rec) {
+        memset(&m, 0, sizeof m);
+        m.first_qp_failed_replan = -1;
+        m.flight_time = -1.0;
+        m.safety_ratio_agent = INFINITY;
+        m.safety_replan = m.safety_agent = m.safety_other = -1;
+    }
+    const int32_t K = r->K;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(r->goal, gl.data(), gl.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(r->rec, rec.data(), rec.size() * sizeof(lscqp_mission_record), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(r->unfinished, &K, sizeof K, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(r->dist, 0, nt * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(r->last, 0, nt * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(r->points, 0, nt * (size_t)r->a.n_samples * 3 * sizeof(float));
+    return e == hipSuccess ? LSCQP_OK : hip_fail(e, "lscqp_record_reset");
+}
+
+int lscqp_record_step_device(lscqp_record r, const lscqp_header* d_hdr, const double* d_x_all, const int32_t* d_status, const int32_t* d_goal_status,
+                             const int32_t* d_sfc_status, const int32_t* d_valid, const int32_t* d_in_range, const lscqp_safety* d_safety,
+                             const int32_t* d_waypoint_updated, void* stream) {
+    if (!r) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null record");
+    if (!d_hdr || !d_x_all || !d_status || !d_goal_status || !d_sfc_status || !d_valid || !d_in_range || !d_safety)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_record_step_device: null buffer (only d_waypoint_updated may be NULL)");
+    lscrecord::Args a = r->a;
+    a.hdr = d_hdr, a.x_all = d_x_all, a.status = d_status, a.goal_status = d_goal_status, a.sfc_status = d_sfc_status, a.valid = d_valid;
+    a.in_range = d_in_range, a.safety = d_safety, a.waypoint_updated = d_waypoint_updated;
+    hipLaunchKernelGGL(lscrecord::record_kernel, dim3((unsigned)r->K), dim3(lscrecord::kThreads), 0, (hipStream_t)stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "HIP launch failed (mission record)");
+    return LSCQP_OK;
+}
+
+int lscqp_record_download(lscqp_record r, lscqp_mission_record* out, double* agent_distance) {
+    if (!r || !out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    DeviceGuard g(r->device);
+    std::vector<double> dist((size_t)r->a.n_total);
+    hipError_t e = hipMemcpy(out, r->rec, (size_t)r->K * sizeof(lscqp_mission_record), hipMemcpyDeviceToHost);  // waits for the device
+    if (e == hipSuccess) e = hipMemcpy(dist.data(), r->dist, dist.size() * sizeof(double), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "lscqp_record_download");
+    for (int k = 0; k < r->K; k++) {  // the agents' distances in id order
+        double s = 0;
+        for (int64_t a = r->off[k]; a < r->off[k + 1]; a++) s += dist[(size_t)a];
+        out[k].distance = s;
+    }
+    if (agent_distance) memcpy(agent_distance, dist.data(), dist.size() * sizeof(double));
+    return LSCQP_OK;
+}
+
+void* lscqp_record_points(lscqp_record r, uint64_t* bytes_out) {
+    if (!r) {
+        lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null record");
+        return nullptr;
+    }
+    if (bytes_out) *bytes_out = (uint64_t)r->a.n_total * (uint64_t)r->a.n_samples * 3 * sizeof(float);
+    return r->points;
+}
+
+int lscqp_record_unfinished(lscqp_record r, int32_t* unfinished_out) {
+    if (!r || !unfinished_out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    DeviceGuard g(r->device);
+    const hipError_t e = hipMemcpy(unfinished_out, r->unfinished, sizeof(int32_t), hipMemcpyDeviceToHost);
+    return e == hipSuccess ? LSCQP_OK : hip_fail(e, "lscqp_record_unfinished");
+}
+
+// (library-internal, lscplan.hip: lscqp_plan_run) the unfinished word as `stream` leaves it, waited for
+int lscqp_record_unfinished_on_(lscqp_record r, void* stream, int32_t* unfinished_out) {
+    hipError_t e = hipMemcpyAsync(r->h_word, r->unfinished, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "lscqp_plan_run");
+    *unfinished_out = *r->h_word;
+    return LSCQP_OK;
+}
+
+}  // extern "C"

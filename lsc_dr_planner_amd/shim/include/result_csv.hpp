@@ -6,7 +6,8 @@
 // fields per agent, numbers in std::ostream's default formatting (6 significant digits).  Missions with obstacles (mission.on != 0)
 // carry "obs_id,t,px,py,pz,size" per obstacle behind the agents' columns (:603-610, :638-652): the obstacle MODELS are out of scope,
 // the six fields are plain numbers the caller hands in (ObstacleSample).  SimulationSummaryCsv is the one-line-per-mission summary of
-// saveSummarizedResultAsCSV (:658-709) with the reference's own column names.
+// saveSummarizedResultAsCSV (:658-709) with the reference's own column names; fillSummaryFromRecord takes its flight figures from a
+// mission record of the device library.
 #pragma once
 #include <cstddef>
 #include <fstream>
@@ -15,6 +16,8 @@
 #include <string>
 #include <stdexcept>
 #include <vector>
+
+#include <lscqp.h>
 
 #include "sp_const.hpp"
 #include "trajectory.hpp"
@@ -94,6 +97,17 @@ struct SimulationSummary {
     int world_dimension = 0, M = 0;
     double dt = 0;
 };
+
+// The fields of the summary line a mission record holds (include/lscqp.h, "the mission record"): total_flight_time (-1 while the mission
+// has not finished), total_flight_distance, safety_ratio_agent, and the excess ratios as the reference prints them -- the float norm() of
+// the three per-axis maxima (vel_excess_ratio.norm(), :685-686).  Everything else, safety_ratio_obs included, stays the caller's.
+inline void fillSummaryFromRecord(SimulationSummary& s, const lscqp_mission_record& r) {
+    s.total_flight_time = r.flight_time;
+    s.total_flight_distance = r.distance;
+    s.safety_ratio_agent = r.safety_ratio_agent;
+    s.vel_excess_ratio = point3d((float)r.vel_excess_ratio[0], (float)r.vel_excess_ratio[1], (float)r.vel_excess_ratio[2]).norm();
+    s.acc_excess_ratio = point3d((float)r.acc_excess_ratio[0], (float)r.acc_excess_ratio[1], (float)r.acc_excess_ratio[2]).norm();
+}
 
 class SimulationSummaryCsv {
 public:

@@ -5,6 +5,7 @@
                                   -> isSolValid / next state -> safety metrics ]
 
     python tools/closed_loop.py [--steps 40] [--world tests/golden/forest10_world.json]
+    python tools/closed_loop.py --missions 25 --until-finished [MAX]      (K seeded missions in one plan, flown to the finish on the device)
 
 The host keeps the per-agent headers and, with --router host (the default), picks each agent's next waypoint with a stand-in
 for the grid-based planner (8-connected shortest paths, no conflict handling between agents).  --router device replaces
@@ -119,9 +120,12 @@ def seeded_missions(world, occ, grid_min, missions, seed=0):
     return np.arange(missions + 1) * n, np.concatenate(starts), np.concatenate(goals)
 
 
-def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=0, graph=True):
+def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=0, graph=True, until_finished=None, check_every=16,
+                 goal_threshold=0.1):
     """`missions` seeded missions over one world flown by ONE lscqp_plan with a mission partition (include/lscqp.h, "many missions over one
-    map"): waypoint_mode 1, closed loop, one captured graph per replan.  The summary has the figures of `run` per mission."""
+    map"): waypoint_mode 1, closed loop, one captured graph per replan.  The summary has the figures of `run` per mission.
+    until_finished = MAX: the plan keeps a mission record (include/lscqp.h, "the mission record") and lscqp_plan_run flies it until every
+    mission has finished or MAX replans, with no download in between; per mission the summary then holds the device's record."""
     import torch
 
     from lsc_dr_planner_amd import api
@@ -139,6 +143,26 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     ag["radius"], ag["downwash"], ag["max_vel"], ag["max_acc"], ag["nominal_velocity"] = g["radius"], 2.0, 1.0, 2.0, 1.0
     plan = api.Plan(sol, wmap, N, n_obs, ag, constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, optimize_goal=True, closed_loop=True,
                     z_2d=float(g["z_2d"]), safety_samples=2, record_time_step=0.1, waypoint_mode=api.WAYPOINT_GRID_PIBT, mission_offsets=off)
+    if until_finished:
+        plan.set_record(goal_threshold)
+        plan.reset(starts, goals)
+        enqueued = plan.run(int(until_finished), check_every=check_every, graph=graph)
+        rec, _ = plan.record().download()
+        status = plan.mission_status()
+        per = [dict(mission=k, agents=n, finished=int(r["finished"]), replans=int(r["replans"]), flight_time_s=float(r["flight_time"]),
+                    flight_distance_m=float(r["distance"]), qp_failed=int(r["qp_failed"]), first_qp_failed_replan=int(r["first_qp_failed_replan"]),
+                    invalid=int(r["invalid"]), goal_failed=int(r["goal_failed"]), sfc_kept=int(r["sfc_kept"]), min_safety_ratio=float(r["safety_ratio_agent"]),
+                    safety_replan=int(r["safety_replan"]), safety_agents=[int(r["safety_agent"]), int(r["safety_other"])],
+                    max_vel_excess=float(np.linalg.norm(np.float32(r["vel_excess_ratio"]))), max_acc_excess=float(np.linalg.norm(np.float32(r["acc_excess_ratio"]))),
+                    waypoints_updated=int(r["waypoint_updates"]), max_in_range=int(r["max_in_range"]), truncated_agent_steps=int(r["truncated"]),
+                    walk_bound_reached=int(status[k])) for k, r in enumerate(rec)]
+        log = dict(until_finished=int(until_finished), check_every=check_every, goal_threshold=goal_threshold, replans_enqueued=enqueued, missions=missions,
+                   agents=N, row_slots=n_obs, router="device", sim_time_s=enqueued * dt, graph_nodes=plan.graph_nodes(),
+                   finished=sum(m["finished"] for m in per), qp_failed=sum(m["qp_failed"] for m in per), invalid=sum(m["invalid"] for m in per),
+                   min_safety_ratio=min(m["min_safety_ratio"] for m in per), per_mission=per)
+        plan.close()
+        wmap.close()
+        return log
     plan.reset(starts, goals)
     per = [dict(mission=k, agents=n, qp_failed=0, invalid=0, min_safety_ratio=np.inf, max_vel_excess=0.0, max_acc_excess=0.0, waypoints_updated=0,
                 truncated_agent_steps=0) for k in range(missions)]
@@ -170,20 +194,23 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
 
 
 def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None, router="host", missions=None,
-        decision="one"):
+        decision="one", until_finished=None):
     """script (optional): {"waypoint": (K, N, 3), "state": (K, N, 9)} -- replay of a recorded mission: replan k takes every agent's
     state and waypoint from the script instead of the loop's own step / router (the plans, goal points, corridors and neighbour sets are
     still the loop's own), and the result carries every replan's solution (`x`, (K, N, nv)) and goal point (`goal`, (K, N, 3)).
     router: "host" (GridRouter) or "device" (lscqp_waypoints_device over the previous plans, states and goal points).
     missions: K > 0 flies K seeded missions over the world in one lscqp_plan (run_missions) and reports per-mission figures.
     decision (router "device"): "one" (lscqp_waypoints_device), "wide" (lscqp_waypoints_wide_device) or "auto" (wide from
-    DECISION_AUTO_MIN_AGENTS agents on); the flight is the same whichever is chosen."""
+    DECISION_AUTO_MIN_AGENTS agents on); the flight is the same whichever is chosen.
+    until_finished (with missions): fly until every mission has finished, at most that many replans (run_missions)."""
     if router not in ("host", "device"):
         raise ValueError("router must be 'host' or 'device'")
     if decision not in ("one", "wide", "auto"):
         raise ValueError("decision must be 'one', 'wide' or 'auto'")
+    if until_finished and not missions:
+        raise ValueError("until_finished needs missions=K (one lscqp_plan with a mission record)")
     if missions:
-        return run_missions(world_json, int(missions), steps=steps, M=M, dt=dt, n_obs=n_obs)
+        return run_missions(world_json, int(missions), steps=steps, M=M, dt=dt, n_obs=n_obs, until_finished=until_finished)
     import torch
 
     from lsc_dr_planner_amd import api
@@ -380,9 +407,13 @@ if __name__ == "__main__":
     ap.add_argument("--obs", type=int, default=None, help="neighbour capacity per agent")
     ap.add_argument("--dump", default=None, help="npz path: inputs of the first replan with a failed QP")
     ap.add_argument("--missions", type=int, default=0, help="K > 0: K seeded missions over the world in ONE plan with a mission partition, figures per mission")
+    ap.add_argument("--until-finished", type=int, nargs="?", const=400, default=None, metavar="MAX",
+                    help="with --missions K: fly until every mission has finished (lscqp_plan_run over the plan's mission record), at most MAX replans (default 400); "
+                         "one record per mission")
     ap.add_argument("--decision", default="one", choices=("one", "wide", "auto"),
                     help="with --router device: the one-workgroup decision, lscqp_waypoints_wide_device, or wide from DECISION_AUTO_MIN_AGENTS agents on")
     ap.add_argument("--router", default="host", choices=("host", "device"), help="where the waypoints come from: the host stand-in or lscqp_waypoints_device")
     a = ap.parse_args()
     world = random_forest_world(a.forest) if a.forest > 0 else a.world
-    print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router, missions=a.missions, decision=a.decision)))
+    print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router, missions=a.missions, decision=a.decision,
+                         until_finished=a.until_finished)))
