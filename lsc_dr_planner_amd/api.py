@@ -6,6 +6,7 @@ calls.  It never computes anything and has NO CPU fallback: if liblscqp.so is mi
 """
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -103,6 +104,45 @@ class LscqpError(RuntimeError):
         self.code = code
 
 
+_SCALARS = {"void": None, "int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double}
+_STRUCTS = {"lscqp_class_desc": ClassDesc, "lscqp_work": Work, "SolvePlan": _Plan}  # the pointers that stay typed; every other one is void*
+
+
+def _prototypes():
+    """{name: (restype, argtypes)} of every `ret name(args);` of include/lscqp.h, and of the few library-internal entries that the wrappers
+    below call for the tests.  The prototypes of liblscqp.so are written down once, in those two headers; this reads them from there."""
+    texts = []
+    for path in (os.path.join(_HERE, "..", "include", "lscqp.h"), os.path.join(_HERE, "csrc", "lscqp_internal.hpp")):
+        if not os.path.exists(path):
+            raise ImportError("cannot read the prototypes of liblscqp.so: %s is missing" % os.path.abspath(path))
+        texts.append(re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(path).read(), flags=re.S))
+    handles = set(re.findall(r"typedef\s+struct\s+\w+\s*\*\s*(\w+)\s*;", texts[0]))  # typedef struct lscqp_solver* lscqp_handle;
+
+    def ctype(decl, named):
+        words = re.sub(r"\b(const|struct)\b|\*", " ", decl).split()
+        base, stars = words[0], decl.count("*")
+        if "[" in decl or len(words) > 1 + named:
+            raise ImportError("include/lscqp.h, csrc/lscqp_internal.hpp: cannot read the C type `%s`" % decl.strip())
+        if stars == 0 and (base in _SCALARS or base in handles):
+            return _SCALARS[base] if base in _SCALARS else C.c_void_p
+        if stars == 1 and base == "char":
+            return C.c_char_p
+        if stars == 1 and base in _STRUCTS:
+            return C.POINTER(_STRUCTS[base])
+        if stars == 1 and base in handles:
+            return C.POINTER(C.c_void_p)
+        if stars:
+            return C.c_void_p
+        raise ImportError("include/lscqp.h, csrc/lscqp_internal.hpp: no ctypes type for the C type `%s`" % decl.strip())
+
+    out = {}
+    for text, names in zip(texts, (r"lscqp_\w+", r"lscqp_optimize_goal_fin_device_|lscqp_commit_validate_raw_|lscqp_debug_\w+_")):
+        for ret, name, args in re.findall(r"^([\w ]+?[ *]+)(%s)\s*\(([^()]*)\)\s*;" % names, text, flags=re.M):
+            args = [] if args.strip() in ("", "void") else args.split(",")
+            out[name] = (ctype(ret, 0), [ctype(a, 1) for a in args])
+    return out
+
+
 _lib = None
 
 
@@ -120,230 +160,9 @@ def lib():
         import torch  # noqa: F401
 
         L = C.CDLL(LIB_PATH)
-        vp = C.c_void_p
-        L.lscqp_create.restype = C.c_int
-        L.lscqp_create.argtypes = [C.POINTER(ClassDesc), C.POINTER(vp)]
-        L.lscqp_update.restype = C.c_int
-        L.lscqp_update.argtypes = [vp, C.POINTER(ClassDesc)]
-        L.lscqp_destroy.restype = C.c_int
-        L.lscqp_destroy.argtypes = [vp]
-        L.lscqp_num_variables.restype = C.c_int
-        L.lscqp_num_variables.argtypes = [vp]
-        L.lscqp_num_inequalities.restype = C.c_int
-        L.lscqp_num_inequalities.argtypes = [vp, C.c_int32]
-        L.lscqp_algorithmic_bytes.restype = C.c_int64
-        L.lscqp_algorithmic_bytes.argtypes = [vp, C.c_int32]
-        L.lscqp_solve_batch.restype = C.c_int
-        L.lscqp_solve_batch.argtypes = [vp, C.c_int64] + [vp] * 9
-        L.lscqp_solve_batch_device.restype = C.c_int
-        L.lscqp_solve_batch_device.argtypes = [vp, C.c_int64, C.c_int32] + [vp] * 10
-        L.lscqp_solve_batch_device_ex.restype = C.c_int
-        L.lscqp_solve_batch_device_ex.argtypes = [vp, C.c_int64, C.c_int32] + [vp] * 9 + [C.c_int32, vp]
-        L.lscqp_solve_batch_device_ordered.restype = C.c_int
-        L.lscqp_solve_batch_device_ordered.argtypes = [vp, C.c_int64, C.c_int32] + [vp] * 9 + [C.c_int32, vp, vp]
-        L.lscqp_launch_capacity.restype = C.c_int64
-        L.lscqp_launch_capacity.argtypes = [vp, C.c_int64, C.c_int32]
-        L.lscqp_order_by_cost_device.restype = C.c_int
-        L.lscqp_order_by_cost_device.argtypes = [C.c_int64, vp, vp, vp]
-        L.lscqp_construct_sfc_device_ordered.restype = C.c_int
-        L.lscqp_construct_sfc_device_ordered.argtypes = [vp, vp, C.c_int32, C.c_int64] + [vp] * 7
-        L.lscqp_order_by_work_device.restype = C.c_int
-        L.lscqp_order_by_work_device.argtypes = [C.c_int64, vp, vp, vp]
-        L.lscqp_solve_batch_stream.restype = C.c_int
-        L.lscqp_solve_batch_stream.argtypes = [vp, C.c_int64] + [vp] * 10
-        for f in ("lscqp_num_segments", "lscqp_uses_sfc", "lscqp_row_bytes", "lscqp_max_obstacles"):
-            getattr(L, f).restype = C.c_int
-            getattr(L, f).argtypes = [vp]
-        L.lscqp_comm_create.restype = C.c_int
-        L.lscqp_comm_create.argtypes = [C.c_int32, vp, C.POINTER(vp)]
-        L.lscqp_comm_destroy.restype = None
-        L.lscqp_comm_destroy.argtypes = [vp]
-        L.lscqp_comm_size.restype = C.c_int32
-        L.lscqp_comm_size.argtypes = [vp]
-        L.lscqp_comm_device.restype = C.c_int32
-        L.lscqp_comm_device.argtypes = [vp, C.c_int32]
-        L.lscqp_comm_stream.restype = vp
-        L.lscqp_comm_stream.argtypes = [vp, C.c_int32]
-        L.lscqp_comm_backend.restype = C.c_char_p
-        L.lscqp_comm_backend.argtypes = [vp]
-        L.lscqp_comm_set_min_agents_per_device.restype = C.c_int
-        L.lscqp_comm_set_min_agents_per_device.argtypes = [vp, C.c_int64]
-        L.lscqp_comm_devices_for.restype = C.c_int32
-        L.lscqp_comm_devices_for.argtypes = [vp, C.c_int64]
-        L.lscqp_comm_devices_for_class.restype = C.c_int32
-        L.lscqp_comm_devices_for_class.argtypes = [vp, vp, C.c_int64, C.c_int32]
-        L.lscqp_device_fill.restype = C.c_int64
-        L.lscqp_device_fill.argtypes = [vp, C.c_int64, C.c_int32]
-        L.lscqp_comm_shard.restype = C.c_int
-        L.lscqp_comm_shard.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp]
-        L.lscqp_shard_range.restype = C.c_int
-        L.lscqp_shard_range.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp]
-        L.lscqp_exchange_schedule.restype = C.c_int
-        L.lscqp_exchange_schedule.argtypes = [C.c_int64, C.c_int32, vp, vp, C.c_int64, vp, C.c_int32, vp]
-        L.lscqp_exchange_schedule_padded.restype = C.c_int
-        L.lscqp_exchange_schedule_padded.argtypes = [C.c_int64, C.c_int32, vp, vp, C.c_int64, C.c_int64, vp, C.c_int32, vp]
-        L.lscqp_comm_synchronize.restype = C.c_int
-        L.lscqp_comm_synchronize.argtypes = [vp]
-        L.lscqp_solve_batch_sharded.restype = C.c_int
-        L.lscqp_solve_batch_sharded.argtypes = [vp, vp, C.c_int64] + [vp] * 10
-        L.lscqp_solve_batch_sharded_device.restype = C.c_int
-        L.lscqp_solve_batch_sharded_device.argtypes = [vp, vp, vp, C.c_int32] + [vp] * 9 + [C.c_int32]
-        L.lscqp_allgather.restype = C.c_int
-        L.lscqp_allgather.argtypes = [vp, vp, vp, C.c_int64]
-        L.lscqp_generate_lsc_device.restype = C.c_int
-        L.lscqp_generate_lsc_device.argtypes = [vp, C.c_int64, C.c_int32, C.c_int64] + [vp] * 7
-        L.lscqp_generate_constraints_device.restype = C.c_int
-        L.lscqp_generate_constraints_device.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32, C.c_int64] + [vp] * 7
-        L.lscqp_generate_constraints_device_ex.restype = C.c_int
-        L.lscqp_generate_constraints_device_ex.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32, C.c_int64] + [vp] * 6 + [C.c_int32, C.c_int32, vp]
-        L.lscqp_generate_lsc_obstacles_device.restype = C.c_int
-        L.lscqp_generate_lsc_obstacles_device.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64] + [vp] * 7 + [C.c_int32, C.c_int32, vp]
-        L.lscqp_shift_traj_partial_device.restype = C.c_int
-        L.lscqp_shift_traj_partial_device.argtypes = [vp, C.c_int64, C.c_double, C.c_double, vp, vp, vp]
-        L.lscqp_select_neighbours_device.restype = C.c_int
-        L.lscqp_select_neighbours_device.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_double, vp, vp, vp, vp]
-        L.lscqp_shift_traj_device.restype = C.c_int
-        L.lscqp_shift_traj_device.argtypes = [vp, C.c_int64, C.c_int32, C.c_double, vp, vp, vp]
-        L.lscqp_generate_lsc_bytes.restype = C.c_int64
-        L.lscqp_generate_lsc_bytes.argtypes = [vp, C.c_int64, C.c_int32, C.c_int64]
-        L.lscqp_optimize_goal_device.restype = C.c_int
-        L.lscqp_optimize_goal_device.argtypes = [vp, C.c_int64] + [vp] * 6
-        L.lscqp_optimize_goal.restype = C.c_int
-        L.lscqp_optimize_goal.argtypes = [vp, C.c_int64] + [vp] * 5
-        L.lscqp_safety_metrics_device.restype = C.c_int
-        L.lscqp_safety_metrics_device.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double] + [vp] * 6
-        L.lscqp_safety_obstacles_device.restype = C.c_int
-        L.lscqp_safety_obstacles_device.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, vp, vp, vp, C.c_int32, vp, vp, vp]
-        L.lscqp_map_create.restype = C.c_int
-        L.lscqp_map_create.argtypes = [vp, C.c_int64, vp, vp, C.c_double, C.c_double, C.POINTER(C.c_void_p)]
-        L.lscqp_map_create_from_csv.restype = C.c_int
-        L.lscqp_map_create_from_csv.argtypes = [C.c_char_p, vp, vp, C.c_double, C.c_double, C.POINTER(C.c_void_p)]
-        L.lscqp_map_destroy.restype = None
-        L.lscqp_map_destroy.argtypes = [vp]
-        L.lscqp_map_info.restype = C.c_int
-        L.lscqp_map_info.argtypes = [vp, vp, vp]
-        L.lscqp_map_download.restype = C.c_int
-        L.lscqp_map_download.argtypes = [vp, vp, vp]
-        L.lscqp_construct_sfc.restype = C.c_int
-        L.lscqp_construct_sfc.argtypes = [vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp]
-        L.lscqp_construct_sfc_device.restype = C.c_int
-        L.lscqp_construct_sfc_device.argtypes = [vp, vp, C.c_int32, C.c_int64] + [vp] * 5
-        L.lscqp_validate_step_device.restype = C.c_int
-        L.lscqp_validate_step_device.argtypes = [vp, C.c_int64, C.c_double, C.c_double] + [vp] * 6
-        # library-internal entries of the replan chain (csrc/lscplan.hip), wrapped for the tests like the lscqp_debug_*_ symbols below
-        L.lscqp_optimize_goal_fin_device_.restype = C.c_int
-        L.lscqp_optimize_goal_fin_device_.argtypes = [vp, C.c_int64] + [vp] * 5 + [C.c_double, vp]
-        L.lscqp_commit_validate_raw_.restype = C.c_int
-        L.lscqp_commit_validate_raw_.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int64, C.c_double, C.c_double] + [vp] * 10
-        L.lscqp_plan_create.restype = C.c_int
-        L.lscqp_plan_create.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_void_p)]
-        L.lscqp_plan_destroy.restype = None
-        L.lscqp_plan_destroy.argtypes = [vp]
-        L.lscqp_plan_reset.restype = C.c_int
-        L.lscqp_plan_reset.argtypes = [vp, vp, vp]
-        L.lscqp_plan_buffer.restype = C.c_void_p
-        L.lscqp_plan_buffer.argtypes = [vp, C.c_int32, vp]
-        L.lscqp_plan_upload.restype = C.c_int
-        L.lscqp_plan_upload.argtypes = [vp, C.c_int32, vp, C.c_uint64, C.c_uint64]
-        L.lscqp_plan_download.restype = C.c_int
-        L.lscqp_plan_download.argtypes = [vp, C.c_int32, vp, C.c_uint64, C.c_uint64]
-        L.lscqp_plan_step.restype = C.c_int
-        L.lscqp_plan_step.argtypes = [vp, vp]
-        L.lscqp_plan_step_graph.restype = C.c_int
-        L.lscqp_plan_step_graph.argtypes = [vp, vp]
-        L.lscqp_plan_graph_nodes.restype = C.c_int64
-        L.lscqp_plan_graph_nodes.argtypes = [vp]
-        L.lscqp_plan_group_step.restype = C.c_int
-        L.lscqp_plan_group_step.argtypes = [vp, vp, C.c_int32]
-        L.lscqp_plan_set_grid.restype = C.c_int
-        L.lscqp_plan_set_grid.argtypes = [vp, C.c_double]
-        L.lscqp_plan_grid.restype = C.c_void_p
-        L.lscqp_plan_grid.argtypes = [vp]
-        L.lscqp_grid_shape.restype = C.c_int
-        L.lscqp_grid_shape.argtypes = [vp, vp, C.c_double, C.c_int32, C.c_double, vp, vp]
-        L.lscqp_grid_create.restype = C.c_int
-        L.lscqp_grid_create.argtypes = [vp, vp, C.POINTER(C.c_void_p)]
-        L.lscqp_grid_destroy.restype = None
-        L.lscqp_grid_destroy.argtypes = [vp]
-        for name in ("lscqp_grid_info", "lscqp_grid_download", "lscqp_grid_download_mission", "lscqp_grid_status"):
-            getattr(L, name).restype = C.c_int
-        L.lscqp_grid_info.argtypes = [vp, vp, vp]
-        L.lscqp_grid_download.argtypes = [vp, vp]
-        L.lscqp_grid_download_mission.argtypes = [vp, vp]
-        L.lscqp_grid_status.argtypes = [vp, vp]
-        L.lscqp_grid_reserve.restype = C.c_int
-        L.lscqp_grid_reserve.argtypes = [vp, C.c_int64]
-        L.lscqp_grid_fields_device.restype = C.c_int
-        L.lscqp_grid_fields_device.argtypes = [vp, C.c_int64] + [vp] * 5
-        L.lscqp_waypoints_device.restype = C.c_int
-        L.lscqp_waypoints_device.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_int64] + [vp] * 10
-        i64, i32 = C.c_int64, C.c_int32
-        L.lscqp_grid_reserve_wide.restype = C.c_int
-        L.lscqp_grid_reserve_wide.argtypes = [vp, C.c_int64]
-        L.lscqp_waypoints_wide_device.restype = C.c_int
-        L.lscqp_waypoints_wide_device.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_int64] + [vp] * 10
-        L.lscqp_plan_set_waypoint_decision.restype = C.c_int
-        L.lscqp_plan_set_waypoint_decision.argtypes = [vp, C.c_int32]
-        L.lscqp_plan_set_missions.restype = C.c_int
-        L.lscqp_plan_set_missions.argtypes = [vp, i32, vp]
-        L.lscqp_plan_missions.restype = C.c_int
-        L.lscqp_plan_missions.argtypes = [vp, vp, vp]
-        L.lscqp_plan_mission_status.restype = C.c_int
-        L.lscqp_plan_mission_status.argtypes = [vp, vp]
-        L.lscqp_select_neighbours_missions_device.restype = C.c_int
-        L.lscqp_select_neighbours_missions_device.argtypes = [vp, i64, i32, vp, vp, i32, C.c_double, vp, vp, vp, vp]
-        L.lscqp_safety_metrics_missions_device.restype = C.c_int
-        L.lscqp_safety_metrics_missions_device.argtypes = [vp, i64, i32, vp, vp, i32, C.c_double, C.c_double] + [vp] * 6
-        L.lscqp_grid_fields_missions_device.restype = C.c_int
-        L.lscqp_grid_fields_missions_device.argtypes = [vp, i64, i32, vp, vp] + [vp] * 5
-        L.lscqp_waypoints_missions_device.restype = C.c_int
-        L.lscqp_waypoints_missions_device.argtypes = [vp, C.c_double, i32, i32, i64, i32, vp, vp] + [vp] * 10
-        L.lscqp_grid_mission_status.restype = C.c_int
-        L.lscqp_grid_mission_status.argtypes = [vp, i32, vp]
-        L.lscqp_record_create.restype = C.c_int
-        L.lscqp_record_create.argtypes = [vp, i64, i32, vp, i32, C.c_double, C.c_double, C.c_double, vp, C.POINTER(C.c_void_p)]
-        L.lscqp_record_destroy.restype = None
-        L.lscqp_record_destroy.argtypes = [vp]
-        L.lscqp_record_reset.restype = C.c_int
-        L.lscqp_record_reset.argtypes = [vp, vp]
-        L.lscqp_record_step_device.restype = C.c_int
-        L.lscqp_record_step_device.argtypes = [vp] * 11
-        L.lscqp_record_download.restype = C.c_int
-        L.lscqp_record_download.argtypes = [vp, vp, vp]
-        L.lscqp_record_points.restype = C.c_void_p
-        L.lscqp_record_points.argtypes = [vp, vp]
-        L.lscqp_record_unfinished.restype = C.c_int
-        L.lscqp_record_unfinished.argtypes = [vp, vp]
-        L.lscqp_plan_set_record.restype = C.c_int
-        L.lscqp_plan_set_record.argtypes = [vp, vp]
-        L.lscqp_plan_record.restype = C.c_void_p
-        L.lscqp_plan_record.argtypes = [vp]
-        L.lscqp_plan_run.restype = C.c_int
-        L.lscqp_plan_run.argtypes = [vp, i64, i32, i32, vp, vp]
-        L.lscqp_last_error.restype = C.c_char_p
-        L.lscqp_version.restype = C.c_char_p
-        L.lscqp_instance_work.restype = C.c_int
-        L.lscqp_instance_work.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(Work)]
-        L.lscqp_diagnose.restype = C.c_int
-        L.lscqp_diagnose.argtypes = [vp, C.c_int64] + [vp] * 5 + [C.c_double, vp]
-        L.lscqp_diagnose_device.restype = C.c_int
-        L.lscqp_diagnose_device.argtypes = [vp, C.c_int64] + [vp] * 5 + [C.c_double, vp, vp]
-        L.lscqp_dump_instance.restype = C.c_int
-        L.lscqp_dump_instance.argtypes = [vp, vp, vp, vp, C.c_char_p]
-        L.lscqp_row_family_name.restype = C.c_char_p
-        L.lscqp_row_family_name.argtypes = [C.c_int32]
-        if hasattr(L, "lscqp_set_prescreen"):  # (LSCQP_LIB may name an A/B build that predates the prescreen: tools/prescreen_timing.py)
-            L.lscqp_prescreen_batch_device.restype = C.c_int
-            L.lscqp_prescreen_batch_device.argtypes = [vp, C.c_int64, C.c_int32] + [vp] * 6
-            L.lscqp_set_prescreen.restype = C.c_int
-            L.lscqp_set_prescreen.argtypes = [vp, C.c_int32]
-            L.lscqp_prescreen.restype = C.c_int
-            L.lscqp_prescreen.argtypes = [vp]
-            L.lscqp_debug_prescreen_twin_.restype = C.c_int
-            L.lscqp_debug_prescreen_twin_.argtypes = [vp, C.c_int64, C.c_int32] + [vp] * 5
-        if hasattr(L, "lscqp_debug_solve_plan_"):  # (an A/B build may predate the solve plan: tools/solve_plan_ab.py)
-            L.lscqp_debug_solve_plan_.restype = C.c_int
-            L.lscqp_debug_solve_plan_.argtypes = [vp, C.c_int64, C.c_int32] + [C.c_int32] * 7 + [C.POINTER(_Plan)]
+        for name, (restype, argtypes) in _prototypes().items():
+            if hasattr(L, name):  # (LSCQP_LIB may name an A/B build that predates an entry: tools/prescreen_timing.py, tools/solve_plan_ab.py)
+                getattr(L, name).restype, getattr(L, name).argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -421,8 +240,6 @@ class WorldMap:
 
     def prepare(self, max_radius):
         """lscqp_map_prepare: the free-space table that lets the corridor kernel pass tests in open space without sampling."""
-        lib().lscqp_map_prepare.restype = C.c_int
-        lib().lscqp_map_prepare.argtypes = [C.c_void_p, C.c_double]
         rc = lib().lscqp_map_prepare(self._h, float(max_radius))
         if rc != OK:
             raise LscqpError(rc, lib().lscqp_last_error().decode())

@@ -50,134 +50,102 @@ def _run(cmd):
     return r.stderr
 
 
-def build(force=False, verbose=False, jobs=None):
-    os.makedirs(OBJ, exist_ok=True)
-    hdrs = [os.path.join(CSRC, f) for f in ("lscqp_kernel.hpp", "lscqp_launch.hpp", "lscqp_staging.hpp", "lscqp_missions.hpp")] + [
-        os.path.join(HERE, "..", "include", "lscqp.h"), os.path.abspath(__file__)]
-    tasks = []
-    objs = []
+def _workers(jobs):
+    # (a GPU machine shows hundreds of CPUs and allows a command 16)
+    return jobs or int(os.environ.get("MAX_JOBS") or 0) or min(os.cpu_count() or 4, 16)
+
+
+def _env(name):
+    return os.environ.get(name, "").split() if name else []
+
+
+def units():
+    """Every translation unit: (source, object name, extra flags, LSCQP_EXTRA_* variable or None, has a _sync twin), in link order."""
+    rows = []
     for (M, D, E, S, W, X) in instances():
-        o = os.path.join(OBJ, "inst_%d_%d_%d_%d_%d_%d.o" % (M, D, E, S, W, X))
-        objs.append(o)
-        src = os.path.join(CSRC, "lscqp_inst.hip")
-        if force or _newer(o, hdrs + [src]):
-            extra = os.environ.get("LSCQP_EXTRA_MIXED_FLAGS", "").split() if X else os.environ.get("LSCQP_EXTRA_F64_FLAGS", "").split()
-            tasks.append([HIPCC] + FLAGS + extra + ["-DLSCQP_M=%d" % M, "-DLSCQP_DIM=%d" % D, "-DLSCQP_ES=%d" % E, "-DLSCQP_NSLOT=%d" % S, "-DLSCQP_W=%d" % W, "-DLSCQP_MIXED=%d" % X, "-c", src, "-o", o])
+        rows.append(("lscqp_inst.hip", "inst_%d_%d_%d_%d_%d_%d" % (M, D, E, S, W, X),
+                     ["-DLSCQP_M=%d" % M, "-DLSCQP_DIM=%d" % D, "-DLSCQP_ES=%d" % E, "-DLSCQP_NSLOT=%d" % S, "-DLSCQP_W=%d" % W, "-DLSCQP_MIXED=%d" % X],
+                     "LSCQP_EXTRA_MIXED_FLAGS" if X else "LSCQP_EXTRA_F64_FLAGS", False))
     # the fused forms (csrc/lscqp_fused.hip): phase + first interior-point pass in one launch; built like the instances (the phase's half keeps
     # its own fp contraction through lscqp_das.hpp's pragma), and a second time from the race test's twin of the phase for liblscqp_sync.so
-    das_hdr = [os.path.join(CSRC, "lscqp_das.hpp"), os.path.join(CSRC, "lscqp_das_body.inc")]
-    fused_src = os.path.join(CSRC, "lscqp_fused.hip")
-    fused_pairs = []  # (product object, twin object)
     for (M, D, E, S, W) in fused_instances():
-        defs = ["-DLSCQP_M=%d" % M, "-DLSCQP_DIM=%d" % D, "-DLSCQP_ES=%d" % E, "-DLSCQP_NSLOT=%d" % S, "-DLSCQP_W=%d" % W]
-        fo = os.path.join(OBJ, "fused_%d_%d_%d_%d_%d.o" % (M, D, E, S, W))
-        fs = os.path.join(OBJ, "fused_%d_%d_%d_%d_%d_sync.o" % (M, D, E, S, W))
-        fused_pairs.append((fo, fs))
-        objs.append(fo)
-        extra = os.environ.get("LSCQP_EXTRA_F64_FLAGS", "").split()
-        if force or _newer(fo, hdrs + das_hdr + [fused_src]):
-            tasks.append([HIPCC] + FLAGS + extra + defs + ["-c", fused_src, "-o", fo])
-        if force or _newer(fs, hdrs + das_hdr + [fused_src]):
-            tasks.append([HIPCC] + FLAGS + extra + defs + ["-DLSCQP_DAS_FULL_SYNC", "-c", fused_src, "-o", fs])
-    api_o = os.path.join(OBJ, "api.o")
-    objs.append(api_o)
-    api_src = os.path.join(CSRC, "lscqp_api.hip")
-    if force or _newer(api_o, hdrs + [api_src, os.path.join(CSRC, "lscqp_solve_plan.hpp")]):
-        tasks.append([HIPCC] + FLAGS + os.environ.get("LSCQP_EXTRA_F64_FLAGS", "").split() + ["-c", api_src, "-o", api_o])
-    post_o = os.path.join(OBJ, "lscpost.o")
-    objs.append(post_o)
-    post_src = os.path.join(CSRC, "lscpost.hip")
-    traj_hdr = os.path.join(CSRC, "lscpost_traj.hpp")
-    if force or _newer(post_o, hdrs + [post_src, traj_hdr]):
-        tasks.append([HIPCC] + FLAGS + ["-c", post_src, "-o", post_o])
-    # the mission record (csrc/lscrecord.hip).  -Rpass-analysis=kernel-resource-usage puts the kernel's registers, scratch and LDS into the
-    # build log (a verbose build prints it): the kernel is required to use no scratch
-    rec_o = os.path.join(OBJ, "lscrecord.o")
-    objs.append(rec_o)
-    rec_src = os.path.join(CSRC, "lscrecord.hip")
-    if force or _newer(rec_o, hdrs + [rec_src, traj_hdr]):
-        tasks.append([HIPCC] + FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", rec_src, "-o", rec_o])
-    goal_o = os.path.join(OBJ, "lscgoal.o")
-    objs.append(goal_o)
-    goal_src = os.path.join(CSRC, "lscgoal.hip")
-    if force or _newer(goal_o, hdrs + [goal_src]):
-        tasks.append([HIPCC] + FLAGS + ["-c", goal_src, "-o", goal_o])
-    sfc_o = os.path.join(OBJ, "lscsfc.o")
-    objs.append(sfc_o)
-    sfc_src = os.path.join(CSRC, "lscsfc.hip")
-    if force or _newer(sfc_o, hdrs + [sfc_src]):
-        tasks.append([HIPCC] + FLAGS + ["-c", sfc_src, "-o", sfc_o])
-    sfct_o = os.path.join(OBJ, "lscsfc_tp.o")
-    objs.append(sfct_o)
-    sfct_src = os.path.join(CSRC, "lscsfc_tp.hip")
-    if force or _newer(sfct_o, hdrs + [sfct_src, sfc_src]):
-        tasks.append([HIPCC] + FLAGS + ["-c", sfct_src, "-o", sfct_o])
-    comm_o = os.path.join(OBJ, "lscqp_comm.o")
-    objs.append(comm_o)
-    comm_src = os.path.join(CSRC, "lscqp_comm.hip")
-    if force or _newer(comm_o, hdrs + [comm_src]):
-        tasks.append([HIPCC] + FLAGS + ["-c", comm_src, "-o", comm_o])
-    plan_o = os.path.join(OBJ, "lscplan.o")
-    objs.append(plan_o)
-    plan_src = os.path.join(CSRC, "lscplan.hip")
-    if force or _newer(plan_o, hdrs + [plan_src]):
-        tasks.append([HIPCC] + FLAGS + ["-c", plan_src, "-o", plan_o])
-    grid_o = os.path.join(OBJ, "lscgrid.o")
-    objs.append(grid_o)
-    grid_src = os.path.join(CSRC, "lscgrid.hip")
-    if force or _newer(grid_o, hdrs + [grid_src]):
-        tasks.append([HIPCC] + FLAGS + ["-c", grid_src, "-o", grid_o])
-    gen_o = os.path.join(OBJ, "lscgen.o")
-    objs.append(gen_o)
-    gen_src = os.path.join(CSRC, "lscgen.hip")
-    if force or _newer(gen_o, hdrs + [gen_src]):
-        tasks.append([HIPCC] + FLAGS + ["-c", gen_src, "-o", gen_o])
-    gen_o = os.path.join(OBJ, "lscqp_generic.o")
-    objs.append(gen_o)
-    gen_src = os.path.join(CSRC, "lscqp_generic.hip")
-    if force or _newer(gen_o, hdrs + [gen_src]):
-        tasks.append([HIPCC] + FLAGS + ["-c", gen_src, "-o", gen_o])
-    das_o = os.path.join(OBJ, "lscqp_das.o")
-    objs.append(das_o)
-    das_src = os.path.join(CSRC, "lscqp_das.hip")
-    if force or _newer(das_o, hdrs + das_hdr + [das_src]):
+        rows.append(("lscqp_fused.hip", "fused_%d_%d_%d_%d_%d" % (M, D, E, S, W),
+                     ["-DLSCQP_M=%d" % M, "-DLSCQP_DIM=%d" % D, "-DLSCQP_ES=%d" % E, "-DLSCQP_NSLOT=%d" % S, "-DLSCQP_W=%d" % W], "LSCQP_EXTRA_F64_FLAGS", True))
+    rows += [
+        ("lscqp_api.hip", "api", [], "LSCQP_EXTRA_F64_FLAGS", False),
+        ("lscpost.hip", "lscpost", [], None, False),
+        # the mission record.  -Rpass-analysis=kernel-resource-usage puts the kernel's registers, scratch and LDS into the build log (a verbose
+        # build prints it): the kernel is required to use no scratch
+        ("lscrecord.hip", "lscrecord", ["-Rpass-analysis=kernel-resource-usage"], None, False),
+        ("lscgoal.hip", "lscgoal", [], None, False),
+        ("lscsfc.hip", "lscsfc", [], None, False),
+        ("lscsfc_tp.hip", "lscsfc_tp", [], None, False),
+        ("lscqp_comm.hip", "lscqp_comm", [], None, False),
+        ("lscplan.hip", "lscplan", [], None, False),
+        ("lscgrid.hip", "lscgrid", [], None, False),
+        ("lscgen.hip", "lscgen", [], None, False),
+        ("lscqp_generic.hip", "lscqp_generic", [], None, False),
         # -ffp-contract=on: a multiply-add is fused where the SOURCE writes a * b + c in one expression and nowhere else.  The default (fast) lets
         # the backend fuse across statements as the surrounding code happens to allow -- the kernel's instantiations (row formats, wavefronts
-        # per QP, launch forms) then differ in the last bit, and the phase's results are required to be identical across all of them
-        tasks.append([HIPCC] + FLAGS + ["-ffp-contract=on", "-c", das_src, "-o", das_o])
-    # the race test's twin of the dual active-set kernel (csrc/lscqp_das.hip: LSCQP_DAS_FULL_SYNC) -> liblscqp_sync.so, linked below from the
-    # product's own objects with this one in place of lscqp_das.o (tests/test_race_twin.py)
-    das_sync_o = os.path.join(OBJ, "lscqp_das_sync.o")
-    if force or _newer(das_sync_o, hdrs + das_hdr + [das_src]):
-        tasks.append([HIPCC] + FLAGS + ["-ffp-contract=on", "-DLSCQP_DAS_FULL_SYNC", "-c", das_src, "-o", das_sync_o])
-    pre_o = os.path.join(OBJ, "lscqp_prescreen.o")
-    objs.append(pre_o)
-    pre_src = os.path.join(CSRC, "lscqp_prescreen.hip")
-    if force or _newer(pre_o, hdrs + [pre_src]):
+        # per QP, launch forms) then differ in the last bit, and the phase's results are required to be identical across all of them.
+        # Its twin (LSCQP_DAS_FULL_SYNC) goes into liblscqp_sync.so in its place, beside the product's own objects (tests/test_race_twin.py)
+        ("lscqp_das.hip", "lscqp_das", ["-ffp-contract=on"], None, True),
         # (-ffp-contract=on as the phase: the row formats' instantiations and the host twin then round alike wherever the source writes one expression)
-        tasks.append([HIPCC] + FLAGS + ["-ffp-contract=on", "-c", pre_src, "-o", pre_o])
-    diag_o = os.path.join(OBJ, "lscqp_diag.o")
-    objs.append(diag_o)
-    diag_src = os.path.join(CSRC, "lscqp_diag.hip")
-    if force or _newer(diag_o, hdrs + [diag_src]):
-        tasks.append([HIPCC] + FLAGS + ["-c", diag_src, "-o", diag_o])
+        ("lscqp_prescreen.hip", "lscqp_prescreen", ["-ffp-contract=on"], None, False),
+        ("lscqp_diag.hip", "lscqp_diag", [], None, False),
+    ]
+    return rows
+
+
+def _stale(o, mtime):
+    """Dependencies come from the compiler (-MD -MF <obj>.d): an object is stale when it or its depfile is missing, or this file or any
+    file the depfile names is newer (a named file that is gone counts as newer)."""
+    d = o + ".d"
+    if not os.path.exists(o) or not os.path.exists(d):
+        return True
+    deps = open(d).read().replace("\\\n", " ").split(":", 1)[1].split()
+    t = os.path.getmtime(o)
+    return any(mtime(p) > t for p in deps + [os.path.abspath(__file__)])
+
+
+def commands(force=False):
+    """The (object, command line) pairs build() would run, in its order; nothing is run."""
+    seen = {}
+
+    def mtime(p):
+        if p not in seen:
+            seen[p] = os.path.getmtime(p) if os.path.exists(p) else float("inf")
+        return seen[p]
+
+    out = []
+    for src, name, flags, env, twin in units():
+        for suffix, more in (("", []), ("_sync", ["-DLSCQP_DAS_FULL_SYNC"]))[:2 if twin else 1]:
+            o = os.path.join(OBJ, name + suffix + ".o")
+            if force or _stale(o, mtime):
+                out.append((o, [HIPCC] + FLAGS + _env(env) + flags + more + ["-MD", "-MF", o + ".d", "-c", os.path.join(CSRC, src), "-o", o]))
+    return out
+
+
+def build(force=False, verbose=False, jobs=None):
+    os.makedirs(OBJ, exist_ok=True)
+    tasks = commands(force)
     if tasks:
-        with ThreadPoolExecutor(max_workers=jobs or os.cpu_count() or 4) as ex:
-            for msg in ex.map(_run, tasks):
+        with ThreadPoolExecutor(max_workers=_workers(jobs)) as ex:
+            for msg in ex.map(_run, [cmd for _, cmd in tasks]):
                 if verbose and msg:
                     sys.stderr.write(msg)
+    objs = [os.path.join(OBJ, name + ".o") for _, name, _, _, _ in units()]
+    twin = {os.path.join(OBJ, name + ".o"): os.path.join(OBJ, name + "_sync.o") for _, name, _, _, has_twin in units() if has_twin}
     # work counters of every instance, read off its machine code (isa_work.py) -> one small generated host TU
     work_o = os.path.join(OBJ, "lscqp_work_table.o")
-    objs.append(work_o)
     inst_objs = [o for o in objs if os.path.basename(o).startswith("inst_")]
+    objs.append(work_o)
     if force or _newer(work_o, inst_objs + [os.path.join(HERE, "isa_work.py"), os.path.abspath(__file__)]):
         _work_table(inst_objs, work_o, jobs)
         tasks.append("work table")
     if tasks or not os.path.exists(LIB):
         _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl", "-lpthread"])
     if tasks or not os.path.exists(SYNC_LIB):
-        twin = dict(fused_pairs)
-        twin[das_o] = das_sync_o
         _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SYNC_LIB] + [twin.get(o, o) for o in objs] + ["-ldl", "-lpthread"])
     return LIB
 
@@ -205,7 +173,7 @@ def _work_table(inst_objs, work_o, jobs=None):
             sys.stderr.write("build.py: warning: no work counters for %s (%s: %s)\n" % (os.path.basename(o), type(ex).__name__, str(ex)[:200]))
             return None
 
-    with ThreadPoolExecutor(max_workers=jobs or os.cpu_count() or 4) as ex:
+    with ThreadPoolExecutor(max_workers=_workers(jobs)) as ex:
         works = list(ex.map(one, inst_objs))
     src = os.path.join(OBJ, "lscqp_work_table.cpp")
     with open(src, "w") as f:

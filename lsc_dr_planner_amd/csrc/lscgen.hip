@@ -19,6 +19,7 @@
 #include <string>
 
 #include "../../include/lscqp.h"
+#include "lscqp_internal.hpp"
 #include "lscqp_missions.hpp"
 
 namespace lscgen {
@@ -755,8 +756,6 @@ __global__ __launch_bounds__(64) void select_neighbours_kernel(int64_t n_agents,
 }
 
 }  // namespace lscgen
-
-extern "C" int lscqp_set_error_(int code, const char* msg);  // lscqp_api.hip
 
 extern "C" int lscqp_select_neighbours_raw_(int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_obs, double range,
                                             const double* d_pos, int32_t* d_nbr, int32_t* d_count, void* stream) {

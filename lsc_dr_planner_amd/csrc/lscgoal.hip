@@ -14,6 +14,7 @@
 #include <string>
 
 #include "../../include/lscqp.h"
+#include "lscqp_internal.hpp"
 
 namespace lscgoal {
 
@@ -115,8 +116,6 @@ __global__ __launch_bounds__(kThreads) void goal_kernel(int M, int dim, int use_
 }
 
 }  // namespace lscgoal
-
-extern "C" int lscqp_set_error_(int code, const char* msg);
 
 extern "C" int lscqp_goal_fin_raw_(int M, int dim, int use_sfc, int rows_f32, double fin_dt, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows,
                                    const uint64_t* d_row_offsets, const lscqp_box* d_sfc, int32_t* d_status, void* stream) {

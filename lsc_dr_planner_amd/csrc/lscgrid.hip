@@ -29,9 +29,8 @@
 
 #include "../../include/lscqp.h"
 #include "lscqp_missions.hpp"
+#include "lscqp_internal.hpp"
 
-extern "C" int lscqp_set_error_(int code, const char* msg);
-extern "C" int lscqp_map_raw_(lscqp_map mp, double* res, float* world_min, float* world_max, int* key0, int* dims, const int32_t** d_nearest, int* device);
 
 namespace lscgrid {
 
@@ -933,8 +932,6 @@ void launch_fields(const lscqp_grid_s* g, int64_t n, const uint8_t* occ, const d
 
 }  // namespace
 
-extern "C" int lscqp_check_missions_(int64_t n_total, int32_t n_missions, const int64_t* mission_offsets);  // lscqp_api.hip
-
 extern "C" {
 
 int lscqp_grid_shape(const double* world_min, const double* world_max, double resolution, int32_t world_dimension, double z_2d, double* grid_min,
@@ -1176,7 +1173,6 @@ int lscqp_waypoints_wide_device(lscqp_grid g, double communication_range, int32_
     return LSCQP_OK;
 }
 
-// (library-internal, also lscplan.hip) work arrays for n agents in n_missions missions; grows on demand, which synchronises and allocates
 int lscqp_grid_reserve_missions_(lscqp_grid g, int64_t n, int32_t n_missions) {
     if (!g || n < 0 || n_missions < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
     const int rc = lscqp_grid_reserve(g, n);

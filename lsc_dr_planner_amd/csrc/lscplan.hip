@@ -27,27 +27,7 @@
 #include <vector>
 
 #include "../../include/lscqp.h"
-
-extern "C" int lscqp_set_error_(int code, const char* msg);
-extern "C" const lscqp_class_desc* lscqp_class_desc_of_(lscqp_handle h);
-extern "C" uint64_t lscqp_handle_generation_(lscqp_handle h);
-extern "C" int lscqp_map_device_(lscqp_map mp);
-extern "C" int lscqp_commit_validate_raw_(int M, int dim, int use_sfc, double dt, int64_t n, double time_step, double z_2d, const int32_t* d_qp_status,
-                                          const double* d_x_new, const double* d_x_init, double* d_x_plan, double* d_goal, const lscqp_header* d_hdr,
-                                          const lscqp_box* d_sfc, int32_t* d_valid, double* d_state, void* stream);
-extern "C" int lscqp_optimize_goal_fin_device_(lscqp_handle h, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows, const uint64_t* d_row_offsets,
-                                               const lscqp_box* d_sfc, int32_t* d_status_out, double fin_dt, void* stream);
-extern "C" uint64_t lscqp_map_generation_(lscqp_map mp);
-extern "C" int lscqp_check_missions_(int64_t n_total, int32_t n_missions, const int64_t* mission_offsets);
-extern "C" int lscqp_grid_reserve_missions_(lscqp_grid g, int64_t n, int32_t n_missions);
-extern "C" int lscqp_generate_constraints_own_(lscqp_handle h, int32_t mode, int64_t n_agents, int32_t n_obs, int64_t first_agent,
-                                               const double* d_traj, const double* d_own_traj, const int32_t* d_neighbours, const double* d_radius,
-                                               const double* d_downwash, const double* d_goal_all, lscqp_row* d_rows_out, int32_t n_obs_total,
-                                               int32_t slot0, void* stream);
-extern "C" int lscqp_record_create_(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
-                                    const int64_t* d_offsets_borrowed, int32_t n_samples, double record_time_step, double time_step, double z_2d,
-                                    const lscqp_record_desc* desc, lscqp_record* out);
-extern "C" int lscqp_record_unfinished_on_(lscqp_record r, void* stream, int32_t* unfinished_out);
+#include "lscqp_internal.hpp"
 
 namespace lscplan {
 
@@ -932,7 +912,7 @@ int lscqp_plan_run(lscqp_plan p, int64_t max_replans, int32_t check_every, int32
     return LSCQP_OK;
 }
 
-const lscqp_plan_desc* lscqp_plan_desc_of_(lscqp_plan p) { return &p->d; }  // (library-internal: lscqp_comm.hip)
+const lscqp_plan_desc* lscqp_plan_desc_of_(lscqp_plan p) { return &p->d; }
 int lscqp_plan_device_(lscqp_plan p) { return p->device; }
 
 int64_t lscqp_plan_graph_nodes(lscqp_plan p) {

@@ -16,6 +16,7 @@
 #include <string>
 
 #include "../../include/lscqp.h"
+#include "lscqp_internal.hpp"
 #include "lscpost_traj.hpp"
 
 namespace lscpost {
@@ -299,8 +300,6 @@ __global__ __launch_bounds__(kObsT) void safety_obstacles_kernel(int M, int dim,
 
 }  // namespace lscpost
 
-extern "C" int lscqp_set_error_(int code, const char* msg);
-
 extern "C" int lscqp_safety_obstacles_raw_(int M, int dim, double dt, int64_t n_agents, int64_t first_agent, int n_samples, double record_time_step,
                                            double z_2d, const double* d_x_all, const double* d_radius, const double* d_downwash, int n_obstacles,
                                            const lscqp_obstacle* d_obstacles, lscqp_safety_obs* d_out, void* stream) {
@@ -353,7 +352,6 @@ extern "C" int lscqp_validate_step_raw_(int M, int dim, int use_sfc, double dt, 
     return LSCQP_OK;
 }
 
-// (library-internal, lscplan.hip) commit + isSolValid + doStep of the local agents in one launch; d_x_plan / d_goal: the local block
 extern "C" int lscqp_commit_validate_raw_(int M, int dim, int use_sfc, double dt, int64_t n, double time_step, double z_2d, const int32_t* d_qp_status,
                                           const double* d_x_new, const double* d_x_init, double* d_x_plan, double* d_goal, const lscqp_header* d_hdr,
                                           const lscqp_box* d_sfc, int32_t* d_valid, double* d_state, void* stream) {

@@ -15,6 +15,7 @@
 #include "lscqp_kernel.hpp"
 #include "lscqp_launch.hpp"
 #include "lscqp_staging.hpp"
+#include "lscqp_internal.hpp"
 
 #define LSCQP_DECL(M, D, E, S, W, X)                                                                                      \
     extern "C" hipError_t lscqp_launch_##M##_##D##_##E##_##S##_##W##_##X(const lscqp::DevClass*, int64_t, const lscqp_header*, \
@@ -24,26 +25,6 @@
 LSCQP_INSTANCES(LSCQP_DECL)
 #undef LSCQP_DECL
 
-// the run-time-shaped instance (lscqp_generic.hip): every (M, dim, planner mode) / neighbour count the compiled table does not serve
-extern "C" int lscqp_generic_supports(int M, int dim, int es);
-extern "C" int lscqp_generic_max_obstacles(int M, int dim, int es);
-extern "C" size_t lscqp_generic_lds_bytes(int M, int dim, int es, int n_obs_max);
-extern "C" hipError_t lscqp_launch_generic(const lscqp::DevClass* cls, int M, int dim, int es, int64_t n, const lscqp_header* hdr, const lscqp_row* rows,
-                                           const uint64_t* row_offsets, const lscqp_box* sfc, const double* x_init, double* x_out, double* obj_out,
-                                           int32_t* status_out, lscqp_info* info_out, hipStream_t stream);
-
-// the dual active-set phase (lscqp_das.hip)
-extern "C" size_t lscqp_das_build_tables(int M, int es, double dt, double w_c, double w_t, double* out);
-extern "C" size_t lscqp_das_build_pairs(int M, int dim, int comm_on, int32_t* out);
-extern "C" size_t lscqp_das_lds_bytes(int M, int dim, int kmax, int cacheC, int stage_rows);
-extern "C" hipError_t lscqp_launch_das(const lscqp::DevClass* cls, int M, int dim, int es, int cap, int threads, int kmax, int max_steps, int cacheC,
-                                       int stage_rows, int screen, const double* d_tab, int64_t n, const lscqp_header* hdr, const lscqp_row* rows, const uint64_t* row_offsets,
-                                       const lscqp_box* sfc, const double* x_init, double* x_out, double* obj_out, int32_t* status_out,
-                                       lscqp_info* info_out, hipStream_t stream);
-// the prescreen (lscqp_prescreen.hip): cert_out for the standalone entry, the solve's outputs in front of a solve
-extern "C" hipError_t lscqp_launch_prescreen(const lscqp::DevClass* cls, int M, int dim, int cap, int64_t n, const lscqp_header* hdr, const lscqp_row* rows,
-                                             const uint64_t* row_offsets, const lscqp_box* sfc, const double* x_init, lscqp_prescreen_cert* cert_out,
-                                             double* x_out, double* obj_out, int32_t* status_out, lscqp_info* info_out, hipStream_t stream);
 // the phase and the first interior-point pass in one launch (lscqp_fused.hip), per instance of LSCQP_FUSED_INSTANCES
 using fused_fn = hipError_t (*)(const lscqp::DevClass*, int, int, int, int, int, const double*, int64_t, const lscqp_header*, const lscqp_row*,
                                 const uint64_t*, const lscqp_box*, const double*, double*, double*, int32_t*, lscqp_info*, hipStream_t);
@@ -53,38 +34,6 @@ using fused_fn = hipError_t (*)(const lscqp::DevClass*, int, int, int, int, int,
                                                                          const double*, double*, double*, int32_t*, lscqp_info*, hipStream_t);
 LSCQP_FUSED_INSTANCES(LSCQP_FUSED_DECL)
 #undef LSCQP_FUSED_DECL
-extern "C" int lscqp_generate_lsc_raw_(int mode, int M, int dim, int64_t n_agents, int32_t n_obs, int64_t first_agent,
-                                       const double* d_traj, const double* d_own_traj, const int32_t* d_neighbours, const double* d_radius,
-                                       const double* d_downwash, const double* d_goal, const double* d_goal_all, int rows_f32,
-                                       int32_t n_obs_total, int32_t slot0, lscqp_row* d_rows_out, void* stream);
-extern "C" int lscqp_shift_traj_partial_raw_(int M, int dim, int64_t n, const double* w36, double z_2d, const double* d_x_prev, double* d_traj,
-                                             void* stream);
-extern "C" int lscqp_generate_lsc_obstacles_raw_(int M, int dim, double dt, const lscqp_obstacle_param* p, int64_t n_agents, int32_t n_dyn,
-                                                 int64_t first_agent, const double* d_traj, const int32_t* d_ids, const lscqp_obstacle* d_table,
-                                                 const double* d_radius, const double* d_goal, const lscqp_header* d_hdr, int rows_f32,
-                                                 int32_t n_obs_total, int32_t slot0, const double* d_binv3, lscqp_row* d_rows_out, void* stream);
-extern "C" int lscqp_goal_fin_raw_(int M, int dim, int use_sfc, int rows_f32, double fin_dt, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows,
-                                   const uint64_t* d_row_offsets, const lscqp_box* d_sfc, int32_t* d_status, void* stream);
-extern "C" int lscqp_goal_raw_(int M, int dim, int use_sfc, int rows_f32, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows,
-                               const uint64_t* d_row_offsets, const lscqp_box* d_sfc, int32_t* d_status, void* stream);
-extern "C" int lscqp_safety_metrics_raw_(int M, int dim, double dt, int64_t n_agents, int64_t first_agent, int64_t n_total, int n_samples,
-                                         double record_time_step, double z_2d, const double* d_x_all, const double* d_radius,
-                                         const double* d_downwash, const lscqp_header* d_hdr, lscqp_safety* d_out, void* stream);
-extern "C" int lscqp_construct_sfc_raw_(lscqp_map mp, int mode, int M, int64_t n, const double* d_points, const double* d_radius,
-                                        lscqp_box* d_sfc, int32_t* d_status_out, void* stream);
-extern "C" int lscqp_select_neighbours_raw_(int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_obs, double range,
-                                            const double* d_pos, int32_t* d_nbr, int32_t* d_count, void* stream);
-extern "C" int lscqp_validate_step_raw_(int M, int dim, int use_sfc, double dt, int64_t n, double time_step, double z_2d, const double* d_x,
-                                        const lscqp_header* d_hdr, const lscqp_box* d_sfc, int32_t* d_valid, double* d_state,
-                                        void* stream);
-extern "C" int lscqp_select_neighbours_missions_raw_(int64_t n_total, int32_t n_missions, const int64_t* d_off, int32_t n_obs, double range,
-                                                     const double* d_pos, int32_t* d_nbr, int32_t* d_count, void* stream);
-extern "C" int lscqp_safety_metrics_missions_raw_(int M, int dim, double dt, int64_t n_total, int32_t n_missions, int64_t largest_mission,
-                                                  const int64_t* d_off, int n_samples, double record_time_step, double z_2d, const double* d_x_all,
-                                                  const double* d_radius, const double* d_downwash, const lscqp_header* d_hdr, lscqp_safety* d_out,
-                                                  void* stream);
-extern "C" int lscqp_shift_traj_raw_(int M, int dim, int64_t n, int shift, double z_2d, const double* d_x_prev, double* d_traj,
-                                     void* stream);
 
 namespace {
 
@@ -517,8 +466,6 @@ static int derive(lscqp_solver* s, const lscqp_class_desc* d) {
 
 extern "C" const lscqp_class_desc* lscqp_class_desc_of_(lscqp_handle h) { return &h->desc; }  // for lscplan.hip
 extern "C" uint64_t lscqp_handle_generation_(lscqp_handle h) { return h->generation; }
-// (library-internal, lscqp_comm.hip) does a batch of this shape have a second chance on the instance with the other elimination order?
-extern "C" int lscqp_has_other_order_(lscqp_handle h, int64_t n, int32_t n_obs_max);
 
 // one device's copy of the current tables, in a buffer no launch has seen yet (mu held; the caller restores the current device).
 // false: allocation or copy failed -- the device then has no tables and its launches run without the phase (or fail loudly, das_device_table)
@@ -642,8 +589,6 @@ int lscqp_prepare_device(lscqp_handle h) {
     return LSCQP_OK;
 }
 
-// (library-internal, tests and development tools) re-read the handle's switches from the environment / set one by name; -1 restores a
-// launch-shape override to the policy's value
 int lscqp_debug_reload_knobs_(lscqp_handle h) {
     if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
     Knobs k = h->knobs;
@@ -723,7 +668,6 @@ int64_t lscqp_launch_capacity(lscqp_handle h, int64_t n, int32_t n_obs_max) {
 
 // Instances ONE device works on at once in the first kernel of a solve of this class (include/lscqp.h): with the dual active-set phase on,
 // the phase's one-wavefront form at the occupancy the runtime reports for its LDS footprint; otherwise lscqp_launch_capacity.
-extern "C" int lscqp_das_blocks_per_cu(int M, int dim, int kmax, int rows_f32);
 int64_t lscqp_device_fill(lscqp_handle h, int64_t n, int32_t n_obs_max) {
     if (!h || n < 0 || n_obs_max < 0) return -1;
     const int n_cu = cu_count();
@@ -742,7 +686,6 @@ int64_t lscqp_device_fill(lscqp_handle h, int64_t n, int32_t n_obs_max) {
 
 // Work counters of the kernel instance a launch would select (include/lscqp.h): the per-wavefront instruction counts come from the
 // table the build reads off each instance's machine code (lsc_dr_planner_amd/isa_work.py -> lscqp_work_table_, generated TU).
-extern "C" int lscqp_work_table_(int M, int D, int E, int S, int W, int X, double* out24);
 int lscqp_instance_work(lscqp_handle h, int64_t n, int32_t n_obs_max, lscqp_work* out) {
     if (!h || !out) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
     if (n < 0 || n_obs_max < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
@@ -865,13 +808,6 @@ int lscqp_shift_traj_partial_device(lscqp_handle h, int64_t n, double fraction, 
     return lscqp_shift_traj_partial_raw_(h->desc.M, h->desc.dim, n, W, z_2d, d_x_prev, d_traj, stream);
 }
 
-// (library-internal, lscplan.hip) lscqp_generate_constraints_device_ex with the planning agents' initial trajectories kept apart from
-// the predicted trajectories of the agents as obstacles: d_own_traj [n_agents][M][6][3], NULL = rows d_traj[first_agent + a]
-extern "C" int lscqp_generate_constraints_own_(lscqp_handle h, int32_t mode, int64_t n_agents, int32_t n_obs, int64_t first_agent,
-                                               const double* d_traj, const double* d_own_traj, const int32_t* d_neighbours, const double* d_radius,
-                                               const double* d_downwash, const double* d_goal_all, lscqp_row* d_rows_out, int32_t n_obs_total,
-                                               int32_t slot0, void* stream);
-
 int lscqp_generate_constraints_device_ex(lscqp_handle h, int32_t mode, int64_t n_agents, int32_t n_obs, int64_t first_agent,
                                          const double* d_traj, const int32_t* d_neighbours, const double* d_radius,
                                          const double* d_downwash, const double* d_goal_all, lscqp_row* d_rows_out, int32_t n_obs_total,
@@ -916,9 +852,6 @@ int64_t lscqp_generate_lsc_bytes(lscqp_handle h, int64_t n_agents, int32_t n_obs
            + n_agents * ((int64_t)n_obs * 4 + 24); /* neighbour ids, goal */
 }
 
-// (library-internal, lscplan.hip) the goal LP that also finishes the headers of the chain: goal as a point3d, terminal_segments (fin_dt = the class's dt)
-int lscqp_optimize_goal_fin_device_(lscqp_handle h, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows, const uint64_t* d_row_offsets,
-                                    const lscqp_box* d_sfc, int32_t* d_status_out, double fin_dt, void* stream);
 int lscqp_optimize_goal_device(lscqp_handle h, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows,
                                const uint64_t* d_row_offsets, const lscqp_box* d_sfc, int32_t* d_status_out, void* stream) {
     return lscqp_optimize_goal_fin_device_(h, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_status_out, 0.0, stream);
@@ -994,10 +927,6 @@ int lscqp_safety_metrics_device(lscqp_handle h, int64_t n_agents, int64_t first_
                                      d_x_all, d_radius, d_downwash, d_hdr, d_out, stream);
 }
 
-extern "C" int lscqp_safety_obstacles_raw_(int M, int dim, double dt, int64_t n_agents, int64_t first_agent, int n_samples, double record_time_step,
-                                           double z_2d, const double* d_x_all, const double* d_radius, const double* d_downwash, int n_obstacles,
-                                           const lscqp_obstacle* d_obstacles, lscqp_safety_obs* d_out, void* stream);
-
 int lscqp_safety_obstacles_device(lscqp_handle h, int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_samples,
                                   double record_time_step, double z_2d, const double* d_x_all, const double* d_radius,
                                   const double* d_downwash, int32_t n_obstacles, const lscqp_obstacle* d_obstacles,
@@ -1011,9 +940,6 @@ int lscqp_safety_obstacles_device(lscqp_handle h, int64_t n_agents, int64_t firs
     return lscqp_safety_obstacles_raw_(h->desc.M, h->desc.dim, h->desc.dt, n_agents, first_agent, n_samples, record_time_step, z_2d, d_x_all,
                                        d_radius, d_downwash, n_obstacles, d_obstacles, d_out, stream);
 }
-
-extern "C" int lscqp_construct_sfc_raw_ex_(lscqp_map mp, int mode, int M, int64_t n, const double* d_points, const double* d_radius, lscqp_box* d_sfc,
-                                           int32_t* d_status_out, const int32_t* d_order, uint32_t* d_cost_out, void* stream);
 
 int lscqp_construct_sfc_device(lscqp_handle h, lscqp_map mp, int32_t mode, int64_t n, const double* d_points, const double* d_radius,
                                lscqp_box* d_sfc, int32_t* d_status_out, void* stream) {
@@ -1057,7 +983,6 @@ int lscqp_select_neighbours_device(lscqp_handle h, int64_t n_agents, int64_t fir
                                         d_count_out, stream);
 }
 
-// (library-internal: every entry point that takes a mission partition) mission_offsets[0..n_missions], host: strictly increasing from 0 to n_total
 int lscqp_check_missions_(int64_t n_total, int32_t n_missions, const int64_t* mission_offsets) {
     if (n_missions < 1 || !mission_offsets) return fail(LSCQP_ERR_INVALID_ARGUMENT, "a mission partition needs n_missions >= 1 and its offset list");
     if (mission_offsets[0] != 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "mission_offsets[0] must be 0");
@@ -1240,8 +1165,6 @@ int lscqp_solve_batch_device_ordered(lscqp_handle h, int64_t n, int32_t n_obs_ma
                                               retry, PART_WHOLE, d_order, stream, nullptr);
 }
 
-// (library-internal, tests) the plan of a call of this handle, from the planner the worker above runs -- on no device: the CU count and
-// whether the class's tables are on the device are arguments.  has_order: taken because a call has it; no rule reads it today.
 int lscqp_debug_solve_plan_(lscqp_handle h, int64_t n, int32_t n_obs_max, int32_t retry, int32_t part, int32_t has_x_init, int32_t has_order,
                             int32_t deferred, int32_t n_cu, int32_t tables_available, SolvePlan* out) {
     if (!h || !out || n < 0 || n_obs_max < 0 || retry < 0 || retry > 3 || part < PART_WHOLE || part > PART_RESCUE)
@@ -1285,10 +1208,6 @@ int lscqp_set_prescreen(lscqp_handle h, int32_t mode) {
     return LSCQP_OK;
 }
 int lscqp_prescreen(lscqp_handle h) { return h ? h->prescreen : -1; }
-// (library-internal, tests only) the prescreen's per-control-point arithmetic on HOST arrays (lscqp_prescreen.hip: lscqp_prescreen_host_twin_) -- holds the
-// certificate contract to the referee on a machine without a device.  No entry point of the ABI calls it; the product path has no CPU fallback.
-extern "C" int lscqp_prescreen_host_twin_(const lscqp::DevClass* cls, int M, int dim, int cap, int64_t n, const lscqp_header* hdr, const void* rows,
-                                          const uint64_t* row_offsets, const lscqp_box* sfc, lscqp_prescreen_cert* cert_out);
 int lscqp_debug_prescreen_twin_(lscqp_handle h, int64_t n, int32_t n_obs_max, const lscqp_header* hdr, const lscqp_row* rows, const uint64_t* row_offsets,
                                 const lscqp_box* sfc, lscqp_prescreen_cert* cert_out) {
     if (!h || n < 0 || n_obs_max < 0 || !hdr || !cert_out || (n_obs_max > 0 && (!rows || !row_offsets)) || (h->desc.use_sfc && !sfc))

@@ -23,16 +23,9 @@
 
 #include "../../include/lscqp.h"
 #include "lscqp_staging.hpp"
+#include "lscqp_internal.hpp"
 
-extern "C" int lscqp_set_error_(int code, const char* msg);
-extern "C" const lscqp_plan_desc* lscqp_plan_desc_of_(lscqp_plan p);  // lscplan.hip
-extern "C" int lscqp_plan_device_(lscqp_plan p);
-extern "C" int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_max, const lscqp_header* d_hdr, const lscqp_row* d_rows,
-                                                  const uint64_t* d_row_offsets, const lscqp_box* d_sfc, const double* d_x_init, double* d_x_out, double* d_obj_out,
-                                                  int32_t* d_status_out, lscqp_info* d_info_out, int32_t retry, int32_t part, const int32_t* d_order, void* stream,
-                                                  int* deferred);
 constexpr int32_t kPartOtherOrder = 2;  // lscqp_solve_plan.hpp: PART_OTHER_ORDER, only the repair pass on the instance of the other elimination order
-extern "C" int lscqp_has_other_order_(lscqp_handle h, int64_t n, int32_t n_obs_max);
 
 namespace {
 

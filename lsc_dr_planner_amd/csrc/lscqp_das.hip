@@ -8,6 +8,7 @@
 #include <mutex>
 #include <vector>
 
+#include "lscqp_internal.hpp"
 #include "lscqp_das.hpp"
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------

@@ -22,9 +22,7 @@
 #include <vector>
 
 #include "../../include/lscqp.h"
-
-extern "C" int lscqp_set_error_(int code, const char* msg);
-extern "C" const lscqp_class_desc* lscqp_class_desc_of_(lscqp_handle h);
+#include "lscqp_internal.hpp"
 
 namespace {
 

@@ -30,6 +30,7 @@
 #endif
 #include "lscqp_kernel.hpp"  // DevClass, KQ, TBc, fast_rcp (shared with the compiled instances)
 #include "lscqp_launch.hpp"
+#include "lscqp_internal.hpp"
 
 namespace lscqp_generic {
 

@@ -29,6 +29,7 @@
 #include <cstdint>
 
 #include "lscqp_kernel.hpp"
+#include "lscqp_internal.hpp"
 
 namespace lscqp_pre {
 
@@ -324,8 +325,6 @@ extern "C" hipError_t lscqp_launch_prescreen(const lscqp::DevClass* cls, int M, 
     return hipGetLastError();
 }
 
-// (library-internal, tests only) test_point over a batch in HOST memory, control point by control point in index order: the kernel's own
-// arithmetic without a device, so that the certificate contract can be held to the referee where no GPU is.  No entry point of the ABI calls it.
 extern "C" int lscqp_prescreen_host_twin_(const lscqp::DevClass* cls, int M, int dim, int cap, int64_t n, const lscqp_header* hdr, const void* rows,
                                           const uint64_t* row_offsets, const lscqp_box* sfc, lscqp_prescreen_cert* cert_out) {
     using namespace lscqp_pre;

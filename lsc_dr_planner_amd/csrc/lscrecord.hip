@@ -18,10 +18,8 @@
 
 #include "../../include/lscqp.h"
 #include "lscpost_traj.hpp"
+#include "lscqp_internal.hpp"
 
-extern "C" int lscqp_set_error_(int code, const char* msg);
-extern "C" const lscqp_class_desc* lscqp_class_desc_of_(lscqp_handle h);
-extern "C" int lscqp_check_missions_(int64_t n_total, int32_t n_missions, const int64_t* mission_offsets);
 
 namespace lscrecord {
 
@@ -249,7 +247,6 @@ struct DeviceGuard {
 
 }  // namespace
 
-// (library-internal, lscplan.hip) d_offsets_borrowed: the partition's offsets as the plan already has them on the device; NULL: an own copy
 extern "C" int lscqp_record_create_(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
                                     const int64_t* d_offsets_borrowed, int32_t n_samples, double record_time_step, double time_step, double z_2d,
                                     const lscqp_record_desc* desc, lscqp_record* out) {
@@ -395,7 +392,6 @@ int lscqp_record_unfinished(lscqp_record r, int32_t* unfinished_out) {
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "lscqp_record_unfinished");
 }
 
-// (library-internal, lscplan.hip: lscqp_plan_run) the unfinished word as `stream` leaves it, waited for
 int lscqp_record_unfinished_on_(lscqp_record r, void* stream, int32_t* unfinished_out) {
     hipError_t e = hipMemcpyAsync(r->h_word, r->unfinished, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);

@@ -32,10 +32,9 @@
 
 #include "../../include/lscqp.h"
 #include "lscqp_staging.hpp"
+#include "lscqp_internal.hpp"
 
 #pragma clang fp contract(off)
-
-extern "C" int lscqp_set_error_(int code, const char* msg);  // lscqp_api.hip
 
 struct lscqp_map_s {
     double res;
@@ -55,7 +54,6 @@ struct lscqp_map_s {
 #ifndef LSCSFC_VARIANT_ONLY
 extern "C" int lscqp_map_device_(lscqp_map mp) { return mp->device; }
 extern "C" uint64_t lscqp_map_generation_(lscqp_map mp) { return mp->generation; }
-// (library-internal: lscgrid.hip evaluates the grid planner's occupancy from the same nearest-occupied-cell field)
 extern "C" int lscqp_map_raw_(lscqp_map mp, double* res, float* world_min, float* world_max, int* key0, int* dims, const int32_t** d_nearest, int* device) {
     *res = mp->res;
     for (int k = 0; k < 3; k++) world_min[k] = mp->world_min[k], world_max[k] = mp->world_max[k], key0[k] = mp->key0[k], dims[k] = mp->dims[k];
@@ -1315,10 +1313,6 @@ extern "C" hipError_t lscsfc_launch_throughput_(const void* view, int mode, int 
     return hipGetLastError();
 }
 #else
-extern "C" hipError_t lscsfc_launch_throughput_(const void* view, int mode, int M, int64_t n, const double* d_points, const double* d_radius,
-                                                lscqp_box* d_sfc, int32_t* d_status_out, void* stream);  // lscsfc_tp.hip
-extern "C" int lscsfc_throughput_max_cells_(void);
-
 extern "C" {
 
 #ifdef LSCSFC_DEBUG
@@ -1489,8 +1483,6 @@ int lscqp_map_download(lscqp_map mp, uint8_t* occ, int32_t* nearest) {
     return LSCQP_OK;
 }
 
-int lscqp_construct_sfc_raw_ex_(lscqp_map mp, int mode, int M, int64_t n, const double* d_points, const double* d_radius, lscqp_box* d_sfc,
-                                int32_t* d_status_out, const int32_t* d_order, uint32_t* d_cost_out, void* stream);
 int lscqp_construct_sfc_raw_(lscqp_map mp, int mode, int M, int64_t n, const double* d_points, const double* d_radius, lscqp_box* d_sfc,
                              int32_t* d_status_out, void* stream) {
     return lscqp_construct_sfc_raw_ex_(mp, mode, M, n, d_points, d_radius, d_sfc, d_status_out, nullptr, nullptr, stream);

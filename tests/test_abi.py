@@ -194,3 +194,33 @@ def test_python_constants_are_the_headers(api):
             assert hdr.get("LSCQP_" + name) == val, (name, val, hdr.get("LSCQP_" + name))
             seen += 1
     assert seen >= 16 and hdr["LSCQP_INFO_RESCUED"] == 32
+
+
+def test_prototypes_read_from_the_headers_are_the_hand_written_ones(api):
+    """api.lib() reads restype / argtypes from include/lscqp.h and csrc/lscqp_internal.hpp; these are the literals of the table that was
+    written by hand before (every width, every typed pointer, a string and a pointer result, two library-internal entries)."""
+    L = api.lib()
+    vp, i32, i64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+    want = {
+        "lscqp_select_neighbours_missions_device": (C.c_int, [vp, i64, i32, vp, vp, i32, dbl, vp, vp, vp, vp]),
+        "lscqp_record_create": (C.c_int, [vp, i64, i32, vp, i32, dbl, dbl, dbl, vp, C.POINTER(C.c_void_p)]),
+        "lscqp_safety_obstacles_device": (C.c_int, [vp, i64, i64, i64, i32, dbl, dbl, vp, vp, vp, i32, vp, vp, vp]),
+        "lscqp_exchange_schedule_padded": (C.c_int, [i64, i32, vp, vp, i64, i64, vp, i32, vp]),
+        "lscqp_plan_run": (C.c_int, [vp, i64, i32, i32, vp, vp]),
+        "lscqp_comm_backend": (C.c_char_p, [vp]),
+        "lscqp_plan_buffer": (C.c_void_p, [vp, i32, vp]),
+        "lscqp_commit_validate_raw_": (C.c_int, [C.c_int, C.c_int, C.c_int, dbl, i64, dbl, dbl] + [vp] * 10),
+        "lscqp_debug_solve_plan_": (C.c_int, [vp, i64, i32] + [i32] * 7 + [C.POINTER(api._Plan)]),
+    }
+    for name, (restype, argtypes) in want.items():
+        f = getattr(L, name)
+        assert f.restype is restype and list(f.argtypes) == argtypes, name
+
+
+def test_every_exported_symbol_has_the_headers_parameter_count(api):
+    L = api.lib()
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    count = {name: 0 if args.strip() in ("", "void") else args.count(",") + 1 for name, args in re.findall(r"\b(lscqp_[a-z_]+)\s*\(([^()]*)\)\s*;", txt)}
+    assert sorted(count) == sorted(api.EXPORTED_SYMBOLS)
+    for name in api.EXPORTED_SYMBOLS:
+        assert getattr(L, name).argtypes is not None and len(getattr(L, name).argtypes) == count[name], name
