@@ -104,6 +104,11 @@ def _stale(o, mtime):
     if not os.path.exists(o) or not os.path.exists(d):
         return True
     deps = open(d).read().replace("\\\n", " ").split(":", 1)[1].split()
+    # The depfile names the tree it was written in.  A built tree that was copied elsewhere is judged by ITS files: the first name is the
+    # unit's own source, <that tree>/csrc/<unit>, and every name under that directory (the ../../include ones too) is read under CSRC.
+    was = os.path.dirname(deps[0]) if deps else CSRC
+    if was != CSRC:
+        deps = [CSRC + p[len(was):] if p.startswith(was + os.sep) else p for p in deps]
     t = os.path.getmtime(o)
     return any(mtime(p) > t for p in deps + [os.path.abspath(__file__)])
 

@@ -42,6 +42,18 @@ __device__ __forceinline__ double fast_rcp(double d) {
     return r;
 }
 
+// a b - c d with the rounding error of c d recovered by one fma (Kahan): the result is good to about an ulp of ITSELF, however much of
+// the two products cancels.  The triangle solve below needs that: on a sliver (height h of the base) its determinant and both
+// numerators are h^2 of their terms, and `a * b - c * d` left to the compiler becomes fma(a, b, -(c * d)) -- one product exact, the other
+// rounded -- which puts an error of 2^-53 / h^2 of the weights into a distance that is LINEAR in them (G_ii - u r1 - v r2): at
+// h = 2^-20 the triangle then loses to one of its own edges and the normal is 3e-6 off (tests/lscgen_cases.py: sliver_cases).
+__device__ __forceinline__ double diff_of_products(double a, double b, double c, double d) {
+    const double w = c * d;
+    const double e = fma(c, d, -w);  // c d = w + e exactly
+    const double f = fma(a, b, -w);
+    return f - e;
+}
+
 // Closest point to the origin on conv{p[0..5]}: 6 vertices, 15 edges, 20 triangles, then a supporting-plane test that
 // decides whether the origin is inside (distance 0).  Everything is evaluated on the Gram matrix G_ij = p_i . p_j (21
 // dot products, computed once): an edge or triangle candidate then costs a dozen scalar operations instead of vector
@@ -92,10 +104,10 @@ __device__ __forceinline__ P3 hull_closest_point(const P3 (&p)[6], bool planar =
                 const double g11 = G[j][j] - 2.0 * G[i][j] + G[i][i], g22 = G[l][l] - 2.0 * G[i][l] + G[i][i];
                 const double g12 = G[j][l] - G[i][j] - G[i][l] + G[i][i];
                 const double r1 = G[i][i] - G[i][j], r2 = G[i][i] - G[i][l];
-                const double det = g11 * g22 - g12 * g12;
+                const double det = diff_of_products(g11, g22, g12, g12);
                 const bool ok = det > 1e-14 * fmax(g11 * g22, 1e-300);  // degenerate triangle: its edges cover it
                 const double idet = fast_rcp(ok ? det : 1.0);
-                const double u = (r1 * g22 - r2 * g12) * idet, v = (r2 * g11 - r1 * g12) * idet;
+                const double u = diff_of_products(r1, g22, r2, g12) * idet, v = diff_of_products(r2, g11, r1, g12) * idet;
                 consider(G[i][i] - u * r1 - v * r2, ok && u >= 0.0 && v >= 0.0 && u + v <= 1.0, i, j, l, u, v);
             }
     auto pick = [&](int k) -> P3 {

@@ -53,3 +53,25 @@ def test_commands_are_what_build_runs():
     assert flags["lscqp_das.o"] == ["-ffp-contract=on"] and flags["lscqp_das_sync.o"] == ["-ffp-contract=on", "-DLSCQP_DAS_FULL_SYNC"]
     assert flags["lscqp_prescreen.o"] == ["-ffp-contract=on"] and flags["lscrecord.o"] == ["-Rpass-analysis=kernel-resource-usage"]
     assert all(flags[f][-1] == "-DLSCQP_DAS_FULL_SYNC" for f in FUSED if f.endswith("_sync.o"))
+
+
+def test_a_copied_tree_is_judged_by_its_own_files(tmp_path):
+    """A depfile names the tree it was written in.  In a built tree that was copied elsewhere, the names under the old csrc/ directory
+    (the ../../include ones too) are read under this tree's: nothing is stale, and touching THIS tree's header schedules the object."""
+    was = "/some/other/checkout/lsc_dr_planner_amd/csrc"
+    o = str(tmp_path / "lscgen.o")
+    open(o, "w").close()
+    with open(o + ".d", "w") as f:
+        f.write("%s: \\\n  %s/lscgen.hip \\\n  %s/lscqp_missions.hpp %s/../../include/lscqp.h\n" % (o, was, was, was))
+    seen = []
+
+    def mtime(p, newer=()):
+        seen.append(p)
+        assert os.path.exists(p), p  # (a named file that is gone would count as newer)
+        return float("inf") if os.path.basename(p) in newer else 0.0
+
+    assert not build._stale(o, mtime)
+    assert {os.path.join(build.CSRC, "lscgen.hip"), os.path.join(build.CSRC, "lscqp_missions.hpp"),
+            os.path.join(build.CSRC, "..", "..", "include", "lscqp.h")} <= set(seen)
+    assert build._stale(o, lambda p: mtime(p, newer=("lscqp_missions.hpp",)))
+    assert build._stale(o, lambda p: mtime(p, newer=("lscqp.h",)))

@@ -230,3 +230,60 @@ def test_bvc_mode_end_to_end_on_the_default_shape(api, oracle):
     # no end stop in BVC mode: some plan still moves at the end of the horizon
     X = x.reshape(N, dim, M, 6)
     assert np.abs(X[:, :, M - 1, 5] - X[:, :, M - 1, 4]).max() > 1e-4
+
+
+# ---- generateCLSC on constructed hulls and on the segment-segment fixture (tests/lscgen_cases.py, tests/hull_reference.py) -------
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim,M", [(3, 5), (2, 5), (3, 2)])
+def test_gpu_generate_clsc_on_constructed_hulls(api, oracle, dim, M):
+    """generate_lsc_kernel<CLSC>, segments m < M-1: the same closest-point search as generateLSC on every constructed family, held to
+    the constructed result, the exact referee and the oracle.  No fallback here: a hull around the origin gives a zero normal and
+    b = (r_a + r_b) / 2 exactly, and a hull closer than 1e-5 m keeps its own normal (both stated by construction)."""
+    from tests import lscgen_cases as LC
+    from tests import lscgen_checks as T
+
+    cases, _, n_ref, n_con = LC.suite(dim)
+    pk = LC.pack_pairs(cases, M, dim, hull_segments=M - 1)
+    got = LC.run_pairs_device(api, CLSC, pk)
+    T._hold_device(cases, pk, got, LC.oracle_pairs(oracle, api, CLSC, pk), n_con, n_ref, "clsc", lambda n: LC.expected_for_pack(cases, pk, n, "clsc"))
+    T._coverage_line(cases, pk, dim, "generate_clsc (M=%d)" % M)
+
+
+@pytest.mark.gpu
+def test_gpu_clsc_last_segment_on_the_segment_segment_fixture(api, oracle):
+    """The 240 cases of tests/golden/segseg.json (generic, planar, parallel, degenerate, crossing) through segseg_closest ON THE DEVICE:
+    the neighbour's last point and goal are segment 1, the agent's are segment 2 (M = 2, downwash 1).  Rows against the oracle at the
+    standing bars; the distance recovered from the rows, 2 d - (r_a + r_b) with d = b - n . p, against the fixture's exact distance
+    at the fixture's 2e-5 bar."""
+    from tests import lscgen_cases as LC
+
+    g = H.load_golden("segseg")["cases"]
+    N, M, r = len(g), 2, 0.15
+    assert N == 240
+    traj = np.zeros((2 * N, M, 6, 3))
+    goal_all = np.zeros((2 * N, 3))
+    for a, c in enumerate(g):
+        traj[a, :, :] = np.float32(c["l2s"])
+        traj[N + a, :, :] = np.float32(c["l1s"])
+        traj[a, 0] += 16.0  # segment 0: two separated points (a hull case of no interest here)
+        goal_all[a], goal_all[N + a] = np.float32(c["l2e"]), np.float32(c["l1e"])
+    pk = dict(N=N, M=M, dim=3, traj=traj, nbr=(N + np.arange(N, dtype=np.int32)).reshape(N, 1), radius=np.full(2 * N, r), downwash=np.ones(2 * N),
+              goal_all=goal_all)
+    got = LC.run_pairs_device(api, CLSC, pk)
+    L = oracle.generate_constraints(CLSC, traj, pk["nbr"], pk["radius"], pk["downwash"], goal_all, dim=3)
+    want = LC.oracle_pairs(oracle, api, CLSC, pk)
+    dn, db = np.abs(got - want)[..., :3].max(), np.abs(got - want)[..., 3].max()
+    print("segseg through CLSC: device vs oracle normal %.3g b %.3g" % (dn, db))
+    assert dn <= 2e-7 and db <= 2e-6, (dn, db)
+    last = got[:, M - 1]  # (N, 6, 4): one normal, one point, one margin for the six control points
+    assert (last == last[:, :1]).all()
+    p = L["p"][:, 0, M - 1, 0]  # the oracle's closest point on segment 1 (the device does not return it)
+    d = last[:, 0, 3] - (last[:, 0, :3] * p).sum(-1)
+    dist = 2 * d - 2 * r
+    worst = np.abs(dist - np.array([c["dist"] for c in g])).max()
+    print("segseg through CLSC: recovered distance vs exact %.3g" % worst)
+    assert worst <= 2e-5, worst
+    # the oracle itself says the same of these pairs (segseg_closest, as test_segment_segment_closest_points_against_exact_golden holds it)
+    for a in (0, 100, 239):
+        dd, c1, _ = oracle.segseg_closest(g[a]["l1s"], g[a]["l1e"], g[a]["l2s"], g[a]["l2e"])
+        assert abs((2 * L["d"][a, 0, M - 1, 0] - 2 * r) - dd) <= 1e-12 and np.array_equal(c1, p[a])
