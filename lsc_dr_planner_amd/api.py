@@ -167,6 +167,35 @@ def lib():
     return _lib
 
 
+def _arg(a):
+    """One argument of an entry as ctypes takes it: a torch tensor is its device address, a numpy array its host address; None (a NULL
+    pointer), numbers and ctypes values pass as they are."""
+    if hasattr(a, "data_ptr"):
+        return C.c_void_p(a.data_ptr())
+    return a.ctypes.data_as(C.c_void_p) if isinstance(a, np.ndarray) else a
+
+
+def _call(name, *args, stream=False):
+    """Call the entry `name` of liblscqp.so (its argtypes come from the headers, lib()) and raise LscqpError unless it returns OK.
+    stream: for an entry whose last parameter is the stream -- a torch.cuda.Stream, or None for torch's current one; it is returned."""
+    args = [_arg(a) for a in args]
+    if stream is not False:
+        if stream is None:
+            import torch
+
+            stream = torch.cuda.current_stream()
+        args.append(C.c_void_p(stream.cuda_stream))
+    rc = getattr(lib(), name)(*args)
+    if rc != OK:
+        raise LscqpError(rc, lib().lscqp_last_error().decode())
+    return stream
+
+
+def _stream_or_null(stream):
+    """(an entry for which NULL means the default stream, passed among the arguments)"""
+    return None if stream is None else C.c_void_p(stream.cuda_stream)
+
+
 EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_variables", "lscqp_num_inequalities",
                     "lscqp_algorithmic_bytes", "lscqp_solve_batch", "lscqp_solve_batch_stream", "lscqp_solve_batch_device", "lscqp_solve_batch_device_ex", "lscqp_solve_batch_device_ordered", "lscqp_order_by_work_device", "lscqp_launch_capacity", "lscqp_order_by_cost_device", "lscqp_construct_sfc_device_ordered",
                     "lscqp_num_segments", "lscqp_uses_sfc", "lscqp_row_bytes", "lscqp_max_obstacles", "lscqp_prepare_device", "lscqp_comm_prepare", "lscqp_comm_create", "lscqp_comm_destroy", "lscqp_comm_size",
@@ -225,14 +254,10 @@ class WorldMap:
         wmax = np.ascontiguousarray(world_max, dtype=np.float64)
         h = C.c_void_p()
         if csv_path is not None:
-            rc = lib().lscqp_map_create_from_csv(os.fsencode(csv_path), wmin.ctypes.data_as(C.c_void_p), wmax.ctypes.data_as(C.c_void_p),
-                                                 float(resolution), float(max_dist), C.byref(h))
+            _call("lscqp_map_create_from_csv", os.fsencode(csv_path), wmin, wmax, float(resolution), float(max_dist), C.byref(h))
         else:
             b = np.ascontiguousarray(boxes, dtype=np.float64).reshape(-1, 6)
-            rc = lib().lscqp_map_create(b.ctypes.data_as(C.c_void_p), b.shape[0], wmin.ctypes.data_as(C.c_void_p),
-                                        wmax.ctypes.data_as(C.c_void_p), float(resolution), float(max_dist), C.byref(h))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+            _call("lscqp_map_create", b, b.shape[0], wmin, wmax, float(resolution), float(max_dist), C.byref(h))
         self._h = h
         dims, key0 = np.zeros(3, np.int32), np.zeros(3, np.int32)
         lib().lscqp_map_info(self._h, dims.ctypes.data_as(C.c_void_p), key0.ctypes.data_as(C.c_void_p))
@@ -240,17 +265,13 @@ class WorldMap:
 
     def prepare(self, max_radius):
         """lscqp_map_prepare: the free-space table that lets the corridor kernel pass tests in open space without sampling."""
-        rc = lib().lscqp_map_prepare(self._h, float(max_radius))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_map_prepare", self._h, float(max_radius))
 
     def download(self):
         """(occ uint8, nearest int32), both shaped (dims[2], dims[1], dims[0])."""
         shape = (int(self.dims[2]), int(self.dims[1]), int(self.dims[0]))
         occ, near = np.zeros(shape, np.uint8), np.zeros(shape, np.int32)
-        rc = lib().lscqp_map_download(self._h, occ.ctypes.data_as(C.c_void_p), near.ctypes.data_as(C.c_void_p))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_map_download", self._h, occ, near)
         return occ, near
 
     def close(self):
@@ -276,15 +297,8 @@ def grid_shape(world_min, world_max, resolution=0.5, world_dimension=2, z_2d=1.0
     """lscqp_grid_shape (GridBasedPlanner::updateGridInfo): (grid_min float64[3], dims int32[3]).  No device call."""
     wmin, wmax = np.ascontiguousarray(world_min, dtype=np.float64), np.ascontiguousarray(world_max, dtype=np.float64)
     gmin, dims = np.zeros(3, np.float64), np.zeros(3, np.int32)
-    rc = lib().lscqp_grid_shape(wmin.ctypes.data_as(C.c_void_p), wmax.ctypes.data_as(C.c_void_p), float(resolution), int(world_dimension), float(z_2d),
-                                gmin.ctypes.data_as(C.c_void_p), dims.ctypes.data_as(C.c_void_p))
-    if rc != OK:
-        raise LscqpError(rc, lib().lscqp_last_error().decode())
+    _call("lscqp_grid_shape", wmin, wmax, float(resolution), int(world_dimension), float(z_2d), gmin, dims)
     return gmin, dims
-
-
-def _dptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def mission_offsets_arg(offsets, device=None, d_offsets=None):
@@ -311,18 +325,12 @@ class Grid:
         if handle is None:
             d = GridDesc(float(resolution), float(radius), float(z_2d), int(world_dimension), 0)
             h = C.c_void_p()
-            rc = lib().lscqp_grid_create(world_map._h, C.byref(d), C.byref(h))
-            if rc != OK:
-                raise LscqpError(rc, lib().lscqp_last_error().decode())
+            _call("lscqp_grid_create", world_map._h, C.byref(d), C.byref(h))
             handle = h
         self._h = handle
         self.grid_min, self.dims = np.zeros(3, np.float64), np.zeros(3, np.int32)
         lib().lscqp_grid_info(self._h, self.grid_min.ctypes.data_as(C.c_void_p), self.dims.ctypes.data_as(C.c_void_p))
         self.resolution = float(resolution)
-
-    def _check(self, rc):
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
 
     def close(self):
         if self._h and self._own:
@@ -338,16 +346,16 @@ class Grid:
     def download(self, mission=False):
         """Occupancy, uint8 (dims[1], dims[0]); mission=True: with the start and goal nodes of the last `fields` call cleared."""
         occ = np.zeros((int(self.dims[1]), int(self.dims[0])), np.uint8)
-        self._check((lib().lscqp_grid_download_mission if mission else lib().lscqp_grid_download)(self._h, occ.ctypes.data_as(C.c_void_p)))
+        _call("lscqp_grid_download_mission" if mission else "lscqp_grid_download", self._h, occ)
         return occ
 
     def status(self):
         st = np.zeros(1, np.int32)
-        self._check(lib().lscqp_grid_status(self._h, st.ctypes.data_as(C.c_void_p)))
+        _call("lscqp_grid_status", self._h, st)
         return int(st[0])
 
     def reserve(self, n):
-        self._check(lib().lscqp_grid_reserve(self._h, int(n)))
+        _call("lscqp_grid_reserve", self._h, int(n))
 
     def fields(self, d_start_points, d_goal_points, d_field=None, d_init_d=None, stream=None):
         """lscqp_grid_fields_device: (d_field int32 (n, dims[1], dims[0]), d_init_d int32 (n,)), torch tensors on the device."""
@@ -358,8 +366,7 @@ class Grid:
             d_field = torch.empty((n, int(self.dims[1]), int(self.dims[0])), dtype=torch.int32, device=d_start_points.device)
         if d_init_d is None:
             d_init_d = torch.empty(n, dtype=torch.int32, device=d_start_points.device)
-        s = stream if stream is not None else torch.cuda.current_stream()
-        self._check(lib().lscqp_grid_fields_device(self._h, n, _dptr(d_start_points), _dptr(d_goal_points), _dptr(d_field), _dptr(d_init_d), C.c_void_p(s.cuda_stream)))
+        _call("lscqp_grid_fields_device", self._h, n, d_start_points, d_goal_points, d_field, d_init_d, stream=stream)
         return d_field, d_init_d
 
     def waypoints(self, communication_range, M, dim, d_state, d_plan, d_current_goal, d_field, d_init_d, d_waypoint, stream=None):
@@ -368,14 +375,13 @@ class Grid:
 
         n = d_waypoint.numel() // 3
         out = [torch.empty(n, dtype=torch.int32, device=d_waypoint.device) for _ in range(3)]
-        s = stream if stream is not None else torch.cuda.current_stream()
-        self._check(lib().lscqp_waypoints_device(self._h, float(communication_range), int(M), int(dim), n, _dptr(d_state), _dptr(d_plan), _dptr(d_current_goal),
-                                                 _dptr(d_field), _dptr(d_init_d), _dptr(d_waypoint), _dptr(out[0]), _dptr(out[1]), _dptr(out[2]), C.c_void_p(s.cuda_stream)))
+        _call("lscqp_waypoints_device", self._h, float(communication_range), int(M), int(dim), n, d_state, d_plan, d_current_goal, d_field, d_init_d,
+              d_waypoint, *out, stream=stream)
         return tuple(out)
 
     def reserve_wide(self, n):
         """lscqp_grid_reserve_wide: the work arrays of `waypoints_wide` for n agents (those of `waypoints` included)."""
-        self._check(lib().lscqp_grid_reserve_wide(self._h, int(n)))
+        _call("lscqp_grid_reserve_wide", self._h, int(n))
 
     def waypoints_wide(self, communication_range, M, dim, d_state, d_plan, d_current_goal, d_field, d_init_d, d_waypoint, stream=None):
         """lscqp_waypoints_wide_device: `waypoints` spread over the device; same arguments, the same outputs bit for bit."""
@@ -383,16 +389,14 @@ class Grid:
 
         n = d_waypoint.numel() // 3
         out = [torch.empty(n, dtype=torch.int32, device=d_waypoint.device) for _ in range(3)]
-        s = stream if stream is not None else torch.cuda.current_stream()
-        self._check(lib().lscqp_waypoints_wide_device(self._h, float(communication_range), int(M), int(dim), n, _dptr(d_state), _dptr(d_plan), _dptr(d_current_goal),
-                                                      _dptr(d_field), _dptr(d_init_d), _dptr(d_waypoint), _dptr(out[0]), _dptr(out[1]), _dptr(out[2]),
-                                                      C.c_void_p(s.cuda_stream)))
+        _call("lscqp_waypoints_wide_device", self._h, float(communication_range), int(M), int(dim), n, d_state, d_plan, d_current_goal, d_field, d_init_d,
+              d_waypoint, *out, stream=stream)
         return tuple(out)
 
     def mission_status(self, n_missions):
         """lscqp_grid_mission_status: int32 (n_missions,), the word of each mission's waypoint walk."""
         st = np.zeros(int(n_missions), np.int32)
-        self._check(lib().lscqp_grid_mission_status(self._h, int(n_missions), st.ctypes.data_as(C.c_void_p)))
+        _call("lscqp_grid_mission_status", self._h, int(n_missions), st)
         return st
 
     def fields_missions(self, offsets, d_start_points, d_goal_points, d_field=None, d_init_d=None, stream=None, d_offsets=None):
@@ -406,9 +410,7 @@ class Grid:
             d_field = torch.empty((n, int(self.dims[1]), int(self.dims[0])), dtype=torch.int32, device=d_start_points.device)
         if d_init_d is None:
             d_init_d = torch.empty(n, dtype=torch.int32, device=d_start_points.device)
-        s = stream if stream is not None else torch.cuda.current_stream()
-        self._check(lib().lscqp_grid_fields_missions_device(self._h, n, K, off.ctypes.data_as(C.c_void_p), _dptr(d_off), _dptr(d_start_points), _dptr(d_goal_points),
-                                                            _dptr(d_field), _dptr(d_init_d), C.c_void_p(s.cuda_stream)))
+        s = _call("lscqp_grid_fields_missions_device", self._h, n, K, off, d_off, d_start_points, d_goal_points, d_field, d_init_d, stream=stream)
         if d_offsets is None:
             s.synchronize()  # (d_off is this call's own)
         return d_field, d_init_d
@@ -422,10 +424,8 @@ class Grid:
         n = d_waypoint.numel() // 3
         K, off, d_off = mission_offsets_arg(offsets, d_waypoint.device, d_offsets)
         out = [torch.empty(n, dtype=torch.int32, device=d_waypoint.device) for _ in range(3)]
-        s = stream if stream is not None else torch.cuda.current_stream()
-        self._check(lib().lscqp_waypoints_missions_device(self._h, float(communication_range), int(M), int(dim), n, K, off.ctypes.data_as(C.c_void_p), _dptr(d_off),
-                                                          _dptr(d_state), _dptr(d_plan), _dptr(d_current_goal), _dptr(d_field), _dptr(d_init_d), _dptr(d_waypoint),
-                                                          _dptr(out[0]), _dptr(out[1]), _dptr(out[2]), C.c_void_p(s.cuda_stream)))
+        s = _call("lscqp_waypoints_missions_device", self._h, float(communication_range), int(M), int(dim), n, K, off, d_off, d_state, d_plan,
+                  d_current_goal, d_field, d_init_d, d_waypoint, *out, stream=stream)
         if d_offsets is None:
             s.synchronize()
         return tuple(out)
@@ -463,15 +463,9 @@ class Record:
         if offsets is not None:
             K, off, _ = mission_offsets_arg(offsets)
         h = C.c_void_p()
-        rc = lib().lscqp_record_create(solver._h, self.n_total, K, None if off is None else off.ctypes.data_as(C.c_void_p), self.n_samples,
-                                       float(record_time_step), float(time_step), float(z_2d), C.byref(d), C.byref(h))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_record_create", solver._h, self.n_total, K, off, self.n_samples, float(record_time_step), float(time_step), float(z_2d), C.byref(d),
+              C.byref(h))
         self._r, self.n_missions, self._solver = h, K, solver
-
-    def _check(self, rc):
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
 
     def close(self):
         if self._r and self._own:
@@ -486,18 +480,17 @@ class Record:
 
     def reset(self, goal_points):
         gp = np.ascontiguousarray(goal_points, dtype=np.float64).reshape(self.n_total, 3)
-        self._check(lib().lscqp_record_reset(self._r, gp.ctypes.data_as(C.c_void_p)))
+        _call("lscqp_record_reset", self._r, gp)
 
     def step_device(self, d_hdr, d_x_all, d_status, d_goal_status, d_sfc_status, d_valid, d_in_range, d_safety, d_waypoint_updated=None, stream=None):
-        sp = C.c_void_p(stream.cuda_stream) if stream is not None else None
-        self._check(lib().lscqp_record_step_device(self._r, _dptr(d_hdr), _dptr(d_x_all), _dptr(d_status), _dptr(d_goal_status), _dptr(d_sfc_status),
-                                                   _dptr(d_valid), _dptr(d_in_range), _dptr(d_safety), _dptr(d_waypoint_updated), sp))
+        _call("lscqp_record_step_device", self._r, d_hdr, d_x_all, d_status, d_goal_status, d_sfc_status, d_valid, d_in_range, d_safety, d_waypoint_updated,
+              _stream_or_null(stream))
 
     def download(self):
         """(records (K,) MISSION_RECORD_DTYPE, agent distances (n_total,) float64); waits for the device."""
         rec = np.zeros(self.n_missions, MISSION_RECORD_DTYPE)
         dist = np.zeros(self.n_total, np.float64)
-        self._check(lib().lscqp_record_download(self._r, rec.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p)))
+        _call("lscqp_record_download", self._r, rec, dist)
         return rec, dist
 
     def points(self):
@@ -515,7 +508,7 @@ class Record:
 
     def unfinished(self):
         w = C.c_int32()
-        self._check(lib().lscqp_record_unfinished(self._r, C.byref(w)))
+        _call("lscqp_record_unfinished", self._r, C.byref(w))
         return int(w.value)
 
 
@@ -567,16 +560,14 @@ class Plan:
         if ag.shape != (n_total,):
             raise ValueError("agents: one AGENT_PARAM_DTYPE record per agent of the mission")
         h = C.c_void_p()
-        rc = lib().lscqp_plan_create(solver._h, world_map._h if world_map is not None else None, C.byref(d), ag.ctypes.data_as(C.c_void_p), C.byref(h))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_plan_create", solver._h, world_map._h if world_map is not None else None, C.byref(d), ag, C.byref(h))
         self._p, self._solver, self._map = h, solver, world_map  # (keeps the solver and the map alive)
         self.n_agents, self.n_total, self.first_agent, self.n_obs, self.M, self.nv = n_agents, n_total, first_agent, n_obs, solver.desc.M, solver.nv
         self._dt = dict(self._DT)
         self._dt.update({PLAN_HEADER: HEADER_DTYPE, PLAN_ROWS: ROW_DTYPE, PLAN_SFC: BOX_DTYPE, PLAN_INFO: INFO_DTYPE, PLAN_SAFETY: SAFETY_DTYPE})
         self.waypoint_mode, self.grid_resolution, self._safety_samples = int(waypoint_mode), float(grid_resolution), int(safety_samples)
         if self.waypoint_mode == WAYPOINT_GRID_PIBT and float(grid_resolution) != 0.5:
-            self._check(lib().lscqp_plan_set_grid(self._p, float(grid_resolution)))
+            _call("lscqp_plan_set_grid", self._p, float(grid_resolution))
         if mission_offsets is not None:
             try:
                 self.set_missions(mission_offsets)
@@ -587,28 +578,25 @@ class Plan:
     def set_missions(self, offsets):
         """lscqp_plan_set_missions: offsets[0..K] cut the agents into K independent missions over the plan's map (None or K <= 1: one
         mission).  Call it before `reset`."""
-        if offsets is None:
-            self._check(lib().lscqp_plan_set_missions(self._p, 0, None))
-            return
-        K, off, _ = mission_offsets_arg(offsets)
-        self._check(lib().lscqp_plan_set_missions(self._p, K, off.ctypes.data_as(C.c_void_p)))
+        K, off = (0, None) if offsets is None else mission_offsets_arg(offsets)[:2]
+        _call("lscqp_plan_set_missions", self._p, K, off)
 
     def set_waypoint_decision(self, which):
         """lscqp_plan_set_waypoint_decision: DECISION_ONE_WORKGROUP (default), DECISION_WIDE or DECISION_AUTO; waypoint_mode 1 only."""
-        self._check(lib().lscqp_plan_set_waypoint_decision(self._p, int(which)))
+        _call("lscqp_plan_set_waypoint_decision", self._p, int(which))
 
     def missions(self):
         """lscqp_plan_missions: the partition's offsets, int64 (K + 1,); [0, n_total] without one."""
         K = C.c_int32()
-        self._check(lib().lscqp_plan_missions(self._p, C.byref(K), None))
+        _call("lscqp_plan_missions", self._p, C.byref(K), None)
         off = np.zeros(K.value + 1, np.int64)
-        self._check(lib().lscqp_plan_missions(self._p, C.byref(K), off.ctypes.data_as(C.c_void_p)))
+        _call("lscqp_plan_missions", self._p, C.byref(K), off)
         return off
 
     def mission_status(self):
         """lscqp_plan_mission_status: int32 (K,), 1 where a mission's waypoint walk reached its bound."""
         st = np.zeros(len(self.missions()) - 1, np.int32)
-        self._check(lib().lscqp_plan_mission_status(self._p, st.ctypes.data_as(C.c_void_p)))
+        _call("lscqp_plan_mission_status", self._p, st)
         return st
 
     def grid(self):
@@ -627,14 +615,10 @@ class Plan:
         except Exception:
             pass
 
-    def _check(self, rc):
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
-
     def reset(self, start_positions, goal_points=None):
         sp = np.ascontiguousarray(start_positions, dtype=np.float64).reshape(self.n_total, 3)
         gp = None if goal_points is None else np.ascontiguousarray(goal_points, dtype=np.float64).reshape(self.n_total, 3)
-        self._check(lib().lscqp_plan_reset(self._p, sp.ctypes.data_as(C.c_void_p), None if gp is None else gp.ctypes.data_as(C.c_void_p)))
+        _call("lscqp_plan_reset", self._p, sp, gp)
 
     def pointer(self, which):
         nb = C.c_uint64()
@@ -644,7 +628,7 @@ class Plan:
     def get(self, which):
         _, nb = self.pointer(which)
         out = np.zeros(nb // np.dtype(self._dt[which]).itemsize, dtype=self._dt[which])
-        self._check(lib().lscqp_plan_download(self._p, which, out.ctypes.data_as(C.c_void_p), 0, nb))
+        _call("lscqp_plan_download", self._p, which, out, 0, nb)
         return out
 
     def put(self, which, array, first=0):
@@ -654,7 +638,7 @@ class Plan:
         per = {PLAN_STATE: 72, PLAN_WAYPOINT: 24, PLAN_GOAL: 24, PLAN_PLAN: 8 * self.nv, PLAN_SFC: 48 * self.M}.get(which)
         if per is None:
             raise ValueError("not an input buffer")
-        self._check(lib().lscqp_plan_upload(self._p, which, a.ctypes.data_as(C.c_void_p), first * per, a.nbytes))
+        _call("lscqp_plan_upload", self._p, which, a, first * per, a.nbytes)
 
     def tensor(self, which):
         """Zero-copy torch view of a float64 buffer of the plan (PLAN_PLAN, PLAN_STATE, PLAN_GOAL, ...): what
@@ -673,19 +657,14 @@ class Plan:
     def step(self, stream=None, graph=False):
         if getattr(self, "_solver", None) is not None:
             self._solver._sync_knobs()
-        sp = C.c_void_p(stream.cuda_stream) if stream is not None else None
-        self._check((lib().lscqp_plan_step_graph if graph else lib().lscqp_plan_step)(self._p, sp))
+        _call("lscqp_plan_step_graph" if graph else "lscqp_plan_step", self._p, _stream_or_null(stream))
 
     def graph_nodes(self):
         return int(lib().lscqp_plan_graph_nodes(self._p))
 
     def set_record(self, goal_threshold=0.1):
         """lscqp_plan_set_record: the plan keeps a mission record, accumulated by the chain's last node (None: no record).  `reset` must follow."""
-        if goal_threshold is None:
-            self._check(lib().lscqp_plan_set_record(self._p, None))
-            return
-        d = RecordDesc(float(goal_threshold))
-        self._check(lib().lscqp_plan_set_record(self._p, C.byref(d)))
+        _call("lscqp_plan_set_record", self._p, None if goal_threshold is None else C.byref(RecordDesc(float(goal_threshold))))
 
     def record(self):
         """The plan's own Record (owned by the plan), None without one."""
@@ -698,18 +677,15 @@ class Plan:
         """lscqp_plan_run: replans until every mission of the record has finished or max_replans; returns the replans enqueued."""
         if getattr(self, "_solver", None) is not None:
             self._solver._sync_knobs()
-        sp = C.c_void_p(stream.cuda_stream) if stream is not None else None
         n = C.c_int64()
-        self._check(lib().lscqp_plan_run(self._p, int(max_replans), int(check_every), int(bool(graph)), sp, C.byref(n)))
+        _call("lscqp_plan_run", self._p, int(max_replans), int(check_every), int(bool(graph)), _stream_or_null(stream), C.byref(n))
         return int(n.value)
 
 
 def shard_range(n, n_used, g):
     """lscqp_shard_range: block [first, first + count) of device g when n agents are spread over n_used devices."""
     f, c = C.c_int64(), C.c_int64()
-    rc = lib().lscqp_shard_range(n, n_used, g, C.byref(f), C.byref(c))
-    if rc != OK:
-        raise LscqpError(rc, lib().lscqp_last_error().decode())
+    _call("lscqp_shard_range", n, n_used, g, C.byref(f), C.byref(c))
     return f.value, c.value
 
 
@@ -728,11 +704,9 @@ def exchange_schedule(n_total, first, count, per=1, pad_agents=None):
     ops = np.zeros(max(len(first), 1), EXCHANGE_OP_DTYPE)
     n = C.c_int32()
     if pad_agents is not None:
-        rc = lib().lscqp_exchange_schedule_padded(int(n_total), len(first), first.ctypes.data, count.ctypes.data, int(per), int(pad_agents), ops.ctypes.data, len(ops), C.byref(n))
+        _call("lscqp_exchange_schedule_padded", int(n_total), len(first), first, count, int(per), int(pad_agents), ops, len(ops), C.byref(n))
     else:
-        rc = lib().lscqp_exchange_schedule(int(n_total), len(first), first.ctypes.data, count.ctypes.data, int(per), ops.ctypes.data, len(ops), C.byref(n))
-    if rc != OK:
-        raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_exchange_schedule", int(n_total), len(first), first, count, int(per), ops, len(ops), C.byref(n))
     return ops[: n.value]
 
 
@@ -742,9 +716,7 @@ class Comm:
     def __init__(self, n_devices=0, device_ids=None):
         self._h = C.c_void_p()
         ids = None if device_ids is None else np.ascontiguousarray(device_ids, dtype=np.int32)
-        rc = lib().lscqp_comm_create(int(n_devices), None if ids is None else ids.ctypes.data_as(C.c_void_p), C.byref(self._h))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_comm_create", int(n_devices), ids, C.byref(self._h))
         self.size = lib().lscqp_comm_size(self._h)
         self.backend = lib().lscqp_comm_backend(self._h).decode()
 
@@ -760,9 +732,7 @@ class Comm:
             pass
 
     def set_min_agents_per_device(self, n):
-        rc = lib().lscqp_comm_set_min_agents_per_device(self._h, int(n))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_comm_set_min_agents_per_device", self._h, int(n))
 
     def devices_for(self, n):
         return lib().lscqp_comm_devices_for(self._h, int(n))
@@ -773,17 +743,13 @@ class Comm:
 
     def prepare(self, solver):
         """lscqp_comm_prepare: the solver's active-set tables on every device of the communicator."""
-        rc = lib().lscqp_comm_prepare(self._h, solver._h)
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_comm_prepare", self._h, solver._h)
 
     def stream(self, g):
         return lib().lscqp_comm_stream(self._h, g)
 
     def synchronize(self):
-        rc = lib().lscqp_comm_synchronize(self._h)
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_comm_synchronize", self._h)
 
     def plan_group_step(self, plans, graph=False):
         """lscqp_plan_group_step: plans[g] lives on device g and owns its block of the mission's agents; every plan's replan is
@@ -791,9 +757,7 @@ class Comm:
         if len(plans) != self.size:
             raise ValueError("one plan per device of the communicator")
         arr = (C.c_void_p * self.size)(*[p._p.value for p in plans])
-        rc = lib().lscqp_plan_group_step(self._h, arr, int(bool(graph)))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_plan_group_step", self._h, arr, int(bool(graph)))
 
     def allgather(self, send, recv, count):
         """send / recv: lists of torch CUDA tensors, one per device (device g contributes send[g][:count] doubles and
@@ -801,9 +765,7 @@ class Comm:
         vp = C.c_void_p * self.size
         ps = vp(*[t.data_ptr() for t in send])
         pr = vp(*[t.data_ptr() for t in recv])
-        rc = lib().lscqp_allgather(self._h, ps, pr, int(count))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_allgather", self._h, ps, pr, int(count))
 
 
 # The library reads its environment when a handle is CREATED and never afterwards (csrc/lscqp_api.hip: Knobs).  The test suite and bench.py
@@ -822,9 +784,7 @@ class Solver:
         self.desc = desc
         self._h = C.c_void_p()
         self._knob_seen = _knob_env()
-        rc = lib().lscqp_create(C.byref(desc), C.byref(self._h))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_create", C.byref(desc), C.byref(self._h))
         self.nv = lib().lscqp_num_variables(self._h)
         self.M, self.dim, self.P = desc.M, desc.dim, desc.M * 6
 
@@ -837,14 +797,10 @@ class Solver:
     def set_knob(self, name, value):
         """lscqp_debug_set_knob_ (library-internal): one of the handle's development switches by name, e.g. the launch-shape overrides of
         the dual active-set phase (das_threads, das_kmax, das_steps, das_cache, das_stage, das_screen, das_loop; -1 = the policy's value)."""
-        rc = lib().lscqp_debug_set_knob_(self._h, name.encode(), int(value))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_debug_set_knob_", self._h, name.encode(), int(value))
 
     def prepare_device(self):
-        rc = lib().lscqp_prepare_device(self._h)
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_prepare_device", self._h)
 
     def bind_device(self, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, d_x, d_obj, d_status, d_info=None, stream=None, d_x_init=None, retry=False,
                     d_order=None):
@@ -855,10 +811,7 @@ class Solver:
 
         self._sync_knobs()
         s = stream if stream is not None else torch.cuda.current_stream()
-
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-
+        p = _arg
         fn = lib().lscqp_solve_batch_device_ordered
         args = (self._h, n, n_obs_max, p(d_hdr), p(d_rows), p(d_off), p(d_sfc), p(d_x_init), p(d_x), p(d_obj), p(d_status), p(d_info), int(retry),
                 p(d_order), C.c_void_p(s.cuda_stream))
@@ -896,9 +849,7 @@ class Solver:
             pass
 
     def update(self, desc):
-        rc = lib().lscqp_update(self._h, C.byref(desc))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_update", self._h, C.byref(desc))
         self.desc = desc
 
     def max_obstacles(self):
@@ -908,9 +859,7 @@ class Solver:
         """lscqp_instance_work: work counters (from the machine code) of the kernel instance a launch of n QPs would select."""
         self._sync_knobs()
         w = Work()
-        rc = lib().lscqp_instance_work(self._h, int(n), int(n_obs_max), C.byref(w))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_instance_work", self._h, int(n), int(n_obs_max), C.byref(w))
         return {f: (getattr(w, f).decode() if f == "kernel" else getattr(w, f)) for f, _ in Work._fields_}
 
     def algorithmic_bytes(self, n_obs):
@@ -935,15 +884,9 @@ class Solver:
             assert len(row_offsets) == n + 1
         if sfc is not None:
             sfc = np.ascontiguousarray(sfc, dtype=BOX_DTYPE).reshape(-1)
-
-        def p(a):
-            return None if a is None else a.ctypes.data_as(C.c_void_p)
-
         if x_init is not None:
             x_init = np.ascontiguousarray(x_init, dtype=np.float64).reshape(n, self.nv)
-        rc = lib().lscqp_solve_batch(self._h, n, p(hdr), p(rows), p(row_offsets), p(sfc), p(x_init), p(x), p(obj), p(status), p(info))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_solve_batch", self._h, n, hdr, rows, row_offsets, sfc, x_init, x, obj, status, info)
         return dict(x=x, obj=obj, status=status, info=info)
 
     def solve_sharded(self, comm, hdr, rows=None, row_offsets=None, sfc=None, want_info=True, x_init=None):
@@ -962,15 +905,8 @@ class Solver:
             sfc = np.ascontiguousarray(sfc, dtype=BOX_DTYPE).reshape(-1)
         if x_init is not None:
             x_init = np.ascontiguousarray(x_init, dtype=np.float64).reshape(n, self.nv)
-
-        def p(a):
-            return None if a is None else a.ctypes.data_as(C.c_void_p)
-
         used = C.c_int32(0)
-        rc = lib().lscqp_solve_batch_sharded(self._h, comm._h, n, p(hdr), p(rows), p(row_offsets), p(sfc), p(x_init), p(x), p(obj),
-                                             p(status), p(info), C.cast(C.byref(used), C.c_void_p))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_solve_batch_sharded", self._h, comm._h, n, hdr, rows, row_offsets, sfc, x_init, x, obj, status, info, C.cast(C.byref(used), C.c_void_p))
         return dict(x=x, obj=obj, status=status, info=info, devices_used=used.value)
 
     # ---- failure diagnostics (include/lscqp.h) -------------------------------------------------------------
@@ -985,13 +921,7 @@ class Solver:
         if sfc is not None:
             sfc = np.ascontiguousarray(sfc, dtype=BOX_DTYPE).reshape(-1)
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(n, self.nv)
-
-        def p(a):
-            return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-        rc = lib().lscqp_diagnose(self._h, n, p(hdr), p(rows), p(row_offsets), p(sfc), p(x), float(tol), p(out))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_diagnose", self._h, n, hdr, rows, row_offsets, sfc, x, float(tol), out)
         return out
 
     def dump_instance(self, hdr_one, rows_one, sfc_one, path):
@@ -999,13 +929,7 @@ class Solver:
         hdr = np.ascontiguousarray(hdr_one, dtype=HEADER_DTYPE).reshape(1)
         rows = None if rows_one is None else self.rows_in_format(rows_one)
         sfc = None if sfc_one is None else np.ascontiguousarray(sfc_one, dtype=BOX_DTYPE).reshape(-1)
-
-        def p(a):
-            return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-        rc = lib().lscqp_dump_instance(self._h, p(hdr), p(rows), p(sfc), os.fsencode(path))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_dump_instance", self._h, hdr, rows, sfc, os.fsencode(path))
 
     def solve_sharded_device(self, comm, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, d_x, d_obj, d_status, d_info=None, d_x_init=None, retry=False):
         """lscqp_solve_batch_sharded_device: lists of per-device torch CUDA tensors (entry g lives on device g of `comm`), n[g] agents on
@@ -1018,10 +942,8 @@ class Solver:
             return None if ts is None else vp(*[(None if t is None else t.data_ptr()) for t in ts])
 
         nn = (C.c_int64 * G)(*[int(v) for v in n])
-        rc = lib().lscqp_solve_batch_sharded_device(self._h, comm._h, nn, int(n_obs_max), arr(d_hdr), arr(d_rows), arr(d_off), arr(d_sfc),
-                                                    arr(d_x_init), arr(d_x), arr(d_obj), arr(d_status), arr(d_info), int(bool(retry)))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_solve_batch_sharded_device", self._h, comm._h, nn, int(n_obs_max), arr(d_hdr), arr(d_rows), arr(d_off), arr(d_sfc), arr(d_x_init),
+              arr(d_x), arr(d_obj), arr(d_status), arr(d_info), int(bool(retry)))
 
     # ---- device-pointer call (torch tensors hold the HBM buffers) --------------------------------------
     def solve_device(self, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, d_x, d_obj, d_status, d_info=None, stream=None,
@@ -1029,26 +951,14 @@ class Solver:
         """All arguments are torch CUDA tensors (any dtype; only data_ptr() is used) or None.
         Asynchronous on `stream` (torch.cuda.Stream) or torch's current stream.  retry: lscqp_solve_batch_device_ex's second pass.
         d_order: int32 permutation of 0 .. n-1 (lscqp_solve_batch_device_ordered: the k-th slot of the launch solves instance d_order[k])."""
-        import torch
-
         self._sync_knobs()
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-
-        rc = lib().lscqp_solve_batch_device_ordered(self._h, n, n_obs_max, p(d_hdr), p(d_rows), p(d_off), p(d_sfc), p(d_x_init), p(d_x),
-                                                    p(d_obj), p(d_status), p(d_info), int(retry), p(d_order), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_solve_batch_device_ordered", self._h, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, d_x_init, d_x, d_obj, d_status, d_info, int(retry),
+              d_order, stream=stream)
 
     # ---- the prescreen (include/lscqp.h) --------------------------------------------------------------------
     def set_prescreen(self, mode):
         """lscqp_set_prescreen: PRESCREEN_ON / PRESCREEN_OFF -- the per-control-point infeasibility test in front of every solve of this handle."""
-        rc = lib().lscqp_set_prescreen(self._h, int(mode))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_set_prescreen", self._h, int(mode))
 
     def prescreen(self):
         return lib().lscqp_prescreen(self._h)
@@ -1056,16 +966,7 @@ class Solver:
     def prescreen_device(self, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, d_cert, stream=None):
         """lscqp_prescreen_batch_device: the test alone, one PRESCREEN_CERT_DTYPE record per instance into d_cert (72 n bytes).  Torch CUDA
         tensors (only data_ptr() is used) or None; asynchronous on `stream` or torch's current stream."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-
-        rc = lib().lscqp_prescreen_batch_device(self._h, n, n_obs_max, p(d_hdr), p(d_rows), p(d_off), p(d_sfc), p(d_cert), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_prescreen_batch_device", self._h, n, n_obs_max, d_hdr, d_rows, d_off, d_sfc, d_cert, stream=stream)
 
     def prescreen_host(self, hdr, rows, row_offsets, sfc):
         """The prescreen on host arrays: staged to the current device, tested there, the certificates (PRESCREEN_CERT_DTYPE[n]) fetched back."""
@@ -1099,14 +1000,8 @@ class Solver:
         row_offsets = np.ascontiguousarray(row_offsets, dtype=np.uint64) if row_offsets is not None else None
         sfc = np.ascontiguousarray(sfc, dtype=BOX_DTYPE).reshape(-1) if sfc is not None else None
         out = np.zeros(n, PRESCREEN_CERT_DTYPE)
-
-        def p(a):
-            return None if a is None else a.ctypes.data_as(C.c_void_p)
-
         cap = int(hdr["n_obs"].max()) if n_obs_max is None else int(n_obs_max)
-        rc = lib().lscqp_debug_prescreen_twin_(self._h, n, max(cap, 0), p(hdr), p(rows), p(row_offsets), p(sfc), p(out))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_debug_prescreen_twin_", self._h, n, max(cap, 0), hdr, rows, row_offsets, sfc, out)
         return out
 
     def solve_plan(self, n, n_obs_max, retry=0, part=PLAN_WHOLE, has_x_init=False, has_order=False, deferred=False, n_cu=256, tables_available=True):
@@ -1115,10 +1010,8 @@ class Solver:
         "instance" pass that run in its place when the fused launcher refuses the budgets."""
         self._sync_knobs()
         out = _Plan()
-        rc = lib().lscqp_debug_solve_plan_(self._h, int(n), int(n_obs_max), int(retry), int(part), int(has_x_init), int(has_order), int(deferred),
-                                           int(n_cu), int(tables_available), C.byref(out))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_debug_solve_plan_", self._h, int(n), int(n_obs_max), int(retry), int(part), int(has_x_init), int(has_order), int(deferred), int(n_cu),
+              int(tables_available), C.byref(out))
         passes = []
         for ps in out.passes[:out.n_pass]:
             d = {k: getattr(ps, k) for k, _ in _PlanPass._fields_ if k != "inst"}
@@ -1141,23 +1034,12 @@ class Solver:
     @staticmethod
     def order_by_cost_device(n, d_cost_prev, d_order_out, stream=None):
         """lscqp_order_by_cost_device: d_order_out (int32[n]) := agents by the cost (uint32) of their previous corridor, most expensive first."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-        rc = lib().lscqp_order_by_cost_device(int(n), C.c_void_p(d_cost_prev.data_ptr()), C.c_void_p(d_order_out.data_ptr()), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_order_by_cost_device", int(n), d_cost_prev, d_order_out, stream=stream)
 
     @staticmethod
     def order_by_work_device(n, d_info_prev, d_order_out, stream=None):
         """lscqp_order_by_work_device: d_order_out (int32[n]) := instances by the iterations of their previous solve, most first."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-        rc = lib().lscqp_order_by_work_device(int(n), C.c_void_p(d_info_prev.data_ptr()), C.c_void_p(d_order_out.data_ptr()), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
-
+        _call("lscqp_order_by_work_device", int(n), d_info_prev, d_order_out, stream=stream)
 
     # ---- GoalOptimizer::solve in closed form (SURVEY.md section 8f-2) ----------------------------------------
     def optimize_goal_host(self, hdr, rows=None, row_offsets=None, sfc=None):
@@ -1170,212 +1052,96 @@ class Solver:
             row_offsets = np.ascontiguousarray(row_offsets, dtype=np.uint64)
         if sfc is not None:
             sfc = np.ascontiguousarray(sfc, dtype=BOX_DTYPE).reshape(-1)
-
-        def p(a):
-            return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-        rc = lib().lscqp_optimize_goal(self._h, n, p(hdr), p(rows), p(row_offsets), p(sfc), p(status))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_optimize_goal", self._h, n, hdr, rows, row_offsets, sfc, status)
         return hdr, status
 
     def optimize_goal_device(self, n, d_hdr, d_rows, d_off, d_sfc, d_status, stream=None):
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-
-        rc = lib().lscqp_optimize_goal_device(self._h, n, p(d_hdr), p(d_rows), p(d_off), p(d_sfc), p(d_status), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_optimize_goal_device", self._h, n, d_hdr, d_rows, d_off, d_sfc, d_status, stream=stream)
 
     def optimize_goal_fin_device(self, n, d_hdr, d_rows, d_off, d_sfc, d_status, fin_dt, stream=None):
         """(library-internal, tests) lscqp_optimize_goal_fin_device_: the goal LP as the replan chain runs it -- the goal left as a point3d
         (float32 values) and terminal_segments written from it (fin_dt = the class's dt)."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-        rc = lib().lscqp_optimize_goal_fin_device_(self._h, n, _dptr(d_hdr), _dptr(d_rows), _dptr(d_off), _dptr(d_sfc), _dptr(d_status), float(fin_dt),
-                                                   C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_optimize_goal_fin_device_", self._h, n, d_hdr, d_rows, d_off, d_sfc, d_status, float(fin_dt), stream=stream)
 
     # ---- isSolValid + getStateAt + doStep (SURVEY.md section 8f-3) -------------------------------------------
     def safety_metrics_device(self, n_agents, first_agent, n_total, n_samples, record_time_step, d_x_all, d_radius, d_downwash, d_hdr,
                               d_out, z_2d=1.0, stream=None):
         """MultiSyncSimulator::update's safety ratio / excess ratios per local agent (SAFETY_DTYPE records in d_out)."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        rc = lib().lscqp_safety_metrics_device(self._h, n_agents, first_agent, n_total, int(n_samples), float(record_time_step), float(z_2d),
-                                               p(d_x_all), p(d_radius), p(d_downwash), p(d_hdr), p(d_out), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_safety_metrics_device", self._h, n_agents, first_agent, n_total, int(n_samples), float(record_time_step), float(z_2d), d_x_all,
+              d_radius, d_downwash, d_hdr, d_out, stream=stream)
 
     def safety_obstacles_device(self, n_agents, first_agent, n_total, n_samples, record_time_step, d_x_all, d_radius, d_downwash, n_obstacles,
                                 d_obstacles, d_out, z_2d=1.0, stream=None):
         """MultiSyncSimulator::update's obstacle safety ratio per local agent (SAFETY_OBS_DTYPE records in d_out; d_obstacles: OBSTACLE_DTYPE)."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)  # noqa: E731
-        rc = lib().lscqp_safety_obstacles_device(self._h, n_agents, first_agent, n_total, int(n_samples), float(record_time_step), float(z_2d),
-                                                 p(d_x_all), p(d_radius), p(d_downwash), int(n_obstacles), p(d_obstacles), p(d_out),
-                                                 C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_safety_obstacles_device", self._h, n_agents, first_agent, n_total, int(n_samples), float(record_time_step), float(z_2d), d_x_all,
+              d_radius, d_downwash, int(n_obstacles), d_obstacles, d_out, stream=stream)
 
     def construct_sfc_device(self, world_map, mode, n, d_points, d_radius, d_sfc, d_status, stream=None, d_order=None, d_cost=None):
         """Corridor update of n agents on the device (SFC_INIT / SFC_FROM_HULL / SFC_FROM_POINT, see include/lscqp.h).  d_order: int32
         permutation (workgroup k builds agent d_order[k]'s corridor); d_cost: uint32[n], every agent's cost of this launch."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)  # noqa: E731
-        rc = lib().lscqp_construct_sfc_device_ordered(self._h, world_map._h, int(mode), n, p(d_points), p(d_radius), p(d_sfc), p(d_status),
-                                                      p(d_order), p(d_cost), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_construct_sfc_device_ordered", self._h, world_map._h, int(mode), n, d_points, d_radius, d_sfc, d_status, d_order, d_cost, stream=stream)
 
     def validate_step_device(self, n, time_step, d_x, d_hdr, d_sfc, d_valid, d_state, z_2d=1.0, stream=None):
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-
-        rc = lib().lscqp_validate_step_device(self._h, n, float(time_step), float(z_2d), p(d_x), p(d_hdr), p(d_sfc), p(d_valid),
-                                              p(d_state), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_validate_step_device", self._h, n, float(time_step), float(z_2d), d_x, d_hdr, d_sfc, d_valid, d_state, stream=stream)
 
     def commit_validate_device(self, n, time_step, d_qp_status, d_x_new, d_x_init, d_x_plan, d_goal, d_hdr, d_sfc, d_valid, d_state, z_2d=1.0,
                                stream=None):
         """(library-internal, tests) lscqp_commit_validate_raw_: the replan chain's commit (x_plan = x_new where the QP is OPTIMAL, else
         x_init; goal = hdr.goal) with isSolValid + doStep on the plan it chose, in one launch."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
         d = self.desc
-        rc = lib().lscqp_commit_validate_raw_(int(d.M), int(d.dim), int(d.use_sfc), float(d.dt), n, float(time_step), float(z_2d), _dptr(d_qp_status),
-                                              _dptr(d_x_new), _dptr(d_x_init), _dptr(d_x_plan), _dptr(d_goal), _dptr(d_hdr), _dptr(d_sfc),
-                                              _dptr(d_valid), _dptr(d_state), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_commit_validate_raw_", int(d.M), int(d.dim), int(d.use_sfc), float(d.dt), n, float(time_step), float(z_2d), d_qp_status, d_x_new,
+              d_x_init, d_x_plan, d_goal, d_hdr, d_sfc, d_valid, d_state, stream=stream)
 
     # ---- the producer of the rows (SURVEY.md section 8f-1), device pointers -----------------------------------
     def generate_lsc_device(self, n_agents, n_obs, first_agent, d_traj, d_neighbours, d_radius, d_downwash, d_goal, d_rows,
                             stream=None):
         """TrajPlanner::generateLSC for agent obstacles, rows written in the layout solve_device consumes."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-        rc = lib().lscqp_generate_lsc_device(self._h, n_agents, n_obs, first_agent, C.c_void_p(d_traj.data_ptr()),
-                                             C.c_void_p(d_neighbours.data_ptr()), C.c_void_p(d_radius.data_ptr()),
-                                             C.c_void_p(d_downwash.data_ptr()), C.c_void_p(d_goal.data_ptr()),
-                                             C.c_void_p(d_rows.data_ptr()), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_generate_lsc_device", self._h, n_agents, n_obs, first_agent, d_traj, d_neighbours, d_radius, d_downwash, d_goal, d_rows, stream=stream)
 
     def generate_constraints_device(self, mode, n_agents, n_obs, first_agent, d_traj, d_neighbours, d_radius, d_downwash, d_goal_all,
                                     d_rows, stream=None):
         """generateLSC / generateCLSC / generateBVC (mode GEN_LSC / GEN_CLSC / GEN_BVC) on the device; d_goal_all holds the
         current goal point of every agent, indexed by global id (see include/lscqp.h)."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-        rc = lib().lscqp_generate_constraints_device(self._h, int(mode), n_agents, n_obs, first_agent, C.c_void_p(d_traj.data_ptr()),
-                                                     C.c_void_p(d_neighbours.data_ptr()), C.c_void_p(d_radius.data_ptr()),
-                                                     C.c_void_p(d_downwash.data_ptr()), C.c_void_p(d_goal_all.data_ptr()),
-                                                     C.c_void_p(d_rows.data_ptr()), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_generate_constraints_device", self._h, int(mode), n_agents, n_obs, first_agent, d_traj, d_neighbours, d_radius, d_downwash, d_goal_all,
+              d_rows, stream=stream)
 
     def select_neighbours_device(self, n_agents, first_agent, n_total, n_obs, comm_range, d_positions, d_neighbours, d_count, stream=None):
         """broadcastMsgs' range filter on the device: neighbour ids (ascending, -1 padded) and the in-range counts."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-        rc = lib().lscqp_select_neighbours_device(self._h, n_agents, first_agent, n_total, int(n_obs), float(comm_range),
-                                                  C.c_void_p(d_positions.data_ptr()), C.c_void_p(d_neighbours.data_ptr()),
-                                                  C.c_void_p(d_count.data_ptr()), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_select_neighbours_device", self._h, n_agents, first_agent, n_total, int(n_obs), float(comm_range), d_positions, d_neighbours, d_count,
+              stream=stream)
 
     def select_neighbours_missions_device(self, offsets, n_obs, comm_range, d_positions, d_neighbours, d_count, stream=None):
         """select_neighbours_device with the agent's own mission of the partition `offsets` (host, [K + 1]) as its candidates."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
         K, off, d_off = mission_offsets_arg(offsets, d_positions.device)
-        rc = lib().lscqp_select_neighbours_missions_device(self._h, int(off[-1]), K, off.ctypes.data_as(C.c_void_p), _dptr(d_off), int(n_obs), float(comm_range),
-                                                           _dptr(d_positions), _dptr(d_neighbours), _dptr(d_count), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        s = _call("lscqp_select_neighbours_missions_device", self._h, int(off[-1]), K, off, d_off, int(n_obs), float(comm_range), d_positions, d_neighbours,
+                  d_count, stream=stream)
         s.synchronize()  # (d_off is this call's own)
 
     def safety_metrics_missions_device(self, offsets, n_samples, record_time_step, d_x_all, d_radius, d_downwash, d_hdr, d_out, z_2d=1.0, stream=None):
         """safety_metrics_device over the pairs within each mission of the partition `offsets` (host, [K + 1])."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
         K, off, d_off = mission_offsets_arg(offsets, d_x_all.device)
-        rc = lib().lscqp_safety_metrics_missions_device(self._h, int(off[-1]), K, off.ctypes.data_as(C.c_void_p), _dptr(d_off), int(n_samples), float(record_time_step),
-                                                        float(z_2d), _dptr(d_x_all), _dptr(d_radius), _dptr(d_downwash), _dptr(d_hdr), _dptr(d_out),
-                                                        C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        s = _call("lscqp_safety_metrics_missions_device", self._h, int(off[-1]), K, off, d_off, int(n_samples), float(record_time_step), float(z_2d), d_x_all,
+                  d_radius, d_downwash, d_hdr, d_out, stream=stream)
         s.synchronize()
 
     def shift_traj_device(self, n, d_x_prev, d_traj, z_2d=1.0, shift=1, stream=None):
         """initialTrajPlanningPrevSol: solver output [n][dim*M*6] -> initial trajectories [n][M][6][3] (float32 values)."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-        rc = lib().lscqp_shift_traj_device(self._h, n, int(shift), float(z_2d), C.c_void_p(d_x_prev.data_ptr()), C.c_void_p(d_traj.data_ptr()),
-                                           C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_shift_traj_device", self._h, n, int(shift), float(z_2d), d_x_prev, d_traj, stream=stream)
 
     def shift_traj_partial_device(self, n, d_x_prev, d_traj, fraction, z_2d=1.0, stream=None):
         """multisim_time_step < dt: segment 0 := subSegment(fraction, 1) of the previous plan's, the others kept."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-        rc = lib().lscqp_shift_traj_partial_device(self._h, n, float(fraction), float(z_2d), C.c_void_p(d_x_prev.data_ptr()),
-                                                   C.c_void_p(d_traj.data_ptr()), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_shift_traj_partial_device", self._h, n, float(fraction), float(z_2d), d_x_prev, d_traj, stream=stream)
 
     def generate_constraints_device_ex(self, mode, n_agents, n_obs, first_agent, d_traj, d_neighbours, d_radius, d_downwash, d_goal_all,
                                        d_rows, n_obs_total, slot0, stream=None):
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-        rc = lib().lscqp_generate_constraints_device_ex(self._h, int(mode), n_agents, n_obs, first_agent, C.c_void_p(d_traj.data_ptr()),
-                                                        C.c_void_p(d_neighbours.data_ptr()), C.c_void_p(d_radius.data_ptr()),
-                                                        C.c_void_p(d_downwash.data_ptr()), C.c_void_p(d_goal_all.data_ptr()),
-                                                        C.c_void_p(d_rows.data_ptr()), int(n_obs_total), int(slot0), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_generate_constraints_device_ex", self._h, int(mode), n_agents, n_obs, first_agent, d_traj, d_neighbours, d_radius, d_downwash,
+              d_goal_all, d_rows, int(n_obs_total), int(slot0), stream=stream)
 
     def generate_lsc_obstacles_device(self, param, n_agents, n_dyn, first_agent, d_traj, d_ids, d_obstacles, d_radius, d_goal, d_hdr, d_rows,
                                       n_obs_total, slot0, stream=None):
         """generateLSC for non-agent obstacles (param: ObstacleParam; d_obstacles: OBSTACLE_DTYPE table on the device)."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream()
-        rc = lib().lscqp_generate_lsc_obstacles_device(self._h, C.cast(C.byref(param), C.c_void_p), n_agents, n_dyn, first_agent,
-                                                       C.c_void_p(d_traj.data_ptr()), C.c_void_p(d_ids.data_ptr()),
-                                                       C.c_void_p(d_obstacles.data_ptr()), C.c_void_p(d_radius.data_ptr()),
-                                                       C.c_void_p(d_goal.data_ptr()), C.c_void_p(d_hdr.data_ptr()), C.c_void_p(d_rows.data_ptr()),
-                                                       int(n_obs_total), int(slot0), C.c_void_p(s.cuda_stream))
-        if rc != OK:
-            raise LscqpError(rc, lib().lscqp_last_error().decode())
+        _call("lscqp_generate_lsc_obstacles_device", self._h, C.cast(C.byref(param), C.c_void_p), n_agents, n_dyn, first_agent, d_traj, d_ids, d_obstacles,
+              d_radius, d_goal, d_hdr, d_rows, int(n_obs_total), int(slot0), stream=stream)
 
     def generate_lsc_bytes(self, n_agents, n_obs, n_total):
         return lib().lscqp_generate_lsc_bytes(self._h, n_agents, n_obs, n_total)

@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <string>
+#include <cmath>
 
 #include "../../include/lscqp.h"
 #include "lscqp_internal.hpp"
@@ -769,26 +769,39 @@ __global__ __launch_bounds__(64) void select_neighbours_kernel(int64_t n_agents,
 
 }  // namespace lscgen
 
-extern "C" int lscqp_select_neighbours_raw_(int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_obs, double range,
-                                            const double* d_pos, int32_t* d_nbr, int32_t* d_count, void* stream) {
+// The public device entries (include/lscqp.h): every check in front of its launch.  What they need of the handle: the class description, the
+// row format (lscqp_row_bytes) and P = 6 M.
+static int rows_f32_of(lscqp_handle h) { return lscqp_row_bytes(h) == (int)sizeof(lscqp_row_f32); }
+
+extern "C" int lscqp_select_neighbours_device(lscqp_handle h, int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_obs,
+                                              double communication_range, const double* d_positions, int32_t* d_neighbours_out,
+                                              int32_t* d_count_out, void* stream) {
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_agents < 0 || first_agent < 0 || n_obs < 0 || n_total < first_agent + n_agents)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
     if (n_agents == 0) return LSCQP_OK;
+    if (!d_positions || !d_count_out || (n_obs > 0 && !d_neighbours_out)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
     hipLaunchKernelGGL(lscgen::select_neighbours_kernel<false>, dim3((unsigned)n_agents), dim3(64), 0, (hipStream_t)stream, n_agents, first_agent,
-                       n_total, n_obs, range, d_pos, d_nbr, d_count, (const int64_t*)nullptr, 0);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
-    return LSCQP_OK;
+                       n_total, n_obs, communication_range, d_positions, d_neighbours_out, d_count_out, (const int64_t*)nullptr, 0);
+    return lscqp_launch_result_(hipGetLastError());
 }
 
-extern "C" int lscqp_select_neighbours_missions_raw_(int64_t n_total, int32_t n_missions, const int64_t* d_off, int32_t n_obs, double range,
-                                                     const double* d_pos, int32_t* d_nbr, int32_t* d_count, void* stream) {
-    if (n_total == 0) return LSCQP_OK;
+extern "C" int lscqp_select_neighbours_missions_device(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
+                                                       const int64_t* d_mission_offsets, int32_t n_obs, double communication_range,
+                                                       const double* d_positions, int32_t* d_neighbours_out, int32_t* d_count_out, void* stream) {
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_total < 0 || n_obs < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
+    if (const int rc = lscqp_check_missions_(n_total, n_missions, mission_offsets)) return rc;  // (a partition has no empty mission: n_total > 0)
+    if (!d_mission_offsets || !d_positions || !d_count_out || (n_obs > 0 && !d_neighbours_out))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
     hipLaunchKernelGGL(lscgen::select_neighbours_kernel<true>, dim3((unsigned)n_total), dim3(64), 0, (hipStream_t)stream, n_total, (int64_t)0, n_total,
-                       n_obs, range, d_pos, d_nbr, d_count, d_off, (int)n_missions);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
-    return LSCQP_OK;
+                       n_obs, communication_range, d_positions, d_neighbours_out, d_count_out, d_mission_offsets, (int)n_missions);
+    return lscqp_launch_result_(hipGetLastError());
 }
 
+// (library-internal: the four generator entries below, and the tests for M = 1) one launch of the generator, no checks
 extern "C" int lscqp_generate_lsc_raw_(int mode, int M, int dim, int64_t n_agents, int32_t n_obs, int64_t first_agent,
                                        const double* d_traj, const double* d_own_traj, const int32_t* d_neighbours, const double* d_radius,
                                        const double* d_downwash, const double* d_goal, const double* d_goal_all, int rows_f32,
@@ -801,47 +814,162 @@ extern "C" int lscqp_generate_lsc_raw_(int mode, int M, int dim, int64_t n_agent
                                          : lscgen::generate_lsc_kernel<LSCQP_GEN_LSC>;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(lscgen::kThreads), 0, (hipStream_t)stream, M, dim, n_units, n_obs, first_agent, d_traj,
                        d_own_traj, d_neighbours, d_radius, d_downwash, d_goal, d_goal_all, rows_f32, n_obs_total, slot0, d_rows_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
-    return LSCQP_OK;
+    return lscqp_launch_result_(hipGetLastError());
 }
 
-extern "C" int lscqp_shift_traj_partial_raw_(int M, int dim, int64_t n, const double* w36, double z_2d, const double* d_x_prev, double* d_traj,
-                                             void* stream) {
-    const int64_t total = n * M * 6;
-    if (total == 0) return LSCQP_OK;
-    lscgen::SubSegW W;
-    for (int i = 0; i < 36; i++) W.w[i] = w36[i];
-    const unsigned blocks = (unsigned)((total + lscgen::kThreads - 1) / lscgen::kThreads);
-    hipLaunchKernelGGL(lscgen::shift_traj_partial_kernel, dim3(blocks), dim3(lscgen::kThreads), 0, (hipStream_t)stream, M, dim, n, W, z_2d,
-                       d_x_prev, d_traj);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
-    return LSCQP_OK;
+extern "C" int lscqp_generate_lsc_device(lscqp_handle h, int64_t n_agents, int32_t n_obs, int64_t first_agent, const double* d_traj,
+                                         const int32_t* d_neighbours, const double* d_radius, const double* d_downwash,
+                                         const double* d_goal, lscqp_row* d_rows_out, void* stream) {
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_agents < 0 || n_obs < 0 || first_agent < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
+    if (n_agents == 0 || n_obs == 0) return LSCQP_OK;
+    if (!d_traj || !d_neighbours || !d_radius || !d_downwash || !d_goal || !d_rows_out)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
+    const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
+    return lscqp_generate_lsc_raw_(LSCQP_GEN_LSC, cd->M, cd->dim, n_agents, n_obs, first_agent, d_traj, nullptr, d_neighbours, d_radius, d_downwash,
+                                   d_goal, nullptr, rows_f32_of(h), n_obs, 0, d_rows_out, stream);
 }
 
-extern "C" int lscqp_generate_lsc_obstacles_raw_(int M, int dim, double dt, const lscqp_obstacle_param* p, int64_t n_agents, int32_t n_dyn,
-                                                 int64_t first_agent, const double* d_traj, const int32_t* d_ids, const lscqp_obstacle* d_table,
-                                                 const double* d_radius, const double* d_goal, const lscqp_header* d_hdr, int rows_f32,
-                                                 int32_t n_obs_total, int32_t slot0, const double* d_binv3, lscqp_row* d_rows_out, void* stream) {
-    const int64_t n_units = n_agents * (int64_t)n_dyn * M;
-    if (n_units == 0) return LSCQP_OK;
+extern "C" int lscqp_generate_constraints_own_(lscqp_handle h, int32_t mode, int64_t n_agents, int32_t n_obs, int64_t first_agent,
+                                               const double* d_traj, const double* d_own_traj, const int32_t* d_neighbours, const double* d_radius,
+                                               const double* d_downwash, const double* d_goal_all, lscqp_row* d_rows_out, int32_t n_obs_total,
+                                               int32_t slot0, void* stream) {
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (slot0 < 0 || n_obs_total < slot0 + n_obs) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "n_obs_total >= slot0 + n_obs required");
+    if (mode != LSCQP_GEN_LSC && mode != LSCQP_GEN_CLSC && mode != LSCQP_GEN_BVC)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "mode must be LSCQP_GEN_LSC, LSCQP_GEN_CLSC or LSCQP_GEN_BVC");
+    if (n_agents < 0 || n_obs < 0 || first_agent < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
+    if (n_agents == 0 || n_obs == 0) return LSCQP_OK;
+    if (!d_traj || !d_neighbours || !d_radius || !d_downwash || !d_goal_all || !d_rows_out)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
+    const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
+    return lscqp_generate_lsc_raw_(mode, cd->M, cd->dim, n_agents, n_obs, first_agent, d_traj, d_own_traj, d_neighbours, d_radius, d_downwash,
+                                   d_goal_all + 3 * first_agent, d_goal_all, rows_f32_of(h), n_obs_total, slot0, d_rows_out, stream);
+}
+
+extern "C" int lscqp_generate_constraints_device_ex(lscqp_handle h, int32_t mode, int64_t n_agents, int32_t n_obs, int64_t first_agent,
+                                                    const double* d_traj, const int32_t* d_neighbours, const double* d_radius,
+                                                    const double* d_downwash, const double* d_goal_all, lscqp_row* d_rows_out,
+                                                    int32_t n_obs_total, int32_t slot0, void* stream) {
+    return lscqp_generate_constraints_own_(h, mode, n_agents, n_obs, first_agent, d_traj, nullptr, d_neighbours, d_radius, d_downwash, d_goal_all,
+                                           d_rows_out, n_obs_total, slot0, stream);
+}
+
+extern "C" int lscqp_generate_constraints_device(lscqp_handle h, int32_t mode, int64_t n_agents, int32_t n_obs, int64_t first_agent,
+                                                 const double* d_traj, const int32_t* d_neighbours, const double* d_radius,
+                                                 const double* d_downwash, const double* d_goal_all, lscqp_row* d_rows_out, void* stream) {
+    return lscqp_generate_constraints_device_ex(h, mode, n_agents, n_obs, first_agent, d_traj, d_neighbours, d_radius, d_downwash, d_goal_all,
+                                                d_rows_out, n_obs, 0, stream);
+}
+
+// rows 0..2 of B^-1 for n = 5 (monomial -> Bernstein, closed form C(j,i) / C(n,i)): the size polynomial of
+// obstacleSizePredictionWithConstAcc has monomial coefficients (c0, c1, c2, 0, 0, 0)
+static const double* device_binv3() {
+    static double* d[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    if (!d[dev]) {
+        auto C5 = [](int n_, int k_) { double r = 1; for (int i = 1; i <= k_; i++) r = r * (n_ - k_ + i) / i; return r; };
+        double hbuf[18];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 6; j++) hbuf[i * 6 + j] = (j >= i) ? C5(j, i) / C5(5, i) : 0.0;
+        if (hipMalloc(&d[dev], sizeof hbuf) != hipSuccess) return nullptr;
+        if (hipMemcpy(d[dev], hbuf, sizeof hbuf, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    }
+    return d[dev];
+}
+
+extern "C" int lscqp_generate_lsc_obstacles_device(lscqp_handle h, const lscqp_obstacle_param* param, int64_t n_agents, int32_t n_dyn,
+                                                   int64_t first_agent, const double* d_traj, const int32_t* d_obstacle_ids,
+                                                   const lscqp_obstacle* d_obstacles, const double* d_radius, const double* d_goal,
+                                                   const lscqp_header* d_hdr, lscqp_row* d_rows_out, int32_t n_obs_total, int32_t slot0,
+                                                   void* stream) {
+    if (!h || !param) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_agents < 0 || n_dyn < 0 || first_agent < 0 || slot0 < 0 || n_obs_total < slot0 + n_dyn)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes (n_obs_total >= slot0 + n_dyn required)");
+    const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
+    if (cd->M > 32) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "obstacle prediction supports M <= 32");
+    if (n_agents == 0 || n_dyn == 0) return LSCQP_OK;
+    if (!d_traj || !d_obstacle_ids || !d_obstacles || !d_radius || !d_goal || !d_hdr || !d_rows_out)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
+    const double* binv3 = device_binv3();
+    if (!binv3) return lscqp_set_error_(LSCQP_ERR_HIP, "constant upload failed");
+    const int64_t n_units = n_agents * (int64_t)n_dyn * cd->M;
     const unsigned blocks = (unsigned)((n_units + lscgen::kThreads - 1) / lscgen::kThreads);
-    hipLaunchKernelGGL(lscgen::generate_lsc_obstacle_kernel, dim3(blocks), dim3(lscgen::kThreads), 0, (hipStream_t)stream, M, dim, dt, *p, n_units,
-                       n_dyn, first_agent, d_traj, d_ids, d_table, d_radius, d_goal, d_hdr, rows_f32, n_obs_total, slot0, d_binv3, d_rows_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
-    return LSCQP_OK;
+    hipLaunchKernelGGL(lscgen::generate_lsc_obstacle_kernel, dim3(blocks), dim3(lscgen::kThreads), 0, (hipStream_t)stream, cd->M, cd->dim, cd->dt,
+                       *param, n_units, n_dyn, first_agent, d_traj, d_obstacle_ids, d_obstacles, d_radius, d_goal, d_hdr, rows_f32_of(h), n_obs_total,
+                       slot0, binv3, d_rows_out);
+    return lscqp_launch_result_(hipGetLastError());
 }
 
-extern "C" int lscqp_shift_traj_raw_(int M, int dim, int64_t n, int shift, double z_2d, const double* d_x_prev, double* d_traj,
-                                     void* stream) {
-    const int64_t total = n * M * 6;
-    if (total == 0) return LSCQP_OK;
+extern "C" int lscqp_shift_traj_device(lscqp_handle h, int64_t n, int32_t shift_segments, double z_2d, const double* d_x_prev, double* d_traj,
+                                       void* stream) {
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
+    if (shift_segments < 0 || shift_segments > 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "shift_segments must be 0 or 1");
+    if (n == 0) return LSCQP_OK;
+    if (!d_x_prev || !d_traj) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
+    const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
+    const int64_t total = n * cd->M * 6;
     const unsigned blocks = (unsigned)((total + lscgen::kThreads - 1) / lscgen::kThreads);
-    hipLaunchKernelGGL(lscgen::shift_traj_kernel, dim3(blocks), dim3(lscgen::kThreads), 0, (hipStream_t)stream, M, dim, n, shift, z_2d,
-                       d_x_prev, d_traj);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
-    return LSCQP_OK;
+    hipLaunchKernelGGL(lscgen::shift_traj_kernel, dim3(blocks), dim3(lscgen::kThreads), 0, (hipStream_t)stream, cd->M, cd->dim, n,
+                       (int)shift_segments, z_2d, d_x_prev, d_traj);
+    return lscqp_launch_result_(hipGetLastError());
 }
+
+// W = B A B^-1 (src/trajectory.cpp:24-38): B Bernstein -> monomial (include/polynomial.hpp:281-294), A(i,j) = C(i,j) a^j b^(i-j) for
+// t -> a t + b with b = fraction, a = 1 - fraction, B^-1 in closed form
+static lscgen::SubSegW sub_segment_matrix(double fraction) {
+    auto Cn = [](int n_, int k_) { double r = 1; for (int i = 1; i <= k_; i++) r = r * (n_ - k_ + i) / i; return k_ > n_ ? 0.0 : r; };
+    double B[6][6], Bi[6][6], A[6][6], BA[6][6];
+    lscgen::SubSegW W;
+    const double b = fraction, a = 1.0 - fraction;
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) {
+            B[i][j] = (j >= i) ? Cn(5, i) * Cn(5 - i, 5 - j) * (((j - i) & 1) ? -1.0 : 1.0) : 0.0;
+            Bi[i][j] = (j >= i) ? Cn(j, i) / Cn(5, i) : 0.0;
+            A[i][j] = (j <= i) ? Cn(i, j) * std::pow(a, j) * std::pow(b, i - j) : 0.0;
+        }
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) {
+            BA[i][j] = 0;
+            for (int l = 0; l < 6; l++) BA[i][j] += B[i][l] * A[l][j];
+        }
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) {
+            double v = 0;
+            for (int l = 0; l < 6; l++) v += BA[i][l] * Bi[l][j];
+            W.w[i * 6 + j] = v;
+        }
+    return W;
+}
+
+extern "C" int lscqp_shift_traj_partial_device(lscqp_handle h, int64_t n, double fraction, double z_2d, const double* d_x_prev, double* d_traj,
+                                               void* stream) {
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
+    if (!(fraction > 0.0 && fraction < 1.0))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "fraction = multisim_time_step / dt must lie in (0, 1)");
+    if (n == 0) return LSCQP_OK;
+    if (!d_x_prev || !d_traj) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
+    const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
+    const int64_t total = n * cd->M * 6;
+    const unsigned blocks = (unsigned)((total + lscgen::kThreads - 1) / lscgen::kThreads);
+    hipLaunchKernelGGL(lscgen::shift_traj_partial_kernel, dim3(blocks), dim3(lscgen::kThreads), 0, (hipStream_t)stream, cd->M, cd->dim, n,
+                       sub_segment_matrix(fraction), z_2d, d_x_prev, d_traj);
+    return lscqp_launch_result_(hipGetLastError());
+}
+
+extern "C" int64_t lscqp_generate_lsc_bytes(lscqp_handle h, int64_t n_agents, int32_t n_obs, int64_t n_total) {
+    if (!h) return -1;
+    const int64_t P = 6 * lscqp_class_desc_of_(h)->M;
+    return n_agents * (int64_t)n_obs * P * (rows_f32_of(h) ? 16 : 32) /* rows written */
+           + n_total * (P * 24 + 16)               /* control points, radius, downwash */
+           + n_agents * ((int64_t)n_obs * 4 + 24); /* neighbour ids, goal */
+}
+

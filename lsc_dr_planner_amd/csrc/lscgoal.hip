@@ -11,8 +11,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "../../include/lscqp.h"
 #include "lscqp_internal.hpp"
 
@@ -117,19 +115,24 @@ __global__ __launch_bounds__(kThreads) void goal_kernel(int M, int dim, int use_
 
 }  // namespace lscgoal
 
-extern "C" int lscqp_goal_fin_raw_(int M, int dim, int use_sfc, int rows_f32, double fin_dt, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows,
-                                   const uint64_t* d_row_offsets, const lscqp_box* d_sfc, int32_t* d_status, void* stream) {
+// (library-internal, lscplan.hip) fin_dt = the class's dt: the goal LP that also finishes the headers of the chain; 0: the public entry below
+extern "C" int lscqp_optimize_goal_fin_device_(lscqp_handle h, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows, const uint64_t* d_row_offsets,
+                                               const lscqp_box* d_sfc, int32_t* d_status_out, double fin_dt, void* stream) {
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
     if (n == 0) return LSCQP_OK;
+    const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
+    if (!d_hdr || !d_status_out || (cd->use_sfc && !d_sfc)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
     const int64_t per = lscgoal::kThreads / 64;
     const unsigned blocks = (unsigned)((n + per - 1) / per);
-    hipLaunchKernelGGL(lscgoal::goal_kernel, dim3(blocks), dim3(lscgoal::kThreads), 0, (hipStream_t)stream, M, dim, use_sfc, rows_f32, fin_dt, n, d_hdr, d_rows,
-                       d_row_offsets, d_sfc, d_status);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
-    return LSCQP_OK;
+    const int rows_f32 = lscqp_row_bytes(h) == (int)sizeof(lscqp_row_f32);
+    hipLaunchKernelGGL(lscgoal::goal_kernel, dim3(blocks), dim3(lscgoal::kThreads), 0, (hipStream_t)stream, cd->M, cd->dim, cd->use_sfc, rows_f32, fin_dt, n,
+                       d_hdr, d_rows, d_row_offsets, d_sfc, d_status_out);
+    return lscqp_launch_result_(hipGetLastError());
 }
 
-extern "C" int lscqp_goal_raw_(int M, int dim, int use_sfc, int rows_f32, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows,
-                               const uint64_t* d_row_offsets, const lscqp_box* d_sfc, int32_t* d_status, void* stream) {
-    return lscqp_goal_fin_raw_(M, dim, use_sfc, rows_f32, 0.0, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_status, stream);
+extern "C" int lscqp_optimize_goal_device(lscqp_handle h, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows,
+                                          const uint64_t* d_row_offsets, const lscqp_box* d_sfc, int32_t* d_status_out, void* stream) {
+    return lscqp_optimize_goal_fin_device_(h, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_status_out, 0.0, stream);
 }

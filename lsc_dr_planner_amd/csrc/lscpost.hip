@@ -13,7 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <string>
+#include <algorithm>
 
 #include "../../include/lscqp.h"
 #include "lscqp_internal.hpp"
@@ -300,65 +300,85 @@ __global__ __launch_bounds__(kObsT) void safety_obstacles_kernel(int M, int dim,
 
 }  // namespace lscpost
 
-extern "C" int lscqp_safety_obstacles_raw_(int M, int dim, double dt, int64_t n_agents, int64_t first_agent, int n_samples, double record_time_step,
-                                           double z_2d, const double* d_x_all, const double* d_radius, const double* d_downwash, int n_obstacles,
-                                           const lscqp_obstacle* d_obstacles, lscqp_safety_obs* d_out, void* stream) {
+// The public device entries (include/lscqp.h): every check in front of its launch.
+extern "C" int lscqp_safety_metrics_device(lscqp_handle h, int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_samples,
+                                           double record_time_step, double z_2d, const double* d_x_all, const double* d_radius,
+                                           const double* d_downwash, const lscqp_header* d_hdr, lscqp_safety* d_out, void* stream) {
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_agents < 0 || first_agent < 0 || n_samples < 0 || n_total < first_agent + n_agents)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
     if (n_agents == 0) return LSCQP_OK;
-    const unsigned blocks = (unsigned)((n_agents + lscpost::kObsT - 1) / lscpost::kObsT);
-    hipLaunchKernelGGL(lscpost::safety_obstacles_kernel, dim3(blocks), dim3(lscpost::kObsT), 0, (hipStream_t)stream, M, dim, dt, n_agents, first_agent,
-                       n_samples, record_time_step, z_2d, d_x_all, d_radius, d_downwash, n_obstacles, d_obstacles, d_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
-    return LSCQP_OK;
-}
-
-extern "C" int lscqp_safety_metrics_raw_(int M, int dim, double dt, int64_t n_agents, int64_t first_agent, int64_t n_total, int n_samples,
-                                         double record_time_step, double z_2d, const double* d_x_all, const double* d_radius,
-                                         const double* d_downwash, const lscqp_header* d_hdr, lscqp_safety* d_out, void* stream) {
-    if (n_agents == 0) return LSCQP_OK;
+    if (!d_x_all || !d_radius || !d_downwash || !d_hdr || !d_out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
+    const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
     const unsigned blocks = (unsigned)((n_agents + lscpost::kSafI - 1) / lscpost::kSafI);
-    hipLaunchKernelGGL(lscpost::safety_metrics_kernel<false>, dim3(blocks), dim3(lscpost::kSafT), 0, (hipStream_t)stream, M, dim, dt, n_agents,
-                       first_agent, n_total, n_samples, record_time_step, z_2d, d_x_all, d_radius, d_downwash, d_hdr, d_out, (const int64_t*)nullptr, 1u);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
-    return LSCQP_OK;
+    hipLaunchKernelGGL(lscpost::safety_metrics_kernel<false>, dim3(blocks), dim3(lscpost::kSafT), 0, (hipStream_t)stream, cd->M, cd->dim, cd->dt, n_agents,
+                       first_agent, n_total, (int)n_samples, record_time_step, z_2d, d_x_all, d_radius, d_downwash, d_hdr, d_out,
+                       (const int64_t*)nullptr, 1u);
+    return lscqp_launch_result_(hipGetLastError());
 }
 
-// largest_mission: the agents of the largest mission of the partition (sizes the grid: every mission gets that many workgroups)
-extern "C" int lscqp_safety_metrics_missions_raw_(int M, int dim, double dt, int64_t n_total, int32_t n_missions, int64_t largest_mission,
-                                                  const int64_t* d_off, int n_samples, double record_time_step, double z_2d, const double* d_x_all,
-                                                  const double* d_radius, const double* d_downwash, const lscqp_header* d_hdr, lscqp_safety* d_out,
-                                                  void* stream) {
-    if (n_total == 0) return LSCQP_OK;
-    const int64_t per_mission = (largest_mission + lscpost::kSafI - 1) / lscpost::kSafI;
+extern "C" int lscqp_safety_obstacles_device(lscqp_handle h, int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_samples,
+                                             double record_time_step, double z_2d, const double* d_x_all, const double* d_radius,
+                                             const double* d_downwash, int32_t n_obstacles, const lscqp_obstacle* d_obstacles,
+                                             lscqp_safety_obs* d_out, void* stream) {
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_agents < 0 || first_agent < 0 || n_samples < 0 || n_obstacles < 0 || n_total < first_agent + n_agents)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
+    if (n_agents == 0) return LSCQP_OK;
+    if (!d_x_all || !d_radius || !d_downwash || !d_out || (n_obstacles > 0 && !d_obstacles))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
+    const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
+    const unsigned blocks = (unsigned)((n_agents + lscpost::kObsT - 1) / lscpost::kObsT);
+    hipLaunchKernelGGL(lscpost::safety_obstacles_kernel, dim3(blocks), dim3(lscpost::kObsT), 0, (hipStream_t)stream, cd->M, cd->dim, cd->dt, n_agents,
+                       first_agent, (int)n_samples, record_time_step, z_2d, d_x_all, d_radius, d_downwash, (int)n_obstacles, d_obstacles, d_out);
+    return lscqp_launch_result_(hipGetLastError());
+}
+
+extern "C" int lscqp_safety_metrics_missions_device(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
+                                                    const int64_t* d_mission_offsets, int32_t n_samples, double record_time_step, double z_2d,
+                                                    const double* d_x_all, const double* d_radius, const double* d_downwash,
+                                                    const lscqp_header* d_hdr, lscqp_safety* d_out, void* stream) {
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_total < 0 || n_samples < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
+    if (const int rc = lscqp_check_missions_(n_total, n_missions, mission_offsets)) return rc;  // (a partition has no empty mission: n_total > 0)
+    if (!d_mission_offsets || !d_x_all || !d_radius || !d_downwash || !d_hdr || !d_out)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
+    // the agents of the largest mission size the grid: every mission gets that many workgroups
+    int64_t largest = 0;
+    for (int32_t k = 0; k < n_missions; k++) largest = std::max(largest, mission_offsets[k + 1] - mission_offsets[k]);
+    const int64_t per_mission = (largest + lscpost::kSafI - 1) / lscpost::kSafI;
     if (per_mission * n_missions > 0x7fffffff)
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the partition needs more than 2^31 workgroups (missions x the largest mission's agents / 32)");
-    hipLaunchKernelGGL(lscpost::safety_metrics_kernel<true>, dim3((unsigned)(per_mission * n_missions)), dim3(lscpost::kSafT), 0, (hipStream_t)stream, M, dim, dt,
-                       n_total, (int64_t)0, n_total, n_samples, record_time_step, z_2d, d_x_all, d_radius, d_downwash, d_hdr, d_out, d_off,
-                       (unsigned)per_mission);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
-    return LSCQP_OK;
+    const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
+    hipLaunchKernelGGL(lscpost::safety_metrics_kernel<true>, dim3((unsigned)(per_mission * n_missions)), dim3(lscpost::kSafT), 0, (hipStream_t)stream, cd->M,
+                       cd->dim, cd->dt, n_total, (int64_t)0, n_total, (int)n_samples, record_time_step, z_2d, d_x_all, d_radius, d_downwash, d_hdr, d_out,
+                       d_mission_offsets, (unsigned)per_mission);
+    return lscqp_launch_result_(hipGetLastError());
 }
 
-extern "C" int lscqp_validate_step_raw_(int M, int dim, int use_sfc, double dt, int64_t n, double time_step, double z_2d, const double* d_x,
-                                        const lscqp_header* d_hdr, const lscqp_box* d_sfc, int32_t* d_valid, double* d_state,
-                                        void* stream) {
+extern "C" int lscqp_validate_step_device(lscqp_handle h, int64_t n, double time_step, double z_2d, const double* d_x, const lscqp_header* d_hdr,
+                                          const lscqp_box* d_sfc, int32_t* d_valid_out, double* d_state_out, void* stream) {
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n < 0 || !(time_step >= 0)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "negative size or time");
     if (n == 0) return LSCQP_OK;
-    hipLaunchKernelGGL(lscpost::validate_step_kernel, dim3((unsigned)n), dim3(lscpost::kThreads), 0, (hipStream_t)stream, M, dim, use_sfc, dt, n,
-                       time_step, z_2d, d_x, d_hdr, d_sfc, d_valid, d_state, lscpost::Commit{nullptr, nullptr, nullptr, nullptr, nullptr});
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
-    return LSCQP_OK;
+    const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
+    if (!d_x || !d_hdr || !d_valid_out || !d_state_out || (cd->use_sfc && !d_sfc)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
+    hipLaunchKernelGGL(lscpost::validate_step_kernel, dim3((unsigned)n), dim3(lscpost::kThreads), 0, (hipStream_t)stream, cd->M, cd->dim, cd->use_sfc, cd->dt,
+                       n, time_step, z_2d, d_x, d_hdr, d_sfc, d_valid_out, d_state_out, lscpost::Commit{nullptr, nullptr, nullptr, nullptr, nullptr});
+    return lscqp_launch_result_(hipGetLastError());
 }
 
+// (library-internal, lscplan.hip and the tests) commit + isSolValid + doStep of the local agents in one launch, no checks
 extern "C" int lscqp_commit_validate_raw_(int M, int dim, int use_sfc, double dt, int64_t n, double time_step, double z_2d, const int32_t* d_qp_status,
                                           const double* d_x_new, const double* d_x_init, double* d_x_plan, double* d_goal, const lscqp_header* d_hdr,
                                           const lscqp_box* d_sfc, int32_t* d_valid, double* d_state, void* stream) {
     if (n == 0) return LSCQP_OK;
     hipLaunchKernelGGL(lscpost::validate_step_kernel, dim3((unsigned)n), dim3(lscpost::kThreads), 0, (hipStream_t)stream, M, dim, use_sfc, dt, n,
                        time_step, z_2d, d_x_new, d_hdr, d_sfc, d_valid, d_state, lscpost::Commit{d_qp_status, d_x_new, d_x_init, d_x_plan, d_goal});
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
-    return LSCQP_OK;
+    return lscqp_launch_result_(hipGetLastError());
 }
+

@@ -61,6 +61,14 @@ int need_device_say_why() {
 
 }  // namespace
 extern "C" int lscqp_set_error_(int code, const char* msg) { return fail(code, msg); }
+// for the device entries the other units define (lscgen.hip, lscgoal.hip, lscpost.hip, lscsfc.hip): the no-device answer with the fixed text, and
+// what a launch left behind
+extern "C" int lscqp_need_device_(void) {
+    return have_device() ? LSCQP_OK : fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
+}
+extern "C" int lscqp_launch_result_(hipError_t e) {
+    return e == hipSuccess ? LSCQP_OK : fail(LSCQP_ERR_HIP, std::string("HIP launch failed: ") + hipGetErrorString(e));
+}
 namespace {
 
 // Development / test switches of a handle.  They are read from the environment ONCE, when the handle is created (load_knobs), and live in
@@ -579,7 +587,8 @@ int lscqp_create(const lscqp_class_desc* desc, lscqp_handle* out) {
 }
 
 // The class's active-set tables on the CURRENT device, now: what the first solve on a device would otherwise do lazily -- and cannot do
-// inside a stream capture.  lscqp_create does it for the device that is current then, lscqp_comm_create for every device of the communicator.
+// inside a stream capture.  lscqp_create does it for the device that is current then, lscqp_comm_prepare for every device of a communicator
+// (lscqp_comm_create prepares none).
 int lscqp_prepare_device(lscqp_handle h) {
     if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
     if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
@@ -720,152 +729,6 @@ int lscqp_instance_work(lscqp_handle h, int64_t n, int32_t n_obs_max, lscqp_work
 }
 int lscqp_row_bytes(lscqp_handle h) { return h ? (int)row_bytes(h) : -1; }
 
-int lscqp_generate_lsc_device(lscqp_handle h, int64_t n_agents, int32_t n_obs, int64_t first_agent, const double* d_traj,
-                              const int32_t* d_neighbours, const double* d_radius, const double* d_downwash,
-                              const double* d_goal, lscqp_row* d_rows_out, void* stream) {
-    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_agents < 0 || n_obs < 0 || first_agent < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
-    if (n_agents == 0 || n_obs == 0) return LSCQP_OK;
-    if (!d_traj || !d_neighbours || !d_radius || !d_downwash || !d_goal || !d_rows_out)
-        return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    return lscqp_generate_lsc_raw_(LSCQP_GEN_LSC, h->desc.M, h->desc.dim, n_agents, n_obs, first_agent, d_traj, nullptr, d_neighbours, d_radius,
-                                   d_downwash, d_goal, nullptr, h->dev.rows_f32, n_obs, 0, d_rows_out, stream);
-}
-
-int lscqp_generate_constraints_device(lscqp_handle h, int32_t mode, int64_t n_agents, int32_t n_obs, int64_t first_agent,
-                                      const double* d_traj, const int32_t* d_neighbours, const double* d_radius,
-                                      const double* d_downwash, const double* d_goal_all, lscqp_row* d_rows_out, void* stream) {
-    return lscqp_generate_constraints_device_ex(h, mode, n_agents, n_obs, first_agent, d_traj, d_neighbours, d_radius, d_downwash, d_goal_all,
-                                                d_rows_out, n_obs, 0, stream);
-}
-
-// rows 0..2 of B^-1 for n = 5 (monomial -> Bernstein, closed form C(j,i) / C(n,i)): the size polynomial of
-// obstacleSizePredictionWithConstAcc has monomial coefficients (c0, c1, c2, 0, 0, 0)
-static const double* device_binv3() {
-    static double* d[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    if (!d[dev]) {
-        auto C5 = [](int n_, int k_) { double r = 1; for (int i = 1; i <= k_; i++) r = r * (n_ - k_ + i) / i; return r; };
-        double hbuf[18];
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 6; j++) hbuf[i * 6 + j] = (j >= i) ? C5(j, i) / C5(5, i) : 0.0;
-        if (hipMalloc(&d[dev], sizeof hbuf) != hipSuccess) return nullptr;
-        if (hipMemcpy(d[dev], hbuf, sizeof hbuf, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    }
-    return d[dev];
-}
-
-int lscqp_generate_lsc_obstacles_device(lscqp_handle h, const lscqp_obstacle_param* param, int64_t n_agents, int32_t n_dyn,
-                                        int64_t first_agent, const double* d_traj, const int32_t* d_obstacle_ids,
-                                        const lscqp_obstacle* d_obstacles, const double* d_radius, const double* d_goal,
-                                        const lscqp_header* d_hdr, lscqp_row* d_rows_out, int32_t n_obs_total, int32_t slot0, void* stream) {
-    if (!h || !param) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_agents < 0 || n_dyn < 0 || first_agent < 0 || slot0 < 0 || n_obs_total < slot0 + n_dyn)
-        return fail(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes (n_obs_total >= slot0 + n_dyn required)");
-    if (h->desc.M > 32) return fail(LSCQP_ERR_UNSUPPORTED, "obstacle prediction supports M <= 32");
-    if (n_agents == 0 || n_dyn == 0) return LSCQP_OK;
-    if (!d_traj || !d_obstacle_ids || !d_obstacles || !d_radius || !d_goal || !d_hdr || !d_rows_out)
-        return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    const double* binv3 = device_binv3();
-    if (!binv3) return fail(LSCQP_ERR_HIP, "constant upload failed");
-    return lscqp_generate_lsc_obstacles_raw_(h->desc.M, h->desc.dim, h->desc.dt, param, n_agents, n_dyn, first_agent, d_traj, d_obstacle_ids,
-                                             d_obstacles, d_radius, d_goal, d_hdr, h->dev.rows_f32, n_obs_total, slot0, binv3, d_rows_out, stream);
-}
-
-int lscqp_shift_traj_partial_device(lscqp_handle h, int64_t n, double fraction, double z_2d, const double* d_x_prev, double* d_traj,
-                                    void* stream) {
-    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
-    if (!(fraction > 0.0 && fraction < 1.0)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "fraction = multisim_time_step / dt must lie in (0, 1)");
-    if (n == 0) return LSCQP_OK;
-    if (!d_x_prev || !d_traj) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    // W = B A B^-1 (src/trajectory.cpp:24-38): B Bernstein -> monomial (include/polynomial.hpp:281-294), A(i,j) = C(i,j) a^j b^(i-j) for
-    // t -> a t + b with b = fraction, a = 1 - fraction, B^-1 in closed form
-    auto Cn = [](int n_, int k_) { double r = 1; for (int i = 1; i <= k_; i++) r = r * (n_ - k_ + i) / i; return k_ > n_ ? 0.0 : r; };
-    double B[6][6], Bi[6][6], A[6][6], BA[6][6], W[36];
-    const double b = fraction, a = 1.0 - fraction;
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j < 6; j++) {
-            B[i][j] = (j >= i) ? Cn(5, i) * Cn(5 - i, 5 - j) * (((j - i) & 1) ? -1.0 : 1.0) : 0.0;
-            Bi[i][j] = (j >= i) ? Cn(j, i) / Cn(5, i) : 0.0;
-            A[i][j] = (j <= i) ? Cn(i, j) * std::pow(a, j) * std::pow(b, i - j) : 0.0;
-        }
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j < 6; j++) {
-            BA[i][j] = 0;
-            for (int l = 0; l < 6; l++) BA[i][j] += B[i][l] * A[l][j];
-        }
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j < 6; j++) {
-            double v = 0;
-            for (int l = 0; l < 6; l++) v += BA[i][l] * Bi[l][j];
-            W[i * 6 + j] = v;
-        }
-    return lscqp_shift_traj_partial_raw_(h->desc.M, h->desc.dim, n, W, z_2d, d_x_prev, d_traj, stream);
-}
-
-int lscqp_generate_constraints_device_ex(lscqp_handle h, int32_t mode, int64_t n_agents, int32_t n_obs, int64_t first_agent,
-                                         const double* d_traj, const int32_t* d_neighbours, const double* d_radius,
-                                         const double* d_downwash, const double* d_goal_all, lscqp_row* d_rows_out, int32_t n_obs_total,
-                                         int32_t slot0, void* stream) {
-    return lscqp_generate_constraints_own_(h, mode, n_agents, n_obs, first_agent, d_traj, nullptr, d_neighbours, d_radius, d_downwash, d_goal_all,
-                                           d_rows_out, n_obs_total, slot0, stream);
-}
-
-int lscqp_generate_constraints_own_(lscqp_handle h, int32_t mode, int64_t n_agents, int32_t n_obs, int64_t first_agent,
-                                    const double* d_traj, const double* d_own_traj, const int32_t* d_neighbours, const double* d_radius,
-                                    const double* d_downwash, const double* d_goal_all, lscqp_row* d_rows_out, int32_t n_obs_total,
-                                    int32_t slot0, void* stream) {
-    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (slot0 < 0 || n_obs_total < slot0 + n_obs) return fail(LSCQP_ERR_INVALID_ARGUMENT, "n_obs_total >= slot0 + n_obs required");
-    if (mode != LSCQP_GEN_LSC && mode != LSCQP_GEN_CLSC && mode != LSCQP_GEN_BVC)
-        return fail(LSCQP_ERR_INVALID_ARGUMENT, "mode must be LSCQP_GEN_LSC, LSCQP_GEN_CLSC or LSCQP_GEN_BVC");
-    if (n_agents < 0 || n_obs < 0 || first_agent < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
-    if (n_agents == 0 || n_obs == 0) return LSCQP_OK;
-    if (!d_traj || !d_neighbours || !d_radius || !d_downwash || !d_goal_all || !d_rows_out)
-        return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    return lscqp_generate_lsc_raw_(mode, h->desc.M, h->desc.dim, n_agents, n_obs, first_agent, d_traj, d_own_traj, d_neighbours, d_radius,
-                                   d_downwash, d_goal_all + 3 * first_agent, d_goal_all, h->dev.rows_f32, n_obs_total, slot0, d_rows_out, stream);
-}
-
-int lscqp_shift_traj_device(lscqp_handle h, int64_t n, int32_t shift_segments, double z_2d, const double* d_x_prev, double* d_traj,
-                            void* stream) {
-    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
-    if (shift_segments < 0 || shift_segments > 1) return fail(LSCQP_ERR_INVALID_ARGUMENT, "shift_segments must be 0 or 1");
-    if (n == 0) return LSCQP_OK;
-    if (!d_x_prev || !d_traj) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    return lscqp_shift_traj_raw_(h->desc.M, h->desc.dim, n, shift_segments, z_2d, d_x_prev, d_traj, stream);
-}
-
-int64_t lscqp_generate_lsc_bytes(lscqp_handle h, int64_t n_agents, int32_t n_obs, int64_t n_total) {
-    if (!h) return -1;
-    const int64_t P = h->P;
-    return n_agents * (int64_t)n_obs * P * (h->dev.rows_f32 ? 16 : 32) /* rows written */
-           + n_total * (P * 24 + 16)               /* control points, radius, downwash */
-           + n_agents * ((int64_t)n_obs * 4 + 24); /* neighbour ids, goal */
-}
-
-int lscqp_optimize_goal_device(lscqp_handle h, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows,
-                               const uint64_t* d_row_offsets, const lscqp_box* d_sfc, int32_t* d_status_out, void* stream) {
-    return lscqp_optimize_goal_fin_device_(h, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_status_out, 0.0, stream);
-}
-int lscqp_optimize_goal_fin_device_(lscqp_handle h, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows, const uint64_t* d_row_offsets,
-                                    const lscqp_box* d_sfc, int32_t* d_status_out, double fin_dt, void* stream) {
-    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
-    if (n == 0) return LSCQP_OK;
-    if (!d_hdr || !d_status_out || (h->desc.use_sfc && !d_sfc)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    return lscqp_goal_fin_raw_(h->desc.M, h->desc.dim, h->desc.use_sfc, h->dev.rows_f32, fin_dt, n, d_hdr, d_rows, d_row_offsets, d_sfc, d_status_out, stream);
-}
-
 int lscqp_optimize_goal(lscqp_handle h, int64_t n, lscqp_header* hdr, const lscqp_row* rows, const uint64_t* row_offsets,
                         const lscqp_box* sfc, int32_t* status_out) {
     if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
@@ -914,38 +777,6 @@ int lscqp_optimize_goal(lscqp_handle h, int64_t n, lscqp_header* hdr, const lscq
     return LSCQP_OK;
 }
 
-int lscqp_safety_metrics_device(lscqp_handle h, int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_samples,
-                                double record_time_step, double z_2d, const double* d_x_all, const double* d_radius,
-                                const double* d_downwash, const lscqp_header* d_hdr, lscqp_safety* d_out, void* stream) {
-    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_agents < 0 || first_agent < 0 || n_samples < 0 || n_total < first_agent + n_agents)
-        return fail(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
-    if (n_agents == 0) return LSCQP_OK;
-    if (!d_x_all || !d_radius || !d_downwash || !d_hdr || !d_out) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    return lscqp_safety_metrics_raw_(h->desc.M, h->desc.dim, h->desc.dt, n_agents, first_agent, n_total, n_samples, record_time_step, z_2d,
-                                     d_x_all, d_radius, d_downwash, d_hdr, d_out, stream);
-}
-
-int lscqp_safety_obstacles_device(lscqp_handle h, int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_samples,
-                                  double record_time_step, double z_2d, const double* d_x_all, const double* d_radius,
-                                  const double* d_downwash, int32_t n_obstacles, const lscqp_obstacle* d_obstacles,
-                                  lscqp_safety_obs* d_out, void* stream) {
-    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_agents < 0 || first_agent < 0 || n_samples < 0 || n_obstacles < 0 || n_total < first_agent + n_agents)
-        return fail(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
-    if (n_agents == 0) return LSCQP_OK;
-    if (!d_x_all || !d_radius || !d_downwash || !d_out || (n_obstacles > 0 && !d_obstacles)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    return lscqp_safety_obstacles_raw_(h->desc.M, h->desc.dim, h->desc.dt, n_agents, first_agent, n_samples, record_time_step, z_2d, d_x_all,
-                                       d_radius, d_downwash, n_obstacles, d_obstacles, d_out, stream);
-}
-
-int lscqp_construct_sfc_device(lscqp_handle h, lscqp_map mp, int32_t mode, int64_t n, const double* d_points, const double* d_radius,
-                               lscqp_box* d_sfc, int32_t* d_status_out, void* stream) {
-    return lscqp_construct_sfc_device_ordered(h, mp, mode, n, d_points, d_radius, d_sfc, d_status_out, nullptr, nullptr, stream);
-}
-
 int lscqp_order_by_cost_device(int64_t n, const uint32_t* d_cost_prev, int32_t* d_order_out, void* stream) {
     if (n < 0 || n > 0x7fffffff) return fail(LSCQP_ERR_INVALID_ARGUMENT, "0 <= n < 2^31 required");
     if (n == 0) return LSCQP_OK;
@@ -957,32 +788,6 @@ int lscqp_order_by_cost_device(int64_t n, const uint32_t* d_cost_prev, int32_t* 
     return LSCQP_OK;
 }
 
-int lscqp_construct_sfc_device_ordered(lscqp_handle h, lscqp_map mp, int32_t mode, int64_t n, const double* d_points, const double* d_radius,
-                                       lscqp_box* d_sfc, int32_t* d_status_out, const int32_t* d_order, uint32_t* d_cost_out, void* stream) {
-    if (!h || !mp) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (mode != LSCQP_SFC_INIT && mode != LSCQP_SFC_FROM_HULL && mode != LSCQP_SFC_FROM_POINT)
-        return fail(LSCQP_ERR_INVALID_ARGUMENT, "mode must be LSCQP_SFC_INIT, LSCQP_SFC_FROM_HULL or LSCQP_SFC_FROM_POINT");
-    if (n < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
-    if (n == 0) return LSCQP_OK;
-    if (!d_points || !d_radius || !d_sfc || !d_status_out) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (h->desc.M > 21) return fail(LSCQP_ERR_UNSUPPORTED, "corridor shift supports M <= 21");
-    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    return lscqp_construct_sfc_raw_ex_(mp, mode, h->desc.M, n, d_points, d_radius, d_sfc, d_status_out, d_order, d_cost_out, stream);
-}
-
-int lscqp_select_neighbours_device(lscqp_handle h, int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_obs,
-                                   double communication_range, const double* d_positions, int32_t* d_neighbours_out,
-                                   int32_t* d_count_out, void* stream) {
-    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_agents < 0 || first_agent < 0 || n_obs < 0 || n_total < first_agent + n_agents)
-        return fail(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
-    if (n_agents == 0) return LSCQP_OK;
-    if (!d_positions || !d_count_out || (n_obs > 0 && !d_neighbours_out)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    return lscqp_select_neighbours_raw_(n_agents, first_agent, n_total, n_obs, communication_range, d_positions, d_neighbours_out,
-                                        d_count_out, stream);
-}
-
 int lscqp_check_missions_(int64_t n_total, int32_t n_missions, const int64_t* mission_offsets) {
     if (n_missions < 1 || !mission_offsets) return fail(LSCQP_ERR_INVALID_ARGUMENT, "a mission partition needs n_missions >= 1 and its offset list");
     if (mission_offsets[0] != 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "mission_offsets[0] must be 0");
@@ -990,47 +795,6 @@ int lscqp_check_missions_(int64_t n_total, int32_t n_missions, const int64_t* mi
         if (mission_offsets[k + 1] <= mission_offsets[k]) return fail(LSCQP_ERR_INVALID_ARGUMENT, "mission_offsets must be strictly increasing (no empty mission)");
     if (mission_offsets[n_missions] != n_total) return fail(LSCQP_ERR_INVALID_ARGUMENT, "mission_offsets[n_missions] must be the number of agents");
     return LSCQP_OK;
-}
-
-int lscqp_select_neighbours_missions_device(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
-                                            const int64_t* d_mission_offsets, int32_t n_obs, double communication_range,
-                                            const double* d_positions, int32_t* d_neighbours_out, int32_t* d_count_out, void* stream) {
-    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_total < 0 || n_obs < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
-    const int rc = lscqp_check_missions_(n_total, n_missions, mission_offsets);
-    if (rc != LSCQP_OK) return rc;
-    if (!d_mission_offsets || !d_positions || !d_count_out || (n_obs > 0 && !d_neighbours_out)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    return lscqp_select_neighbours_missions_raw_(n_total, n_missions, d_mission_offsets, n_obs, communication_range, d_positions, d_neighbours_out,
-                                                 d_count_out, stream);
-}
-
-int lscqp_safety_metrics_missions_device(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
-                                         const int64_t* d_mission_offsets, int32_t n_samples, double record_time_step, double z_2d,
-                                         const double* d_x_all, const double* d_radius, const double* d_downwash, const lscqp_header* d_hdr,
-                                         lscqp_safety* d_out, void* stream) {
-    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_total < 0 || n_samples < 0) return fail(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes");
-    const int rc = lscqp_check_missions_(n_total, n_missions, mission_offsets);
-    if (rc != LSCQP_OK) return rc;
-    if (!d_mission_offsets || !d_x_all || !d_radius || !d_downwash || !d_hdr || !d_out) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    int64_t largest = 0;
-    for (int32_t k = 0; k < n_missions; k++) largest = std::max(largest, mission_offsets[k + 1] - mission_offsets[k]);
-    return lscqp_safety_metrics_missions_raw_(h->desc.M, h->desc.dim, h->desc.dt, n_total, n_missions, largest, d_mission_offsets, n_samples,
-                                              record_time_step, z_2d, d_x_all, d_radius, d_downwash, d_hdr, d_out, stream);
-}
-
-int lscqp_validate_step_device(lscqp_handle h, int64_t n, double time_step, double z_2d, const double* d_x,
-                               const lscqp_header* d_hdr, const lscqp_box* d_sfc, int32_t* d_valid_out, double* d_state_out,
-                               void* stream) {
-    if (!h) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || !(time_step >= 0)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "negative size or time");
-    if (n == 0) return LSCQP_OK;
-    if (!d_x || !d_hdr || !d_valid_out || !d_state_out || (h->desc.use_sfc && !d_sfc)) return fail(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!have_device()) return fail(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    return lscqp_validate_step_raw_(h->desc.M, h->desc.dim, h->desc.use_sfc, h->desc.dt, n, time_step, z_2d, d_x, d_hdr, d_sfc, d_valid_out,
-                                    d_state_out, stream);
 }
 
 int lscqp_num_inequalities(lscqp_handle h, int32_t n_obs) {

@@ -2,6 +2,9 @@
 // of include/lscqp.h).  Every unit that defines or calls one of them includes this file: a definition that drifts from its declaration
 // then fails to compile instead of linking and passing garbage.  api.py reads the prototypes of the entries its wrappers call
 // (lscqp_optimize_goal_fin_device_, lscqp_commit_validate_raw_, lscqp_debug_*_) from this text.
+// A public device entry is DEFINED in the unit that owns its kernel, checks in front of the launch; no `_raw_` half of it is declared here.
+// The three `_raw_` functions that remain have a caller besides their own public entry: lscqp_generate_lsc_raw_ (four generator entries, the
+// tests for M = 1), lscqp_commit_validate_raw_ (lscplan.hip, api.py) and lscqp_map_raw_ (lscgrid.hip).
 #ifndef LSCQP_INTERNAL_HPP
 #define LSCQP_INTERNAL_HPP
 
@@ -22,6 +25,10 @@ extern "C" {
 
 // ---- lscqp_api.hip
 int lscqp_set_error_(int code, const char* msg);
+// for a device entry, after its argument checks: LSCQP_OK, or LSCQP_ERR_NO_DEVICE with the fixed text (there is no CPU fallback)
+int lscqp_need_device_(void);
+// ... and behind its launch: LSCQP_OK, or LSCQP_ERR_HIP with "HIP launch failed: <what the runtime says>"
+int lscqp_launch_result_(hipError_t e);
 const lscqp_class_desc* lscqp_class_desc_of_(lscqp_handle h);  // for lscplan.hip
 uint64_t lscqp_handle_generation_(lscqp_handle h);
 // (library-internal, lscqp_comm.hip) does a batch of this shape have a second chance on the instance with the other elimination order?
@@ -30,15 +37,6 @@ int lscqp_has_other_order_(lscqp_handle h, int64_t n, int32_t n_obs_max);
 // launch-shape override to the policy's value
 int lscqp_debug_reload_knobs_(lscqp_handle h);
 int lscqp_debug_set_knob_(lscqp_handle h, const char* name, int value);
-// (library-internal, lscplan.hip) lscqp_generate_constraints_device_ex with the planning agents' initial trajectories kept apart from
-// the predicted trajectories of the agents as obstacles: d_own_traj [n_agents][M][6][3], NULL = rows d_traj[first_agent + a]
-int lscqp_generate_constraints_own_(lscqp_handle h, int32_t mode, int64_t n_agents, int32_t n_obs, int64_t first_agent,
-                                    const double* d_traj, const double* d_own_traj, const int32_t* d_neighbours, const double* d_radius,
-                                    const double* d_downwash, const double* d_goal_all, lscqp_row* d_rows_out, int32_t n_obs_total,
-                                    int32_t slot0, void* stream);
-// (library-internal, lscplan.hip) the goal LP that also finishes the headers of the chain: goal as a point3d, terminal_segments (fin_dt = the class's dt)
-int lscqp_optimize_goal_fin_device_(lscqp_handle h, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows, const uint64_t* d_row_offsets,
-                                    const lscqp_box* d_sfc, int32_t* d_status_out, double fin_dt, void* stream);
 // (library-internal: every entry point that takes a mission partition) mission_offsets[0..n_missions], host: strictly increasing from 0 to n_total
 int lscqp_check_missions_(int64_t n_total, int32_t n_missions, const int64_t* mission_offsets);
 int lscqp_solve_batch_device_internal_(lscqp_handle h, int64_t n, int32_t n_obs_max, const lscqp_header* d_hdr, const lscqp_row* d_rows,
@@ -85,43 +83,24 @@ int lscqp_prescreen_host_twin_(const lscqp::DevClass* cls, int M, int dim, int c
                                const uint64_t* row_offsets, const lscqp_box* sfc, lscqp_prescreen_cert* cert_out);
 
 // ---- lscgen.hip
-int lscqp_select_neighbours_raw_(int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_obs, double range,
-                                 const double* d_pos, int32_t* d_nbr, int32_t* d_count, void* stream);
-int lscqp_select_neighbours_missions_raw_(int64_t n_total, int32_t n_missions, const int64_t* d_off, int32_t n_obs, double range,
-                                          const double* d_pos, int32_t* d_nbr, int32_t* d_count, void* stream);
+// (library-internal: the generator entries, and the tests for M = 1) one launch of the generator, no checks
 int lscqp_generate_lsc_raw_(int mode, int M, int dim, int64_t n_agents, int32_t n_obs, int64_t first_agent,
                             const double* d_traj, const double* d_own_traj, const int32_t* d_neighbours, const double* d_radius,
                             const double* d_downwash, const double* d_goal, const double* d_goal_all, int rows_f32,
                             int32_t n_obs_total, int32_t slot0, lscqp_row* d_rows_out, void* stream);
-int lscqp_shift_traj_partial_raw_(int M, int dim, int64_t n, const double* w36, double z_2d, const double* d_x_prev, double* d_traj,
-                                  void* stream);
-int lscqp_generate_lsc_obstacles_raw_(int M, int dim, double dt, const lscqp_obstacle_param* p, int64_t n_agents, int32_t n_dyn,
-                                      int64_t first_agent, const double* d_traj, const int32_t* d_ids, const lscqp_obstacle* d_table,
-                                      const double* d_radius, const double* d_goal, const lscqp_header* d_hdr, int rows_f32,
-                                      int32_t n_obs_total, int32_t slot0, const double* d_binv3, lscqp_row* d_rows_out, void* stream);
-int lscqp_shift_traj_raw_(int M, int dim, int64_t n, int shift, double z_2d, const double* d_x_prev, double* d_traj,
-                          void* stream);
+// (library-internal, lscplan.hip) lscqp_generate_constraints_device_ex with the planning agents' initial trajectories kept apart from
+// the predicted trajectories of the agents as obstacles: d_own_traj [n_agents][M][6][3], NULL = rows d_traj[first_agent + a]
+int lscqp_generate_constraints_own_(lscqp_handle h, int32_t mode, int64_t n_agents, int32_t n_obs, int64_t first_agent,
+                                    const double* d_traj, const double* d_own_traj, const int32_t* d_neighbours, const double* d_radius,
+                                    const double* d_downwash, const double* d_goal_all, lscqp_row* d_rows_out, int32_t n_obs_total,
+                                    int32_t slot0, void* stream);
 
 // ---- lscgoal.hip
-int lscqp_goal_fin_raw_(int M, int dim, int use_sfc, int rows_f32, double fin_dt, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows,
-                        const uint64_t* d_row_offsets, const lscqp_box* d_sfc, int32_t* d_status, void* stream);
-int lscqp_goal_raw_(int M, int dim, int use_sfc, int rows_f32, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows,
-                    const uint64_t* d_row_offsets, const lscqp_box* d_sfc, int32_t* d_status, void* stream);
+// (library-internal, lscplan.hip) the goal LP that also finishes the headers of the chain: goal as a point3d, terminal_segments (fin_dt = the class's dt)
+int lscqp_optimize_goal_fin_device_(lscqp_handle h, int64_t n, lscqp_header* d_hdr, const lscqp_row* d_rows, const uint64_t* d_row_offsets,
+                                    const lscqp_box* d_sfc, int32_t* d_status_out, double fin_dt, void* stream);
 
 // ---- lscpost.hip
-int lscqp_safety_obstacles_raw_(int M, int dim, double dt, int64_t n_agents, int64_t first_agent, int n_samples, double record_time_step,
-                                double z_2d, const double* d_x_all, const double* d_radius, const double* d_downwash, int n_obstacles,
-                                const lscqp_obstacle* d_obstacles, lscqp_safety_obs* d_out, void* stream);
-int lscqp_safety_metrics_raw_(int M, int dim, double dt, int64_t n_agents, int64_t first_agent, int64_t n_total, int n_samples,
-                              double record_time_step, double z_2d, const double* d_x_all, const double* d_radius,
-                              const double* d_downwash, const lscqp_header* d_hdr, lscqp_safety* d_out, void* stream);
-int lscqp_safety_metrics_missions_raw_(int M, int dim, double dt, int64_t n_total, int32_t n_missions, int64_t largest_mission,
-                                       const int64_t* d_off, int n_samples, double record_time_step, double z_2d, const double* d_x_all,
-                                       const double* d_radius, const double* d_downwash, const lscqp_header* d_hdr, lscqp_safety* d_out,
-                                       void* stream);
-int lscqp_validate_step_raw_(int M, int dim, int use_sfc, double dt, int64_t n, double time_step, double z_2d, const double* d_x,
-                             const lscqp_header* d_hdr, const lscqp_box* d_sfc, int32_t* d_valid, double* d_state,
-                             void* stream);
 // (library-internal, lscplan.hip) commit + isSolValid + doStep of the local agents in one launch; d_x_plan / d_goal: the local block
 int lscqp_commit_validate_raw_(int M, int dim, int use_sfc, double dt, int64_t n, double time_step, double z_2d, const int32_t* d_qp_status,
                                const double* d_x_new, const double* d_x_init, double* d_x_plan, double* d_goal, const lscqp_header* d_hdr,
@@ -132,10 +111,6 @@ int lscqp_map_device_(lscqp_map mp);
 uint64_t lscqp_map_generation_(lscqp_map mp);
 // (library-internal: lscgrid.hip evaluates the grid planner's occupancy from the same nearest-occupied-cell field)
 int lscqp_map_raw_(lscqp_map mp, double* res, float* world_min, float* world_max, int* key0, int* dims, const int32_t** d_nearest, int* device);
-int lscqp_construct_sfc_raw_(lscqp_map mp, int mode, int M, int64_t n, const double* d_points, const double* d_radius,
-                             lscqp_box* d_sfc, int32_t* d_status_out, void* stream);
-int lscqp_construct_sfc_raw_ex_(lscqp_map mp, int mode, int M, int64_t n, const double* d_points, const double* d_radius, lscqp_box* d_sfc,
-                                int32_t* d_status_out, const int32_t* d_order, uint32_t* d_cost_out, void* stream);
 hipError_t lscsfc_launch_throughput_(const void* view, int mode, int M, int64_t n, const double* d_points, const double* d_radius,
                                      lscqp_box* d_sfc, int32_t* d_status_out, void* stream);  // lscsfc_tp.hip
 int lscsfc_throughput_max_cells_(void);

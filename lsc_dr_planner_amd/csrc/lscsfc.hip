@@ -1483,12 +1483,9 @@ int lscqp_map_download(lscqp_map mp, uint8_t* occ, int32_t* nearest) {
     return LSCQP_OK;
 }
 
-int lscqp_construct_sfc_raw_(lscqp_map mp, int mode, int M, int64_t n, const double* d_points, const double* d_radius, lscqp_box* d_sfc,
-                             int32_t* d_status_out, void* stream) {
-    return lscqp_construct_sfc_raw_ex_(mp, mode, M, n, d_points, d_radius, d_sfc, d_status_out, nullptr, nullptr, stream);
-}
-int lscqp_construct_sfc_raw_ex_(lscqp_map mp, int mode, int M, int64_t n, const double* d_points, const double* d_radius, lscqp_box* d_sfc,
-                                int32_t* d_status_out, const int32_t* d_order, uint32_t* d_cost_out, void* stream) {
+// one launch of the corridor kernel, no checks: the device entries below and the host form lscqp_construct_sfc
+static int launch_corridors(lscqp_map mp, int mode, int M, int64_t n, const double* d_points, const double* d_radius, lscqp_box* d_sfc,
+                            int32_t* d_status_out, const int32_t* d_order, uint32_t* d_cost_out, void* stream) {
     lscsfc::MapView v;
     v.order = d_order;
     v.cost = d_cost_out;
@@ -1527,8 +1524,26 @@ int lscqp_construct_sfc_raw_ex_(lscqp_map mp, int mode, int M, int64_t n, const 
                            d_radius, d_sfc, d_status_out);
         e = hipGetLastError();
     }
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("HIP launch failed: ") + hipGetErrorString(e)).c_str());
-    return LSCQP_OK;
+    return lscqp_launch_result_(e);
+}
+
+int lscqp_construct_sfc_device_ordered(lscqp_handle h, lscqp_map mp, int32_t mode, int64_t n, const double* d_points, const double* d_radius,
+                                       lscqp_box* d_sfc, int32_t* d_status_out, const int32_t* d_order, uint32_t* d_cost_out, void* stream) {
+    if (!h || !mp) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (mode != LSCQP_SFC_INIT && mode != LSCQP_SFC_FROM_HULL && mode != LSCQP_SFC_FROM_POINT)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "mode must be LSCQP_SFC_INIT, LSCQP_SFC_FROM_HULL or LSCQP_SFC_FROM_POINT");
+    if (n < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
+    if (n == 0) return LSCQP_OK;
+    if (!d_points || !d_radius || !d_sfc || !d_status_out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    const int M = lscqp_class_desc_of_(h)->M;
+    if (M > 21) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "corridor shift supports M <= 21");
+    if (const int rc = lscqp_need_device_()) return rc;
+    return launch_corridors(mp, mode, M, n, d_points, d_radius, d_sfc, d_status_out, d_order, d_cost_out, stream);
+}
+
+int lscqp_construct_sfc_device(lscqp_handle h, lscqp_map mp, int32_t mode, int64_t n, const double* d_points, const double* d_radius,
+                               lscqp_box* d_sfc, int32_t* d_status_out, void* stream) {
+    return lscqp_construct_sfc_device_ordered(h, mp, mode, n, d_points, d_radius, d_sfc, d_status_out, nullptr, nullptr, stream);
 }
 
 // HOST pointers, synchronous: the batch-of-1 form the unchanged planner loop uses (TrajPlanner::generateSFC, one agent at a time)
@@ -1556,8 +1571,8 @@ int lscqp_construct_sfc(lscqp_map mp, int32_t mode, int32_t M, int64_t n, const 
     memcpy(hb + b_p, radius, n * sizeof(double));
     memcpy(hb + b_p + b_r, sfc, n * M * sizeof(lscqp_box));
     LSCSFC_HIP(hipMemcpyAsync(db, hb, b_p + b_r + b_s, hipMemcpyHostToDevice, st));
-    const int rc = lscqp_construct_sfc_raw_(mp, mode, M, n, (const double*)db, (const double*)(db + b_p), (lscqp_box*)(db + b_p + b_r),
-                                            (int32_t*)(db + b_p + b_r + b_s), st);
+    const int rc = launch_corridors(mp, mode, M, n, (const double*)db, (const double*)(db + b_p), (lscqp_box*)(db + b_p + b_r),
+                                    (int32_t*)(db + b_p + b_r + b_s), nullptr, nullptr, st);
     if (rc != LSCQP_OK) return rc;
     LSCSFC_HIP(hipMemcpyAsync(hb + b_p + b_r, db + b_p + b_r, b_s + b_st, hipMemcpyDeviceToHost, st));
     LSCSFC_HIP(hipStreamSynchronize(st));
