@@ -165,18 +165,23 @@ __device__ __forceinline__ int fdiv(int a, float inv_b) { return (int)(((float)a
 #define LSCQP_DAS_CYCLES das_cycles  // (the fused translation unit keeps its totals under a name of its own: das_fused_cycles)
 #endif
 __device__ unsigned long long LSCQP_DAS_CYCLES[16];
-// (thread 0 accumulates in LDS and adds to the global totals once, at the end: an atomic behind every probe would be waited for by the next
+// (-DLSCQP_DAS_TIMING_TID=<thread>: the thread of each workgroup that is booked, in the same 16 slots -- 64 books the second wavefront, the
+// objective's side of the verification; a probe inside code only wavefront 0 runs then books nothing)
+#ifndef LSCQP_DAS_TIMING_TID
+#define LSCQP_DAS_TIMING_TID 0
+#endif
+// (the booked thread -- thread 0 unless LSCQP_DAS_TIMING_TID says otherwise -- accumulates in LDS and adds to the global totals once, at the end: an atomic behind every probe would be waited for by the next
 // wait on vector memory -- a round trip of microseconds booked on whatever phase comes next)
 #define DAS_T_DECL()                                                                                                                  \
     unsigned long long* const das_tl_ = reinterpret_cast<unsigned long long*>(smem + L.o_tl);                                         \
-    if (threadIdx.x == 0)                                                                                                             \
+    if (threadIdx.x == LSCQP_DAS_TIMING_TID)                                                                                          \
         for (int i_ = 0; i_ < 16; i_++) das_tl_[i_] = 0;                                                                              \
     unsigned long long tprev_ = __builtin_readcyclecounter()
 #define DAS_T(slot)                                                        \
     do {                                                                   \
         if ((LSCQP_DAS_TIMING >> (slot)) & 1) {                            \
             const unsigned long long now_ = __builtin_readcyclecounter();  \
-            if (tid == 0) das_tl_[slot] += now_ - tprev_;                  \
+            if (tid == LSCQP_DAS_TIMING_TID) das_tl_[slot] += now_ - tprev_; \
             tprev_ = now_;                                                 \
         }                                                                  \
     } while (0)
@@ -185,7 +190,7 @@ __device__ unsigned long long LSCQP_DAS_CYCLES[16];
 #endif
 #define DAS_T_FLUSH()                                                                    \
     do {                                                                                 \
-        if (tid == 0 && steps >= LSCQP_DAS_TIMING_MIN_STEPS)                             \
+        if (tid == LSCQP_DAS_TIMING_TID && steps >= LSCQP_DAS_TIMING_MIN_STEPS)          \
             for (int i_ = 0; i_ < 16; i_++) atomicAdd(&LSCQP_DAS_CYCLES[i_], das_tl_[i_]);   \
     } while (0)
 #else

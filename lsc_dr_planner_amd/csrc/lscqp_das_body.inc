@@ -12,8 +12,11 @@
 //   forms serve the batches that fill the chip, where a quiet instance must not pay for step setup).  1: the later passes read the
 //   staged rows with clamped, untested loads, all in flight at once.  2: what the first step needs and only the header decides is done
 //   ahead of it -- the factor zeroed in the prologue, the class's table left in LDS by the first pass (needs LSCQP_DAS_LAYOUT and more than
-//   one wavefront).  4: a joining row's descriptors are stored from registers, not copied from the candidate's slot.  As the prologues,
-//   the settings differ in when and by which thread a value is moved, in no expression that rounds (tests/test_das_step_path.py);
+//   one wavefront).  4: a joining row's descriptors are stored from registers, not copied from the candidate's slot.  8: the verification as
+//   straight-line code -- every operand asked for before the first arithmetic, lam_ kept zero from the prologue on instead of zeroed
+//   behind a barrier of its own (needs LSCQP_DAS_PROLOGUE 1 and more than one wavefront).  16: not used.  32: the objective's rounding
+//   term from one block of loads instead of a loop of six dependent ones (with bit 8 only: the text is in its branch).  As the prologues, the settings differ in when and by which thread a value is moved, in no expression
+//   that rounds (tests/test_das_step_path.py, tests/test_das_verification.py);
 //   LSCQP_DAS_END(verdict): leaves the phase with a DasVerdict, taken by the whole workgroup at once;
 //   LSCQP_DAS_LAYOUT (optional): the LDS carve as a constant expression, with room for at least kmax active rows, the class's table and
 //   stage_rows staged rows; without it the carve is made at run time from kmax, cacheC and stage_rows.  kmax, max_steps, cacheC and
@@ -384,6 +387,11 @@
         for (int e = tid; e < kcap * LDL / 2; e += T) J2[e] = make_double2(0.0, 0.0);
     }
 #endif
+#if LSCQP_DAS_STEP_PATH & 8
+    // A'u is zero wherever no multiplier is held: the verification reads lam_ without a test and thread 0 adds to it without zeroing it
+    // first (finish_local).  The barrier below publishes the zeros; whoever verifies a second time restores them (the polish path).
+    for (int e = tid; e < NX; e += T) lam_[e] = 0.0;
+#endif
 #if LSCQP_DAS_PROLOGUE
     // the workgroup's verdict on `empty` with ONE barrier: every wavefront leaves its own ballot in a slot of red_ no reduction uses
     // ([20, 24) of the first half), every thread reads all of them behind the barrier that also publishes c_ and the two-sided rows
@@ -724,6 +732,168 @@
         // (the class's, left in LDS by the prologue; the two ka_ names stand in front of the block's registers for DAS_CLS below)
         const double dt = wb_[6], q2s = wb_[7], ka_w_t = ctl_[4], ka_w_c = red_[44], wt2 = 2.0 * ka_w_t;
 #endif
+#if LSCQP_DAS_STEP_PATH & 8
+        // The same verification as straight-line code (the expressions that round are the text below's, word for word): every operand of
+        // a stationarity lane -- header words, origin, the twelve words of c_ of its segment and the next -- is asked for before the first
+        // arithmetic, at clamped indices and without a test around a load (a lane past the last row evaluates the last row, a last
+        // segment evaluates itself as its "next" one; their values are dropped by selects).  lam_ is read as it stands: the prologue
+        // zeroed it, thread 0 adds A'u to the zeros, so no zeroing pass and no barrier of its own stand in front of thread 0's sums.
+#if !LSCQP_DAS_PROLOGUE
+#error "LSCQP_DAS_STEP_PATH & 8 reads the class's scalars from LDS: it needs the rescheduled prologue"
+#endif
+        static_assert(NW > 1, "the stationarity rows take one trip of the workgroup");
+        // the objective's part of this thread (bit 32: from one block of loads; otherwise the text of the #else branch below)
+        auto objective_local = [&]() {
+#if LSCQP_DAS_STEP_PATH & 32
+            // One wavefront, straight-line: the lane's six control points, the 36 words of the rounding term, origin and goal are all asked
+            // for in front of the first arithmetic (the row-at-a-time loop was six dependent LDS round trips); the sums in the loop's order.
+            // (a lane without a segment evaluates the last one and its value is dropped)
+            static_assert(NW > 1, "the objective's lanes are the second wavefront's");
+            part = 0.0;
+            if (__builtin_amdgcn_readfirstlane(wv) == 1) {
+                const bool on = lane < dim * M;
+                const int lv = on ? lane : dim * M - 1;
+                const int kx = lv / M, m = lv - kx * M;
+                const double* cc = &c_[kx * P + 6 * m];
+                double cv[6], dqv[36];
+                double ok_ = org[kx], gl_ = Hd->goal[kx];
+#pragma unroll
+                for (int i = 0; i < 6; i++) cv[i] = cc[i];
+#pragma unroll
+                for (int i = 0; i < 36; i++) dqv[i] = dq_[i];
+                asm volatile("" : "+v"(ok_), "+v"(gl_));
+#pragma unroll
+                for (int i = 0; i < 6; i++) asm volatile("" : "+v"(cv[i]));
+#pragma unroll
+                for (int i = 0; i < 36; i++) asm volatile("" : "+v"(dqv[i]));
+                const double j0 = (cv[3] - cv[0]) - 3.0 * (cv[2] - cv[1]);
+                const double j1 = (cv[4] - cv[1]) - 3.0 * (cv[3] - cv[2]);
+                const double j2 = (cv[5] - cv[2]) - 3.0 * (cv[4] - cv[3]);
+                const double quad = 0.2 * (j0 * j0 + j2 * j2) + (2.0 / 15.0) * j1 * j1 + 0.2 * (j0 * j1 + j1 * j2) + (1.0 / 15.0) * j0 * j2;
+                double pp = 0.5 * q2s * 3600.0 * quad;
+                double corr = 0;
+                const double s0 = cv[0] + ok_, s1 = cv[1] + ok_, s2 = cv[2] + ok_, s3 = cv[3] + ok_, s4 = cv[4] + ok_, s5 = cv[5] + ok_;
+#pragma unroll
+                for (int i = 0; i < 6; i++) {
+                    const double* dr = dqv + 6 * i;
+                    double r = 0;
+                    r += dr[0] * s0, r += dr[1] * s1, r += dr[2] * s2, r += dr[3] * s3, r += dr[4] * s4, r += dr[5] * s5;
+                    corr += r * (cv[i] + ok_);
+                }
+                pp += DAS_CLS(w_c) * corr;
+                const double dgoal = cv[5] - (gl_ - ok_);
+                pp += (m >= M - ts) ? DAS_CLS(w_t) * dgoal * dgoal : 0.0;
+                const double sum = part + pp;
+                part = on ? sum : part;
+            }
+#else
+            part = 0.0;
+            // (the objective's threads sit in the second wavefront when there is one: its arithmetic runs beside the stationarity rows' instead of behind them)
+            for (int lv = tid - (NW > 1 ? 64 : 0); lv < dim * M; lv += T) {
+                if (lv < 0) continue;
+                const int kx = lv / M, m = lv - kx * M;
+                const double* cc = &c_[kx * P + 6 * m];
+                const double j0 = (cc[3] - cc[0]) - 3.0 * (cc[2] - cc[1]);
+                const double j1 = (cc[4] - cc[1]) - 3.0 * (cc[3] - cc[2]);
+                const double j2 = (cc[5] - cc[2]) - 3.0 * (cc[4] - cc[3]);
+                const double quad = 0.2 * (j0 * j0 + j2 * j2) + (2.0 / 15.0) * j1 * j1 + 0.2 * (j0 * j1 + j1 * j2) + (1.0 / 15.0) * j0 * j2;
+                double pp = 0.5 * q2s * 3600.0 * quad;
+                const double ok_ = org[kx];
+                double corr = 0;
+                const double s0 = cc[0] + ok_, s1 = cc[1] + ok_, s2 = cc[2] + ok_, s3 = cc[3] + ok_, s4 = cc[4] + ok_, s5 = cc[5] + ok_;
+#pragma unroll 1
+                for (int i = 0; i < 6; i++) {  // (a row of the term at a time: unrolled, its 36 entries would be requested -- and held in registers -- at once)
+                    const double* dr = dq_ + 6 * i;
+                    double r = 0;
+                    r += dr[0] * s0, r += dr[1] * s1, r += dr[2] * s2, r += dr[3] * s3, r += dr[4] * s4, r += dr[5] * s5;
+                    corr += r * (cc[i] + ok_);
+                }
+                pp += DAS_CLS(w_c) * corr;
+                const double dgoal = cc[5] - (Hd->goal[kx] - ok_);
+                pp += (m >= M - ts) ? DAS_CLS(w_t) * dgoal * dgoal : 0.0;
+                part += pp;
+            }
+#endif
+        };
+        const int nz = dim * NZA;  // (<= 108 < T)
+        const bool zw = __builtin_amdgcn_readfirstlane(wv) * 64 < nz;  // (wave-uniform: a wavefront without a row skips the section)
+        const bool zon = tid < nz;
+        const int zi = zon ? tid : nz - 1;
+        const int kx = zi / NZA, a = zi - kx * NZA;
+        const bool last = es && a == 3 * (M - 1);
+        const int m = last ? M - 1 : a / 3, j = last ? 0 : a % 3;
+        const bool has_next = m + 1 < M;
+        const int mn = has_next ? m + 1 : M - 1;
+        double hv0, ha0, hgl, hok, va[6], vb[6];
+        if (zw) {
+            hv0 = Hd->v0[kx], ha0 = Hd->a0[kx], hgl = Hd->goal[kx], hok = org[kx];
+#pragma unroll
+            for (int i = 0; i < 6; i++) va[i] = c_[kx * P + 6 * m + i], vb[i] = c_[kx * P + 6 * mn + i];
+        }
+        if (k > 0) {  // A'u, per control point, onto the zeros
+            if (tid == 0) {
+                for (int j_ = 0; j_ < k; j_++)
+#pragma unroll
+                    for (int t_ = 0; t_ < 3; t_++) {
+                        const int en = aint_[4 * j_ + 1 + t_];
+                        lam_[ent_axis(en) * P + ent_cp(en)] += u_[j_] * acoef_[3 * j_ + t_];
+                    }
+            }
+            LSCQP_DAS_BARRIER();
+        }
+        objective_local();  // (behind the barrier, beside the stationarity rows: in front of it, beside thread 0's sums, the slot timed the same)
+        rd = 0.0, gs = 0.0;
+        if (zw) {
+            double la[3], lb[3];
+#pragma unroll
+            for (int i = 0; i < 3; i++) la[i] = lam_[kx * P + 6 * m + 3 + i], lb[i] = lam_[kx * P + 6 * mn + i];
+            double dt_ = dt, q2s_ = q2s, wt2_ = wt2;
+            asm volatile("" : "+v"(hv0), "+v"(ha0), "+v"(hgl), "+v"(hok), "+v"(dt_), "+v"(q2s_), "+v"(wt2_));
+#pragma unroll
+            for (int i = 0; i < 6; i++) asm volatile("" : "+v"(va[i]), "+v"(vb[i]));
+#pragma unroll
+            for (int i = 0; i < 3; i++) asm volatile("" : "+v"(la[i]), "+v"(lb[i]));
+            {
+                const double dt = dt_, q2s = q2s_, wt2 = wt2_;
+                const double c1 = hv0 * dt * 0.2;
+                const double c2 = ha0 * dt * dt * 0.05 + 2.0 * c1;
+                const double gk = hgl - hok;
+                // the six rows of Hx of one segment on this axis: g = Hx c + fx, g0 = Hx cfix + fx (constant indices: registers)
+                auto seg = [&](int mm, const double* cc, double* g, double* g0) {
+                    const double v0 = cc[0], v1 = cc[1], v2 = cc[2], v3 = cc[3], v4 = cc[4], v5 = cc[5];
+                    lscqp::static_for<0, 6>([&](auto Ic) {
+                        constexpr int i = decltype(Ic)::value;
+                        g[i] = q2s * (KQ(i, 0) * v0 + KQ(i, 1) * v1 + KQ(i, 2) * v2 + KQ(i, 3) * v3 + KQ(i, 4) * v4 + KQ(i, 5) * v5);
+                        g0[i] = (mm == 0) ? q2s * (KQ(i, 1) * c1 + KQ(i, 2) * c2) : 0.0;
+                    });
+                    if (mm >= M - ts) {
+                        g[5] += wt2 * (v5 - gk);
+                        g0[5] += -wt2 * gk;
+                    }
+                };
+                double g[6], g0[6];
+                seg(m, va, g, g0);
+                const double lm3 = la[0], lm4 = la[1], lm5 = la[2];  // A'u on the segment's last three control points
+                double cf, cg, c0;  // T' of: full residual, gradient, gradient at the fixed part
+                {
+                    const double cf_l = (g[3] - lm3) + (g[4] - lm4) + (g[5] - lm5), cg_l = g[3] + g[4] + g[5], c0_l = g0[3] + g0[4] + g0[5];
+                    const double gs_ = j == 0 ? g[3] : j == 1 ? g[4] : g[5], ls_ = j == 0 ? lm3 : j == 1 ? lm4 : lm5, g0s = j == 0 ? g0[3] : j == 1 ? g0[4] : g0[5];
+                    cf = last ? cf_l : gs_ - ls_, cg = last ? cg_l : gs_, c0 = last ? c0_l : g0s;
+                }
+                {  // (c0, c1, c2) of the next segment = TB (c3, c4, c5) of this one, TB = [[0,0,1],[0,-1,2],[1,-4,4]]
+                    seg(mn, vb, g, g0);
+                    const double* const lm = lb;
+                    const double w0 = (j == 2) ? 1.0 : 0.0, w1 = (j == 1) ? -1.0 : (j == 2) ? 2.0 : 0.0, w2 = (j == 0) ? 1.0 : (j == 1) ? -4.0 : 4.0;
+                    const double cf_n = cf + (w0 * (g[0] - lm[0]) + w1 * (g[1] - lm[1]) + w2 * (g[2] - lm[2]));
+                    const double cg_n = cg + (w0 * g[0] + w1 * g[1] + w2 * g[2]);
+                    const double c0_n = c0 + (w0 * g0[0] + w1 * g0[1] + w2 * g0[2]);
+                    cf = has_next ? cf_n : cf, cg = has_next ? cg_n : cg, c0 = has_next ? c0_n : c0;
+                }
+                const double rd_ = fmax(rd, fabs(cf)), gs_z = fmax(gs, fmax(fabs(cg), fabs(c0)));
+                rd = zon ? rd_ : rd, gs = zon ? gs_z : gs;
+            }
+        }
+#else
         if (k > 0) {  // A'u, per control point
             for (int e = tid; e < NX; e += T) lam_[e] = 0.0;
             LSCQP_DAS_BARRIER();
@@ -805,6 +975,7 @@
             pp += (m >= M - ts) ? DAS_CLS(w_t) * dgoal * dgoal : 0.0;
             part += pp;
         }
+#endif
     };
     // (buffer rb_: the wavefronts' stationarity maxima at [8, 12), gradient scales at [12, 16), objective parts at [16, 20))
     auto finish_combine = [&](const double* rb_, double& rd, double& gs, double& part) {
@@ -891,6 +1062,19 @@
             // multipliers, c = c_u + sum u_j C a_j -- stationary up to the table's rounding -- and one refinement of the multipliers that
             // puts the active rows back at zero slack:  rho = h_A - A c,  du = S^-1 rho,  u += du,  c += sum du_j C a_j.  Then every row
             // is looked at again.
+#if LSCQP_DAS_STEP_PATH & 8
+            // (this path verifies again: lam_ goes back to zero first -- behind the verification's reduction barrier, so every lane has
+            // read it -- where thread 0 added, and only inside lam_: in 2-D an LSC row's third entry names axis 2 with coefficient 0,
+            // which addresses plo_ behind lam_, and that word keeps what the sums left in it.  The barriers below publish the zeros.)
+            if (tid == 0) {
+                for (int j_ = 0; j_ < k; j_++)
+#pragma unroll
+                    for (int t_ = 0; t_ < 3; t_++) {
+                        const int en = aint_[4 * j_ + 1 + t_], at = ent_axis(en) * P + ent_cp(en);
+                        if (at < NX) lam_[at] = 0.0;
+                    }
+            }
+#endif
             LSCQP_DAS_BARRIER();
             add_columns(k, u_, cu_);
             LSCQP_DAS_BARRIER();

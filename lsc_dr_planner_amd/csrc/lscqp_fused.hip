@@ -37,12 +37,15 @@ constexpr bool carve_fits(int M, int dim, int kmax, int stage_rows) {
 #define LSCQP_FUSED_PROLOGUE 1
 #endif
 // Which changes to the stepping instance's path the phase runs here (lscqp_das_body.inc, LSCQP_DAS_STEP_PATH: a set of bits, one per
-// change): the M = 5 form runs all three.  The M = 10 forms keep the text they had: with the changes the 2-D one spills one scalar
-// register more (252 against 251) and has no timing that would pay for it, the 3-D one 301 - 312 against 292 (NOTES section 24).
+// change): the M = 5 form and the M = 10, 2-D form run the three of NOTES section 24 (bits 1, 2, 4) and the straight-line verification
+// with the objective's rounding term from one block of loads (bits 8, 32: NOTES section 31).  The rule of section 24 decides per form: an
+// item stays where the scalar-register spills do not grow or a timing pays for the growth.  With three row slots (below) the 2-D form
+// spills 242 with all of them against 245 without and the parent's 251, and c0 runs 7 % faster; the M = 10, 3-D form spilled 301 - 312
+// against 292 with the first three, has not been built with the others, and keeps the text it had.
 // (-DLSCQP_FUSED_STEP_PATH=<bits> builds a subset: the timing twins of one change.)
 #ifndef LSCQP_FUSED_STEP_PATH
-#if LSCQP_M == 5
-#define LSCQP_FUSED_STEP_PATH 7
+#if LSCQP_M == 5 || (LSCQP_M == 10 && LSCQP_DIM == 2)
+#define LSCQP_FUSED_STEP_PATH (7 | 8 | 32)
 #else
 #define LSCQP_FUSED_STEP_PATH 0
 #endif
@@ -77,11 +80,23 @@ __global__ __launch_bounds__(256, 1) void das_pdip_kernel(DevClass cls, int cap,
 #endif
     int verdict = kDasSolved;
     {  // the phase: das_kernel<4, false, false, false>'s body (lscqp_das_body.inc) with the class's shape as constants and nothing in front
-        constexpr int NW = 4, T = 64 * NW, kU = 4;
+        using FC = FusedCarve<M, DIM, ES, NSLOT, W>;
+        constexpr int NW = 4, T = 64 * NW;
+        // Row slots per thread, from the carve: as many as a full instance's rows need, at most four.  The 600-row forms get three -- a
+        // fourth would load, translate, stage-test and evaluate a row that cannot exist, in the prologue and in every pass; the 2 400-row
+        // form keeps four and loops.  (The pass's (slack, id) minimum is lexicographic: it does not depend on which thread saw which row.)
+        // (-DLSCQP_FUSED_ROW_SLOTS=4 builds the four slots every form had: a timing twin's column)
+#ifdef LSCQP_FUSED_ROW_SLOTS
+        constexpr int kU = LSCQP_FUSED_ROW_SLOTS;
+#else
+        constexpr int kU = (FC::kStage + T - 1) / T < 4 ? (FC::kStage + T - 1) / T : 4;
+#endif
         constexpr bool F32 = false, SCREEN = false, PEEL = false;
         constexpr int dim = DIM, es = ES ? 1 : 0, behind = 0;
-        using FC = FusedCarve<M, DIM, ES, NSLOT, W>;
         constexpr int kMaxNL = FC::kStage;  // (an instance beyond the launch's cap <= MAX_OBS is handed over before its rows are read)
+        // fewer than four slots: one block of kU * T rows holds every row of an instance the phase accepts (the first pass has no further trip)
+        static_assert(kU == 4 || kMaxNL <= kU * T, "the row slots must cover the carve's staged rows");
+        static_assert(kU >= 1, "an instance has rows");
 #define LSCQP_DAS_END(verdict_)   \
     do {                          \
         verdict = (verdict_);     \

@@ -5,6 +5,8 @@ lscqp_das_fused_cycles).  The run prints the totals of whichever kernel served t
 
 usage: python tools/das_timing.py --build-only   (here)      python tools/das_timing.py [c1 c0 c3s ...]   (GPU box; LSCQP_LIB is set by the tool)
   DAS_TIMING_MIN_STEPS=1 (both steps): book only the instances that took at least one active-set step
+  --tid=<thread> (or DAS_TIMING_TID, build step): the thread of each workgroup the twin books, default 0; 64 books the second wavefront
+  (the objective's side of the verification) in the same slots
   DAS_TIMING_OUT / DAS_TIMING_LIB: the library to build / to run (default lsc_dr_planner_amd/liblscqp_dastime.so)"""
 import ctypes as C
 import glob
@@ -26,7 +28,8 @@ if "--build-only" in sys.argv:
 
     from lsc_dr_planner_amd import build as B
 
-    timing = ["-DLSCQP_DAS_TIMING=0xffff", "-DLSCQP_DAS_TIMING_MIN_STEPS=%s" % os.environ.get("DAS_TIMING_MIN_STEPS", "0")]
+    tid = ([a[6:] for a in sys.argv if a.startswith("--tid=")] or [os.environ.get("DAS_TIMING_TID", "0")])[0]
+    timing = ["-DLSCQP_DAS_TIMING=0xffff", "-DLSCQP_DAS_TIMING_MIN_STEPS=%s" % os.environ.get("DAS_TIMING_MIN_STEPS", "0"), "-DLSCQP_DAS_TIMING_TID=%d" % int(tid)]
     with tempfile.TemporaryDirectory() as td:
         o = os.path.join(td, "lscqp_das_timing.o")
         subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + timing + ["-c", os.path.join(CSRC, "lscqp_das.hip"), "-o", o])
@@ -85,7 +88,7 @@ for key in [a for a in sys.argv[1:] if not a.startswith("-")] or ["c1", "c0", "c
         c = np.array(list(cc)[:16], dtype=float) / reps / Nb
         if not c.any():
             continue
-        print("%s [%s]: %d QPs, steps mean %.2f max %d, %d booked (>= %d steps), %.1f us per call | cycles per booked QP (thread 0 of each workgroup): total %.0f" % (
+        print("%s [%s]: %d QPs, steps mean %.2f max %d, %d booked (>= %d steps), %.1f us per call | cycles per booked QP (one thread of each workgroup: thread 0 unless the twin was built with --tid): total %.0f" % (
             key, kname, N, info["iterations"].mean(), info["iterations"].max(), Nb, nbook, e0.elapsed_time(e1) / reps * 1e3, c.sum()))
         for n_, v in zip(NAMES, c):
             print("      %-34s %9.0f" % (n_, v))
