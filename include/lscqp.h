@@ -816,7 +816,9 @@ int lscqp_waypoints_wide_device(lscqp_grid grid, double communication_range, int
  * lscqp_waypoints_device (decentralizedMAPP precedes the planning loop in the simulator too) and a mission flies from start points and
  * goal points alone: lscqp_plan_reset, then lscqp_plan_step_graph in a loop, with no host work between replans.  (Unless closed_loop is
  * set, the simulator writes the agents' states.)
- * Dynamic (non-agent) obstacles are not part of the chain (lscqp_generate_lsc_obstacles_device is available separately).
+ * Dynamic (non-agent) obstacles join the chain through lscqp_plan_set_obstacles ("dynamic obstacles in the chain" below): they move on
+ * the device from replan to replan, take the first row slots of every agent and enter the safety figures.  A plan without them
+ * enqueues the chain described here, node for node.
  * Sharding (section 8e): rank r owns the agents [first_agent, first_agent + n_agents) of n_total; its plan needs every agent's
  * previous plan, state and goal point, so the owners' slices of LSCQP_PLAN_BUF_PLAN / _STATE / _GOAL are all-gathered between
  * steps (lscqp_allgather; the layout is [n_total][...] on every rank, so the gather is in place). */
@@ -1074,6 +1076,92 @@ int lscqp_record_unfinished(lscqp_record rec, int32_t* unfinished_out);
 int lscqp_plan_set_record(lscqp_plan plan, const lscqp_record_desc* desc);
 lscqp_record lscqp_plan_record(lscqp_plan plan);
 int lscqp_plan_run(lscqp_plan plan, int64_t max_replans, int32_t check_every, int32_t use_graph, void* stream, int64_t* replans_enqueued);
+
+/* ---- dynamic obstacles in the chain: their motion on the device, their rows and their safety figures ------------------------------------
+ *
+ * The reference's missions list dynamic obstacles (mission file "obstacles": spin, straight, patrol, chasing, gaussian, real; include/
+ * obstacle.hpp).  ObstacleGenerator::update(t, 0) moves them once per replan, at the replan's start time and without observer noise
+ * (src/multi_sync_simulator.cpp:311); broadcastMsgs hands EVERY agent all of them, unfiltered, in front of the in-range agents (:310-333);
+ * their LSC rows are hard rows like an agent's (CollisionConstraints::dynamic_obstacle_indices is never filled); the safety figures of
+ * the replan read the same positions (:527-557); planMAPF's grid does not see them.
+ * A model describes how ONE obstacle moves; `kind` selects the reference class:
+ *   LSCQP_OBSTACLE_STRAIGHT  StraightObstacle (:138-214): start -> goal under a trapezoidal speed profile (speed, max_acc), both branches
+ *                            (dist_to_goal > 2 dist_acc, and the short one) with their phases; past the last phase the obstacle rests
+ *                            at the goal with zero velocity.  Reads start, goal.
+ *   LSCQP_OBSTACLE_PATROL    PatrolObstacle (:216-264): n_waypoints <= LSCQP_OBSTACLE_MAX_WAYPOINTS legs flown as straight obstacles one
+ *                            after the other, the last leg back to waypoint 0, for ever.  Reads waypoints.  Whole laps are taken off
+ *                            the time first and at most n_waypoints legs are walked, whatever the time (the reference subtracts leg by
+ *                            leg from t = 0): equal in the first lap, within rounding of the lap time afterwards.
+ *   LSCQP_OBSTACLE_SPIN      SpinObstacle (:83-136): `start` rotated about the axis (axis_point, axis_direction) at angular speed
+ *                            speed / spin radius, in double; the velocity is the position's offset turned by 90 degrees about the axis
+ *                            times the angular speed, as the reference forms it.
+ *   LSCQP_OBSTACLE_HELD      the kernel leaves the table entry alone: the caller writes position and velocity between eager replans
+ *                            (chasing, gaussian and real obstacles, whose motion is not modelled here).  `start` is where the entry is
+ *                            put by lscqp_plan_set_obstacles / lscqp_plan_reset.
+ * Positions and velocities are point3d in the reference: the kernel writes float32 values held in double, formed with the reference's
+ * own mix of float and double operations and without fused multiply-adds.
+ * lscqp_obstacle_model_prepare   HOST, no device needed: checks n models and fills their derived fields in place -- per leg the
+ *                            direction, dist_to_goal, dist_acc and flight_time of StraightObstacle's constructor in its own arithmetic
+ *                            (Vector3::distance and normalized() on float32 points), the lap time, the spin's unit axis, offset and
+ *                            angular speed.  LSCQP_ERR_INVALID_ARGUMENT names the model and what is wrong with it: an unknown kind, a
+ *                            non-finite field, radius < 0, max_acc <= 0, speed <= 0 (not asked of a HELD model), n_waypoints outside
+ *                            [1, LSCQP_OBSTACLE_MAX_WAYPOINTS], a patrol whose lap time is not positive (a lap of no length would never
+ *                            end in the reference either), a spin whose axis direction or spin radius is zero.
+ * lscqp_obstacles_advance_device one launch of ONE workgroup over n_dyn <= lscqp_max_obstacles(h) PREPARED models in device memory:
+ *                            reads the obstacle clock r (int32, device) and forms t as the reference's clock does -- r steps of
+ *                            ros::Duration(time_step), whole nanoseconds, then seconds -- writes entry oi of d_obstacles (position,
+ *                            velocity, radius, downwash, max_acc, type = DYNAMICOBSTACLE) for every model that is not HELD, and stores
+ *                            r + 1.  The clock lives on the device because a captured graph carries constant arguments.
+ * lscqp_plan_set_obstacles   gives the plan n_dyn obstacles (host models, prepared by the call itself; the caller's array is not
+ *                            written) and the generator's parameters; n_dyn = 0 or models = NULL takes them away.  Like
+ *                            lscqp_plan_set_record it waits for the device and drops a captured graph, lscqp_plan_reset must follow (a step
+ *                            before it is refused) and the reset puts the table at t = 0 and zeroes the clock.  desc.n_obs stays the
+ *                            number of row slots per agent: slots [0, n_dyn) are the obstacles in table order, slots [n_dyn, n_obs) the
+ *                            in-range agents (the range filter then cuts to the n_obs - n_dyn nearest).  Refused, leaving the plan as
+ *                            it was: n_dyn > n_obs (LSCQP_ERR_INVALID_ARGUMENT), constraint_mode != LSCQP_GEN_LSC (LSCQP_ERR_UNSUPPORTED:
+ *                            the obstacle rows are generateLSC's), a model lscqp_obstacle_model_prepare refuses.
+ *                            Per replan the chain gains, on its one stream: the advance in front of the prepare step, the obstacle
+ *                            rows (lscqp_generate_lsc_obstacles_device over the planning agents' initial trajectories) behind the agent
+ *                            rows, and with safety_samples > 0 lscqp_safety_obstacles_device behind the agent safety figures.  A mission
+ *                            partition shares the obstacles like the map; every owner of a sharded mission advances its own copy of the
+ *                            same table.  The waypoint decision does not see obstacles, as in the reference.  The mission record keeps
+ *                            no obstacle figure.
+ * lscqp_plan_obstacle_buffer / _upload / _download   the buffers that exist only with obstacles (NULL and 0 bytes otherwise), addressed
+ *                            by LSCQP_PLAN_OBS_*; copies are synchronous like lscqp_plan_upload / _download. */
+#define LSCQP_OBSTACLE_MAX_WAYPOINTS 8
+#define LSCQP_OBSTACLE_HELD 0 /* values of lscqp_obstacle_model.kind (lscqp_obstacle.type is another field: 0 = DYNAMICOBSTACLE) */
+#define LSCQP_OBSTACLE_STRAIGHT 1
+#define LSCQP_OBSTACLE_PATROL 2
+#define LSCQP_OBSTACLE_SPIN 3
+typedef struct lscqp_obstacle_leg { /* StraightObstacle's members; 64 bytes */
+    float start[3], goal[3], n[3]; /* point3d */
+    float reserved;
+    double dist_to_goal, dist_acc, flight_time;
+} lscqp_obstacle_leg;
+typedef struct lscqp_obstacle_model { /* 912 bytes */
+    int32_t kind;        /* LSCQP_OBSTACLE_* */
+    int32_t n_waypoints; /* PATROL */
+    double radius, downwash, max_acc, speed; /* mission file: size, downwash, max_acc, speed */
+    double start[3], goal[3];                /* STRAIGHT; start also SPIN and HELD */
+    double waypoints[LSCQP_OBSTACLE_MAX_WAYPOINTS][3];
+    double axis_point[3], axis_direction[3]; /* SPIN: axis.pose.position, axis.pose.orientation x y z */
+    /* derived, filled by lscqp_obstacle_model_prepare */
+    int32_t n_legs, prepared;
+    lscqp_obstacle_leg leg[LSCQP_OBSTACLE_MAX_WAYPOINTS];
+    double lap_time;                                   /* flight_time[0] + flight_time[1] + ... in that order */
+    double spin_axis[3], spin_offset[3], spin_w;       /* n, a = start - axis_point, w = speed / |a - (a.n) n| */
+} lscqp_obstacle_model;
+int lscqp_obstacle_model_prepare(lscqp_obstacle_model* models, int32_t n);
+int lscqp_obstacles_advance_device(lscqp_handle h, const lscqp_obstacle_model* d_models, int32_t n_dyn, double time_step, int32_t* d_clock,
+                                   lscqp_obstacle* d_obstacles, void* stream);
+#define LSCQP_PLAN_OBS_TABLE 0  /* i/o  lscqp_obstacle[n_dyn]: the table as the last replan's advance left it (HELD entries: the caller's) */
+#define LSCQP_PLAN_OBS_SAFETY 1 /* out  lscqp_safety_obs[n_agents] of the last replan (safety_samples > 0) */
+#define LSCQP_PLAN_OBS_CLOCK 2  /* i/o  int32: the replan index the NEXT advance evaluates */
+#define LSCQP_PLAN_OBS_COUNT 3
+int lscqp_plan_set_obstacles(lscqp_plan plan, const lscqp_obstacle_param* param, int32_t n_dyn, const lscqp_obstacle_model* models);
+void* lscqp_plan_obstacle_buffer(lscqp_plan plan, int32_t which, uint64_t* bytes_out);
+int lscqp_plan_obstacle_upload(lscqp_plan plan, int32_t which, const void* host, uint64_t offset, uint64_t bytes);
+int lscqp_plan_obstacle_download(lscqp_plan plan, int32_t which, void* host, uint64_t offset, uint64_t bytes);
 
 /* ---- work counters of a launch (the fp64-VALU figure next to the HBM one) -----------------------------
  *

@@ -42,6 +42,18 @@ SAFETY_OBS_DTYPE = np.dtype([("safety_ratio_obs", "f8"), ("closest_obstacle", "i
 OBSTACLE_REAL = 2
 OBSTACLE_DTYPE = np.dtype([("position", "f8", 3), ("velocity", "f8", 3), ("radius", "f8"), ("downwash", "f8"), ("max_acc", "f8"),
                            ("type", "i4"), ("reserved", "i4")])  # lscqp_obstacle
+# lscqp_obstacle_model: how one dynamic obstacle moves (include/lscqp.h, "dynamic obstacles in the chain"); the fields from n_legs on are
+# filled by obstacle_model_prepare
+OBSTACLE_MAX_WAYPOINTS = 8
+OBSTACLE_HELD, OBSTACLE_STRAIGHT, OBSTACLE_PATROL, OBSTACLE_SPIN = 0, 1, 2, 3  # lscqp_obstacle_model.kind
+OBSTACLE_LEG_DTYPE = np.dtype([("start", "f4", 3), ("goal", "f4", 3), ("n", "f4", 3), ("reserved", "f4"), ("dist_to_goal", "f8"), ("dist_acc", "f8"),
+                               ("flight_time", "f8")])
+OBSTACLE_MODEL_DTYPE = np.dtype([("kind", "i4"), ("n_waypoints", "i4"), ("radius", "f8"), ("downwash", "f8"), ("max_acc", "f8"), ("speed", "f8"),
+                                 ("start", "f8", 3), ("goal", "f8", 3), ("waypoints", "f8", (OBSTACLE_MAX_WAYPOINTS, 3)), ("axis_point", "f8", 3),
+                                 ("axis_direction", "f8", 3), ("n_legs", "i4"), ("prepared", "i4"), ("leg", OBSTACLE_LEG_DTYPE, OBSTACLE_MAX_WAYPOINTS),
+                                 ("lap_time", "f8"), ("spin_axis", "f8", 3), ("spin_offset", "f8", 3), ("spin_w", "f8")])
+assert OBSTACLE_LEG_DTYPE.itemsize == 64 and OBSTACLE_MODEL_DTYPE.itemsize == 912
+PLAN_OBS_TABLE, PLAN_OBS_SAFETY, PLAN_OBS_CLOCK = 0, 1, 2  # lscqp_plan_obstacle_buffer
 
 
 class ObstacleParam(C.Structure):  # lscqp_obstacle_param
@@ -214,6 +226,8 @@ EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_
                     "lscqp_safety_metrics_missions_device", "lscqp_grid_fields_missions_device", "lscqp_waypoints_missions_device", "lscqp_grid_mission_status",
                     "lscqp_record_create", "lscqp_record_destroy", "lscqp_record_reset", "lscqp_record_step_device", "lscqp_record_download",
                     "lscqp_record_points", "lscqp_record_unfinished", "lscqp_plan_set_record", "lscqp_plan_record", "lscqp_plan_run",
+                    "lscqp_obstacle_model_prepare", "lscqp_obstacles_advance_device", "lscqp_plan_set_obstacles", "lscqp_plan_obstacle_buffer",
+                    "lscqp_plan_obstacle_upload", "lscqp_plan_obstacle_download",
                     "lscqp_instance_work", "lscqp_diagnose", "lscqp_diagnose_device", "lscqp_dump_instance", "lscqp_row_family_name",
                     "lscqp_prescreen_batch_device", "lscqp_set_prescreen", "lscqp_prescreen",
                     "lscqp_last_error", "lscqp_version"]
@@ -235,6 +249,46 @@ def make_desc(M=5, dim=3, dt=0.2, w_c=0.01, w_t=1.0, comm_range=3.0, planner_mod
         d.world_max[k] = float(world_max[k])
     d.max_iter, d.tol = max_iter, tol
     return d
+
+
+def obstacle_models(specs):
+    """OBSTACLE_MODEL_DTYPE records from a list of dicts in the reference's mission-file vocabulary (missions/*.json, "obstacles"):
+    type ("straight", "patrol", "spin"; anything else -- "chasing", "gaussian", "real" -- is HELD at `start`), start, goal, waypoints, axis
+    (a pose: position x y z and the axis direction in orientation x y z, or six numbers), size (the radius), speed, max_acc, downwash.
+    Points are [x, y, z] or {"x":, "y":, "z":}.  Not prepared: obstacle_model_prepare or Plan.set_obstacles does that."""
+    def pt(v):
+        return [float(v[k]) for k in ("x", "y", "z")] if isinstance(v, dict) else [float(c) for c in v]
+
+    out = np.zeros(len(specs), OBSTACLE_MODEL_DTYPE)
+    for m, o in zip(out, specs):
+        kind = {"straight": OBSTACLE_STRAIGHT, "patrol": OBSTACLE_PATROL, "spin": OBSTACLE_SPIN}.get(o.get("type", "held"), OBSTACLE_HELD)
+        m["kind"], m["radius"], m["downwash"] = kind, float(o.get("size", 0.15)), float(o.get("downwash", 1.0))
+        m["max_acc"], m["speed"] = float(o.get("max_acc", 1.0)), float(o.get("speed", 0.0))
+        if "start" in o:
+            m["start"] = pt(o["start"])
+        if "goal" in o:
+            m["goal"] = pt(o["goal"])
+        if kind == OBSTACLE_PATROL:
+            wp = [pt(w) for w in o["waypoints"]]
+            m["n_waypoints"] = len(wp)
+            if len(wp) <= OBSTACLE_MAX_WAYPOINTS:  # (more: the library refuses the count)
+                m["waypoints"][:len(wp)] = wp
+                m["start"] = wp[0]
+        if kind == OBSTACLE_SPIN:
+            ax = o["axis"]
+            if isinstance(ax, dict):
+                pose = ax.get("pose", ax)
+                m["axis_point"], m["axis_direction"] = pt(pose["position"]), pt(pose["orientation"])
+            else:
+                m["axis_point"], m["axis_direction"] = pt(ax[:3]), pt(ax[3:6])
+    return out
+
+
+def obstacle_model_prepare(models):
+    """lscqp_obstacle_model_prepare on a copy of `models` (OBSTACLE_MODEL_DTYPE): checked, derived fields filled; no device needed."""
+    m = np.array(models, dtype=OBSTACLE_MODEL_DTYPE, ndmin=1)
+    _call("lscqp_obstacle_model_prepare", m, len(m))
+    return m
 
 
 def pack_rows(lsc):
@@ -563,6 +617,7 @@ class Plan:
         _call("lscqp_plan_create", solver._h, world_map._h if world_map is not None else None, C.byref(d), ag, C.byref(h))
         self._p, self._solver, self._map = h, solver, world_map  # (keeps the solver and the map alive)
         self.n_agents, self.n_total, self.first_agent, self.n_obs, self.M, self.nv = n_agents, n_total, first_agent, n_obs, solver.desc.M, solver.nv
+        self.n_dyn = 0  # dynamic obstacles (set_obstacles)
         self._dt = dict(self._DT)
         self._dt.update({PLAN_HEADER: HEADER_DTYPE, PLAN_ROWS: ROW_DTYPE, PLAN_SFC: BOX_DTYPE, PLAN_INFO: INFO_DTYPE, PLAN_SAFETY: SAFETY_DTYPE})
         self.waypoint_mode, self.grid_resolution, self._safety_samples = int(waypoint_mode), float(grid_resolution), int(safety_samples)
@@ -661,6 +716,40 @@ class Plan:
 
     def graph_nodes(self):
         return int(lib().lscqp_plan_graph_nodes(self._p))
+
+    def set_obstacles(self, models, param=None):
+        """lscqp_plan_set_obstacles: models is an OBSTACLE_MODEL_DTYPE array (obstacle_models builds one from mission-file entries) or None /
+        empty to take the obstacles away; param an ObstacleParam (default: the reference's launch-file values).  `reset` must follow."""
+        if models is None or len(models) == 0:
+            _call("lscqp_plan_set_obstacles", self._p, None, 0, None)
+            self.n_dyn = 0
+            return
+        m = np.ascontiguousarray(models, dtype=OBSTACLE_MODEL_DTYPE)
+        if param is None:
+            param = ObstacleParam(1.0, 0.75, 3.0, 0.1, 1, 1)
+        _call("lscqp_plan_set_obstacles", self._p, C.byref(param), len(m), m)
+        self.n_dyn = len(m)
+
+    _OBS_DT = {PLAN_OBS_TABLE: OBSTACLE_DTYPE, PLAN_OBS_SAFETY: SAFETY_OBS_DTYPE, PLAN_OBS_CLOCK: np.int32}
+
+    def obstacle_pointer(self, which):
+        nb = C.c_uint64()
+        ptr = lib().lscqp_plan_obstacle_buffer(self._p, which, C.byref(nb))
+        return ptr, nb.value
+
+    def get_obstacles(self, which=PLAN_OBS_TABLE):
+        """The plan's obstacle table as the last replan's advance left it (OBSTACLE_DTYPE), or with which = PLAN_OBS_SAFETY / PLAN_OBS_CLOCK the
+        obstacle safety figures / the clock; an empty array without obstacles."""
+        _, nb = self.obstacle_pointer(which)
+        out = np.zeros(nb // np.dtype(self._OBS_DT[which]).itemsize, dtype=self._OBS_DT[which])
+        if nb:
+            _call("lscqp_plan_obstacle_download", self._p, which, out, 0, nb)
+        return out
+
+    def put_obstacles(self, table, first=0):
+        """Entries [first, first + len) of the table: the caller's to write for OBSTACLE_HELD models, between eager replans."""
+        a = np.ascontiguousarray(table, dtype=OBSTACLE_DTYPE)
+        _call("lscqp_plan_obstacle_upload", self._p, PLAN_OBS_TABLE, a, first * OBSTACLE_DTYPE.itemsize, a.nbytes)
 
     def set_record(self, goal_threshold=0.1):
         """lscqp_plan_set_record: the plan keeps a mission record, accumulated by the chain's last node (None: no record).  `reset` must follow."""
@@ -1142,6 +1231,10 @@ class Solver:
         """generateLSC for non-agent obstacles (param: ObstacleParam; d_obstacles: OBSTACLE_DTYPE table on the device)."""
         _call("lscqp_generate_lsc_obstacles_device", self._h, C.cast(C.byref(param), C.c_void_p), n_agents, n_dyn, first_agent, d_traj, d_ids, d_obstacles,
               d_radius, d_goal, d_hdr, d_rows, int(n_obs_total), int(slot0), stream=stream)
+
+    def obstacles_advance_device(self, d_models, n_dyn, time_step, d_clock, d_obstacles, stream=None):
+        """lscqp_obstacles_advance_device: the table moved to the clock's replan, the clock advanced; d_models PREPARED models on the device."""
+        _call("lscqp_obstacles_advance_device", self._h, d_models, int(n_dyn), float(time_step), d_clock, d_obstacles, stream=stream)
 
     def generate_lsc_bytes(self, n_agents, n_obs, n_total):
         return lib().lscqp_generate_lsc_bytes(self._h, n_agents, n_obs, n_total)

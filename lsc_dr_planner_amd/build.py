@@ -81,7 +81,9 @@ def units():
         ("lscsfc.hip", "lscsfc", [], None, False),
         ("lscsfc_tp.hip", "lscsfc_tp", [], None, False),
         ("lscqp_comm.hip", "lscqp_comm", [], None, False),
-        ("lscplan.hip", "lscplan", [], None, False),
+        # (lscplan.hip includes lscobstacle.hip, the obstacles' motion: one object.  The remark puts obstacle_advance_kernel's registers,
+        # scratch and LDS into the verbose build's log: the kernel is required to use no scratch)
+        ("lscplan.hip", "lscplan", ["-Rpass-analysis=kernel-resource-usage"], None, False),
         ("lscgrid.hip", "lscgrid", [], None, False),
         ("lscgen.hip", "lscgen", [], None, False),
         ("lscqp_generic.hip", "lscqp_generic", [], None, False),

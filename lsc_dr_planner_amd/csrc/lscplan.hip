@@ -19,6 +19,9 @@
 // A plan with a mission partition (lscqp_plan_set_missions) flies many independent missions over one map in the same chain: the three
 // steps in which agents see each other -- the waypoint decision, the range filter, the safety figures -- run as their mission-aware twins,
 // every other step is per agent and does not know.
+// A plan with dynamic obstacles (lscqp_plan_set_obstacles) gains three nodes: the obstacles' motion (lscobstacle.hip) in front of `prepare`, their
+// rows (generateLSC's non-agent branch) behind the agents' rows -- they take the first row slots of every agent -- and the obstacle leg of the
+// safety figures behind the agents'.  ObstacleGenerator::update(t, 0) -> obstacle_advance_kernel, src/multi_sync_simulator.cpp:311.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -28,6 +31,8 @@
 
 #include "../../include/lscqp.h"
 #include "lscqp_internal.hpp"
+// the obstacles' motion: obstacle_advance_kernel, lscqp_obstacle_model_prepare, lscqp_obstacles_advance_device (built as part of this unit)
+#include "lscobstacle.hip"
 
 namespace lscplan {
 
@@ -220,6 +225,15 @@ struct lscqp_plan_s {
     lscqp_record_desc rec_desc = {0.0};
     lscqp_record rec = nullptr;
     bool record_pending = false;  // the record was set or its partition changed and lscqp_plan_reset has not come yet
+    // dynamic obstacles (lscqp_plan_set_obstacles): n_dyn = 0 = none, the chain as it always was.  They take row slots [0, n_dyn) of every agent
+    int32_t n_dyn = 0;
+    lscqp_obstacle_param obs_param = {};
+    std::vector<lscqp_obstacle_model> obs_models;  // prepared; HELD entries start at `start`
+    lscqp_obstacle_model* d_obs_models = nullptr;
+    lscqp_obstacle* obs_table = nullptr;
+    int32_t *obs_ids = nullptr, *obs_clock = nullptr;  // ids: 0 .. n_dyn - 1 for every local agent
+    lscqp_safety_obs* obs_safety = nullptr;
+    bool obstacles_pending = false;  // the obstacles were set and lscqp_plan_reset has not come yet
     bool wide() const { return decision == LSCQP_DECISION_WIDE || (decision == LSCQP_DECISION_AUTO && s.n_total >= LSCQP_DECISION_AUTO_MIN_AGENTS); }
 };
 
@@ -283,6 +297,8 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     if (p->missions_pending) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_missions: lscqp_plan_reset must come before the next step");
     if (p->rec_on && (p->record_pending || !p->rec))
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: lscqp_plan_reset must come before the next step");
+    if (p->obstacles_pending) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacles: lscqp_plan_reset must come before the next step");
+    const int32_t n_dyn = p->n_dyn, n_nbr = s.n_obs - n_dyn;  // row slots [0, n_dyn): the obstacles, [n_dyn, n_obs): the in-range agents
     // decentralizedMAPP precedes the planning loop (src/multi_sync_simulator.cpp:101-120): the waypoints of this replan, from the plans as the
     // last replan left them (AgentManager::getTraj is desired_traj, un-shifted)
     if (p->grid) {
@@ -298,6 +314,8 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
             PLAN_TRY(lscqp_waypoints_device(p->grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, state, x_plan, goal, p->field, p->init_d,
                                             waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], p->desired_node, (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
     }
+    // obstacle_generator.update(t, 0) at the replan's start time (src/multi_sync_simulator.cpp:311); the clock is the device's
+    if (n_dyn > 0) PLAN_TRY(lscqp_obstacles_advance_device(h, p->d_obs_models, n_dyn, p->d.time_step, p->obs_clock, p->obs_table, stream));
     // obstaclePredictionWithPrevSol / initialTrajPlanningPrevSol for every agent of the mission (:273-310, 399-423)
     const bool from_plans = !first_replan && (s.prediction_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION || s.initial_traj_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION);
     const bool whole_shift = from_plans && fraction >= 1.0 - 1e-9;  // (done by prepare_kernel itself)
@@ -315,14 +333,19 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
                                                     p->radius + s.first_agent, sfc, sfc_status, sfc_order, p->sfc_cost, stream));
     }
     if (K > 1)
-        PLAN_TRY(lscqp_select_neighbours_missions_device(h, s.n_total, K, p->moff.data(), p->d_moff, s.n_obs, lscqp_class_desc_of_(h)->communication_range, p->pos,
+        PLAN_TRY(lscqp_select_neighbours_missions_device(h, s.n_total, K, p->moff.data(), p->d_moff, n_nbr, lscqp_class_desc_of_(h)->communication_range, p->pos,
                                                          p->nbr, count, stream));
     else
-        PLAN_TRY(lscqp_select_neighbours_device(h, s.n_agents, s.first_agent, s.n_total, s.n_obs, lscqp_class_desc_of_(h)->communication_range, p->pos, p->nbr, count,
+        PLAN_TRY(lscqp_select_neighbours_device(h, s.n_agents, s.first_agent, s.n_total, n_nbr, lscqp_class_desc_of_(h)->communication_range, p->pos, p->nbr, count,
                                                 stream));
-    if (s.n_obs > 0)
-        PLAN_TRY(lscqp_generate_constraints_own_(h, p->d.constraint_mode, s.n_agents, s.n_obs, s.first_agent, p->traj, p->own, p->nbr, p->radius,
-                                                 p->downwash, goal, rows, s.n_obs, 0, stream));
+    if (n_nbr > 0)
+        PLAN_TRY(lscqp_generate_constraints_own_(h, p->d.constraint_mode, s.n_agents, n_nbr, s.first_agent, p->traj, p->own, p->nbr, p->radius,
+                                                 p->downwash, goal, rows, s.n_obs, n_dyn, stream));
+    // the obstacles' rows (generateLSC's non-agent branch) over the planning agents' INITIAL trajectories: `own`, indexed by local id like
+    // the radii, goals and headers handed over here -- `traj` holds the agents' predictions as each other's obstacles by now
+    if (n_dyn > 0)
+        PLAN_TRY(lscqp_generate_lsc_obstacles_device(h, &p->obs_param, s.n_agents, n_dyn, 0, p->own, p->obs_ids, p->obs_table, p->radius + s.first_agent,
+                                                     goal + s.first_agent * 3, hdr, rows, s.n_obs, 0, stream));
     if (p->d.optimize_goal) {  // (the goal LP's kernel finishes the headers itself: one node less)
         PLAN_TRY(lscqp_optimize_goal_fin_device_(h, s.n_agents, hdr, rows, p->off, p->map ? sfc : nullptr, goal_status, s.dt, stream));
     } else {
@@ -353,6 +376,10 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     else if (p->d.safety_samples > 0)  // MultiSyncSimulator::update's safety ratio / excess ratios over the step just planned (:486-577)
         PLAN_TRY(lscqp_safety_metrics_device(h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan,
                                              p->radius, p->downwash, hdr, (lscqp_safety*)p->buf[LSCQP_PLAN_BUF_SAFETY], stream));
+    // the obstacle leg of the safety figures (:527-557), against the positions this replan's advance left
+    if (p->d.safety_samples > 0 && n_dyn > 0)
+        PLAN_TRY(lscqp_safety_obstacles_device(h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan, p->radius,
+                                               p->downwash, n_dyn, p->obs_table, p->obs_safety, stream));
     // the mission record: the figures of this replan and the finish test on the state it started from (hdr.p0), the chain's last node
     if (p->rec_on)
         PLAN_TRY(lscqp_record_step_device(p->rec, hdr, x_plan, status, goal_status, sfc_status, valid, count, (const lscqp_safety*)p->buf[LSCQP_PLAN_BUF_SAFETY],
@@ -369,6 +396,29 @@ void drop_graph(lscqp_plan_s* p) {
     if (p->graph) (void)hipGraphDestroy(p->graph);
     p->exec = nullptr;
     p->graph = nullptr;
+}
+
+void free_obstacles(lscqp_plan_s* p) {
+    for (void* q : {(void*)p->d_obs_models, (void*)p->obs_table, (void*)p->obs_ids, (void*)p->obs_clock, (void*)p->obs_safety})
+        if (q) (void)hipFree(q);
+    p->d_obs_models = nullptr, p->obs_table = nullptr, p->obs_ids = nullptr, p->obs_clock = nullptr, p->obs_safety = nullptr;
+    p->obs_models.clear();
+    p->n_dyn = 0;
+    p->obstacles_pending = false;
+}
+
+// the table at t = 0 as far as the host knows it -- common fields, HELD entries at their start; the first advance writes the rest -- and the clock
+int reset_obstacles(lscqp_plan_s* p) {
+    std::vector<lscqp_obstacle> tab((size_t)p->n_dyn);
+    memset(tab.data(), 0, tab.size() * sizeof(lscqp_obstacle));
+    for (int i = 0; i < p->n_dyn; i++) {
+        const lscqp_obstacle_model& m = p->obs_models[(size_t)i];
+        for (int k = 0; k < 3; k++) tab[(size_t)i].position[k] = (double)(float)m.start[k];
+        tab[(size_t)i].radius = m.radius, tab[(size_t)i].downwash = m.downwash, tab[(size_t)i].max_acc = m.max_acc;
+    }
+    hipError_t e = hipMemcpy(p->obs_table, tab.data(), tab.size() * sizeof(lscqp_obstacle), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(p->obs_clock, 0, sizeof(int32_t));
+    return e == hipSuccess ? LSCQP_OK : hip_fail(e, "plan reset (obstacles)");
 }
 
 // the plan's grid and the buffers sized by it (waypoint_mode 1): made at lscqp_plan_create, again by lscqp_plan_set_grid
@@ -644,6 +694,7 @@ void lscqp_plan_destroy(lscqp_plan p) {
     if (p->field) (void)hipFree(p->field);
     if (p->rec) lscqp_record_destroy(p->rec);
     if (p->d_moff) (void)hipFree(p->d_moff);
+    free_obstacles(p);
     if (p->own_hq) lscqp_destroy(p->hq);
     delete p;
 }
@@ -686,6 +737,8 @@ int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* 
         PLAN_TRY(lscqp_record_reset(p->rec, want.data()));
         p->record_pending = false;
     }
+    if (p->n_dyn > 0) PLAN_TRY(reset_obstacles(p));
+    p->obstacles_pending = false;
     p->missions_pending = false;
     p->first = true;
     p->steps = 0;
@@ -887,6 +940,110 @@ int lscqp_plan_set_record(lscqp_plan p, const lscqp_record_desc* desc) {
 }
 
 lscqp_record lscqp_plan_record(lscqp_plan p) { return p ? p->rec : nullptr; }
+
+int lscqp_plan_set_obstacles(lscqp_plan p, const lscqp_obstacle_param* param, int32_t n_dyn, const lscqp_obstacle_model* models) {
+    if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
+    if (n_dyn < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacles: negative n_dyn");
+    const bool none = n_dyn == 0 || !models;
+    std::vector<lscqp_obstacle_model> prepared;
+    if (!none) {
+        if (!param) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacles: null param");
+        if (n_dyn > p->s.n_obs)
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacles: n_dyn exceeds the plan's row slots per agent (n_dyn <= desc.n_obs required)");
+        if (p->d.constraint_mode != LSCQP_GEN_LSC)
+            return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_plan_set_obstacles: constraint_mode must be LSCQP_GEN_LSC (the obstacle rows are generateLSC's)");
+        prepared.assign(models, models + n_dyn);
+        PLAN_TRY(lscqp_obstacle_model_prepare(prepared.data(), n_dyn));
+    }
+    DeviceGuard g(p->device);
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_obstacles");
+    if (none) {
+        drop_graph(p);  // (a captured chain holds the obstacles' nodes and the slot split)
+        free_obstacles(p);
+        return LSCQP_OK;
+    }
+    // (everything that can fail comes before the plan changes)
+    const size_t n = (size_t)p->s.n_agents, nd = (size_t)n_dyn;
+    void *dm = nullptr, *tab = nullptr, *ids = nullptr, *clk = nullptr, *saf = nullptr;
+    std::vector<int32_t> hid((n ? n : 1) * nd);
+    for (size_t a = 0; a < n; a++)
+        for (size_t o = 0; o < nd; o++) hid[a * nd + o] = (int32_t)o;
+    e = hipMalloc(&dm, nd * sizeof(lscqp_obstacle_model));
+    if (e == hipSuccess) e = hipMalloc(&tab, nd * sizeof(lscqp_obstacle));
+    if (e == hipSuccess) e = hipMalloc(&ids, hid.size() * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&clk, sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&saf, (n ? n : 1) * sizeof(lscqp_safety_obs));
+    if (e == hipSuccess) e = hipMemcpy(dm, prepared.data(), nd * sizeof(lscqp_obstacle_model), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ids, hid.data(), hid.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(saf, 0, (n ? n : 1) * sizeof(lscqp_safety_obs));
+    if (e != hipSuccess) {
+        for (void* q : {dm, tab, ids, clk, saf})
+            if (q) (void)hipFree(q);
+        return hip_fail(e, "lscqp_plan_set_obstacles");
+    }
+    drop_graph(p);
+    free_obstacles(p);
+    p->d_obs_models = (lscqp_obstacle_model*)dm, p->obs_table = (lscqp_obstacle*)tab, p->obs_ids = (int32_t*)ids, p->obs_clock = (int32_t*)clk;
+    p->obs_safety = (lscqp_safety_obs*)saf;
+    p->obs_models.swap(prepared);
+    p->obs_param = *param;
+    p->n_dyn = n_dyn;
+    const int rc = reset_obstacles(p);  // (so that the table can be read, and HELD entries written, before the reset)
+    if (rc != LSCQP_OK) {
+        free_obstacles(p);
+        return rc;
+    }
+    p->obstacles_pending = true;
+    return LSCQP_OK;
+}
+
+namespace {
+void* obstacle_buffer(lscqp_plan_s* p, int32_t which, size_t* bytes) {
+    *bytes = 0;
+    if (p->n_dyn == 0) return nullptr;
+    switch (which) {
+    case LSCQP_PLAN_OBS_TABLE: *bytes = (size_t)p->n_dyn * sizeof(lscqp_obstacle); return p->obs_table;
+    case LSCQP_PLAN_OBS_SAFETY: *bytes = (size_t)p->s.n_agents * sizeof(lscqp_safety_obs); return p->obs_safety;
+    case LSCQP_PLAN_OBS_CLOCK: *bytes = sizeof(int32_t); return p->obs_clock;
+    }
+    return nullptr;
+}
+}  // namespace
+
+void* lscqp_plan_obstacle_buffer(lscqp_plan p, int32_t which, uint64_t* bytes_out) {
+    if (bytes_out) *bytes_out = 0;
+    if (!p || which < 0 || which >= LSCQP_PLAN_OBS_COUNT) {
+        lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "unknown obstacle buffer");
+        return nullptr;
+    }
+    size_t b = 0;
+    void* q = obstacle_buffer(p, which, &b);
+    if (bytes_out) *bytes_out = b;
+    return q;
+}
+
+int lscqp_plan_obstacle_upload(lscqp_plan p, int32_t which, const void* host, uint64_t offset, uint64_t bytes) {
+    if (!p || !host || which < 0 || which >= LSCQP_PLAN_OBS_COUNT) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
+    size_t b = 0;
+    void* q = obstacle_buffer(p, which, &b);
+    if (offset > b || bytes > b - offset) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "range exceeds the buffer");
+    if (bytes == 0) return LSCQP_OK;
+    DeviceGuard g(p->device);
+    const hipError_t e = hipMemcpy((char*)q + offset, host, bytes, hipMemcpyHostToDevice);
+    return e == hipSuccess ? LSCQP_OK : hip_fail(e, "plan obstacle upload");
+}
+
+int lscqp_plan_obstacle_download(lscqp_plan p, int32_t which, void* host, uint64_t offset, uint64_t bytes) {
+    if (!p || !host || which < 0 || which >= LSCQP_PLAN_OBS_COUNT) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
+    size_t b = 0;
+    void* q = obstacle_buffer(p, which, &b);
+    if (offset > b || bytes > b - offset) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "range exceeds the buffer");
+    if (bytes == 0) return LSCQP_OK;
+    DeviceGuard g(p->device);
+    const hipError_t e = hipMemcpy(host, (const char*)q + offset, bytes, hipMemcpyDeviceToHost);  // waits for the device
+    return e == hipSuccess ? LSCQP_OK : hip_fail(e, "plan obstacle download");
+}
 
 int lscqp_plan_run(lscqp_plan p, int64_t max_replans, int32_t check_every, int32_t use_graph, void* stream, int64_t* replans_enqueued) {
     if (replans_enqueued) *replans_enqueued = 0;

@@ -120,12 +120,24 @@ def seeded_missions(world, occ, grid_min, missions, seed=0):
     return np.arange(missions + 1) * n, np.concatenate(starts), np.concatenate(goals)
 
 
+def load_obstacles(path):
+    """The reference's mission-file obstacle list (missions/*.json: "obstacles": [{"type", "start", "goal", "waypoints", "axis", "size", "speed",
+    "max_acc", "downwash"}, ...]; a bare list is taken too) as api.OBSTACLE_MODEL_DTYPE records.  2-D worlds: the file gives z as well."""
+    from lsc_dr_planner_amd import api
+
+    doc = json.load(open(path))
+    return api.obstacle_models(doc["obstacles"] if isinstance(doc, dict) else doc)
+
+
 def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=0, graph=True, until_finished=None, check_every=16,
-                 goal_threshold=0.1):
+                 goal_threshold=0.1, obstacles=None):
     """`missions` seeded missions over one world flown by ONE lscqp_plan with a mission partition (include/lscqp.h, "many missions over one
     map"): waypoint_mode 1, closed loop, one captured graph per replan.  The summary has the figures of `run` per mission.
     until_finished = MAX: the plan keeps a mission record (include/lscqp.h, "the mission record") and lscqp_plan_run flies it until every
-    mission has finished or MAX replans, with no download in between; per mission the summary then holds the device's record."""
+    mission has finished or MAX replans, with no download in between; per mission the summary then holds the device's record.
+    obstacles: api.OBSTACLE_MODEL_DTYPE records (load_obstacles) -- the dynamic obstacles every mission shares, moved by the chain itself
+    (lscqp_plan_set_obstacles).  Their rows are generateLSC's, so the agents' rows are LSC rows too (GEN_LSC instead of GEN_CLSC), and
+    they take the first row slots: n_obs counts the agent slots, the plan gets n_obs + len(obstacles)."""
     import torch
 
     from lsc_dr_planner_amd import api
@@ -138,11 +150,15 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     off, starts, goals = seeded_missions(g, probe.download(), probe.grid_min, missions, seed)
     probe.close()
     N = int(off[-1])
-    n_obs = max(1, min(n - 1 if n_obs is None else n_obs, sol.max_obstacles()))
+    n_dyn = 0 if obstacles is None else len(obstacles)
+    n_obs = max(1, min((n - 1 if n_obs is None else n_obs) + n_dyn, sol.max_obstacles()))
     ag = np.zeros(N, api.AGENT_PARAM_DTYPE)
     ag["radius"], ag["downwash"], ag["max_vel"], ag["max_acc"], ag["nominal_velocity"] = g["radius"], 2.0, 1.0, 2.0, 1.0
-    plan = api.Plan(sol, wmap, N, n_obs, ag, constraint_mode=api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, optimize_goal=True, closed_loop=True,
-                    z_2d=float(g["z_2d"]), safety_samples=2, record_time_step=0.1, waypoint_mode=api.WAYPOINT_GRID_PIBT, mission_offsets=off)
+    plan = api.Plan(sol, wmap, N, n_obs, ag, constraint_mode=api.GEN_LSC if n_dyn else api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, optimize_goal=True,
+                    closed_loop=True, z_2d=float(g["z_2d"]), safety_samples=2, record_time_step=0.1, waypoint_mode=api.WAYPOINT_GRID_PIBT,
+                    mission_offsets=off)
+    if n_dyn:
+        plan.set_obstacles(obstacles)
     if until_finished:
         plan.set_record(goal_threshold)
         plan.reset(starts, goals)
@@ -160,16 +176,21 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
                    agents=N, row_slots=n_obs, router="device", sim_time_s=enqueued * dt, graph_nodes=plan.graph_nodes(),
                    finished=sum(m["finished"] for m in per), qp_failed=sum(m["qp_failed"] for m in per), invalid=sum(m["invalid"] for m in per),
                    min_safety_ratio=min(m["min_safety_ratio"] for m in per), per_mission=per)
+        if n_dyn:  # (the record keeps no obstacle figure: the last replan's is what the plan still holds)
+            log.update(obstacles=n_dyn, last_obstacle_safety_ratio=float(plan.get_obstacles(api.PLAN_OBS_SAFETY)["safety_ratio_obs"].min()))
         plan.close()
         wmap.close()
         return log
     plan.reset(starts, goals)
+    min_obstacle_ratio = np.inf
     per = [dict(mission=k, agents=n, qp_failed=0, invalid=0, min_safety_ratio=np.inf, max_vel_excess=0.0, max_acc_excess=0.0, waypoints_updated=0,
                 truncated_agent_steps=0) for k in range(missions)]
     for _ in range(steps):
         plan.step(graph=graph)
         torch.cuda.synchronize()
         st, valid, saf, upd, cnt = (plan.get(b) for b in (api.PLAN_STATUS, api.PLAN_VALID, api.PLAN_SAFETY, api.PLAN_WAYPOINT_UPDATED, api.PLAN_IN_RANGE))
+        if n_dyn:
+            min_obstacle_ratio = float(min(min_obstacle_ratio, plan.get_obstacles(api.PLAN_OBS_SAFETY)["safety_ratio_obs"].min()))
         for k, m in enumerate(per):
             sl = slice(int(off[k]), int(off[k + 1]))
             m["qp_failed"] += int((st[sl] != 0).sum())
@@ -178,7 +199,7 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
             m["max_vel_excess"] = float(max(m["max_vel_excess"], saf["vel_excess_ratio"][sl].max()))
             m["max_acc_excess"] = float(max(m["max_acc_excess"], saf["acc_excess_ratio"][sl].max()))
             m["waypoints_updated"] += int(upd[sl].sum())
-            m["truncated_agent_steps"] += int((cnt[sl] > n_obs).sum())
+            m["truncated_agent_steps"] += int((cnt[sl] > n_obs - n_dyn).sum())
     state = plan.get(api.PLAN_STATE).reshape(N, 9)
     progress = np.linalg.norm(goals[:, :2] - starts[:, :2], axis=1) - np.linalg.norm(goals[:, :2] - state[:, :2], axis=1)
     status = plan.mission_status()
@@ -188,13 +209,15 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     log = dict(steps=steps, missions=missions, agents=N, row_slots=n_obs, router="device", sim_time_s=steps * dt, graph_nodes=plan.graph_nodes(),
                qp_failed=sum(m["qp_failed"] for m in per), invalid=sum(m["invalid"] for m in per),
                min_safety_ratio=min(m["min_safety_ratio"] for m in per), per_mission=per)
+    if n_dyn:
+        log.update(obstacles=n_dyn, min_obstacle_safety_ratio=min_obstacle_ratio)
     plan.close()
     wmap.close()
     return log
 
 
 def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None, router="host", missions=None,
-        decision="one", until_finished=None):
+        decision="one", until_finished=None, obstacles=None):
     """script (optional): {"waypoint": (K, N, 3), "state": (K, N, 9)} -- replay of a recorded mission: replan k takes every agent's
     state and waypoint from the script instead of the loop's own step / router (the plans, goal points, corridors and neighbour sets are
     still the loop's own), and the result carries every replan's solution (`x`, (K, N, nv)) and goal point (`goal`, (K, N, 3)).
@@ -202,15 +225,18 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
     missions: K > 0 flies K seeded missions over the world in one lscqp_plan (run_missions) and reports per-mission figures.
     decision (router "device"): "one" (lscqp_waypoints_device), "wide" (lscqp_waypoints_wide_device) or "auto" (wide from
     DECISION_AUTO_MIN_AGENTS agents on); the flight is the same whichever is chosen.
-    until_finished (with missions): fly until every mission has finished, at most that many replans (run_missions)."""
+    until_finished (with missions): fly until every mission has finished, at most that many replans (run_missions).
+    obstacles (with missions): dynamic obstacles flown by the plan's own chain (load_obstacles, run_missions)."""
     if router not in ("host", "device"):
         raise ValueError("router must be 'host' or 'device'")
     if decision not in ("one", "wide", "auto"):
         raise ValueError("decision must be 'one', 'wide' or 'auto'")
     if until_finished and not missions:
         raise ValueError("until_finished needs missions=K (one lscqp_plan with a mission record)")
+    if obstacles is not None and not missions:
+        raise ValueError("obstacles need missions=K (K >= 1): they fly in the chain of an lscqp_plan (lscqp_plan_set_obstacles)")
     if missions:
-        return run_missions(world_json, int(missions), steps=steps, M=M, dt=dt, n_obs=n_obs, until_finished=until_finished)
+        return run_missions(world_json, int(missions), steps=steps, M=M, dt=dt, n_obs=n_obs, until_finished=until_finished, obstacles=obstacles)
     import torch
 
     from lsc_dr_planner_amd import api
@@ -412,8 +438,11 @@ if __name__ == "__main__":
                          "one record per mission")
     ap.add_argument("--decision", default="one", choices=("one", "wide", "auto"),
                     help="with --router device: the one-workgroup decision, lscqp_waypoints_wide_device, or wide from DECISION_AUTO_MIN_AGENTS agents on")
+    ap.add_argument("--obstacles", default=None, metavar="FILE.json",
+                    help="with --missions K: the dynamic obstacles of a reference mission file (its \"obstacles\" list, or a bare list: type, start, goal, "
+                         "waypoints, axis, size, speed, max_acc, downwash), shared by every mission and moved by the plan's chain")
     ap.add_argument("--router", default="host", choices=("host", "device"), help="where the waypoints come from: the host stand-in or lscqp_waypoints_device")
     a = ap.parse_args()
     world = random_forest_world(a.forest) if a.forest > 0 else a.world
     print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router, missions=a.missions, decision=a.decision,
-                         until_finished=a.until_finished)))
+                         until_finished=a.until_finished, obstacles=load_obstacles(a.obstacles) if a.obstacles else None)))
