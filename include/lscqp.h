@@ -930,8 +930,9 @@ int lscqp_plan_group_step(lscqp_comm c, const lscqp_plan* plans, int32_t use_gra
 
 /* ---- many missions over one map: a mission partition of a plan's agents --------------------------------------------------------------
  *
- * The reference is evaluated on sets of missions over ONE world (launch/test_all_*.launch: missions/<set>/<set>_1..30.json, one result
- * line per mission).  A partition lets one plan fly K such missions in one chain per replan.  Missions are contiguous ranges of global
+ * The reference is evaluated on sets of missions (launch/test_all_*.launch: missions/<set>/<set>_1..30.json, one result line per
+ * mission), mission k over world k of a set of worlds of one shape -- see "each mission over its own world" below for the worlds; with
+ * ONE map every mission of the plan flies over that map.  A partition lets one plan fly K such missions in one chain per replan.  Missions are contiguous ranges of global
  * agent ids, [mission_offsets[k], mission_offsets[k + 1]), the list strictly increasing from 0 to n_total (no empty mission).  Agents of
  * different missions share the map and the solver class and nothing else: they are never each other's neighbours (no LSC / BVC rows for
  * each other), never in one communication group, never compete for a grid node, never enter each other's safety figures, and their start
@@ -941,7 +942,8 @@ int lscqp_plan_group_step(lscqp_comm c, const lscqp_plan* plans, int32_t use_gra
  *                             lscqp_plan_reset is refused (LSCQP_ERR_INVALID_ARGUMENT).  n_missions <= 1 or NULL offsets: back to the single
  *                             mission, whose chain is the one a plan without this call runs, launch for launch.  A bad offset list and a
  *                             sharded plan (n_agents != n_total, the rule of safety_samples and waypoint_mode 1) are refused and leave the
- *                             plan as it was.  Out of scope: different maps, classes or n_obs per mission; missions across devices.
+ *                             plan as it was.  Out of scope: different classes or n_obs per mission; missions across devices (a map per mission:
+ *                             lscqp_plan_set_worlds, which refuses another mission count here while worlds are set).
  *   lscqp_plan_missions       the partition read back: *n_missions_out (1 without a partition) and, if offsets_out != NULL, its
  *                             n_missions + 1 offsets.
  *   lscqp_plan_mission_status status_out [n_missions], host; waits for the device.  The word of each mission's waypoint walk: 0 = fine,
@@ -996,6 +998,63 @@ int lscqp_waypoints_missions_device(lscqp_grid grid, double communication_range,
                                     const double* d_plan, const double* d_current_goal, const int32_t* d_field, const int32_t* d_init_d,
                                     double* d_waypoint, int32_t* d_group_out, int32_t* d_desired_out, int32_t* d_updated_out, void* stream);
 int lscqp_grid_mission_status(lscqp_grid grid, int32_t n_missions, int32_t* status_out);
+
+/* ---- each mission over its own world: a set of maps of one shape ------------------------------------------------------------------------
+ *
+ * The reference's evaluation sets pair mission k with world k (launch/test_all_forest.launch names a mission directory and a world
+ * directory of thirty files each; Mission::loadMission, src/mission.cpp:82-92, pairs them by index when the lists are equally long, and
+ * multi_sync_simulator_node.cpp:44-59 loops over the pairs): thirty missions over thirty worlds of ONE SHAPE -- same world box, same
+ * resolution, different pillars.  Two steps of a replan read the map: the corridor kernel and the grid's static occupancy.
+ *   lscqp_worlds_create      n_worlds >= 1 maps on the current device that agree in resolution, world box (as float32), key0, dims and
+ *                            max_dist; anything else is LSCQP_ERR_INVALID_ARGUMENT naming the first differing member and field.  The set
+ *                            BORROWS its maps (they must outlive it; one map may appear twice) and owns one small device table: per world
+ *                            the address of the nearest-cell field and of the free-space table.
+ *   lscqp_worlds_prepare     lscqp_map_prepare on every member with one margin -- max_radius, or the largest margin a member already has a
+ *                            table for -- and the table rewritten.  The corridor kernel carries the margin by value, so one margin serves
+ *                            all worlds: if a member has no table, or the members' margins differ (one was prepared directly), a launch
+ *                            uses no table at all -- every test is evaluated, the boxes are the same bit for bit.
+ *   lscqp_worlds_info        *n_worlds, and dims[3] / key0[3] of the common shape (either may be NULL).
+ *                            The set's own work (its table, lscqp_worlds_prepare, lscqp_worlds_destroy) and lscqp_grid_set_worlds run on
+ *                            the device the set / the grid lives on, whichever is current; a LAUNCH with another device current is refused.
+ *   lscqp_construct_sfc_worlds_device   lscqp_construct_sfc_device_ordered in which agent a is tested against world d_world_of[a]
+ *                            (int32 [n], device).  The index belongs to the AGENT: with a work order, workgroup k builds agent d_order[k]
+ *                            in world d_world_of[d_order[k]].  PRECONDITION: every index lies in [0, n_worlds); the kernel does not test
+ *                            it.  A member prepared behind the set's back is noticed through its generation counter: the table is
+ *                            rewritten before the launch (which waits for the device), or -- on a stream that is being captured -- the
+ *                            launch is refused.  A stale address is never launched.  The kernel fetches its agent's two addresses once,
+ *                            two scalar loads per workgroup, and then runs the statements of lscqp_construct_sfc_device.
+ *   lscqp_grid_set_worlds    the grid's base occupancy per world: updateGridMap once per member into [n_worlds][nodes], with the
+ *                            arithmetic of lscqp_grid_create.  The worlds' box must give the grid's own shape.  The grid keeps nothing of
+ *                            the maps.  lscqp_grid_fields_missions_device then starts mission k's copy from base k and refuses a partition
+ *                            whose n_missions differs from the world count; the one-mission entries (lscqp_grid_fields_device,
+ *                            lscqp_waypoints_device, lscqp_waypoints_wide_device) refuse such a grid with LSCQP_ERR_UNSUPPORTED.
+ *                            NULL: back to the one base of lscqp_grid_create.  lscqp_grid_download_world: base k, uint8 [dims[1]][dims[0]].
+ *   lscqp_plan_set_worlds    world k for mission k of the plan's partition.  Like lscqp_plan_set_missions it waits for the device, drops a
+ *                            captured graph and invalidates the distance fields, and a step before the next lscqp_plan_reset is refused.
+ *                            Refused, the plan left as it was: no partition or one whose mission count differs from the world count; a
+ *                            shape or device other than that of the map the plan was created with; a class without corridors.  While
+ *                            worlds are set lscqp_plan_set_missions with another count is refused; one with the same count and other
+ *                            offsets is taken, and the agents' world index follows it: an agent that changes mission changes world.  The plan's corridor node becomes the
+ *                            worlds launch (work order and cost carry-over as before), in waypoint_mode 1 its grid gets the worlds
+ *                            (lscqp_plan_set_grid re-applies them), the members are prepared through lscqp_worlds_prepare with the agents'
+ *                            largest radius -- the last step of the call that can fail and the one that reaches beyond the plan: where it
+ *                            has to rebuild a member's free-space table that map's generation counter moves, and every OTHER plan over
+ *                            that map drops its captured graph (and re-makes its grid) at its next step, also when this call is refused
+ *                            behind it --, and the generation check in front of every step covers every member.  The set must outlive
+ *                            the plan or be taken away first.  NULL: back to the one map -- such a plan, and one that never saw the call,
+ *                            enqueues the chain it always did node for node.  Dynamic obstacles are shared by all missions; the record and
+ *                            lscqp_plan_run do not know.  Out of scope: worlds of different shape; sharded plans; 3-D grids. */
+typedef struct lscqp_worlds_s* lscqp_worlds;
+int lscqp_worlds_create(const lscqp_map* maps, int32_t n_worlds, lscqp_worlds* out);
+void lscqp_worlds_destroy(lscqp_worlds worlds);
+int lscqp_worlds_prepare(lscqp_worlds worlds, double max_radius);
+int lscqp_worlds_info(lscqp_worlds worlds, int32_t* n_worlds, int32_t* dims, int32_t* key0);
+int lscqp_construct_sfc_worlds_device(lscqp_handle h, lscqp_worlds worlds, int32_t mode, int64_t n, const int32_t* d_world_of,
+                                      const double* d_points, const double* d_radius, lscqp_box* d_sfc, int32_t* d_status_out,
+                                      const int32_t* d_order, uint32_t* d_cost_out, void* stream);
+int lscqp_grid_set_worlds(lscqp_grid grid, lscqp_worlds worlds);
+int lscqp_grid_download_world(lscqp_grid grid, int32_t k, uint8_t* occ);
+int lscqp_plan_set_worlds(lscqp_plan plan, lscqp_worlds worlds);
 
 /* ---- the mission record: each mission's summary figures kept on the device, and plans flown to the finish -----------------------------
  *

@@ -228,6 +228,8 @@ EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_
                     "lscqp_record_points", "lscqp_record_unfinished", "lscqp_plan_set_record", "lscqp_plan_record", "lscqp_plan_run",
                     "lscqp_obstacle_model_prepare", "lscqp_obstacles_advance_device", "lscqp_plan_set_obstacles", "lscqp_plan_obstacle_buffer",
                     "lscqp_plan_obstacle_upload", "lscqp_plan_obstacle_download",
+                    "lscqp_worlds_create", "lscqp_worlds_destroy", "lscqp_worlds_prepare", "lscqp_worlds_info", "lscqp_construct_sfc_worlds_device",
+                    "lscqp_grid_set_worlds", "lscqp_grid_download_world", "lscqp_plan_set_worlds",
                     "lscqp_instance_work", "lscqp_diagnose", "lscqp_diagnose_device", "lscqp_dump_instance", "lscqp_row_family_name",
                     "lscqp_prescreen_batch_device", "lscqp_set_prescreen", "lscqp_prescreen",
                     "lscqp_last_error", "lscqp_version"]
@@ -340,6 +342,43 @@ class WorldMap:
             pass
 
 
+class Worlds:
+    """lscqp_worlds: WorldMaps of one shape, world k for mission k (include/lscqp.h, "each mission over its own world").  The set borrows
+    its maps: this object keeps them alive."""
+
+    def __init__(self, maps):
+        self._w = None
+        self.maps = list(maps)
+        arr = (C.c_void_p * max(len(self.maps), 1))(*[None if m is None else m._h for m in self.maps])
+        h = C.c_void_p()
+        _call("lscqp_worlds_create", arr, len(self.maps), C.byref(h))
+        self._w = h
+
+    def __len__(self):
+        return len(self.maps)
+
+    def prepare(self, max_radius):
+        """lscqp_worlds_prepare: every member's free-space table with one margin."""
+        _call("lscqp_worlds_prepare", self._w, float(max_radius))
+
+    def info(self):
+        """(n_worlds, dims int32[3], key0 int32[3]) of the common shape."""
+        n, dims, key0 = C.c_int32(), np.zeros(3, np.int32), np.zeros(3, np.int32)
+        _call("lscqp_worlds_info", self._w, C.byref(n), dims, key0)
+        return int(n.value), dims, key0
+
+    def close(self):
+        if self._w:
+            lib().lscqp_worlds_destroy(self._w)
+            self._w = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 GRID_UNREACHABLE = 0x3FFFFFFF  # LSCQP_GRID_UNREACHABLE
 
 
@@ -401,6 +440,17 @@ class Grid:
         """Occupancy, uint8 (dims[1], dims[0]); mission=True: with the start and goal nodes of the last `fields` call cleared."""
         occ = np.zeros((int(self.dims[1]), int(self.dims[0])), np.uint8)
         _call("lscqp_grid_download_mission" if mission else "lscqp_grid_download", self._h, occ)
+        return occ
+
+    def set_worlds(self, worlds):
+        """lscqp_grid_set_worlds: a base occupancy per world of a Worlds set (mission k starts from base k); None: the one base again."""
+        _call("lscqp_grid_set_worlds", self._h, None if worlds is None else worlds._w)
+        self._worlds = worlds
+
+    def download_world(self, k):
+        """lscqp_grid_download_world: the base occupancy of world k, uint8 (dims[1], dims[0])."""
+        occ = np.zeros((int(self.dims[1]), int(self.dims[0])), np.uint8)
+        _call("lscqp_grid_download_world", self._h, int(k), occ)
         return occ
 
     def status(self):
@@ -636,6 +686,12 @@ class Plan:
         K, off = (0, None) if offsets is None else mission_offsets_arg(offsets)[:2]
         _call("lscqp_plan_set_missions", self._p, K, off)
 
+    def set_worlds(self, worlds):
+        """lscqp_plan_set_worlds: world k of a Worlds set for mission k of the partition (None: the plan's one map again).  Call it after
+        `set_missions` and before `reset`."""
+        _call("lscqp_plan_set_worlds", self._p, None if worlds is None else worlds._w)
+        self._worlds = worlds  # (the set, and through it its maps, stay alive with the plan)
+
     def set_waypoint_decision(self, which):
         """lscqp_plan_set_waypoint_decision: DECISION_ONE_WORKGROUP (default), DECISION_WIDE or DECISION_AUTO; waypoint_mode 1 only."""
         _call("lscqp_plan_set_waypoint_decision", self._p, int(which))
@@ -663,6 +719,7 @@ class Plan:
         if self._p:
             lib().lscqp_plan_destroy(self._p)
             self._p = None
+        self._worlds = None
 
     def __del__(self):
         try:
@@ -1169,6 +1226,12 @@ class Solver:
         """Corridor update of n agents on the device (SFC_INIT / SFC_FROM_HULL / SFC_FROM_POINT, see include/lscqp.h).  d_order: int32
         permutation (workgroup k builds agent d_order[k]'s corridor); d_cost: uint32[n], every agent's cost of this launch."""
         _call("lscqp_construct_sfc_device_ordered", self._h, world_map._h, int(mode), n, d_points, d_radius, d_sfc, d_status, d_order, d_cost, stream=stream)
+
+    def construct_sfc_worlds_device(self, worlds, mode, n, d_world_of, d_points, d_radius, d_sfc, d_status, stream=None, d_order=None, d_cost=None):
+        """lscqp_construct_sfc_worlds_device: construct_sfc_device in which agent a is tested against world d_world_of[a] (int32 (n,)) of a
+        Worlds set; every index must lie in [0, len(worlds))."""
+        _call("lscqp_construct_sfc_worlds_device", self._h, worlds._w, int(mode), n, d_world_of, d_points, d_radius, d_sfc, d_status, d_order, d_cost,
+              stream=stream)
 
     def validate_step_device(self, n, time_step, d_x, d_hdr, d_sfc, d_valid, d_state, z_2d=1.0, stream=None):
         _call("lscqp_validate_step_device", self._h, n, float(time_step), float(z_2d), d_x, d_hdr, d_sfc, d_valid, d_state, stream=stream)

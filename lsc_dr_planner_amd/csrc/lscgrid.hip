@@ -880,6 +880,9 @@ struct lscqp_grid_s {
     int32_t* d_status_k = nullptr;  // [missions]
     int32_t* d_tables_k = nullptr;  // [missions][2][nodes], all zero between launches
     std::vector<int64_t> fields_off;  // the partition of the last lscqp_grid_fields_missions_device: the one the copies were cleared for
+    // a base occupancy per world (lscqp_grid_set_worlds): mission k's copy starts from base k; 0 = the one base d_occ
+    int worlds = 0;
+    uint8_t* d_occ_w = nullptr;  // [worlds][nodes]
     // the wide form of the decision (lscqp_grid_reserve_wide)
     int64_t wide_reserved = 0;
     void* d_wide = nullptr;
@@ -898,6 +901,11 @@ int grid_hip_fail(hipError_t e, const char* what) {
     } while (0)
 
 constexpr int64_t kPerAgentInts = 9 + 2 * 5;  // cur, vnext, order, stack, label, blocker, keep, onnode, gsize + cand[5], cost[5]
+
+// what the one-mission entries answer on a grid with a base occupancy per world (lscqp_grid_set_worlds)
+const char* const kOneMissionOverWorlds =
+    "the grid has a base occupancy per world (lscqp_grid_set_worlds): the one-mission entries have no single base to read -- use the "
+    "_missions_ entries with one mission per world, or lscqp_grid_set_worlds(grid, NULL)";
 
 bool tables_fit_lds(const lscqp_grid_s* g) {
     return (size_t)2 * g->dims[0] * g->dims[1] * sizeof(int32_t) <= (size_t)lscgrid::kTableLdsBytes;
@@ -1007,7 +1015,7 @@ void lscqp_grid_destroy(lscqp_grid g) {
     int prev = -1;
     if (hipGetDevice(&prev) == hipSuccess && prev != g->device) (void)hipSetDevice(g->device);
     (void)hipDeviceSynchronize();
-    for (void* p : {(void*)g->d_occ, (void*)g->d_occ_mission, (void*)g->d_agent_scratch, (void*)g->d_tables, (void*)g->d_occ_k, (void*)g->d_status_k, (void*)g->d_tables_k, g->d_wide})
+    for (void* p : {(void*)g->d_occ, (void*)g->d_occ_mission, (void*)g->d_agent_scratch, (void*)g->d_tables, (void*)g->d_occ_k, (void*)g->d_status_k, (void*)g->d_tables_k, g->d_wide, (void*)g->d_occ_w})
         if (p) (void)hipFree(p);
     if (prev >= 0 && prev != g->device) (void)hipSetDevice(prev);
     delete g;
@@ -1062,6 +1070,7 @@ int lscqp_grid_fields_device(lscqp_grid g, int64_t n, const double* d_start_poin
                              void* stream) {
     if (!g || n < 0 || (n > 0 && (!d_start_points || !d_goal_points || !d_field || !d_init_d)))
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (g->worlds) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, kOneMissionOverWorlds);
     if (n == 0) return LSCQP_OK;
     hipStream_t st = (hipStream_t)stream;
     const int nodes = g->dims[0] * g->dims[1];
@@ -1082,6 +1091,7 @@ int lscqp_waypoints_device(lscqp_grid g, double communication_range, int32_t M, 
                                            "bad argument", communication_range, M, dim, d_plan);
         if (rc != LSCQP_OK) return rc;
     }
+    if (g->worlds) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, kOneMissionOverWorlds);
     if (n == 0) return LSCQP_OK;
     if (n > g->reserved) {  // (synchronises and allocates: a caller that captures the launch reserves beforehand)
         const int rc = lscqp_grid_reserve(g, n);
@@ -1134,6 +1144,7 @@ int lscqp_waypoints_wide_device(lscqp_grid g, double communication_range, int32_
                                            "bad argument", communication_range, M, dim, d_plan);
         if (rc != LSCQP_OK) return rc;
     }
+    if (g->worlds) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, kOneMissionOverWorlds);
     if (n == 0) return LSCQP_OK;
     if (n > g->wide_reserved || n > g->reserved) {  // (synchronises and allocates: a caller that captures the launch reserves beforehand)
         const int rc = lscqp_grid_reserve_wide(g, n);
@@ -1197,6 +1208,70 @@ int lscqp_grid_reserve_missions_(lscqp_grid g, int64_t n, int32_t n_missions) {
     return LSCQP_OK;
 }
 
+// updateGridMap once per world: [n_worlds][nodes] base occupancies by the kernel and the arithmetic of lscqp_grid_create.  Synchronous; the grid
+// keeps nothing of the maps.  NULL: back to the one base
+int lscqp_grid_set_worlds(lscqp_grid g, lscqp_worlds worlds) {
+    if (!g) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null grid");
+    if (const int rc = lscqp_need_device_()) return rc;
+    struct OnDevice {  // the grid's device made current while its bases are allocated, written and waited for
+        int prev = -1;
+        explicit OnDevice(int dev) {
+            if (hipGetDevice(&prev) != hipSuccess || prev == dev) prev = -1;
+            else (void)hipSetDevice(dev);
+        }
+        ~OnDevice() {
+            if (prev >= 0) (void)hipSetDevice(prev);
+        }
+    } on(g->device);
+    uint8_t* fresh = nullptr;
+    int K = 0;
+    if (worlds) {
+        K = lscqp_worlds_count_(worlds);
+        const int nodes = g->dims[0] * g->dims[1];
+        for (int k = 0; k < K; k++) {
+            double res = 0;
+            float wmin[3], wmax[3];
+            int key0[3], mdims[3], mdev = 0;
+            const int32_t* nearest = nullptr;
+            lscqp_map_raw_(lscqp_worlds_map_(worlds, k), &res, wmin, wmax, key0, mdims, &nearest, &mdev);
+            if (k == 0) {  // (the members agree in shape: the first speaks for all)
+                if (mdev != g->device) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_grid_set_worlds: the worlds live on another device than the grid");
+                const double wmin_d[3] = {wmin[0], wmin[1], wmin[2]}, wmax_d[3] = {wmax[0], wmax[1], wmax[2]};
+                double gmin[3];
+                int32_t dims[3];
+                const int rc = lscqp_grid_shape(wmin_d, wmax_d, g->v.res, 2, g->v.z_2d, gmin, dims);
+                if (rc != LSCQP_OK) return rc;
+                if (gmin[0] != g->gmin[0] || gmin[1] != g->gmin[1] || dims[0] != g->dims[0] || dims[1] != g->dims[1])
+                    return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_grid_set_worlds: the worlds' box gives another grid than this one (world box differs from the grid's map)");
+                GRID_HIP(hipMalloc((void**)&fresh, (size_t)K * nodes));
+            }
+            const lscgrid::MapRaw mraw{res, key0[0], key0[1], key0[2], mdims[0], mdims[1], mdims[2], nearest};
+            hipLaunchKernelGGL(lscgrid::occupancy_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, (hipStream_t)0, g->v, mraw, g->radius, fresh + (size_t)k * nodes);
+        }
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            (void)hipFree(fresh);
+            return grid_hip_fail(e, "lscqp_grid_set_worlds");
+        }
+    } else {
+        GRID_HIP(hipDeviceSynchronize());  // (a launch may still be reading the bases)
+    }
+    if (g->d_occ_w) (void)hipFree(g->d_occ_w);
+    g->d_occ_w = fresh;
+    g->worlds = K;
+    g->fields_off.clear();  // (the mission copies were made from other bases: lscqp_grid_fields_missions_device must come again)
+    return LSCQP_OK;
+}
+
+int lscqp_grid_download_world(lscqp_grid g, int32_t k, uint8_t* occ) {
+    if (!g || !occ) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    if (k < 0 || k >= g->worlds) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_grid_download_world: the grid has no such world (lscqp_grid_set_worlds)");
+    const size_t nodes = (size_t)g->dims[0] * g->dims[1];
+    GRID_HIP(hipMemcpy(occ, g->d_occ_w + (size_t)k * nodes, nodes, hipMemcpyDeviceToHost));
+    return LSCQP_OK;
+}
+
 int lscqp_grid_mission_status(lscqp_grid g, int32_t n_missions, int32_t* status_out) {
     if (!g || !status_out || n_missions < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
     if (n_missions > g->missions) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the grid has seen no partition of that many missions");
@@ -1212,6 +1287,9 @@ int lscqp_grid_fields_missions_device(lscqp_grid g, int64_t n, int32_t n_mission
         if (rc != LSCQP_OK) return rc;
     }
     if (!d_mission_offsets || !d_start_points || !d_goal_points || !d_field || !d_init_d) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (g->worlds && n_missions != g->worlds)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, ("lscqp_grid_fields_missions_device: the grid has " + std::to_string(g->worlds) + " worlds, the partition " +
+                                                             std::to_string(n_missions) + " missions: mission k flies over world k").c_str());
     if (n_missions > g->missions || n > g->reserved) {  // (synchronises and allocates)
         const int rc = lscqp_grid_reserve_missions_(g, n, n_missions);
         if (rc != LSCQP_OK) return rc;
@@ -1219,7 +1297,10 @@ int lscqp_grid_fields_missions_device(lscqp_grid g, int64_t n, int32_t n_mission
     hipStream_t st = (hipStream_t)stream;
     const int nodes = g->dims[0] * g->dims[1], K = n_missions;
     g->fields_off.assign(mission_offsets, mission_offsets + K + 1);
-    hipLaunchKernelGGL(lscgrid::spread_occupancy_kernel, dim3((unsigned)(((int64_t)nodes * K + 255) / 256)), dim3(256), 0, st, nodes, K, g->d_occ, g->d_occ_k);
+    if (g->worlds)  // mission k's copy starts from world k's base
+        GRID_HIP(hipMemcpyAsync(g->d_occ_k, g->d_occ_w, (size_t)nodes * K, hipMemcpyDeviceToDevice, st));
+    else
+        hipLaunchKernelGGL(lscgrid::spread_occupancy_kernel, dim3((unsigned)(((int64_t)nodes * K + 255) / 256)), dim3(256), 0, st, nodes, K, g->d_occ, g->d_occ_k);
     GRID_HIP(hipMemsetAsync(g->d_status_k, 0, (size_t)K * sizeof(int32_t), st));  // new missions: their status words start at 0
     hipLaunchKernelGGL(lscgrid::clear_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, d_start_points, d_goal_points, g->d_occ_k,
                        d_mission_offsets, K);

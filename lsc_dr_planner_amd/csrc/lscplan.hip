@@ -16,9 +16,12 @@
 // ten kernel launches per replan.  The waypoints of the grid planner / MAPF layer are either written into the plan's waypoint buffer by
 // the caller before each step (waypoint_mode 0) or decided at the head of the chain by lscqp_waypoints_device (waypoint_mode 1, lscgrid.hip):
 //   MultiSyncSimulator::decentralizedMAPP               -> lscqp_waypoints_device over the state, plans and goal points of the last replan
-// A plan with a mission partition (lscqp_plan_set_missions) flies many independent missions over one map in the same chain: the three
+// A plan with a mission partition (lscqp_plan_set_missions) flies many independent missions in the same chain, over its one map: the three
 // steps in which agents see each other -- the waypoint decision, the range filter, the safety figures -- run as their mission-aware twins,
 // every other step is per agent and does not know.
+// A plan whose missions have a world each (lscqp_plan_set_worlds: world k of a set of maps of one shape for mission k, as the reference's
+// evaluation sets pair them) swaps two things and adds no node: its corridor node is the worlds launch, every agent tested against the map
+// of its mission, and its grid starts each mission's occupancy from that world's base.
 // A plan with dynamic obstacles (lscqp_plan_set_obstacles) gains three nodes: the obstacles' motion (lscobstacle.hip) in front of `prepare`, their
 // rows (generateLSC's non-agent branch) behind the agents' rows -- they take the first row slots of every agent -- and the obstacle leg of the
 // safety figures behind the agents'.  ObstacleGenerator::update(t, 0) -> obstacle_advance_kernel, src/multi_sync_simulator.cpp:311.
@@ -234,6 +237,11 @@ struct lscqp_plan_s {
     int32_t *obs_ids = nullptr, *obs_clock = nullptr;  // ids: 0 .. n_dyn - 1 for every local agent
     lscqp_safety_obs* obs_safety = nullptr;
     bool obstacles_pending = false;  // the obstacles were set and lscqp_plan_reset has not come yet
+    // a world per mission (lscqp_plan_set_worlds): NULL = the one map, the chain as it always was.  Borrowed
+    lscqp_worlds worlds = nullptr;
+    int32_t* world_of = nullptr;  // [n_total]: the agent's mission
+    uint64_t worlds_gen = 0;      // the members' generation counters, summed, when the graph and the fields were derived
+    bool worlds_pending = false;  // the worlds changed and lscqp_plan_reset has not come yet
     bool wide() const { return decision == LSCQP_DECISION_WIDE || (decision == LSCQP_DECISION_AUTO && s.n_total >= LSCQP_DECISION_AUTO_MIN_AGENTS); }
 };
 
@@ -298,6 +306,7 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     if (p->rec_on && (p->record_pending || !p->rec))
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: lscqp_plan_reset must come before the next step");
     if (p->obstacles_pending) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacles: lscqp_plan_reset must come before the next step");
+    if (p->worlds_pending) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_worlds: lscqp_plan_reset must come before the next step");
     const int32_t n_dyn = p->n_dyn, n_nbr = s.n_obs - n_dyn;  // row slots [0, n_dyn): the obstacles, [n_dyn, n_obs): the in-range agents
     // decentralizedMAPP precedes the planning loop (src/multi_sync_simulator.cpp:101-120): the waypoints of this replan, from the plans as the
     // last replan left them (AgentManager::getTraj is desired_traj, un-shifted)
@@ -329,8 +338,12 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
             PLAN_TRY(lscqp_order_by_cost_device(s.n_agents, p->sfc_cost, p->sfc_order, stream));
             sfc_order = p->sfc_order;
         }
-        PLAN_TRY(lscqp_construct_sfc_device_ordered(h, p->map, first_replan ? LSCQP_SFC_INIT : p->d.sfc_mode, s.n_agents, p->points,
-                                                    p->radius + s.first_agent, sfc, sfc_status, sfc_order, p->sfc_cost, stream));
+        if (p->worlds)  // every agent in the world of its mission (a partition has every agent local: first_agent = 0)
+            PLAN_TRY(lscqp_construct_sfc_worlds_device(h, p->worlds, first_replan ? LSCQP_SFC_INIT : p->d.sfc_mode, s.n_agents, p->world_of, p->points,
+                                                       p->radius + s.first_agent, sfc, sfc_status, sfc_order, p->sfc_cost, stream));
+        else
+            PLAN_TRY(lscqp_construct_sfc_device_ordered(h, p->map, first_replan ? LSCQP_SFC_INIT : p->d.sfc_mode, s.n_agents, p->points,
+                                                        p->radius + s.first_agent, sfc, sfc_status, sfc_order, p->sfc_cost, stream));
     }
     if (K > 1)
         PLAN_TRY(lscqp_select_neighbours_missions_device(h, s.n_total, K, p->moff.data(), p->d_moff, n_nbr, lscqp_class_desc_of_(h)->communication_range, p->pos,
@@ -428,6 +441,13 @@ int make_grid(lscqp_plan_s* p, double resolution) {
     gd.resolution = resolution, gd.radius = p->grid_radius, gd.z_2d = p->d.z_2d, gd.world_dimension = p->s.dim;
     lscqp_grid gnew = nullptr;
     PLAN_TRY(lscqp_grid_create(p->map, &gd, &gnew));
+    if (p->worlds) {  // (a new grid of a plan with worlds gets them again)
+        const int rcw = lscqp_grid_set_worlds(gnew, p->worlds);
+        if (rcw != LSCQP_OK) {
+            lscqp_grid_destroy(gnew);
+            return rcw;
+        }
+    }
     double gmin[3];
     int32_t dims[3];
     lscqp_grid_info(gnew, gmin, dims);
@@ -481,8 +501,10 @@ int make_record(lscqp_plan_s* p) {
 // compare the generation counters before every step, drop the graph and re-derive the clone when they moved.
 int refresh(lscqp_plan_s* p) {
     const uint64_t hg = lscqp_handle_generation_(p->h), mg = p->map ? lscqp_map_generation_(p->map) : 0;
-    if (hg == p->h_gen && mg == p->map_gen) return LSCQP_OK;
+    const uint64_t wg = p->worlds ? lscqp_worlds_generation_(p->worlds) : 0;  // (every member map of a plan with worlds)
+    if (hg == p->h_gen && mg == p->map_gen && wg == p->worlds_gen) return LSCQP_OK;
     drop_graph(p);
+    if (p->worlds) PLAN_TRY(lscqp_worlds_refresh_(p->worlds));  // (the set's table follows its members before anything is enqueued)
     if (hg != p->h_gen) {
         // the buffers and the launch shapes of prepare / commit were sized at lscqp_plan_create: an update that changes the SHAPE of the
         // class (segments, dimension, corridor rows on / off, row format, a kernel capacity below the plan's neighbour slots) cannot be
@@ -518,7 +540,7 @@ int refresh(lscqp_plan_s* p) {
             if (rc != LSCQP_OK) return rc;
         }
     }
-    if (mg != p->map_gen && p->grid && p->fields_valid) {  // the map moved under the mission: its grid and fields are made again
+    if ((mg != p->map_gen || wg != p->worlds_gen) && p->grid && p->fields_valid) {  // the map moved under the mission: its grid and fields are made again
         const int rc = make_grid(p, p->grid_resolution);
         if (rc != LSCQP_OK) return rc;
         const int rc2 = make_fields(p);
@@ -526,6 +548,23 @@ int refresh(lscqp_plan_s* p) {
     }
     p->h_gen = hg;
     p->map_gen = mg;
+    p->worlds_gen = wg;
+    return LSCQP_OK;
+}
+
+// the per-agent world index of a plan with worlds: the agent's mission in the partition `off` ([K + 1]); a fresh device array
+int make_world_of(int64_t n_total, const int64_t* off, int K, int32_t** out) {
+    std::vector<int32_t> host((size_t)n_total);
+    for (int k = 0; k < K; k++)
+        for (int64_t a = off[k]; a < off[k + 1]; a++) host[(size_t)a] = k;
+    int32_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, host.size() * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(d, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (d) (void)hipFree(d);
+        return hip_fail(e, "world index of the agents");
+    }
+    *out = d;
     return LSCQP_OK;
 }
 
@@ -694,6 +733,7 @@ void lscqp_plan_destroy(lscqp_plan p) {
     if (p->field) (void)hipFree(p->field);
     if (p->rec) lscqp_record_destroy(p->rec);
     if (p->d_moff) (void)hipFree(p->d_moff);
+    if (p->world_of) (void)hipFree(p->world_of);
     free_obstacles(p);
     if (p->own_hq) lscqp_destroy(p->hq);
     delete p;
@@ -740,6 +780,7 @@ int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* 
     if (p->n_dyn > 0) PLAN_TRY(reset_obstacles(p));
     p->obstacles_pending = false;
     p->missions_pending = false;
+    p->worlds_pending = false;
     p->first = true;
     p->steps = 0;
     return LSCQP_OK;
@@ -830,6 +871,10 @@ lscqp_grid lscqp_plan_grid(lscqp_plan p) { return p ? p->grid : nullptr; }
 int lscqp_plan_set_missions(lscqp_plan p, int32_t n_missions, const int64_t* mission_offsets) {
     if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
     const bool single = n_missions <= 1 || !mission_offsets;
+    if (p->worlds && (single ? 1 : n_missions) != lscqp_worlds_count_(p->worlds))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
+                                ("lscqp_plan_set_missions: the plan has " + std::to_string(lscqp_worlds_count_(p->worlds)) +
+                                 " worlds (lscqp_plan_set_worlds), one per mission: another mission count needs other worlds, or none, first").c_str());
     if (!single) {
         if (p->s.n_agents != p->s.n_total)
             return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "a mission partition needs every agent on this device (n_agents == n_total): a sharded plan flies one mission");
@@ -844,10 +889,17 @@ int lscqp_plan_set_missions(lscqp_plan p, int32_t n_missions, const int64_t* mis
         int64_t* d = nullptr;
         e = hipMalloc((void**)&d, (size_t)(n_missions + 1) * sizeof(int64_t));
         if (e == hipSuccess) e = hipMemcpy(d, mission_offsets, (size_t)(n_missions + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
-        const int rc = e != hipSuccess ? hip_fail(e, "lscqp_plan_set_missions") : (p->grid ? lscqp_grid_reserve_missions_(p->grid, p->s.n_total, n_missions) : LSCQP_OK);
+        int rc = e != hipSuccess ? hip_fail(e, "lscqp_plan_set_missions") : (p->grid ? lscqp_grid_reserve_missions_(p->grid, p->s.n_total, n_missions) : LSCQP_OK);
+        // worlds are set (the count is theirs): the agents' world index follows the NEW offsets -- an agent that changes mission changes world
+        int32_t* wof = nullptr;
+        if (rc == LSCQP_OK && p->worlds) rc = make_world_of(p->s.n_total, mission_offsets, n_missions, &wof);
         if (rc != LSCQP_OK) {
             if (d) (void)hipFree(d);
             return rc;
+        }
+        if (wof) {
+            (void)hipFree(p->world_of);
+            p->world_of = wof;
         }
         if (p->d_moff) (void)hipFree(p->d_moff);
         p->d_moff = d;
@@ -865,6 +917,61 @@ int lscqp_plan_set_missions(lscqp_plan p, int32_t n_missions, const int64_t* mis
         p->rec = nullptr;
     }
     p->record_pending = p->rec_on;
+    return LSCQP_OK;
+}
+
+int lscqp_plan_set_worlds(lscqp_plan p, lscqp_worlds worlds) {
+    if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
+    const lscplan::Shape& s = p->s;
+    if (worlds) {
+        const int K = lscqp_worlds_count_(worlds);
+        if (p->moff.empty())
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_worlds: the plan has no mission partition (lscqp_plan_set_missions first): world k belongs to mission k");
+        if (K != p->n_missions())
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, ("lscqp_plan_set_worlds: " + std::to_string(K) + " worlds for " + std::to_string(p->n_missions()) +
+                                                                 " missions: one world per mission required").c_str());
+        if (!p->map)
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_worlds: the plan's class has no corridors (use_sfc = 0) and its grid no map: nothing in its chain reads a world");
+        if (const char* f = lscqp_worlds_shape_difference_(worlds, p->map))
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
+                                    (std::string("lscqp_plan_set_worlds: the worlds differ from the map the plan was created with in ") + f).c_str());
+    }
+    DeviceGuard g(p->device);
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_worlds");
+    int32_t* wof = nullptr;
+    if (worlds) {  // (everything that can fail comes before the plan changes)
+        const size_t nt = (size_t)s.n_total;
+        std::vector<double> r(nt);
+        e = hipMemcpy(r.data(), p->radius, nt * sizeof(double), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_worlds");
+        double rmax = 0;
+        for (const double v : r) rmax = v > rmax ? v : rmax;
+        PLAN_TRY(make_world_of(s.n_total, p->moff.data(), p->n_missions(), &wof));
+        int rc = p->grid ? lscqp_grid_set_worlds(p->grid, worlds) : LSCQP_OK;
+        // The free-space tables for the agents of this plan, one margin for all worlds -- LAST of what can fail, because it is the one step
+        // that reaches beyond the plan: it may rebuild the members' tables, which moves their generation counters (include/lscqp.h).  A
+        // failure behind the grid's change puts the grid back
+        if (rc == LSCQP_OK && rmax > 0) {
+            rc = lscqp_worlds_prepare(worlds, rmax);
+            if (rc == LSCQP_ERR_UNSUPPORTED) rc = LSCQP_OK;  // (maps too large for the table: the corridors work without it)
+            if (rc != LSCQP_OK && p->grid) (void)lscqp_grid_set_worlds(p->grid, p->worlds);
+        }
+        if (rc != LSCQP_OK) {
+            (void)hipFree(wof);
+            return rc;
+        }
+    } else if (p->grid) {
+        PLAN_TRY(lscqp_grid_set_worlds(p->grid, nullptr));
+    }
+    drop_graph(p);  // (a captured chain holds the other corridor node)
+    if (p->world_of) (void)hipFree(p->world_of);
+    p->world_of = wof;
+    p->worlds = worlds;
+    p->worlds_gen = worlds ? lscqp_worlds_generation_(worlds) : 0;
+    if (p->map) p->map_gen = lscqp_map_generation_(p->map);  // (the plan's own map may be a member just prepared: nothing derived from it is left)
+    p->fields_valid = false;
+    p->worlds_pending = true;
     return LSCQP_OK;
 }
 

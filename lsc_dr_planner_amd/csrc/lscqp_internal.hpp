@@ -113,7 +113,17 @@ uint64_t lscqp_map_generation_(lscqp_map mp);
 int lscqp_map_raw_(lscqp_map mp, double* res, float* world_min, float* world_max, int* key0, int* dims, const int32_t** d_nearest, int* device);
 hipError_t lscsfc_launch_throughput_(const void* view, int mode, int M, int64_t n, const double* d_points, const double* d_radius,
                                      lscqp_box* d_sfc, int32_t* d_status_out, void* stream);  // lscsfc_tp.hip
+hipError_t lscsfc_launch_throughput_worlds_(const void* view, int mode, int M, int64_t n, const double* d_points, const double* d_radius,
+                                            lscqp_box* d_sfc, int32_t* d_status_out, const void* d_table, const int32_t* d_world_of, void* stream);
 int lscsfc_throughput_max_cells_(void);
+// (library-internal: lscgrid.hip, lscplan.hip) a set of worlds: its members, the sum of their generation counters (it only rises), its
+// table rewritten if a member was prepared behind its back (waits for the device), and the first field in which the set's shape or device
+// differs from a map's (NULL: none)
+int lscqp_worlds_count_(lscqp_worlds w);
+lscqp_map lscqp_worlds_map_(lscqp_worlds w, int k);
+uint64_t lscqp_worlds_generation_(lscqp_worlds w);
+int lscqp_worlds_refresh_(lscqp_worlds w);
+const char* lscqp_worlds_shape_difference_(lscqp_worlds w, lscqp_map mp);
 
 // ---- lscgrid.hip
 // (library-internal, also lscplan.hip) work arrays for n agents in n_missions missions; grows on demand, which synchronises and allocates

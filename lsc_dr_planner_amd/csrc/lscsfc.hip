@@ -86,6 +86,27 @@ struct MapView {
     __host__ __device__ __forceinline__ int dims(int k) const { return k == 0 ? dims0 : (k == 1 ? dims1 : dims2); }
 };
 
+// A set of maps of one shape (lscqp_worlds): what differs between its members is where the nearest-cell field and the free-space table
+// lie.  One row of the set's device table per world; sat is NULL in EVERY row unless all members have a table of one margin (the view
+// carries the margin by value).
+struct WorldPtrs {
+    const int32_t* nearest;
+    const int32_t* sat;
+};
+// ... and the row as the worlds form of the kernel holds it.  Two things the compiler has to be told.  An address read from memory is a
+// generic one to it, and every map read behind it a flat load: these are typed as the global addresses they are.  And they are NOT written
+// into the kernel's by-value view: a view nobody writes to is re-read from the kernel's argument segment wherever registers are short,
+// one that was written to is copied once, held and spilled (measured: +27 us on a 250-agent launch, profiles/r25_worlds.txt).  So the
+// functions that read the map take the view AND the row, and which of the two they read is decided at compile time (WORLDS): the one-map
+// instantiation reads its view exactly as before.
+typedef const __attribute__((address_space(1))) int32_t* global_words;
+struct GlobalPtrs {
+    global_words nearest;
+    global_words sat;
+};
+template <bool WORLDS> __device__ __forceinline__ auto sat_of(const MapView& mp, const GlobalPtrs& wp) { if constexpr (WORLDS) return wp.sat; else return mp.sat; }
+template <bool WORLDS> __device__ __forceinline__ auto nearest_of(const MapView& mp, const GlobalPtrs& wp) { if constexpr (WORLDS) return wp.nearest; else return mp.nearest; }
+
 __host__ __device__ inline int key_of(double coord, double res) { return (int)floor((1.0 / res) * coord); }  // coordToKey
 
 // ---- map construction ----------------------------------------------------------------------------------------------
@@ -243,11 +264,12 @@ struct BoxF {
 };
 
 // true: none of the map cells [x0, x1] x [y0, y1] x [z0, z1] (inside the map) can make a test fail (lscqp_map_prepare's table)
-__device__ __forceinline__ bool cells_free(const MapView& mp, int x0, int x1, int y0, int y1, int z0, int z1) {
+template <bool WORLDS>
+__device__ __forceinline__ bool cells_free(const MapView& mp, const GlobalPtrs& wp, int x0, int x1, int y0, int y1, int z0, int z1) {
     // (32-bit index arithmetic: lscqp_map_prepare refuses maps of more than 2^31 - 1 cells)
     const uint32_t sy = (uint32_t)mp.dims(0), sz = (uint32_t)mp.dims(0) * (uint32_t)mp.dims(1);
     auto at = [&](int x, int y, int z) -> int64_t {  // prefix sum up to (x, y, z) inclusive; -1 on any axis: empty
-        return (x < 0 || y < 0 || z < 0) ? 0 : (int64_t)mp.sat[(uint32_t)x + (uint32_t)y * sy + (uint32_t)z * sz];
+        return (x < 0 || y < 0 || z < 0) ? 0 : (int64_t)sat_of<WORLDS>(mp, wp)[(uint32_t)x + (uint32_t)y * sy + (uint32_t)z * sz];
     };
     const int xa = x0 - 1, ya = y0 - 1, za = z0 - 1;
     const int64_t cnt = at(x1, y1, z1) - at(xa, y1, z1) - at(x1, ya, z1) - at(x1, y1, za) + at(xa, ya, z1) + at(xa, y1, za) + at(x1, ya, za) - at(xa, ya, za);
@@ -282,8 +304,9 @@ __device__ __forceinline__ int cell_range(const int* vtab, int tab, int n, int& 
 }
 
 // true: no sample point of the box (n[k] points from lo[k] in steps of res) can be within margin of an obstacle -- see lscqp_map_prepare
-__device__ __forceinline__ bool surely_free(const MapView& mp, double margin, float lo0, float lo1, float lo2, int n0, int n1, int n2) {
-    if (mp.sat == nullptr || !(margin <= mp.sat_margin)) return false;
+template <bool WORLDS>
+__device__ __forceinline__ bool surely_free(const MapView& mp, const GlobalPtrs& wp, double margin, float lo0, float lo1, float lo2, int n0, int n1, int n2) {
+    if (sat_of<WORLDS>(mp, wp) == nullptr || !(margin <= mp.sat_margin)) return false;
     const double res = mp.res;
     int a[3], b[3];
     const float lo[3] = {lo0, lo1, lo2};
@@ -315,18 +338,19 @@ __device__ __forceinline__ bool surely_free(const MapView& mp, double margin, fl
         inside = inside && a[k] >= 0 && b[k] < mp.dims(k) && a[k] <= b[k];
     }
     if (!inside) return false;  // (a sample outside the distance map is measured against the origin cell: the exact path handles it)
-    return cells_free(mp, a[0], b[0], a[1], b[1], a[2], b[2]);
+    return cells_free<WORLDS>(mp, wp, a[0], b[0], a[1], b[1], a[2], b[2]);
 }
 
 // isObstacleInSFC (:777-808): the block's lanes take the sample points of the box in turn and vote
-__device__ bool obstacle_in(const MapView& mp, const BoxF& b, double margin) {
+template <bool WORLDS>
+__device__ bool obstacle_in(const MapView& mp, const GlobalPtrs& wp, const BoxF& b, double margin) {
     const double res = mp.res;
     const float delta = (float)(0.5 * res);
     int n[3];
     for (int k = 0; k < 3; k++) n[k] = (int)floor(((double)(b.hi[k] - b.lo[k]) + 1e-5) / res) + 1;
     // an inverted box (a hull clipped to a previous box it does not touch) has no sample points
     const int64_t total = (n[0] <= 0 || n[1] <= 0 || n[2] <= 0) ? 0 : (int64_t)n[0] * n[1] * n[2];
-    if (total > 0 && surely_free(mp, margin, b.lo[0], b.lo[1], b.lo[2], n[0], n[1], n[2])) return false;  // (block-uniform)
+    if (total > 0 && surely_free<WORLDS>(mp, wp, margin, b.lo[0], b.lo[1], b.lo[2], n[0], n[1], n[2])) return false;  // (block-uniform)
     const int lane = threadIdx.x;
     // kU chunks of 64 points per vote: the kU nearest-cell loads of a lane are independent and in flight together, which is
     // what bounds a large slab (the loop is a chain of dependent HBM / L2 reads otherwise)
@@ -359,7 +383,7 @@ __device__ bool obstacle_in(const MapView& mp, const BoxF& b, double margin) {
                 v[u][k] = key_of((double)p[u][k], res) - mp.key0(k);       // worldToMap
                 inside = inside && v[u][k] >= 0 && v[u][k] < mp.dims(k);
             }
-            code[u] = inside ? mp.nearest[((int64_t)v[u][2] * mp.dims(1) + v[u][1]) * mp.dims(0) + v[u][0]] : 0;
+            code[u] = inside ? nearest_of<WORLDS>(mp, wp)[((int64_t)v[u][2] * mp.dims(1) + v[u][1]) * mp.dims(0) + v[u][0]] : 0;
         }
         bool hit = false;
 #pragma unroll
@@ -554,7 +578,8 @@ __device__ __forceinline__ float axis_dist(const Ahead& A, int k, bool have, int
 }
 
 // tests the recorded boxes (slots 0 .. A.nsamp-1); returns the test index of the first one holding an obstacle, kAhead if none
-__device__ int obstacle_in_batch(const MapView& mp, Ahead& A, double margin) {
+template <bool WORLDS>
+__device__ int obstacle_in_batch(const MapView& mp, const GlobalPtrs& wp, Ahead& A, double margin) {
     const int J = A.nsamp;
     const double res = mp.res;
     const float delta = (float)(0.5 * res);
@@ -566,14 +591,14 @@ __device__ int obstacle_in_batch(const MapView& mp, Ahead& A, double margin) {
         const int key0 = mp.key0(k), dimk = mp.dims(k);
         const double lo = (double)A.lo[j][k];
         bool any_far = false;  // (the whole box far from the origin on some axis: its samples outside the map are harmless, see surely_free)
-        if (mp.sat != nullptr)
+        if (sat_of<WORLDS>(mp, wp) != nullptr)
             for (int m = 0; m < 3; m++)
                 any_far = any_far || (A.n[j][m] > 0 && range_far_from_origin(mp, A.lo[j][m], (float)((double)A.lo[j][m] + (double)(A.n[j][m] - 1) * res)));
         for (int it = lane & 63; it < n; it += 64) {
             const float p = (float)(lo + (double)it * res);
             const int v = key_of((double)p, res) - key0;
             A.ptab[o + it] = p;
-            A.vtab[o + it] = (v >= 0 && v < dimk) ? v : ((mp.sat != nullptr && (any_far || far_from_origin(mp, p))) ? kBeyondFree : -1);
+            A.vtab[o + it] = (v >= 0 && v < dimk) ? v : ((sat_of<WORLDS>(mp, wp) != nullptr && (any_far || far_from_origin(mp, p))) ? kBeyondFree : -1);
         }
     }
     __syncthreads();
@@ -594,7 +619,7 @@ __device__ int obstacle_in_batch(const MapView& mp, Ahead& A, double margin) {
     const int all_chunks = A.first[J];
     bool listed = false, from_back = false;
     int n_rounds = all_chunks;
-    if (mp.sat != nullptr && margin <= mp.sat_margin && all_chunks >= 64 && all_chunks <= kTodo) {
+    if (sat_of<WORLDS>(mp, wp) != nullptr && margin <= mp.sat_margin && all_chunks >= 64 && all_chunks <= kTodo) {
         if (lane == 0) A.ntodo = 0, A.ntodo2 = 0;
         int zsh = 0;  // segments per column, rounded up to a power of two (uniform: J <= kSamp slots)
         for (int t = 0; t < J; t++) {
@@ -633,7 +658,7 @@ __device__ int obstacle_in_batch(const MapView& mp, Ahead& A, double margin) {
                 const int y0 = ca == 1 ? va0 : (cb == 1 ? vb0 : vl0), y1 = ca == 1 ? va1 : (cb == 1 ? vb1 : vl1);
                 const int z0 = ca == 2 ? va0 : (cb == 2 ? vb0 : vl0), z1 = ca == 2 ? va1 : (cb == 2 ? vb1 : vl1);
                 const long long ti1_ = clock64();
-                free_ = cells_free(mp, x0, x1, y0, y1, z0, z1);
+                free_ = cells_free<WORLDS>(mp, wp, x0, x1, y0, y1, z0, z1);
                 SFC_DBG(27, ti1_ - ti0_); SFC_DBG(28, clock64() - ti1_ + (free_ ? 0 : 0)); SFC_DBG(29, 1);
             }
             return free_;
@@ -691,7 +716,7 @@ __device__ int obstacle_in_batch(const MapView& mp, Ahead& A, double margin) {
         if (ia < 0) ib--, ia += na;
         if (ia >= na) ib++, ia -= na;
         const int el = __builtin_amdgcn_readfirstlane(A.tab[j][la]);
-        if (!listed && nl >= 8 && mp.sat != nullptr && margin <= mp.sat_margin) {
+        if (!listed && nl >= 8 && sat_of<WORLDS>(mp, wp) != nullptr && margin <= mp.sat_margin) {
             // the 64 columns of this chunk with a long thin axis (a slab of a large 3-D box: 64 x nl samples; for the one-sample columns
             // of a layer the table's eight reads cost more than the sample's one -- measured): if the cells they run
             // through are provably free there is nothing to evaluate.  Wave-uniform: the chunk's columns span the rows ib0 .. ib1 of
@@ -710,7 +735,7 @@ __device__ int obstacle_in_batch(const MapView& mp, Ahead& A, double margin) {
                 const int x0 = ca == 0 ? va0 : (cb == 0 ? vb0 : vl0), x1 = ca == 0 ? va1 : (cb == 0 ? vb1 : vl1);
                 const int y0 = ca == 1 ? va0 : (cb == 1 ? vb0 : vl0), y1 = ca == 1 ? va1 : (cb == 1 ? vb1 : vl1);
                 const int z0 = ca == 2 ? va0 : (cb == 2 ? vb0 : vl0), z1 = ca == 2 ? va1 : (cb == 2 ? vb1 : vl1);
-                if (__builtin_amdgcn_readfirstlane((int)cells_free(mp, x0, x1, y0, y1, z0, z1))) continue;
+                if (__builtin_amdgcn_readfirstlane((int)cells_free<WORLDS>(mp, wp, x0, x1, y0, y1, z0, z1))) continue;
             }
         }
         const int ea = A.tab[j][ca] + ia, eb = A.tab[j][cb] + ib;
@@ -731,7 +756,7 @@ __device__ int obstacle_in_batch(const MapView& mp, Ahead& A, double margin) {
                 const int zi = (z0 + z < nl) ? z0 + z : nl - 1;  // (the tail repeats the last point: same verdict)
                 vl[z] = A.vtab[el + zi];
                 pl[z] = A.ptab[el + zi];
-                code[z] = (inab && vl[z] >= 0) ? mp.nearest[base_ab + (int64_t)vl[z] * sl] : 0;
+                code[z] = (inab && vl[z] >= 0) ? nearest_of<WORLDS>(mp, wp)[base_ab + (int64_t)vl[z] * sl] : 0;
             }
 #pragma unroll
             for (int z = 0; z < kZ; z++) {
@@ -766,9 +791,10 @@ __device__ int obstacle_in_batch(const MapView& mp, Ahead& A, double margin) {
 }
 
 // expandSFC (:819-881 without goal, :883-946 with it)
-__device__ __forceinline__ bool expand_sfc(const MapView& mp, Ahead& A, bool tables, const BoxF& initial, bool use_goal, const float* goal, double margin,
+template <bool WORLDS>
+__device__ __forceinline__ bool expand_sfc(const MapView& mp, const GlobalPtrs& wp, Ahead& A, bool tables, const BoxF& initial, bool use_goal, const float* goal, double margin,
                                            BoxF& out) {
-    if (obstacle_in(mp, initial, margin)) return false;
+    if (obstacle_in<WORLDS>(mp, wp, initial, margin)) return false;
     // the candidate directions, one per nibble (an indexed register array would live in scratch memory: one memory round trip per
     // expansion step)
     unsigned cands = 0x543210u;
@@ -1014,7 +1040,7 @@ __device__ __forceinline__ bool expand_sfc(const MapView& mp, Ahead& A, bool tab
             bool empty = n[0] <= 0 || n[1] <= 0 || n[2] <= 0;
             // a box the boundary fails is not looked at (the reference's test is `obstacle || !boundary`); a box the map's summary
             // proves free passes like an empty one: no table entries, no columns (lscqp_map_prepare)
-            empty = empty || !inb || (mine && surely_free(mp, margin, u.lo[0], u.lo[1], u.lo[2], n[0], n[1], n[2]));
+            empty = empty || !inb || (mine && surely_free<WORLDS>(mp, wp, margin, u.lo[0], u.lo[1], u.lo[2], n[0], n[1], n[2]));
             SFC_DBG(24, clock64() - tg0_);
             // thin axis: the columns run along it (ties: the later axis, so that x stays a column axis)
             la = (n[2] <= n[1] && n[2] <= n[0]) ? 2 : (n[1] <= n[0] ? 1 : 0);
@@ -1120,12 +1146,12 @@ __device__ __forceinline__ bool expand_sfc(const MapView& mp, Ahead& A, bool tab
             if (!in_boundary(mp, upd, 0)) {
                 jfail = 0;
             } else {
-                jfail = obstacle_in(mp, upd, margin) ? 0 : kAhead;
+                jfail = obstacle_in<WORLDS>(mp, wp, upd, margin) ? 0 : kAhead;
             }
             J = 1;
             jstop = kAhead;
         } else {
-            jfail = (J > 0 && A.nsamp > 0) ? obstacle_in_batch(mp, A, margin) : kAhead;
+            jfail = (J > 0 && A.nsamp > 0) ? obstacle_in_batch<WORLDS>(mp, wp, A, margin) : kAhead;
         }
         SFC_DBG(4, clock64() - t0_);
         const int jf = jfail < jstop ? jfail : jstop;  // the test of this batch that ends it by failing, kAhead if none does
@@ -1193,11 +1219,24 @@ __device__ void clip_to_prev(const BoxF& prev, BoxF& ini, double res) {  // :677
 #else
 #define LSCSFC_KERNEL_ATTR
 #endif
+// W...: nothing -- the kernel over one map, with the arguments it always had -- or (const WorldPtrs* worlds, const int32_t* world_of): the
+// agent is tested against world world_of[agent].  Its two pointers are fetched once, at entry -- the agent is uniform for the workgroup, so
+// these are two scalar loads -- into a row of their own (GlobalPtrs above) and from then on the kernel runs the statements it runs over one map.  The index belongs to the AGENT: with
+// a work order, workgroup k builds agent order[k] in world world_of[order[k]].  Not tested: 0 <= index < worlds.
+template <class... W>
 __global__ __launch_bounds__(kSfcThreads) LSCSFC_KERNEL_ATTR void construct_sfc_kernel(MapView mp, int mode, int M, int64_t n, const double* __restrict__ pts,
                                                            const double* __restrict__ radius, lscqp_box* __restrict__ sfc,
-                                                           int32_t* __restrict__ status) {
+                                                           int32_t* __restrict__ status, W... world_args) {
     if ((int64_t)blockIdx.x >= n) return;
     const int64_t a = mp.order ? (int64_t)mp.order[blockIdx.x] : (int64_t)blockIdx.x;
+    constexpr bool kWorlds = sizeof...(W) == 2;
+    GlobalPtrs wp{nullptr, nullptr};
+    if constexpr (kWorlds) {
+        const auto pick = [&](const WorldPtrs* worlds, const int32_t* world_of) { return worlds[world_of[a]]; };
+        const WorldPtrs w = pick(world_args...);
+        wp.nearest = (global_words)w.nearest;
+        wp.sat = (global_words)w.sat;
+    }
     const long long t_begin_ = clock64();
     const double res = mp.res;
     const double margin = radius[a];
@@ -1249,7 +1288,7 @@ __global__ __launch_bounds__(kSfcThreads) LSCSFC_KERNEL_ATTR void construct_sfc_
             }
             if (mode == LSCQP_SFC_FROM_POINT) clip_to_prev(prev, ini, res);
         }
-        ok = expand_sfc(mp, A, tables, ini, mode == LSCQP_SFC_FROM_POINT, P[1], margin, out);
+        ok = expand_sfc<kWorlds>(mp, wp, A, tables, ini, mode == LSCQP_SFC_FROM_POINT, P[1], margin, out);
         if (ok && mode == LSCQP_SFC_FROM_HULL && att == 0)  // isSuperSetOfConvexHull :135-150
             for (int k = 0; k < 3; k++)
                 ok = ok && !((double)hull_mn[k] < (double)out.lo[k] - 1e-5 || (double)hull_mx[k] > (double)out.hi[k] + 1e-5);
@@ -1308,12 +1347,163 @@ __global__ __launch_bounds__(kSfcThreads) LSCSFC_KERNEL_ATTR void construct_sfc_
 // the registers capped so that two workgroups share a CU; only its launcher is exported, the map and host entry points live in lscsfc.hip.
 extern "C" hipError_t lscsfc_launch_throughput_(const void* view, int mode, int M, int64_t n, const double* d_points, const double* d_radius,
                                                 lscqp_box* d_sfc, int32_t* d_status_out, void* stream) {
-    hipLaunchKernelGGL(lscsfc::construct_sfc_kernel, dim3((unsigned)n), dim3(lscsfc::kSfcThreads), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(lscsfc::construct_sfc_kernel<>, dim3((unsigned)n), dim3(lscsfc::kSfcThreads), 0, (hipStream_t)stream,
                        *reinterpret_cast<const lscsfc::MapView*>(view), mode, M, n, d_points, d_radius, d_sfc, d_status_out);
     return hipGetLastError();
 }
+extern "C" hipError_t lscsfc_launch_throughput_worlds_(const void* view, int mode, int M, int64_t n, const double* d_points, const double* d_radius,
+                                                       lscqp_box* d_sfc, int32_t* d_status_out, const void* d_table, const int32_t* d_world_of, void* stream) {
+    hipLaunchKernelGGL((lscsfc::construct_sfc_kernel<const lscsfc::WorldPtrs*, const int32_t*>), dim3((unsigned)n), dim3(lscsfc::kSfcThreads), 0, (hipStream_t)stream,
+                       *reinterpret_cast<const lscsfc::MapView*>(view), mode, M, n, d_points, d_radius, d_sfc, d_status_out,
+                       reinterpret_cast<const lscsfc::WorldPtrs*>(d_table), d_world_of);
+    return hipGetLastError();
+}
 #else
+// lscqp_worlds: K maps of one shape.  The set borrows its maps and owns one device table, a WorldPtrs row per world.
+struct lscqp_worlds_s {
+    std::vector<lscqp_map> maps;
+    std::vector<uint64_t> gens;  // the members' generation counters when the table was last written
+    void* d_table = nullptr;     // lscsfc::WorldPtrs[maps.size()]
+    double sat_margin = 0;       // the one margin of all members' free-space tables; 0: the launch uses no table
+    int device = 0;
+};
+
+namespace {
+
+// the set's device made current for a scope (its table and its members' tables are allocated, written and waited for there)
+struct WorldsDevice {
+    int prev = -1;
+    explicit WorldsDevice(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess || prev == dev) prev = -1;
+        else (void)hipSetDevice(dev);
+    }
+    ~WorldsDevice() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+bool worlds_stale(const lscqp_worlds_s* w) {
+    for (size_t k = 0; k < w->maps.size(); k++)
+        if (w->maps[k]->generation != w->gens[k]) return true;
+    return false;
+}
+
+// the table from the members as they are now.  Waits for the device first: no launch may be reading the rows it overwrites
+int worlds_write_table(lscqp_worlds_s* w) {
+    const size_t K = w->maps.size();
+    WorldsDevice on(w->device);
+    bool tables = true;
+    for (size_t k = 0; k < K; k++)
+        tables = tables && w->maps[k]->d_sat != nullptr && w->maps[k]->sat_margin > 0 && w->maps[k]->sat_margin == w->maps[0]->sat_margin;
+    std::vector<lscsfc::WorldPtrs> rows(K);
+    for (size_t k = 0; k < K; k++) rows[k] = lscsfc::WorldPtrs{w->maps[k]->d_nearest, tables ? w->maps[k]->d_sat : nullptr};
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(w->d_table, rows.data(), K * sizeof(lscsfc::WorldPtrs), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("lscqp_worlds (table): ") + hipGetErrorString(e)).c_str());
+    w->sat_margin = tables ? w->maps[0]->sat_margin : 0.0;
+    for (size_t k = 0; k < K; k++) w->gens[k] = w->maps[k]->generation;
+    return LSCQP_OK;
+}
+
+// the first field in which two maps differ in shape, NULL if none
+const char* shape_difference(const lscqp_map_s* a, const lscqp_map_s* b) {
+    if (a->res != b->res) return "resolution";
+    for (int k = 0; k < 3; k++)
+        if (a->world_min[k] != b->world_min[k]) return "world_min";
+    for (int k = 0; k < 3; k++)
+        if (a->world_max[k] != b->world_max[k]) return "world_max";
+    for (int k = 0; k < 3; k++)
+        if (a->key0[k] != b->key0[k]) return "key0";
+    for (int k = 0; k < 3; k++)
+        if (a->dims[k] != b->dims[k]) return "dims";
+    if (a->radius_cells != b->radius_cells) return "max_dist";
+    return nullptr;
+}
+
+}  // namespace
+
 extern "C" {
+
+int lscqp_worlds_create(const lscqp_map* maps, int32_t n_worlds, lscqp_worlds* out) {
+    if (!out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_worlds_create: null argument");
+    if (n_worlds < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_worlds_create: at least one world required");
+    if (!maps) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_worlds_create: null argument");
+    for (int32_t k = 0; k < n_worlds; k++)
+        if (!maps[k]) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, ("lscqp_worlds_create: map " + std::to_string(k) + " is null").c_str());
+    for (int32_t k = 1; k < n_worlds; k++) {
+        if (maps[k]->device != maps[0]->device)
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, ("lscqp_worlds_create: map " + std::to_string(k) + " differs from map 0 in device").c_str());
+        if (const char* f = shape_difference(maps[0], maps[k]))
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, ("lscqp_worlds_create: map " + std::to_string(k) + " differs from map 0 in " + f).c_str());
+    }
+    if (const int rc = lscqp_need_device_()) return rc;
+    int cur = 0;
+    if (hipGetDevice(&cur) != hipSuccess || cur != maps[0]->device)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_worlds_create: the maps live on another device than the current one");
+    lscqp_worlds_s* w = new lscqp_worlds_s();
+    w->maps.assign(maps, maps + n_worlds);
+    w->gens.assign((size_t)n_worlds, 0);
+    w->device = cur;
+    const hipError_t e = hipMalloc(&w->d_table, (size_t)n_worlds * sizeof(lscsfc::WorldPtrs));
+    if (e != hipSuccess) {
+        delete w;
+        return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("hipMalloc(worlds table): ") + hipGetErrorString(e)).c_str());
+    }
+    if (const int rc = worlds_write_table(w)) {
+        (void)hipFree(w->d_table);
+        delete w;
+        return rc;
+    }
+    *out = w;
+    return LSCQP_OK;
+}
+
+void lscqp_worlds_destroy(lscqp_worlds w) {
+    if (!w) return;
+    if (w->d_table) {
+        WorldsDevice on(w->device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(w->d_table);
+    }
+    delete w;
+}
+
+int lscqp_worlds_info(lscqp_worlds w, int32_t* n_worlds, int32_t* dims, int32_t* key0) {
+    if (!w || !n_worlds) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    *n_worlds = (int32_t)w->maps.size();
+    for (int k = 0; k < 3; k++) {
+        if (dims) dims[k] = w->maps[0]->dims[k];
+        if (key0) key0[k] = w->maps[0]->key0[k];
+    }
+    return LSCQP_OK;
+}
+
+int lscqp_worlds_prepare(lscqp_worlds w, double max_radius) {
+    if (!w) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null worlds");
+    if (!(max_radius > 0)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "max_radius > 0 required");
+    WorldsDevice on(w->device);
+    // one margin for all: a member that already has a table for a larger radius keeps it (lscqp_map_prepare), so the others follow it
+    double margin = max_radius;
+    for (lscqp_map mp : w->maps)
+        if (mp->d_sat && mp->sat_margin > margin) margin = mp->sat_margin;
+    int rc = LSCQP_OK;
+    for (size_t k = 0; k < w->maps.size() && rc == LSCQP_OK; k++) rc = lscqp_map_prepare(w->maps[k], margin);
+    const int rc_table = worlds_write_table(w);  // (also after a failure: the members' tables may have moved)
+    return rc != LSCQP_OK ? rc : rc_table;
+}
+
+int lscqp_worlds_count_(lscqp_worlds w) { return (int)w->maps.size(); }
+lscqp_map lscqp_worlds_map_(lscqp_worlds w, int k) { return w->maps[(size_t)k]; }
+uint64_t lscqp_worlds_generation_(lscqp_worlds w) {  // (every member's counter only rises: so does the sum)
+    uint64_t g = 0;
+    for (lscqp_map mp : w->maps) g += mp->generation;
+    return g;
+}
+int lscqp_worlds_refresh_(lscqp_worlds w) { return worlds_stale(w) ? worlds_write_table(w) : LSCQP_OK; }
+const char* lscqp_worlds_shape_difference_(lscqp_worlds w, lscqp_map mp) {
+    if (w->maps[0]->device != mp->device) return "device";
+    return shape_difference(mp, w->maps[0]);
+}
 
 #ifdef LSCSFC_DEBUG
 int lscsfc_dbg_read(unsigned long long* out, int reset) {
@@ -1483,9 +1673,11 @@ int lscqp_map_download(lscqp_map mp, uint8_t* occ, int32_t* nearest) {
     return LSCQP_OK;
 }
 
-// one launch of the corridor kernel, no checks: the device entries below and the host form lscqp_construct_sfc
+// one launch of the corridor kernel, no checks: the device entries below and the host form lscqp_construct_sfc.  ws != NULL: the worlds
+// form -- mp is the set's first member (the shape), the two map pointers come from the set's table by d_world_of
 static int launch_corridors(lscqp_map mp, int mode, int M, int64_t n, const double* d_points, const double* d_radius, lscqp_box* d_sfc,
-                            int32_t* d_status_out, const int32_t* d_order, uint32_t* d_cost_out, void* stream) {
+                            int32_t* d_status_out, const int32_t* d_order, uint32_t* d_cost_out, void* stream, const lscqp_worlds_s* ws = nullptr,
+                            const int32_t* d_world_of = nullptr) {
     lscsfc::MapView v;
     v.order = d_order;
     v.cost = d_cost_out;
@@ -1497,6 +1689,7 @@ static int launch_corridors(lscqp_map mp, int mode, int M, int64_t n, const doub
     v.nearest = mp->d_nearest;
     v.sat = mp->d_sat;
     v.sat_margin = mp->sat_margin;
+    if (ws) v.nearest = nullptr, v.sat = nullptr, v.sat_margin = ws->sat_margin;  // (the pointers: the kernel's, from the table; margin 0 without tables)
     // Two builds of the one kernel source.  LATENCY (this file): 1024 threads per agent, one workgroup per CU -- the sixteen wavefronts
     // shorten the chain of dependent tests of ONE corridor (171 / 204 / 335 us per corridor with 1024 / 512 / 256 threads), right while
     // agents <= CUs.  THROUGHPUT (lscsfc_tp.hip): 256 threads per agent, registers capped at 128, batch tables cut to 35 KB of LDS: four
@@ -1517,10 +1710,16 @@ static int launch_corridors(lscqp_map mp, int mode, int M, int64_t n, const doub
     const bool fits = mp->dims[0] <= tp_cells && mp->dims[1] <= tp_cells && mp->dims[2] <= tp_cells;
     const bool tp = fits && (force ? (force[0] == 't') : (n > (int64_t)n_cu));
     hipError_t e;
-    if (tp) {
+    if (tp && ws) {
+        e = lscsfc_launch_throughput_worlds_(&v, mode, M, n, d_points, d_radius, d_sfc, d_status_out, ws->d_table, d_world_of, stream);
+    } else if (ws) {
+        hipLaunchKernelGGL((lscsfc::construct_sfc_kernel<const lscsfc::WorldPtrs*, const int32_t*>), dim3((unsigned)n), dim3(lscsfc::kSfcThreads), 0, (hipStream_t)stream, v, mode, M, n, d_points,
+                           d_radius, d_sfc, d_status_out, (const lscsfc::WorldPtrs*)ws->d_table, d_world_of);
+        e = hipGetLastError();
+    } else if (tp) {
         e = lscsfc_launch_throughput_(&v, mode, M, n, d_points, d_radius, d_sfc, d_status_out, stream);
     } else {
-        hipLaunchKernelGGL(lscsfc::construct_sfc_kernel, dim3((unsigned)n), dim3(lscsfc::kSfcThreads), 0, (hipStream_t)stream, v, mode, M, n, d_points,
+        hipLaunchKernelGGL(lscsfc::construct_sfc_kernel<>, dim3((unsigned)n), dim3(lscsfc::kSfcThreads), 0, (hipStream_t)stream, v, mode, M, n, d_points,
                            d_radius, d_sfc, d_status_out);
         e = hipGetLastError();
     }
@@ -1539,6 +1738,38 @@ int lscqp_construct_sfc_device_ordered(lscqp_handle h, lscqp_map mp, int32_t mod
     if (M > 21) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "corridor shift supports M <= 21");
     if (const int rc = lscqp_need_device_()) return rc;
     return launch_corridors(mp, mode, M, n, d_points, d_radius, d_sfc, d_status_out, d_order, d_cost_out, stream);
+}
+
+// lscqp_construct_sfc_device_ordered in which agent a is tested against world d_world_of[a] (every index in [0, n_worlds): a precondition,
+// tested nowhere).  A member prepared behind the set's back is noticed here by its generation counter and the table rewritten -- unless
+// `stream` is being captured, where rewriting (it waits for the device) is impossible: then the launch is refused.  A stale row is never launched.
+int lscqp_construct_sfc_worlds_device(lscqp_handle h, lscqp_worlds w, int32_t mode, int64_t n, const int32_t* d_world_of, const double* d_points,
+                                      const double* d_radius, lscqp_box* d_sfc, int32_t* d_status_out, const int32_t* d_order, uint32_t* d_cost_out,
+                                      void* stream) {
+    if (!h || !w) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (mode != LSCQP_SFC_INIT && mode != LSCQP_SFC_FROM_HULL && mode != LSCQP_SFC_FROM_POINT)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "mode must be LSCQP_SFC_INIT, LSCQP_SFC_FROM_HULL or LSCQP_SFC_FROM_POINT");
+    if (n < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
+    if (n == 0) return LSCQP_OK;
+    if (!d_points || !d_radius || !d_sfc || !d_status_out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (!d_world_of) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null d_world_of: every agent needs the index of its world");
+    const int M = lscqp_class_desc_of_(h)->M;
+    if (M > 21) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "corridor shift supports M <= 21");
+    if (const int rc = lscqp_need_device_()) return rc;
+    {   // (the launch goes to the current device's stream and dereferences the members' grids)
+        int cur = 0;
+        if (hipGetDevice(&cur) != hipSuccess || cur != w->device)
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_construct_sfc_worlds_device: the worlds live on another device than the current one");
+    }
+    if (worlds_stale(w)) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (stream && hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
+                                    "lscqp_construct_sfc_worlds_device: a member map was prepared after the set's table was written and the stream is "
+                                    "being captured: call lscqp_worlds_prepare (or launch once outside a capture) first");
+        if (const int rc = worlds_write_table(w)) return rc;
+    }
+    return launch_corridors(w->maps[0], mode, M, n, d_points, d_radius, d_sfc, d_status_out, d_order, d_cost_out, stream, w, d_world_of);
 }
 
 int lscqp_construct_sfc_device(lscqp_handle h, lscqp_map mp, int32_t mode, int64_t n, const double* d_points, const double* d_radius,

@@ -6,6 +6,7 @@
 
     python tools/closed_loop.py [--steps 40] [--world tests/golden/forest10_world.json]
     python tools/closed_loop.py --missions 25 --until-finished [MAX]      (K seeded missions in one plan, flown to the finish on the device)
+    python tools/closed_loop.py --missions 4 --worlds A.csv B.csv C.csv D.csv   (mission k over world k: one plan, a world per mission)
 
 The host keeps the per-agent headers and, with --router host (the default), picks each agent's next waypoint with a stand-in
 for the grid-based planner (8-connected shortest paths, no conflict handling between agents).  --router device replaces
@@ -16,6 +17,7 @@ group, the simulator's update filter), so its paths differ from the stand-in's. 
 import argparse
 import json
 import os
+import re
 import sys
 
 import numpy as np
@@ -106,18 +108,47 @@ def random_forest_world(n_agents=64, side=24.0, n_boxes=150, seed=0, clearance=0
             "z_2d": z, "radius": 0.15, "starts": [[p[0], p[1], z] for p in starts], "goals": [[p[0], p[1], z] for p in goals]}
 
 
-def seeded_missions(world, occ, grid_min, missions, seed=0):
-    """K missions over one world: mission 0 is the world's own, mission k > 0 has as many agents on distinct free grid nodes and distinct
-    free goal nodes drawn from (seed, k).  Returns (offsets [K + 1], starts, goals)."""
-    starts, goals = [np.array(world["starts"], float)], [np.array(world["goals"], float)]
-    n = len(starts[0])
+def seeded_mission(world, occ, grid_min, k, seed=0):
+    """Mission k over the grid occupancy `occ`: mission 0 is the world's own, mission k > 0 has as many agents on distinct free grid nodes and
+    distinct free goal nodes drawn from (seed, k).  Returns (starts, goals)."""
+    if k == 0:
+        return np.array(world["starts"], float), np.array(world["goals"], float)
+    n = len(world["starts"])
     ys, xs = np.nonzero(~occ.astype(bool))
-    for k in range(1, missions):
-        pick = np.random.default_rng([seed, k]).choice(len(xs), size=2 * n, replace=False)
-        pts = np.c_[grid_min[0] + 0.5 * xs[pick], grid_min[1] + 0.5 * ys[pick], np.full(2 * n, float(world["z_2d"]))]
-        starts.append(pts[:n])
-        goals.append(pts[n:])
-    return np.arange(missions + 1) * n, np.concatenate(starts), np.concatenate(goals)
+    pick = np.random.default_rng([seed, k]).choice(len(xs), size=2 * n, replace=False)
+    pts = np.c_[grid_min[0] + 0.5 * xs[pick], grid_min[1] + 0.5 * ys[pick], np.full(2 * n, float(world["z_2d"]))]
+    return pts[:n], pts[n:]
+
+
+def seeded_missions(world, occ, grid_min, missions, seed=0):
+    """K missions over one world (seeded_mission for k = 0 .. K - 1).  Returns (offsets [K + 1], starts, goals)."""
+    per = [seeded_mission(world, occ, grid_min, k, seed) for k in range(missions)]
+    return np.arange(missions + 1) * len(world["starts"]), np.concatenate([m[0] for m in per]), np.concatenate([m[1] for m in per])
+
+
+def load_worlds(spec, missions):
+    """Box lists ((n, 6) arrays: centre xyz, size xyz), one per mission, for `worlds=`: a directory of world CSVs (its *.csv in natural order,
+    as Mission::loadMission lists a world directory), a list of CSV paths, or a list of box lists.  Exactly `missions` of them: the
+    reference pairs mission k with world k only when the two lists are equally long.  No device needed."""
+    if isinstance(spec, (str, os.PathLike)):
+        spec = [spec]
+    spec = list(spec)
+    if len(spec) == 1 and isinstance(spec[0], (str, os.PathLike)) and os.path.isdir(spec[0]):
+        d = os.fspath(spec[0])
+        names = sorted((f for f in os.listdir(d) if f.endswith(".csv")), key=lambda f: [int(t) if t.isdigit() else t for t in re.split(r"(\d+)", f)])
+        spec = [os.path.join(d, f) for f in names]
+    if not missions or len(spec) != int(missions):
+        raise ValueError("worlds: %d worlds for missions=%s -- one world per mission required" % (len(spec), missions))
+    out = []
+    for w in spec:
+        if isinstance(w, (str, os.PathLike)):
+            if not os.path.isfile(w):
+                raise ValueError("worlds: no such world file: %s" % os.fspath(w))
+            rows = [line.replace(",", " ").split() for line in open(w)]
+            w = [[float(v) for v in r[:6]] for r in rows if len(r) >= 6]
+        b = np.asarray(w, dtype=np.float64).reshape(-1, 6)
+        out.append(b)
+    return out
 
 
 def load_obstacles(path):
@@ -130,14 +161,17 @@ def load_obstacles(path):
 
 
 def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=0, graph=True, until_finished=None, check_every=16,
-                 goal_threshold=0.1, obstacles=None):
+                 goal_threshold=0.1, obstacles=None, worlds=None):
     """`missions` seeded missions over one world flown by ONE lscqp_plan with a mission partition (include/lscqp.h, "many missions over one
     map"): waypoint_mode 1, closed loop, one captured graph per replan.  The summary has the figures of `run` per mission.
     until_finished = MAX: the plan keeps a mission record (include/lscqp.h, "the mission record") and lscqp_plan_run flies it until every
     mission has finished or MAX replans, with no download in between; per mission the summary then holds the device's record.
     obstacles: api.OBSTACLE_MODEL_DTYPE records (load_obstacles) -- the dynamic obstacles every mission shares, moved by the chain itself
     (lscqp_plan_set_obstacles).  Their rows are generateLSC's, so the agents' rows are LSC rows too (GEN_LSC instead of GEN_CLSC), and
-    they take the first row slots: n_obs counts the agent slots, the plan gets n_obs + len(obstacles)."""
+    they take the first row slots: n_obs counts the agent slots, the plan gets n_obs + len(obstacles).
+    worlds: one world per mission (load_worlds) in the world's box -- mission k flies over world k (include/lscqp.h, "each mission over its
+    own world"; lscqp_plan_set_worlds), its seeded agents drawn from the free nodes of its own world; world 0 replaces the world's own boxes."""
+    world_boxes = None if worlds is None else load_worlds(worlds, missions)  # (before anything needs a device)
     import torch
 
     from lsc_dr_planner_amd import api
@@ -145,9 +179,16 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     g = world_json if isinstance(world_json, dict) else json.load(open(world_json))
     n = len(g["starts"])
     sol = api.Solver(api.make_desc(M=M, dim=2, dt=dt, world_min=g["world_min"], world_max=g["world_max"]))
-    wmap = api.WorldMap(g["boxes"], g["world_min"], g["world_max"], g["resolution"], g["max_dist"])
+    maps = [api.WorldMap(b, g["world_min"], g["world_max"], g["resolution"], g["max_dist"]) for b in (world_boxes or [g["boxes"]])]
+    wmap = maps[0]
+    off = np.arange(missions + 1) * n
     probe = api.Grid(wmap, 0.5, float(g["radius"]), float(g["z_2d"]))
-    off, starts, goals = seeded_missions(g, probe.download(), probe.grid_min, missions, seed)
+    if world_boxes:  # mission k's agents: (seed, k) over the free nodes of the world it flies over
+        probe.set_worlds(api.Worlds(maps))
+        per = [seeded_mission(g, probe.download_world(k), probe.grid_min, k, seed) for k in range(missions)]
+        starts, goals = np.concatenate([m[0] for m in per]), np.concatenate([m[1] for m in per])
+    else:
+        _, starts, goals = seeded_missions(g, probe.download(), probe.grid_min, missions, seed)
     probe.close()
     N = int(off[-1])
     n_dyn = 0 if obstacles is None else len(obstacles)
@@ -157,6 +198,10 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     plan = api.Plan(sol, wmap, N, n_obs, ag, constraint_mode=api.GEN_LSC if n_dyn else api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, optimize_goal=True,
                     closed_loop=True, z_2d=float(g["z_2d"]), safety_samples=2, record_time_step=0.1, waypoint_mode=api.WAYPOINT_GRID_PIBT,
                     mission_offsets=off)
+    world_set = None
+    if world_boxes:
+        world_set = api.Worlds(maps)
+        plan.set_worlds(world_set)
     if n_dyn:
         plan.set_obstacles(obstacles)
     if until_finished:
@@ -178,8 +223,13 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
                    min_safety_ratio=min(m["min_safety_ratio"] for m in per), per_mission=per)
         if n_dyn:  # (the record keeps no obstacle figure: the last replan's is what the plan still holds)
             log.update(obstacles=n_dyn, last_obstacle_safety_ratio=float(plan.get_obstacles(api.PLAN_OBS_SAFETY)["safety_ratio_obs"].min()))
+        if world_set:
+            log["worlds"] = len(world_set)
         plan.close()
-        wmap.close()
+        if world_set:
+            world_set.close()
+        for m_ in maps:
+            m_.close()
         return log
     plan.reset(starts, goals)
     min_obstacle_ratio = np.inf
@@ -211,13 +261,18 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
                min_safety_ratio=min(m["min_safety_ratio"] for m in per), per_mission=per)
     if n_dyn:
         log.update(obstacles=n_dyn, min_obstacle_safety_ratio=min_obstacle_ratio)
+    if world_set:
+        log["worlds"] = len(world_set)
     plan.close()
-    wmap.close()
+    if world_set:
+        world_set.close()
+    for m_ in maps:
+        m_.close()
     return log
 
 
 def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None, router="host", missions=None,
-        decision="one", until_finished=None, obstacles=None):
+        decision="one", until_finished=None, obstacles=None, worlds=None):
     """script (optional): {"waypoint": (K, N, 3), "state": (K, N, 9)} -- replay of a recorded mission: replan k takes every agent's
     state and waypoint from the script instead of the loop's own step / router (the plans, goal points, corridors and neighbour sets are
     still the loop's own), and the result carries every replan's solution (`x`, (K, N, nv)) and goal point (`goal`, (K, N, 3)).
@@ -226,7 +281,8 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
     decision (router "device"): "one" (lscqp_waypoints_device), "wide" (lscqp_waypoints_wide_device) or "auto" (wide from
     DECISION_AUTO_MIN_AGENTS agents on); the flight is the same whichever is chosen.
     until_finished (with missions): fly until every mission has finished, at most that many replans (run_missions).
-    obstacles (with missions): dynamic obstacles flown by the plan's own chain (load_obstacles, run_missions)."""
+    obstacles (with missions): dynamic obstacles flown by the plan's own chain (load_obstacles, run_missions).
+    worlds (with missions): one world per mission -- a directory of world CSVs, a list of CSV paths or of box lists (load_worlds, run_missions)."""
     if router not in ("host", "device"):
         raise ValueError("router must be 'host' or 'device'")
     if decision not in ("one", "wide", "auto"):
@@ -235,8 +291,11 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
         raise ValueError("until_finished needs missions=K (one lscqp_plan with a mission record)")
     if obstacles is not None and not missions:
         raise ValueError("obstacles need missions=K (K >= 1): they fly in the chain of an lscqp_plan (lscqp_plan_set_obstacles)")
+    if worlds is not None and not missions:
+        raise ValueError("worlds need missions=K: world k belongs to mission k of an lscqp_plan (lscqp_plan_set_worlds)")
     if missions:
-        return run_missions(world_json, int(missions), steps=steps, M=M, dt=dt, n_obs=n_obs, until_finished=until_finished, obstacles=obstacles)
+        return run_missions(world_json, int(missions), steps=steps, M=M, dt=dt, n_obs=n_obs, until_finished=until_finished, obstacles=obstacles,
+                            worlds=worlds)
     import torch
 
     from lsc_dr_planner_amd import api
@@ -441,8 +500,11 @@ if __name__ == "__main__":
     ap.add_argument("--obstacles", default=None, metavar="FILE.json",
                     help="with --missions K: the dynamic obstacles of a reference mission file (its \"obstacles\" list, or a bare list: type, start, goal, "
                          "waypoints, axis, size, speed, max_acc, downwash), shared by every mission and moved by the plan's chain")
+    ap.add_argument("--worlds", default=None, nargs="+", metavar="CSV",
+                    help="with --missions K: K world CSVs (or one directory holding K) in the world's box -- mission k flies over world k, as "
+                         "launch/test_all_*.launch pair a mission directory with a world directory")
     ap.add_argument("--router", default="host", choices=("host", "device"), help="where the waypoints come from: the host stand-in or lscqp_waypoints_device")
     a = ap.parse_args()
     world = random_forest_world(a.forest) if a.forest > 0 else a.world
     print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router, missions=a.missions, decision=a.decision,
-                         until_finished=a.until_finished, obstacles=load_obstacles(a.obstacles) if a.obstacles else None)))
+                         until_finished=a.until_finished, obstacles=load_obstacles(a.obstacles) if a.obstacles else None, worlds=a.worlds)))
