@@ -1264,6 +1264,24 @@ int lscqp_instance_work(lscqp_handle h, int64_t n, int32_t n_obs_max, lscqp_work
  *                            non-OPTIMAL instance (the iterate the solver stopped at) it names the rows that instance cannot satisfy.
  *                            Units are the reference's: metres for bounds / SFC / LSC (normal-weighted) / communication rows,
  *                            m/s and m/s^2 for the dynamic limits, the row's own scaling for the equalities.
+ *                            A two-sided limit (bounds, corridor faces of one axis, |v|, |a|, communication rows) is ONE row with
+ *                            one name; its violation is the larger of its two sides.  A row is counted when violation > tol, strictly.
+ *                            Names (family, obstacle, segment, point, axis), -1 where a field does not apply:
+ *                              BOUND, SFC            (-1, m, i, k)   control point i of segment m, axis k
+ *                              LSC                   (oi, m, i, -1)  obstacle slot oi; a row with |n| < 1e-5 does not exist (:409-411)
+ *                              VEL, ACC              (-1, m, i, k)   the difference that starts at control point i
+ *                              COMM_PAIR             (mi, m, 5, k)   |c[m][5] - c[mi][0]|, mi <= m
+ *                              COMM_WAYPOINT         (-1, m, 5, k)
+ *                              EQUALITY              (-1, 0, j, k)   initial position / velocity / acceleration, j = 0 / 1 / 2
+ *                                                    (-1, m, j, k)   m >= 1: the C0 / C1 / C2 join of segment m - 1 to m, j = 0 / 1 / 2
+ *                                                    (-1, M-1, 4 | 3, k)  the end stop c5 = c4, c5 = c3 (LSC planner mode)
+ *                            TIES.  Among rows of equal violation the named row is the least in (family, obstacle, segment, point,
+ *                            axis), compared lexicographically -- e.g. a corridor face that coincides with a world face names BOUND.
+ *                            NON-FINITE INPUT.  A row whose value is NaN or +inf cannot be shown to hold: it counts as violated, its
+ *                            family's `worst` is +inf, and the named row is the least such row by the tie rule with violation = +inf.
+ *                            That holds wherever the NaN enters: a control point, a header field, an LSC row, or ONE face of a
+ *                            corridor or of the world box (a two-sided row is NaN if either side is).
+ *                            The instances of a batch do not affect each other.
  *   lscqp_dump_instance      one instance as a CPLEX LP file, rows and variable names (x_m_i, y_m_i, z_m_i) as populatebyrow
  *                            creates them -- what cplex.exportModel writes to log/QPmodel_trajOpt.lp; HOST pointers, rows / sfc of
  *                            THIS instance ([n_obs*P] rows, [M] boxes); needs no device.

@@ -36,12 +36,21 @@ struct DiagClass {
 
 struct Worst {  // running argmax of one lane
     double v;
+    unsigned long long key;
     int fam, obs, seg, pt, axis;
 };
 
+// (family, obstacle, segment, point, axis) as one integer that orders like the tuple (include/lscqp.h, the tie rule); -1 fields sort first
+__device__ __forceinline__ unsigned long long name_key(int fam, int obs, int seg, int pt, int axis) {
+    return ((unsigned long long)(unsigned)fam << 56) | ((unsigned long long)(unsigned)(obs + 1) << 32) | ((unsigned long long)(unsigned)(seg + 1) << 16) |
+           ((unsigned long long)(unsigned)(pt + 1) << 8) | (unsigned long long)(unsigned)(axis + 1);
+}
+
 __device__ __forceinline__ void take(Worst& w, double v, int fam, int obs, int seg, int pt, int axis) {
-    if (v > w.v) {
+    const unsigned long long key = name_key(fam, obs, seg, pt, axis);
+    if (v > w.v || (v == w.v && key < w.key)) {
         w.v = v;
+        w.key = key;
         w.fam = fam;
         w.obs = obs;
         w.seg = seg;
@@ -49,6 +58,9 @@ __device__ __forceinline__ void take(Worst& w, double v, int fam, int obs, int s
         w.axis = axis;
     }
 }
+
+// The value of a two-sided row: the larger side, and NaN if either side is (fmax alone would drop a NaN face or bound)
+__device__ __forceinline__ double two_sided(double below, double above) { return (below != below || above != above) ? NAN : fmax(below, above); }
 
 // One wavefront per instance.  x: control points in the reference variable order x[k*P + 6m + i], world frame.
 __global__ __launch_bounds__(64) void diagnose_kernel(DiagClass c, int64_t n, const lscqp_header* __restrict__ hdr, const lscqp_row* __restrict__ rows,
@@ -68,8 +80,9 @@ __global__ __launch_bounds__(64) void diagnose_kernel(DiagClass c, int64_t n, co
         fam_worst[f] = -1e300;
         fam_cnt[f] = 0;
     }
-    Worst w{-1e300, -1, -1, -1, -1, -1};
+    Worst w{-1e300, ~0ull, -1, -1, -1, -1, -1};
     auto row = [&](int fam, double v, int obs, int seg, int pt, int axis) {
+        if (v != v) v = INFINITY;  // a NaN row cannot be shown to hold: it counts as violated, like +inf (include/lscqp.h)
 #pragma unroll
         for (int f = 0; f < LSCQP_ROW_FAMILIES; f++)
             if (f == fam) {
@@ -88,10 +101,10 @@ __global__ __launch_bounds__(64) void diagnose_kernel(DiagClass c, int64_t n, co
             hi = 100.0;
         }
         const double v = at(k, m, i);
-        row(LSCQP_ROW_BOUND, fmax(lo - v, v - hi), -1, m, i, k);
+        row(LSCQP_ROW_BOUND, two_sided(lo - v, v - hi), -1, m, i, k);
         if (c.use_sfc && sfc) {
             const lscqp_box& b = sfc[q * M + m];
-            row(LSCQP_ROW_SFC, fmax(b.bmin[k] - v, v - b.bmax[k]), -1, m, i, k);
+            row(LSCQP_ROW_SFC, two_sided(b.bmin[k] - v, v - b.bmax[k]), -1, m, i, k);
         }
     }
     // LSC / BVC half-spaces (:399-437): n.(c - p) - d >= 0 <=> n.c >= b; rows with a normal shorter than 1e-5 do not exist (:409-411)
@@ -154,7 +167,7 @@ __global__ __launch_bounds__(64) void diagnose_kernel(DiagClass c, int64_t n, co
             row(LSCQP_ROW_EQUALITY, fabs(at(k, m, 5) - at(k, m, 3)), -1, m, 3, k);
         }
     }
-    // wave reduction: per family max / count, and the argmax (ties: the lowest lane, i.e. deterministic)
+    // wave reduction: per family max / count, and the argmax (ties: the least name among the lanes that hold the best value)
 #pragma unroll
     for (int f = 0; f < LSCQP_ROW_FAMILIES; f++) {
         for (int d = 32; d >= 1; d >>= 1) {
@@ -164,7 +177,12 @@ __global__ __launch_bounds__(64) void diagnose_kernel(DiagClass c, int64_t n, co
     }
     double best = w.v;
     for (int d = 32; d >= 1; d >>= 1) best = fmax(best, __shfl_xor(best, d));
-    const unsigned long long owners = __ballot(w.v == best);
+    unsigned long long kmin = (w.v == best) ? w.key : ~0ull;
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long other = __shfl_xor(kmin, d);
+        kmin = other < kmin ? other : kmin;
+    }
+    const unsigned long long owners = __ballot(w.v == best && w.key == kmin);
     const int owner = owners ? (int)__builtin_ctzll(owners) : 0;
     if (lane == owner) {
         lscqp_diag& D = out[q];
