@@ -15,7 +15,14 @@
 //   one wavefront).  4: a joining row's descriptors are stored from registers, not copied from the candidate's slot.  8: the verification as
 //   straight-line code -- every operand asked for before the first arithmetic, lam_ kept zero from the prologue on instead of zeroed
 //   behind a barrier of its own (needs LSCQP_DAS_PROLOGUE 1 and more than one wavefront).  16: not used.  32: the objective's rounding
-//   term from one block of loads instead of a loop of six dependent ones (with bit 8 only: the text is in its branch).  As the prologues, the settings differ in when and by which thread a value is moved, in no expression
+//   term from one block of loads instead of a loop of six dependent ones (with bit 8 only: the text is in its branch).  64 .. 2048
+//   (four wavefronts and LSCQP_DAS_LAYOUT; 2048 needs bit 1 and a shape whose rows fit one block of row slots): LDS round trips that held
+//   one or two reads, folded -- 64: the four empty-interval ballots in one read, no branch; 128: the pass's minimum across the wavefronts from
+//   one block of reads, by selects; 256: `primal` read with t, kind and l in front of the test on kind; 512: a two-sided candidate's
+//   stencil and both bounds asked for together; 1024: the candidate's multiplier so far in a register of wavefront 0 beside ctl_[3];
+//   2048: the thread's two-sided rows in registers from the prologue on, and a later pass that asks for its staged rows and every
+//   operand in c_ in one block (tests/test_das_round_trips.py).
+//   As the prologues, the settings differ in when and by which thread a value is moved, in no expression
 //   that rounds (tests/test_das_step_path.py, tests/test_das_verification.py);
 //   LSCQP_DAS_END(verdict): leaves the phase with a DasVerdict, taken by the whole workgroup at once;
 //   LSCQP_DAS_LAYOUT (optional): the LDS carve as a constant expression, with room for at least kmax active rows, the class's table and
@@ -328,6 +335,21 @@
     // type 0: no row; 1: interval; 2: velocity; 3: acceleration; 4: pair.  Entry indices are positions in c_ (axis * P + control point).
     bool empty = false;
     const double hv_c = dt * 0.2, ha_c = dt * dt * 0.05;
+#if LSCQP_DAS_STEP_PATH & 2048
+    // This thread's two-sided rows stay in registers across the loop of steps -- they never change after this section, which computes and
+    // stores them anyway: the packed stencil, its three positions in c_ and two coefficients (pair_val's), lo, hi.  A slot without a row
+    // (r >= NPAIR) holds stencil 0: no row.  Sized from the shape, as kU is: one slot at M = 5 in 3-D (255 rows), two at M = 10 in 2-D (320).
+#ifndef LSCQP_DAS_LAYOUT
+#error "LSCQP_DAS_STEP_PATH & 2048 sizes its register copy from the compile-time carve"
+#endif
+    constexpr int kPR = (L.NPAIR + T - 1) / T;
+    static_assert(kPR <= kPB && L.NPAIR <= kPB * T, "the section's first block of four slots holds every two-sided row of the shape");
+    int tp_pk[kPR], tp_i0[kPR], tp_i1[kPR], tp_e0[kPR];
+    double tp_a1[kPR], tp_a2[kPR], tp_lo[kPR], tp_hi[kPR];
+#pragma unroll
+    for (int u = 0; u < kPR; u++)  // (a thread behind the last row never enters the section's loop)
+        tp_pk[u] = tp_i0[u] = tp_i1[u] = tp_e0[u] = 0, tp_a1[u] = tp_a2[u] = tp_lo[u] = tp_hi[u] = 0.0;
+#endif
     for (int r0 = tid; r0 < NPAIR; r0 += kPB * T) {
         if (r0 != tid) {
 #pragma unroll
@@ -363,6 +385,20 @@
                 plo_[r] = lo, phi_[r] = hi;
                 pix_[r] = w0;
             }
+#if LSCQP_DAS_STEP_PATH & 2048
+            if (u < kPR) {  // (a constant of the unrolled loop; r = tid + u T here: the section has one block)
+                const int pk = r < NPAIR ? w0 : 0;
+                const int type = pk >> 24, e0 = (pk >> 12) & 0xfff, e1 = pk & 0xfff;  // (pair_val's decoding, below)
+                const int us = u < kPR ? u : 0;  // (the index stays inside the arrays in the unrolled copies this test removes)
+                tp_pk[us] = pk;
+                tp_i0[us] = (type == 4) ? e1 : e0 + max(type - 1, 0);
+                tp_i1[us] = (type == 3) ? e0 + 1 : e0;
+                tp_e0[us] = e0;
+                tp_a1[us] = (type <= 1) ? 0.0 : (type == 3) ? -2.0 : -1.0;
+                tp_a2[us] = (type == 3) ? 1.0 : 0.0;
+                tp_lo[us] = lo, tp_hi[us] = hi;
+            }
+#endif
         }
     }
     // ---- unconstrained optimum: c_u[k] = cfix[k] - c1_k U1 - c2_k U2 + 2 w_t goal_k G1 ---------------------------------------------------
@@ -402,9 +438,18 @@
     LSCQP_DAS_BARRIER();
     bool empty_g = empty_w;
     if constexpr (NW > 1) {
+#if LSCQP_DAS_STEP_PATH & 64
+        // the four ballots in one request and one wait, combined without a branch (`||` around a load is a test around a load: four
+        // dependent LDS round trips); they are adjacent and 16-byte aligned in the carve.  A ballot is 0 or 1: their maximum, compared
+        // once (four comparisons joined with `|` are four scalar-register pairs, and <5,3,1,5,2> spilled 184 of them against 174)
+        static_assert(NW == 4 && L.o_red % 2 == 0, "four ballots, two 16-byte words");
+        const double2 b01 = *reinterpret_cast<const double2*>(red_ + 20), b23 = *reinterpret_cast<const double2*>(red_ + 22);
+        empty_g = fmax(fmax(b01.x, b01.y), fmax(b23.x, b23.y)) != 0.0;
+#else
         empty_g = false;
 #pragma unroll
         for (int w = 0; w < NW; w++) empty_g = empty_g || red_[20 + w] != 0.0;
+#endif
     }
 #else
     if (tid == 0) ctl_[4] = 0.0;
@@ -477,10 +522,23 @@
             R.rhs = b;
             return;
         }
+#if LSCQP_DAS_STEP_PATH & 512
+        // the stencil and BOTH bounds asked for together, at a clamped index; the side selects the bound (it chose which one to READ,
+        // behind the stencil's wait: a second round trip).  (Not taken by an empty asm: that costs <5,3,1,5,2> four scalar-register
+        // spills.  Without it <10,2,1,5,2>, where the id is a scalar, still waits for the stencil in front of the two bounds.)
+        const int s = rid - nL, rc_ = min(s >> 1, NPAIR - 1);
+        const int pk = pix_[rc_];
+        const double lo_w = plo_[rc_], hi_w = phi_[rc_];
+#else
         const int s = rid - nL, r = s >> 1, pk = pix_[r];
+#endif
         const int type = pk >> 24, e0 = (pk >> 12) & 0xfff, e1 = pk & 0xfff;
         const double sg = (s & 1) ? -1.0 : 1.0;
+#if LSCQP_DAS_STEP_PATH & 512
+        R.rhs = (s & 1) ? -hi_w : lo_w;
+#else
         R.rhs = (s & 1) ? -phi_[r] : plo_[r];
+#endif
         // 1: c[e0]   2: c[e0+1] - c[e0]   3: c[e0+2] - 2 c[e0+1] + c[e0]   else (4): c[e1] - c[e0].  Selects, not a chain of branches: with
         // the fused kernel's compile-time carve, the compiler merged the branches so that a pair row (type 4) left the phase with coef[1]
         // undefined (0 in practice) -- a different row, found on c1_infeasible_1pct (NOTES.md section 16).  The values are the branches' own.
@@ -539,6 +597,27 @@
             }
         };
         double rx[kU], ry[kU], rz[kU], rb[kU];
+#if LSCQP_DAS_STEP_PATH & 2048
+        // the two-sided rows of this thread from the registers the prologue left (tp_*): the pass reads nothing of pix_ / plo_ / phi_, only
+        // the stencils' operands in c_, and asks for those where `ts_request` stands
+        double tv0[kPR], tv1[kPR], tv2[kPR];
+        bool ts_asked = false;  // (a constant after inlining)
+        auto ts_request = [&]() {
+#pragma unroll
+            for (int u = 0; u < kPR; u++) tv0[u] = c_[tp_i0[u]], tv1[u] = c_[tp_i1[u]], tv2[u] = c_[tp_e0[u]];
+            ts_asked = true;
+        };
+        auto ts_see = [&]() {
+#pragma unroll
+            for (int u = 0; u < kPR; u++) {
+                const int r = tid + u * T;
+                const double d = (tv0[u] + tp_a1[u] * tv1[u]) + tp_a2[u] * tv2[u];  // (pair_val's expression)
+                const bool on = (tp_pk[u] >> 24) != 0;
+                see(on ? d - tp_lo[u] : 1.0, nL + 2 * r);
+                see(on ? tp_hi[u] - d : 1.0, nL + 2 * r + 1);
+            }
+        };
+#endif
         if (first_pass) {
             // the prologue's rows, then the rest from memory
             prep(tid, px, py, pz, pw, rx, ry, rz, rb);
@@ -553,7 +632,33 @@
                 eval(j0, rx, ry, rz, rb);
             }
         } else if (rows_in_lds) {
-#if LSCQP_DAS_STEP_PATH & 1
+#if LSCQP_DAS_STEP_PATH & 2048
+            // The later pass in TWO round trips: the staged rows (as bit 1 asks for them; one block holds every row of the shape, so no
+            // loop and no test on the thread's first row stand around the loads), and behind them in the same block of requests the
+            // operands in c_ of the LSC rows AND of the two-sided rows -- their addresses depend on nothing that is loaded.
+            static_assert((LSCQP_DAS_STEP_PATH & 1) && kMaxNL <= kU * T, "one block of clamped, untested loads covers the instance's rows");
+            double lx[kU], ly[kU], lz[kU], lb[kU], cx[kU], cy[kU], cz[kU];
+#pragma unroll
+            for (int u = 0; u < kU; u++) {
+                const int j = tid + u * T, jc = j < nL ? j : 0;
+                lx[u] = Sx_[jc], ly[u] = Sy_[jc], lz[u] = Sz_[jc], lb[u] = Sb_[jc];
+            }
+#pragma unroll
+            for (int u = 0; u < kU; u++) {
+                const int j = tid + u * T, jc = j < nL ? j : 0;
+                const int cp = jc - P * fdiv(jc, iP);
+                cx[u] = c_[cp], cy[u] = c_[P + cp], cz[u] = c_[2 * P + cp];
+            }
+            ts_request();
+            __builtin_amdgcn_sched_barrier(0);  // (every request above stands in front of the first use below)
+#pragma unroll
+            for (int u = 0; u < kU; u++) {
+                const int j = tid + u * T;
+                const bool in = j < nL;
+                rx[u] = in ? lx[u] : 0.0, ry[u] = in ? ly[u] : 0.0, rz[u] = in ? lz[u] : 0.0, rb[u] = in ? lb[u] : -1.0;
+                see(rx[u] * cx[u] + ry[u] * cy[u] + rz[u] * cz[u] - rb[u], j);  // (eval's expression)
+            }
+#elif LSCQP_DAS_STEP_PATH & 1
             // every staged row of this thread asked for at once, the index clamped into the staged arrays and no test around a load; a slot
             // past the end becomes the harmless row by selects on the loaded values (a test around a load serialises the loads: each slot
             // then is an LDS round trip of its own, and the reads of c_ in eval come behind the last of them)
@@ -593,6 +698,10 @@
         }
         first_pass = false;
         DAS_T(8);
+#if LSCQP_DAS_STEP_PATH & 2048
+        if (!ts_asked) ts_request();  // (the first pass, and a pass over rows that are not staged)
+        ts_see();
+#else
         for (int r0 = tid; r0 < NPAIR; r0 += 2 * T) {  // two at a time: their LDS round trips overlap
             const int r1 = r0 + T, r1c = r1 < NPAIR ? r1 : r0;
             const int pk0 = pix_[r0], pk1 = pix_[r1c];
@@ -604,10 +713,26 @@
             see(on1 ? d1 - lo1 : 1.0, nL + 2 * r1);
             see(on1 ? hi1 - d1 : 1.0, nL + 2 * r1 + 1);
         }
+#endif
         DAS_T(9);
     };
     // the workgroup's (slack, id) minimum out of the wavefronts' (buffer rb_: values at [0, 4), ids as ints at [4, 6))
     auto pass_combine = [&](const double* rb_, double& bv, int& bi) {
+#if LSCQP_DAS_STEP_PATH & 128
+        // the four values and the four ids in one request and one wait (the buffer is 16-byte aligned), the lexicographic minimum by
+        // selects in the loop's order: `||` and `&&` around the loads made three to four dependent LDS round trips and six branches of it
+        static_assert(NW == 4 && L.o_red % 2 == 0, "four values and four ids, three 16-byte words");
+        const double2 v01 = *reinterpret_cast<const double2*>(rb_), v23 = *reinterpret_cast<const double2*>(rb_ + 2);
+        const int4 ids = *reinterpret_cast<const int4*>(rb_ + 4);
+        const double ovs[4] = {v01.x, v01.y, v23.x, v23.y};
+        const int ois[4] = {ids.x, ids.y, ids.z, ids.w};
+        bv = ovs[0], bi = ois[0];
+#pragma unroll
+        for (int w = 1; w < NW; w++) {
+            const bool lt = (ovs[w] < bv) | ((ovs[w] == bv) & (ois[w] < bi));
+            bv = lt ? ovs[w] : bv, bi = lt ? ois[w] : bi;
+        }
+#else
         bv = rb_[0], bi = reinterpret_cast<const int*>(rb_ + 4)[0];
 #pragma unroll
         for (int w = 1; w < NW; w++) {
@@ -615,6 +740,7 @@
             const int oi = reinterpret_cast<const int*>(rb_ + 4)[w];
             if (ov < bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
         }
+#endif
     };
     auto pass = [&](double& best, int& bid) {
         const bool was_first = first_pass;
@@ -1155,6 +1281,14 @@
         if constexpr (NW == 1) compute_wp(0, T);
         DAS_T(5);  // candidate: decode, table copy (one wavefront: w_p)
         double spp = 0.0;  // a_p'C a_p (wavefront 0)
+#if LSCQP_DAS_STEP_PATH & 1024
+        // the candidate's multiplier so far, in a register of wavefront 0 beside ctl_[3] (zeroed above, the same sums in the same order:
+        // the decision's t is the same in every lane of the wavefront); the decision takes the register instead of a round trip to LDS
+        double u_cand = 0.0;
+#define DAS_U_CAND u_cand
+#else
+#define DAS_U_CAND ctl_[3]
+#endif
         bool stop = false, first_step = true;
         for (;;) {  // partial steps until p has joined the set
             steps++;
@@ -1172,6 +1306,17 @@
                 const double sp = row_dot(Rp.ent, Rp.coef, c_) - Rp.rhs;
                 const double t = (spp > 1e-12 * spp) ? -sp / spp : 1e300;
                 const int kind = (t < 1e299) ? 1 : 0;
+#if LSCQP_DAS_STEP_PATH & 1024
+                u_cand = u_cand + t;
+                if (lane == 0) {
+                    if (kind == 1) Jm_[0] = rsqrt(spp), u_[0] = u_cand;
+                    ctl_[0] = t;
+                    ctl_[1] = (double)kind;
+                    ctl_[2] = 0.0;
+                    ctl_[3] = u_cand;
+                    ctl_[5] = (t < 1e299) ? 1.0 : 0.0;
+                }
+#else
                 if (lane == 0) {
                     if (kind == 1) Jm_[0] = rsqrt(spp), u_[0] = ctl_[3] + t;
                     ctl_[0] = t;
@@ -1180,6 +1325,7 @@
                     ctl_[3] += t;
                     ctl_[5] = (t < 1e299) ? 1.0 : 0.0;
                 }
+#endif
             } else if (wv == 0) {
                 if (first_step) spp = cdot(Rp.ent, Rp.coef, Rp.ent, Rp.coef, Cm, P);
                 const double vj = (lane < k) ? row_dot(Rp.ent, Rp.coef, W_ + (size_t)lane * NX) : 0.0;
@@ -1204,14 +1350,21 @@
                     if (kind == 1) {  // one more row of J: (-r', 1) / sqrt(curv); the column above its diagonal entry is zero
                         const double idl = rsqrt(curv);
                         if (lane < k) Jm_[k * LDL + lane] = -ri * idl, Jm_[lane * LDL + k] = 0.0;
-                        if (lane == 0) Jm_[k * LDL + k] = idl, u_[k] = ctl_[3] + t;
+                        if (lane == 0) Jm_[k * LDL + k] = idl, u_[k] = DAS_U_CAND + t;
                     }
                 }
+#if LSCQP_DAS_STEP_PATH & 1024
+                u_cand = u_cand + t;
+#endif
                 if (lane == 0) {
                     ctl_[0] = t;
                     ctl_[1] = (double)kind;
                     ctl_[2] = (double)l;
+#if LSCQP_DAS_STEP_PATH & 1024
+                    ctl_[3] = u_cand;
+#else
                     ctl_[3] += t;
+#endif
                     ctl_[5] = (t2 < 1e299) ? 1.0 : 0.0;  // a primal step is taken
                     ctl_[7] = -sp;
                 }
@@ -1221,6 +1374,12 @@
             LSCQP_DAS_BARRIER();
             const double t = ctl_[0];
             const int kind = __builtin_amdgcn_readfirstlane((int)ctl_[1]), l = __builtin_amdgcn_readfirstlane((int)ctl_[2]);  // (uniform: scalar loop bounds)
+#if LSCQP_DAS_STEP_PATH & 256
+            // `primal` in the same block of reads as t, kind and l, in front of the test on kind (behind it the read was a round trip of
+            // its own; the decision stores ctl_[5] whatever kind it finds)
+            double primal_w = ctl_[5];
+            asm volatile("" : "+v"(primal_w));
+#endif
             if (kind == 0 || kind == 3) {
                 stop = true;
                 why = LSCQP_DAS_WHY_NO_STEP;
@@ -1229,7 +1388,11 @@
             }
             // c += t (w_p - sum r_j w_j)   (r_ holds this step's r); a leaving row closes the gap in W on the way (the candidate moves down too)
             const int ks = __builtin_amdgcn_readfirstlane(k);  // (uniform by construction; said so: scalar loop bounds)
+#if LSCQP_DAS_STEP_PATH & 256
+            const bool primal = __builtin_amdgcn_readfirstlane((int)primal_w) != 0;
+#else
             const bool primal = __builtin_amdgcn_readfirstlane((int)ctl_[5]) != 0;
+#endif
             for (int e = tid; e < NX; e += T) {
                 if (primal) {
                     double a = W_[(size_t)ks * NX + e];
@@ -1333,4 +1496,5 @@
     DAS_T(7);  // epilogue
     DAS_T_FLUSH();
     LSCQP_DAS_END(kDasSolved);
+#undef DAS_U_CAND
 #undef DAS_CLS

@@ -42,10 +42,14 @@ constexpr bool carve_fits(int M, int dim, int kmax, int stage_rows) {
 // item stays where the scalar-register spills do not grow or a timing pays for the growth.  With three row slots (below) the 2-D form
 // spills 242 with all of them against 245 without and the parent's 251, and c0 runs 7 % faster; the M = 10, 3-D form spilled 301 - 312
 // against 292 with the first three, has not been built with the others, and keeps the text it had.
+// Bits 64 .. 2048 (NOTES section 35) fold LDS round trips that held one or two reads: the empty-interval ballots, the pass's minimum
+// across the wavefronts, `primal` beside the step's decision, a two-sided candidate's stencil and bounds, the candidate's multiplier in
+// a register, the thread's two-sided rows in registers across the loop of steps.  With them the two forms spill 171 and 234 scalar
+// registers (174 and 242 without).  Bit 512 is kept for the headline, not for its own slot: see the section.
 // (-DLSCQP_FUSED_STEP_PATH=<bits> builds a subset: the timing twins of one change.)
 #ifndef LSCQP_FUSED_STEP_PATH
 #if LSCQP_M == 5 || (LSCQP_M == 10 && LSCQP_DIM == 2)
-#define LSCQP_FUSED_STEP_PATH (7 | 8 | 32)
+#define LSCQP_FUSED_STEP_PATH (7 | 8 | 32 | 64 | 128 | 256 | 512 | 1024 | 2048)
 #else
 #define LSCQP_FUSED_STEP_PATH 0
 #endif
