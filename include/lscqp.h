@@ -553,6 +553,30 @@ int lscqp_generate_lsc_obstacles_device(lscqp_handle h, const lscqp_obstacle_par
                                         const lscqp_obstacle* d_obstacles, const double* d_radius, const double* d_goal,
                                         const lscqp_header* d_hdr, lscqp_row* d_rows_out, int32_t n_obs_total, int32_t slot0, void* stream);
 
+/* The rows of non-agent obstacles for the constraint generator constructLSC selects (:551-557), same units, slot remap and row formats as
+ * lscqp_generate_lsc_obstacles_device, selected by `mode`:
+ *   LSCQP_GEN_LSC   lscqp_generate_lsc_obstacles_device itself, argument for argument (the same bits); d_obstacle_goal is ignored
+ *   LSCQP_GEN_CLSC  the non-agent branch of generateCLSC (:659-706): an in-range agent and a dynamic obstacle are treated alike.  Segments
+ *                   m < M-1: the normal of normalVectorBetweenPolys between the agent's initial trajectory and the obstacle's
+ *                   constant-velocity prediction (z of the hull dropped for a tall dynamic obstacle, :1188-1191; no fallback normal: a hull
+ *                   around the origin leaves zero rows) and the reciprocal half margin d_i = (radius + r_own + rel_i . n) / 2 -- against an
+ *                   obstacle that does not do its half, so a CLSC row can let the agent closer than an LSC row would.  Segment M-1: the
+ *                   line segments (predicted last point -> obstacle goal point) and (own last point -> agent goal point) separated by
+ *                   closestPointsBetweenLineSegments, one obstacle point and one margin for all control points.  downwashBetween for a
+ *                   non-agent (:1235-1237), the transform skipped in 2-D (:666-672).  In 2-D the row is the one the 2-D QP and goal LP
+ *                   build from the record (src/traj_optimizer.cpp:414-421): n_z = 0 and b = d + n_x p_x + n_y p_y, whatever z the
+ *                   record's normal and obstacle point have -- on the last segment they have one when the obstacle's goal point lies
+ *                   off the mission's plane, as the origin does at z_2d != 0.  obs_pred_sizes and the velocity guard play no part:
+ *                   of `param` only obs_downwash_threshold is read, and d_hdr may be NULL.
+ *   LSCQP_GEN_BVC   LSCQP_ERR_UNSUPPORTED (generateBVC's non-agent branch is not built); any other mode LSCQP_ERR_INVALID_ARGUMENT
+ *   d_obstacle_goal [..][3]  Obstacle::goal_point per entry of the obstacle table, or NULL = the origin for every obstacle: what the
+ *                   reference's ObstacleGenerator::getObstacle leaves there (include/obstacle.hpp:23, 37-49 never set it).  CLSC only. */
+int lscqp_generate_obstacle_rows_device(lscqp_handle h, int32_t mode, const lscqp_obstacle_param* param, int64_t n_agents, int32_t n_dyn,
+                                        int64_t first_agent, const double* d_traj, const int32_t* d_obstacle_ids,
+                                        const lscqp_obstacle* d_obstacles, const double* d_obstacle_goal, const double* d_radius,
+                                        const double* d_goal, const lscqp_header* d_hdr, lscqp_row* d_rows_out, int32_t n_obs_total, int32_t slot0,
+                                        void* stream);
+
 /* initialTrajPlanningPrevSol / obstaclePredictionWithPrevSol when the simulation step is SHORTER than a segment
  * (multisim_time_step < dt, reference src/traj_planner.cpp:296-306, 413-421): segment 0 of the new initial trajectory :=
  * prev_traj[0].subSegment(fraction, 1) (Segment::subSegment, src/trajectory.cpp:15-49), the other segments are kept.
@@ -1177,11 +1201,14 @@ int lscqp_plan_run(lscqp_plan plan, int64_t max_replans, int32_t check_every, in
  *                            before it is refused) and the reset puts the table at t = 0 and zeroes the clock.  desc.n_obs stays the
  *                            number of row slots per agent: slots [0, n_dyn) are the obstacles in table order, slots [n_dyn, n_obs) the
  *                            in-range agents (the range filter then cuts to the n_obs - n_dyn nearest).  Refused, leaving the plan as
- *                            it was: n_dyn > n_obs (LSCQP_ERR_INVALID_ARGUMENT), constraint_mode != LSCQP_GEN_LSC (LSCQP_ERR_UNSUPPORTED:
- *                            the obstacle rows are generateLSC's), a model lscqp_obstacle_model_prepare refuses.
+ *                            it was: n_dyn > n_obs (LSCQP_ERR_INVALID_ARGUMENT), constraint_mode LSCQP_GEN_BVC (LSCQP_ERR_UNSUPPORTED:
+ *                            the obstacle rows are generateLSC's or generateCLSC's), a model lscqp_obstacle_model_prepare refuses.
  *                            Per replan the chain gains, on its one stream: the advance in front of the prepare step, the obstacle
- *                            rows (lscqp_generate_lsc_obstacles_device over the planning agents' initial trajectories) behind the agent
- *                            rows, and with safety_samples > 0 lscqp_safety_obstacles_device behind the agent safety figures.  A mission
+ *                            rows of the plan's constraint_mode over the planning agents' initial trajectories behind the agent rows
+ *                            (LSCQP_GEN_LSC: lscqp_generate_lsc_obstacles_device; LSCQP_GEN_CLSC: lscqp_generate_obstacle_rows_device
+ *                            in that mode without obstacle goal points, i.e. the origin, as in the reference -- the goal LP reads the
+ *                            last-segment rows of every slot, the obstacles' too), and with safety_samples > 0
+ *                            lscqp_safety_obstacles_device behind the agent safety figures.  A mission
  *                            partition shares the obstacles like the map; every owner of a sharded mission advances its own copy of the
  *                            same table.  The waypoint decision does not see obstacles, as in the reference.  The mission record keeps
  *                            no obstacle figure.

@@ -215,7 +215,7 @@ EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_
                     "lscqp_comm_devices_for", "lscqp_comm_devices_for_class", "lscqp_device_fill", "lscqp_comm_shard", "lscqp_shard_range", "lscqp_exchange_schedule", "lscqp_exchange_schedule_padded", "lscqp_comm_synchronize", "lscqp_solve_batch_sharded",
                     "lscqp_solve_batch_sharded_device", "lscqp_allgather", "lscqp_generate_lsc_device", "lscqp_select_neighbours_device", "lscqp_generate_constraints_device",
                     "lscqp_shift_traj_device", "lscqp_shift_traj_partial_device", "lscqp_generate_constraints_device_ex",
-                    "lscqp_generate_lsc_obstacles_device", "lscqp_generate_lsc_bytes", "lscqp_optimize_goal_device", "lscqp_optimize_goal", "lscqp_validate_step_device", "lscqp_map_create", "lscqp_map_create_from_csv", "lscqp_map_destroy", "lscqp_map_info",
+                    "lscqp_generate_lsc_obstacles_device", "lscqp_generate_obstacle_rows_device", "lscqp_generate_lsc_bytes", "lscqp_optimize_goal_device", "lscqp_optimize_goal", "lscqp_validate_step_device", "lscqp_map_create", "lscqp_map_create_from_csv", "lscqp_map_destroy", "lscqp_map_info",
                     "lscqp_map_download", "lscqp_map_prepare", "lscqp_construct_sfc_device", "lscqp_construct_sfc", "lscqp_safety_metrics_device", "lscqp_safety_obstacles_device",
                     "lscqp_plan_create", "lscqp_plan_destroy", "lscqp_plan_reset", "lscqp_plan_buffer", "lscqp_plan_upload", "lscqp_plan_download",
                     "lscqp_plan_step", "lscqp_plan_step_graph", "lscqp_plan_graph_nodes", "lscqp_plan_group_step", "lscqp_plan_set_grid", "lscqp_plan_grid",
@@ -1294,6 +1294,13 @@ class Solver:
         """generateLSC for non-agent obstacles (param: ObstacleParam; d_obstacles: OBSTACLE_DTYPE table on the device)."""
         _call("lscqp_generate_lsc_obstacles_device", self._h, C.cast(C.byref(param), C.c_void_p), n_agents, n_dyn, first_agent, d_traj, d_ids, d_obstacles,
               d_radius, d_goal, d_hdr, d_rows, int(n_obs_total), int(slot0), stream=stream)
+
+    def generate_obstacle_rows_device(self, mode, param, n_agents, n_dyn, first_agent, d_traj, d_ids, d_obstacles, d_obstacle_goal, d_radius, d_goal,
+                                      d_hdr, d_rows, n_obs_total, slot0, stream=None):
+        """The rows of non-agent obstacles by generator: GEN_LSC is generate_lsc_obstacles_device, GEN_CLSC generateCLSC's non-agent branch
+        (d_obstacle_goal: [table][3] goal points or None = the origin; d_hdr may be None)."""
+        _call("lscqp_generate_obstacle_rows_device", self._h, int(mode), C.cast(C.byref(param), C.c_void_p), n_agents, n_dyn, first_agent, d_traj, d_ids,
+              d_obstacles, d_obstacle_goal, d_radius, d_goal, d_hdr, d_rows, int(n_obs_total), int(slot0), stream=stream)
 
     def obstacles_advance_device(self, d_models, n_dyn, time_step, d_clock, d_obstacles, stream=None):
         """lscqp_obstacles_advance_device: the table moved to the clock's replan, the clock advanced; d_models PREPARED models on the device."""

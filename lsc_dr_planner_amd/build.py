@@ -85,7 +85,8 @@ def units():
         # scratch and LDS into the verbose build's log: the kernel is required to use no scratch)
         ("lscplan.hip", "lscplan", ["-Rpass-analysis=kernel-resource-usage"], None, False),
         ("lscgrid.hip", "lscgrid", [], None, False),
-        ("lscgen.hip", "lscgen", [], None, False),
+        # (the remark: generate_clsc_obstacle_kernel is required to use no scratch)
+        ("lscgen.hip", "lscgen", ["-Rpass-analysis=kernel-resource-usage"], None, False),
         ("lscqp_generic.hip", "lscqp_generic", [], None, False),
         # -ffp-contract=on: a multiply-add is fused where the SOURCE writes a * b + c in one expression and nowhere else.  The default (fast) lets
         # the backend fuse across statements as the surrounding code happens to allow -- the kernel's instantiations (row formats, wavefronts

@@ -629,6 +629,119 @@ __global__ __launch_bounds__(kThreads) void generate_lsc_obstacle_kernel(int M, 
     }
 }
 
+// Trajectory::planConstVelTraj (src/trajectory.cpp:79-91) for an obstacle of the table: position + velocity * (float)time in point3d arithmetic
+__device__ __forceinline__ F3 const_vel_point(const lscqp_obstacle& ob, double time) {
+#pragma clang fp contract(off)
+    const float tf = (float)time;
+    return {(float)ob.position[0] + (float)ob.velocity[0] * tf, (float)ob.position[1] + (float)ob.velocity[1] * tf,
+            (float)ob.position[2] + (float)ob.velocity[2] * tf};
+}
+// downwashBetween for a non-agent (:1235-1237): the agent formula with the planning agent's downwash at 1
+__device__ __forceinline__ double downwash_nonagent(double r_own, const lscqp_obstacle& ob) {
+#pragma clang fp contract(off)
+    return (r_own + ob.downwash * ob.radius) / (r_own + ob.radius);
+}
+
+// generateCLSC for NON-AGENT obstacles (reference src/traj_planner.cpp:659-706): the loop body of generate_lsc_kernel<LSCQP_GEN_CLSC> with the
+// neighbour's shifted plan replaced by the obstacle's constant-velocity prediction (planConstVelTraj as the kernel above forms it: time
+// accumulated in double in steps of dt / 5 from 0), downwashBetween for a non-agent (:1235-1237, never gated by the dimension; the
+// transform itself is skipped in 2-D, :666-672), and the z component of the HULL dropped for tall dynamic obstacles (:1188-1191) -- the
+// margins keep the unflattened differences (:684-685).  Segments m < M-1: reciprocal half margin d_i = (collision_dist + rel_i . n) / 2
+// against the predicted points, no fallback normal (a hull around the origin leaves zero rows).  Segment M-1: the line segments
+// (predicted last point -> obstacle goal point) and (own last point -> agent goal point) are separated (:691-703); goal_obs [table][3] or
+// NULL = the origin, which is what ObstacleGenerator::getObstacle leaves in Obstacle::goal_point.  Neither obs_pred_sizes nor the
+// velocity guard plays a part.  Units, slot remap and store as generate_lsc_obstacle_kernel; the float32 restatements keep their own
+// contraction pragmas and the double tail is written as generate_lsc_kernel writes it, so both kernels round alike.
+__global__ __launch_bounds__(kThreads) void generate_clsc_obstacle_kernel(int M, int dim, double dt, double obs_downwash_threshold, int64_t n_units,
+                                                                          int32_t n_dyn, int64_t first_agent, const double* __restrict__ traj,
+                                                                          const int32_t* __restrict__ ids, const lscqp_obstacle* __restrict__ table,
+                                                                          const double* __restrict__ goal_obs, const double* __restrict__ radius,
+                                                                          const double* __restrict__ goal, int rows_f32, int32_t n_obs_total,
+                                                                          int32_t slot0, lscqp_row* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (t >= n_units) return;
+    const int m = (int)(t % M);
+    const int64_t ao = t / M;
+    const int o = (int)(ao % n_dyn);
+    const int64_t a = ao / n_dyn;
+    const int64_t ga = first_agent + a;
+    const int32_t id = ids[a * n_dyn + o];
+    const int64_t row0 = (((a * n_obs_total) + slot0 + o) * M + m) * 6;
+    double4* o4 = reinterpret_cast<double4*>(out);
+    float4* o4f = reinterpret_cast<float4*>(out);
+    auto put = [&](int i, double4 v) {
+        if (rows_f32)
+            o4f[row0 + i] = float4{(float)v.x, (float)v.y, (float)v.z, (float)v.w};
+        else
+            o4[row0 + i] = v;
+    };
+    if (id < 0) {  // no obstacle in this slot: all-zero rows, which the solver drops (:409-411)
+        for (int i = 0; i < 6; i++) put(i, double4{0, 0, 0, 0});
+        return;
+    }
+    const lscqp_obstacle ob = table[id];
+    const double r_own = radius[ga];
+    const double dw = downwash_nonagent(r_own, ob);
+    const float dwf = (float)dw;
+    const bool tr = dim != 2;
+    const double collision_dist = ob.radius + r_own;  // :661
+    auto own_pt = [&](int mm, int i) -> F3 {
+        const double* p = traj + ((ga * M + mm) * 6 + i) * 3;
+        return F3{(float)p[0], (float)p[1], (float)p[2]};
+    };
+    auto trf = [&](F3 p) -> F3 {
+        if (tr) p.z = p.z / dwf;
+        return p;
+    };
+    F3 nrm = {0, 0, 0};
+    double d[6];
+    F3 pob[6];
+    if (m < M - 1) {
+        double time = 0;
+        for (int s_ = 0; s_ < m * 6; s_++) time += dt / 5;
+        const bool tall = ob.type == 0 && ob.downwash > obs_downwash_threshold;
+        F3 relf[6];
+        P3 rel[6];
+        bool flat = dim == 2 || tall;  // planar search only if every z of the hull is 0 (generateCLSC relies on equal z in 2-D, it does not drop it)
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            pob[i] = const_vel_point(ob, time);
+            time += dt / 5;
+            relf[i] = fsub(trf(own_pt(m, i)), trf(pob[i]));
+            const float hz = tall ? 0.0f : relf[i].z;  // the hull's copy only (:1188-1191)
+            rel[i] = {(double)relf[i].x, (double)relf[i].y, (double)hz};
+            flat = flat && hz == 0.0f;
+        }
+        const P3 cp = hull_closest_point(rel, flat);
+        nrm = fnormalized(F3{(float)cp.x, (float)cp.y, (float)cp.z});  // no fallback normal in generateCLSC: zero rows drop out
+#pragma unroll
+        for (int i = 0; i < 6; i++) d[i] = 0.5 * (collision_dist + fdot(relf[i], nrm));
+    } else {
+        double time = 0;
+        for (int s_ = 0; s_ < M * 6 - 1; s_++) time += dt / 5;
+        const double* gw = goal + 3 * a;
+        F3 go = {0, 0, 0};
+        if (goal_obs) go = F3{(float)goal_obs[3 * (int64_t)id], (float)goal_obs[3 * (int64_t)id + 1], (float)goal_obs[3 * (int64_t)id + 2]};
+        F3 cp1, cp2;
+        const double dist = segseg_closest(trf(const_vel_point(ob, time)), go, trf(own_pt(M - 1, 5)), F3{(float)gw[0], (float)gw[1], (float)gw[2]}, cp1, cp2);
+        nrm = fnormalized(fsub(cp2, cp1));
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            d[i] = 0.5 * (collision_dist + dist);
+            pob[i] = cp1;
+        }
+    }
+    // 2-D: the QP and the goal LP hold n_x (x - p_x) + n_y (y - p_y) >= d and nothing of z (src/traj_optimizer.cpp:414-421), so the packed
+    // row carries n_z = 0 and b stops at the y term.  It matters on the last segment: the obstacle's goal point, the origin, lies off a
+    // plane at z_2d != 0, and the segment-to-segment normal then has a z component that an agent pair, both goals in the plane, never has.
+    const double onx = (double)nrm.x, ony = (double)nrm.y, onz = (dim == 2) ? 0.0 : (double)(float)((double)nrm.z / dw);
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        const double b = d[i] + (onx * (double)pob[i].x + ony * (double)pob[i].y + onz * (double)pob[i].z);  // (onz = 0: the z term adds an exact 0)
+        put(i, double4{onx, ony, onz, b});
+    }
+}
+
 // MultiSyncSimulator::broadcastMsgs (reference src/multi_sync_simulator.cpp:305-352): agent i receives every other agent j
 // with LInfinityDistance(p_i, p_j) <= communication_range (all of them when the range is <= 0), in id order.  One
 // wavefront per local agent: the lanes test 64 candidates at a time, and a ballot + prefix population count compacts the
@@ -903,6 +1016,45 @@ extern "C" int lscqp_generate_lsc_obstacles_device(lscqp_handle h, const lscqp_o
                        *param, n_units, n_dyn, first_agent, d_traj, d_obstacle_ids, d_obstacles, d_radius, d_goal, d_hdr, rows_f32_of(h), n_obs_total,
                        slot0, binv3, d_rows_out);
     return lscqp_launch_result_(hipGetLastError());
+}
+
+// (library-internal: the entry below, and the tests for M = 1, which no handle admits) one launch of generate_clsc_obstacle_kernel, no checks
+extern "C" int lscqp_generate_clsc_obstacles_raw_(int M, int dim, double dt, double obs_downwash_threshold, int64_t n_agents, int32_t n_dyn,
+                                                  int64_t first_agent, const double* d_traj, const int32_t* d_obstacle_ids,
+                                                  const lscqp_obstacle* d_obstacles, const double* d_obstacle_goal, const double* d_radius,
+                                                  const double* d_goal, int rows_f32, int32_t n_obs_total, int32_t slot0, lscqp_row* d_rows_out,
+                                                  void* stream) {
+    const int64_t n_units = n_agents * (int64_t)n_dyn * M;
+    if (n_units == 0) return LSCQP_OK;
+    const unsigned blocks = (unsigned)((n_units + lscgen::kThreads - 1) / lscgen::kThreads);
+    hipLaunchKernelGGL(lscgen::generate_clsc_obstacle_kernel, dim3(blocks), dim3(lscgen::kThreads), 0, (hipStream_t)stream, M, dim, dt,
+                       obs_downwash_threshold, n_units, n_dyn, first_agent, d_traj, d_obstacle_ids, d_obstacles, d_obstacle_goal, d_radius, d_goal,
+                       rows_f32, n_obs_total, slot0, d_rows_out);
+    return lscqp_launch_result_(hipGetLastError());
+}
+
+// The non-agent branch of constructLSC (:551-557) by mode: generateLSC's is the entry above, argument for argument; generateCLSC's is
+// generate_clsc_obstacle_kernel, which reads obs_downwash_threshold of `param` only and no header
+extern "C" int lscqp_generate_obstacle_rows_device(lscqp_handle h, int32_t mode, const lscqp_obstacle_param* param, int64_t n_agents, int32_t n_dyn,
+                                                   int64_t first_agent, const double* d_traj, const int32_t* d_obstacle_ids,
+                                                   const lscqp_obstacle* d_obstacles, const double* d_obstacle_goal, const double* d_radius,
+                                                   const double* d_goal, const lscqp_header* d_hdr, lscqp_row* d_rows_out, int32_t n_obs_total,
+                                                   int32_t slot0, void* stream) {
+    if (!h || !param) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_agents < 0 || n_dyn < 0 || first_agent < 0 || slot0 < 0 || n_obs_total < slot0 + n_dyn)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes (n_obs_total >= slot0 + n_dyn required)");
+    if (mode == LSCQP_GEN_BVC)
+        return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_generate_obstacle_rows_device: no LSCQP_GEN_BVC rows for non-agent obstacles (generateBVC's non-agent branch is not built)");
+    if (mode != LSCQP_GEN_LSC && mode != LSCQP_GEN_CLSC) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "mode must be LSCQP_GEN_LSC or LSCQP_GEN_CLSC");
+    if (mode == LSCQP_GEN_LSC)
+        return lscqp_generate_lsc_obstacles_device(h, param, n_agents, n_dyn, first_agent, d_traj, d_obstacle_ids, d_obstacles, d_radius, d_goal, d_hdr,
+                                                   d_rows_out, n_obs_total, slot0, stream);
+    const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
+    if (n_agents == 0 || n_dyn == 0) return LSCQP_OK;
+    if (!d_traj || !d_obstacle_ids || !d_obstacles || !d_radius || !d_goal || !d_rows_out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
+    return lscqp_generate_clsc_obstacles_raw_(cd->M, cd->dim, cd->dt, param->obs_downwash_threshold, n_agents, n_dyn, first_agent, d_traj, d_obstacle_ids,
+                                              d_obstacles, d_obstacle_goal, d_radius, d_goal, rows_f32_of(h), n_obs_total, slot0, d_rows_out, stream);
 }
 
 extern "C" int lscqp_shift_traj_device(lscqp_handle h, int64_t n, int32_t shift_segments, double z_2d, const double* d_x_prev, double* d_traj,

@@ -23,8 +23,9 @@
 // evaluation sets pair them) swaps two things and adds no node: its corridor node is the worlds launch, every agent tested against the map
 // of its mission, and its grid starts each mission's occupancy from that world's base.
 // A plan with dynamic obstacles (lscqp_plan_set_obstacles) gains three nodes: the obstacles' motion (lscobstacle.hip) in front of `prepare`, their
-// rows (generateLSC's non-agent branch) behind the agents' rows -- they take the first row slots of every agent -- and the obstacle leg of the
-// safety figures behind the agents'.  ObstacleGenerator::update(t, 0) -> obstacle_advance_kernel, src/multi_sync_simulator.cpp:311.
+// rows (the non-agent branch of generateLSC or of generateCLSC, by the plan's constraint_mode; a BVC plan takes no obstacles) behind the agents'
+// rows -- they take the first row slots of every agent -- and the obstacle leg of the safety figures behind the agents'.
+// ObstacleGenerator::update(t, 0) -> obstacle_advance_kernel, src/multi_sync_simulator.cpp:311.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -354,9 +355,13 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     if (n_nbr > 0)
         PLAN_TRY(lscqp_generate_constraints_own_(h, p->d.constraint_mode, s.n_agents, n_nbr, s.first_agent, p->traj, p->own, p->nbr, p->radius,
                                                  p->downwash, goal, rows, s.n_obs, n_dyn, stream));
-    // the obstacles' rows (generateLSC's non-agent branch) over the planning agents' INITIAL trajectories: `own`, indexed by local id like
-    // the radii, goals and headers handed over here -- `traj` holds the agents' predictions as each other's obstacles by now
-    if (n_dyn > 0)
+    // the obstacles' rows (the non-agent branch of the plan's generator) over the planning agents' INITIAL trajectories: `own`, indexed by
+    // local id like the radii, goals and headers handed over here -- `traj` holds the agents' predictions as each other's obstacles by now.
+    // generateCLSC's rows take no obstacle goal points: Obstacle::goal_point is the origin in the reference (include/obstacle.hpp:23, 37-49)
+    if (n_dyn > 0 && p->d.constraint_mode == LSCQP_GEN_CLSC)
+        PLAN_TRY(lscqp_generate_obstacle_rows_device(h, LSCQP_GEN_CLSC, &p->obs_param, s.n_agents, n_dyn, 0, p->own, p->obs_ids, p->obs_table, nullptr,
+                                                     p->radius + s.first_agent, goal + s.first_agent * 3, nullptr, rows, s.n_obs, 0, stream));
+    else if (n_dyn > 0)
         PLAN_TRY(lscqp_generate_lsc_obstacles_device(h, &p->obs_param, s.n_agents, n_dyn, 0, p->own, p->obs_ids, p->obs_table, p->radius + s.first_agent,
                                                      goal + s.first_agent * 3, hdr, rows, s.n_obs, 0, stream));
     if (p->d.optimize_goal) {  // (the goal LP's kernel finishes the headers itself: one node less)
@@ -1057,8 +1062,8 @@ int lscqp_plan_set_obstacles(lscqp_plan p, const lscqp_obstacle_param* param, in
         if (!param) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacles: null param");
         if (n_dyn > p->s.n_obs)
             return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacles: n_dyn exceeds the plan's row slots per agent (n_dyn <= desc.n_obs required)");
-        if (p->d.constraint_mode != LSCQP_GEN_LSC)
-            return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_plan_set_obstacles: constraint_mode must be LSCQP_GEN_LSC (the obstacle rows are generateLSC's)");
+        if (p->d.constraint_mode != LSCQP_GEN_LSC && p->d.constraint_mode != LSCQP_GEN_CLSC)
+            return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_plan_set_obstacles: constraint_mode must be LSCQP_GEN_LSC or LSCQP_GEN_CLSC (generateBVC's obstacle rows are not built)");
         prepared.assign(models, models + n_dyn);
         PLAN_TRY(lscqp_obstacle_model_prepare(prepared.data(), n_dyn));
     }

@@ -3,8 +3,9 @@
 // then fails to compile instead of linking and passing garbage.  api.py reads the prototypes of the entries its wrappers call
 // (lscqp_optimize_goal_fin_device_, lscqp_commit_validate_raw_, lscqp_debug_*_) from this text.
 // A public device entry is DEFINED in the unit that owns its kernel, checks in front of the launch; no `_raw_` half of it is declared here.
-// The three `_raw_` functions that remain have a caller besides their own public entry: lscqp_generate_lsc_raw_ (four generator entries, the
-// tests for M = 1), lscqp_commit_validate_raw_ (lscplan.hip, api.py) and lscqp_map_raw_ (lscgrid.hip).
+// The four `_raw_` functions that remain have a caller besides their own public entry: lscqp_generate_lsc_raw_ (four generator entries, the
+// tests for M = 1), lscqp_generate_clsc_obstacles_raw_ (the tests for M = 1), lscqp_commit_validate_raw_ (lscplan.hip, api.py) and
+// lscqp_map_raw_ (lscgrid.hip).
 #ifndef LSCQP_INTERNAL_HPP
 #define LSCQP_INTERNAL_HPP
 
@@ -88,6 +89,12 @@ int lscqp_generate_lsc_raw_(int mode, int M, int dim, int64_t n_agents, int32_t 
                             const double* d_traj, const double* d_own_traj, const int32_t* d_neighbours, const double* d_radius,
                             const double* d_downwash, const double* d_goal, const double* d_goal_all, int rows_f32,
                             int32_t n_obs_total, int32_t slot0, lscqp_row* d_rows_out, void* stream);
+// (library-internal: lscqp_generate_obstacle_rows_device, and the tests for M = 1) one launch of generateCLSC's non-agent rows, no checks
+int lscqp_generate_clsc_obstacles_raw_(int M, int dim, double dt, double obs_downwash_threshold, int64_t n_agents, int32_t n_dyn,
+                                       int64_t first_agent, const double* d_traj, const int32_t* d_obstacle_ids,
+                                       const lscqp_obstacle* d_obstacles, const double* d_obstacle_goal, const double* d_radius,
+                                       const double* d_goal, int rows_f32, int32_t n_obs_total, int32_t slot0, lscqp_row* d_rows_out,
+                                       void* stream);
 // (library-internal, lscplan.hip) lscqp_generate_constraints_device_ex with the planning agents' initial trajectories kept apart from
 // the predicted trajectories of the agents as obstacles: d_own_traj [n_agents][M][6][3], NULL = rows d_traj[first_agent + a]
 int lscqp_generate_constraints_own_(lscqp_handle h, int32_t mode, int64_t n_agents, int32_t n_obs, int64_t first_agent,

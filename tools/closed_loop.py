@@ -161,14 +161,15 @@ def load_obstacles(path):
 
 
 def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=0, graph=True, until_finished=None, check_every=16,
-                 goal_threshold=0.1, obstacles=None, worlds=None):
+                 goal_threshold=0.1, obstacles=None, worlds=None, obstacle_rows="lsc"):
     """`missions` seeded missions over one world flown by ONE lscqp_plan with a mission partition (include/lscqp.h, "many missions over one
     map"): waypoint_mode 1, closed loop, one captured graph per replan.  The summary has the figures of `run` per mission.
     until_finished = MAX: the plan keeps a mission record (include/lscqp.h, "the mission record") and lscqp_plan_run flies it until every
     mission has finished or MAX replans, with no download in between; per mission the summary then holds the device's record.
     obstacles: api.OBSTACLE_MODEL_DTYPE records (load_obstacles) -- the dynamic obstacles every mission shares, moved by the chain itself
-    (lscqp_plan_set_obstacles).  Their rows are generateLSC's, so the agents' rows are LSC rows too (GEN_LSC instead of GEN_CLSC), and
-    they take the first row slots: n_obs counts the agent slots, the plan gets n_obs + len(obstacles).
+    (lscqp_plan_set_obstacles).  obstacle_rows "lsc": their rows are generateLSC's, so the agents' rows are LSC rows too (GEN_LSC instead
+    of GEN_CLSC); "clsc": the plan stays in GEN_CLSC, the mode the reference's launch files run, and the obstacles get generateCLSC's rows
+    like an in-range agent.  They take the first row slots: n_obs counts the agent slots, the plan gets n_obs + len(obstacles).
     worlds: one world per mission (load_worlds) in the world's box -- mission k flies over world k (include/lscqp.h, "each mission over its
     own world"; lscqp_plan_set_worlds), its seeded agents drawn from the free nodes of its own world; world 0 replaces the world's own boxes."""
     world_boxes = None if worlds is None else load_worlds(worlds, missions)  # (before anything needs a device)
@@ -191,11 +192,13 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
         _, starts, goals = seeded_missions(g, probe.download(), probe.grid_min, missions, seed)
     probe.close()
     N = int(off[-1])
+    if obstacle_rows not in ("lsc", "clsc"):
+        raise ValueError("obstacle_rows must be 'lsc' or 'clsc'")
     n_dyn = 0 if obstacles is None else len(obstacles)
     n_obs = max(1, min((n - 1 if n_obs is None else n_obs) + n_dyn, sol.max_obstacles()))
     ag = np.zeros(N, api.AGENT_PARAM_DTYPE)
     ag["radius"], ag["downwash"], ag["max_vel"], ag["max_acc"], ag["nominal_velocity"] = g["radius"], 2.0, 1.0, 2.0, 1.0
-    plan = api.Plan(sol, wmap, N, n_obs, ag, constraint_mode=api.GEN_LSC if n_dyn else api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, optimize_goal=True,
+    plan = api.Plan(sol, wmap, N, n_obs, ag, constraint_mode=api.GEN_LSC if n_dyn and obstacle_rows == "lsc" else api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, optimize_goal=True,
                     closed_loop=True, z_2d=float(g["z_2d"]), safety_samples=2, record_time_step=0.1, waypoint_mode=api.WAYPOINT_GRID_PIBT,
                     mission_offsets=off)
     world_set = None
@@ -272,7 +275,7 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
 
 
 def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None, router="host", missions=None,
-        decision="one", until_finished=None, obstacles=None, worlds=None):
+        decision="one", until_finished=None, obstacles=None, worlds=None, obstacle_rows="lsc"):
     """script (optional): {"waypoint": (K, N, 3), "state": (K, N, 9)} -- replay of a recorded mission: replan k takes every agent's
     state and waypoint from the script instead of the loop's own step / router (the plans, goal points, corridors and neighbour sets are
     still the loop's own), and the result carries every replan's solution (`x`, (K, N, nv)) and goal point (`goal`, (K, N, 3)).
@@ -281,7 +284,8 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
     decision (router "device"): "one" (lscqp_waypoints_device), "wide" (lscqp_waypoints_wide_device) or "auto" (wide from
     DECISION_AUTO_MIN_AGENTS agents on); the flight is the same whichever is chosen.
     until_finished (with missions): fly until every mission has finished, at most that many replans (run_missions).
-    obstacles (with missions): dynamic obstacles flown by the plan's own chain (load_obstacles, run_missions).
+    obstacles (with missions): dynamic obstacles flown by the plan's own chain (load_obstacles, run_missions); obstacle_rows "lsc" or "clsc":
+    the generator of their rows, and with it the plan's constraint mode (run_missions).
     worlds (with missions): one world per mission -- a directory of world CSVs, a list of CSV paths or of box lists (load_worlds, run_missions)."""
     if router not in ("host", "device"):
         raise ValueError("router must be 'host' or 'device'")
@@ -295,7 +299,7 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
         raise ValueError("worlds need missions=K: world k belongs to mission k of an lscqp_plan (lscqp_plan_set_worlds)")
     if missions:
         return run_missions(world_json, int(missions), steps=steps, M=M, dt=dt, n_obs=n_obs, until_finished=until_finished, obstacles=obstacles,
-                            worlds=worlds)
+                            worlds=worlds, obstacle_rows=obstacle_rows)
     import torch
 
     from lsc_dr_planner_amd import api
@@ -500,6 +504,9 @@ if __name__ == "__main__":
     ap.add_argument("--obstacles", default=None, metavar="FILE.json",
                     help="with --missions K: the dynamic obstacles of a reference mission file (its \"obstacles\" list, or a bare list: type, start, goal, "
                          "waypoints, axis, size, speed, max_acc, downwash), shared by every mission and moved by the plan's chain")
+    ap.add_argument("--obstacle-rows", default="lsc", choices=("lsc", "clsc"),
+                    help="with --obstacles: lsc = generateLSC's rows for obstacles and agents alike (the plan flies GEN_LSC); clsc = the plan keeps "
+                         "GEN_CLSC, the reference's launch mode, and the obstacles get generateCLSC's rows")
     ap.add_argument("--worlds", default=None, nargs="+", metavar="CSV",
                     help="with --missions K: K world CSVs (or one directory holding K) in the world's box -- mission k flies over world k, as "
                          "launch/test_all_*.launch pair a mission directory with a world directory")
@@ -507,4 +514,5 @@ if __name__ == "__main__":
     a = ap.parse_args()
     world = random_forest_world(a.forest) if a.forest > 0 else a.world
     print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router, missions=a.missions, decision=a.decision,
-                         until_finished=a.until_finished, obstacles=load_obstacles(a.obstacles) if a.obstacles else None, worlds=a.worlds)))
+                         until_finished=a.until_finished, obstacles=load_obstacles(a.obstacles) if a.obstacles else None, worlds=a.worlds,
+                         obstacle_rows=a.obstacle_rows)))
