@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/lscqp.h"
+#include "lscqp_device.hpp"
 #include "lscqp_missions.hpp"
 #include "lscqp_internal.hpp"
 
@@ -868,36 +869,34 @@ struct lscqp_grid_s {
     double radius = 0, gmin[3] = {0, 0, 0};
     int dims[3] = {0, 0, 0};
     int device = 0;
-    uint8_t *d_occ = nullptr, *d_occ_mission = nullptr;
+    lscqp::dev_ptr<uint8_t> d_occ, d_occ_mission;
     int64_t reserved = 0;
-    int32_t* d_agent_scratch = nullptr;  // 11 arrays, the candidate ones five wide
-    int32_t* d_tables = nullptr;         // now, next, status
+    lscqp::dev_ptr<int32_t> d_agent_scratch;  // 11 arrays, the candidate ones five wide
+    lscqp::dev_ptr<int32_t> d_tables;         // now, next, status
     lscgrid::Scratch s;
     // a mission partition (lscqp_grid_reserve_missions_): one occupancy copy and one status word per mission, and where the node tables do
     // not fit in LDS one slab of them per mission
     int missions = 0;
-    uint8_t* d_occ_k = nullptr;     // [missions][nodes]
-    int32_t* d_status_k = nullptr;  // [missions]
-    int32_t* d_tables_k = nullptr;  // [missions][2][nodes], all zero between launches
+    lscqp::dev_ptr<uint8_t> d_occ_k;     // [missions][nodes]
+    lscqp::dev_ptr<int32_t> d_status_k;  // [missions]
+    lscqp::dev_ptr<int32_t> d_tables_k;  // [missions][2][nodes], all zero between launches
     std::vector<int64_t> fields_off;  // the partition of the last lscqp_grid_fields_missions_device: the one the copies were cleared for
     // a base occupancy per world (lscqp_grid_set_worlds): mission k's copy starts from base k; 0 = the one base d_occ
     int worlds = 0;
-    uint8_t* d_occ_w = nullptr;  // [worlds][nodes]
+    lscqp::dev_ptr<uint8_t> d_occ_w;  // [worlds][nodes]
     // the wide form of the decision (lscqp_grid_reserve_wide)
     int64_t wide_reserved = 0;
-    void* d_wide = nullptr;
+    lscqp::dev_ptr<char> d_wide;
     lscgrid::Wide w;
 };
 
 namespace {
 
-int grid_hip_fail(hipError_t e, const char* what) {
-    return lscqp_set_error_(LSCQP_ERR_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-#define GRID_HIP(call)                                     \
-    do {                                                   \
-        const hipError_t e_ = (call);                      \
-        if (e_ != hipSuccess) return grid_hip_fail(e_, #call); \
+// a failed call answers with its own text; an allocation (lscqp::dev_alloc) names the hipMalloc it makes in the same way
+#define GRID_HIP(call)                                            \
+    do {                                                          \
+        const hipError_t e_ = (call);                             \
+        if (e_ != hipSuccess) return lscqp::hip_fail(e_, #call);  \
     } while (0)
 
 constexpr int64_t kPerAgentInts = 9 + 2 * 5;  // cur, vnext, order, stack, label, blocker, keep, onnode, gsize + cand[5], cost[5]
@@ -977,47 +976,34 @@ int lscqp_grid_create(lscqp_map map, const lscqp_grid_desc* desc, lscqp_grid* ou
     if (hipGetDevice(&cur_dev) != hipSuccess) return lscqp_set_error_(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
     if (mdev != cur_dev) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the map lives on another device than the current one");
     const double wmin_d[3] = {wmin[0], wmin[1], wmin[2]}, wmax_d[3] = {wmax[0], wmax[1], wmax[2]};  // (mission.world_min / _max are point3d)
-    lscqp_grid_s* g = new lscqp_grid_s();
-    int rc = lscqp_grid_shape(wmin_d, wmax_d, desc->resolution, 2, desc->z_2d, g->gmin, g->dims);
-    if (rc == LSCQP_OK && (int64_t)g->dims[0] * g->dims[1] > (int64_t)1 << 26) rc = lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "more than 2^26 grid nodes");
-    if (rc != LSCQP_OK) {
-        delete g;
-        return rc;
-    }
+    std::unique_ptr<lscqp_grid_s> g(new lscqp_grid_s());
+    if (const int rc = lscqp_grid_shape(wmin_d, wmax_d, desc->resolution, 2, desc->z_2d, g->gmin, g->dims)) return rc;
+    if ((int64_t)g->dims[0] * g->dims[1] > (int64_t)1 << 26) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "more than 2^26 grid nodes");
     g->device = cur_dev;
     g->radius = desc->radius;
     g->v = lscgrid::View{g->gmin[0], g->gmin[1], desc->resolution, desc->z_2d, g->dims[0], g->dims[1]};
     const lscgrid::MapRaw mraw{res, key0[0], key0[1], key0[2], mdims[0], mdims[1], mdims[2], nearest};  // (read by the occupancy kernel below and not kept: the grid outlives its map)
     const int nodes = g->dims[0] * g->dims[1];
-    hipError_t e = hipMalloc((void**)&g->d_occ, (size_t)nodes);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->d_occ_mission, (size_t)nodes);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->d_tables, ((size_t)2 * nodes + 4) * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemset(g->d_tables, 0, ((size_t)2 * nodes + 4) * sizeof(int32_t));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(lscgrid::occupancy_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, (hipStream_t)0, g->v, mraw, g->radius, g->d_occ);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(g->d_occ_mission, g->d_occ, (size_t)nodes, hipMemcpyDeviceToDevice);
+    const char* const what = "lscqp_grid_create";
+    if (const int rc = lscqp::dev_alloc(g->d_occ, (size_t)nodes, what)) return rc;
+    if (const int rc = lscqp::dev_alloc(g->d_occ_mission, (size_t)nodes, what)) return rc;
+    if (const int rc = lscqp::dev_alloc(g->d_tables, (size_t)2 * nodes + 4, what, true)) return rc;
+    hipLaunchKernelGGL(lscgrid::occupancy_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, (hipStream_t)0, g->v, mraw, g->radius, g->d_occ.get());
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(g->d_occ_mission.get(), g->d_occ.get(), (size_t)nodes, hipMemcpyDeviceToDevice);
     // (the LDS form of the field kernel may ask for more than the 64 KB a kernel gets by default)
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lscgrid::fields_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lscgrid::kLdsNodes * 2);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        lscqp_grid_destroy(g);
-        return grid_hip_fail(e, "lscqp_grid_create");
-    }
-    *out = g;
+    if (e != hipSuccess) return lscqp::hip_fail(e, what);
+    *out = g.release();
     return LSCQP_OK;
 }
 
 void lscqp_grid_destroy(lscqp_grid g) {
     if (!g) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) == hipSuccess && prev != g->device) (void)hipSetDevice(g->device);
+    lscqp::OnDevice on(g->device);
     (void)hipDeviceSynchronize();
-    for (void* p : {(void*)g->d_occ, (void*)g->d_occ_mission, (void*)g->d_agent_scratch, (void*)g->d_tables, (void*)g->d_occ_k, (void*)g->d_status_k, (void*)g->d_tables_k, g->d_wide, (void*)g->d_occ_w})
-        if (p) (void)hipFree(p);
-    if (prev >= 0 && prev != g->device) (void)hipSetDevice(prev);
     delete g;
 }
 
@@ -1029,19 +1015,19 @@ int lscqp_grid_info(lscqp_grid g, double* grid_min, int32_t* dims) {
 
 int lscqp_grid_download(lscqp_grid g, uint8_t* occ) {
     if (!g || !occ) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
-    GRID_HIP(hipMemcpy(occ, g->d_occ, (size_t)g->dims[0] * g->dims[1], hipMemcpyDeviceToHost));
+    GRID_HIP(hipMemcpy(occ, g->d_occ.get(), (size_t)g->dims[0] * g->dims[1], hipMemcpyDeviceToHost));
     return LSCQP_OK;
 }
 
 int lscqp_grid_download_mission(lscqp_grid g, uint8_t* occ) {
     if (!g || !occ) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
-    GRID_HIP(hipMemcpy(occ, g->d_occ_mission, (size_t)g->dims[0] * g->dims[1], hipMemcpyDeviceToHost));
+    GRID_HIP(hipMemcpy(occ, g->d_occ_mission.get(), (size_t)g->dims[0] * g->dims[1], hipMemcpyDeviceToHost));
     return LSCQP_OK;
 }
 
 int lscqp_grid_status(lscqp_grid g, int32_t* status_out) {
     if (!g || !status_out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
-    GRID_HIP(hipMemcpy(status_out, g->d_tables + (size_t)2 * g->dims[0] * g->dims[1], sizeof(int32_t), hipMemcpyDeviceToHost));
+    GRID_HIP(hipMemcpy(status_out, g->d_tables.get() + (size_t)2 * g->dims[0] * g->dims[1], sizeof(int32_t), hipMemcpyDeviceToHost));
     return LSCQP_OK;
 }
 
@@ -1050,19 +1036,17 @@ int lscqp_grid_reserve(lscqp_grid g, int64_t n) {
     if (n > ((int64_t)1 << 24)) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "more than 2^24 agents");
     if (n > g->reserved) {
         GRID_HIP(hipDeviceSynchronize());
-        if (g->d_agent_scratch) GRID_HIP(hipFree(g->d_agent_scratch));
-        g->d_agent_scratch = nullptr;
         g->reserved = 0;
-        GRID_HIP(hipMalloc((void**)&g->d_agent_scratch, (size_t)n * kPerAgentInts * sizeof(int32_t)));
+        if (const int rc = lscqp::dev_alloc(g->d_agent_scratch, (size_t)n * kPerAgentInts, "hipMalloc((void**)&g->d_agent_scratch, (size_t)n * kPerAgentInts * sizeof(int32_t))")) return rc;
         g->reserved = n;
     }
-    int32_t* b = g->d_agent_scratch;
+    int32_t* b = g->d_agent_scratch.get();
     const int64_t r = g->reserved;
     lscgrid::Scratch& s = g->s;
     s.cur = b, s.vnext = b + r, s.order = b + 2 * r, s.stack = b + 3 * r, s.label = b + 4 * r, s.blocker = b + 5 * r, s.keep = b + 6 * r;
     s.onnode = b + 7 * r, s.gsize = b + 8 * r, s.cand = b + 9 * r, s.cost = b + 14 * r;
     const int64_t nodes = (int64_t)g->dims[0] * g->dims[1];
-    s.now = g->d_tables, s.next = g->d_tables + nodes, s.status = g->d_tables + 2 * nodes;
+    s.now = g->d_tables.get(), s.next = s.now + nodes, s.status = s.now + 2 * nodes;
     return LSCQP_OK;
 }
 
@@ -1074,11 +1058,11 @@ int lscqp_grid_fields_device(lscqp_grid g, int64_t n, const double* d_start_poin
     if (n == 0) return LSCQP_OK;
     hipStream_t st = (hipStream_t)stream;
     const int nodes = g->dims[0] * g->dims[1];
-    GRID_HIP(hipMemcpyAsync(g->d_occ_mission, g->d_occ, (size_t)nodes, hipMemcpyDeviceToDevice, st));
-    GRID_HIP(hipMemsetAsync(g->d_tables + (size_t)2 * nodes, 0, 4 * sizeof(int32_t), st));  // a new mission: the status word starts at 0
-    hipLaunchKernelGGL(lscgrid::clear_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, d_start_points, d_goal_points, g->d_occ_mission,
+    GRID_HIP(hipMemcpyAsync(g->d_occ_mission.get(), g->d_occ.get(), (size_t)nodes, hipMemcpyDeviceToDevice, st));
+    GRID_HIP(hipMemsetAsync(g->d_tables.get() + (size_t)2 * nodes, 0, 4 * sizeof(int32_t), st));  // a new mission: the status word starts at 0
+    hipLaunchKernelGGL(lscgrid::clear_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, d_start_points, d_goal_points, g->d_occ_mission.get(),
                        (const int64_t*)nullptr, 0);
-    launch_fields(g, n, g->d_occ_mission, d_start_points, d_goal_points, d_field, d_init_d, nullptr, 0, st);
+    launch_fields(g, n, g->d_occ_mission.get(), d_start_points, d_goal_points, d_field, d_init_d, nullptr, 0, st);
     GRID_HIP(hipGetLastError());
     return LSCQP_OK;
 }
@@ -1099,7 +1083,7 @@ int lscqp_waypoints_device(lscqp_grid g, double communication_range, int32_t M, 
     }
     hipStream_t st = (hipStream_t)stream;
     const int nodes = g->dims[0] * g->dims[1];
-    hipLaunchKernelGGL(lscgrid::gather_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, communication_range, g->d_occ_mission, d_waypoint, d_field, g->s,
+    hipLaunchKernelGGL(lscgrid::gather_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, communication_range, g->d_occ_mission.get(), d_waypoint, d_field, g->s,
                        (const int64_t*)nullptr, 0);
     const size_t table_bytes = (size_t)2 * nodes * sizeof(int32_t);
     const int in_lds = table_bytes <= (size_t)lscgrid::kTableLdsBytes;
@@ -1118,14 +1102,13 @@ int lscqp_grid_reserve_wide(lscqp_grid g, int64_t n) {
     }
     if (n <= g->wide_reserved) return LSCQP_OK;
     GRID_HIP(hipDeviceSynchronize());
-    if (g->d_wide) GRID_HIP(hipFree(g->d_wide));
-    g->d_wide = nullptr;
     g->wide_reserved = 0;
     const size_t r = (size_t)n, cells = 2 * r + 17;
     const size_t ints = 3 * r + 3 * cells + 24 * r + 4;
-    GRID_HIP(hipMalloc(&g->d_wide, r * sizeof(float4) + r * sizeof(uint64_t) + ints * sizeof(int32_t)));
+    if (const int rc = lscqp::dev_alloc(g->d_wide, r * sizeof(float4) + r * sizeof(uint64_t) + ints * sizeof(int32_t),
+                              "hipMalloc(&g->d_wide, r * sizeof(float4) + r * sizeof(uint64_t) + ints * sizeof(int32_t))")) return rc;
     lscgrid::Wide& w = g->w;
-    w.sorted = (float4*)g->d_wide;
+    w.sorted = (float4*)g->d_wide.get();
     w.keys = (uint64_t*)(w.sorted + r);
     int32_t* b = (int32_t*)(w.keys + r);
     w.segstart = b, w.fill = b + r, w.grouplist = b + 2 * r;
@@ -1156,7 +1139,7 @@ int lscqp_waypoints_wide_device(lscqp_grid g, double communication_range, int32_
     const dim3 per_agent((unsigned)((n + 255) / 256)), b256(256);
     const lscgrid::Scratch& s = g->s;
     const lscgrid::Wide& w = g->w;
-    hipLaunchKernelGGL(lscgrid::gather_kernel<false>, per_agent, b256, 0, st, g->v, n, range, g->d_occ_mission, d_waypoint, d_field, s, (const int64_t*)nullptr, 0);
+    hipLaunchKernelGGL(lscgrid::gather_kernel<false>, per_agent, b256, 0, st, g->v, n, range, g->d_occ_mission.get(), d_waypoint, d_field, s, (const int64_t*)nullptr, 0);
     if (range > 0) {
         // the cell side: the range and a margin for the rounding of the float32 subtraction in the test, enlarged until 2 n + 16 cells cover the
         // grid's box (positions outside fall into the edge cells)
@@ -1191,18 +1174,15 @@ int lscqp_grid_reserve_missions_(lscqp_grid g, int64_t n, int32_t n_missions) {
     if (n_missions <= g->missions) return LSCQP_OK;
     const size_t nodes = (size_t)g->dims[0] * g->dims[1], K = (size_t)n_missions;
     GRID_HIP(hipDeviceSynchronize());
-    for (void** p : {(void**)&g->d_occ_k, (void**)&g->d_status_k, (void**)&g->d_tables_k}) {
-        if (*p) GRID_HIP(hipFree(*p));
-        *p = nullptr;
-    }
+    g->d_occ_k.reset(), g->d_status_k.reset(), g->d_tables_k.reset();
     g->missions = 0;
     g->fields_off.clear();  // (the copies are gone)
-    GRID_HIP(hipMalloc((void**)&g->d_occ_k, K * nodes));
-    GRID_HIP(hipMalloc((void**)&g->d_status_k, K * sizeof(int32_t)));
-    GRID_HIP(hipMemset(g->d_status_k, 0, K * sizeof(int32_t)));
+    if (const int rc = lscqp::dev_alloc(g->d_occ_k, K * nodes, "hipMalloc((void**)&g->d_occ_k, K * nodes)")) return rc;
+    if (const int rc = lscqp::dev_alloc(g->d_status_k, K, "hipMalloc((void**)&g->d_status_k, K * sizeof(int32_t))")) return rc;
+    GRID_HIP(hipMemset(g->d_status_k.get(), 0, K * sizeof(int32_t)));
     if (!tables_fit_lds(g)) {
-        GRID_HIP(hipMalloc((void**)&g->d_tables_k, K * 2 * nodes * sizeof(int32_t)));
-        GRID_HIP(hipMemset(g->d_tables_k, 0, K * 2 * nodes * sizeof(int32_t)));
+        if (const int rc = lscqp::dev_alloc(g->d_tables_k, K * 2 * nodes, "hipMalloc((void**)&g->d_tables_k, K * 2 * nodes * sizeof(int32_t))")) return rc;
+        GRID_HIP(hipMemset(g->d_tables_k.get(), 0, K * 2 * nodes * sizeof(int32_t)));
     }
     g->missions = n_missions;
     return LSCQP_OK;
@@ -1213,17 +1193,8 @@ int lscqp_grid_reserve_missions_(lscqp_grid g, int64_t n, int32_t n_missions) {
 int lscqp_grid_set_worlds(lscqp_grid g, lscqp_worlds worlds) {
     if (!g) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null grid");
     if (const int rc = lscqp_need_device_()) return rc;
-    struct OnDevice {  // the grid's device made current while its bases are allocated, written and waited for
-        int prev = -1;
-        explicit OnDevice(int dev) {
-            if (hipGetDevice(&prev) != hipSuccess || prev == dev) prev = -1;
-            else (void)hipSetDevice(dev);
-        }
-        ~OnDevice() {
-            if (prev >= 0) (void)hipSetDevice(prev);
-        }
-    } on(g->device);
-    uint8_t* fresh = nullptr;
+    lscqp::OnDevice on(g->device);  // (current while the bases are allocated, written and waited for)
+    lscqp::dev_ptr<uint8_t> fresh;
     int K = 0;
     if (worlds) {
         K = lscqp_worlds_count_(worlds);
@@ -1243,22 +1214,18 @@ int lscqp_grid_set_worlds(lscqp_grid g, lscqp_worlds worlds) {
                 if (rc != LSCQP_OK) return rc;
                 if (gmin[0] != g->gmin[0] || gmin[1] != g->gmin[1] || dims[0] != g->dims[0] || dims[1] != g->dims[1])
                     return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_grid_set_worlds: the worlds' box gives another grid than this one (world box differs from the grid's map)");
-                GRID_HIP(hipMalloc((void**)&fresh, (size_t)K * nodes));
+                if (const int rc = lscqp::dev_alloc(fresh, (size_t)K * nodes, "hipMalloc((void**)&fresh, (size_t)K * nodes)")) return rc;
             }
             const lscgrid::MapRaw mraw{res, key0[0], key0[1], key0[2], mdims[0], mdims[1], mdims[2], nearest};
-            hipLaunchKernelGGL(lscgrid::occupancy_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, (hipStream_t)0, g->v, mraw, g->radius, fresh + (size_t)k * nodes);
+            hipLaunchKernelGGL(lscgrid::occupancy_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, (hipStream_t)0, g->v, mraw, g->radius, fresh.get() + (size_t)k * nodes);
         }
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) {
-            (void)hipFree(fresh);
-            return grid_hip_fail(e, "lscqp_grid_set_worlds");
-        }
+        if (e != hipSuccess) return lscqp::hip_fail(e, "lscqp_grid_set_worlds");
     } else {
         GRID_HIP(hipDeviceSynchronize());  // (a launch may still be reading the bases)
     }
-    if (g->d_occ_w) (void)hipFree(g->d_occ_w);
-    g->d_occ_w = fresh;
+    g->d_occ_w = std::move(fresh);
     g->worlds = K;
     g->fields_off.clear();  // (the mission copies were made from other bases: lscqp_grid_fields_missions_device must come again)
     return LSCQP_OK;
@@ -1268,14 +1235,14 @@ int lscqp_grid_download_world(lscqp_grid g, int32_t k, uint8_t* occ) {
     if (!g || !occ) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
     if (k < 0 || k >= g->worlds) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_grid_download_world: the grid has no such world (lscqp_grid_set_worlds)");
     const size_t nodes = (size_t)g->dims[0] * g->dims[1];
-    GRID_HIP(hipMemcpy(occ, g->d_occ_w + (size_t)k * nodes, nodes, hipMemcpyDeviceToHost));
+    GRID_HIP(hipMemcpy(occ, g->d_occ_w.get() + (size_t)k * nodes, nodes, hipMemcpyDeviceToHost));
     return LSCQP_OK;
 }
 
 int lscqp_grid_mission_status(lscqp_grid g, int32_t n_missions, int32_t* status_out) {
     if (!g || !status_out || n_missions < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
     if (n_missions > g->missions) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the grid has seen no partition of that many missions");
-    GRID_HIP(hipMemcpy(status_out, g->d_status_k, (size_t)n_missions * sizeof(int32_t), hipMemcpyDeviceToHost));
+    GRID_HIP(hipMemcpy(status_out, g->d_status_k.get(), (size_t)n_missions * sizeof(int32_t), hipMemcpyDeviceToHost));
     return LSCQP_OK;
 }
 
@@ -1298,13 +1265,13 @@ int lscqp_grid_fields_missions_device(lscqp_grid g, int64_t n, int32_t n_mission
     const int nodes = g->dims[0] * g->dims[1], K = n_missions;
     g->fields_off.assign(mission_offsets, mission_offsets + K + 1);
     if (g->worlds)  // mission k's copy starts from world k's base
-        GRID_HIP(hipMemcpyAsync(g->d_occ_k, g->d_occ_w, (size_t)nodes * K, hipMemcpyDeviceToDevice, st));
+        GRID_HIP(hipMemcpyAsync(g->d_occ_k.get(), g->d_occ_w.get(), (size_t)nodes * K, hipMemcpyDeviceToDevice, st));
     else
-        hipLaunchKernelGGL(lscgrid::spread_occupancy_kernel, dim3((unsigned)(((int64_t)nodes * K + 255) / 256)), dim3(256), 0, st, nodes, K, g->d_occ, g->d_occ_k);
-    GRID_HIP(hipMemsetAsync(g->d_status_k, 0, (size_t)K * sizeof(int32_t), st));  // new missions: their status words start at 0
-    hipLaunchKernelGGL(lscgrid::clear_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, d_start_points, d_goal_points, g->d_occ_k,
+        hipLaunchKernelGGL(lscgrid::spread_occupancy_kernel, dim3((unsigned)(((int64_t)nodes * K + 255) / 256)), dim3(256), 0, st, nodes, K, g->d_occ.get(), g->d_occ_k.get());
+    GRID_HIP(hipMemsetAsync(g->d_status_k.get(), 0, (size_t)K * sizeof(int32_t), st));  // new missions: their status words start at 0
+    hipLaunchKernelGGL(lscgrid::clear_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, d_start_points, d_goal_points, g->d_occ_k.get(),
                        d_mission_offsets, K);
-    launch_fields(g, n, g->d_occ_k, d_start_points, d_goal_points, d_field, d_init_d, d_mission_offsets, K, st);
+    launch_fields(g, n, g->d_occ_k.get(), d_start_points, d_goal_points, d_field, d_init_d, d_mission_offsets, K, st);
     GRID_HIP(hipGetLastError());
     return LSCQP_OK;
 }
@@ -1333,13 +1300,13 @@ int lscqp_waypoints_missions_device(lscqp_grid g, double communication_range, in
     }
     hipStream_t st = (hipStream_t)stream;
     const int nodes = g->dims[0] * g->dims[1], K = n_missions;
-    hipLaunchKernelGGL(lscgrid::gather_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, communication_range, g->d_occ_k, d_waypoint, d_field, g->s,
+    hipLaunchKernelGGL(lscgrid::gather_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g->v, n, communication_range, g->d_occ_k.get(), d_waypoint, d_field, g->s,
                        d_mission_offsets, K);
     const size_t table_bytes = (size_t)2 * nodes * sizeof(int32_t);
     const int in_lds = tables_fit_lds(g);
     lscgrid::Scratch s = g->s;
-    if (!in_lds) s.now = g->d_tables_k, s.next = g->d_tables_k + nodes;
-    s.status = g->d_status_k;
+    if (!in_lds) s.now = g->d_tables_k.get(), s.next = g->d_tables_k.get() + nodes;
+    s.status = g->d_status_k.get();
     hipLaunchKernelGGL(lscgrid::decide_kernel<true>, dim3((unsigned)K), dim3(lscgrid::kDecideThreads), in_lds ? (table_bytes + 15) / 16 * 16 : 0, st, g->v, n,
                        communication_range, (int)M, (int)dim, in_lds, d_state, d_plan, d_current_goal, d_init_d, d_waypoint, s, d_group_out, d_desired_out,
                        d_updated_out, d_mission_offsets);

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "../../include/lscqp.h"
+#include "lscqp_device.hpp"
 #include "lscqp_internal.hpp"
 // the obstacles' motion: obstacle_advance_kernel, lscqp_obstacle_model_prepare, lscqp_obstacles_advance_device (built as part of this unit)
 #include "lscobstacle.hip"
@@ -183,11 +184,32 @@ __global__ __launch_bounds__(kThreads) void finalize_goal_kernel(Shape s, lscqp_
     H->terminal_segments = ts > 1 ? ts : 1;
 }
 
+// owners of the library's own objects a plan holds
+struct GridDestroy {
+    void operator()(lscqp_grid g) const { lscqp_grid_destroy(g); }
+};
+struct RecordDestroy {
+    void operator()(lscqp_record r) const { lscqp_record_destroy(r); }
+};
+struct HandleDestroy {
+    void operator()(lscqp_handle h) const { lscqp_destroy(h); }
+};
+
+// the setters whose change waits for lscqp_plan_reset, in the order in which a step names them: bit i of lscqp_plan_s::pending
+enum : unsigned { kPendMissions = 1u << 0, kPendRecord = 1u << 1, kPendObstacles = 1u << 2, kPendWorlds = 1u << 3 };
+constexpr const char* kPendSetter[] = {"lscqp_plan_set_missions", "lscqp_plan_set_record", "lscqp_plan_set_obstacles", "lscqp_plan_set_worlds"};
+
 }  // namespace lscplan
 
+using lscqp::dev_ptr;
+using lscqp::hip_fail;
+using lscqp::OnDevice;
+
+// What the plan owns frees itself with the plan (lscqp_plan_destroy has made the plan's device current and waited for it).  The state of each
+// option is a struct of its own: its setter builds the new state complete in a local and moves it in, so a setter that fails changes nothing.
 struct lscqp_plan_s {
     lscqp_handle hq = nullptr;  // the handle the QP solves run on: the caller's, or a private clone of its class in LSCQP_WARM_TIGHT mode
-    bool own_hq = false;
+    std::unique_ptr<lscqp_solver, lscplan::HandleDestroy> own_hq;  // the clone, where hq is one
     lscqp_handle h = nullptr;
     lscqp_map map = nullptr;
     lscqp_plan_desc d;
@@ -210,58 +232,63 @@ struct lscqp_plan_s {
     hipStream_t cap = nullptr;
     // what the captured graph (and the tight-warm-start clone) was derived from: a later lscqp_update / lscqp_map_prepare bumps these
     uint64_t h_gen = 0, map_gen = 0;
-    std::vector<void*> owned;
+    std::vector<dev_ptr<void>> owned;  // the buffers made at lscqp_plan_create, public and private
+    // which setters changed the plan since the last lscqp_plan_reset (lscplan::kPend*): a step waits for the reset
+    unsigned pending = 0;
     // waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: the grid, the mission's distance fields (one per agent, made by lscqp_plan_reset) and start points
-    lscqp_grid grid = nullptr;
-    double grid_resolution = 0.5, grid_radius = 0;
-    int32_t *field = nullptr, *init_d = nullptr, *desired_node = nullptr;
-    double* start_pts = nullptr;
-    bool fields_valid = false;
+    struct Waypoints {
+        std::unique_ptr<lscqp_grid_s, lscplan::GridDestroy> grid;
+        double resolution = 0.5, radius = 0;
+        dev_ptr<int32_t> field;
+        int32_t *init_d = nullptr, *desired_node = nullptr;  // (these three: made at lscqp_plan_create, in `owned`)
+        double* start_pts = nullptr;
+        bool fields_valid = false;
+        int decision = LSCQP_DECISION_ONE_WORKGROUP;  // which form of the decision heads the chain (lscqp_plan_set_waypoint_decision)
+    } wp;
     // a mission partition (lscqp_plan_set_missions): empty = one mission, the chain as it always was
-    std::vector<int64_t> moff;  // [K + 1]
-    int64_t* d_moff = nullptr;
-    bool missions_pending = false;  // the partition changed and lscqp_plan_reset has not come yet
-    int n_missions() const { return moff.empty() ? 1 : (int)moff.size() - 1; }
-    // which form of the waypoint decision heads the chain (lscqp_plan_set_waypoint_decision)
-    int decision = LSCQP_DECISION_ONE_WORKGROUP;
+    struct Missions {
+        std::vector<int64_t> moff;  // [K + 1]
+        dev_ptr<int64_t> d_moff;
+    } mis;
+    int n_missions() const { return mis.moff.empty() ? 1 : (int)mis.moff.size() - 1; }
     // a mission record (lscqp_plan_set_record): accumulated by the last node of the chain
-    bool rec_on = false;
-    lscqp_record_desc rec_desc = {0.0};
-    lscqp_record rec = nullptr;
-    bool record_pending = false;  // the record was set or its partition changed and lscqp_plan_reset has not come yet
+    struct Record {
+        bool on = false;
+        lscqp_record_desc desc = {0.0};
+        std::unique_ptr<lscqp_record_s, lscplan::RecordDestroy> held;  // of the partition in force; empty between set_missions and the reset
+    } rec;
     // dynamic obstacles (lscqp_plan_set_obstacles): n_dyn = 0 = none, the chain as it always was.  They take row slots [0, n_dyn) of every agent
-    int32_t n_dyn = 0;
-    lscqp_obstacle_param obs_param = {};
-    std::vector<lscqp_obstacle_model> obs_models;  // prepared; HELD entries start at `start`
-    lscqp_obstacle_model* d_obs_models = nullptr;
-    lscqp_obstacle* obs_table = nullptr;
-    int32_t *obs_ids = nullptr, *obs_clock = nullptr;  // ids: 0 .. n_dyn - 1 for every local agent
-    lscqp_safety_obs* obs_safety = nullptr;
-    bool obstacles_pending = false;  // the obstacles were set and lscqp_plan_reset has not come yet
-    // a world per mission (lscqp_plan_set_worlds): NULL = the one map, the chain as it always was.  Borrowed
-    lscqp_worlds worlds = nullptr;
-    int32_t* world_of = nullptr;  // [n_total]: the agent's mission
-    uint64_t worlds_gen = 0;      // the members' generation counters, summed, when the graph and the fields were derived
-    bool worlds_pending = false;  // the worlds changed and lscqp_plan_reset has not come yet
-    bool wide() const { return decision == LSCQP_DECISION_WIDE || (decision == LSCQP_DECISION_AUTO && s.n_total >= LSCQP_DECISION_AUTO_MIN_AGENTS); }
+    struct Obstacles {
+        int32_t n_dyn = 0;
+        lscqp_obstacle_param param = {};
+        std::vector<lscqp_obstacle_model> models;  // prepared; HELD entries start at `start`
+        dev_ptr<lscqp_obstacle_model> d_models;
+        dev_ptr<lscqp_obstacle> table;
+        dev_ptr<int32_t> ids, clock;  // ids: 0 .. n_dyn - 1 for every local agent
+        dev_ptr<lscqp_safety_obs> safety;
+    } obs;
+    // a world per mission (lscqp_plan_set_worlds): set = NULL = the one map, the chain as it always was
+    struct Worlds {
+        lscqp_worlds set = nullptr;  // borrowed
+        dev_ptr<int32_t> world_of;   // [n_total]: the agent's mission
+        uint64_t gen = 0;            // the members' generation counters, summed, when the graph and the fields were derived
+    } wld;
+    bool wide() const { return wp.decision == LSCQP_DECISION_WIDE || (wp.decision == LSCQP_DECISION_AUTO && s.n_total >= LSCQP_DECISION_AUTO_MIN_AGENTS); }
 };
 
 namespace {
 
-int hip_fail(hipError_t e, const char* what) {
-    return lscqp_set_error_(LSCQP_ERR_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-
+// a zeroed buffer of the plan's own, at least one element
 template <class T>
 int dalloc(lscqp_plan_s* p, T** out, size_t count) {
-    void* ptr = nullptr;
-    const size_t b = (count ? count : 1) * sizeof(T);
-    hipError_t e = hipMalloc(&ptr, b);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(plan buffer)");
-    e = hipMemset(ptr, 0, b);
+    dev_ptr<T> q;
+    const size_t c = count ? count : 1;
+    const int rc = lscqp::dev_alloc(q, c, "hipMalloc(plan buffer)");
+    if (rc != LSCQP_OK) return rc;
+    const hipError_t e = hipMemset(q.get(), 0, c * sizeof(T));
     if (e != hipSuccess) return hip_fail(e, "hipMemset(plan buffer)");
-    p->owned.push_back(ptr);
-    *out = (T*)ptr;
+    *out = q.get();
+    p->owned.emplace_back(q.release());
     return LSCQP_OK;
 }
 
@@ -303,29 +330,27 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     lscqp_info* info = (lscqp_info*)p->buf[LSCQP_PLAN_BUF_INFO];
     const double fraction = p->d.time_step / s.dt;
     const int K = p->n_missions();
-    if (p->missions_pending) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_missions: lscqp_plan_reset must come before the next step");
-    if (p->rec_on && (p->record_pending || !p->rec))
-        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: lscqp_plan_reset must come before the next step");
-    if (p->obstacles_pending) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacles: lscqp_plan_reset must come before the next step");
-    if (p->worlds_pending) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_worlds: lscqp_plan_reset must come before the next step");
-    const int32_t n_dyn = p->n_dyn, n_nbr = s.n_obs - n_dyn;  // row slots [0, n_dyn): the obstacles, [n_dyn, n_obs): the in-range agents
+    const lscqp_plan_s::Waypoints& wp = p->wp;
+    const lscqp_plan_s::Obstacles& obs = p->obs;
+    lscqp_grid grid = wp.grid.get();
+    const int64_t *moff = p->mis.moff.data(), *d_moff = p->mis.d_moff.get();
+    const int32_t n_dyn = obs.n_dyn, n_nbr = s.n_obs - n_dyn;  // row slots [0, n_dyn): the obstacles, [n_dyn, n_obs): the in-range agents
     // decentralizedMAPP precedes the planning loop (src/multi_sync_simulator.cpp:101-120): the waypoints of this replan, from the plans as the
     // last replan left them (AgentManager::getTraj is desired_traj, un-shifted)
-    if (p->grid) {
-        if (!p->fields_valid) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: lscqp_plan_reset must come before the first step");
+    if (grid) {
         if (K > 1)
-            PLAN_TRY(lscqp_waypoints_missions_device(p->grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, K, p->moff.data(), p->d_moff,
-                                                     state, x_plan, goal, p->field, p->init_d, waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], p->desired_node,
+            PLAN_TRY(lscqp_waypoints_missions_device(grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, K, moff, d_moff,
+                                                     state, x_plan, goal, wp.field.get(), wp.init_d, waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], wp.desired_node,
                                                      (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
         else if (p->wide())
-            PLAN_TRY(lscqp_waypoints_wide_device(p->grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, state, x_plan, goal, p->field, p->init_d,
-                                                 waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], p->desired_node, (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
+            PLAN_TRY(lscqp_waypoints_wide_device(grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, state, x_plan, goal, wp.field.get(), wp.init_d,
+                                                 waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], wp.desired_node, (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
         else
-            PLAN_TRY(lscqp_waypoints_device(p->grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, state, x_plan, goal, p->field, p->init_d,
-                                            waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], p->desired_node, (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
+            PLAN_TRY(lscqp_waypoints_device(grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, state, x_plan, goal, wp.field.get(), wp.init_d,
+                                            waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], wp.desired_node, (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
     }
     // obstacle_generator.update(t, 0) at the replan's start time (src/multi_sync_simulator.cpp:311); the clock is the device's
-    if (n_dyn > 0) PLAN_TRY(lscqp_obstacles_advance_device(h, p->d_obs_models, n_dyn, p->d.time_step, p->obs_clock, p->obs_table, stream));
+    if (n_dyn > 0) PLAN_TRY(lscqp_obstacles_advance_device(h, obs.d_models.get(), n_dyn, p->d.time_step, obs.clock.get(), obs.table.get(), stream));
     // obstaclePredictionWithPrevSol / initialTrajPlanningPrevSol for every agent of the mission (:273-310, 399-423)
     const bool from_plans = !first_replan && (s.prediction_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION || s.initial_traj_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION);
     const bool whole_shift = from_plans && fraction >= 1.0 - 1e-9;  // (done by prepare_kernel itself)
@@ -339,15 +364,15 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
             PLAN_TRY(lscqp_order_by_cost_device(s.n_agents, p->sfc_cost, p->sfc_order, stream));
             sfc_order = p->sfc_order;
         }
-        if (p->worlds)  // every agent in the world of its mission (a partition has every agent local: first_agent = 0)
-            PLAN_TRY(lscqp_construct_sfc_worlds_device(h, p->worlds, first_replan ? LSCQP_SFC_INIT : p->d.sfc_mode, s.n_agents, p->world_of, p->points,
+        if (p->wld.set)  // every agent in the world of its mission (a partition has every agent local: first_agent = 0)
+            PLAN_TRY(lscqp_construct_sfc_worlds_device(h, p->wld.set, first_replan ? LSCQP_SFC_INIT : p->d.sfc_mode, s.n_agents, p->wld.world_of.get(), p->points,
                                                        p->radius + s.first_agent, sfc, sfc_status, sfc_order, p->sfc_cost, stream));
         else
             PLAN_TRY(lscqp_construct_sfc_device_ordered(h, p->map, first_replan ? LSCQP_SFC_INIT : p->d.sfc_mode, s.n_agents, p->points,
                                                         p->radius + s.first_agent, sfc, sfc_status, sfc_order, p->sfc_cost, stream));
     }
     if (K > 1)
-        PLAN_TRY(lscqp_select_neighbours_missions_device(h, s.n_total, K, p->moff.data(), p->d_moff, n_nbr, lscqp_class_desc_of_(h)->communication_range, p->pos,
+        PLAN_TRY(lscqp_select_neighbours_missions_device(h, s.n_total, K, moff, d_moff, n_nbr, lscqp_class_desc_of_(h)->communication_range, p->pos,
                                                          p->nbr, count, stream));
     else
         PLAN_TRY(lscqp_select_neighbours_device(h, s.n_agents, s.first_agent, s.n_total, n_nbr, lscqp_class_desc_of_(h)->communication_range, p->pos, p->nbr, count,
@@ -359,10 +384,10 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     // local id like the radii, goals and headers handed over here -- `traj` holds the agents' predictions as each other's obstacles by now.
     // generateCLSC's rows take no obstacle goal points: Obstacle::goal_point is the origin in the reference (include/obstacle.hpp:23, 37-49)
     if (n_dyn > 0 && p->d.constraint_mode == LSCQP_GEN_CLSC)
-        PLAN_TRY(lscqp_generate_obstacle_rows_device(h, LSCQP_GEN_CLSC, &p->obs_param, s.n_agents, n_dyn, 0, p->own, p->obs_ids, p->obs_table, nullptr,
+        PLAN_TRY(lscqp_generate_obstacle_rows_device(h, LSCQP_GEN_CLSC, &obs.param, s.n_agents, n_dyn, 0, p->own, obs.ids.get(), obs.table.get(), nullptr,
                                                      p->radius + s.first_agent, goal + s.first_agent * 3, nullptr, rows, s.n_obs, 0, stream));
     else if (n_dyn > 0)
-        PLAN_TRY(lscqp_generate_lsc_obstacles_device(h, &p->obs_param, s.n_agents, n_dyn, 0, p->own, p->obs_ids, p->obs_table, p->radius + s.first_agent,
+        PLAN_TRY(lscqp_generate_lsc_obstacles_device(h, &obs.param, s.n_agents, n_dyn, 0, p->own, obs.ids.get(), obs.table.get(), p->radius + s.first_agent,
                                                      goal + s.first_agent * 3, hdr, rows, s.n_obs, 0, stream));
     if (p->d.optimize_goal) {  // (the goal LP's kernel finishes the headers itself: one node less)
         PLAN_TRY(lscqp_optimize_goal_fin_device_(h, s.n_agents, hdr, rows, p->off, p->map ? sfc : nullptr, goal_status, s.dt, stream));
@@ -389,7 +414,7 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
                                             x_plan + s.first_agent * s.nv, goal + s.first_agent * 3, hdr, p->map ? sfc : nullptr, valid, state_out, stream));
     }
     if (p->d.safety_samples > 0 && K > 1)
-        PLAN_TRY(lscqp_safety_metrics_missions_device(h, s.n_total, K, p->moff.data(), p->d_moff, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan,
+        PLAN_TRY(lscqp_safety_metrics_missions_device(h, s.n_total, K, moff, d_moff, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan,
                                                       p->radius, p->downwash, hdr, (lscqp_safety*)p->buf[LSCQP_PLAN_BUF_SAFETY], stream));
     else if (p->d.safety_samples > 0)  // MultiSyncSimulator::update's safety ratio / excess ratios over the step just planned (:486-577)
         PLAN_TRY(lscqp_safety_metrics_device(h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan,
@@ -397,10 +422,10 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     // the obstacle leg of the safety figures (:527-557), against the positions this replan's advance left
     if (p->d.safety_samples > 0 && n_dyn > 0)
         PLAN_TRY(lscqp_safety_obstacles_device(h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan, p->radius,
-                                               p->downwash, n_dyn, p->obs_table, p->obs_safety, stream));
+                                               p->downwash, n_dyn, obs.table.get(), obs.safety.get(), stream));
     // the mission record: the figures of this replan and the finish test on the state it started from (hdr.p0), the chain's last node
-    if (p->rec_on)
-        PLAN_TRY(lscqp_record_step_device(p->rec, hdr, x_plan, status, goal_status, sfc_status, valid, count, (const lscqp_safety*)p->buf[LSCQP_PLAN_BUF_SAFETY],
+    if (p->rec.on)
+        PLAN_TRY(lscqp_record_step_device(p->rec.held.get(), hdr, x_plan, status, goal_status, sfc_status, valid, count, (const lscqp_safety*)p->buf[LSCQP_PLAN_BUF_SAFETY],
                                           (const int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
     // (closed loop: LSCQP_PLAN_BUF_NEXT_STATE is the local agents' slice of the state buffer itself, so doStep's result is the next
     // replan's current state without a copy)
@@ -416,26 +441,31 @@ void drop_graph(lscqp_plan_s* p) {
     p->graph = nullptr;
 }
 
-void free_obstacles(lscqp_plan_s* p) {
-    for (void* q : {(void*)p->d_obs_models, (void*)p->obs_table, (void*)p->obs_ids, (void*)p->obs_clock, (void*)p->obs_safety})
-        if (q) (void)hipFree(q);
-    p->d_obs_models = nullptr, p->obs_table = nullptr, p->obs_ids = nullptr, p->obs_clock = nullptr, p->obs_safety = nullptr;
-    p->obs_models.clear();
-    p->n_dyn = 0;
-    p->obstacles_pending = false;
+// may the plan step?  The refusals of a plan that waits for lscqp_plan_reset, in the order a step has always given them.  Asked before
+// anything is enqueued or captured
+int may_step(const lscqp_plan_s* p) {
+    if (p->s.n_agents == 0) return LSCQP_OK;  // (an empty block of a sharded mission replans nothing)
+    unsigned waits = p->pending;
+    if (p->rec.on && !p->rec.held) waits |= lscplan::kPendRecord;
+    for (unsigned i = 0; i < sizeof lscplan::kPendSetter / sizeof *lscplan::kPendSetter; i++)
+        if (waits & (1u << i))
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, (std::string(lscplan::kPendSetter[i]) + ": lscqp_plan_reset must come before the next step").c_str());
+    if (p->wp.grid && !p->wp.fields_valid)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: lscqp_plan_reset must come before the first step");
+    return LSCQP_OK;
 }
 
 // the table at t = 0 as far as the host knows it -- common fields, HELD entries at their start; the first advance writes the rest -- and the clock
-int reset_obstacles(lscqp_plan_s* p) {
-    std::vector<lscqp_obstacle> tab((size_t)p->n_dyn);
+int reset_obstacles(const lscqp_plan_s::Obstacles& o) {
+    std::vector<lscqp_obstacle> tab((size_t)o.n_dyn);
     memset(tab.data(), 0, tab.size() * sizeof(lscqp_obstacle));
-    for (int i = 0; i < p->n_dyn; i++) {
-        const lscqp_obstacle_model& m = p->obs_models[(size_t)i];
+    for (int i = 0; i < o.n_dyn; i++) {
+        const lscqp_obstacle_model& m = o.models[(size_t)i];
         for (int k = 0; k < 3; k++) tab[(size_t)i].position[k] = (double)(float)m.start[k];
         tab[(size_t)i].radius = m.radius, tab[(size_t)i].downwash = m.downwash, tab[(size_t)i].max_acc = m.max_acc;
     }
-    hipError_t e = hipMemcpy(p->obs_table, tab.data(), tab.size() * sizeof(lscqp_obstacle), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(p->obs_clock, 0, sizeof(int32_t));
+    hipError_t e = hipMemcpy(o.table.get(), tab.data(), tab.size() * sizeof(lscqp_obstacle), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(o.clock.get(), 0, sizeof(int32_t));
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "plan reset (obstacles)");
 }
 
@@ -443,60 +473,50 @@ int reset_obstacles(lscqp_plan_s* p) {
 int make_grid(lscqp_plan_s* p, double resolution) {
     lscqp_grid_desc gd;
     memset(&gd, 0, sizeof gd);
-    gd.resolution = resolution, gd.radius = p->grid_radius, gd.z_2d = p->d.z_2d, gd.world_dimension = p->s.dim;
-    lscqp_grid gnew = nullptr;
-    PLAN_TRY(lscqp_grid_create(p->map, &gd, &gnew));
-    if (p->worlds) {  // (a new grid of a plan with worlds gets them again)
-        const int rcw = lscqp_grid_set_worlds(gnew, p->worlds);
-        if (rcw != LSCQP_OK) {
-            lscqp_grid_destroy(gnew);
-            return rcw;
-        }
+    gd.resolution = resolution, gd.radius = p->wp.radius, gd.z_2d = p->d.z_2d, gd.world_dimension = p->s.dim;
+    decltype(p->wp.grid) gnew;
+    {
+        lscqp_grid g = nullptr;
+        PLAN_TRY(lscqp_grid_create(p->map, &gd, &g));
+        gnew.reset(g);
     }
+    if (p->wld.set) PLAN_TRY(lscqp_grid_set_worlds(gnew.get(), p->wld.set));  // (a new grid of a plan with worlds gets them again)
     double gmin[3];
     int32_t dims[3];
-    lscqp_grid_info(gnew, gmin, dims);
-    void* f = nullptr;
-    const hipError_t e = hipMalloc(&f, (size_t)p->s.n_total * dims[0] * dims[1] * sizeof(int32_t));
-    int rc = e != hipSuccess ? hip_fail(e, "hipMalloc(distance fields)")
-                             : (p->n_missions() > 1 ? lscqp_grid_reserve_missions_(gnew, p->s.n_total, p->n_missions()) : lscqp_grid_reserve(gnew, p->s.n_total));
-    if (rc == LSCQP_OK && p->decision != LSCQP_DECISION_ONE_WORKGROUP) rc = lscqp_grid_reserve_wide(gnew, p->s.n_total);
-    if (rc != LSCQP_OK) {
-        if (f) (void)hipFree(f);
-        lscqp_grid_destroy(gnew);
-        return rc;
-    }
-    if (p->grid) lscqp_grid_destroy(p->grid);
-    if (p->field) (void)hipFree(p->field);
-    p->grid = gnew;
-    p->field = (int32_t*)f;
-    p->grid_resolution = resolution;
-    p->fields_valid = false;
+    lscqp_grid_info(gnew.get(), gmin, dims);
+    dev_ptr<int32_t> f;
+    PLAN_TRY(lscqp::dev_alloc(f, (size_t)p->s.n_total * dims[0] * dims[1], "hipMalloc(distance fields)"));
+    PLAN_TRY(p->n_missions() > 1 ? lscqp_grid_reserve_missions_(gnew.get(), p->s.n_total, p->n_missions()) : lscqp_grid_reserve(gnew.get(), p->s.n_total));
+    if (p->wp.decision != LSCQP_DECISION_ONE_WORKGROUP) PLAN_TRY(lscqp_grid_reserve_wide(gnew.get(), p->s.n_total));
+    p->wp.grid = std::move(gnew);
+    p->wp.field = std::move(f);
+    p->wp.resolution = resolution;
+    p->wp.fields_valid = false;
     return LSCQP_OK;
 }
 
 // updateGridMission + createDistanceTable for the whole mission (include/lscqp.h, DIFFERENCE 1); synchronous
 int make_fields(lscqp_plan_s* p) {
+    lscqp_plan_s::Waypoints& wp = p->wp;
     if (p->n_missions() > 1)
-        PLAN_TRY(lscqp_grid_fields_missions_device(p->grid, p->s.n_total, p->n_missions(), p->moff.data(), p->d_moff, p->start_pts,
-                                                   (const double*)p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], p->field, p->init_d, nullptr));
+        PLAN_TRY(lscqp_grid_fields_missions_device(wp.grid.get(), p->s.n_total, p->n_missions(), p->mis.moff.data(), p->mis.d_moff.get(), wp.start_pts,
+                                                   (const double*)p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], wp.field.get(), wp.init_d, nullptr));
     else
-        PLAN_TRY(lscqp_grid_fields_device(p->grid, p->s.n_total, p->start_pts, (const double*)p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], p->field, p->init_d, nullptr));
+        PLAN_TRY(lscqp_grid_fields_device(wp.grid.get(), p->s.n_total, wp.start_pts, (const double*)p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], wp.field.get(), wp.init_d, nullptr));
     const hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "distance fields");
-    p->fields_valid = true;
+    wp.fields_valid = true;
     return LSCQP_OK;
 }
 
 // the plan's record for the partition in force (its offsets are the ones the partition already has on the device); the old one is dropped
-int make_record(lscqp_plan_s* p) {
+int make_record(lscqp_plan_s* p, const lscqp_record_desc& desc) {
     lscqp_record rnew = nullptr;
-    const bool one = p->moff.empty();
-    PLAN_TRY(lscqp_record_create_(p->h, p->s.n_total, one ? 1 : p->n_missions(), one ? nullptr : p->moff.data(), one ? nullptr : p->d_moff,
-                                  p->d.safety_samples, p->d.record_time_step, p->d.time_step, p->s.z_2d, &p->rec_desc, &rnew));
+    const bool one = p->mis.moff.empty();
+    PLAN_TRY(lscqp_record_create_(p->h, p->s.n_total, one ? 1 : p->n_missions(), one ? nullptr : p->mis.moff.data(), one ? nullptr : p->mis.d_moff.get(),
+                                  p->d.safety_samples, p->d.record_time_step, p->d.time_step, p->s.z_2d, &desc, &rnew));
     drop_graph(p);  // (a captured chain holds the old record's buffers)
-    if (p->rec) lscqp_record_destroy(p->rec);
-    p->rec = rnew;
+    p->rec.held.reset(rnew);
     return LSCQP_OK;
 }
 
@@ -506,10 +526,10 @@ int make_record(lscqp_plan_s* p) {
 // compare the generation counters before every step, drop the graph and re-derive the clone when they moved.
 int refresh(lscqp_plan_s* p) {
     const uint64_t hg = lscqp_handle_generation_(p->h), mg = p->map ? lscqp_map_generation_(p->map) : 0;
-    const uint64_t wg = p->worlds ? lscqp_worlds_generation_(p->worlds) : 0;  // (every member map of a plan with worlds)
-    if (hg == p->h_gen && mg == p->map_gen && wg == p->worlds_gen) return LSCQP_OK;
+    const uint64_t wg = p->wld.set ? lscqp_worlds_generation_(p->wld.set) : 0;  // (every member map of a plan with worlds)
+    if (hg == p->h_gen && mg == p->map_gen && wg == p->wld.gen) return LSCQP_OK;
     drop_graph(p);
-    if (p->worlds) PLAN_TRY(lscqp_worlds_refresh_(p->worlds));  // (the set's table follows its members before anything is enqueued)
+    if (p->wld.set) PLAN_TRY(lscqp_worlds_refresh_(p->wld.set));  // (the set's table follows its members before anything is enqueued)
     if (hg != p->h_gen) {
         // the buffers and the launch shapes of prepare / commit were sized at lscqp_plan_create: an update that changes the SHAPE of the
         // class (segments, dimension, corridor rows on / off, row format, a kernel capacity below the plan's neighbour slots) cannot be
@@ -533,8 +553,8 @@ int refresh(lscqp_plan_s* p) {
                 lscqp_handle hq = nullptr;
                 const int rc = lscqp_create(&cd, &hq);
                 if (rc != LSCQP_OK) return rc;
+                p->own_hq.reset(hq);
                 p->hq = hq;
-                p->own_hq = true;
             }
         } else if (p->own_hq) {  // h became WARM_TIGHT itself: the clone only has to follow it
             const int rc = lscqp_update(p->hq, &cd);
@@ -545,45 +565,32 @@ int refresh(lscqp_plan_s* p) {
             if (rc != LSCQP_OK) return rc;
         }
     }
-    if ((mg != p->map_gen || wg != p->worlds_gen) && p->grid && p->fields_valid) {  // the map moved under the mission: its grid and fields are made again
-        const int rc = make_grid(p, p->grid_resolution);
+    if ((mg != p->map_gen || wg != p->wld.gen) && p->wp.grid && p->wp.fields_valid) {  // the map moved under the mission: its grid and fields are made again
+        const int rc = make_grid(p, p->wp.resolution);
         if (rc != LSCQP_OK) return rc;
         const int rc2 = make_fields(p);
         if (rc2 != LSCQP_OK) return rc2;
     }
     p->h_gen = hg;
     p->map_gen = mg;
-    p->worlds_gen = wg;
+    p->wld.gen = wg;
     return LSCQP_OK;
 }
 
 // the per-agent world index of a plan with worlds: the agent's mission in the partition `off` ([K + 1]); a fresh device array
-int make_world_of(int64_t n_total, const int64_t* off, int K, int32_t** out) {
+int make_world_of(int64_t n_total, const int64_t* off, int K, dev_ptr<int32_t>& out) {
     std::vector<int32_t> host((size_t)n_total);
     for (int k = 0; k < K; k++)
         for (int64_t a = off[k]; a < off[k + 1]; a++) host[(size_t)a] = k;
-    int32_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, host.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpy(d, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    const char* const what = "world index of the agents";
+    PLAN_TRY(lscqp::dev_alloc(out, host.size(), what));
+    const hipError_t e = hipMemcpy(out.get(), host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        if (d) (void)hipFree(d);
-        return hip_fail(e, "world index of the agents");
+        out.reset();
+        return hip_fail(e, what);
     }
-    *out = d;
     return LSCQP_OK;
 }
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-        else prev = -1;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 }  // namespace
 
@@ -640,18 +647,16 @@ int lscqp_plan_create(lscqp_handle h, lscqp_map map, const lscqp_plan_desc* desc
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
                                 "the map lives on another device than the plan (create the map with the plan's device current: the corridor "
                                 "kernel dereferences the map's grids)");
-    lscqp_plan_s* p = new lscqp_plan_s();
+    std::unique_ptr<lscqp_plan_s, void (*)(lscqp_plan)> owner(new lscqp_plan_s(), lscqp_plan_destroy);
+    lscqp_plan_s* p = owner.get();
     p->h = h;
     p->hq = h;
+    p->device = cur_dev;
     if (desc->tight_warm_start && lscqp_class_desc_of_(h)->warm_start != LSCQP_WARM_TIGHT) {
         lscqp_class_desc cd = *lscqp_class_desc_of_(h);
         cd.warm_start = LSCQP_WARM_TIGHT;
-        const int rc_clone = lscqp_create(&cd, &p->hq);
-        if (rc_clone != LSCQP_OK) {
-            delete p;
-            return rc_clone;  // (lscqp_create has set the message)
-        }
-        p->own_hq = true;
+        PLAN_TRY(lscqp_create(&cd, &p->hq));  // (lscqp_create has set the message)
+        p->own_hq.reset(p->hq);
         if (lscqp_prescreen(h) != LSCQP_PRESCREEN_OFF) (void)lscqp_set_prescreen(p->hq, lscqp_prescreen(h));
     }
     p->h_gen = lscqp_handle_generation_(h);
@@ -670,7 +675,6 @@ int lscqp_plan_create(lscqp_handle h, lscqp_map map, const lscqp_plan_desc* desc
     p->s.prediction_mode = desc->prediction_mode;
     p->s.initial_traj_mode = desc->initial_traj_mode;
     p->s.reset_threshold = desc->reset_threshold;
-    p->device = cur_dev;
     const size_t n = (size_t)desc->n_agents, nt = (size_t)desc->n_total, P = (size_t)M * 6, no = (size_t)desc->n_obs;
     int rc = LSCQP_OK;
     auto ok = [&](int r) { return rc == LSCQP_OK && (rc = r) == LSCQP_OK; };
@@ -691,8 +695,8 @@ int lscqp_plan_create(lscqp_handle h, lscqp_map map, const lscqp_plan_desc* desc
         ((map && n > lscplan::kSfcOrderMin) ? (ok(dalloc(p, &p->sfc_order, n)) && ok(dalloc(p, &p->sfc_cost, n))) : true);
     if (desc->waypoint_mode == LSCQP_WAYPOINT_GRID_PIBT) {
         ok(dalloc_pub<double>(p, LSCQP_PLAN_BUF_DESIRED_GOAL, nt * 3)) && ok(dalloc_pub<int32_t>(p, LSCQP_PLAN_BUF_WAYPOINT_UPDATED, n)) &&
-            ok(dalloc_pub<int32_t>(p, LSCQP_PLAN_BUF_GROUP, n)) && ok(dalloc(p, &p->init_d, nt)) && ok(dalloc(p, &p->desired_node, nt)) && ok(dalloc(p, &p->start_pts, nt * 3));
-        p->grid_radius = agents[0].radius;  // (planMAPF is handed mission.agents[0].radius, src/multi_sync_simulator.cpp:211-214)
+            ok(dalloc_pub<int32_t>(p, LSCQP_PLAN_BUF_GROUP, n)) && ok(dalloc(p, &p->wp.init_d, nt)) && ok(dalloc(p, &p->wp.desired_node, nt)) && ok(dalloc(p, &p->wp.start_pts, nt * 3));
+        p->wp.radius = agents[0].radius;  // (planMAPF is handed mission.agents[0].radius, src/multi_sync_simulator.cpp:211-214)
         if (rc == LSCQP_OK) rc = make_grid(p, 0.5);
     }
     if (rc == LSCQP_OK) {
@@ -719,46 +723,35 @@ int lscqp_plan_create(lscqp_handle h, lscqp_map map, const lscqp_plan_desc* desc
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->cap, hipStreamNonBlocking);
         if (e != hipSuccess) rc = hip_fail(e, "plan set-up");
     }
-    if (rc != LSCQP_OK) {
-        lscqp_plan_destroy(p);
-        return rc;
-    }
-    *out = p;
+    if (rc != LSCQP_OK) return rc;
+    *out = owner.release();
     return LSCQP_OK;
 }
 
 void lscqp_plan_destroy(lscqp_plan p) {
     if (!p) return;
-    DeviceGuard g(p->device);
+    OnDevice on(p->device);
     (void)hipDeviceSynchronize();
     drop_graph(p);
     if (p->cap) (void)hipStreamDestroy(p->cap);
-    for (void* q : p->owned) (void)hipFree(q);
-    if (p->grid) lscqp_grid_destroy(p->grid);
-    if (p->field) (void)hipFree(p->field);
-    if (p->rec) lscqp_record_destroy(p->rec);
-    if (p->d_moff) (void)hipFree(p->d_moff);
-    if (p->world_of) (void)hipFree(p->world_of);
-    free_obstacles(p);
-    if (p->own_hq) lscqp_destroy(p->hq);
     delete p;
 }
 
 int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* goal_points) {
     if (!p || !start_positions) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
-    if (p->grid && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: the mission's goal points are required");
-    if (p->rec_on && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: the mission's goal points are required (the desired goals of the finish test)");
-    DeviceGuard g(p->device);
+    if (p->wp.grid && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: the mission's goal points are required");
+    if (p->rec.on && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: the mission's goal points are required (the desired goals of the finish test)");
+    OnDevice on(p->device);
     const lscplan::Shape& s = p->s;
     const size_t nt = (size_t)s.n_total, P = (size_t)s.M * 6;
-    std::vector<double> st(nt * 9, 0.0), x(nt * s.nv), gl(nt * 3), dg(p->grid ? nt * 3 : 0);
+    std::vector<double> st(nt * 9, 0.0), x(nt * s.nv), gl(nt * 3), dg(p->wp.grid ? nt * 3 : 0);
     for (size_t a = 0; a < nt; a++) {
         for (int k = 0; k < 3; k++) {
             // State holds point3d; a 2-D mission flies at z = world_z_2d (src/agent_manager.cpp:40-42)
             const double v = (k < s.dim) ? (double)(float)start_positions[a * 3 + k] : (double)(float)s.z_2d;
             st[a * 9 + k] = v;
-            gl[a * 3 + k] = (goal_points && !p->grid) ? (double)(float)goal_points[a * 3 + k] : v;  // AgentManager ctor: current_goal_point = start
-            if (p->grid) dg[a * 3 + k] = (k < s.dim) ? (double)(float)goal_points[a * 3 + k] : v;  // Agent::desired_goal_point, in the mission's plane
+            gl[a * 3 + k] = (goal_points && !p->wp.grid) ? (double)(float)goal_points[a * 3 + k] : v;  // AgentManager ctor: current_goal_point = start
+            if (p->wp.grid) dg[a * 3 + k] = (k < s.dim) ? (double)(float)goal_points[a * 3 + k] : v;  // Agent::desired_goal_point, in the mission's plane
         }
         for (int k = 0; k < s.dim; k++)
             for (size_t j = 0; j < P; j++) x[a * s.nv + k * P + j] = st[a * 9 + k];
@@ -768,24 +761,21 @@ int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* 
     if (e == hipSuccess) e = hipMemcpy(p->buf[LSCQP_PLAN_BUF_PLAN], x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p->buf[LSCQP_PLAN_BUF_GOAL], gl.data(), gl.size() * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(p->buf[LSCQP_PLAN_BUF_WAYPOINT], gl.data() + s.first_agent * 3, (size_t)s.n_agents * 3 * sizeof(double), hipMemcpyHostToDevice);
-    if (p->grid) {  // (gl holds the start positions here: the waypoints above start there, src/agent_manager.cpp:10)
+    if (p->wp.grid) {  // (gl holds the start positions here: the waypoints above start there, src/agent_manager.cpp:10)
         if (e == hipSuccess) e = hipMemcpy(p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], dg.data(), dg.size() * sizeof(double), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(p->start_pts, gl.data(), gl.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(p->wp.start_pts, gl.data(), gl.size() * sizeof(double), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) return hip_fail(e, "plan reset");
-    if (p->grid) PLAN_TRY(make_fields(p));
-    if (p->rec_on) {  // the record of the partition in force, cleared; desired goals in the mission's plane like the states
-        if (!p->rec || p->record_pending || p->missions_pending) PLAN_TRY(make_record(p));
+    if (p->wp.grid) PLAN_TRY(make_fields(p));
+    if (p->rec.on) {  // the record of the partition in force, cleared; desired goals in the mission's plane like the states
+        if (!p->rec.held || (p->pending & (lscplan::kPendRecord | lscplan::kPendMissions))) PLAN_TRY(make_record(p, p->rec.desc));
         std::vector<double> want(nt * 3);
         for (size_t a = 0; a < nt; a++)
             for (int k = 0; k < 3; k++) want[a * 3 + k] = (k < s.dim) ? goal_points[a * 3 + k] : st[a * 9 + k];
-        PLAN_TRY(lscqp_record_reset(p->rec, want.data()));
-        p->record_pending = false;
+        PLAN_TRY(lscqp_record_reset(p->rec.held.get(), want.data()));
     }
-    if (p->n_dyn > 0) PLAN_TRY(reset_obstacles(p));
-    p->obstacles_pending = false;
-    p->missions_pending = false;
-    p->worlds_pending = false;
+    if (p->obs.n_dyn > 0) PLAN_TRY(reset_obstacles(p->obs));
+    p->pending = 0;
     p->first = true;
     p->steps = 0;
     return LSCQP_OK;
@@ -803,7 +793,7 @@ void* lscqp_plan_buffer(lscqp_plan p, int32_t which, uint64_t* bytes_out) {
 int lscqp_plan_upload(lscqp_plan p, int32_t which, const void* host, uint64_t offset, uint64_t bytes) {
     if (!p || !host || which < 0 || which >= LSCQP_PLAN_BUF_COUNT) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
     if (offset + bytes > p->bytes[which]) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "range exceeds the buffer");
-    DeviceGuard g(p->device);
+    OnDevice on(p->device);
     const hipError_t e = hipMemcpy((char*)p->buf[which] + offset, host, bytes, hipMemcpyHostToDevice);
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "plan upload");
 }
@@ -811,18 +801,17 @@ int lscqp_plan_upload(lscqp_plan p, int32_t which, const void* host, uint64_t of
 int lscqp_plan_download(lscqp_plan p, int32_t which, void* host, uint64_t offset, uint64_t bytes) {
     if (!p || !host || which < 0 || which >= LSCQP_PLAN_BUF_COUNT) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "bad argument");
     if (offset + bytes > p->bytes[which]) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "range exceeds the buffer");
-    DeviceGuard g(p->device);
+    OnDevice on(p->device);
     const hipError_t e = hipMemcpy(host, (const char*)p->buf[which] + offset, bytes, hipMemcpyDeviceToHost);  // waits for the device
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "plan download");
 }
 
 int lscqp_plan_step(lscqp_plan p, void* stream) {
     if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
-    DeviceGuard g(p->device);
-    int rc = refresh(p);
-    if (rc != LSCQP_OK) return rc;
-    rc = enqueue(p, p->first, (hipStream_t)stream);
-    if (rc != LSCQP_OK) return rc;
+    OnDevice on(p->device);
+    PLAN_TRY(refresh(p));
+    PLAN_TRY(may_step(p));
+    PLAN_TRY(enqueue(p, p->first, (hipStream_t)stream));
     p->first = false;
     p->steps++;
     return LSCQP_OK;
@@ -832,11 +821,9 @@ int lscqp_plan_step_graph(lscqp_plan p, void* stream) {
     if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
     // the first replan differs (initializeSFC) and it also warms the kernels' one-time function attributes up: eager
     if (p->first || p->s.n_agents == 0) return lscqp_plan_step(p, stream);
-    DeviceGuard g(p->device);
-    {
-        const int rc_ = refresh(p);
-        if (rc_ != LSCQP_OK) return rc_;
-    }
+    OnDevice on(p->device);
+    PLAN_TRY(refresh(p));
+    PLAN_TRY(may_step(p));
     if (!p->exec) {
         hipError_t e = hipStreamBeginCapture(p->cap, hipStreamCaptureModeThreadLocal);
         if (e != hipSuccess) return hip_fail(e, "hipStreamBeginCapture");
@@ -863,65 +850,50 @@ int lscqp_plan_step_graph(lscqp_plan p, void* stream) {
 
 int lscqp_plan_set_grid(lscqp_plan p, double resolution) {
     if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
-    if (!p->grid) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the plan has no grid (waypoint_mode = LSCQP_WAYPOINT_FROM_CALLER)");
-    DeviceGuard g(p->device);
+    if (!p->wp.grid) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the plan has no grid (waypoint_mode = LSCQP_WAYPOINT_FROM_CALLER)");
+    OnDevice on(p->device);
     const hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_grid");
     drop_graph(p);  // (a captured chain holds the old grid's buffers)
     return make_grid(p, resolution);
 }
 
-lscqp_grid lscqp_plan_grid(lscqp_plan p) { return p ? p->grid : nullptr; }
+lscqp_grid lscqp_plan_grid(lscqp_plan p) { return p ? p->wp.grid.get() : nullptr; }
 
 int lscqp_plan_set_missions(lscqp_plan p, int32_t n_missions, const int64_t* mission_offsets) {
     if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
     const bool single = n_missions <= 1 || !mission_offsets;
-    if (p->worlds && (single ? 1 : n_missions) != lscqp_worlds_count_(p->worlds))
+    if (p->wld.set && (single ? 1 : n_missions) != lscqp_worlds_count_(p->wld.set))
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
-                                ("lscqp_plan_set_missions: the plan has " + std::to_string(lscqp_worlds_count_(p->worlds)) +
+                                ("lscqp_plan_set_missions: the plan has " + std::to_string(lscqp_worlds_count_(p->wld.set)) +
                                  " worlds (lscqp_plan_set_worlds), one per mission: another mission count needs other worlds, or none, first").c_str());
     if (!single) {
         if (p->s.n_agents != p->s.n_total)
             return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "a mission partition needs every agent on this device (n_agents == n_total): a sharded plan flies one mission");
         PLAN_TRY(lscqp_check_missions_(p->s.n_total, n_missions, mission_offsets));
-        if (p->decision != LSCQP_DECISION_ONE_WORKGROUP)
+        if (p->wp.decision != LSCQP_DECISION_ONE_WORKGROUP)
             return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "a partition of more than one mission keeps one workgroup per mission: set LSCQP_DECISION_ONE_WORKGROUP first");
     }
-    DeviceGuard g(p->device);
+    OnDevice on(p->device);
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_missions");
-    if (!single) {  // (everything that can fail comes before the plan changes)
-        int64_t* d = nullptr;
-        e = hipMalloc((void**)&d, (size_t)(n_missions + 1) * sizeof(int64_t));
-        if (e == hipSuccess) e = hipMemcpy(d, mission_offsets, (size_t)(n_missions + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
-        int rc = e != hipSuccess ? hip_fail(e, "lscqp_plan_set_missions") : (p->grid ? lscqp_grid_reserve_missions_(p->grid, p->s.n_total, n_missions) : LSCQP_OK);
+    lscqp_plan_s::Missions next;  // (one mission: empty)
+    dev_ptr<int32_t> wof;
+    if (!single) {
+        next.moff.assign(mission_offsets, mission_offsets + n_missions + 1);
+        PLAN_TRY(lscqp::dev_alloc(next.d_moff, next.moff.size(), "lscqp_plan_set_missions"));
+        e = hipMemcpy(next.d_moff.get(), mission_offsets, next.moff.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_missions");
+        if (p->wp.grid) PLAN_TRY(lscqp_grid_reserve_missions_(p->wp.grid.get(), p->s.n_total, n_missions));
         // worlds are set (the count is theirs): the agents' world index follows the NEW offsets -- an agent that changes mission changes world
-        int32_t* wof = nullptr;
-        if (rc == LSCQP_OK && p->worlds) rc = make_world_of(p->s.n_total, mission_offsets, n_missions, &wof);
-        if (rc != LSCQP_OK) {
-            if (d) (void)hipFree(d);
-            return rc;
-        }
-        if (wof) {
-            (void)hipFree(p->world_of);
-            p->world_of = wof;
-        }
-        if (p->d_moff) (void)hipFree(p->d_moff);
-        p->d_moff = d;
-        p->moff.assign(mission_offsets, mission_offsets + n_missions + 1);
-    } else {
-        if (p->d_moff) (void)hipFree(p->d_moff);
-        p->d_moff = nullptr;
-        p->moff.clear();
+        if (p->wld.set) PLAN_TRY(make_world_of(p->s.n_total, mission_offsets, n_missions, wof));
     }
+    if (wof) p->wld.world_of = std::move(wof);
+    p->mis = std::move(next);
     drop_graph(p);  // (a captured chain holds the old partition's launches)
-    p->fields_valid = false;
-    p->missions_pending = true;
-    if (p->rec) {  // (the record was built for the old partition and reads its device offsets: made again at the reset)
-        lscqp_record_destroy(p->rec);
-        p->rec = nullptr;
-    }
-    p->record_pending = p->rec_on;
+    p->wp.fields_valid = false;
+    p->rec.held.reset();  // (the record was built for the old partition and reads its device offsets: made again at the reset)
+    p->pending |= lscplan::kPendMissions | (p->rec.on ? lscplan::kPendRecord : 0u);
     return LSCQP_OK;
 }
 
@@ -930,7 +902,7 @@ int lscqp_plan_set_worlds(lscqp_plan p, lscqp_worlds worlds) {
     const lscplan::Shape& s = p->s;
     if (worlds) {
         const int K = lscqp_worlds_count_(worlds);
-        if (p->moff.empty())
+        if (p->mis.moff.empty())
             return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_worlds: the plan has no mission partition (lscqp_plan_set_missions first): world k belongs to mission k");
         if (K != p->n_missions())
             return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, ("lscqp_plan_set_worlds: " + std::to_string(K) + " worlds for " + std::to_string(p->n_missions()) +
@@ -941,10 +913,11 @@ int lscqp_plan_set_worlds(lscqp_plan p, lscqp_worlds worlds) {
             return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
                                     (std::string("lscqp_plan_set_worlds: the worlds differ from the map the plan was created with in ") + f).c_str());
     }
-    DeviceGuard g(p->device);
+    OnDevice on(p->device);
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_worlds");
-    int32_t* wof = nullptr;
+    lscqp_plan_s::Worlds next;
+    lscqp_grid grid = p->wp.grid.get();
     if (worlds) {  // (everything that can fail comes before the plan changes)
         const size_t nt = (size_t)s.n_total;
         std::vector<double> r(nt);
@@ -952,31 +925,27 @@ int lscqp_plan_set_worlds(lscqp_plan p, lscqp_worlds worlds) {
         if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_worlds");
         double rmax = 0;
         for (const double v : r) rmax = v > rmax ? v : rmax;
-        PLAN_TRY(make_world_of(s.n_total, p->moff.data(), p->n_missions(), &wof));
-        int rc = p->grid ? lscqp_grid_set_worlds(p->grid, worlds) : LSCQP_OK;
+        PLAN_TRY(make_world_of(s.n_total, p->mis.moff.data(), p->n_missions(), next.world_of));
+        int rc = grid ? lscqp_grid_set_worlds(grid, worlds) : LSCQP_OK;
         // The free-space tables for the agents of this plan, one margin for all worlds -- LAST of what can fail, because it is the one step
         // that reaches beyond the plan: it may rebuild the members' tables, which moves their generation counters (include/lscqp.h).  A
         // failure behind the grid's change puts the grid back
         if (rc == LSCQP_OK && rmax > 0) {
             rc = lscqp_worlds_prepare(worlds, rmax);
             if (rc == LSCQP_ERR_UNSUPPORTED) rc = LSCQP_OK;  // (maps too large for the table: the corridors work without it)
-            if (rc != LSCQP_OK && p->grid) (void)lscqp_grid_set_worlds(p->grid, p->worlds);
+            if (rc != LSCQP_OK && grid) (void)lscqp_grid_set_worlds(grid, p->wld.set);
         }
-        if (rc != LSCQP_OK) {
-            (void)hipFree(wof);
-            return rc;
-        }
-    } else if (p->grid) {
-        PLAN_TRY(lscqp_grid_set_worlds(p->grid, nullptr));
+        if (rc != LSCQP_OK) return rc;
+        next.set = worlds;
+        next.gen = lscqp_worlds_generation_(worlds);
+    } else if (grid) {
+        PLAN_TRY(lscqp_grid_set_worlds(grid, nullptr));
     }
     drop_graph(p);  // (a captured chain holds the other corridor node)
-    if (p->world_of) (void)hipFree(p->world_of);
-    p->world_of = wof;
-    p->worlds = worlds;
-    p->worlds_gen = worlds ? lscqp_worlds_generation_(worlds) : 0;
+    p->wld = std::move(next);
     if (p->map) p->map_gen = lscqp_map_generation_(p->map);  // (the plan's own map may be a member just prepared: nothing derived from it is left)
-    p->fields_valid = false;
-    p->worlds_pending = true;
+    p->wp.fields_valid = false;
+    p->pending |= lscplan::kPendWorlds;
     return LSCQP_OK;
 }
 
@@ -984,15 +953,15 @@ int lscqp_plan_set_waypoint_decision(lscqp_plan p, int32_t which) {
     if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
     if (which != LSCQP_DECISION_ONE_WORKGROUP && which != LSCQP_DECISION_WIDE && which != LSCQP_DECISION_AUTO)
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "which must be LSCQP_DECISION_ONE_WORKGROUP, LSCQP_DECISION_WIDE or LSCQP_DECISION_AUTO");
-    if (!p->grid) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the plan decides no waypoints (waypoint_mode = LSCQP_WAYPOINT_FROM_CALLER)");
+    if (!p->wp.grid) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "the plan decides no waypoints (waypoint_mode = LSCQP_WAYPOINT_FROM_CALLER)");
     if (which != LSCQP_DECISION_ONE_WORKGROUP && p->n_missions() > 1)
         return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "a partition of more than one mission keeps one workgroup per mission");
-    DeviceGuard g(p->device);
+    OnDevice on(p->device);
     const hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_waypoint_decision");
-    if (which != LSCQP_DECISION_ONE_WORKGROUP) PLAN_TRY(lscqp_grid_reserve_wide(p->grid, p->s.n_total));  // (before the plan changes)
+    if (which != LSCQP_DECISION_ONE_WORKGROUP) PLAN_TRY(lscqp_grid_reserve_wide(p->wp.grid.get(), p->s.n_total));  // (before the plan changes)
     drop_graph(p);  // (a captured chain holds the other form's launches)
-    p->decision = which;
+    p->wp.decision = which;
     return LSCQP_OK;
 }
 
@@ -1001,7 +970,7 @@ int lscqp_plan_missions(lscqp_plan p, int32_t* n_missions_out, int64_t* offsets_
     const int K = p->n_missions();
     *n_missions_out = K;
     if (offsets_out) {
-        if (K > 1) memcpy(offsets_out, p->moff.data(), (size_t)(K + 1) * sizeof(int64_t));
+        if (K > 1) memcpy(offsets_out, p->mis.moff.data(), (size_t)(K + 1) * sizeof(int64_t));
         else offsets_out[0] = 0, offsets_out[1] = p->s.n_total;
     }
     return LSCQP_OK;
@@ -1010,12 +979,12 @@ int lscqp_plan_missions(lscqp_plan p, int32_t* n_missions_out, int64_t* offsets_
 int lscqp_plan_mission_status(lscqp_plan p, int32_t* status_out) {
     if (!p || !status_out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
     const int K = p->n_missions();
-    if (!p->grid) {  // (no waypoint walk in this plan: nothing to report)
+    if (!p->wp.grid) {  // (no waypoint walk in this plan: nothing to report)
         for (int k = 0; k < K; k++) status_out[k] = 0;
         return LSCQP_OK;
     }
-    DeviceGuard g(p->device);
-    return K > 1 ? lscqp_grid_mission_status(p->grid, K, status_out) : lscqp_grid_status(p->grid, status_out);
+    OnDevice on(p->device);
+    return K > 1 ? lscqp_grid_mission_status(p->wp.grid.get(), K, status_out) : lscqp_grid_status(p->wp.grid.get(), status_out);
 }
 
 int lscqp_plan_set_record(lscqp_plan p, const lscqp_record_desc* desc) {
@@ -1027,31 +996,25 @@ int lscqp_plan_set_record(lscqp_plan p, const lscqp_record_desc* desc) {
             return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: the record needs every agent on this device (n_agents == n_total)");
         if (!(desc->goal_threshold >= 0)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: goal_threshold must be >= 0");
     }
-    DeviceGuard g(p->device);
+    OnDevice on(p->device);
     const hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_record");
     if (!desc) {
         drop_graph(p);  // (a captured chain ends in the record's node)
-        if (p->rec) lscqp_record_destroy(p->rec);
-        p->rec = nullptr;
-        p->rec_on = p->record_pending = false;
+        p->rec = {};
+        p->pending &= ~lscplan::kPendRecord;
         return LSCQP_OK;
     }
-    const lscqp_record_desc before = p->rec_desc;
-    p->rec_desc = *desc;
-    if (!p->missions_pending) {  // (otherwise the partition's device offsets are about to change: lscqp_plan_reset makes it)
-        const int rc = make_record(p);
-        if (rc != LSCQP_OK) {
-            p->rec_desc = before;
-            return rc;
-        }
-    }
+    // (with the partition pending its device offsets are about to change: lscqp_plan_reset makes the record)
+    if (!(p->pending & lscplan::kPendMissions)) PLAN_TRY(make_record(p, *desc));
     drop_graph(p);
-    p->rec_on = p->record_pending = true;
+    p->rec.desc = *desc;
+    p->rec.on = true;
+    p->pending |= lscplan::kPendRecord;
     return LSCQP_OK;
 }
 
-lscqp_record lscqp_plan_record(lscqp_plan p) { return p ? p->rec : nullptr; }
+lscqp_record lscqp_plan_record(lscqp_plan p) { return p ? p->rec.held.get() : nullptr; }
 
 int lscqp_plan_set_obstacles(lscqp_plan p, const lscqp_obstacle_param* param, int32_t n_dyn, const lscqp_obstacle_model* models) {
     if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
@@ -1067,57 +1030,44 @@ int lscqp_plan_set_obstacles(lscqp_plan p, const lscqp_obstacle_param* param, in
         prepared.assign(models, models + n_dyn);
         PLAN_TRY(lscqp_obstacle_model_prepare(prepared.data(), n_dyn));
     }
-    DeviceGuard g(p->device);
+    OnDevice on(p->device);
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_obstacles");
-    if (none) {
-        drop_graph(p);  // (a captured chain holds the obstacles' nodes and the slot split)
-        free_obstacles(p);
-        return LSCQP_OK;
+    lscqp_plan_s::Obstacles next;  // (none: empty)
+    if (!none) {  // (everything that can fail comes before the plan changes)
+        const size_t n = (size_t)p->s.n_agents, nd = (size_t)n_dyn;
+        std::vector<int32_t> hid((n ? n : 1) * nd);
+        for (size_t a = 0; a < n; a++)
+            for (size_t o = 0; o < nd; o++) hid[a * nd + o] = (int32_t)o;
+        const char* const what = "lscqp_plan_set_obstacles";
+        PLAN_TRY(lscqp::dev_alloc(next.d_models, nd, what));
+        PLAN_TRY(lscqp::dev_alloc(next.table, nd, what));
+        PLAN_TRY(lscqp::dev_alloc(next.ids, hid.size(), what));
+        PLAN_TRY(lscqp::dev_alloc(next.clock, 1, what));
+        PLAN_TRY(lscqp::dev_alloc(next.safety, n ? n : 1, what, true));
+        e = hipMemcpy(next.d_models.get(), prepared.data(), nd * sizeof(lscqp_obstacle_model), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(next.ids.get(), hid.data(), hid.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, what);
+        next.models.swap(prepared);
+        next.param = *param;
+        next.n_dyn = n_dyn;
+        PLAN_TRY(reset_obstacles(next));  // (so that the table can be read, and HELD entries written, before the reset)
     }
-    // (everything that can fail comes before the plan changes)
-    const size_t n = (size_t)p->s.n_agents, nd = (size_t)n_dyn;
-    void *dm = nullptr, *tab = nullptr, *ids = nullptr, *clk = nullptr, *saf = nullptr;
-    std::vector<int32_t> hid((n ? n : 1) * nd);
-    for (size_t a = 0; a < n; a++)
-        for (size_t o = 0; o < nd; o++) hid[a * nd + o] = (int32_t)o;
-    e = hipMalloc(&dm, nd * sizeof(lscqp_obstacle_model));
-    if (e == hipSuccess) e = hipMalloc(&tab, nd * sizeof(lscqp_obstacle));
-    if (e == hipSuccess) e = hipMalloc(&ids, hid.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&clk, sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&saf, (n ? n : 1) * sizeof(lscqp_safety_obs));
-    if (e == hipSuccess) e = hipMemcpy(dm, prepared.data(), nd * sizeof(lscqp_obstacle_model), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ids, hid.data(), hid.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(saf, 0, (n ? n : 1) * sizeof(lscqp_safety_obs));
-    if (e != hipSuccess) {
-        for (void* q : {dm, tab, ids, clk, saf})
-            if (q) (void)hipFree(q);
-        return hip_fail(e, "lscqp_plan_set_obstacles");
-    }
-    drop_graph(p);
-    free_obstacles(p);
-    p->d_obs_models = (lscqp_obstacle_model*)dm, p->obs_table = (lscqp_obstacle*)tab, p->obs_ids = (int32_t*)ids, p->obs_clock = (int32_t*)clk;
-    p->obs_safety = (lscqp_safety_obs*)saf;
-    p->obs_models.swap(prepared);
-    p->obs_param = *param;
-    p->n_dyn = n_dyn;
-    const int rc = reset_obstacles(p);  // (so that the table can be read, and HELD entries written, before the reset)
-    if (rc != LSCQP_OK) {
-        free_obstacles(p);
-        return rc;
-    }
-    p->obstacles_pending = true;
+    drop_graph(p);  // (a captured chain holds the obstacles' nodes and the slot split)
+    p->obs = std::move(next);
+    p->pending = none ? p->pending & ~lscplan::kPendObstacles : p->pending | lscplan::kPendObstacles;
     return LSCQP_OK;
 }
 
 namespace {
 void* obstacle_buffer(lscqp_plan_s* p, int32_t which, size_t* bytes) {
     *bytes = 0;
-    if (p->n_dyn == 0) return nullptr;
+    const lscqp_plan_s::Obstacles& o = p->obs;
+    if (o.n_dyn == 0) return nullptr;
     switch (which) {
-    case LSCQP_PLAN_OBS_TABLE: *bytes = (size_t)p->n_dyn * sizeof(lscqp_obstacle); return p->obs_table;
-    case LSCQP_PLAN_OBS_SAFETY: *bytes = (size_t)p->s.n_agents * sizeof(lscqp_safety_obs); return p->obs_safety;
-    case LSCQP_PLAN_OBS_CLOCK: *bytes = sizeof(int32_t); return p->obs_clock;
+    case LSCQP_PLAN_OBS_TABLE: *bytes = (size_t)o.n_dyn * sizeof(lscqp_obstacle); return o.table.get();
+    case LSCQP_PLAN_OBS_SAFETY: *bytes = (size_t)p->s.n_agents * sizeof(lscqp_safety_obs); return o.safety.get();
+    case LSCQP_PLAN_OBS_CLOCK: *bytes = sizeof(int32_t); return o.clock.get();
     }
     return nullptr;
 }
@@ -1141,7 +1091,7 @@ int lscqp_plan_obstacle_upload(lscqp_plan p, int32_t which, const void* host, ui
     void* q = obstacle_buffer(p, which, &b);
     if (offset > b || bytes > b - offset) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "range exceeds the buffer");
     if (bytes == 0) return LSCQP_OK;
-    DeviceGuard g(p->device);
+    OnDevice on(p->device);
     const hipError_t e = hipMemcpy((char*)q + offset, host, bytes, hipMemcpyHostToDevice);
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "plan obstacle upload");
 }
@@ -1152,7 +1102,7 @@ int lscqp_plan_obstacle_download(lscqp_plan p, int32_t which, void* host, uint64
     void* q = obstacle_buffer(p, which, &b);
     if (offset > b || bytes > b - offset) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "range exceeds the buffer");
     if (bytes == 0) return LSCQP_OK;
-    DeviceGuard g(p->device);
+    OnDevice on(p->device);
     const hipError_t e = hipMemcpy(host, (const char*)q + offset, bytes, hipMemcpyDeviceToHost);  // waits for the device
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "plan obstacle download");
 }
@@ -1160,8 +1110,8 @@ int lscqp_plan_obstacle_download(lscqp_plan p, int32_t which, void* host, uint64
 int lscqp_plan_run(lscqp_plan p, int64_t max_replans, int32_t check_every, int32_t use_graph, void* stream, int64_t* replans_enqueued) {
     if (replans_enqueued) *replans_enqueued = 0;
     if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
-    if (!p->rec_on) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_run: the plan has no record (lscqp_plan_set_record): nothing tells when a mission is over");
-    if (!p->d.closed_loop || !p->grid)
+    if (!p->rec.on) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_run: the plan has no record (lscqp_plan_set_record): nothing tells when a mission is over");
+    if (!p->d.closed_loop || !p->wp.grid)
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
                                 "lscqp_plan_run: closed_loop != 0 and waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT required (nothing else flies without host writes between replans)");
     if (max_replans < 1 || check_every < 1) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_run: max_replans >= 1 and check_every >= 1 required");
@@ -1174,8 +1124,8 @@ int lscqp_plan_run(lscqp_plan p, int64_t max_replans, int32_t check_every, int32
         }
         if (replans_enqueued) *replans_enqueued = done;
         int32_t left = 0;
-        DeviceGuard g(p->device);
-        PLAN_TRY(lscqp_record_unfinished_on_(p->rec, stream, &left));
+        OnDevice on(p->device);
+        PLAN_TRY(lscqp_record_unfinished_on_(p->rec.held.get(), stream, &left));
         if (left == 0) break;
     }
     return LSCQP_OK;

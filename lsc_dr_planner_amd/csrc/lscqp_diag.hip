@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/lscqp.h"
+#include "lscqp_device.hpp"
 #include "lscqp_internal.hpp"
 
 namespace {
@@ -258,6 +259,7 @@ int lscqp_diagnose(lscqp_handle h, int64_t n, const lscqp_header* hdr, const lsc
     char* dev = nullptr;
     const size_t total = al(b_hdr) + al(b_rows) + al(b_off) + al(b_sfc) + al(b_x) + al(b_out);
     if (hipMalloc(&dev, total) != hipSuccess) return fail(LSCQP_ERR_HIP, "hipMalloc failed");
+    const lscqp::dev_ptr<char> owner(dev);
     char* p = dev;
     hipError_t up = hipSuccess;  // the first upload that failed
     auto put = [&](const void* src, size_t b) -> char* {
@@ -274,13 +276,9 @@ int lscqp_diagnose(lscqp_handle h, int64_t n, const lscqp_header* hdr, const lsc
     const lscqp_box* d_sfc = (const lscqp_box*)put(sfc, b_sfc);
     const double* d_x = (const double*)put(x, b_x);
     lscqp_diag* d_out = (lscqp_diag*)p;
-    if (up != hipSuccess) {
-        (void)hipFree(dev);
-        return fail(LSCQP_ERR_HIP, std::string("hipMemcpy (H2D) failed: ") + hipGetErrorString(up));
-    }
+    if (up != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("hipMemcpy (H2D) failed: ") + hipGetErrorString(up));
     int rc = lscqp_diagnose_device(h, n, d_hdr, d_rows, d_off, b_sfc ? d_sfc : nullptr, d_x, tol, d_out, nullptr);
     if (rc == LSCQP_OK && hipMemcpy(out, d_out, b_out, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(LSCQP_ERR_HIP, "hipMemcpy (D2H) failed");
-    (void)hipFree(dev);
     return rc;
 }
 
@@ -489,10 +487,10 @@ extern "C" int lscqp_debug_calibrate_(int64_t bytes, void* stream) {
     bytes = bytes / 32 * 32;
     char* buf = nullptr;
     unsigned* sink = nullptr;
-    if (hipMalloc(&buf, (size_t)bytes) != hipSuccess || hipMalloc(&sink, 64) != hipSuccess) {
-        if (buf) (void)hipFree(buf);
-        return fail(LSCQP_ERR_HIP, "calibration: hipMalloc failed");
-    }
+    const bool got = hipMalloc(&buf, (size_t)bytes) == hipSuccess && hipMalloc(&sink, 64) == hipSuccess;
+    const lscqp::dev_ptr<char> buf_owner(buf);
+    const lscqp::dev_ptr<unsigned> sink_owner(sink);
+    if (!got) return fail(LSCQP_ERR_HIP, "calibration: hipMalloc failed");
     hipStream_t st = (hipStream_t)stream;
     (void)hipMemsetAsync(buf, 0, (size_t)bytes, st);
     (void)hipMemsetAsync(sink, 0, 64, st);
@@ -503,8 +501,6 @@ extern "C" int lscqp_debug_calibrate_(int64_t bytes, void* stream) {
     hipLaunchKernelGGL(lscqp_calib::write_kernel<8>, grid, block, 0, st, buf, bytes / 8);
     hipLaunchKernelGGL(lscqp_calib::write_kernel<16>, grid, block, 0, st, buf, bytes / 16);
     const hipError_t e = hipStreamSynchronize(st);
-    (void)hipFree(buf);
-    (void)hipFree(sink);
     if (e != hipSuccess) return fail(LSCQP_ERR_HIP, std::string("calibration kernels: ") + hipGetErrorString(e));
     return LSCQP_OK;
 }

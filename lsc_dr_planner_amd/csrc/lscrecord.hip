@@ -18,6 +18,7 @@
 
 #include "../../include/lscqp.h"
 #include "lscpost_traj.hpp"
+#include "lscqp_device.hpp"
 #include "lscqp_internal.hpp"
 
 
@@ -218,34 +219,17 @@ struct lscqp_record_s {
     lscrecord::Args a;  // (the per-step pointers are filled by lscqp_record_step_device)
     int K = 1;
     int device = 0;
-    std::vector<int64_t> off;  // [K + 1]
-    int64_t* d_off = nullptr;  // own copy of the offsets, or NULL where the caller's device copy is borrowed
-    float *goal = nullptr, *points = nullptr, *last = nullptr;
-    double* dist = nullptr;
-    lscqp_mission_record* rec = nullptr;
-    int32_t* unfinished = nullptr;
-    int32_t* h_word = nullptr;  // pinned: where lscqp_plan_run's 4-byte copies land
+    std::vector<int64_t> off;        // [K + 1]
+    lscqp::dev_ptr<int64_t> d_off;   // own copy of the offsets, or empty where the caller's device copy is borrowed
+    lscqp::dev_ptr<float> goal, points, last;
+    lscqp::dev_ptr<double> dist;
+    lscqp::dev_ptr<lscqp_mission_record> rec;
+    lscqp::dev_ptr<int32_t> unfinished;
+    lscqp::pinned_ptr<int32_t> h_word;  // pinned: where lscqp_plan_run's 4-byte copies land
 };
 
-namespace {
-
-int hip_fail(hipError_t e, const char* what) {
-    return lscqp_set_error_(LSCQP_ERR_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-        else prev = -1;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-}  // namespace
+using lscqp::hip_fail;
+using lscqp::OnDevice;
 
 extern "C" int lscqp_record_create_(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
                                     const int64_t* d_offsets_borrowed, int32_t n_samples, double record_time_step, double time_step, double z_2d,
@@ -262,7 +246,7 @@ extern "C" int lscqp_record_create_(lscqp_handle h, int64_t n_total, int32_t n_m
     }
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return lscqp_set_error_(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    lscqp_record_s* r = new lscqp_record_s();
+    std::unique_ptr<lscqp_record_s> r(new lscqp_record_s());
     memset(&r->a, 0, sizeof r->a);
     r->device = dev;
     r->K = single ? 1 : n_missions;
@@ -275,31 +259,30 @@ extern "C" int lscqp_record_create_(lscqp_handle h, int64_t n_total, int32_t n_m
     r->a.goal_threshold = desc->goal_threshold;
     r->a.n_total = n_total;
     const size_t nt = (size_t)n_total;
-    hipError_t e = hipSuccess;
+    const char* const what = "lscqp_record_create";
     if (!single && !d_offsets_borrowed) {
-        e = hipMalloc((void**)&r->d_off, (size_t)(n_missions + 1) * sizeof(int64_t));
-        if (e == hipSuccess) e = hipMemcpy(r->d_off, mission_offsets, (size_t)(n_missions + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
+        if (const int rc = lscqp::dev_alloc(r->d_off, (size_t)n_missions + 1, what)) return rc;
+        const hipError_t e = hipMemcpy(r->d_off.get(), mission_offsets, (size_t)(n_missions + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, what);
     }
-    if (e == hipSuccess) e = hipMalloc((void**)&r->goal, nt * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->points, nt * (size_t)n_samples * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->last, nt * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->dist, nt * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->rec, (size_t)r->K * sizeof(lscqp_mission_record));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->unfinished, sizeof(int32_t));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&r->h_word, sizeof(int32_t), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        lscqp_record_destroy(r);
-        return hip_fail(e, "lscqp_record_create");
+    if (const int rc = lscqp::dev_alloc(r->goal, nt * 3, what)) return rc;
+    if (const int rc = lscqp::dev_alloc(r->points, nt * (size_t)n_samples * 3, what)) return rc;
+    if (const int rc = lscqp::dev_alloc(r->last, nt * 3, what)) return rc;
+    if (const int rc = lscqp::dev_alloc(r->dist, nt, what)) return rc;
+    if (const int rc = lscqp::dev_alloc(r->rec, (size_t)r->K, what)) return rc;
+    if (const int rc = lscqp::dev_alloc(r->unfinished, 1, what)) return rc;
+    {
+        void* word = nullptr;
+        const hipError_t e = hipHostMalloc(&word, sizeof(int32_t), hipHostMallocDefault);
+        if (e != hipSuccess) return hip_fail(e, what);
+        r->h_word.reset((int32_t*)word);
     }
-    r->a.off = single ? nullptr : (d_offsets_borrowed ? d_offsets_borrowed : r->d_off);
-    r->a.goal = r->goal, r->a.points = r->points, r->a.last = r->last, r->a.dist = r->dist, r->a.rec = r->rec, r->a.unfinished = r->unfinished;
+    r->a.off = single ? nullptr : (d_offsets_borrowed ? d_offsets_borrowed : r->d_off.get());
+    r->a.goal = r->goal.get(), r->a.points = r->points.get(), r->a.last = r->last.get(), r->a.dist = r->dist.get(), r->a.rec = r->rec.get();
+    r->a.unfinished = r->unfinished.get();
     std::vector<double> zero(nt * 3, 0.0);
-    const int rc = lscqp_record_reset(r, zero.data());
-    if (rc != LSCQP_OK) {
-        lscqp_record_destroy(r);
-        return rc;
-    }
-    *out = r;
+    if (const int rc = lscqp_record_reset(r.get(), zero.data())) return rc;
+    *out = r.release();
     return LSCQP_OK;
 }
 
@@ -312,17 +295,14 @@ int lscqp_record_create(lscqp_handle h, int64_t n_total, int32_t n_missions, con
 
 void lscqp_record_destroy(lscqp_record r) {
     if (!r) return;
-    DeviceGuard g(r->device);
+    OnDevice on(r->device);
     (void)hipDeviceSynchronize();
-    for (void* q : {(void*)r->d_off, (void*)r->goal, (void*)r->points, (void*)r->last, (void*)r->dist, (void*)r->rec, (void*)r->unfinished})
-        if (q) (void)hipFree(q);
-    if (r->h_word) (void)hipHostFree(r->h_word);
     delete r;
 }
 
 int lscqp_record_reset(lscqp_record r, const double* goal_points) {
     if (!r || !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
-    DeviceGuard g(r->device);
+    OnDevice on(r->device);
     const size_t nt = (size_t)r->a.n_total;
     std::vector<float> gl(nt * 3);
     for (size_t i = 0; i < nt * 3; i++) gl[i] = (float)goal_points[i];
@@ -336,12 +316,12 @@ int lscqp_record_reset(lscqp_record r, const double* goal_points) {
     }
     const int32_t K = r->K;
     hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(r->goal, gl.data(), gl.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(r->rec, rec.data(), rec.size() * sizeof(lscqp_mission_record), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(r->unfinished, &K, sizeof K, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(r->dist, 0, nt * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(r->last, 0, nt * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(r->points, 0, nt * (size_t)r->a.n_samples * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(r->goal.get(), gl.data(), gl.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(r->rec.get(), rec.data(), rec.size() * sizeof(lscqp_mission_record), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(r->unfinished.get(), &K, sizeof K, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(r->dist.get(), 0, nt * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(r->last.get(), 0, nt * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(r->points.get(), 0, nt * (size_t)r->a.n_samples * 3 * sizeof(float));
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "lscqp_record_reset");
 }
 
@@ -362,10 +342,10 @@ int lscqp_record_step_device(lscqp_record r, const lscqp_header* d_hdr, const do
 
 int lscqp_record_download(lscqp_record r, lscqp_mission_record* out, double* agent_distance) {
     if (!r || !out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
-    DeviceGuard g(r->device);
+    OnDevice on(r->device);
     std::vector<double> dist((size_t)r->a.n_total);
-    hipError_t e = hipMemcpy(out, r->rec, (size_t)r->K * sizeof(lscqp_mission_record), hipMemcpyDeviceToHost);  // waits for the device
-    if (e == hipSuccess) e = hipMemcpy(dist.data(), r->dist, dist.size() * sizeof(double), hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpy(out, r->rec.get(), (size_t)r->K * sizeof(lscqp_mission_record), hipMemcpyDeviceToHost);  // waits for the device
+    if (e == hipSuccess) e = hipMemcpy(dist.data(), r->dist.get(), dist.size() * sizeof(double), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "lscqp_record_download");
     for (int k = 0; k < r->K; k++) {  // the agents' distances in id order
         double s = 0;
@@ -382,18 +362,18 @@ void* lscqp_record_points(lscqp_record r, uint64_t* bytes_out) {
         return nullptr;
     }
     if (bytes_out) *bytes_out = (uint64_t)r->a.n_total * (uint64_t)r->a.n_samples * 3 * sizeof(float);
-    return r->points;
+    return r->points.get();
 }
 
 int lscqp_record_unfinished(lscqp_record r, int32_t* unfinished_out) {
     if (!r || !unfinished_out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
-    DeviceGuard g(r->device);
-    const hipError_t e = hipMemcpy(unfinished_out, r->unfinished, sizeof(int32_t), hipMemcpyDeviceToHost);
+    OnDevice on(r->device);
+    const hipError_t e = hipMemcpy(unfinished_out, r->unfinished.get(), sizeof(int32_t), hipMemcpyDeviceToHost);
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "lscqp_record_unfinished");
 }
 
 int lscqp_record_unfinished_on_(lscqp_record r, void* stream, int32_t* unfinished_out) {
-    hipError_t e = hipMemcpyAsync(r->h_word, r->unfinished, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    hipError_t e = hipMemcpyAsync(r->h_word.get(), r->unfinished.get(), sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "lscqp_plan_run");
     *unfinished_out = *r->h_word;

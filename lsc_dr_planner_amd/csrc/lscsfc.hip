@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/lscqp.h"
+#include "lscqp_device.hpp"
 #include "lscqp_staging.hpp"
 #include "lscqp_internal.hpp"
 
@@ -41,13 +42,13 @@ struct lscqp_map_s {
     float world_min[3], world_max[3];
     int key0[3], dims[3];
     int radius_cells;
-    uint8_t* d_occ;
-    int32_t* d_nearest;
-    int32_t* d_sat = nullptr;  // lscqp_map_prepare: summed-area table of the cells that are NOT provably free for agents up to sat_margin
+    lscqp::dev_ptr<uint8_t> d_occ;
+    lscqp::dev_ptr<int32_t> d_nearest;
+    lscqp::dev_ptr<int32_t> d_sat;  // lscqp_map_prepare: summed-area table of the cells that are NOT provably free for agents up to sat_margin
     double sat_margin = 0;
     // staging of the host-pointer corridor call: a pinned buffer + device mirror + private stream per concurrent call (the map
     // handle is shared by all agents' CollisionConstraints: two threads must never share a staging buffer)
-    lscqp::StagePool* pool = nullptr;
+    std::unique_ptr<lscqp::StagePool> pool;
     int device = 0;           // the device the grids live on: a plan on another device must not be handed this map
     uint64_t generation = 0;  // bumped whenever the free-space table is rebuilt: captured graphs hold its margin by value
 };
@@ -57,7 +58,7 @@ extern "C" uint64_t lscqp_map_generation_(lscqp_map mp) { return mp->generation;
 extern "C" int lscqp_map_raw_(lscqp_map mp, double* res, float* world_min, float* world_max, int* key0, int* dims, const int32_t** d_nearest, int* device) {
     *res = mp->res;
     for (int k = 0; k < 3; k++) world_min[k] = mp->world_min[k], world_max[k] = mp->world_max[k], key0[k] = mp->key0[k], dims[k] = mp->dims[k];
-    *d_nearest = mp->d_nearest;
+    *d_nearest = mp->d_nearest.get();
     *device = mp->device;
     return 0;
 }
@@ -1339,7 +1340,7 @@ __global__ __launch_bounds__(kSfcThreads) LSCSFC_KERNEL_ATTR void construct_sfc_
 #define LSCSFC_HIP(call)                                                                                              \
     do {                                                                                                              \
         const hipError_t e_ = (call);                                                                                 \
-        if (e_ != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string(#call ": ") + hipGetErrorString(e_)).c_str()); \
+        if (e_ != hipSuccess) return lscqp::hip_fail(e_, #call);                                                      \
     } while (0)
 
 #ifdef LSCSFC_VARIANT_ONLY
@@ -1363,24 +1364,12 @@ extern "C" hipError_t lscsfc_launch_throughput_worlds_(const void* view, int mod
 struct lscqp_worlds_s {
     std::vector<lscqp_map> maps;
     std::vector<uint64_t> gens;  // the members' generation counters when the table was last written
-    void* d_table = nullptr;     // lscsfc::WorldPtrs[maps.size()]
+    lscqp::dev_ptr<lscsfc::WorldPtrs> d_table;  // [maps.size()]
     double sat_margin = 0;       // the one margin of all members' free-space tables; 0: the launch uses no table
     int device = 0;
 };
 
 namespace {
-
-// the set's device made current for a scope (its table and its members' tables are allocated, written and waited for there)
-struct WorldsDevice {
-    int prev = -1;
-    explicit WorldsDevice(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess || prev == dev) prev = -1;
-        else (void)hipSetDevice(dev);
-    }
-    ~WorldsDevice() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 bool worlds_stale(const lscqp_worlds_s* w) {
     for (size_t k = 0; k < w->maps.size(); k++)
@@ -1391,15 +1380,15 @@ bool worlds_stale(const lscqp_worlds_s* w) {
 // the table from the members as they are now.  Waits for the device first: no launch may be reading the rows it overwrites
 int worlds_write_table(lscqp_worlds_s* w) {
     const size_t K = w->maps.size();
-    WorldsDevice on(w->device);
+    lscqp::OnDevice on(w->device);  // (the set's table and its members' tables are allocated, written and waited for there)
     bool tables = true;
     for (size_t k = 0; k < K; k++)
         tables = tables && w->maps[k]->d_sat != nullptr && w->maps[k]->sat_margin > 0 && w->maps[k]->sat_margin == w->maps[0]->sat_margin;
     std::vector<lscsfc::WorldPtrs> rows(K);
-    for (size_t k = 0; k < K; k++) rows[k] = lscsfc::WorldPtrs{w->maps[k]->d_nearest, tables ? w->maps[k]->d_sat : nullptr};
+    for (size_t k = 0; k < K; k++) rows[k] = lscsfc::WorldPtrs{w->maps[k]->d_nearest.get(), tables ? w->maps[k]->d_sat.get() : nullptr};
     hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(w->d_table, rows.data(), K * sizeof(lscsfc::WorldPtrs), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("lscqp_worlds (table): ") + hipGetErrorString(e)).c_str());
+    if (e == hipSuccess) e = hipMemcpy(w->d_table.get(), rows.data(), K * sizeof(lscsfc::WorldPtrs), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return lscqp::hip_fail(e, "lscqp_worlds (table)");
     w->sat_margin = tables ? w->maps[0]->sat_margin : 0.0;
     for (size_t k = 0; k < K; k++) w->gens[k] = w->maps[k]->generation;
     return LSCQP_OK;
@@ -1440,31 +1429,20 @@ int lscqp_worlds_create(const lscqp_map* maps, int32_t n_worlds, lscqp_worlds* o
     int cur = 0;
     if (hipGetDevice(&cur) != hipSuccess || cur != maps[0]->device)
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_worlds_create: the maps live on another device than the current one");
-    lscqp_worlds_s* w = new lscqp_worlds_s();
+    std::unique_ptr<lscqp_worlds_s> w(new lscqp_worlds_s());
     w->maps.assign(maps, maps + n_worlds);
     w->gens.assign((size_t)n_worlds, 0);
     w->device = cur;
-    const hipError_t e = hipMalloc(&w->d_table, (size_t)n_worlds * sizeof(lscsfc::WorldPtrs));
-    if (e != hipSuccess) {
-        delete w;
-        return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("hipMalloc(worlds table): ") + hipGetErrorString(e)).c_str());
-    }
-    if (const int rc = worlds_write_table(w)) {
-        (void)hipFree(w->d_table);
-        delete w;
-        return rc;
-    }
-    *out = w;
+    if (const int rc = lscqp::dev_alloc(w->d_table, (size_t)n_worlds, "hipMalloc(worlds table)")) return rc;
+    if (const int rc = worlds_write_table(w.get())) return rc;
+    *out = w.release();
     return LSCQP_OK;
 }
 
 void lscqp_worlds_destroy(lscqp_worlds w) {
     if (!w) return;
-    if (w->d_table) {
-        WorldsDevice on(w->device);
-        (void)hipDeviceSynchronize();
-        (void)hipFree(w->d_table);
-    }
+    lscqp::OnDevice on(w->device);
+    (void)hipDeviceSynchronize();
     delete w;
 }
 
@@ -1481,7 +1459,7 @@ int lscqp_worlds_info(lscqp_worlds w, int32_t* n_worlds, int32_t* dims, int32_t*
 int lscqp_worlds_prepare(lscqp_worlds w, double max_radius) {
     if (!w) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null worlds");
     if (!(max_radius > 0)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "max_radius > 0 required");
-    WorldsDevice on(w->device);
+    lscqp::OnDevice on(w->device);
     // one margin for all: a member that already has a table for a larger radius keeps it (lscqp_map_prepare), so the others follow it
     double margin = max_radius;
     for (lscqp_map mp : w->maps)
@@ -1521,8 +1499,8 @@ int lscqp_map_create(const double* boxes, int64_t n_boxes, const double* world_m
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return lscqp_set_error_(LSCQP_ERR_NO_DEVICE, "no HIP device: lscqp has no CPU fallback");
-    lscqp_map_s* mp = new lscqp_map_s();
-    mp->pool = new lscqp::StagePool();
+    std::unique_ptr<lscqp_map_s> mp(new lscqp_map_s());
+    mp->pool.reset(new lscqp::StagePool());
     (void)hipGetDevice(&mp->device);
     mp->res = resolution;
     int64_t nvox = 1;
@@ -1531,56 +1509,34 @@ int lscqp_map_create(const double* boxes, int64_t n_boxes, const double* world_m
         mp->world_max[k] = (float)world_max[k];
         mp->key0[k] = lscsfc::key_of((double)mp->world_min[k], resolution);  // DynamicEDTOctomap bounding box keys
         mp->dims[k] = lscsfc::key_of((double)mp->world_max[k], resolution) - mp->key0[k] + 1;
-        if (mp->dims[k] <= 0) {
-            delete mp;
-            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "world_max must not be below world_min");
-        }
+        if (mp->dims[k] <= 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "world_max must not be below world_min");
         nvox *= mp->dims[k];
     }
     const int R = (int)floor(max_dist / resolution + 1e-9);
-    if (R > 120) {
-        delete mp;
-        return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "max_dist / resolution must be <= 120 cells");
-    }
+    if (R > 120) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "max_dist / resolution must be <= 120 cells");
     mp->radius_cells = R;
-    mp->d_occ = nullptr;
-    mp->d_nearest = nullptr;
-    double* d_boxes = nullptr;
-    int8_t *d_a = nullptr, *d_b = nullptr, *d_c = nullptr;
-    auto cleanup = [&]() {
-        if (d_boxes) (void)hipFree(d_boxes);
-        if (d_a) (void)hipFree(d_a);
-        if (d_b) (void)hipFree(d_b);
-        if (d_c) (void)hipFree(d_c);
-    };
-    auto fail = [&](hipError_t e, const char* what) {
-        cleanup();
-        if (mp->d_occ) (void)hipFree(mp->d_occ);
-        if (mp->d_nearest) (void)hipFree(mp->d_nearest);
-        delete mp;
-        return lscqp_set_error_(LSCQP_ERR_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-    };
+    lscqp::dev_ptr<double> d_boxes;
+    lscqp::dev_ptr<int8_t> d_a, d_b, d_c;  // scratch of the three passes: gone with this call, whichever way it ends
     hipError_t e;
-    if ((e = hipMalloc(&mp->d_occ, nvox)) != hipSuccess) return fail(e, "hipMalloc(occupancy)");
-    if ((e = hipMalloc(&mp->d_nearest, nvox * sizeof(int32_t))) != hipSuccess) return fail(e, "hipMalloc(nearest)");
-    if ((e = hipMalloc(&d_a, nvox)) != hipSuccess || (e = hipMalloc(&d_b, nvox)) != hipSuccess || (e = hipMalloc(&d_c, nvox)) != hipSuccess)
-        return fail(e, "hipMalloc(scratch)");
-    if ((e = hipMemset(mp->d_occ, 0, nvox)) != hipSuccess) return fail(e, "hipMemset");
+    if (const int rc = lscqp::dev_alloc(mp->d_occ, (size_t)nvox, "hipMalloc(occupancy)")) return rc;
+    if (const int rc = lscqp::dev_alloc(mp->d_nearest, (size_t)nvox, "hipMalloc(nearest)")) return rc;
+    for (lscqp::dev_ptr<int8_t>* q : {&d_a, &d_b, &d_c})
+        if (const int rc = lscqp::dev_alloc(*q, (size_t)nvox, "hipMalloc(scratch)")) return rc;
+    if ((e = hipMemset(mp->d_occ.get(), 0, nvox)) != hipSuccess) return lscqp::hip_fail(e, "hipMemset");
     if (n_boxes > 0) {
-        if ((e = hipMalloc(&d_boxes, n_boxes * 6 * sizeof(double))) != hipSuccess) return fail(e, "hipMalloc(boxes)");
-        if ((e = hipMemcpy(d_boxes, boxes, n_boxes * 6 * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy(boxes)");
-        hipLaunchKernelGGL(lscsfc::rasterise_kernel, dim3((unsigned)n_boxes), dim3(256), 0, 0, d_boxes, resolution, mp->key0[0], mp->key0[1],
-                           mp->key0[2], mp->dims[0], mp->dims[1], mp->dims[2], mp->d_occ);
+        if (const int rc = lscqp::dev_alloc(d_boxes, (size_t)n_boxes * 6, "hipMalloc(boxes)")) return rc;
+        if ((e = hipMemcpy(d_boxes.get(), boxes, n_boxes * 6 * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) return lscqp::hip_fail(e, "hipMemcpy(boxes)");
+        hipLaunchKernelGGL(lscsfc::rasterise_kernel, dim3((unsigned)n_boxes), dim3(256), 0, 0, d_boxes.get(), resolution, mp->key0[0], mp->key0[1],
+                           mp->key0[2], mp->dims[0], mp->dims[1], mp->dims[2], mp->d_occ.get());
     }
     const unsigned blocks = (unsigned)((nvox + 255) / 256);
-    hipLaunchKernelGGL(lscsfc::nearest_x_kernel, dim3(blocks), dim3(256), 0, 0, mp->dims[0], nvox, R, mp->d_occ, d_a);
-    hipLaunchKernelGGL(lscsfc::nearest_y_kernel, dim3(blocks), dim3(256), 0, 0, mp->dims[0], mp->dims[1], nvox, R, d_a, d_b, d_c);
-    hipLaunchKernelGGL(lscsfc::nearest_z_kernel, dim3(blocks), dim3(256), 0, 0, mp->dims[0], mp->dims[1], mp->dims[2], nvox, R, d_b, d_c,
-                       mp->d_nearest);
-    if ((e = hipGetLastError()) != hipSuccess) return fail(e, "map kernels");
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return fail(e, "map kernels");
-    cleanup();
-    *out = mp;
+    hipLaunchKernelGGL(lscsfc::nearest_x_kernel, dim3(blocks), dim3(256), 0, 0, mp->dims[0], nvox, R, mp->d_occ.get(), d_a.get());
+    hipLaunchKernelGGL(lscsfc::nearest_y_kernel, dim3(blocks), dim3(256), 0, 0, mp->dims[0], mp->dims[1], nvox, R, d_a.get(), d_b.get(), d_c.get());
+    hipLaunchKernelGGL(lscsfc::nearest_z_kernel, dim3(blocks), dim3(256), 0, 0, mp->dims[0], mp->dims[1], mp->dims[2], nvox, R, d_b.get(), d_c.get(),
+                       mp->d_nearest.get());
+    if ((e = hipGetLastError()) != hipSuccess) return lscqp::hip_fail(e, "map kernels");
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return lscqp::hip_fail(e, "map kernels");
+    *out = mp.release();
     return LSCQP_OK;
 }
 
@@ -1616,10 +1572,7 @@ int lscqp_map_create_from_csv(const char* path, const double* world_min, const d
 
 void lscqp_map_destroy(lscqp_map mp) {
     if (!mp) return;
-    if (mp->d_occ) (void)hipFree(mp->d_occ);
-    if (mp->d_nearest) (void)hipFree(mp->d_nearest);
-    if (mp->d_sat) (void)hipFree(mp->d_sat);
-    delete mp->pool;
+    lscqp::OnDevice on(mp->device);
     delete mp;
 }
 
@@ -1630,12 +1583,11 @@ int lscqp_map_prepare(lscqp_map mp, double max_radius) {
     const int nx = mp->dims[0], ny = mp->dims[1], nz = mp->dims[2];
     const int64_t nvox = (int64_t)nx * ny * nz;
     if (nvox > 0x7fffffffLL) return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "the free-space table counts cells in 32 bits: map too large (the corridors work without it)");
+    lscqp::OnDevice on(mp->device);
     hipError_t e = hipDeviceSynchronize();  // (no corridor launch may be reading the old table)
-    if (e != hipSuccess) return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("hipDeviceSynchronize: ") + hipGetErrorString(e)).c_str());
-    if (!mp->d_sat && (e = hipMalloc(&mp->d_sat, nvox * sizeof(int32_t))) != hipSuccess) {
-        mp->d_sat = nullptr;
-        return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("hipMalloc(free-space table): ") + hipGetErrorString(e)).c_str());
-    }
+    if (e != hipSuccess) return lscqp::hip_fail(e, "hipDeviceSynchronize");
+    if (!mp->d_sat)
+        if (const int rc = lscqp::dev_alloc(mp->d_sat, (size_t)nvox, "hipMalloc(free-space table)")) return rc;
     mp->sat_margin = 0;
     mp->generation++;
     // what the float arithmetic of the exact test can lose against the cell bound: the sample, the cell centre and centre -+ half a cell
@@ -1644,16 +1596,16 @@ int lscqp_map_prepare(lscqp_map mp, double max_radius) {
     for (int k = 0; k < 3; k++) wabs = fmax(wabs, fmax(fabs((double)mp->world_min[k]), fabs((double)mp->world_max[k])) + 2.0 * mp->res);
     const double slop = 1e-4 + 4.0 * wabs * 1.1920929e-7;
     hipLaunchKernelGGL(lscsfc::classify_free_kernel, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, 0, nx, ny, nz, mp->key0[0], mp->key0[1], mp->key0[2],
-                       mp->res, max_radius, slop, mp->d_nearest, mp->d_sat);
+                       mp->res, max_radius, slop, mp->d_nearest.get(), mp->d_sat.get());
     // x lines: one per (y, z); y lines: one per (x, z); z lines: one per (x, y)
     const int64_t lx = (int64_t)ny * nz, ly = (int64_t)nx * nz, lz = (int64_t)nx * ny;
-    hipLaunchKernelGGL(lscsfc::prefix_axis_kernel, dim3((unsigned)((lx + 255) / 256)), dim3(256), 0, 0, lx, nx, (int64_t)1, lx, (int64_t)nx, (int64_t)0, mp->d_sat);
-    hipLaunchKernelGGL(lscsfc::prefix_axis_kernel, dim3((unsigned)((ly + 255) / 256)), dim3(256), 0, 0, ly, ny, (int64_t)nx, (int64_t)nx, (int64_t)1, (int64_t)nx * ny, mp->d_sat);
-    hipLaunchKernelGGL(lscsfc::prefix_axis_kernel, dim3((unsigned)((lz + 255) / 256)), dim3(256), 0, 0, lz, nz, (int64_t)nx * ny, lz, (int64_t)1, (int64_t)0, mp->d_sat);
+    hipLaunchKernelGGL(lscsfc::prefix_axis_kernel, dim3((unsigned)((lx + 255) / 256)), dim3(256), 0, 0, lx, nx, (int64_t)1, lx, (int64_t)nx, (int64_t)0, mp->d_sat.get());
+    hipLaunchKernelGGL(lscsfc::prefix_axis_kernel, dim3((unsigned)((ly + 255) / 256)), dim3(256), 0, 0, ly, ny, (int64_t)nx, (int64_t)nx, (int64_t)1, (int64_t)nx * ny, mp->d_sat.get());
+    hipLaunchKernelGGL(lscsfc::prefix_axis_kernel, dim3((unsigned)((lz + 255) / 256)), dim3(256), 0, 0, lz, nz, (int64_t)nx * ny, lz, (int64_t)1, (int64_t)0, mp->d_sat.get());
     if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
         // the table stays allocated (a captured plan graph may still hold the pointer) but serves nobody: margin 0, and the bumped
         // generation makes every plan drop its graph before the next replan
-        return lscqp_set_error_(LSCQP_ERR_HIP, (std::string("free-space table: ") + hipGetErrorString(e)).c_str());
+        return lscqp::hip_fail(e, "free-space table");
     }
     mp->sat_margin = max_radius;
     return LSCQP_OK;
@@ -1668,8 +1620,8 @@ int lscqp_map_info(lscqp_map mp, int32_t* dims, int32_t* key0) {
 int lscqp_map_download(lscqp_map mp, uint8_t* occ, int32_t* nearest) {
     if (!mp) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null map");
     const int64_t nvox = (int64_t)mp->dims[0] * mp->dims[1] * mp->dims[2];
-    if (occ) LSCSFC_HIP(hipMemcpy(occ, mp->d_occ, nvox, hipMemcpyDeviceToHost));
-    if (nearest) LSCSFC_HIP(hipMemcpy(nearest, mp->d_nearest, nvox * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (occ) LSCSFC_HIP(hipMemcpy(occ, mp->d_occ.get(), nvox, hipMemcpyDeviceToHost));
+    if (nearest) LSCSFC_HIP(hipMemcpy(nearest, mp->d_nearest.get(), nvox * sizeof(int32_t), hipMemcpyDeviceToHost));
     return LSCQP_OK;
 }
 
@@ -1686,8 +1638,8 @@ static int launch_corridors(lscqp_map mp, int mode, int M, int64_t n, const doub
     v.wmax0 = mp->world_max[0], v.wmax1 = mp->world_max[1], v.wmax2 = mp->world_max[2];
     v.key00 = mp->key0[0], v.key01 = mp->key0[1], v.key02 = mp->key0[2];
     v.dims0 = mp->dims[0], v.dims1 = mp->dims[1], v.dims2 = mp->dims[2];
-    v.nearest = mp->d_nearest;
-    v.sat = mp->d_sat;
+    v.nearest = mp->d_nearest.get();
+    v.sat = mp->d_sat.get();
     v.sat_margin = mp->sat_margin;
     if (ws) v.nearest = nullptr, v.sat = nullptr, v.sat_margin = ws->sat_margin;  // (the pointers: the kernel's, from the table; margin 0 without tables)
     // Two builds of the one kernel source.  LATENCY (this file): 1024 threads per agent, one workgroup per CU -- the sixteen wavefronts
@@ -1711,10 +1663,10 @@ static int launch_corridors(lscqp_map mp, int mode, int M, int64_t n, const doub
     const bool tp = fits && (force ? (force[0] == 't') : (n > (int64_t)n_cu));
     hipError_t e;
     if (tp && ws) {
-        e = lscsfc_launch_throughput_worlds_(&v, mode, M, n, d_points, d_radius, d_sfc, d_status_out, ws->d_table, d_world_of, stream);
+        e = lscsfc_launch_throughput_worlds_(&v, mode, M, n, d_points, d_radius, d_sfc, d_status_out, ws->d_table.get(), d_world_of, stream);
     } else if (ws) {
         hipLaunchKernelGGL((lscsfc::construct_sfc_kernel<const lscsfc::WorldPtrs*, const int32_t*>), dim3((unsigned)n), dim3(lscsfc::kSfcThreads), 0, (hipStream_t)stream, v, mode, M, n, d_points,
-                           d_radius, d_sfc, d_status_out, (const lscsfc::WorldPtrs*)ws->d_table, d_world_of);
+                           d_radius, d_sfc, d_status_out, (const lscsfc::WorldPtrs*)ws->d_table.get(), d_world_of);
         e = hipGetLastError();
     } else if (tp) {
         e = lscsfc_launch_throughput_(&v, mode, M, n, d_points, d_radius, d_sfc, d_status_out, stream);

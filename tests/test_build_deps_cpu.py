@@ -30,6 +30,8 @@ def test_a_built_tree_schedules_nothing():
     ("lscsfc.hip", {"lscsfc.o", "lscsfc_tp.o"}),
     ("lscqp_staging.hpp", {"api.o", "lscsfc.o", "lscsfc_tp.o", "lscqp_comm.o"}),
     ("lscqp_internal.hpp", INTERNAL),
+    # (the units that keep host objects; not through lscqp_internal.hpp: the kernels-only units do not need it)
+    ("lscqp_device.hpp", {"lscplan.o", "lscgrid.o", "lscrecord.o", "lscsfc.o", "lscsfc_tp.o", "lscqp_diag.o"}),
 ])
 def test_a_touched_file_schedules_exactly_its_dependents(touched, objects):
     path = os.path.join(build.CSRC, touched)
