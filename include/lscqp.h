@@ -1160,6 +1160,61 @@ int lscqp_plan_set_record(lscqp_plan plan, const lscqp_record_desc* desc);
 lscqp_record lscqp_plan_record(lscqp_plan plan);
 int lscqp_plan_run(lscqp_plan plan, int64_t max_replans, int32_t check_every, int32_t use_graph, void* stream, int64_t* replans_enqueued);
 
+/* ---- the flight log: every replan's sampled states kept on the device ------------------------------------------------------------------
+ *
+ * The reference's second file per mission is the result log (MultiSyncSimulator::saveSimulationResultAsCSV, src/multi_sync_simulator.cpp
+ * :586-656): at every sample time of every replan each agent's position, velocity and acceleration and each obstacle's position and size;
+ * its replayer reads that file.  The record's points buffer holds the last replan only, and a flight through lscqp_plan_run or a replayed
+ * graph overwrites the plan buffer every replan.  A record with a log keeps every replan's rows: ONE more kernel (csrc/lscrecord.hip:
+ * flight_log_kernel), enqueued in front of the record's own on the same stream.  It reads the record's replan counter before the record
+ * increments it, so row r holds replan r; a thread owns one (agent, sample) pair and stores to that pair's slots alone -- no atomics, and
+ * nothing the record's kernel reads or writes is written.  A mission that has finished is logged no further (its record is frozen, so are
+ * its rows), and neither is one whose log is full: the record goes on counting, which is how overflow is told.
+ *
+ * Layout, mission-major so that one mission's log is one contiguous range.  off[] the partition, n_k = off[k+1] - off[k], S = n_samples,
+ * C = max_replans, r the replan, a the GLOBAL agent id, s the sample:
+ *   LSCQP_LOG_STATES     float  [ C*off[k]*S*9 + ((r*n_k + (a - off[k]))*S + s)*9 + {px,py,pz,vx,vy,vz,ax,ay,az} ]
+ *                        Trajectory::getStateAt of the float32 control points at s * record_time_step (csrc/lscpost_traj.hpp: state_at;
+ *                        axes >= dim: z_2d, at rest), float32 as State holds them.  The positions are the record's points, bit for bit.
+ *   LSCQP_LOG_FLAGS      int32  [ C*off[k] + r*n_k + (a - off[k]) ]   LSCQP_LOG_FLAG_* : the five per-agent conditions the record counts
+ *   LSCQP_LOG_OBSTACLES  float  [ ((k*C + r)*n_dyn + oi)*4 + {px,py,pz,radius} ]   the caller's table entry oi as it stands when the
+ *                        replan's log is written (in a plan: as the replan's advance left it).  One entry per replan: the reference
+ *                        logs the obstacle unchanged over a step's samples.
+ * Row (r, s) stands at time r * time_step + s * record_time_step.  Rows at or beyond a mission's `rows` are unspecified.
+ * lscqp_record_set_log        max_replans > 0 attaches a log of that capacity (zeroed once) with n_dyn >= 0 obstacle columns and no table;
+ *                             0 removes it.  Waits for the device.  A failed call leaves the record as it was.  lscqp_record_reset
+ *                             clears nothing of a log: rows restart at 0 because the counter does.  A record without a log enqueues
+ *                             exactly what it always did.
+ * lscqp_record_log_obstacles  the DEVICE table (borrowed, n_dyn entries) the obstacle columns are read from at every later step; NULL:
+ *                             none are written.
+ * lscqp_record_log            raw device pointer of one buffer (which = LSCQP_LOG_*) and its size, as lscqp_record_points.
+ * lscqp_record_log_rows       rows[k] = min(replans, max_replans) and, if not NULL, overflowed[k] = replans > max_replans, per mission,
+ *                             from the records; waits for the device.
+ * lscqp_record_log_download   replans [first_replan, first_replan + n_replans) of one mission to the host: states [n_replans][n_k][S][9],
+ *                             flags [n_replans][n_k], obstacles [n_replans][n_dyn][4]; any of the three may be NULL.  Waits for the
+ *                             device.  LSCQP_ERR_INVALID_ARGUMENT where the range exceeds the mission's rows.
+ * lscqp_plan_set_flight_log   max_replans > 0 gives the plan's record a log of that capacity (0: takes it away), with the plan's obstacle
+ *                             columns and table -- lscqp_plan_set_obstacles may come before or after.  Needs a record
+ *                             (lscqp_plan_set_record first; taking the record away takes the log with it).  lscqp_plan_reset must follow.
+ *                             The chain gains one node, immediately in front of the record's, which stays the last.  Because missions
+ *                             freeze, the log of a flight through lscqp_plan_run does not depend on check_every. */
+#define LSCQP_LOG_STATES 0
+#define LSCQP_LOG_FLAGS 1
+#define LSCQP_LOG_OBSTACLES 2
+#define LSCQP_LOG_COUNT 3
+#define LSCQP_LOG_FLAG_QP_FAILED 1    /* QP status != LSCQP_STATUS_OPTIMAL */
+#define LSCQP_LOG_FLAG_INVALID 2      /* valid == 0 */
+#define LSCQP_LOG_FLAG_GOAL_FAILED 4  /* goal LP status != 0 */
+#define LSCQP_LOG_FLAG_SFC_KEPT 8     /* sfc_status == 0 */
+#define LSCQP_LOG_FLAG_WAYPOINT 16    /* waypoint updated (never set where the step has no such buffer) */
+int lscqp_record_set_log(lscqp_record rec, int32_t max_replans, int32_t n_dyn);
+int lscqp_record_log_obstacles(lscqp_record rec, const lscqp_obstacle* d_table);
+void* lscqp_record_log(lscqp_record rec, int32_t which, uint64_t* bytes_out);
+int lscqp_record_log_rows(lscqp_record rec, int32_t* rows, int32_t* overflowed);
+int lscqp_record_log_download(lscqp_record rec, int32_t mission, int32_t first_replan, int32_t n_replans, float* states, int32_t* flags,
+                              float* obstacles);
+int lscqp_plan_set_flight_log(lscqp_plan plan, int32_t max_replans);
+
 /* ---- dynamic obstacles in the chain: their motion on the device, their rows and their safety figures ------------------------------------
  *
  * The reference's missions list dynamic obstacles (mission file "obstacles": spin, straight, patrol, chasing, gaussian, real; include/

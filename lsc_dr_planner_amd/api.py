@@ -226,6 +226,8 @@ EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_
                     "lscqp_safety_metrics_missions_device", "lscqp_grid_fields_missions_device", "lscqp_waypoints_missions_device", "lscqp_grid_mission_status",
                     "lscqp_record_create", "lscqp_record_destroy", "lscqp_record_reset", "lscqp_record_step_device", "lscqp_record_download",
                     "lscqp_record_points", "lscqp_record_unfinished", "lscqp_plan_set_record", "lscqp_plan_record", "lscqp_plan_run",
+                    "lscqp_record_set_log", "lscqp_record_log_obstacles", "lscqp_record_log", "lscqp_record_log_rows", "lscqp_record_log_download",
+                    "lscqp_plan_set_flight_log",
                     "lscqp_obstacle_model_prepare", "lscqp_obstacles_advance_device", "lscqp_plan_set_obstacles", "lscqp_plan_obstacle_buffer",
                     "lscqp_plan_obstacle_upload", "lscqp_plan_obstacle_download",
                     "lscqp_worlds_create", "lscqp_worlds_destroy", "lscqp_worlds_prepare", "lscqp_worlds_info", "lscqp_construct_sfc_worlds_device",
@@ -547,6 +549,11 @@ MISSION_RECORD_DTYPE = np.dtype([("finished", "i4"), ("replans", "i4"), ("first_
                                  ("goal_failed", "i8"), ("sfc_kept", "i8"), ("waypoint_updates", "i8"), ("max_in_range", "i8"), ("truncated", "i8")])
 
 
+# the flight log (include/lscqp.h, "the flight log"): the buffers of lscqp_record_log and the bits of a flags word
+LOG_STATES, LOG_FLAGS, LOG_OBSTACLES = 0, 1, 2
+LOG_FLAG_QP_FAILED, LOG_FLAG_INVALID, LOG_FLAG_GOAL_FAILED, LOG_FLAG_SFC_KEPT, LOG_FLAG_WAYPOINT = 1, 2, 4, 8, 16
+
+
 class RecordDesc(C.Structure):  # lscqp_record_desc
     _fields_ = [("goal_threshold", C.c_double)]
 
@@ -559,6 +566,8 @@ class Record:
                  handle=None, n_missions=None):
         self._r, self._own = None, handle is None
         self.n_total, self.n_samples = int(n_total), int(n_samples)
+        self.offsets = np.array([0, self.n_total], np.int64) if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        self.log_capacity, self.log_n_dyn = 0, 0
         if handle is not None:
             self._r, self.n_missions = handle, int(n_missions)
             return
@@ -614,6 +623,52 @@ class Record:
         w = C.c_int32()
         _call("lscqp_record_unfinished", self._r, C.byref(w))
         return int(w.value)
+
+    def set_log(self, max_replans, n_dyn=0):
+        """lscqp_record_set_log: a flight log of max_replans rows per mission with n_dyn obstacle columns (0 rows: none); waits for the device."""
+        _call("lscqp_record_set_log", self._r, int(max_replans), int(n_dyn))
+        self.log_capacity, self.log_n_dyn = int(max_replans), int(n_dyn) if max_replans else 0
+
+    def log_obstacles(self, d_table):
+        """lscqp_record_log_obstacles: the device table (OBSTACLE_DTYPE records, borrowed) the obstacle columns are read from; None: none."""
+        _call("lscqp_record_log_obstacles", self._r, d_table)
+
+    def log_tensor(self, which):
+        """One raw buffer of the log (LOG_STATES / LOG_OBSTACLES float32, LOG_FLAGS int32) as a flat torch tensor over the device memory
+        itself; the layout is include/lscqp.h's.  None for an empty buffer."""
+        import torch
+
+        nb = C.c_uint64()
+        ptr = lib().lscqp_record_log(self._r, int(which), C.byref(nb))
+        if not ptr:
+            raise LscqpError(ERR_INVALID_ARGUMENT, lib().lscqp_last_error().decode())
+        if nb.value == 0:
+            return None
+
+        class _View:
+            __cuda_array_interface__ = dict(shape=(nb.value // 4,), typestr="<i4" if which == LOG_FLAGS else "<f4", data=(ptr, False), version=2)
+
+        return torch.as_tensor(_View(), device="cuda")
+
+    def log_rows(self):
+        """lscqp_record_log_rows: (rows (K,) int32 = min(replans, capacity), overflowed (K,) int32); waits for the device."""
+        rows, over = np.zeros(self.n_missions, np.int32), np.zeros(self.n_missions, np.int32)
+        _call("lscqp_record_log_rows", self._r, rows, over)
+        return rows, over
+
+    def log(self, mission, first_replan=0, n_replans=None):
+        """lscqp_record_log_download: one mission's rows [first_replan, first_replan + n_replans) -- all of them by default -- as
+        (states (rows, n_k, S, 9) float32, flags (rows, n_k) int32, obstacles (rows, n_dyn, 4) float32); waits for the device."""
+        k = int(mission)
+        known = 0 <= k < self.n_missions  # (an unknown mission is the library's to refuse)
+        if n_replans is None:
+            n_replans = int(self.log_rows()[0][k]) - int(first_replan) if known else 0
+        n, n_k = int(n_replans), int(self.offsets[k + 1] - self.offsets[k]) if known else 0
+        st = np.zeros((max(n, 0), n_k, self.n_samples, 9), np.float32)
+        fl = np.zeros((max(n, 0), n_k), np.int32)
+        ob = np.zeros((max(n, 0), self.log_n_dyn, 4), np.float32)
+        _call("lscqp_record_log_download", self._r, k, int(first_replan), n, st, fl, ob)
+        return st, fl, ob
 
 
 AGENT_PARAM_DTYPE = np.dtype([("radius", "f8"), ("downwash", "f8"), ("max_vel", "f8", 3), ("max_acc", "f8", 3), ("nominal_velocity", "f8")])
@@ -811,13 +866,25 @@ class Plan:
     def set_record(self, goal_threshold=0.1):
         """lscqp_plan_set_record: the plan keeps a mission record, accumulated by the chain's last node (None: no record).  `reset` must follow."""
         _call("lscqp_plan_set_record", self._p, None if goal_threshold is None else C.byref(RecordDesc(float(goal_threshold))))
+        if goal_threshold is None:
+            self._log_capacity = 0  # (the log goes with the record)
 
     def record(self):
         """The plan's own Record (owned by the plan), None without one."""
         h = lib().lscqp_plan_record(self._p)
         if not h:
             return None
-        return Record(handle=C.c_void_p(h), n_total=self.n_total, n_samples=self._safety_samples, n_missions=len(self.missions()) - 1)
+        off = self.missions()
+        rec = Record(handle=C.c_void_p(h), n_total=self.n_total, n_samples=self._safety_samples, n_missions=len(off) - 1, offsets=off)
+        rec.log_capacity = getattr(self, "_log_capacity", 0)
+        rec.log_n_dyn = int(getattr(self, "n_dyn", 0)) if rec.log_capacity else 0
+        return rec
+
+    def set_flight_log(self, max_replans):
+        """lscqp_plan_set_flight_log: the plan's record keeps a flight log of max_replans rows per mission, with the plan's obstacle columns
+        (0: none).  Needs `set_record` first; `reset` must follow."""
+        _call("lscqp_plan_set_flight_log", self._p, int(max_replans))
+        self._log_capacity = int(max_replans)
 
     def run(self, max_replans, check_every=1, graph=True, stream=None):
         """lscqp_plan_run: replans until every mission of the record has finished or max_replans; returns the replans enqueued."""

@@ -196,8 +196,9 @@ struct HandleDestroy {
 };
 
 // the setters whose change waits for lscqp_plan_reset, in the order in which a step names them: bit i of lscqp_plan_s::pending
-enum : unsigned { kPendMissions = 1u << 0, kPendRecord = 1u << 1, kPendObstacles = 1u << 2, kPendWorlds = 1u << 3 };
-constexpr const char* kPendSetter[] = {"lscqp_plan_set_missions", "lscqp_plan_set_record", "lscqp_plan_set_obstacles", "lscqp_plan_set_worlds"};
+enum : unsigned { kPendMissions = 1u << 0, kPendRecord = 1u << 1, kPendObstacles = 1u << 2, kPendWorlds = 1u << 3, kPendFlightLog = 1u << 4 };
+constexpr const char* kPendSetter[] = {"lscqp_plan_set_missions", "lscqp_plan_set_record", "lscqp_plan_set_obstacles", "lscqp_plan_set_worlds",
+                                       "lscqp_plan_set_flight_log"};
 
 }  // namespace lscplan
 
@@ -256,6 +257,7 @@ struct lscqp_plan_s {
         bool on = false;
         lscqp_record_desc desc = {0.0};
         std::unique_ptr<lscqp_record_s, lscplan::RecordDestroy> held;  // of the partition in force; empty between set_missions and the reset
+        int32_t log_capacity = 0;  // the flight log's rows per mission (lscqp_plan_set_flight_log), 0 = none: given to every record made
     } rec;
     // dynamic obstacles (lscqp_plan_set_obstacles): n_dyn = 0 = none, the chain as it always was.  They take row slots [0, n_dyn) of every agent
     struct Obstacles {
@@ -423,7 +425,8 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     if (p->d.safety_samples > 0 && n_dyn > 0)
         PLAN_TRY(lscqp_safety_obstacles_device(h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan, p->radius,
                                                p->downwash, n_dyn, obs.table.get(), obs.safety.get(), stream));
-    // the mission record: the figures of this replan and the finish test on the state it started from (hdr.p0), the chain's last node
+    // the mission record: the figures of this replan and the finish test on the state it started from (hdr.p0), the chain's last node (a
+    // record with a flight log enqueues the log's node in front of its own)
     if (p->rec.on)
         PLAN_TRY(lscqp_record_step_device(p->rec.held.get(), hdr, x_plan, status, goal_status, sfc_status, valid, count, (const lscqp_safety*)p->buf[LSCQP_PLAN_BUF_SAFETY],
                                           (const int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
@@ -509,14 +512,23 @@ int make_fields(lscqp_plan_s* p) {
     return LSCQP_OK;
 }
 
+// the flight log of a plan's record: `capacity` rows per mission with the obstacle columns and the table of `o` (capacity 0: none)
+int give_log(lscqp_record r, int32_t capacity, const lscqp_plan_s::Obstacles& o) {
+    PLAN_TRY(lscqp_record_set_log(r, capacity, o.n_dyn));
+    if (capacity > 0) PLAN_TRY(lscqp_record_log_obstacles(r, o.n_dyn > 0 ? o.table.get() : nullptr));
+    return LSCQP_OK;
+}
+
 // the plan's record for the partition in force (its offsets are the ones the partition already has on the device); the old one is dropped
 int make_record(lscqp_plan_s* p, const lscqp_record_desc& desc) {
     lscqp_record rnew = nullptr;
     const bool one = p->mis.moff.empty();
     PLAN_TRY(lscqp_record_create_(p->h, p->s.n_total, one ? 1 : p->n_missions(), one ? nullptr : p->mis.moff.data(), one ? nullptr : p->mis.d_moff.get(),
                                   p->d.safety_samples, p->d.record_time_step, p->d.time_step, p->s.z_2d, &desc, &rnew));
+    decltype(p->rec.held) made(rnew);
+    PLAN_TRY(give_log(made.get(), p->rec.log_capacity, p->obs));
     drop_graph(p);  // (a captured chain holds the old record's buffers)
-    p->rec.held.reset(rnew);
+    p->rec.held = std::move(made);
     return LSCQP_OK;
 }
 
@@ -1001,8 +1013,8 @@ int lscqp_plan_set_record(lscqp_plan p, const lscqp_record_desc* desc) {
     if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_record");
     if (!desc) {
         drop_graph(p);  // (a captured chain ends in the record's node)
-        p->rec = {};
-        p->pending &= ~lscplan::kPendRecord;
+        p->rec = {};  // (its flight log with it)
+        p->pending &= ~(lscplan::kPendRecord | lscplan::kPendFlightLog);
         return LSCQP_OK;
     }
     // (with the partition pending its device offsets are about to change: lscqp_plan_reset makes the record)
@@ -1015,6 +1027,22 @@ int lscqp_plan_set_record(lscqp_plan p, const lscqp_record_desc* desc) {
 }
 
 lscqp_record lscqp_plan_record(lscqp_plan p) { return p ? p->rec.held.get() : nullptr; }
+
+int lscqp_plan_set_flight_log(lscqp_plan p, int32_t max_replans) {
+    if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
+    if (max_replans < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_flight_log: max_replans >= 0 required");
+    if (!p->rec.on)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_flight_log: the plan has no record (lscqp_plan_set_record first): the log is part of it");
+    OnDevice on(p->device);
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_flight_log");
+    // (without a record in hand -- the partition is pending -- lscqp_plan_reset makes one, with the log)
+    if (p->rec.held) PLAN_TRY(give_log(p->rec.held.get(), max_replans, p->obs));
+    drop_graph(p);  // (a captured chain has, or lacks, the log's node)
+    p->rec.log_capacity = max_replans;
+    p->pending = max_replans > 0 ? p->pending | lscplan::kPendFlightLog : p->pending & ~lscplan::kPendFlightLog;
+    return LSCQP_OK;
+}
 
 int lscqp_plan_set_obstacles(lscqp_plan p, const lscqp_obstacle_param* param, int32_t n_dyn, const lscqp_obstacle_model* models) {
     if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
@@ -1053,6 +1081,8 @@ int lscqp_plan_set_obstacles(lscqp_plan p, const lscqp_obstacle_param* param, in
         next.n_dyn = n_dyn;
         PLAN_TRY(reset_obstacles(next));  // (so that the table can be read, and HELD entries written, before the reset)
     }
+    // (a flight log has the obstacles' columns and reads their table: a new log for the new ones, before the plan changes)
+    if (p->rec.held && p->rec.log_capacity > 0) PLAN_TRY(give_log(p->rec.held.get(), p->rec.log_capacity, next));
     drop_graph(p);  // (a captured chain holds the obstacles' nodes and the slot split)
     p->obs = std::move(next);
     p->pending = none ? p->pending & ~lscplan::kPendObstacles : p->pending | lscplan::kPendObstacles;

@@ -7,12 +7,13 @@
 // One workgroup per mission, its threads stride over the mission's agents: sample points, distance, and the partial figures of its agents,
 // then ONE reduction across the workgroup (DPP moves within a wavefront, LDS across the four wavefronts, combined in wavefront order).  Every
 // reduced figure is a sum of integers, a maximum, or a minimum whose ties go to the lowest agent id: the result does not depend on how the
-// agents fall onto lanes.
+// agents fall onto lanes.  A record may carry a flight log (include/lscqp.h, "the flight log"): a second kernel, below the record's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -213,12 +214,67 @@ __global__ __launch_bounds__(kThreads) void record_kernel(Args A) {
     }
 }
 
+// ---- the flight log (include/lscqp.h, "the flight log"): every replan's sampled states, flags and obstacle entries, kept per mission ----
+//   MultiSyncSimulator::saveSimulationResultAsCSV   reference src/multi_sync_simulator.cpp:586-656 (what the rows become)
+// Enqueued IN FRONT of record_kernel on the same stream: it reads the replan counter the record is about to increment, so row r holds
+// replan r, and stream order is all the synchronisation there is.  A thread owns one (agent, sample) pair of mission blockIdx.x and
+// stores to that pair's slots alone; no LDS, no atomics, no barrier.
+struct LogArgs {
+    int capacity, n_dyn;  // rows per mission, obstacle columns
+    float* states;        // mission k at capacity * off[k] * S * 9: [capacity][n_k][S][9]
+    int32_t* flags;       // mission k at capacity * off[k]:         [capacity][n_k]
+    float* obstacles;     // [K][capacity][n_dyn][4]
+    const lscqp_obstacle* table;  // [n_dyn] or NULL: no obstacle entries are written
+};
+
+__global__ __launch_bounds__(kThreads) void flight_log_kernel(Args A, LogArgs L) {
+    const int k = blockIdx.x;
+    const lscqp_mission_record* R = A.rec + k;
+    if (R->finished != 0) return;  // frozen, as the record (the whole workgroup: one word, the same for every lane)
+    const int r = R->replans;
+    if (r >= L.capacity) return;  // full: the record goes on counting, lscqp_record_log_rows tells
+    const int64_t lo = A.off ? A.off[k] : 0, hi = A.off ? A.off[k + 1] : A.n_total;
+    const size_t n_k = (size_t)(hi - lo), S = (size_t)A.n_samples, cap = (size_t)L.capacity;
+    if (blockIdx.y == 0 && L.table)
+        for (int oi = threadIdx.x; oi < L.n_dyn; oi += kThreads) {
+            const lscqp_obstacle* O = L.table + oi;
+            float* o = L.obstacles + (((size_t)k * cap + (size_t)r) * (size_t)L.n_dyn + (size_t)oi) * 4;
+            o[0] = (float)O->position[0], o[1] = (float)O->position[1], o[2] = (float)O->position[2], o[3] = (float)O->radius;
+        }
+    const size_t i = (size_t)blockIdx.y * kThreads + threadIdx.x;  // (agent, sample) of the mission
+    if (i >= n_k * S) return;
+    const size_t al = i / S, s = i - al * S;
+    const int64_t a = lo + (int64_t)al;
+    float pos[3], vel[3], acc[3];
+    lscpost::state_at(A.M, A.dim, A.dt, (int)s * A.record_time_step, A.z_2d, A.x_all + a * (A.dim * 6 * A.M), pos, vel, acc);
+    float* o = L.states + cap * (size_t)lo * S * 9 + (((size_t)r * n_k + al) * S + s) * 9;
+    o[0] = pos[0], o[1] = pos[1], o[2] = pos[2];
+    o[3] = vel[0], o[4] = vel[1], o[5] = vel[2];
+    o[6] = acc[0], o[7] = acc[1], o[8] = acc[2];
+    if (s == 0) {  // the five per-agent conditions the record counts
+        int w = A.status[a] != LSCQP_STATUS_OPTIMAL ? LSCQP_LOG_FLAG_QP_FAILED : 0;
+        w |= A.valid[a] == 0 ? LSCQP_LOG_FLAG_INVALID : 0;
+        w |= A.goal_status[a] != 0 ? LSCQP_LOG_FLAG_GOAL_FAILED : 0;
+        w |= A.sfc_status[a] == 0 ? LSCQP_LOG_FLAG_SFC_KEPT : 0;
+        w |= (A.waypoint_updated && A.waypoint_updated[a] != 0) ? LSCQP_LOG_FLAG_WAYPOINT : 0;
+        L.flags[cap * (size_t)lo + (size_t)r * n_k + al] = w;
+    }
+}
+
 }  // namespace lscrecord
 
 struct lscqp_record_s {
     lscrecord::Args a;  // (the per-step pointers are filled by lscqp_record_step_device)
     int K = 1;
     int device = 0;
+    // the flight log (lscqp_record_set_log): capacity = 0 = none, the record enqueues what it always did
+    struct Log {
+        int32_t capacity = 0, n_dyn = 0;
+        unsigned tiles = 1;  // workgroups per mission: the largest mission's (agent, sample) pairs in tiles of kThreads
+        lscqp::dev_ptr<float> states, obstacles;
+        lscqp::dev_ptr<int32_t> flags;
+        const lscqp_obstacle* table = nullptr;  // borrowed (lscqp_record_log_obstacles)
+    } log;
     std::vector<int64_t> off;        // [K + 1]
     lscqp::dev_ptr<int64_t> d_off;   // own copy of the offsets, or empty where the caller's device copy is borrowed
     lscqp::dev_ptr<float> goal, points, last;
@@ -334,6 +390,11 @@ int lscqp_record_step_device(lscqp_record r, const lscqp_header* d_hdr, const do
     lscrecord::Args a = r->a;
     a.hdr = d_hdr, a.x_all = d_x_all, a.status = d_status, a.goal_status = d_goal_status, a.sfc_status = d_sfc_status, a.valid = d_valid;
     a.in_range = d_in_range, a.safety = d_safety, a.waypoint_updated = d_waypoint_updated;
+    if (r->log.capacity > 0) {  // in front of the record: row `replans` of every mission still flying
+        const lscqp_record_s::Log& g = r->log;
+        const lscrecord::LogArgs l = {g.capacity, g.n_dyn, g.states.get(), g.flags.get(), g.obstacles.get(), g.table};
+        hipLaunchKernelGGL(lscrecord::flight_log_kernel, dim3((unsigned)r->K, g.tiles), dim3(lscrecord::kThreads), 0, (hipStream_t)stream, a, l);
+    }
     hipLaunchKernelGGL(lscrecord::record_kernel, dim3((unsigned)r->K), dim3(lscrecord::kThreads), 0, (hipStream_t)stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "HIP launch failed (mission record)");
@@ -370,6 +431,100 @@ int lscqp_record_unfinished(lscqp_record r, int32_t* unfinished_out) {
     OnDevice on(r->device);
     const hipError_t e = hipMemcpy(unfinished_out, r->unfinished.get(), sizeof(int32_t), hipMemcpyDeviceToHost);
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "lscqp_record_unfinished");
+}
+
+int lscqp_record_set_log(lscqp_record r, int32_t max_replans, int32_t n_dyn) {
+    if (!r) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null record");
+    if (max_replans < 0 || n_dyn < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_record_set_log: max_replans >= 0 and n_dyn >= 0 required");
+    const size_t nt = (size_t)r->a.n_total, S = (size_t)r->a.n_samples, C = (size_t)max_replans, K = (size_t)r->K;
+    size_t pairs = 0;  // the largest mission's (agent, sample) pairs
+    for (size_t k = 0; k < K; k++) pairs = std::max(pairs, (size_t)(r->off[k + 1] - r->off[k]) * S);
+    const size_t tiles = std::max<size_t>(1, (pairs + lscrecord::kThreads - 1) / lscrecord::kThreads);
+    // (sizes in size_t; the bounds keep every product below 2^63 and the grid's second dimension a legal one)
+    if (tiles > 65535 || (double)C * (double)nt * (double)S * 36.0 > 0x1p46 || (double)K * (double)C * (double)n_dyn * 16.0 > 0x1p46)
+        return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_record_set_log: a log of this size is not kept (64 TiB, or more than 65535 tiles of 256 samples in a mission)");
+    OnDevice on(r->device);
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "lscqp_record_set_log");
+    lscqp_record_s::Log next;  // (none: empty)
+    if (max_replans > 0) {  // (everything that can fail comes before the record changes)
+        const char* const what = "lscqp_record_set_log";
+        if (const int rc = lscqp::dev_alloc(next.states, C * nt * S * 9, what, true)) return rc;
+        if (const int rc = lscqp::dev_alloc(next.flags, C * nt, what, true)) return rc;
+        if (const int rc = lscqp::dev_alloc(next.obstacles, std::max<size_t>(1, K * C * (size_t)n_dyn * 4), what, true)) return rc;
+        next.capacity = max_replans, next.n_dyn = n_dyn, next.tiles = (unsigned)tiles;  // (no table: lscqp_record_log_obstacles names it)
+    }
+    r->log = std::move(next);
+    return LSCQP_OK;
+}
+
+int lscqp_record_log_obstacles(lscqp_record r, const lscqp_obstacle* d_table) {
+    if (!r) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null record");
+    if (r->log.capacity == 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_record_log_obstacles: the record has no log (lscqp_record_set_log)");
+    if (d_table && r->log.n_dyn == 0)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_record_log_obstacles: the log has no obstacle columns (n_dyn = 0 at lscqp_record_set_log)");
+    r->log.table = d_table;
+    return LSCQP_OK;
+}
+
+void* lscqp_record_log(lscqp_record r, int32_t which, uint64_t* bytes_out) {
+    if (bytes_out) *bytes_out = 0;
+    if (!r || r->log.capacity == 0 || which < 0 || which >= LSCQP_LOG_COUNT) {
+        lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, !r ? "null record" : r->log.capacity == 0 ? "lscqp_record_log: the record has no log (lscqp_record_set_log)" : "unknown log buffer");
+        return nullptr;
+    }
+    const lscqp_record_s::Log& g = r->log;
+    const uint64_t C = (uint64_t)g.capacity, nt = (uint64_t)r->a.n_total, S = (uint64_t)r->a.n_samples;
+    switch (which) {
+    case LSCQP_LOG_STATES:
+        if (bytes_out) *bytes_out = C * nt * S * 9 * sizeof(float);
+        return g.states.get();
+    case LSCQP_LOG_FLAGS:
+        if (bytes_out) *bytes_out = C * nt * sizeof(int32_t);
+        return g.flags.get();
+    default:
+        if (bytes_out) *bytes_out = (uint64_t)r->K * C * (uint64_t)g.n_dyn * 4 * sizeof(float);
+        return g.obstacles.get();
+    }
+}
+
+int lscqp_record_log_rows(lscqp_record r, int32_t* rows, int32_t* overflowed) {
+    if (!r || !rows) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    if (r->log.capacity == 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_record_log_rows: the record has no log (lscqp_record_set_log)");
+    OnDevice on(r->device);
+    std::vector<lscqp_mission_record> rec((size_t)r->K);
+    const hipError_t e = hipMemcpy(rec.data(), r->rec.get(), rec.size() * sizeof(lscqp_mission_record), hipMemcpyDeviceToHost);  // waits for the device
+    if (e != hipSuccess) return hip_fail(e, "lscqp_record_log_rows");
+    for (int k = 0; k < r->K; k++) {
+        rows[k] = std::min(rec[(size_t)k].replans, r->log.capacity);
+        if (overflowed) overflowed[k] = rec[(size_t)k].replans > r->log.capacity;
+    }
+    return LSCQP_OK;
+}
+
+int lscqp_record_log_download(lscqp_record r, int32_t mission, int32_t first_replan, int32_t n_replans, float* states, int32_t* flags, float* obstacles) {
+    if (!r) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null record");
+    const lscqp_record_s::Log& g = r->log;
+    if (g.capacity == 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_record_log_download: the record has no log (lscqp_record_set_log)");
+    if (mission < 0 || mission >= r->K || first_replan < 0 || n_replans < 0)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_record_log_download: 0 <= mission < n_missions, first_replan >= 0 and n_replans >= 0 required");
+    OnDevice on(r->device);
+    lscqp_mission_record m;
+    hipError_t e = hipMemcpy(&m, r->rec.get() + mission, sizeof m, hipMemcpyDeviceToHost);  // waits for the device
+    if (e != hipSuccess) return hip_fail(e, "lscqp_record_log_download");
+    const int64_t rows = std::min(m.replans, g.capacity);
+    if ((int64_t)first_replan + n_replans > rows)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, ("lscqp_record_log_download: replans [" + std::to_string(first_replan) + ", " +
+                                                             std::to_string((int64_t)first_replan + n_replans) + ") exceed the mission's " +
+                                                             std::to_string(rows) + " logged rows").c_str());
+    if (n_replans == 0) return LSCQP_OK;
+    const size_t lo = (size_t)r->off[(size_t)mission], n_k = (size_t)r->off[(size_t)mission + 1] - lo, S = (size_t)r->a.n_samples, C = (size_t)g.capacity;
+    const size_t f = (size_t)first_replan, n = (size_t)n_replans, nd = (size_t)g.n_dyn;
+    if (states) e = hipMemcpy(states, g.states.get() + C * lo * S * 9 + f * n_k * S * 9, n * n_k * S * 9 * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && flags) e = hipMemcpy(flags, g.flags.get() + C * lo + f * n_k, n * n_k * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && obstacles && nd > 0)
+        e = hipMemcpy(obstacles, g.obstacles.get() + (((size_t)mission * C + f) * nd) * 4, n * nd * 4 * sizeof(float), hipMemcpyDeviceToHost);
+    return e == hipSuccess ? LSCQP_OK : hip_fail(e, "lscqp_record_log_download");
 }
 
 int lscqp_record_unfinished_on_(lscqp_record r, void* stream, int32_t* unfinished_out) {

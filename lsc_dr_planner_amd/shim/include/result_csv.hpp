@@ -78,6 +78,36 @@ public:
         }
     }
 
+    // one mission's flight log as lscqp_record_log_download hands it over (include/lscqp.h, "the flight log"): states
+    // [n_replans][qn][n_samples][9] = px,py,pz,vx,vy,vz,ax,ay,az in float32 -- what State holds -- and obstacles [n_replans][on][4] =
+    // px,py,pz,radius (NULL with on = 0), the table as it stood at the end of the replan, repeated over the replan's samples as the
+    // reference does (see writeStep).  Row (r, s) stands at t0 + r * time_step + s * record_time_step.  planning_time [n_replans][qn] is the
+    // caller's: host wall time, which no device log holds.
+    void writeFlight(double t0, double time_step, double record_time_step, size_t n_replans, size_t n_samples, const float* states,
+                     const float* obstacles, const std::vector<double>& planning_time) {
+        if (!states || (on_ != 0 && !obstacles) || planning_time.size() < n_replans * qn_)
+            throw std::invalid_argument("SimulationResultCsv::writeFlight: no states / no obstacle rows / fewer planning times than n_replans x agents");
+        std::vector<State> row(qn_);
+        std::vector<ObstacleSample> obs(on_);
+        std::vector<double> pt(qn_);
+        for (size_t r = 0; r < n_replans; r++) {
+            for (size_t qi = 0; qi < qn_; qi++) pt[qi] = planning_time[r * qn_ + qi];
+            for (size_t oi = 0; oi < on_; oi++) {
+                const float* o = obstacles + (r * on_ + oi) * 4;
+                obs[oi].px = o[0], obs[oi].py = o[1], obs[oi].pz = o[2], obs[oi].size = o[3];
+            }
+            for (size_t s = 0; s < n_samples; s++) {
+                for (size_t qi = 0; qi < qn_; qi++) {
+                    const float* v = states + ((r * qn_ + qi) * n_samples + s) * 9;
+                    row[qi].position = point3d(v[0], v[1], v[2]);
+                    row[qi].velocity = point3d(v[3], v[4], v[5]);
+                    row[qi].acceleration = point3d(v[6], v[7], v[8]);
+                }
+                writeRow(t0 + (double)r * time_step + (double)s * record_time_step, row, pt, obs);
+            }
+        }
+    }
+
 private:
     std::ostream& os_;
     size_t qn_, on_;

@@ -160,8 +160,34 @@ def load_obstacles(path):
     return api.obstacle_models(doc["obstacles"] if isinstance(doc, dict) else doc)
 
 
+def _g(v):
+    """A number as std::ostream prints it by default, which is how the reference writes its logs: printf's %g, six significant digits."""
+    return "%g" % float(v)
+
+
+def write_flight_csv(path, states, obstacles, time_step, record_time_step, planning_time=0.0):
+    """One mission's flight log (api.Record.log: states (rows, n, S, 9), obstacles (rows, n_dyn, 4)) as the reference's result log
+    (MultiSyncSimulator::saveSimulationResultAsCSV, src/multi_sync_simulator.cpp:586-656; the shim's SimulationResultCsv::writeFlight writes
+    the same file): per agent "id,t,px,py,pz,vx,vy,vz,ax,ay,az,planning_time", per obstacle "obs_id,t,px,py,pz,size", one line per sample
+    time.  planning_time is host wall time, which the device log does not hold: the caller's, one number or (rows, n) per replan and agent."""
+    rows, n, S, _ = states.shape
+    n_dyn = obstacles.shape[1]
+    pt = np.broadcast_to(np.asarray(planning_time, np.float64), (rows, n))
+    with open(path, "w") as f:
+        f.write(",".join(["id,t,px,py,pz,vx,vy,vz,ax,ay,az,planning_time"] * n + ["obs_id,t,px,py,pz,size"] * n_dyn) + "\n")
+        for r in range(rows):
+            for s in range(S):
+                t = _g(r * time_step + s * record_time_step)
+                fields = []
+                for q in range(n):
+                    fields += [str(q), t] + [_g(v) for v in states[r, q, s]] + [_g(pt[r, q])]
+                for o in range(n_dyn):
+                    fields += [str(o), t] + [_g(v) for v in obstacles[r, o]]
+                f.write(",".join(fields) + "\n")
+
+
 def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=0, graph=True, until_finished=None, check_every=16,
-                 goal_threshold=0.1, obstacles=None, worlds=None, obstacle_rows="lsc"):
+                 goal_threshold=0.1, obstacles=None, worlds=None, obstacle_rows="lsc", log_csv=None):
     """`missions` seeded missions over one world flown by ONE lscqp_plan with a mission partition (include/lscqp.h, "many missions over one
     map"): waypoint_mode 1, closed loop, one captured graph per replan.  The summary has the figures of `run` per mission.
     until_finished = MAX: the plan keeps a mission record (include/lscqp.h, "the mission record") and lscqp_plan_run flies it until every
@@ -171,7 +197,11 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     of GEN_CLSC); "clsc": the plan stays in GEN_CLSC, the mode the reference's launch files run, and the obstacles get generateCLSC's rows
     like an in-range agent.  They take the first row slots: n_obs counts the agent slots, the plan gets n_obs + len(obstacles).
     worlds: one world per mission (load_worlds) in the world's box -- mission k flies over world k (include/lscqp.h, "each mission over its
-    own world"; lscqp_plan_set_worlds), its seeded agents drawn from the free nodes of its own world; world 0 replaces the world's own boxes."""
+    own world"; lscqp_plan_set_worlds), its seeded agents drawn from the free nodes of its own world; world 0 replaces the world's own boxes.
+    log_csv (with until_finished): a directory; the plan keeps a flight log of MAX rows per mission (include/lscqp.h, "the flight log") and
+    every mission's result log is written there in the reference's format, mission_<k>.csv (write_flight_csv)."""
+    if log_csv and not until_finished:
+        raise ValueError("log_csv needs until_finished=MAX: the flight log's capacity")
     world_boxes = None if worlds is None else load_worlds(worlds, missions)  # (before anything needs a device)
     import torch
 
@@ -209,9 +239,18 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
         plan.set_obstacles(obstacles)
     if until_finished:
         plan.set_record(goal_threshold)
+        if log_csv:
+            plan.set_flight_log(int(until_finished))
         plan.reset(starts, goals)
         enqueued = plan.run(int(until_finished), check_every=check_every, graph=graph)
         rec, _ = plan.record().download()
+        csv_files = []
+        if log_csv:
+            os.makedirs(log_csv, exist_ok=True)
+            for k in range(missions):
+                st, _, ob = plan.record().log(k)
+                csv_files.append(os.path.join(log_csv, "mission_%d.csv" % k))
+                write_flight_csv(csv_files[-1], st, ob, dt, 0.1)
         status = plan.mission_status()
         per = [dict(mission=k, agents=n, finished=int(r["finished"]), replans=int(r["replans"]), flight_time_s=float(r["flight_time"]),
                     flight_distance_m=float(r["distance"]), qp_failed=int(r["qp_failed"]), first_qp_failed_replan=int(r["first_qp_failed_replan"]),
@@ -228,6 +267,8 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
             log.update(obstacles=n_dyn, last_obstacle_safety_ratio=float(plan.get_obstacles(api.PLAN_OBS_SAFETY)["safety_ratio_obs"].min()))
         if world_set:
             log["worlds"] = len(world_set)
+        if log_csv:
+            log["log_csv"] = csv_files
         plan.close()
         if world_set:
             world_set.close()
@@ -275,7 +316,7 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
 
 
 def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None, router="host", missions=None,
-        decision="one", until_finished=None, obstacles=None, worlds=None, obstacle_rows="lsc"):
+        decision="one", until_finished=None, obstacles=None, worlds=None, obstacle_rows="lsc", log_csv=None):
     """script (optional): {"waypoint": (K, N, 3), "state": (K, N, 9)} -- replay of a recorded mission: replan k takes every agent's
     state and waypoint from the script instead of the loop's own step / router (the plans, goal points, corridors and neighbour sets are
     still the loop's own), and the result carries every replan's solution (`x`, (K, N, nv)) and goal point (`goal`, (K, N, 3)).
@@ -286,7 +327,8 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
     until_finished (with missions): fly until every mission has finished, at most that many replans (run_missions).
     obstacles (with missions): dynamic obstacles flown by the plan's own chain (load_obstacles, run_missions); obstacle_rows "lsc" or "clsc":
     the generator of their rows, and with it the plan's constraint mode (run_missions).
-    worlds (with missions): one world per mission -- a directory of world CSVs, a list of CSV paths or of box lists (load_worlds, run_missions)."""
+    worlds (with missions): one world per mission -- a directory of world CSVs, a list of CSV paths or of box lists (load_worlds, run_missions).
+    log_csv (with until_finished): a directory for every mission's result log in the reference's format, from the device's flight log."""
     if router not in ("host", "device"):
         raise ValueError("router must be 'host' or 'device'")
     if decision not in ("one", "wide", "auto"):
@@ -297,9 +339,11 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
         raise ValueError("obstacles need missions=K (K >= 1): they fly in the chain of an lscqp_plan (lscqp_plan_set_obstacles)")
     if worlds is not None and not missions:
         raise ValueError("worlds need missions=K: world k belongs to mission k of an lscqp_plan (lscqp_plan_set_worlds)")
+    if log_csv and not until_finished:
+        raise ValueError("log_csv needs until_finished=MAX with missions=K: the log is the plan's flight log, MAX rows per mission")
     if missions:
         return run_missions(world_json, int(missions), steps=steps, M=M, dt=dt, n_obs=n_obs, until_finished=until_finished, obstacles=obstacles,
-                            worlds=worlds, obstacle_rows=obstacle_rows)
+                            worlds=worlds, obstacle_rows=obstacle_rows, log_csv=log_csv)
     import torch
 
     from lsc_dr_planner_amd import api
@@ -510,9 +554,11 @@ if __name__ == "__main__":
     ap.add_argument("--worlds", default=None, nargs="+", metavar="CSV",
                     help="with --missions K: K world CSVs (or one directory holding K) in the world's box -- mission k flies over world k, as "
                          "launch/test_all_*.launch pair a mission directory with a world directory")
+    ap.add_argument("--log-csv", default=None, metavar="DIR",
+                    help="with --until-finished: keep the flight log on the device and write every mission's result log in the reference's format to DIR/mission_<k>.csv")
     ap.add_argument("--router", default="host", choices=("host", "device"), help="where the waypoints come from: the host stand-in or lscqp_waypoints_device")
     a = ap.parse_args()
     world = random_forest_world(a.forest) if a.forest > 0 else a.world
     print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router, missions=a.missions, decision=a.decision,
                          until_finished=a.until_finished, obstacles=load_obstacles(a.obstacles) if a.obstacles else None, worlds=a.worlds,
-                         obstacle_rows=a.obstacle_rows)))
+                         obstacle_rows=a.obstacle_rows, log_csv=a.log_csv)))
