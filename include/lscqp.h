@@ -1233,9 +1233,10 @@ int lscqp_plan_set_flight_log(lscqp_plan plan, int32_t max_replans);
  *   LSCQP_OBSTACLE_SPIN      SpinObstacle (:83-136): `start` rotated about the axis (axis_point, axis_direction) at angular speed
  *                            speed / spin radius, in double; the velocity is the position's offset turned by 90 degrees about the axis
  *                            times the angular speed, as the reference forms it.
- *   LSCQP_OBSTACLE_HELD      the kernel leaves the table entry alone: the caller writes position and velocity between eager replans
- *                            (chasing, gaussian and real obstacles, whose motion is not modelled here).  `start` is where the entry is
- *                            put by lscqp_plan_set_obstacles / lscqp_plan_reset.
+ *   LSCQP_OBSTACLE_HELD      lscqp_obstacles_advance_device leaves the table entry alone.  Without a drive ("chasing and gaussian
+ *                            obstacles" below) the caller writes position and velocity between eager replans (real obstacles; chasing
+ *                            and gaussian ones played on the host); with a drive the entry is moved on the device, in front of the
+ *                            advance.  `start` is where the entry is put by lscqp_plan_set_obstacles / lscqp_plan_reset.
  * Positions and velocities are point3d in the reference: the kernel writes float32 values held in double, formed with the reference's
  * own mix of float and double operations and without fused multiply-adds.
  * lscqp_obstacle_model_prepare   HOST, no device needed: checks n models and fills their derived fields in place -- per leg the
@@ -1303,6 +1304,86 @@ int lscqp_plan_set_obstacles(lscqp_plan plan, const lscqp_obstacle_param* param,
 void* lscqp_plan_obstacle_buffer(lscqp_plan plan, int32_t which, uint64_t* bytes_out);
 int lscqp_plan_obstacle_upload(lscqp_plan plan, int32_t which, const void* host, uint64_t offset, uint64_t bytes);
 int lscqp_plan_obstacle_download(lscqp_plan plan, int32_t which, void* host, uint64_t offset, uint64_t bytes);
+
+/* ---- chasing and gaussian obstacles: the two models whose next state needs more than the time -------------------------------------------
+ *
+ * ChasingObstacle (include/obstacle.hpp:267-364) accelerates towards a goal point and away from the other obstacles as the previous update
+ * left them; GaussianObstacle (:366-469) integrates a history of accelerations, one per acc_update_cycle.  Both stay LSCQP_OBSTACLE_HELD
+ * models -- the advance does not touch them -- and get a DRIVE: one more record per obstacle, in a table beside the models, and one more
+ * kernel in front of the advance that moves every driven entry by one replan.  Radius, max_acc, downwash and `start` are the model's.
+ *   LSCQP_DRIVE_NONE      no drive: the entry is the caller's, as ever.
+ *   LSCQP_DRIVE_CHASING   getChasingObstacle (:313-363), ONE update per replan with dt = t(r) - t(r - 1) of the obstacle clock r (0 at r = 0:
+ *                         t_last_called starts at 0): a = gamma_target (goal - position); over the OTHER table entries in table order, as
+ *                         the previous replan left them, skipping those closer than 1e-5, the repulsion term of :336-337 inside
+ *                         Q* = 2 (radius + other.radius); |a| clamped to max_acc - 0.01; v += a dt; |v| clamped to max_vel;
+ *                         position += v dt, narrowed to float.  The goal point is the position of global agent target_agent in the state
+ *                         buffer at the replan's start (target_agent >= 0) or goal[3] (target_agent = -1; the origin is what the
+ *                         reference's own simulator passes, include/obstacle_generator.hpp:28-32).  The entry's own previous position
+ *                         and velocity are read from the table.  All entries are read before any is written (a Jacobi step).
+ *   LSCQP_DRIVE_GAUSSIAN  getGaussianObstacle (:424-468): the loop over i = 0 .. n, n = floor((t + 1e-5) / acc_update_cycle), with both
+ *                         branches of its max_vel test, over the slice [history_first, history_first + history_len) of ONE shared table of
+ *                         accelerations (double[3] each; GaussianObstacle::set_acc_history).  The state after i_done whole cycles is kept
+ *                         in a checkpoint per obstacle, advanced to n, and the partial step dt = t - n cycle is taken on a copy: the whole
+ *                         cycles of the reference's loop do not depend on t, so this is the loop from zero bit for bit at the cost of the
+ *                         cycles since the last replan.  A checkpoint ahead of the clock (i_done > n: the caller wrote the clock
+ *                         backwards) restarts from `start`.  Past the end of its slice the obstacle accelerates by zero and bit 0 of its
+ *                         table entry's `reserved` word is set (LSCQP_OBSTACLE_HISTORY_ENDED); the reference draws new accelerations there.
+ * Positions and velocities are point3d: float32 held in double, narrowed exactly where the reference stores into one.  The norm of an
+ * Eigen::Vector3d is sqrt((x x + y y) + z z) here (Eigen's own order depends on its version and vectorisation); nothing contracts a multiply
+ * and an add; only + - x / sqrt are used.  broadcastMsgs' repeats of the update with dt = 0, once per agent, are not made.
+ * lscqp_obstacle_drive_check     HOST, no device needed: n drives against their n models, a history table of n_history entries and a
+ *                            mission of n_total agents.  LSCQP_ERR_INVALID_ARGUMENT names the model and the cause: a drive on a model that
+ *                            is not HELD, an unknown kind, a non-finite field, max_vel <= 0, acc_update_cycle <= 0 (GAUSSIAN), a history
+ *                            slice of length 0 or outside [0, n_history) (GAUSSIAN), target_agent outside [-1, n_total) (CHASING),
+ *                            max_acc <= 0.01 (CHASING: the clamp is to max_acc - 0.01).
+ * lscqp_obstacles_drive_device   one launch of ONE workgroup over n_dyn <= lscqp_max_obstacles(h) models and drives in device memory, IN
+ *                            FRONT of lscqp_obstacles_advance_device on the same stream: reads the clock r (forms t(r) and t(r - 1) as the
+ *                            advance forms t; does not write it), moves every entry whose drive is not NONE and writes its radius,
+ *                            downwash, max_acc, type = DYNAMICOBSTACLE and `reserved`.  d_state [n_total][9] is LSCQP_PLAN_BUF_STATE's layout
+ *                            (may be NULL with n_total = 0: every chaser then flies to goal[3]); d_drive_state one checkpoint per obstacle,
+ *                            zeroed by the caller before the first replan (GAUSSIAN only); d_acc_history may be NULL with n_history = 0.
+ *                            An index outside its table is never followed: such a target reads goal[3], such an acceleration is zero.
+ * lscqp_obstacle_drive_host      the same arguments as HOST pointers, one replan on the CPU by the same functions the kernel runs: no device
+ *                            needed.  (The clock is read, not written: the caller advances it, or runs the advance's restatement.)
+ * lscqp_plan_set_obstacle_drives gives the plan's n_dyn obstacles their drives (host arrays, copied and checked by
+ *                            lscqp_obstacle_drive_check against the plan's models and n_total; n_dyn must be the plan's); drives = NULL or
+ *                            n_dyn = 0 takes them away, and so does every lscqp_plan_set_obstacles.  Like the other setters it waits for the
+ *                            device and drops a captured graph, lscqp_plan_reset must follow (a step before it is refused), a refused call
+ *                            leaves the plan as it was; the reset puts driven entries at `start` with zero velocity and zeroes the
+ *                            checkpoints.  Per replan the chain gains exactly one node, in front of the advance; a plan without drives
+ *                            enqueues the chain it always did node for node.  target_agent is a global agent index: a mission partition
+ *                            shares driven obstacles like any other, and every owner of a sharded mission drives its own copy. */
+#define LSCQP_DRIVE_NONE 0
+#define LSCQP_DRIVE_CHASING 1
+#define LSCQP_DRIVE_GAUSSIAN 2
+#define LSCQP_OBSTACLE_HISTORY_ENDED 1 /* bit 0 of lscqp_obstacle.reserved of a GAUSSIAN entry */
+typedef struct lscqp_obstacle_drive { /* 96 bytes */
+    int32_t kind;                     /* LSCQP_DRIVE_* */
+    int32_t target_agent;             /* CHASING: global agent id, or -1 = goal[3] */
+    double max_vel;                   /* mission file: max_vel (both kinds) */
+    double gamma_target, gamma_obs;   /* CHASING */
+    double goal[3];                   /* CHASING with target_agent = -1 */
+    double initial_vel[3];            /* GAUSSIAN (held as point3d) */
+    double acc_update_cycle;          /* GAUSSIAN */
+    int32_t history_first, history_len; /* GAUSSIAN: its slice of the acceleration table */
+} lscqp_obstacle_drive;
+typedef struct lscqp_obstacle_drive_state { /* 56 bytes: a GAUSSIAN obstacle after i_done whole cycles; all zero = at `start` */
+    int32_t i_done, reserved;
+    float position[3], velocity[3]; /* gaussianObstacle.position / .velocity */
+    double v[3];                    /* the loop's v */
+} lscqp_obstacle_drive_state;
+int lscqp_obstacle_drive_check(const lscqp_obstacle_model* models, const lscqp_obstacle_drive* drives, int32_t n, int32_t n_history,
+                               int64_t n_total);
+int lscqp_obstacles_drive_device(lscqp_handle h, const lscqp_obstacle_model* d_models, const lscqp_obstacle_drive* d_drives, int32_t n_dyn,
+                                 const double* d_acc_history, int32_t n_history, const double* d_state, int64_t n_total,
+                                 lscqp_obstacle_drive_state* d_drive_state, double time_step, const int32_t* d_clock,
+                                 lscqp_obstacle* d_obstacles, void* stream);
+int lscqp_obstacle_drive_host(lscqp_handle h, const lscqp_obstacle_model* models, const lscqp_obstacle_drive* drives, int32_t n_dyn,
+                              const double* acc_history, int32_t n_history, const double* state, int64_t n_total,
+                              lscqp_obstacle_drive_state* drive_state, double time_step, const int32_t* clock, lscqp_obstacle* obstacles,
+                              void* stream);
+int lscqp_plan_set_obstacle_drives(lscqp_plan plan, const lscqp_obstacle_drive* drives, int32_t n_dyn, const double* acc_history,
+                                   int32_t n_history);
 
 /* ---- work counters of a launch (the fp64-VALU figure next to the HBM one) -----------------------------
  *

@@ -5,6 +5,7 @@ only moves bytes: numpy structured arrays for host calls, torch CUDA tensors (ra
 calls.  It never computes anything and has NO CPU fallback: if liblscqp.so is missing, importing fails loudly.
 """
 import ctypes as C
+import math
 import os
 import re
 
@@ -54,6 +55,14 @@ OBSTACLE_MODEL_DTYPE = np.dtype([("kind", "i4"), ("n_waypoints", "i4"), ("radius
                                  ("lap_time", "f8"), ("spin_axis", "f8", 3), ("spin_offset", "f8", 3), ("spin_w", "f8")])
 assert OBSTACLE_LEG_DTYPE.itemsize == 64 and OBSTACLE_MODEL_DTYPE.itemsize == 912
 PLAN_OBS_TABLE, PLAN_OBS_SAFETY, PLAN_OBS_CLOCK = 0, 1, 2  # lscqp_plan_obstacle_buffer
+# lscqp_obstacle_drive: how a chasing or gaussian obstacle is moved on the device (include/lscqp.h, "chasing and gaussian obstacles"), and
+# lscqp_obstacle_drive_state, the gaussian obstacle's checkpoint
+DRIVE_NONE, DRIVE_CHASING, DRIVE_GAUSSIAN = 0, 1, 2  # lscqp_obstacle_drive.kind
+OBSTACLE_HISTORY_ENDED = 1                           # bit 0 of lscqp_obstacle.reserved
+OBSTACLE_DRIVE_DTYPE = np.dtype([("kind", "i4"), ("target_agent", "i4"), ("max_vel", "f8"), ("gamma_target", "f8"), ("gamma_obs", "f8"), ("goal", "f8", 3),
+                                 ("initial_vel", "f8", 3), ("acc_update_cycle", "f8"), ("history_first", "i4"), ("history_len", "i4")])
+OBSTACLE_DRIVE_STATE_DTYPE = np.dtype([("i_done", "i4"), ("reserved", "i4"), ("position", "f4", 3), ("velocity", "f4", 3), ("v", "f8", 3)])
+assert OBSTACLE_DRIVE_DTYPE.itemsize == 96 and OBSTACLE_DRIVE_STATE_DTYPE.itemsize == 56
 
 
 class ObstacleParam(C.Structure):  # lscqp_obstacle_param
@@ -230,6 +239,7 @@ EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_
                     "lscqp_plan_set_flight_log",
                     "lscqp_obstacle_model_prepare", "lscqp_obstacles_advance_device", "lscqp_plan_set_obstacles", "lscqp_plan_obstacle_buffer",
                     "lscqp_plan_obstacle_upload", "lscqp_plan_obstacle_download",
+                    "lscqp_obstacle_drive_check", "lscqp_obstacles_drive_device", "lscqp_obstacle_drive_host", "lscqp_plan_set_obstacle_drives",
                     "lscqp_worlds_create", "lscqp_worlds_destroy", "lscqp_worlds_prepare", "lscqp_worlds_info", "lscqp_construct_sfc_worlds_device",
                     "lscqp_grid_set_worlds", "lscqp_grid_download_world", "lscqp_plan_set_worlds",
                     "lscqp_instance_work", "lscqp_diagnose", "lscqp_diagnose_device", "lscqp_dump_instance", "lscqp_row_family_name",
@@ -259,7 +269,8 @@ def obstacle_models(specs):
     """OBSTACLE_MODEL_DTYPE records from a list of dicts in the reference's mission-file vocabulary (missions/*.json, "obstacles"):
     type ("straight", "patrol", "spin"; anything else -- "chasing", "gaussian", "real" -- is HELD at `start`), start, goal, waypoints, axis
     (a pose: position x y z and the axis direction in orientation x y z, or six numbers), size (the radius), speed, max_acc, downwash.
-    Points are [x, y, z] or {"x":, "y":, "z":}.  Not prepared: obstacle_model_prepare or Plan.set_obstacles does that."""
+    Points are [x, y, z] or {"x":, "y":, "z":}.  Not prepared: obstacle_model_prepare or Plan.set_obstacles does that.  A chasing or gaussian
+    entry moves on the device once it has a drive: obstacle_drives reads the same list, Plan.set_obstacle_drives takes the result."""
     def pt(v):
         return [float(v[k]) for k in ("x", "y", "z")] if isinstance(v, dict) else [float(c) for c in v]
 
@@ -293,6 +304,53 @@ def obstacle_model_prepare(models):
     m = np.array(models, dtype=OBSTACLE_MODEL_DTYPE, ndmin=1)
     _call("lscqp_obstacle_model_prepare", m, len(m))
     return m
+
+
+def obstacle_drives(specs, n_total, horizon=60.0, seed=0):
+    """(drives, acc_history) for the list obstacle_models takes: an OBSTACLE_DRIVE_DTYPE record per entry -- DRIVE_CHASING for "chasing",
+    DRIVE_GAUSSIAN for "gaussian", DRIVE_NONE for everything else -- and the one shared [n_history][3] table of accelerations.  Field names are
+    src/mission.cpp's (max_vel, gamma_target, gamma_obs; initial_vel, stddev_acc, acc_update_cycle, 0 = 0.1 s); optional keys: target_agent
+    (a global agent id < n_total; default -1: fly to `goal`), goal (default the origin, what the reference's simulator passes), acc_history (a
+    gaussian obstacle's own accelerations, [n][3]).  Without acc_history ceil(horizon / acc_update_cycle) accelerations are drawn from
+    numpy.random.default_rng(seed), N(0, stddev_acc) per axis, and clamped to max_acc in norm (GaussianObstacle::update_acc_history)."""
+    def pt(v):
+        return [float(v[k]) for k in ("x", "y", "z")] if isinstance(v, dict) else [float(c) for c in v]
+
+    rng = np.random.default_rng(seed)
+    drives, hist = np.zeros(len(specs), OBSTACLE_DRIVE_DTYPE), []
+    drives["target_agent"] = -1
+    for d, o in zip(drives, specs):
+        kind = o.get("type", "held")
+        if kind == "chasing":
+            d["kind"], d["max_vel"] = DRIVE_CHASING, float(o["max_vel"])
+            d["gamma_target"], d["gamma_obs"] = float(o["gamma_target"]), float(o["gamma_obs"])
+            d["target_agent"] = int(o.get("target_agent", -1))
+            if not -1 <= d["target_agent"] < n_total:
+                raise ValueError("target_agent %d outside [-1, %d)" % (d["target_agent"], n_total))
+            d["goal"] = pt(o.get("goal", (0.0, 0.0, 0.0)))
+        elif kind == "gaussian":
+            d["kind"], d["max_vel"] = DRIVE_GAUSSIAN, float(o["max_vel"])
+            d["initial_vel"] = pt(o.get("initial_vel", (0.0, 0.0, 0.0)))
+            d["acc_update_cycle"] = float(o.get("acc_update_cycle", 0.0)) or 0.1
+            if "acc_history" in o:
+                acc = np.array(o["acc_history"], np.float64).reshape(-1, 3)
+            else:
+                max_acc = float(o.get("max_acc", 1.0))
+                acc = rng.normal(0.0, float(o.get("stddev_acc", 0.0)), (int(math.ceil(horizon / d["acc_update_cycle"])), 3))
+                norm = np.sqrt((acc * acc).sum(1))
+                over = norm > max_acc
+                acc[over] *= (max_acc / norm[over])[:, None]
+            d["history_first"], d["history_len"] = sum(len(h) for h in hist), len(acc)
+            hist.append(acc)
+    return drives, (np.concatenate(hist) if hist else np.zeros((0, 3)))
+
+
+def obstacle_drive_check(models, drives, n_history, n_total):
+    """lscqp_obstacle_drive_check: raises LscqpError naming the model and the cause; no device needed."""
+    m, d = np.ascontiguousarray(models, dtype=OBSTACLE_MODEL_DTYPE), np.ascontiguousarray(drives, dtype=OBSTACLE_DRIVE_DTYPE)
+    if len(m) != len(d):
+        raise ValueError("one drive per model")
+    _call("lscqp_obstacle_drive_check", m, d, len(d), int(n_history), int(n_total))
 
 
 def pack_rows(lsc):
@@ -842,7 +900,17 @@ class Plan:
         _call("lscqp_plan_set_obstacles", self._p, C.byref(param), len(m), m)
         self.n_dyn = len(m)
 
-    _OBS_DT = {PLAN_OBS_TABLE: OBSTACLE_DTYPE, PLAN_OBS_SAFETY: SAFETY_OBS_DTYPE, PLAN_OBS_CLOCK: np.int32}
+    def set_obstacle_drives(self, drives, acc_history=None):
+        """lscqp_plan_set_obstacle_drives: an OBSTACLE_DRIVE_DTYPE record per obstacle of the plan and the shared [n_history][3] table of
+        accelerations (obstacle_drives builds both), or None / empty to take the drives away.  `reset` must follow."""
+        if drives is None or len(drives) == 0:
+            _call("lscqp_plan_set_obstacle_drives", self._p, None, 0, None, 0)
+            return
+        d = np.ascontiguousarray(drives, dtype=OBSTACLE_DRIVE_DTYPE)
+        h = np.ascontiguousarray(np.zeros((0, 3)) if acc_history is None else acc_history, dtype=np.float64).reshape(-1, 3)
+        _call("lscqp_plan_set_obstacle_drives", self._p, d, len(d), h if len(h) else None, len(h))
+
+    _OBS_DT ={PLAN_OBS_TABLE: OBSTACLE_DTYPE, PLAN_OBS_SAFETY: SAFETY_OBS_DTYPE, PLAN_OBS_CLOCK: np.int32}
 
     def obstacle_pointer(self, which):
         nb = C.c_uint64()
@@ -1372,6 +1440,26 @@ class Solver:
     def obstacles_advance_device(self, d_models, n_dyn, time_step, d_clock, d_obstacles, stream=None):
         """lscqp_obstacles_advance_device: the table moved to the clock's replan, the clock advanced; d_models PREPARED models on the device."""
         _call("lscqp_obstacles_advance_device", self._h, d_models, int(n_dyn), float(time_step), d_clock, d_obstacles, stream=stream)
+
+    def obstacles_drive_device(self, d_models, d_drives, n_dyn, d_acc_history, n_history, d_state, n_total, d_drive_state, time_step, d_clock,
+                               d_obstacles, stream=None):
+        """lscqp_obstacles_drive_device: the chasing and gaussian entries of the table moved to the clock's replan, IN FRONT of
+        obstacles_advance_device on the same stream (the clock is read, not advanced).  d_drives: OBSTACLE_DRIVE_DTYPE, d_drive_state:
+        OBSTACLE_DRIVE_STATE_DTYPE per obstacle, zeroed before the first replan; d_state [n_total][9]."""
+        _call("lscqp_obstacles_drive_device", self._h, d_models, d_drives, int(n_dyn), d_acc_history, int(n_history), d_state, int(n_total), d_drive_state,
+              float(time_step), d_clock, d_obstacles, stream=stream)
+
+    def obstacle_drive_host(self, models, drives, acc_history, state, drive_state, time_step, clock, table):
+        """lscqp_obstacle_drive_host: one replan of the drives on the CPU, by the functions the kernel runs; numpy arrays, `drive_state`
+        (OBSTACLE_DRIVE_STATE_DTYPE) and `table` (OBSTACLE_DTYPE) are written in place; `clock` is the replan index.  No device needed."""
+        m, d = np.ascontiguousarray(models, dtype=OBSTACLE_MODEL_DTYPE), np.ascontiguousarray(drives, dtype=OBSTACLE_DRIVE_DTYPE)
+        h = np.ascontiguousarray(np.zeros((0, 3)) if acc_history is None else acc_history, dtype=np.float64).reshape(-1, 3)
+        st = np.ascontiguousarray(np.zeros((0, 9)) if state is None else state, dtype=np.float64).reshape(-1, 9)
+        for a, dt in ((drive_state, OBSTACLE_DRIVE_STATE_DTYPE), (table, OBSTACLE_DTYPE)):
+            if a.dtype != dt or not a.flags.c_contiguous or len(a) != len(d):
+                raise ValueError("drive_state and table are written in place: contiguous arrays of their dtypes, one record per drive")
+        _call("lscqp_obstacle_drive_host", self._h, m, d, len(d), h if len(h) else None, len(h), st if len(st) else None, len(st), drive_state,
+              float(time_step), np.array([clock], np.int32), table, None)
 
     def generate_lsc_bytes(self, n_agents, n_obs, n_total):
         return lib().lscqp_generate_lsc_bytes(self._h, n_agents, n_obs, n_total)

@@ -6,6 +6,8 @@
 // reference's own arithmetic: point3d is octomath::Vector3, three FLOATS -- Vector3::distance is the double square root of the double
 // sum of squared float differences, normalized() divides by (float)norm(), norm() is the double square root of a float sum of squares,
 // and `n * 0.5 * max_acc * t * t` is four Vector3::operator*(float) in a row.  Nothing here may contract a multiply and an add.
+// A second kernel, in front of that one, moves the entries whose next state needs more than the time (obstacle_drive_kernel below):
+//   ChasingObstacle / GaussianObstacle::getObstacle   include/obstacle.hpp:267-469
 // This file has no object of its own: lscplan.hip includes it (as lscsfc_tp.hip includes lscsfc.hip), so that it is built with
 // the chain that launches its kernel.
 #include <hip/hip_runtime.h>
@@ -13,6 +15,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+
+#include <vector>
 
 #include "../../include/lscqp.h"
 #include "lscqp_internal.hpp"
@@ -138,6 +142,183 @@ __global__ __launch_bounds__(kThreads) void obstacle_advance_kernel(const lscqp_
     if (threadIdx.x == 0) *clock = r + 1;
 }
 
+// ---- chasing and gaussian obstacles (include/lscqp.h, "chasing and gaussian obstacles"): ChasingObstacle::getChasingObstacle :313-363,
+// GaussianObstacle::getGaussianObstacle :424-468.  The same functions run in obstacle_drive_kernel and in lscqp_obstacle_drive_host.
+
+struct D3 {
+    double x, y, z;
+};
+
+// |v| of an Eigen::Vector3d as this library defines it: sqrt((x x + y y) + z z)
+__host__ __device__ inline double norm3(D3 v) {
+#pragma clang fp contract(off)
+    return sqrt((v.x * v.x + v.y * v.y) + v.z * v.z);
+}
+
+// an entry as the previous replan left it: what a chaser sees of the others (and of itself)
+struct Staged {
+    double px, py, pz, radius;
+};
+
+// t of replan r as obstacle_advance_kernel forms it
+__host__ __device__ inline double clock_seconds(int32_t r, int64_t step_ns) {
+#pragma clang fp contract(off)
+    const int64_t ns = (int64_t)r * step_ns;
+    return (double)(ns / 1000000000LL) + 1e-9 * (double)(ns % 1000000000LL);
+}
+
+// getChasingObstacle with current_state = (own staged position, `vel`) and dt = t - t_last_called; goal: the goal point as point3d
+__host__ __device__ inline void chasing_step(const lscqp_obstacle_model& m, const lscqp_obstacle_drive& d, F3 goal, const Staged* prev, int n_dyn, int self,
+                                             double dt, F3* pos, F3* vel) {
+#pragma clang fp contract(off)
+    const F3 p{(float)prev[self].px, (float)prev[self].py, (float)prev[self].pz};
+    D3 a{d.gamma_target * (double)(goal.x - p.x), d.gamma_target * (double)(goal.y - p.y), d.gamma_target * (double)(goal.z - p.z)};
+    D3 v{(double)vel->x, (double)vel->y, (double)vel->z};
+    for (int oj = 0; oj < n_dyn; oj++) {
+        if (oj == self) continue;
+        const D3 dl{(double)((float)prev[oj].px - p.x), (double)((float)prev[oj].py - p.y), (double)((float)prev[oj].pz - p.z)};
+        const double dist = norm3(dl);
+        if (dist < 1e-5) continue;  // SP_EPSILON_FLOAT
+        const double q_star = 2 * (m.radius + prev[oj].radius);
+        if (dist < q_star) {
+            const double s = d.gamma_obs * (1 - dist / q_star) * (1 / (dist * q_star));
+            a.x += s * (-(dl.x / dist)), a.y += s * (-(dl.y / dist)), a.z += s * (-(dl.z / dist));
+        }
+    }
+    const double a_max = m.max_acc - 0.01, na = norm3(a);
+    if (na > a_max) a = D3{a.x / na * a_max, a.y / na * a_max, a.z / na * a_max};
+    v = D3{v.x + a.x * dt, v.y + a.y * dt, v.z + a.z * dt};
+    const double nv = norm3(v);
+    if (nv > d.max_vel) v = D3{v.x / nv * d.max_vel, v.y / nv * d.max_vel, v.z / nv * d.max_vel};
+    *pos = F3{(float)((double)p.x + v.x * dt), (float)((double)p.y + v.y * dt), (float)((double)p.z + v.z * dt)};
+    *vel = F3{(float)v.x, (float)v.y, (float)v.z};
+}
+
+// one pass of getGaussianObstacle's loop body over dt
+__host__ __device__ inline void gaussian_cycle(lscqp_obstacle_drive_state* c, D3 acc, double dt, double max_vel) {
+#pragma clang fp contract(off)
+    const D3 v{c->v[0], c->v[1], c->v[2]};
+    const D3 v_next{v.x + acc.x * dt, v.y + acc.y * dt, v.z + acc.z * dt};
+    if (norm3(v_next) > max_vel) {  // "If v is over max_vel then ignore acc"
+        c->position[0] = (float)((double)c->position[0] + v.x * dt);
+        c->position[1] = (float)((double)c->position[1] + v.y * dt);
+        c->position[2] = (float)((double)c->position[2] + v.z * dt);
+    } else {
+        c->position[0] = (float)((double)c->position[0] + (v.x * dt + 0.5 * acc.x * dt * dt));
+        c->position[1] = (float)((double)c->position[1] + (v.y * dt + 0.5 * acc.y * dt * dt));
+        c->position[2] = (float)((double)c->position[2] + (v.z * dt + 0.5 * acc.z * dt * dt));
+        c->velocity[0] = (float)((double)c->velocity[0] + acc.x * dt);
+        c->velocity[1] = (float)((double)c->velocity[1] + acc.y * dt);
+        c->velocity[2] = (float)((double)c->velocity[2] + acc.z * dt);
+        c->v[0] = v_next.x, c->v[1] = v_next.y, c->v[2] = v_next.z;
+    }
+}
+
+// getGaussianObstacle(t) from the checkpoint: whole cycles i_done .. n - 1 on the checkpoint, the partial one on a copy.  Returns whether the
+// history ended (an index at or past history_len, or outside the table, was asked for: zero acceleration)
+__host__ __device__ inline bool gaussian_at(const lscqp_obstacle_model& m, const lscqp_obstacle_drive& d, const double* hist, int n_history,
+                                            lscqp_obstacle_drive_state* ckpt, double t, F3* pos, F3* vel) {
+#pragma clang fp contract(off)
+    const double cycle = d.acc_update_cycle;
+    const double q = floor((t + 1e-5) / cycle);
+    const int n = q < 0 ? 0 : (q > 2147483646.0 ? 2147483646 : (int)q);  // (int n = floor(..) of the reference, kept inside an int)
+    lscqp_obstacle_drive_state c = *ckpt;
+    if (c.i_done <= 0 || c.i_done > n) {  // a zeroed checkpoint, or one ahead of a clock that was written backwards: from `start`
+        c.i_done = 0, c.reserved = 0;
+        for (int k = 0; k < 3; k++) {
+            c.position[k] = (float)m.start[k];
+            c.velocity[k] = (float)d.initial_vel[k];
+            c.v[k] = (double)(float)d.initial_vel[k];
+        }
+    }
+    bool ended = false;
+    auto acc_of = [&](int i) {
+        const int64_t at = (int64_t)d.history_first + i;
+        if (i >= d.history_len || at < 0 || at >= n_history) {
+            ended = true;
+            return D3{0.0, 0.0, 0.0};
+        }
+        return D3{hist[at * 3 + 0], hist[at * 3 + 1], hist[at * 3 + 2]};
+    };
+    for (; c.i_done < n; c.i_done++) gaussian_cycle(&c, acc_of(c.i_done), cycle, d.max_vel);
+    if (c.i_done != ckpt->i_done) *ckpt = c;
+    gaussian_cycle(&c, acc_of(n), t - n * cycle, d.max_vel);
+    *pos = F3{c.position[0], c.position[1], c.position[2]};
+    *vel = F3{c.velocity[0], c.velocity[1], c.velocity[2]};
+    return ended;
+}
+
+// One driven entry by one replan: `prev` holds EVERY entry as the previous replan left it, so no entry written here is read by another
+__host__ __device__ inline void drive_entry(const lscqp_obstacle_model* models, const lscqp_obstacle_drive* drives, int n_dyn, const double* hist,
+                                            int n_history, const double* state, int64_t n_total, lscqp_obstacle_drive_state* ckpt, double t, double t_last,
+                                            const Staged* prev, int oi, lscqp_obstacle* table) {
+#pragma clang fp contract(off)
+    const lscqp_obstacle_drive& d = drives[oi];
+    if (d.kind != LSCQP_DRIVE_CHASING && d.kind != LSCQP_DRIVE_GAUSSIAN) return;
+    const lscqp_obstacle_model& m = models[oi];
+    lscqp_obstacle* o = table + oi;
+    F3 p, v;
+    int32_t flags = 0;
+    if (d.kind == LSCQP_DRIVE_CHASING) {
+        const int64_t ta = d.target_agent;
+        const double* g = (state != nullptr && ta >= 0 && ta < n_total) ? state + ta * 9 : d.goal;
+        v = F3{(float)o->velocity[0], (float)o->velocity[1], (float)o->velocity[2]};
+        chasing_step(m, d, F3{(float)g[0], (float)g[1], (float)g[2]}, prev, n_dyn, oi, t - t_last, &p, &v);
+    } else if (gaussian_at(m, d, hist, hist != nullptr ? n_history : 0, ckpt + oi, t, &p, &v)) {
+        flags = LSCQP_OBSTACLE_HISTORY_ENDED;
+    }
+    o->position[0] = (double)p.x, o->position[1] = (double)p.y, o->position[2] = (double)p.z;
+    o->velocity[0] = (double)v.x, o->velocity[1] = (double)v.y, o->velocity[2] = (double)v.z;
+    o->radius = m.radius, o->downwash = m.downwash, o->max_acc = m.max_acc;
+    o->type = 0;  // DYNAMICOBSTACLE (ObstacleBase::getObstacle)
+    o->reserved = flags;
+}
+
+// One workgroup; thread i takes obstacles i, i + 64, ...  Every entry's previous position and radius go to LDS first (n_dyn Staged records
+// of dynamic LDS); behind the barrier the table is only written, and an entry's own velocity is read by the one thread that writes it.
+// The clock word is read, never written: the advance behind this kernel counts it.
+__global__ __launch_bounds__(kThreads) void obstacle_drive_kernel(const lscqp_obstacle_model* __restrict__ models, const lscqp_obstacle_drive* __restrict__ drives,
+                                                                   int n_dyn, const double* __restrict__ hist, int n_history, const double* __restrict__ state,
+                                                                   int64_t n_total, lscqp_obstacle_drive_state* __restrict__ ckpt, int64_t step_ns,
+                                                                   const int32_t* __restrict__ clock, lscqp_obstacle* table) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) char drive_lds[];
+    Staged* prev = (Staged*)drive_lds;
+    const int32_t r = *clock;
+    const double t = clock_seconds(r, step_ns), t_last = r > 0 ? clock_seconds(r - 1, step_ns) : 0.0;
+    for (int oi = threadIdx.x; oi < n_dyn; oi += kThreads)
+        prev[oi] = Staged{table[oi].position[0], table[oi].position[1], table[oi].position[2], table[oi].radius};
+    __syncthreads();
+    for (int oi = threadIdx.x; oi < n_dyn; oi += kThreads) drive_entry(models, drives, n_dyn, hist, n_history, state, n_total, ckpt, t, t_last, prev, oi, table);
+}
+
+constexpr size_t kDriveLdsMax = 64 * 1024;  // (2048 entries: far beyond lscqp_max_obstacles of any class)
+
+inline int refuse_drive(int i, const char* what) {
+    char msg[240];
+    snprintf(msg, sizeof msg, "lscqp_obstacle_drive_check: model %d: %s", i, what);
+    return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, msg);
+}
+
+// the argument checks the device and the host entry share (the advance entry's, and the tables the drives index)
+inline int drive_args(lscqp_handle h, const void* models, const void* drives, int32_t n_dyn, const double* hist, int32_t n_history, const double* state,
+                      int64_t n_total, const void* ckpt, double time_step, const void* clock, const void* table, bool* empty) {
+    *empty = false;
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_dyn < 0 || n_history < 0 || n_total < 0 || !(time_step > 0) || !(time_step < 1e6))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
+                                "inconsistent sizes (n_dyn >= 0, n_history >= 0, n_total >= 0 and a positive, finite time_step required)");
+    if (n_dyn > lscqp_max_obstacles(h) || (size_t)n_dyn * sizeof(Staged) > kDriveLdsMax)
+        return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "n_dyn exceeds the largest compiled kernel instance of the shape (lscqp_max_obstacles)");
+    if (n_dyn == 0) {
+        *empty = true;
+        return LSCQP_OK;
+    }
+    if (!models || !drives || !ckpt || !clock || !table || (n_history > 0 && !hist) || (n_total > 0 && !state))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    return LSCQP_OK;
+}
+
 // StraightObstacle's constructor (:145-161)
 inline void make_leg(const double* start, const double* goal, double speed, double max_acc, lscqp_obstacle_leg* L) {
 #pragma clang fp contract(off)
@@ -243,4 +424,68 @@ extern "C" int lscqp_obstacles_advance_device(lscqp_handle h, const lscqp_obstac
     hipLaunchKernelGGL(lscobstacle::obstacle_advance_kernel, dim3(1), dim3(lscobstacle::kThreads), 0, (hipStream_t)stream, d_models, (int)n_dyn, step_ns,
                        d_clock, d_obstacles);
     return lscqp_launch_result_(hipGetLastError());
+}
+
+extern "C" int lscqp_obstacle_drive_check(const lscqp_obstacle_model* models, const lscqp_obstacle_drive* drives, int32_t n, int32_t n_history,
+                                          int64_t n_total) {
+    using namespace lscobstacle;
+    if (n < 0 || n_history < 0 || n_total < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "negative size");
+    if (n == 0) return LSCQP_OK;
+    if (!models || !drives) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    for (int i = 0; i < n; i++) {
+        const lscqp_obstacle_drive& d = drives[i];
+        const lscqp_obstacle_model& m = models[i];
+        if (d.kind == LSCQP_DRIVE_NONE) continue;
+        if (d.kind != LSCQP_DRIVE_CHASING && d.kind != LSCQP_DRIVE_GAUSSIAN)
+            return refuse_drive(i, "kind must be LSCQP_DRIVE_NONE, _CHASING or _GAUSSIAN");
+        if (m.kind != LSCQP_OBSTACLE_HELD) return refuse_drive(i, "a drive needs an LSCQP_OBSTACLE_HELD model (the advance moves every other kind)");
+        if (!isfinite(d.max_vel) || !isfinite(d.gamma_target) || !isfinite(d.gamma_obs) || !finite3(d.goal) || !finite3(d.initial_vel) ||
+            !isfinite(d.acc_update_cycle) || !isfinite(m.radius) || !isfinite(m.max_acc) || !isfinite(m.downwash) || !finite3(m.start))
+            return refuse_drive(i, "a field is not finite (max_vel, gamma_target, gamma_obs, goal, initial_vel, acc_update_cycle; the model's radius, max_acc, downwash, start)");
+        if (!(d.max_vel > 0)) return refuse_drive(i, "max_vel <= 0");
+        if (d.kind == LSCQP_DRIVE_CHASING) {
+            if (d.target_agent < -1 || d.target_agent >= n_total) return refuse_drive(i, "target_agent outside [-1, n_total)");
+            if (!(m.max_acc > 0.01)) return refuse_drive(i, "max_acc <= 0.01 (a chaser's acceleration is clamped to max_acc - 0.01)");
+        } else {
+            if (!(d.acc_update_cycle > 0)) return refuse_drive(i, "acc_update_cycle <= 0");
+            if (d.history_len <= 0) return refuse_drive(i, "the history slice is empty (history_len >= 1 required)");
+            if (d.history_first < 0 || (int64_t)d.history_first + d.history_len > n_history)
+                return refuse_drive(i, "the history slice lies outside [0, n_history)");
+        }
+    }
+    return LSCQP_OK;
+}
+
+extern "C" int lscqp_obstacles_drive_device(lscqp_handle h, const lscqp_obstacle_model* d_models, const lscqp_obstacle_drive* d_drives, int32_t n_dyn,
+                                            const double* d_acc_history, int32_t n_history, const double* d_state, int64_t n_total,
+                                            lscqp_obstacle_drive_state* d_drive_state, double time_step, const int32_t* d_clock,
+                                            lscqp_obstacle* d_obstacles, void* stream) {
+    bool empty = false;
+    if (const int rc = lscobstacle::drive_args(h, d_models, d_drives, n_dyn, d_acc_history, n_history, d_state, n_total, d_drive_state, time_step, d_clock,
+                                               d_obstacles, &empty))
+        return rc;
+    if (empty) return LSCQP_OK;
+    if (const int rc = lscqp_need_device_()) return rc;
+    const int64_t step_ns = (int64_t)llround(time_step * 1e9);  // ros::Duration(time_step): whole nanoseconds
+    hipLaunchKernelGGL(lscobstacle::obstacle_drive_kernel, dim3(1), dim3(lscobstacle::kThreads), (size_t)n_dyn * sizeof(lscobstacle::Staged), (hipStream_t)stream,
+                       d_models, d_drives, (int)n_dyn, d_acc_history, (int)n_history, d_state, n_total, d_drive_state, step_ns, d_clock, d_obstacles);
+    return lscqp_launch_result_(hipGetLastError());
+}
+
+extern "C" int lscqp_obstacle_drive_host(lscqp_handle h, const lscqp_obstacle_model* models, const lscqp_obstacle_drive* drives, int32_t n_dyn,
+                                         const double* acc_history, int32_t n_history, const double* state, int64_t n_total,
+                                         lscqp_obstacle_drive_state* drive_state, double time_step, const int32_t* clock, lscqp_obstacle* obstacles,
+                                         void* stream) {
+    using namespace lscobstacle;
+    (void)stream;
+    bool empty = false;
+    if (const int rc = drive_args(h, models, drives, n_dyn, acc_history, n_history, state, n_total, drive_state, time_step, clock, obstacles, &empty)) return rc;
+    if (empty) return LSCQP_OK;
+    const int64_t step_ns = (int64_t)llround(time_step * 1e9);
+    const int32_t r = *clock;
+    const double t = clock_seconds(r, step_ns), t_last = r > 0 ? clock_seconds(r - 1, step_ns) : 0.0;
+    std::vector<Staged> prev((size_t)n_dyn);
+    for (int oi = 0; oi < n_dyn; oi++) prev[(size_t)oi] = Staged{obstacles[oi].position[0], obstacles[oi].position[1], obstacles[oi].position[2], obstacles[oi].radius};
+    for (int oi = 0; oi < n_dyn; oi++) drive_entry(models, drives, n_dyn, acc_history, n_history, state, n_total, drive_state, t, t_last, prev.data(), oi, obstacles);
+    return LSCQP_OK;
 }

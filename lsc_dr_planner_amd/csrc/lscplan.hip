@@ -22,6 +22,8 @@
 // A plan whose missions have a world each (lscqp_plan_set_worlds: world k of a set of maps of one shape for mission k, as the reference's
 // evaluation sets pair them) swaps two things and adds no node: its corridor node is the worlds launch, every agent tested against the map
 // of its mission, and its grid starts each mission's occupancy from that world's base.
+// A plan whose obstacles have drives (lscqp_plan_set_obstacle_drives: chasing and gaussian obstacles) gains one node more, obstacle_drive_kernel in
+// front of the advance.
 // A plan with dynamic obstacles (lscqp_plan_set_obstacles) gains three nodes: the obstacles' motion (lscobstacle.hip) in front of `prepare`, their
 // rows (the non-agent branch of generateLSC or of generateCLSC, by the plan's constraint_mode; a BVC plan takes no obstacles) behind the agents'
 // rows -- they take the first row slots of every agent -- and the obstacle leg of the safety figures behind the agents'.
@@ -196,9 +198,16 @@ struct HandleDestroy {
 };
 
 // the setters whose change waits for lscqp_plan_reset, in the order in which a step names them: bit i of lscqp_plan_s::pending
-enum : unsigned { kPendMissions = 1u << 0, kPendRecord = 1u << 1, kPendObstacles = 1u << 2, kPendWorlds = 1u << 3, kPendFlightLog = 1u << 4 };
+enum : unsigned {
+    kPendMissions = 1u << 0,
+    kPendRecord = 1u << 1,
+    kPendObstacles = 1u << 2,
+    kPendWorlds = 1u << 3,
+    kPendFlightLog = 1u << 4,
+    kPendDrives = 1u << 5
+};
 constexpr const char* kPendSetter[] = {"lscqp_plan_set_missions", "lscqp_plan_set_record", "lscqp_plan_set_obstacles", "lscqp_plan_set_worlds",
-                                       "lscqp_plan_set_flight_log"};
+                                       "lscqp_plan_set_flight_log", "lscqp_plan_set_obstacle_drives"};
 
 }  // namespace lscplan
 
@@ -268,6 +277,13 @@ struct lscqp_plan_s {
         dev_ptr<lscqp_obstacle> table;
         dev_ptr<int32_t> ids, clock;  // ids: 0 .. n_dyn - 1 for every local agent
         dev_ptr<lscqp_safety_obs> safety;
+        // the drives of chasing and gaussian obstacles (lscqp_plan_set_obstacle_drives): d_drives = NULL = none, the chain as it always was
+        struct Drives {
+            dev_ptr<lscqp_obstacle_drive> d_drives;
+            dev_ptr<double> history;  // [n_history][3]
+            int32_t n_history = 0;
+            dev_ptr<lscqp_obstacle_drive_state> state;  // a checkpoint per obstacle
+        } drv;
     } obs;
     // a world per mission (lscqp_plan_set_worlds): set = NULL = the one map, the chain as it always was
     struct Worlds {
@@ -351,7 +367,11 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
             PLAN_TRY(lscqp_waypoints_device(grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, state, x_plan, goal, wp.field.get(), wp.init_d,
                                             waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], wp.desired_node, (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
     }
-    // obstacle_generator.update(t, 0) at the replan's start time (src/multi_sync_simulator.cpp:311); the clock is the device's
+    // obstacle_generator.update(t, 0) at the replan's start time (src/multi_sync_simulator.cpp:311); the clock is the device's.  Chasing and
+    // gaussian obstacles first: they read the table as the last replan left it, and the agents' states of this replan's start
+    if (n_dyn > 0 && obs.drv.d_drives)
+        PLAN_TRY(lscqp_obstacles_drive_device(h, obs.d_models.get(), obs.drv.d_drives.get(), n_dyn, obs.drv.history.get(), obs.drv.n_history, state, s.n_total,
+                                              obs.drv.state.get(), p->d.time_step, obs.clock.get(), obs.table.get(), stream));
     if (n_dyn > 0) PLAN_TRY(lscqp_obstacles_advance_device(h, obs.d_models.get(), n_dyn, p->d.time_step, obs.clock.get(), obs.table.get(), stream));
     // obstaclePredictionWithPrevSol / initialTrajPlanningPrevSol for every agent of the mission (:273-310, 399-423)
     const bool from_plans = !first_replan && (s.prediction_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION || s.initial_traj_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION);
@@ -469,6 +489,7 @@ int reset_obstacles(const lscqp_plan_s::Obstacles& o) {
     }
     hipError_t e = hipMemcpy(o.table.get(), tab.data(), tab.size() * sizeof(lscqp_obstacle), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(o.clock.get(), 0, sizeof(int32_t));
+    if (e == hipSuccess && o.drv.d_drives) e = hipMemset(o.drv.state.get(), 0, (size_t)o.n_dyn * sizeof(lscqp_obstacle_drive_state));
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "plan reset (obstacles)");
 }
 
@@ -1086,6 +1107,40 @@ int lscqp_plan_set_obstacles(lscqp_plan p, const lscqp_obstacle_param* param, in
     drop_graph(p);  // (a captured chain holds the obstacles' nodes and the slot split)
     p->obs = std::move(next);
     p->pending = none ? p->pending & ~lscplan::kPendObstacles : p->pending | lscplan::kPendObstacles;
+    p->pending &= ~lscplan::kPendDrives;  // (the drives went with the old obstacles)
+    return LSCQP_OK;
+}
+
+int lscqp_plan_set_obstacle_drives(lscqp_plan p, const lscqp_obstacle_drive* drives, int32_t n_dyn, const double* acc_history, int32_t n_history) {
+    if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
+    if (n_dyn < 0 || n_history < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacle_drives: negative size");
+    const bool none = n_dyn == 0 || !drives;
+    if (!none) {
+        if (p->obs.n_dyn == 0)
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacle_drives: the plan has no obstacles (lscqp_plan_set_obstacles first)");
+        if (n_dyn != p->obs.n_dyn)
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacle_drives: n_dyn is not the number of the plan's obstacles");
+        if (n_history > 0 && !acc_history) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacle_drives: null acc_history");
+        PLAN_TRY(lscqp_obstacle_drive_check(p->obs.models.data(), drives, n_dyn, n_history, p->s.n_total));
+    }
+    OnDevice on(p->device);
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_obstacle_drives");
+    lscqp_plan_s::Obstacles::Drives next;  // (none: empty)
+    if (!none) {  // (everything that can fail comes before the plan changes)
+        const size_t nd = (size_t)n_dyn, nh = (size_t)n_history;
+        const char* const what = "lscqp_plan_set_obstacle_drives";
+        PLAN_TRY(lscqp::dev_alloc(next.d_drives, nd, what));
+        PLAN_TRY(lscqp::dev_alloc(next.history, (nh ? nh : 1) * 3, what));
+        PLAN_TRY(lscqp::dev_alloc(next.state, nd, what, true));
+        e = hipMemcpy(next.d_drives.get(), drives, nd * sizeof(lscqp_obstacle_drive), hipMemcpyHostToDevice);
+        if (e == hipSuccess && nh) e = hipMemcpy(next.history.get(), acc_history, nh * 3 * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, what);
+        next.n_history = n_history;
+    }
+    drop_graph(p);  // (a captured chain has, or lacks, the drive's node)
+    p->obs.drv = std::move(next);
+    p->pending = none ? p->pending & ~lscplan::kPendDrives : p->pending | lscplan::kPendDrives;
     return LSCQP_OK;
 }
 

@@ -156,8 +156,13 @@ def load_obstacles(path):
     "max_acc", "downwash"}, ...]; a bare list is taken too) as api.OBSTACLE_MODEL_DTYPE records.  2-D worlds: the file gives z as well."""
     from lsc_dr_planner_amd import api
 
+    return api.obstacle_models(load_obstacle_specs(path))
+
+
+def load_obstacle_specs(path):
+    """The same list as it stands in the file: what api.obstacle_drives reads the chasing and gaussian entries' parameters from."""
     doc = json.load(open(path))
-    return api.obstacle_models(doc["obstacles"] if isinstance(doc, dict) else doc)
+    return doc["obstacles"] if isinstance(doc, dict) else doc
 
 
 def _g(v):
@@ -187,7 +192,7 @@ def write_flight_csv(path, states, obstacles, time_step, record_time_step, plann
 
 
 def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=0, graph=True, until_finished=None, check_every=16,
-                 goal_threshold=0.1, obstacles=None, worlds=None, obstacle_rows="lsc", log_csv=None):
+                 goal_threshold=0.1, obstacles=None, worlds=None, obstacle_rows="lsc", log_csv=None, obstacle_specs=None, obstacle_seed=0):
     """`missions` seeded missions over one world flown by ONE lscqp_plan with a mission partition (include/lscqp.h, "many missions over one
     map"): waypoint_mode 1, closed loop, one captured graph per replan.  The summary has the figures of `run` per mission.
     until_finished = MAX: the plan keeps a mission record (include/lscqp.h, "the mission record") and lscqp_plan_run flies it until every
@@ -196,6 +201,9 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     (lscqp_plan_set_obstacles).  obstacle_rows "lsc": their rows are generateLSC's, so the agents' rows are LSC rows too (GEN_LSC instead
     of GEN_CLSC); "clsc": the plan stays in GEN_CLSC, the mode the reference's launch files run, and the obstacles get generateCLSC's rows
     like an in-range agent.  They take the first row slots: n_obs counts the agent slots, the plan gets n_obs + len(obstacles).
+    obstacle_specs (with obstacles: the mission-file entries the models were made from, load_obstacle_specs): the chasing and gaussian entries
+    are driven on the device (include/lscqp.h, "chasing and gaussian obstacles"; api.obstacle_drives with obstacle_seed for the gaussian
+    histories, drawn for the whole flight); without it such an entry is HELD at its start.
     worlds: one world per mission (load_worlds) in the world's box -- mission k flies over world k (include/lscqp.h, "each mission over its
     own world"; lscqp_plan_set_worlds), its seeded agents drawn from the free nodes of its own world; world 0 replaces the world's own boxes.
     log_csv (with until_finished): a directory; the plan keeps a flight log of MAX rows per mission (include/lscqp.h, "the flight log") and
@@ -237,6 +245,11 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
         plan.set_worlds(world_set)
     if n_dyn:
         plan.set_obstacles(obstacles)
+    n_driven = 0
+    if n_dyn and obstacle_specs is not None:
+        drives, history = api.obstacle_drives(obstacle_specs, N, horizon=((until_finished or steps) + 1) * dt, seed=obstacle_seed)
+        plan.set_obstacle_drives(drives, history)
+        n_driven = int((drives["kind"] != api.DRIVE_NONE).sum())
     if until_finished:
         plan.set_record(goal_threshold)
         if log_csv:
@@ -264,7 +277,8 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
                    finished=sum(m["finished"] for m in per), qp_failed=sum(m["qp_failed"] for m in per), invalid=sum(m["invalid"] for m in per),
                    min_safety_ratio=min(m["min_safety_ratio"] for m in per), per_mission=per)
         if n_dyn:  # (the record keeps no obstacle figure: the last replan's is what the plan still holds)
-            log.update(obstacles=n_dyn, last_obstacle_safety_ratio=float(plan.get_obstacles(api.PLAN_OBS_SAFETY)["safety_ratio_obs"].min()))
+            log.update(obstacles=n_dyn, driven_obstacles=n_driven,
+                       last_obstacle_safety_ratio=float(plan.get_obstacles(api.PLAN_OBS_SAFETY)["safety_ratio_obs"].min()))
         if world_set:
             log["worlds"] = len(world_set)
         if log_csv:
@@ -304,7 +318,7 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
                qp_failed=sum(m["qp_failed"] for m in per), invalid=sum(m["invalid"] for m in per),
                min_safety_ratio=min(m["min_safety_ratio"] for m in per), per_mission=per)
     if n_dyn:
-        log.update(obstacles=n_dyn, min_obstacle_safety_ratio=min_obstacle_ratio)
+        log.update(obstacles=n_dyn, driven_obstacles=n_driven, min_obstacle_safety_ratio=min_obstacle_ratio)
     if world_set:
         log["worlds"] = len(world_set)
     plan.close()
@@ -316,7 +330,7 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
 
 
 def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None, router="host", missions=None,
-        decision="one", until_finished=None, obstacles=None, worlds=None, obstacle_rows="lsc", log_csv=None):
+        decision="one", until_finished=None, obstacles=None, worlds=None, obstacle_rows="lsc", log_csv=None, obstacle_specs=None, obstacle_seed=0):
     """script (optional): {"waypoint": (K, N, 3), "state": (K, N, 9)} -- replay of a recorded mission: replan k takes every agent's
     state and waypoint from the script instead of the loop's own step / router (the plans, goal points, corridors and neighbour sets are
     still the loop's own), and the result carries every replan's solution (`x`, (K, N, nv)) and goal point (`goal`, (K, N, 3)).
@@ -326,7 +340,8 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
     DECISION_AUTO_MIN_AGENTS agents on); the flight is the same whichever is chosen.
     until_finished (with missions): fly until every mission has finished, at most that many replans (run_missions).
     obstacles (with missions): dynamic obstacles flown by the plan's own chain (load_obstacles, run_missions); obstacle_rows "lsc" or "clsc":
-    the generator of their rows, and with it the plan's constraint mode (run_missions).
+    the generator of their rows, and with it the plan's constraint mode (run_missions).  obstacle_specs, obstacle_seed: the file's entries
+    (load_obstacle_specs) -- its chasing and gaussian obstacles are then driven on the device instead of being HELD at their start.
     worlds (with missions): one world per mission -- a directory of world CSVs, a list of CSV paths or of box lists (load_worlds, run_missions).
     log_csv (with until_finished): a directory for every mission's result log in the reference's format, from the device's flight log."""
     if router not in ("host", "device"):
@@ -343,7 +358,7 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
         raise ValueError("log_csv needs until_finished=MAX with missions=K: the log is the plan's flight log, MAX rows per mission")
     if missions:
         return run_missions(world_json, int(missions), steps=steps, M=M, dt=dt, n_obs=n_obs, until_finished=until_finished, obstacles=obstacles,
-                            worlds=worlds, obstacle_rows=obstacle_rows, log_csv=log_csv)
+                            worlds=worlds, obstacle_rows=obstacle_rows, log_csv=log_csv, obstacle_specs=obstacle_specs, obstacle_seed=obstacle_seed)
     import torch
 
     from lsc_dr_planner_amd import api
@@ -551,6 +566,10 @@ if __name__ == "__main__":
     ap.add_argument("--obstacle-rows", default="lsc", choices=("lsc", "clsc"),
                     help="with --obstacles: lsc = generateLSC's rows for obstacles and agents alike (the plan flies GEN_LSC); clsc = the plan keeps "
                          "GEN_CLSC, the reference's launch mode, and the obstacles get generateCLSC's rows")
+    ap.add_argument("--drive-obstacles", action="store_true",
+                    help="with --obstacles: the file's chasing and gaussian obstacles move on the device, inside the chain (without it they are "
+                         "held at their start)")
+    ap.add_argument("--obstacle-seed", type=int, default=0, help="with --drive-obstacles: seed of the gaussian obstacles' acceleration histories")
     ap.add_argument("--worlds", default=None, nargs="+", metavar="CSV",
                     help="with --missions K: K world CSVs (or one directory holding K) in the world's box -- mission k flies over world k, as "
                          "launch/test_all_*.launch pair a mission directory with a world directory")
@@ -561,4 +580,5 @@ if __name__ == "__main__":
     world = random_forest_world(a.forest) if a.forest > 0 else a.world
     print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router, missions=a.missions, decision=a.decision,
                          until_finished=a.until_finished, obstacles=load_obstacles(a.obstacles) if a.obstacles else None, worlds=a.worlds,
-                         obstacle_rows=a.obstacle_rows, log_csv=a.log_csv)))
+                         obstacle_rows=a.obstacle_rows, log_csv=a.log_csv,
+                         obstacle_specs=load_obstacle_specs(a.obstacles) if a.obstacles and a.drive_obstacles else None, obstacle_seed=a.obstacle_seed)))
