@@ -21,7 +21,11 @@
 //   one block of reads, by selects; 256: `primal` read with t, kind and l in front of the test on kind; 512: a two-sided candidate's
 //   stencil and both bounds asked for together; 1024: the candidate's multiplier so far in a register of wavefront 0 beside ctl_[3];
 //   2048: the thread's two-sided rows in registers from the prologue on, and a later pass that asks for its staged rows and every
-//   operand in c_ in one block (tests/test_das_round_trips.py).
+//   operand in c_ in one block (tests/test_das_round_trips.py).  4096, 8192 (bits 1 and 2048, the compile-time carve, a shape whose rows
+//   fit one block of row slots): 4096: the thread's LSC rows translated once in front of the loop of steps and kept in registers with
+//   their positions in c_ -- a later pass reads no staged row (the stores to the staged arrays stay: decode reads the candidate's row
+//   there); 8192: the first pass asks for its operands in c_ and the two-sided rows' in one block, as the later pass
+//   (tests/test_das_row_registers.py).  16384 and 32768: not used (NOTES section 40: one not built, one measured and taken out).
 //   As the prologues, the settings differ in when and by which thread a value is moved, in no expression
 //   that rounds (tests/test_das_step_path.py, tests/test_das_verification.py);
 //   LSCQP_DAS_END(verdict): leaves the phase with a DasVerdict, taken by the whole workgroup at once;
@@ -559,6 +563,29 @@
     // The FIRST pass consumes the rows requested in the prologue (HBM), asks for the rest four at a time and, in the staged form (small
     // batches: LDS to spare), leaves them translated in LDS; later passes read them from there, or from L2.
     bool first_pass = true;  // (uniform)
+#if LSCQP_DAS_STEP_PATH & (4096 | 8192)
+#ifndef LSCQP_DAS_LAYOUT
+#error "LSCQP_DAS_STEP_PATH & (4096 | 8192) sizes the thread's rows from the compile-time carve"
+#endif
+    static_assert((LSCQP_DAS_STEP_PATH & 1) && (LSCQP_DAS_STEP_PATH & 2048) && kMaxNL <= kU * T, "one block of row slots holds every row of the shape");
+#endif
+#if LSCQP_DAS_STEP_PATH & 4096
+    // This thread's LSC rows stay in registers across the loop of steps: row tid + u T is this thread's in every pass, the first pass
+    // translated it (dropped rows and slots past the end neutralised to (0, 0, 0 | -1)) and stored it to the staged arrays, and a later
+    // pass read back what the same thread had written.  With them the control point of each slot: where the row's operands stand in c_.
+    // The staged arrays keep their stores -- decode and the infeasibility proof read the candidate's row from there.
+    // They are translated HERE, in front of the loop of steps and not inside the first pass: nothing in the loop then writes them, and
+    // they are not carried around it through copies.  (prep's text; the rows from memory are waited for where the first pass did.)
+    double kx_[kU], ky_[kU], kz_[kU], kb_[kU];
+    int kcp_[kU];
+#pragma unroll
+    for (int u = 0; u < kU; u++) {
+        const int j = tid + u * T, jc = j < nL ? j : 0;
+        const bool ok = translate(jc, px[u], py[u], pz[u], pw[u], kx_[u], ky_[u], kz_[u], kb_[u]) && j < nL;
+        kx_[u] = ok ? kx_[u] : 0.0, ky_[u] = ok ? ky_[u] : 0.0, kz_[u] = ok ? kz_[u] : 0.0, kb_[u] = ok ? kb_[u] : -1.0;
+        kcp_[u] = jc - P * fdiv(jc, iP);
+    }
+#endif
     // Rows are judged by their RAW slack (metres, the interior-point kernel's bar), which is also what picks the candidate.  Straight-line code:
     // a dropped row, or a slot behind the instance's last row, is the harmless row (0, 0, 0 | -1) -- slack +1 -- instead of a branch.
     auto pass_local = [&](double& bv, int& bi) {
@@ -596,7 +623,11 @@
                 if (j < nL) Sx_[j] = rx[u], Sy_[j] = ry[u], Sz_[j] = rz[u], Sb_[j] = rb[u];
             }
         };
+#if LSCQP_DAS_STEP_PATH & 4096
+        const double* const rx = kx_, * const ry = ky_, * const rz = kz_, * const rb = kb_;  // (the thread's rows, translated above)
+#else
         double rx[kU], ry[kU], rz[kU], rb[kU];
+#endif
 #if LSCQP_DAS_STEP_PATH & 2048
         // the two-sided rows of this thread from the registers the prologue left (tp_*): the pass reads nothing of pix_ / plo_ / phi_, only
         // the stencils' operands in c_, and asks for those where `ts_request` stands
@@ -619,6 +650,34 @@
         };
 #endif
         if (first_pass) {
+#if LSCQP_DAS_STEP_PATH & 8192
+            // The first pass in ONE block of requests, as the later pass: the operands in c_ of the thread's LSC rows and of its two-sided
+            // rows are asked for in front of the translation (which needs the rows from memory and the origin, nothing else of LDS); the
+            // staging stores are issued behind the requests, the slacks are eval's expression in eval's slot order.  One block of row
+            // slots holds every row of the shape: no further trip.
+            double cx[kU], cy[kU], cz[kU];
+#pragma unroll
+            for (int u = 0; u < kU; u++) {
+#if LSCQP_DAS_STEP_PATH & 4096
+                const int cp = kcp_[u];
+#else
+                const int j = tid + u * T, jc = j < nL ? j : 0;
+                const int cp = jc - P * fdiv(jc, iP);
+#endif
+                cx[u] = c_[cp], cy[u] = c_[P + cp], cz[u] = c_[2 * P + cp];
+            }
+            ts_request();
+            __builtin_amdgcn_sched_barrier(0);  // (every request above stands in front of the first use below)
+#if !(LSCQP_DAS_STEP_PATH & 4096)
+            prep(tid, px, py, pz, pw, rx, ry, rz, rb);
+#endif
+            if (staged) stage(tid, rx, ry, rz, rb);
+#pragma unroll
+            for (int u = 0; u < kU; u++) see(rx[u] * cx[u] + ry[u] * cy[u] + rz[u] * cz[u] - rb[u], tid + u * T);  // (eval's expression)
+#elif LSCQP_DAS_STEP_PATH & 4096
+            if (staged) stage(tid, rx, ry, rz, rb);
+            eval(tid, rx, ry, rz, rb);
+#else
             // the prologue's rows, then the rest from memory
             prep(tid, px, py, pz, pw, rx, ry, rz, rb);
             if (staged) stage(tid, rx, ry, rz, rb);
@@ -631,8 +690,20 @@
                 if (staged) stage(j0, rx, ry, rz, rb);
                 eval(j0, rx, ry, rz, rb);
             }
+#endif
         } else if (rows_in_lds) {
-#if LSCQP_DAS_STEP_PATH & 2048
+#if LSCQP_DAS_STEP_PATH & 4096
+            // The later pass reads NO staged row: the thread's rows are the registers the first pass left (what it stored to the staged
+            // arrays, and the harmless row in a slot past the end -- the values the reads and selects below gave).  ONE block of requests:
+            // the rows' operands in c_ and the two-sided rows'.
+            double cx[kU], cy[kU], cz[kU];
+#pragma unroll
+            for (int u = 0; u < kU; u++) cx[u] = c_[kcp_[u]], cy[u] = c_[P + kcp_[u]], cz[u] = c_[2 * P + kcp_[u]];
+            ts_request();
+            __builtin_amdgcn_sched_barrier(0);  // (every request above stands in front of the first use below)
+#pragma unroll
+            for (int u = 0; u < kU; u++) see(rx[u] * cx[u] + ry[u] * cy[u] + rz[u] * cz[u] - rb[u], tid + u * T);  // (eval's expression)
+#elif LSCQP_DAS_STEP_PATH & 2048
             // The later pass in TWO round trips: the staged rows (as bit 1 asks for them; one block holds every row of the shape, so no
             // loop and no test on the thread's first row stand around the loads), and behind them in the same block of requests the
             // operands in c_ of the LSC rows AND of the two-sided rows -- their addresses depend on nothing that is loaded.
@@ -692,8 +763,14 @@
                 double x[kU], y[kU], z[kU], w[kU];
 #pragma unroll
                 for (int u = 0; u < kU; u++) fetch_row(j0 + u * T < nL ? j0 + u * T : 0, x[u], y[u], z[u], w[u]);
+#if LSCQP_DAS_STEP_PATH & 4096
+                double nx_[kU], ny_[kU], nz_[kU], nb_[kU];  // (rows that are not staged: translated again in every pass, as they were)
+                prep(j0, x, y, z, w, nx_, ny_, nz_, nb_);
+                eval(j0, nx_, ny_, nz_, nb_);
+#else
                 prep(j0, x, y, z, w, rx, ry, rz, rb);
                 eval(j0, rx, ry, rz, rb);
+#endif
             }
         }
         first_pass = false;

@@ -46,10 +46,15 @@ constexpr bool carve_fits(int M, int dim, int kmax, int stage_rows) {
 // across the wavefronts, `primal` beside the step's decision, a two-sided candidate's stencil and bounds, the candidate's multiplier in
 // a register, the thread's two-sided rows in registers across the loop of steps.  With them the two forms spill 171 and 234 scalar
 // registers (174 and 242 without).  Bit 512 is kept for the headline, not for its own slot: see the section.
+// Bits 4096 and 8192 (NOTES section 40) take instructions and LDS trips the result does not need off every pass: the thread's LSC
+// rows translated once in front of the loop of steps and kept in registers (a later pass reads no staged row), and the first pass's
+// operands in one block of requests as the later pass's.  With them the two forms spill 161 and 220 scalar registers.  (Bit 32768 --
+// a quiet wavefront reducing its value alone -- paid in its slot and cost the headline all the other two gained: taken out.  Bit
+// 16384 -- the two-sided rows' decoded fields from a table -- is not built.)
 // (-DLSCQP_FUSED_STEP_PATH=<bits> builds a subset: the timing twins of one change.)
 #ifndef LSCQP_FUSED_STEP_PATH
 #if LSCQP_M == 5 || (LSCQP_M == 10 && LSCQP_DIM == 2)
-#define LSCQP_FUSED_STEP_PATH (7 | 8 | 32 | 64 | 128 | 256 | 512 | 1024 | 2048)
+#define LSCQP_FUSED_STEP_PATH (7 | 8 | 32 | 64 | 128 | 256 | 512 | 1024 | 2048 | 4096 | 8192)
 #else
 #define LSCQP_FUSED_STEP_PATH 0
 #endif
