@@ -1385,6 +1385,68 @@ int lscqp_obstacle_drive_host(lscqp_handle h, const lscqp_obstacle_model* models
 int lscqp_plan_set_obstacle_drives(lscqp_plan plan, const lscqp_obstacle_drive* drives, int32_t n_dyn, const double* acc_history,
                                    int32_t n_history);
 
+/* ---- patrol missions: start and goal swapped on arrival, on the device ------------------------------------------------------------------
+ *
+ * With multisim/patrol set the reference's simulator runs in PlannerState::PATROL (src/multi_sync_simulator.cpp:57-61), isFinished never
+ * ends the flight (:401-404), and every agent, at the top of its own plan(), swaps desired_goal_point and start_point as soon as
+ *   desired_goal_point.distance(current_state.position) < param.goal_threshold        (AgentManager::planningStateTransition,
+ *                                                                                      src/agent_manager.cpp:225-240).
+ * The distance is the one the mission record's finish test forms (float32 differences of the position as the state buffer holds it --
+ * z := (float)z_2d in a 2-D class -- and of the goal narrowed to float32; float32 sum of squares, nothing contracted; the square root in
+ * double), compared in double with a STRICT <.  The record's test is `>`: at exact equality a GOTO mission is finished and a patrolling
+ * agent does not turn.  A threshold of 0 is legal and never turns anyone.
+ * lscqp_patrol_device          the transition alone, one thread per agent of d_state [n][9] (LSCQP_PLAN_BUF_STATE's layout): where the test
+ *                          passes, d_desired[a] and d_start[a] ([n][3] doubles) are exchanged in place, d_legs[a] is incremented and
+ *                          d_swapped[a] = 1; elsewhere d_swapped[a] = 0 -- the word is written on every call.  Asynchronous on `stream`,
+ *                          capturable; dim is the class's 2 or 3.
+ * lscqp_patrol_host            the same arguments as HOST pointers, one call on the CPU by the function the kernel runs: no device needed.
+ * lscqp_patrol_check           HOST, no device needed: what lscqp_plan_set_patrol refuses -- a threshold that is negative or not finite, a
+ *                          sharded plan (n_agents != n_total: the rule of safety_samples) -- with the cause named.
+ * lscqp_field_exchange_device  for every agent with d_swapped[a] == 1 the agent's slice [a * nodes, (a + 1) * nodes) of d_field is exchanged
+ *                          with the same slice of d_field_other, word by word, and d_init_d[a] with d_init_d_other[a]; every other word
+ *                          is left alone.  One launch over (agent, chunk of 1024 nodes), dword accesses only.
+ * lscqp_plan_set_patrol        the plan flies a patrol; NULL takes it away.  Like the other setters it waits for the device, drops a captured
+ *                          graph and invalidates the distance fields; lscqp_plan_reset must follow (a step before it is refused by name);
+ *                          a refused call leaves the plan as it was.  closed_loop = 0 is not refused: the caller writes the states, as
+ *                          always.  The reset needs the goal points, puts every agent on leg 0 and zeroes LEGS and SWAPPED.
+ * THE ORDER (one rule).  The reference's loop is decentralizedMAPP over the OLD goals, then per agent the transition, then
+ * TrajPlanner::plan.  So the transition node sits directly behind the waypoint decision and in front of the obstacles' motion and
+ * `prepare`; in waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT the exchange node follows it directly.  That is exactly two more nodes per replan
+ * with a grid and one without; a plan without patrol enqueues the chain it always did, node for node and argument for argument.
+ * WHICH BUFFERS.  Grid mode: LSCQP_PLAN_BUF_DESIRED_GOAL and the plan's start points themselves.  At the reset the plan computes BOTH legs'
+ * distance fields with the entries it always used (a second call with starts and goals exchanged: the same nodes are cleared, the mission
+ * occupancy is the same; one more field per agent), and an agent that turns gets the other field and init_d by the exchange -- the
+ * decision kernels read the active field where they always did.  A map that moves under the mission rebuilds the active field from
+ * (start, desired) as they stand and the other from the exchanged pair, whatever legs the agents are on.  Static goals (optimize_goal = 0,
+ * waypoint_mode = 0): LSCQP_PLAN_BUF_GOAL is the desired goal (goalPlanningWithStaticGoal) and a start buffer of the patrol's own is filled at
+ * the reset.  Caller's waypoints with the goal LP (optimize_goal = 1, waypoint_mode = 0): desired and start buffers of the patrol's own,
+ * for the caller's planner to read.  A mission partition and worlds compose (the field entries are the ones already used); obstacles and
+ * their drives are untouched.  A plan with a record AND a patrol resets its record with desired goals at +infinity: every distance is
+ * +inf, no mission ever finishes, lscqp_plan_run flies to max_replans.
+ * lscqp_plan_patrol_buffer     the patrol's state (device pointers, NULL and 0 bytes where the plan has none: no patrol, or a FIELD entry
+ *                          without a grid). */
+typedef struct lscqp_patrol_desc { /* 8 bytes */
+    double goal_threshold;         /* param.goal_threshold: the launch files' 0.1 */
+} lscqp_patrol_desc;
+#define LSCQP_PATROL_DESIRED 0      /* double[n_total][3]: the desired goals the transition swaps (grid mode: LSCQP_PLAN_BUF_DESIRED_GOAL itself) */
+#define LSCQP_PATROL_START 1        /* double[n_total][3]: the start points */
+#define LSCQP_PATROL_LEGS 2         /* int32[n_total]: legs completed since the reset */
+#define LSCQP_PATROL_SWAPPED 3      /* int32[n_total]: 1 where the last replan's transition turned the agent */
+#define LSCQP_PATROL_FIELD 4        /* int32[n_total][nodes]: the active distance fields (grid mode) */
+#define LSCQP_PATROL_INIT_D 5       /* int32[n_total] */
+#define LSCQP_PATROL_FIELD_OTHER 6  /* ... and those of the opposite leg */
+#define LSCQP_PATROL_INIT_D_OTHER 7
+#define LSCQP_PATROL_COUNT 8
+int lscqp_patrol_check(const lscqp_patrol_desc* desc, int64_t n_agents, int64_t n_total);
+int lscqp_patrol_device(lscqp_handle h, int64_t n, const double* d_state, double* d_desired, double* d_start, double goal_threshold, int32_t dim,
+                        double z_2d, int32_t* d_legs, int32_t* d_swapped, void* stream);
+int lscqp_patrol_host(lscqp_handle h, int64_t n, const double* state, double* desired, double* start, double goal_threshold, int32_t dim,
+                      double z_2d, int32_t* legs, int32_t* swapped, void* stream);
+int lscqp_field_exchange_device(int64_t n, int64_t nodes, const int32_t* d_swapped, int32_t* d_field, int32_t* d_field_other, int32_t* d_init_d,
+                                int32_t* d_init_d_other, void* stream);
+int lscqp_plan_set_patrol(lscqp_plan plan, const lscqp_patrol_desc* desc);
+void* lscqp_plan_patrol_buffer(lscqp_plan plan, int32_t which, uint64_t* bytes_out);
+
 /* ---- work counters of a launch (the fp64-VALU figure next to the HBM one) -----------------------------
  *
  * The kernel is bound by fp64 vector issue, not by HBM; the figure that goes with that roof is

@@ -63,6 +63,13 @@ OBSTACLE_DRIVE_DTYPE = np.dtype([("kind", "i4"), ("target_agent", "i4"), ("max_v
                                  ("initial_vel", "f8", 3), ("acc_update_cycle", "f8"), ("history_first", "i4"), ("history_len", "i4")])
 OBSTACLE_DRIVE_STATE_DTYPE = np.dtype([("i_done", "i4"), ("reserved", "i4"), ("position", "f4", 3), ("velocity", "f4", 3), ("v", "f8", 3)])
 assert OBSTACLE_DRIVE_DTYPE.itemsize == 96 and OBSTACLE_DRIVE_STATE_DTYPE.itemsize == 56
+# lscqp_plan_patrol_buffer (include/lscqp.h, "patrol missions")
+(PATROL_DESIRED, PATROL_START, PATROL_LEGS, PATROL_SWAPPED, PATROL_FIELD, PATROL_INIT_D, PATROL_FIELD_OTHER, PATROL_INIT_D_OTHER) = range(8)
+PATROL_COUNT = 8
+
+
+class PatrolDesc(C.Structure):  # lscqp_patrol_desc
+    _fields_ = [("goal_threshold", C.c_double)]
 
 
 class ObstacleParam(C.Structure):  # lscqp_obstacle_param
@@ -240,6 +247,8 @@ EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_
                     "lscqp_obstacle_model_prepare", "lscqp_obstacles_advance_device", "lscqp_plan_set_obstacles", "lscqp_plan_obstacle_buffer",
                     "lscqp_plan_obstacle_upload", "lscqp_plan_obstacle_download",
                     "lscqp_obstacle_drive_check", "lscqp_obstacles_drive_device", "lscqp_obstacle_drive_host", "lscqp_plan_set_obstacle_drives",
+                    "lscqp_patrol_check", "lscqp_patrol_device", "lscqp_patrol_host", "lscqp_field_exchange_device", "lscqp_plan_set_patrol",
+                    "lscqp_plan_patrol_buffer",
                     "lscqp_worlds_create", "lscqp_worlds_destroy", "lscqp_worlds_prepare", "lscqp_worlds_info", "lscqp_construct_sfc_worlds_device",
                     "lscqp_grid_set_worlds", "lscqp_grid_download_world", "lscqp_plan_set_worlds",
                     "lscqp_instance_work", "lscqp_diagnose", "lscqp_diagnose_device", "lscqp_dump_instance", "lscqp_row_family_name",
@@ -351,6 +360,11 @@ def obstacle_drive_check(models, drives, n_history, n_total):
     if len(m) != len(d):
         raise ValueError("one drive per model")
     _call("lscqp_obstacle_drive_check", m, d, len(d), int(n_history), int(n_total))
+
+
+def patrol_check(goal_threshold, n_agents, n_total):
+    """lscqp_patrol_check: raises LscqpError naming the cause; no device needed."""
+    _call("lscqp_patrol_check", C.byref(PatrolDesc(float(goal_threshold))), int(n_agents), int(n_total))
 
 
 def pack_rows(lsc):
@@ -931,6 +945,36 @@ class Plan:
         a = np.ascontiguousarray(table, dtype=OBSTACLE_DTYPE)
         _call("lscqp_plan_obstacle_upload", self._p, PLAN_OBS_TABLE, a, first * OBSTACLE_DTYPE.itemsize, a.nbytes)
 
+    def set_patrol(self, goal_threshold=0.1):
+        """lscqp_plan_set_patrol: the plan flies a patrol -- every agent swaps start and goal on arrival within goal_threshold (None: no
+        patrol).  `reset` (with the goal points) must follow."""
+        _call("lscqp_plan_set_patrol", self._p, None if goal_threshold is None else C.byref(PatrolDesc(float(goal_threshold))))
+
+    _PATROL_DT = {PATROL_DESIRED: np.float64, PATROL_START: np.float64}  # (every other one: int32)
+
+    def patrol_pointer(self, which):
+        nb = C.c_uint64()
+        ptr = lib().lscqp_plan_patrol_buffer(self._p, int(which), C.byref(nb))
+        return ptr, nb.value
+
+    def patrol(self, which):
+        """lscqp_plan_patrol_buffer, downloaded (waits for the device): PATROL_DESIRED / PATROL_START (n_total, 3) float64, PATROL_LEGS /
+        PATROL_SWAPPED / PATROL_INIT_D[_OTHER] (n_total,) int32, PATROL_FIELD[_OTHER] (n_total, nodes) int32; an empty array where the plan
+        has none (no patrol, or a field entry without a grid)."""
+        import torch
+
+        ptr, nb = self.patrol_pointer(which)
+        dt = np.dtype(self._PATROL_DT.get(which, np.int32))
+        if not ptr or nb == 0:
+            return np.zeros(0, dt)
+
+        class _View:
+            __cuda_array_interface__ = dict(shape=(nb // dt.itemsize,), typestr=dt.str, data=(ptr, False), version=2)
+
+        torch.cuda.synchronize()
+        out = torch.as_tensor(_View(), device="cuda").cpu().numpy()
+        return out.reshape(self.n_total, -1) if which in (PATROL_DESIRED, PATROL_START, PATROL_FIELD, PATROL_FIELD_OTHER) else out
+
     def set_record(self, goal_threshold=0.1):
         """lscqp_plan_set_record: the plan keeps a mission record, accumulated by the chain's last node (None: no record).  `reset` must follow."""
         _call("lscqp_plan_set_record", self._p, None if goal_threshold is None else C.byref(RecordDesc(float(goal_threshold))))
@@ -1460,6 +1504,26 @@ class Solver:
                 raise ValueError("drive_state and table are written in place: contiguous arrays of their dtypes, one record per drive")
         _call("lscqp_obstacle_drive_host", self._h, m, d, len(d), h if len(h) else None, len(h), st if len(st) else None, len(st), drive_state,
               float(time_step), np.array([clock], np.int32), table, None)
+
+    def patrol_device(self, n, d_state, d_desired, d_start, goal_threshold, dim, z_2d, d_legs, d_swapped, stream=None):
+        """lscqp_patrol_device: the PATROL transition of n agents; d_desired / d_start [n][3] float64 are swapped in place where an agent has
+        arrived, d_legs incremented, d_swapped written (1 / 0) for every agent."""
+        _call("lscqp_patrol_device", self._h, int(n), d_state, d_desired, d_start, float(goal_threshold), int(dim), float(z_2d), d_legs, d_swapped, stream=stream)
+
+    def patrol_host(self, state, desired, start, goal_threshold, dim, z_2d, legs, swapped):
+        """lscqp_patrol_host: the same on the CPU, by the function the kernel runs; `desired`, `start` (float64 (n, 3)), `legs` and `swapped`
+        (int32 (n,)) are written in place.  No device needed."""
+        st = np.ascontiguousarray(state, dtype=np.float64).reshape(-1, 9)
+        for a, dt, per in ((desired, np.float64, 3), (start, np.float64, 3), (legs, np.int32, 1), (swapped, np.int32, 1)):
+            if a.dtype != dt or not a.flags.c_contiguous or a.size != len(st) * per:
+                raise ValueError("desired, start, legs and swapped are written in place: contiguous arrays of their dtypes, one entry per agent")
+        _call("lscqp_patrol_host", self._h, len(st), st if len(st) else None, desired, start, float(goal_threshold), int(dim), float(z_2d), legs, swapped, None)
+
+    @staticmethod
+    def field_exchange_device(n, nodes, d_swapped, d_field, d_field_other, d_init_d, d_init_d_other, stream=None):
+        """lscqp_field_exchange_device: the slices [a * nodes, (a + 1) * nodes) of the two int32 fields, and the two init_d words, exchanged
+        for every agent with d_swapped[a] == 1."""
+        _call("lscqp_field_exchange_device", int(n), int(nodes), d_swapped, d_field, d_field_other, d_init_d, d_init_d_other, stream=stream)
 
     def generate_lsc_bytes(self, n_agents, n_obs, n_total):
         return lib().lscqp_generate_lsc_bytes(self._h, n_agents, n_obs, n_total)

@@ -28,10 +28,15 @@
 // rows (the non-agent branch of generateLSC or of generateCLSC, by the plan's constraint_mode; a BVC plan takes no obstacles) behind the agents'
 // rows -- they take the first row slots of every agent -- and the obstacle leg of the safety figures behind the agents'.
 // ObstacleGenerator::update(t, 0) -> obstacle_advance_kernel, src/multi_sync_simulator.cpp:311.
+// A plan that flies a patrol (lscqp_plan_set_patrol) gains the transition node directly behind the waypoint decision -- the reference decides the
+// waypoints over the old goals, then every agent swaps start and goal on arrival at the top of its plan() -- and, with a grid, the node that
+// exchanges the turned agents' distance fields behind it (lscpatrol.hip).
+//   AgentManager::planningStateTransition (PATROL)      -> patrol_kernel, field_exchange_kernel
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -40,6 +45,8 @@
 #include "lscqp_internal.hpp"
 // the obstacles' motion: obstacle_advance_kernel, lscqp_obstacle_model_prepare, lscqp_obstacles_advance_device (built as part of this unit)
 #include "lscobstacle.hip"
+// patrol missions: patrol_kernel, field_exchange_kernel and their entries (built as part of this unit)
+#include "lscpatrol.hip"
 
 namespace lscplan {
 
@@ -204,10 +211,11 @@ enum : unsigned {
     kPendObstacles = 1u << 2,
     kPendWorlds = 1u << 3,
     kPendFlightLog = 1u << 4,
-    kPendDrives = 1u << 5
+    kPendDrives = 1u << 5,
+    kPendPatrol = 1u << 6
 };
 constexpr const char* kPendSetter[] = {"lscqp_plan_set_missions", "lscqp_plan_set_record", "lscqp_plan_set_obstacles", "lscqp_plan_set_worlds",
-                                       "lscqp_plan_set_flight_log", "lscqp_plan_set_obstacle_drives"};
+                                       "lscqp_plan_set_flight_log", "lscqp_plan_set_obstacle_drives", "lscqp_plan_set_patrol"};
 
 }  // namespace lscplan
 
@@ -250,6 +258,7 @@ struct lscqp_plan_s {
         std::unique_ptr<lscqp_grid_s, lscplan::GridDestroy> grid;
         double resolution = 0.5, radius = 0;
         dev_ptr<int32_t> field;
+        size_t field_nodes = 0;  // nodes per agent in `field`
         int32_t *init_d = nullptr, *desired_node = nullptr;  // (these three: made at lscqp_plan_create, in `owned`)
         double* start_pts = nullptr;
         bool fields_valid = false;
@@ -291,6 +300,16 @@ struct lscqp_plan_s {
         dev_ptr<int32_t> world_of;   // [n_total]: the agent's mission
         uint64_t gen = 0;            // the members' generation counters, summed, when the graph and the fields were derived
     } wld;
+    // a patrol (lscqp_plan_set_patrol): on = false = none, the chain as it always was.  `desired` / `start` are the buffers the transition swaps:
+    // the plan's own in grid mode (LSCQP_PLAN_BUF_DESIRED_GOAL, wp.start_pts) and LSCQP_PLAN_BUF_GOAL for static goals, else the patrol's
+    struct Patrol {
+        bool on = false;
+        lscqp_patrol_desc desc = {0.0};
+        double *desired = nullptr, *start = nullptr;
+        dev_ptr<double> own_desired, own_start;
+        dev_ptr<int32_t> legs, swapped;
+        dev_ptr<int32_t> field_other, init_d_other;  // the opposite leg's fields (grid mode); the active ones are wp.field, wp.init_d
+    } pat;
     bool wide() const { return wp.decision == LSCQP_DECISION_WIDE || (wp.decision == LSCQP_DECISION_AUTO && s.n_total >= LSCQP_DECISION_AUTO_MIN_AGENTS); }
 };
 
@@ -366,6 +385,15 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
         else
             PLAN_TRY(lscqp_waypoints_device(grid, lscqp_class_desc_of_(h)->communication_range, s.M, s.dim, s.n_total, state, x_plan, goal, wp.field.get(), wp.init_d,
                                             waypoint, (int32_t*)p->buf[LSCQP_PLAN_BUF_GROUP], wp.desired_node, (int32_t*)p->buf[LSCQP_PLAN_BUF_WAYPOINT_UPDATED], stream));
+    }
+    // planningStateTransition's PATROL branch at the top of every agent's plan() (src/agent_manager.cpp:225-240): behind decentralizedMAPP, which
+    // decided over the old goals, and in front of everything TrajPlanner::plan does.  An agent that turned flies by its other field from here on
+    if (p->pat.on) {
+        const lscqp_plan_s::Patrol& pat = p->pat;
+        PLAN_TRY(lscqp_patrol_device(h, s.n_total, state, pat.desired, pat.start, pat.desc.goal_threshold, s.dim, s.z_2d, pat.legs.get(), pat.swapped.get(), stream));
+        if (grid)
+            PLAN_TRY(lscqp_field_exchange_device(s.n_total, (int64_t)wp.field_nodes, pat.swapped.get(), wp.field.get(), pat.field_other.get(), wp.init_d,
+                                                 pat.init_d_other.get(), stream));
     }
     // obstacle_generator.update(t, 0) at the replan's start time (src/multi_sync_simulator.cpp:311); the clock is the device's.  Chasing and
     // gaussian obstacles first: they read the table as the last replan left it, and the agents' states of this replan's start
@@ -508,12 +536,15 @@ int make_grid(lscqp_plan_s* p, double resolution) {
     double gmin[3];
     int32_t dims[3];
     lscqp_grid_info(gnew.get(), gmin, dims);
-    dev_ptr<int32_t> f;
+    dev_ptr<int32_t> f, fo;
     PLAN_TRY(lscqp::dev_alloc(f, (size_t)p->s.n_total * dims[0] * dims[1], "hipMalloc(distance fields)"));
+    if (p->pat.on) PLAN_TRY(lscqp::dev_alloc(fo, (size_t)p->s.n_total * dims[0] * dims[1], "hipMalloc(distance fields)"));  // (a patrol: both legs)
     PLAN_TRY(p->n_missions() > 1 ? lscqp_grid_reserve_missions_(gnew.get(), p->s.n_total, p->n_missions()) : lscqp_grid_reserve(gnew.get(), p->s.n_total));
     if (p->wp.decision != LSCQP_DECISION_ONE_WORKGROUP) PLAN_TRY(lscqp_grid_reserve_wide(gnew.get(), p->s.n_total));
     p->wp.grid = std::move(gnew);
     p->wp.field = std::move(f);
+    p->wp.field_nodes = (size_t)dims[0] * dims[1];
+    if (p->pat.on) p->pat.field_other = std::move(fo);
     p->wp.resolution = resolution;
     p->wp.fields_valid = false;
     return LSCQP_OK;
@@ -527,6 +558,13 @@ int make_fields(lscqp_plan_s* p) {
                                                    (const double*)p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], wp.field.get(), wp.init_d, nullptr));
     else
         PLAN_TRY(lscqp_grid_fields_device(wp.grid.get(), p->s.n_total, wp.start_pts, (const double*)p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], wp.field.get(), wp.init_d, nullptr));
+    // a patrol: the opposite leg, by the same entry with starts and goals exchanged (the same nodes are cleared: one mission occupancy)
+    if (p->pat.on && p->n_missions() > 1)
+        PLAN_TRY(lscqp_grid_fields_missions_device(wp.grid.get(), p->s.n_total, p->n_missions(), p->mis.moff.data(), p->mis.d_moff.get(),
+                                                   (const double*)p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], wp.start_pts, p->pat.field_other.get(), p->pat.init_d_other.get(), nullptr));
+    else if (p->pat.on)
+        PLAN_TRY(lscqp_grid_fields_device(wp.grid.get(), p->s.n_total, (const double*)p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], wp.start_pts, p->pat.field_other.get(),
+                                          p->pat.init_d_other.get(), nullptr));
     const hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "distance fields");
     wp.fields_valid = true;
@@ -774,6 +812,7 @@ int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* 
     if (!p || !start_positions) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
     if (p->wp.grid && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: the mission's goal points are required");
     if (p->rec.on && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: the mission's goal points are required (the desired goals of the finish test)");
+    if (p->pat.on && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_patrol: the mission's goal points are required (the far end of every leg)");
     OnDevice on(p->device);
     const lscplan::Shape& s = p->s;
     const size_t nt = (size_t)s.n_total, P = (size_t)s.M * 6;
@@ -798,6 +837,18 @@ int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* 
         if (e == hipSuccess) e = hipMemcpy(p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], dg.data(), dg.size() * sizeof(double), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(p->wp.start_pts, gl.data(), gl.size() * sizeof(double), hipMemcpyHostToDevice);
     }
+    if (p->pat.on) {  // every agent on leg 0: the patrol's own buffers (the plan's were written above), no leg flown, nobody turned
+        std::vector<double> sp(nt * 3), want(nt * 3);
+        for (size_t a = 0; a < nt; a++)
+            for (int k = 0; k < 3; k++) {
+                sp[a * 3 + k] = st[a * 9 + k];
+                want[a * 3 + k] = (k < s.dim) ? (double)(float)goal_points[a * 3 + k] : st[a * 9 + k];
+            }
+        if (e == hipSuccess && p->pat.own_start) e = hipMemcpy(p->pat.own_start.get(), sp.data(), sp.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess && p->pat.own_desired) e = hipMemcpy(p->pat.own_desired.get(), want.data(), want.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(p->pat.legs.get(), 0, nt * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMemset(p->pat.swapped.get(), 0, nt * sizeof(int32_t));
+    }
     if (e != hipSuccess) return hip_fail(e, "plan reset");
     if (p->wp.grid) PLAN_TRY(make_fields(p));
     if (p->rec.on) {  // the record of the partition in force, cleared; desired goals in the mission's plane like the states
@@ -805,6 +856,9 @@ int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* 
         std::vector<double> want(nt * 3);
         for (size_t a = 0; a < nt; a++)
             for (int k = 0; k < 3; k++) want[a * 3 + k] = (k < s.dim) ? goal_points[a * 3 + k] : st[a * 9 + k];
+        // a patrol never finishes (isFinished, src/multi_sync_simulator.cpp:401-404): desired goals at +infinity make every distance of the
+        // record's finish test +inf, which exceeds any threshold -- the record's kernel is the one it always was
+        if (p->pat.on) std::fill(want.begin(), want.end(), (double)INFINITY);
         PLAN_TRY(lscqp_record_reset(p->rec.held.get(), want.data()));
     }
     if (p->obs.n_dyn > 0) PLAN_TRY(reset_obstacles(p->obs));
@@ -1142,6 +1196,65 @@ int lscqp_plan_set_obstacle_drives(lscqp_plan p, const lscqp_obstacle_drive* dri
     p->obs.drv = std::move(next);
     p->pending = none ? p->pending & ~lscplan::kPendDrives : p->pending | lscplan::kPendDrives;
     return LSCQP_OK;
+}
+
+int lscqp_plan_set_patrol(lscqp_plan p, const lscqp_patrol_desc* desc) {
+    if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
+    if (desc) PLAN_TRY(lscqp_patrol_check(desc, p->s.n_agents, p->s.n_total));
+    OnDevice on(p->device);
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_patrol");
+    lscqp_plan_s::Patrol next;  // (none: empty)
+    if (desc) {  // (everything that can fail comes before the plan changes)
+        const size_t nt = (size_t)p->s.n_total;
+        const char* const what = "lscqp_plan_set_patrol";
+        PLAN_TRY(lscqp::dev_alloc(next.legs, nt, what, true));
+        PLAN_TRY(lscqp::dev_alloc(next.swapped, nt, what, true));
+        if (p->wp.grid) {  // the plan's own desired goals and start points, and the opposite leg's fields
+            next.desired = (double*)p->buf[LSCQP_PLAN_BUF_DESIRED_GOAL], next.start = p->wp.start_pts;
+            PLAN_TRY(lscqp::dev_alloc(next.field_other, nt * p->wp.field_nodes, what));
+            PLAN_TRY(lscqp::dev_alloc(next.init_d_other, nt, what, true));
+        } else {
+            PLAN_TRY(lscqp::dev_alloc(next.own_start, nt * 3, what, true));
+            if (p->d.optimize_goal) PLAN_TRY(lscqp::dev_alloc(next.own_desired, nt * 3, what, true));
+            // static goals: LSCQP_PLAN_BUF_GOAL is the desired goal (goalPlanningWithStaticGoal); with the goal LP it is the LP's to write
+            next.desired = p->d.optimize_goal ? next.own_desired.get() : (double*)p->buf[LSCQP_PLAN_BUF_GOAL];
+            next.start = next.own_start.get();
+        }
+        next.desc = *desc;
+        next.on = true;
+    }
+    drop_graph(p);  // (a captured chain has, or lacks, the patrol's nodes)
+    p->pat = std::move(next);
+    p->wp.fields_valid = false;  // (the agents may be on any leg: the reset puts them on leg 0 and makes the fields of both)
+    p->pending |= lscplan::kPendPatrol;
+    return LSCQP_OK;
+}
+
+void* lscqp_plan_patrol_buffer(lscqp_plan p, int32_t which, uint64_t* bytes_out) {
+    if (bytes_out) *bytes_out = 0;
+    if (!p || which < 0 || which >= LSCQP_PATROL_COUNT) {
+        lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "unknown patrol buffer");
+        return nullptr;
+    }
+    const lscqp_plan_s::Patrol& pat = p->pat;
+    if (!pat.on) return nullptr;
+    const uint64_t nt = (uint64_t)p->s.n_total, nodes = (uint64_t)p->wp.field_nodes;
+    const bool grid = p->wp.grid != nullptr;
+    void* q = nullptr;
+    uint64_t b = 0;
+    switch (which) {
+    case LSCQP_PATROL_DESIRED: q = pat.desired, b = nt * 3 * sizeof(double); break;
+    case LSCQP_PATROL_START: q = pat.start, b = nt * 3 * sizeof(double); break;
+    case LSCQP_PATROL_LEGS: q = pat.legs.get(), b = nt * sizeof(int32_t); break;
+    case LSCQP_PATROL_SWAPPED: q = pat.swapped.get(), b = nt * sizeof(int32_t); break;
+    case LSCQP_PATROL_FIELD: if (grid) q = p->wp.field.get(), b = nt * nodes * sizeof(int32_t); break;
+    case LSCQP_PATROL_INIT_D: if (grid) q = p->wp.init_d, b = nt * sizeof(int32_t); break;
+    case LSCQP_PATROL_FIELD_OTHER: if (grid) q = pat.field_other.get(), b = nt * nodes * sizeof(int32_t); break;
+    default: if (grid) q = pat.init_d_other.get(), b = nt * sizeof(int32_t); break;
+    }
+    if (bytes_out) *bytes_out = b;
+    return q;
 }
 
 namespace {

@@ -21,6 +21,7 @@
 #include "lscpost_traj.hpp"
 #include "lscqp_device.hpp"
 #include "lscqp_internal.hpp"
+#include "lscqp_point3d.hpp"
 
 
 namespace lscrecord {
@@ -129,13 +130,8 @@ __device__ __forceinline__ void wave_reduce(Part& p) {
     dpp_step<0x143, 0xc>(p);  // row_bcast:31 into rows 2 and 3
 }
 
-// (a - b).norm() of octomath::Vector3: float differences, float sum of squares, the square root of that value in double
-__device__ __forceinline__ double norm_of_difference(const float (&a)[3], const float (&b)[3]) {
-#pragma clang fp contract(off)
-    const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
-    const float nsq = dx * dx + dy * dy + dz * dz;
-    return sqrt((double)nsq);
-}
+// (a - b).norm() of octomath::Vector3 (lscqp_point3d.hpp: the patrol transition of lscpatrol.hip measures with the same function)
+using lscqp::norm_of_difference;
 
 __global__ __launch_bounds__(kThreads) void record_kernel(Args A) {
     __shared__ Part s_part[kWaves];

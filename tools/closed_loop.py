@@ -7,6 +7,7 @@
     python tools/closed_loop.py [--steps 40] [--world tests/golden/forest10_world.json]
     python tools/closed_loop.py --missions 25 --until-finished [MAX]      (K seeded missions in one plan, flown to the finish on the device)
     python tools/closed_loop.py --missions 4 --worlds A.csv B.csv C.csv D.csv   (mission k over world k: one plan, a world per mission)
+    python tools/closed_loop.py --patrol [--goal-threshold T] [--missions K] --steps 400   (a patrol: legs per agent, per mission)
 
 The host keeps the per-agent headers and, with --router host (the default), picks each agent's next waypoint with a stand-in
 for the grid-based planner (8-connected shortest paths, no conflict handling between agents).  --router device replaces
@@ -192,7 +193,7 @@ def write_flight_csv(path, states, obstacles, time_step, record_time_step, plann
 
 
 def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=0, graph=True, until_finished=None, check_every=16,
-                 goal_threshold=0.1, obstacles=None, worlds=None, obstacle_rows="lsc", log_csv=None, obstacle_specs=None, obstacle_seed=0):
+                 goal_threshold=0.1, obstacles=None, worlds=None, obstacle_rows="lsc", log_csv=None, obstacle_specs=None, obstacle_seed=0, patrol=None):
     """`missions` seeded missions over one world flown by ONE lscqp_plan with a mission partition (include/lscqp.h, "many missions over one
     map"): waypoint_mode 1, closed loop, one captured graph per replan.  The summary has the figures of `run` per mission.
     until_finished = MAX: the plan keeps a mission record (include/lscqp.h, "the mission record") and lscqp_plan_run flies it until every
@@ -207,7 +208,9 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     worlds: one world per mission (load_worlds) in the world's box -- mission k flies over world k (include/lscqp.h, "each mission over its
     own world"; lscqp_plan_set_worlds), its seeded agents drawn from the free nodes of its own world; world 0 replaces the world's own boxes.
     log_csv (with until_finished): a directory; the plan keeps a flight log of MAX rows per mission (include/lscqp.h, "the flight log") and
-    every mission's result log is written there in the reference's format, mission_<k>.csv (write_flight_csv)."""
+    every mission's result log is written there in the reference's format, mission_<k>.csv (write_flight_csv).
+    patrol = T: the plan flies a patrol (include/lscqp.h, "patrol missions"; lscqp_plan_set_patrol with goal_threshold T): every agent swaps
+    start and goal on arrival, no mission finishes, and the summary holds the legs every agent completed, per mission."""
     if log_csv and not until_finished:
         raise ValueError("log_csv needs until_finished=MAX: the flight log's capacity")
     world_boxes = None if worlds is None else load_worlds(worlds, missions)  # (before anything needs a device)
@@ -250,6 +253,8 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
         drives, history = api.obstacle_drives(obstacle_specs, N, horizon=((until_finished or steps) + 1) * dt, seed=obstacle_seed)
         plan.set_obstacle_drives(drives, history)
         n_driven = int((drives["kind"] != api.DRIVE_NONE).sum())
+    if patrol is not None:
+        plan.set_patrol(float(patrol))
     if until_finished:
         plan.set_record(goal_threshold)
         if log_csv:
@@ -272,10 +277,16 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
                     max_vel_excess=float(np.linalg.norm(np.float32(r["vel_excess_ratio"]))), max_acc_excess=float(np.linalg.norm(np.float32(r["acc_excess_ratio"]))),
                     waypoints_updated=int(r["waypoint_updates"]), max_in_range=int(r["max_in_range"]), truncated_agent_steps=int(r["truncated"]),
                     walk_bound_reached=int(status[k])) for k, r in enumerate(rec)]
+        if patrol is not None:
+            legs = plan.patrol(api.PATROL_LEGS)
+            for k, m in enumerate(per):
+                m["legs"] = [int(v) for v in legs[int(off[k]):int(off[k + 1])]]
         log = dict(until_finished=int(until_finished), check_every=check_every, goal_threshold=goal_threshold, replans_enqueued=enqueued, missions=missions,
                    agents=N, row_slots=n_obs, router="device", sim_time_s=enqueued * dt, graph_nodes=plan.graph_nodes(),
                    finished=sum(m["finished"] for m in per), qp_failed=sum(m["qp_failed"] for m in per), invalid=sum(m["invalid"] for m in per),
                    min_safety_ratio=min(m["min_safety_ratio"] for m in per), per_mission=per)
+        if patrol is not None:
+            log.update(patrol_goal_threshold=float(patrol), legs=sum(sum(m["legs"]) for m in per))
         if n_dyn:  # (the record keeps no obstacle figure: the last replan's is what the plan still holds)
             log.update(obstacles=n_dyn, driven_obstacles=n_driven,
                        last_obstacle_safety_ratio=float(plan.get_obstacles(api.PLAN_OBS_SAFETY)["safety_ratio_obs"].min()))
@@ -314,9 +325,15 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     for k, m in enumerate(per):
         m["mean_progress_m"] = float(progress[int(off[k]):int(off[k + 1])].mean())
         m["walk_bound_reached"] = int(status[k])
+    if patrol is not None:
+        legs = plan.patrol(api.PATROL_LEGS)
+        for k, m in enumerate(per):
+            m["legs"] = [int(v) for v in legs[int(off[k]):int(off[k + 1])]]
     log = dict(steps=steps, missions=missions, agents=N, row_slots=n_obs, router="device", sim_time_s=steps * dt, graph_nodes=plan.graph_nodes(),
                qp_failed=sum(m["qp_failed"] for m in per), invalid=sum(m["invalid"] for m in per),
                min_safety_ratio=min(m["min_safety_ratio"] for m in per), per_mission=per)
+    if patrol is not None:
+        log.update(patrol_goal_threshold=float(patrol), legs=sum(sum(m["legs"]) for m in per))
     if n_dyn:
         log.update(obstacles=n_dyn, driven_obstacles=n_driven, min_obstacle_safety_ratio=min_obstacle_ratio)
     if world_set:
@@ -330,7 +347,8 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
 
 
 def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None, router="host", missions=None,
-        decision="one", until_finished=None, obstacles=None, worlds=None, obstacle_rows="lsc", log_csv=None, obstacle_specs=None, obstacle_seed=0):
+        decision="one", until_finished=None, obstacles=None, worlds=None, obstacle_rows="lsc", log_csv=None, obstacle_specs=None, obstacle_seed=0,
+        patrol=None):
     """script (optional): {"waypoint": (K, N, 3), "state": (K, N, 9)} -- replay of a recorded mission: replan k takes every agent's
     state and waypoint from the script instead of the loop's own step / router (the plans, goal points, corridors and neighbour sets are
     still the loop's own), and the result carries every replan's solution (`x`, (K, N, nv)) and goal point (`goal`, (K, N, 3)).
@@ -343,7 +361,10 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
     the generator of their rows, and with it the plan's constraint mode (run_missions).  obstacle_specs, obstacle_seed: the file's entries
     (load_obstacle_specs) -- its chasing and gaussian obstacles are then driven on the device instead of being HELD at their start.
     worlds (with missions): one world per mission -- a directory of world CSVs, a list of CSV paths or of box lists (load_worlds, run_missions).
-    log_csv (with until_finished): a directory for every mission's result log in the reference's format, from the device's flight log."""
+    log_csv (with until_finished): a directory for every mission's result log in the reference's format, from the device's flight log.
+    patrol = T: a patrol with goal_threshold T flown by one lscqp_plan (run_missions; missions defaults to 1): legs per agent, per mission."""
+    if patrol is not None and not missions:
+        missions = 1
     if router not in ("host", "device"):
         raise ValueError("router must be 'host' or 'device'")
     if decision not in ("one", "wide", "auto"):
@@ -358,7 +379,8 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
         raise ValueError("log_csv needs until_finished=MAX with missions=K: the log is the plan's flight log, MAX rows per mission")
     if missions:
         return run_missions(world_json, int(missions), steps=steps, M=M, dt=dt, n_obs=n_obs, until_finished=until_finished, obstacles=obstacles,
-                            worlds=worlds, obstacle_rows=obstacle_rows, log_csv=log_csv, obstacle_specs=obstacle_specs, obstacle_seed=obstacle_seed)
+                            worlds=worlds, obstacle_rows=obstacle_rows, log_csv=log_csv, obstacle_specs=obstacle_specs, obstacle_seed=obstacle_seed,
+                            patrol=patrol, **({} if patrol is None else {"goal_threshold": float(patrol)}))
     import torch
 
     from lsc_dr_planner_amd import api
@@ -575,10 +597,15 @@ if __name__ == "__main__":
                          "launch/test_all_*.launch pair a mission directory with a world directory")
     ap.add_argument("--log-csv", default=None, metavar="DIR",
                     help="with --until-finished: keep the flight log on the device and write every mission's result log in the reference's format to DIR/mission_<k>.csv")
+    ap.add_argument("--patrol", action="store_true",
+                    help="fly a patrol for --steps replans (lscqp_plan_set_patrol): every agent swaps start and goal on arrival; prints the legs per "
+                         "agent, with --missions K per mission")
+    ap.add_argument("--goal-threshold", type=float, default=0.1, metavar="T", help="with --patrol: the arrival threshold (the launch files' 0.1)")
     ap.add_argument("--router", default="host", choices=("host", "device"), help="where the waypoints come from: the host stand-in or lscqp_waypoints_device")
     a = ap.parse_args()
     world = random_forest_world(a.forest) if a.forest > 0 else a.world
     print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router, missions=a.missions, decision=a.decision,
                          until_finished=a.until_finished, obstacles=load_obstacles(a.obstacles) if a.obstacles else None, worlds=a.worlds,
                          obstacle_rows=a.obstacle_rows, log_csv=a.log_csv,
-                         obstacle_specs=load_obstacle_specs(a.obstacles) if a.obstacles and a.drive_obstacles else None, obstacle_seed=a.obstacle_seed)))
+                         obstacle_specs=load_obstacle_specs(a.obstacles) if a.obstacles and a.drive_obstacles else None, obstacle_seed=a.obstacle_seed,
+                         patrol=a.goal_threshold if a.patrol else None)))
