@@ -205,8 +205,13 @@ __device__ unsigned long long LSCQP_DAS_CYCLES[16];
     } while (0)
 #endif
 
-// The kernel-argument block of a kernel that holds the phase with LSCQP_DAS_PROLOGUE 1 (the fused forms): every pointer and class scalar the phase reads before its first pass, asked
-// for at kernel entry and waited for ONCE -- in front of the exit test, the order indirection and every branch.  Left where they are used,
+// The two texts of the phase (lscqp_das_body.inc, whose header says what the second does differently): the values of LSCQP_DAS_FORM, which
+// the including kernel defines.
+#define LSCQP_DAS_THROUGHPUT 1  // every value read where it is used, no step setup ahead of the first step: das_kernel, the fused form <10,3,1,10,4>
+#define LSCQP_DAS_LATENCY 2     // one instance with steps is the launch's time: the fused forms <5,3,1,5,2> and <10,2,1,5,2>
+
+// The kernel-argument block of a kernel that holds the phase with LSCQP_DAS_FORM LSCQP_DAS_LATENCY: every pointer and class scalar the phase
+// reads before its first pass, asked for at kernel entry and waited for ONCE -- in front of the exit test, the order indirection and every branch.  Left where they are used,
 // the compiler sinks these reads behind the tests around their uses (a scalar load and a wait of its own per use: seven dependent waits
 // up to the first barrier, the world box through a tree of divergent branches), and it re-reads a class scalar from the kernel-argument
 // segment rather than keep it in a register -- with a wait on the counter the LDS reads share, in the middle of those reads.  The empty
@@ -293,15 +298,13 @@ __global__ __launch_bounds__(64 * NW, (SCREEN ? LSCQP_DAS_WPES : NW == 1 ? LSCQP
     const int64_t k0 = blockIdx.x;
     if (k0 >= n) return;
     const int64_t q = cls.order ? (int64_t)cls.order[k0] : k0;
-    // (the prologue as it was before the kernel-argument block: with the block every one-wavefront form moved in vector registers, and three
-    // forms spilled more scalar registers -- NOTES section 23; these forms run the batches that fill the chip, and their code is unchanged)
-#define LSCQP_DAS_PROLOGUE 0
-#define LSCQP_DAS_STEP_PATH 0  // (likewise the stepping instance's path: a quiet instance of a full chip must not pay for step setup)
+    // (the throughput text: with the kernel-argument block every one-wavefront form moved in vector registers, and three forms spilled more
+    // scalar registers -- NOTES section 23; these forms run the batches that fill the chip, where a quiet instance must not pay for step setup)
+#define LSCQP_DAS_FORM LSCQP_DAS_THROUGHPUT
 #define LSCQP_DAS_END(verdict_) return
 #include "lscqp_das_body.inc"
 #undef LSCQP_DAS_END
-#undef LSCQP_DAS_STEP_PATH
-#undef LSCQP_DAS_PROLOGUE
+#undef LSCQP_DAS_FORM
 }
 
 }  // namespace lscqp_das

@@ -3,31 +3,36 @@
 //   NW, F32, SCREEN, PEEL, T = 64 * NW, kU, kMaxNL (constants; kMaxNL bounds an instance's LSC rows); cls, M, dim, es, cap, kmax, max_steps,
 //   cacheC, stage_rows, behind, tab, q, hdr, rows, row_offsets, sfc, x_init, x_out, obj_out, status_out, info_out; smem (the dynamic LDS,
 //   lscqp_das_lds_bytes(M, dim, kmax, cacheC, stage_rows), or the carve of LSCQP_DAS_LAYOUT);
-//   LSCQP_DAS_PROLOGUE: 1 -- the prologue (everything above DAS_T(1)) scheduled around the kernel-argument block of LSCQP_DAS_KERNARGS
-//   (lscqp_das.hpp: ka_dt, ka_q2s, ka_w_t, ka_w_c, ka_comm_range, ka_use_sfc, ka_rsfc, ka_wb0 .. 5, ka_roffs, ka_sfc), which the kernel has placed
-//   in front of its exit test: the phase then reads no field of cls and neither row_offsets nor sfc by name (the fused forms);
-//   0 -- the prologue as it was, every value read where it is used (das_kernel).  The two differ in WHEN a value is asked for and waited
-//   for, in no expression that rounds: every form of the phase returns the same bytes (tests/test_das_prologue.py);
-//   LSCQP_DAS_STEP_PATH: a set of bits, one per change to the path of an instance that takes steps (0: the text as it was -- das_kernel, whose
-//   forms serve the batches that fill the chip, where a quiet instance must not pay for step setup).  1: the later passes read the
-//   staged rows with clamped, untested loads, all in flight at once.  2: what the first step needs and only the header decides is done
-//   ahead of it -- the factor zeroed in the prologue, the class's table left in LDS by the first pass (needs LSCQP_DAS_LAYOUT and more than
-//   one wavefront).  4: a joining row's descriptors are stored from registers, not copied from the candidate's slot.  8: the verification as
-//   straight-line code -- every operand asked for before the first arithmetic, lam_ kept zero from the prologue on instead of zeroed
-//   behind a barrier of its own (needs LSCQP_DAS_PROLOGUE 1 and more than one wavefront).  16: not used.  32: the objective's rounding
-//   term from one block of loads instead of a loop of six dependent ones (with bit 8 only: the text is in its branch).  64 .. 2048
-//   (four wavefronts and LSCQP_DAS_LAYOUT; 2048 needs bit 1 and a shape whose rows fit one block of row slots): LDS round trips that held
-//   one or two reads, folded -- 64: the four empty-interval ballots in one read, no branch; 128: the pass's minimum across the wavefronts from
-//   one block of reads, by selects; 256: `primal` read with t, kind and l in front of the test on kind; 512: a two-sided candidate's
-//   stencil and both bounds asked for together; 1024: the candidate's multiplier so far in a register of wavefront 0 beside ctl_[3];
-//   2048: the thread's two-sided rows in registers from the prologue on, and a later pass that asks for its staged rows and every
-//   operand in c_ in one block (tests/test_das_round_trips.py).  4096, 8192 (bits 1 and 2048, the compile-time carve, a shape whose rows
-//   fit one block of row slots): 4096: the thread's LSC rows translated once in front of the loop of steps and kept in registers with
-//   their positions in c_ -- a later pass reads no staged row (the stores to the staged arrays stay: decode reads the candidate's row
-//   there); 8192: the first pass asks for its operands in c_ and the two-sided rows' in one block, as the later pass
-//   (tests/test_das_row_registers.py).  16384 and 32768: not used (NOTES section 40: one not built, one measured and taken out).
-//   As the prologues, the settings differ in when and by which thread a value is moved, in no expression
-//   that rounds (tests/test_das_step_path.py, tests/test_das_verification.py);
+//   LSCQP_DAS_FORM: which of the phase's TWO texts the kernel compiles (the values' names are lscqp_das.hpp's).
+//   LSCQP_DAS_THROUGHPUT -- das_kernel in every form and the fused form <10,3,1,10,4>: every value is read where it is used, and nothing
+//   is set up for a first step ahead of it.  das_kernel's forms serve the batches that fill the chip, where a quiet instance must not
+//   pay for step setup, and every one-wavefront form came out worse with the kernel-argument block (NOTES section 23).
+//   LSCQP_DAS_LATENCY -- the fused forms <5,3,1,5,2> and <10,2,1,5,2>, batches of at most one instance per CU, where ONE instance that
+//   takes steps is the launch's time.  What this text does differently:
+//     - the prologue (everything above DAS_T(1)) is scheduled around the kernel-argument block of LSCQP_DAS_KERNARGS (lscqp_das.hpp:
+//       ka_dt, ka_q2s, ka_w_t, ka_w_c, ka_comm_range, ka_use_sfc, ka_rsfc, ka_wb0 .. 5, ka_roffs, ka_sfc), which the kernel has placed in
+//       front of its exit test: one wave of clamped, untested loads, and the phase reads no field of cls and neither row_offsets nor sfc
+//       by name (NOTES section 23, profiles/r15_prologue.txt);
+//     - what the first step needs and only the header decides is done ahead of it: the factor zeroed in the prologue, the class's
+//       table left in LDS by the first pass where it fits the registers; a joining row's descriptors are stored from registers, not
+//       copied from the candidate's slot (section 24, profiles/r16_step_path.txt);
+//     - the verification is straight-line code -- every operand asked for before the first arithmetic, lam_ kept zero from the
+//       prologue on instead of zeroed behind a barrier of its own -- and the objective's rounding term comes from one block of loads
+//       instead of a loop of six dependent ones (section 31, profiles/r23_verification.txt);
+//     - LDS round trips that held one or two reads are folded: the four empty-interval ballots in one read without a branch; the
+//       pass's minimum across the wavefronts from one block of reads, by selects; `primal` read with t, kind and l in front of the test
+//       on kind; a two-sided candidate's stencil and both bounds asked for together; the candidate's multiplier so far in a register
+//       of wavefront 0 beside ctl_[3] (section 35, profiles/r27_round_trips.txt);
+//     - the thread's two-sided rows sit in registers from the prologue on, and its LSC rows -- translated once in front of the loop of
+//       steps -- with their positions in c_: a later pass reads no staged row (the stores to the staged arrays stay: decode reads the
+//       candidate's row there), and the first pass, as the later one, asks for every operand in c_ in one block of requests (sections
+//       35 and 40, profiles/r31_row_registers.txt).
+//   The two texts differ in WHEN, and by which thread, a value is asked for, moved and waited for: no expression that rounds, no order
+//   of a sum or a comparison, no barrier's place.  Every form of the phase therefore returns the same bytes (tests/test_das_prologue.py,
+//   test_das_step_path.py, test_das_verification.py, test_das_round_trips.py, test_das_row_registers.py).  Each change was once a setting
+//   of its own, so that a timing twin could be built with it alone: NOTES section 42 says what became of those settings.
+//   The latency text needs the compile-time carve (LSCQP_DAS_LAYOUT), four wavefronts, and a shape whose LSC rows and two-sided rows fit
+//   one block of row slots each: checked once, below.
 //   LSCQP_DAS_END(verdict): leaves the phase with a DasVerdict, taken by the whole workgroup at once;
 //   LSCQP_DAS_LAYOUT (optional): the LDS carve as a constant expression, with room for at least kmax active rows, the class's table and
 //   stage_rows staged rows; without it the carve is made at run time from kmax, cacheC and stage_rows.  kmax, max_steps, cacheC and
@@ -35,16 +40,33 @@
 // (Text, not a function: the kernel's own code then is exactly what it was as one function -- a __forceinline__ device function holding this
 // body was simplified before it was inlined, through a generic LDS pointer, and das_kernel came out 2 VGPRs and some SGPR spills different
 // and the 512-QP batches 2 % slower, measured.)
-#if LSCQP_DAS_PROLOGUE
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
 #define DAS_CLS(f) ka_##f  // a scalar of the class: the kernel-argument block's register
-#else
+#elif LSCQP_DAS_FORM == LSCQP_DAS_THROUGHPUT
 #define DAS_CLS(f) cls.f  // a scalar of the class: the kernel argument, read where it is used
+#else
+#error "LSCQP_DAS_FORM is LSCQP_DAS_THROUGHPUT or LSCQP_DAS_LATENCY"
 #endif
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 #ifdef LSCQP_DAS_LAYOUT
     constexpr Layout L = LSCQP_DAS_LAYOUT;
 #else
     const Layout L = Layout::make(M, dim, kmax, cacheC, stage_rows);
+#endif
+    constexpr int kPB = 4;  // two-sided rows a thread asks for in one block (the prologue's, and each trip of the section that computes them)
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
+    // ---- what the latency text needs, all of it ----
+#ifndef LSCQP_DAS_LAYOUT
+#error "the latency text sizes its register copies of the rows, and places the class's table, from the compile-time carve"
+#endif
+    // four wavefronts: the folded reads take four ballots, four minima and four ids; the first pass's barrier publishes the table; the
+    // objective's lanes are the second wavefront's; the stationarity rows take one trip of the workgroup
+    static_assert(NW == 4, "the latency text is the four-wavefront form's");
+    static_assert(kMaxNL <= kU * T, "one block of row slots holds every LSC row of the shape: the thread's rows stay in registers");
+    static_assert(L.NPAIR <= kPB * T, "the prologue's one block of slots holds every two-sided row of the shape");
+    static_assert(L.o_red % 2 == 0, "the folded reads of red_ are 16-byte words");
+    // (the class's table: where it fits the registers, cpre[] is loaded whatever cacheC says -- the latency prologue's c_fits -- and the
+    // first pass stores it from there: kTableEarly, below, needs nothing else)
 #endif
     DAS_T_DECL();
     const int P = L.P, NX = L.NX, NPAIR = L.NPAIR;
@@ -81,7 +103,7 @@
         if ((behind & 1) && st_early == LSCQP_STATUS_OPTIMAL) LSCQP_DAS_END(kDasSolved);
         if ((behind & 2) && st_early == LSCQP_STATUS_INFEASIBLE) LSCQP_DAS_END(kDasInfeasible);
     }
-#if LSCQP_DAS_PROLOGUE
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
     // ---- ONE wave of requests: the instance's row offset and obstacle count, the class's two-sided rows, the header, the corridor
     // boxes and the objective's rounding terms -- straight-line code, every address clamped into memory the instance owns, no test around
     // any load (a branch around a load makes the compiler wait for every load right behind it: the loads have to be in flight TOGETHER).
@@ -102,7 +124,6 @@
     const double* const tab_end = tab + (size_t)M * table_stride(M);  // (behind the tables: lscqp_api.hip, das_refresh)
     double dqw = tab_end[min(tid, 35)];
     // the class's two-sided rows (lscqp_das_build_pairs, behind the tables and the 36 rounding terms): the first four of this thread
-    constexpr int kPB = 4;
     const int2* const pairs_g = reinterpret_cast<const int2*>(tab_end + 36);
     int2 pwr[kPB];
 #pragma unroll
@@ -158,7 +179,6 @@
     const uint64_t roff = row_offsets ? row_offsets[q] : 0;
     // the class's two-sided rows (lscqp_das_build_pairs, behind the tables and the 36 rounding terms): the first four of this thread are asked
     // for NOW -- they depend on nothing the header holds
-    constexpr int kPB = 4;
     const int2* const pairs_g = reinterpret_cast<const int2*>(tab + (size_t)M * table_stride(M) + 36);
     int2 pwr[kPB];
 #pragma unroll
@@ -178,7 +198,7 @@
     DAS_T(0);  // header, boxes, row offset
     const lscqp_header* Hd = reinterpret_cast<const lscqp_header*>(H_);
     const lscqp_box* sfcl = reinterpret_cast<const lscqp_box*>(sfc_);
-#if !LSCQP_DAS_PROLOGUE
+#if LSCQP_DAS_FORM == LSCQP_DAS_THROUGHPUT
     const int n_obs = Hd->n_obs;
 #endif
     // Handing an instance over: the interior-point kernel behind this phase solves whatever is not OPTIMAL (cls.repair == 3 there).
@@ -217,7 +237,7 @@
             }
         }
     };
-#if LSCQP_DAS_PROLOGUE
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
     if (!in_cap)
 #else
     if (n_obs > cap || n_obs < 0)
@@ -242,14 +262,14 @@
     const bool comm_on = DAS_CLS(comm_range) > 0;
     const double rho_pair = 0.5 * DAS_CLS(comm_range) - Hd->radius;  // :484
     const double rho_wp = 0.5 * DAS_CLS(comm_range) - 1e-5;          // :495
-#if !LSCQP_DAS_PROLOGUE
+#if LSCQP_DAS_FORM == LSCQP_DAS_THROUGHPUT
     const int nL = n_obs * P;
 #endif
     const float iP = 1.0f / (float)P;
     const bool staged = stage_rows > 0 && nL <= stage_rows;  // (uniform)
     bool rows_in_lds = false;                                // set by the first pass
 
-#if LSCQP_DAS_PROLOGUE
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
     // ---- behind the rows, and under their trip: the table vectors of this thread's control points (they need ts), clamped, no test ----
     constexpr int NE = 4;  // control-point entries per thread the prologue handles in registers (NX <= 4 T for every shape: 216 at M = 12 in 3-D)
     double tu1[NE], tu2[NE], tg1[NE];
@@ -298,12 +318,20 @@
     // its first step -- and in a batch of 64 that one instance is the launch's time); a quiet instance never waits for these loads.
     constexpr int kCPre = (NW == 4 && !PEEL && !SCREEN) ? 6 : 0;  // table entries per thread held in registers (6 x 256 >= 36 M^2 up to M = 6)
     double cpre[kCPre > 0 ? kCPre : 1];
-#if LSCQP_DAS_PROLOGUE
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
     const bool c_fits = kCPre > 0 && P * P <= kCPre * T;  // (uniform; a constant of the shape: the loads then stand in straight-line code)
     const bool c_prefetched = c_fits && cacheC;           // (uniform; the fused forms always keep the table)
+    // What the first step needs and only the header decides, done under the rows' trip instead of on the stepping instance's path: the
+    // factor zeroed by every thread (below, behind c_u; it was wavefront 0's, 17 stores per lane, in front of the first candidate), and --
+    // where the table fits the registers asked for here -- the table left in LDS by the first pass (in front of that pass's barrier,
+    // which publishes it) whatever cacheC says: the compile-time carve has the room, and the values are the table's own either way.
+    // A quiet instance now waits for the table's loads; in a batch of at most one instance per CU its time is not the launch's.
+    // (this text asks for the table whatever cacheC says: the other one would leave cpre[] unset at cacheC == 0)
+    constexpr bool kTableEarly = kCPre > 0 && L.P * L.P <= kCPre * T;
 #else
     const bool c_prefetched = kCPre > 0 && cacheC && P * P <= kCPre * T;  // (uniform)
     const bool c_fits = c_prefetched;
+    constexpr bool kTableEarly = false;
 #endif
     if constexpr (kCPre > 0) {
         if (c_fits) {
@@ -314,22 +342,6 @@
             }
         }
     }
-#if LSCQP_DAS_STEP_PATH & 2
-    // What the first step needs and only the header decides, done under the rows' trip instead of on the stepping instance's path: the
-    // factor zeroed by every thread (below, behind c_u; it was wavefront 0's, 17 stores per lane, in front of the first candidate), and --
-    // where the table fits the registers asked for above -- the table left in LDS by the first pass (in front of that pass's barrier,
-    // which publishes it) whatever cacheC says: the compile-time carve has the room, and the values are the table's own either way.
-    // A quiet instance now waits for the table's loads; in a batch of at most one instance per CU its time is not the launch's.
-#ifndef LSCQP_DAS_LAYOUT
-#error "LSCQP_DAS_STEP_PATH & 2 needs the compile-time carve"
-#endif
-    static_assert(NW > 1, "the first pass's barrier publishes the table");
-    constexpr bool kTableEarly = kCPre > 0 && L.P * L.P <= kCPre * T;
-    // (only the rescheduled prologue asks for the table whatever cacheC says: the other one would leave cpre[] unset at cacheC == 0)
-    static_assert(!kTableEarly || LSCQP_DAS_PROLOGUE, "the table is stored from cpre[]: it needs the prologue that always loads it");
-#else
-    constexpr bool kTableEarly = false;
-#endif
 
     // ---- the two-sided rows, one table for all four families (ids nL + 2 r + side; side 0: stencil - lo >= 0, side 1: hi - stencil >= 0) ----
     //   r in [0, NX)                    interval of one control point: world box, corridor, communication rows on c[m][5]  (:252-265, 372-397, 482-497)
@@ -339,15 +351,12 @@
     // type 0: no row; 1: interval; 2: velocity; 3: acceleration; 4: pair.  Entry indices are positions in c_ (axis * P + control point).
     bool empty = false;
     const double hv_c = dt * 0.2, ha_c = dt * dt * 0.05;
-#if LSCQP_DAS_STEP_PATH & 2048
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
     // This thread's two-sided rows stay in registers across the loop of steps -- they never change after this section, which computes and
     // stores them anyway: the packed stencil, its three positions in c_ and two coefficients (pair_val's), lo, hi.  A slot without a row
-    // (r >= NPAIR) holds stencil 0: no row.  Sized from the shape, as kU is: one slot at M = 5 in 3-D (255 rows), two at M = 10 in 2-D (320).
-#ifndef LSCQP_DAS_LAYOUT
-#error "LSCQP_DAS_STEP_PATH & 2048 sizes its register copy from the compile-time carve"
-#endif
+    // (r >= NPAIR) holds stencil 0: no row.  Sized from the shape, as kU is: one slot at M = 5 in 3-D (255 rows), two at M = 10 in 2-D (320);
+    // the section's first block of kPB slots holds every row of the shape.
     constexpr int kPR = (L.NPAIR + T - 1) / T;
-    static_assert(kPR <= kPB && L.NPAIR <= kPB * T, "the section's first block of four slots holds every two-sided row of the shape");
     int tp_pk[kPR], tp_i0[kPR], tp_i1[kPR], tp_e0[kPR];
     double tp_a1[kPR], tp_a2[kPR], tp_lo[kPR], tp_hi[kPR];
 #pragma unroll
@@ -389,7 +398,7 @@
                 plo_[r] = lo, phi_[r] = hi;
                 pix_[r] = w0;
             }
-#if LSCQP_DAS_STEP_PATH & 2048
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
             if (u < kPR) {  // (a constant of the unrolled loop; r = tid + u T here: the section has one block)
                 const int pk = r < NPAIR ? w0 : 0;
                 const int type = pk >> 24, e0 = (pk >> 12) & 0xfff, e1 = pk & 0xfff;  // (pair_val's decoding, below)
@@ -421,52 +430,33 @@
     }
     if (dim == 2)
         for (int e = tid; e < P; e += T) c_[2 * P + e] = 0.0;
-#if LSCQP_DAS_STEP_PATH & 2
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
     {  // the factor, zeroed behind the section's own LDS traffic, two entries a store (k (k + 1) is even, the carve aligns to 16 bytes)
         double2* const J2 = reinterpret_cast<double2*>(Jm_);
         for (int e = tid; e < kcap * LDL / 2; e += T) J2[e] = make_double2(0.0, 0.0);
     }
-#endif
-#if LSCQP_DAS_STEP_PATH & 8
     // A'u is zero wherever no multiplier is held: the verification reads lam_ without a test and thread 0 adds to it without zeroing it
     // first (finish_local).  The barrier below publishes the zeros; whoever verifies a second time restores them (the polish path).
     for (int e = tid; e < NX; e += T) lam_[e] = 0.0;
-#endif
-#if LSCQP_DAS_PROLOGUE
     // the workgroup's verdict on `empty` with ONE barrier: every wavefront leaves its own ballot in a slot of red_ no reduction uses
     // ([20, 24) of the first half), every thread reads all of them behind the barrier that also publishes c_ and the two-sided rows
     const bool empty_w = __ballot(empty) != 0;  // (wave-uniform)
-    if constexpr (NW > 1) {
-        if (lane == 0) red_[20 + wv] = empty_w ? 1.0 : 0.0;
-    }
+    if (lane == 0) red_[20 + wv] = empty_w ? 1.0 : 0.0;
     LSCQP_DAS_BARRIER();
-    bool empty_g = empty_w;
-    if constexpr (NW > 1) {
-#if LSCQP_DAS_STEP_PATH & 64
-        // the four ballots in one request and one wait, combined without a branch (`||` around a load is a test around a load: four
-        // dependent LDS round trips); they are adjacent and 16-byte aligned in the carve.  A ballot is 0 or 1: their maximum, compared
-        // once (four comparisons joined with `|` are four scalar-register pairs, and <5,3,1,5,2> spilled 184 of them against 174)
-        static_assert(NW == 4 && L.o_red % 2 == 0, "four ballots, two 16-byte words");
-        const double2 b01 = *reinterpret_cast<const double2*>(red_ + 20), b23 = *reinterpret_cast<const double2*>(red_ + 22);
-        empty_g = fmax(fmax(b01.x, b01.y), fmax(b23.x, b23.y)) != 0.0;
-#else
-        empty_g = false;
-#pragma unroll
-        for (int w = 0; w < NW; w++) empty_g = empty_g || red_[20 + w] != 0.0;
-#endif
-    }
+    // the four ballots in one request and one wait, combined without a branch (`||` around a load is a test around a load: four
+    // dependent LDS round trips); they are adjacent and 16-byte aligned in the carve: two 16-byte words.  A ballot is 0 or 1: their
+    // maximum, compared once (four comparisons joined with `|` are four scalar-register pairs, and <5,3,1,5,2> spilled 184 of them
+    // against 174)
+    const double2 b01 = *reinterpret_cast<const double2*>(red_ + 20), b23 = *reinterpret_cast<const double2*>(red_ + 22);
+    const bool empty_g = fmax(fmax(b01.x, b01.y), fmax(b23.x, b23.y)) != 0.0;
 #else
     if (tid == 0) ctl_[4] = 0.0;
     LSCQP_DAS_BARRIER();
     if (empty) ctl_[4] = 1.0;  // (benign race: every writer stores 1)
     LSCQP_DAS_BARRIER();
+    const bool empty_g = ctl_[4] != 0.0;
 #endif
-#if LSCQP_DAS_PROLOGUE
-    if (empty_g)
-#else
-    if (ctl_[4] != 0.0)
-#endif
-    {  // an empty interval (lo > hi on one control point: exact); its violation is the largest overlap lo - hi
+    if (empty_g) {  // an empty interval (lo > hi on one control point: exact); its violation is the largest overlap lo - hi
         double ov = 0.0;
         if (wv == 0) {  // (the two-sided rows of the other families have lo = -hs <= hi = hs: they never raise it)
             for (int r = lane; r < NPAIR; r += 64)
@@ -526,7 +516,7 @@
             R.rhs = b;
             return;
         }
-#if LSCQP_DAS_STEP_PATH & 512
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
         // the stencil and BOTH bounds asked for together, at a clamped index; the side selects the bound (it chose which one to READ,
         // behind the stencil's wait: a second round trip).  (Not taken by an empty asm: that costs <5,3,1,5,2> four scalar-register
         // spills.  Without it <10,2,1,5,2>, where the id is a scalar, still waits for the stencil in front of the two bounds.)
@@ -538,7 +528,7 @@
 #endif
         const int type = pk >> 24, e0 = (pk >> 12) & 0xfff, e1 = pk & 0xfff;
         const double sg = (s & 1) ? -1.0 : 1.0;
-#if LSCQP_DAS_STEP_PATH & 512
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
         R.rhs = (s & 1) ? -hi_w : lo_w;
 #else
         R.rhs = (s & 1) ? -phi_[r] : plo_[r];
@@ -563,13 +553,7 @@
     // The FIRST pass consumes the rows requested in the prologue (HBM), asks for the rest four at a time and, in the staged form (small
     // batches: LDS to spare), leaves them translated in LDS; later passes read them from there, or from L2.
     bool first_pass = true;  // (uniform)
-#if LSCQP_DAS_STEP_PATH & (4096 | 8192)
-#ifndef LSCQP_DAS_LAYOUT
-#error "LSCQP_DAS_STEP_PATH & (4096 | 8192) sizes the thread's rows from the compile-time carve"
-#endif
-    static_assert((LSCQP_DAS_STEP_PATH & 1) && (LSCQP_DAS_STEP_PATH & 2048) && kMaxNL <= kU * T, "one block of row slots holds every row of the shape");
-#endif
-#if LSCQP_DAS_STEP_PATH & 4096
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
     // This thread's LSC rows stay in registers across the loop of steps: row tid + u T is this thread's in every pass, the first pass
     // translated it (dropped rows and slots past the end neutralised to (0, 0, 0 | -1)) and stored it to the staged arrays, and a later
     // pass read back what the same thread had written.  With them the control point of each slot: where the row's operands stand in c_.
@@ -623,12 +607,8 @@
                 if (j < nL) Sx_[j] = rx[u], Sy_[j] = ry[u], Sz_[j] = rz[u], Sb_[j] = rb[u];
             }
         };
-#if LSCQP_DAS_STEP_PATH & 4096
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
         const double* const rx = kx_, * const ry = ky_, * const rz = kz_, * const rb = kb_;  // (the thread's rows, translated above)
-#else
-        double rx[kU], ry[kU], rz[kU], rb[kU];
-#endif
-#if LSCQP_DAS_STEP_PATH & 2048
         // the two-sided rows of this thread from the registers the prologue left (tp_*): the pass reads nothing of pix_ / plo_ / phi_, only
         // the stencils' operands in c_, and asks for those where `ts_request` stands
         double tv0[kPR], tv1[kPR], tv2[kPR];
@@ -648,35 +628,26 @@
                 see(on ? tp_hi[u] - d : 1.0, nL + 2 * r + 1);
             }
         };
+#else
+        double rx[kU], ry[kU], rz[kU], rb[kU];
 #endif
         if (first_pass) {
-#if LSCQP_DAS_STEP_PATH & 8192
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
             // The first pass in ONE block of requests, as the later pass: the operands in c_ of the thread's LSC rows and of its two-sided
-            // rows are asked for in front of the translation (which needs the rows from memory and the origin, nothing else of LDS); the
-            // staging stores are issued behind the requests, the slacks are eval's expression in eval's slot order.  One block of row
-            // slots holds every row of the shape: no further trip.
+            // rows (the translation above needs the rows from memory and the origin, nothing else of LDS); the staging stores are issued
+            // behind the requests, the slacks are eval's expression in eval's slot order.  One block of row slots holds every row of the
+            // shape: no further trip.
             double cx[kU], cy[kU], cz[kU];
 #pragma unroll
             for (int u = 0; u < kU; u++) {
-#if LSCQP_DAS_STEP_PATH & 4096
                 const int cp = kcp_[u];
-#else
-                const int j = tid + u * T, jc = j < nL ? j : 0;
-                const int cp = jc - P * fdiv(jc, iP);
-#endif
                 cx[u] = c_[cp], cy[u] = c_[P + cp], cz[u] = c_[2 * P + cp];
             }
             ts_request();
             __builtin_amdgcn_sched_barrier(0);  // (every request above stands in front of the first use below)
-#if !(LSCQP_DAS_STEP_PATH & 4096)
-            prep(tid, px, py, pz, pw, rx, ry, rz, rb);
-#endif
             if (staged) stage(tid, rx, ry, rz, rb);
 #pragma unroll
             for (int u = 0; u < kU; u++) see(rx[u] * cx[u] + ry[u] * cy[u] + rz[u] * cz[u] - rb[u], tid + u * T);  // (eval's expression)
-#elif LSCQP_DAS_STEP_PATH & 4096
-            if (staged) stage(tid, rx, ry, rz, rb);
-            eval(tid, rx, ry, rz, rb);
 #else
             // the prologue's rows, then the rest from memory
             prep(tid, px, py, pz, pw, rx, ry, rz, rb);
@@ -692,10 +663,10 @@
             }
 #endif
         } else if (rows_in_lds) {
-#if LSCQP_DAS_STEP_PATH & 4096
-            // The later pass reads NO staged row: the thread's rows are the registers the first pass left (what it stored to the staged
-            // arrays, and the harmless row in a slot past the end -- the values the reads and selects below gave).  ONE block of requests:
-            // the rows' operands in c_ and the two-sided rows'.
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
+            // The later pass reads NO staged row: the thread's rows are the registers the first pass stored to the staged arrays from (and
+            // the harmless row in a slot past the end -- the values the other text's reads give).  ONE block of requests: the rows'
+            // operands in c_ and the two-sided rows'.
             double cx[kU], cy[kU], cz[kU];
 #pragma unroll
             for (int u = 0; u < kU; u++) cx[u] = c_[kcp_[u]], cy[u] = c_[P + kcp_[u]], cz[u] = c_[2 * P + kcp_[u]];
@@ -703,50 +674,6 @@
             __builtin_amdgcn_sched_barrier(0);  // (every request above stands in front of the first use below)
 #pragma unroll
             for (int u = 0; u < kU; u++) see(rx[u] * cx[u] + ry[u] * cy[u] + rz[u] * cz[u] - rb[u], tid + u * T);  // (eval's expression)
-#elif LSCQP_DAS_STEP_PATH & 2048
-            // The later pass in TWO round trips: the staged rows (as bit 1 asks for them; one block holds every row of the shape, so no
-            // loop and no test on the thread's first row stand around the loads), and behind them in the same block of requests the
-            // operands in c_ of the LSC rows AND of the two-sided rows -- their addresses depend on nothing that is loaded.
-            static_assert((LSCQP_DAS_STEP_PATH & 1) && kMaxNL <= kU * T, "one block of clamped, untested loads covers the instance's rows");
-            double lx[kU], ly[kU], lz[kU], lb[kU], cx[kU], cy[kU], cz[kU];
-#pragma unroll
-            for (int u = 0; u < kU; u++) {
-                const int j = tid + u * T, jc = j < nL ? j : 0;
-                lx[u] = Sx_[jc], ly[u] = Sy_[jc], lz[u] = Sz_[jc], lb[u] = Sb_[jc];
-            }
-#pragma unroll
-            for (int u = 0; u < kU; u++) {
-                const int j = tid + u * T, jc = j < nL ? j : 0;
-                const int cp = jc - P * fdiv(jc, iP);
-                cx[u] = c_[cp], cy[u] = c_[P + cp], cz[u] = c_[2 * P + cp];
-            }
-            ts_request();
-            __builtin_amdgcn_sched_barrier(0);  // (every request above stands in front of the first use below)
-#pragma unroll
-            for (int u = 0; u < kU; u++) {
-                const int j = tid + u * T;
-                const bool in = j < nL;
-                rx[u] = in ? lx[u] : 0.0, ry[u] = in ? ly[u] : 0.0, rz[u] = in ? lz[u] : 0.0, rb[u] = in ? lb[u] : -1.0;
-                see(rx[u] * cx[u] + ry[u] * cy[u] + rz[u] * cz[u] - rb[u], j);  // (eval's expression)
-            }
-#elif LSCQP_DAS_STEP_PATH & 1
-            // every staged row of this thread asked for at once, the index clamped into the staged arrays and no test around a load; a slot
-            // past the end becomes the harmless row by selects on the loaded values (a test around a load serialises the loads: each slot
-            // then is an LDS round trip of its own, and the reads of c_ in eval come behind the last of them)
-            for (int j0 = tid; j0 < nL; j0 += kU * T) {
-                double lx[kU], ly[kU], lz[kU], lb[kU];
-#pragma unroll
-                for (int u = 0; u < kU; u++) {
-                    const int j = j0 + u * T, jc = j < nL ? j : 0;
-                    lx[u] = Sx_[jc], ly[u] = Sy_[jc], lz[u] = Sz_[jc], lb[u] = Sb_[jc];
-                }
-#pragma unroll
-                for (int u = 0; u < kU; u++) {
-                    const bool in = j0 + u * T < nL;
-                    rx[u] = in ? lx[u] : 0.0, ry[u] = in ? ly[u] : 0.0, rz[u] = in ? lz[u] : 0.0, rb[u] = in ? lb[u] : -1.0;
-                }
-                eval(j0, rx, ry, rz, rb);
-            }
 #else
             for (int j0 = tid; j0 < nL; j0 += kU * T) {
 #pragma unroll
@@ -763,7 +690,7 @@
                 double x[kU], y[kU], z[kU], w[kU];
 #pragma unroll
                 for (int u = 0; u < kU; u++) fetch_row(j0 + u * T < nL ? j0 + u * T : 0, x[u], y[u], z[u], w[u]);
-#if LSCQP_DAS_STEP_PATH & 4096
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
                 double nx_[kU], ny_[kU], nz_[kU], nb_[kU];  // (rows that are not staged: translated again in every pass, as they were)
                 prep(j0, x, y, z, w, nx_, ny_, nz_, nb_);
                 eval(j0, nx_, ny_, nz_, nb_);
@@ -775,8 +702,8 @@
         }
         first_pass = false;
         DAS_T(8);
-#if LSCQP_DAS_STEP_PATH & 2048
-        if (!ts_asked) ts_request();  // (the first pass, and a pass over rows that are not staged)
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
+        if (!ts_asked) ts_request();  // (a pass over rows that are not staged)
         ts_see();
 #else
         for (int r0 = tid; r0 < NPAIR; r0 += 2 * T) {  // two at a time: their LDS round trips overlap
@@ -795,10 +722,10 @@
     };
     // the workgroup's (slack, id) minimum out of the wavefronts' (buffer rb_: values at [0, 4), ids as ints at [4, 6))
     auto pass_combine = [&](const double* rb_, double& bv, int& bi) {
-#if LSCQP_DAS_STEP_PATH & 128
-        // the four values and the four ids in one request and one wait (the buffer is 16-byte aligned), the lexicographic minimum by
-        // selects in the loop's order: `||` and `&&` around the loads made three to four dependent LDS round trips and six branches of it
-        static_assert(NW == 4 && L.o_red % 2 == 0, "four values and four ids, three 16-byte words");
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
+        // the four values and the four ids in one request and one wait (three 16-byte words: the buffer is 16-byte aligned), the lexicographic
+        // minimum by selects in the loop's order: `||` and `&&` around the loads made three to four dependent LDS round trips and six
+        // branches of it
         const double2 v01 = *reinterpret_cast<const double2*>(rb_), v23 = *reinterpret_cast<const double2*>(rb_ + 2);
         const int4 ids = *reinterpret_cast<const int4*>(rb_ + 4);
         const double ovs[4] = {v01.x, v01.y, v23.x, v23.y};
@@ -824,8 +751,7 @@
         double bv;
         int bi;
         pass_local(bv, bi);
-#if LSCQP_DAS_STEP_PATH & 2
-        if constexpr (kTableEarly) {
+        if constexpr (kTableEarly) {  // (the latency text, where the table fits the registers)
             if (was_first) {  // the class's table, from the registers the prologue asked for; the barrier below publishes it
 #pragma unroll
                 for (int i = 0; i < kCPre; i++) {
@@ -834,7 +760,6 @@
                 }
             }
         }
-#endif
         wave_argmin(bv, bi);
         if constexpr (NW > 1) {
             double* const rb_ = red_ + 24 * par;
@@ -931,27 +856,19 @@
     // as cplex.getObjValue() reports it (as lscqp_kernel.hpp).  Every z thread evaluates the <= 4 control-point rows of Hx it needs itself.
     const int NZA = 3 * (M - 1) + (es ? 1 : 3);
     auto finish_local = [&](int k, double& rd, double& gs, double& part) {
-#if LSCQP_DAS_PROLOGUE
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
         // (the class's, left in LDS by the prologue; the two ka_ names stand in front of the block's registers for DAS_CLS below)
         const double dt = wb_[6], q2s = wb_[7], ka_w_t = ctl_[4], ka_w_c = red_[44], wt2 = 2.0 * ka_w_t;
-#endif
-#if LSCQP_DAS_STEP_PATH & 8
-        // The same verification as straight-line code (the expressions that round are the text below's, word for word): every operand of
-        // a stationarity lane -- header words, origin, the twelve words of c_ of its segment and the next -- is asked for before the first
-        // arithmetic, at clamped indices and without a test around a load (a lane past the last row evaluates the last row, a last
+        // The same verification as straight-line code (the expressions that round are the other text's below, word for word): every operand
+        // of a stationarity lane -- header words, origin, the twelve words of c_ of its segment and the next -- is asked for before the
+        // first arithmetic, at clamped indices and without a test around a load (a lane past the last row evaluates the last row, a last
         // segment evaluates itself as its "next" one; their values are dropped by selects).  lam_ is read as it stands: the prologue
         // zeroed it, thread 0 adds A'u to the zeros, so no zeroing pass and no barrier of its own stand in front of thread 0's sums.
-#if !LSCQP_DAS_PROLOGUE
-#error "LSCQP_DAS_STEP_PATH & 8 reads the class's scalars from LDS: it needs the rescheduled prologue"
-#endif
-        static_assert(NW > 1, "the stationarity rows take one trip of the workgroup");
-        // the objective's part of this thread (bit 32: from one block of loads; otherwise the text of the #else branch below)
+        // the objective's part of this thread, from one block of loads
         auto objective_local = [&]() {
-#if LSCQP_DAS_STEP_PATH & 32
-            // One wavefront, straight-line: the lane's six control points, the 36 words of the rounding term, origin and goal are all asked
-            // for in front of the first arithmetic (the row-at-a-time loop was six dependent LDS round trips); the sums in the loop's order.
-            // (a lane without a segment evaluates the last one and its value is dropped)
-            static_assert(NW > 1, "the objective's lanes are the second wavefront's");
+            // One wavefront (the second), straight-line: the lane's six control points, the 36 words of the rounding term, origin and goal
+            // are all asked for in front of the first arithmetic (the other text's row-at-a-time loop is six dependent LDS round trips);
+            // the sums in the loop's order.  (a lane without a segment evaluates the last one and its value is dropped)
             part = 0.0;
             if (__builtin_amdgcn_readfirstlane(wv) == 1) {
                 const bool on = lane < dim * M;
@@ -989,34 +906,6 @@
                 const double sum = part + pp;
                 part = on ? sum : part;
             }
-#else
-            part = 0.0;
-            // (the objective's threads sit in the second wavefront when there is one: its arithmetic runs beside the stationarity rows' instead of behind them)
-            for (int lv = tid - (NW > 1 ? 64 : 0); lv < dim * M; lv += T) {
-                if (lv < 0) continue;
-                const int kx = lv / M, m = lv - kx * M;
-                const double* cc = &c_[kx * P + 6 * m];
-                const double j0 = (cc[3] - cc[0]) - 3.0 * (cc[2] - cc[1]);
-                const double j1 = (cc[4] - cc[1]) - 3.0 * (cc[3] - cc[2]);
-                const double j2 = (cc[5] - cc[2]) - 3.0 * (cc[4] - cc[3]);
-                const double quad = 0.2 * (j0 * j0 + j2 * j2) + (2.0 / 15.0) * j1 * j1 + 0.2 * (j0 * j1 + j1 * j2) + (1.0 / 15.0) * j0 * j2;
-                double pp = 0.5 * q2s * 3600.0 * quad;
-                const double ok_ = org[kx];
-                double corr = 0;
-                const double s0 = cc[0] + ok_, s1 = cc[1] + ok_, s2 = cc[2] + ok_, s3 = cc[3] + ok_, s4 = cc[4] + ok_, s5 = cc[5] + ok_;
-#pragma unroll 1
-                for (int i = 0; i < 6; i++) {  // (a row of the term at a time: unrolled, its 36 entries would be requested -- and held in registers -- at once)
-                    const double* dr = dq_ + 6 * i;
-                    double r = 0;
-                    r += dr[0] * s0, r += dr[1] * s1, r += dr[2] * s2, r += dr[3] * s3, r += dr[4] * s4, r += dr[5] * s5;
-                    corr += r * (cc[i] + ok_);
-                }
-                pp += DAS_CLS(w_c) * corr;
-                const double dgoal = cc[5] - (Hd->goal[kx] - ok_);
-                pp += (m >= M - ts) ? DAS_CLS(w_t) * dgoal * dgoal : 0.0;
-                part += pp;
-            }
-#endif
         };
         const int nz = dim * NZA;  // (<= 108 < T)
         const bool zw = __builtin_amdgcn_readfirstlane(wv) * 64 < nz;  // (wave-uniform: a wavefront without a row skips the section)
@@ -1265,7 +1154,7 @@
             // multipliers, c = c_u + sum u_j C a_j -- stationary up to the table's rounding -- and one refinement of the multipliers that
             // puts the active rows back at zero slack:  rho = h_A - A c,  du = S^-1 rho,  u += du,  c += sum du_j C a_j.  Then every row
             // is looked at again.
-#if LSCQP_DAS_STEP_PATH & 8
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
             // (this path verifies again: lam_ goes back to zero first -- behind the verification's reduction barrier, so every lane has
             // read it -- where thread 0 added, and only inside lam_: in 2-D an LSC row's third entry names axis 2 with coefficient 0,
             // which addresses plo_ behind lam_, and that word keeps what the sums left in it.  The barriers below publish the zeros.)
@@ -1308,8 +1197,8 @@
             why = LSCQP_DAS_WHY_ROWS;
             break;
         }
-#if LSCQP_DAS_STEP_PATH & 2
-        (void)haveJ, (void)haveC;  // (the first-step setup is done: nothing to remember)
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
+        (void)haveJ, (void)haveC;  // (the prologue has zeroed the factor: nothing to remember)
 #else
         if (!haveJ) {  // (before the first step; by wavefront 0, the only one that touches J: in order with its own use)
             if (wv == 0)
@@ -1358,7 +1247,7 @@
         if constexpr (NW == 1) compute_wp(0, T);
         DAS_T(5);  // candidate: decode, table copy (one wavefront: w_p)
         double spp = 0.0;  // a_p'C a_p (wavefront 0)
-#if LSCQP_DAS_STEP_PATH & 1024
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
         // the candidate's multiplier so far, in a register of wavefront 0 beside ctl_[3] (zeroed above, the same sums in the same order:
         // the decision's t is the same in every lane of the wavefront); the decision takes the register instead of a round trip to LDS
         double u_cand = 0.0;
@@ -1383,7 +1272,7 @@
                 const double sp = row_dot(Rp.ent, Rp.coef, c_) - Rp.rhs;
                 const double t = (spp > 1e-12 * spp) ? -sp / spp : 1e300;
                 const int kind = (t < 1e299) ? 1 : 0;
-#if LSCQP_DAS_STEP_PATH & 1024
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
                 u_cand = u_cand + t;
                 if (lane == 0) {
                     if (kind == 1) Jm_[0] = rsqrt(spp), u_[0] = u_cand;
@@ -1430,14 +1319,14 @@
                         if (lane == 0) Jm_[k * LDL + k] = idl, u_[k] = DAS_U_CAND + t;
                     }
                 }
-#if LSCQP_DAS_STEP_PATH & 1024
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
                 u_cand = u_cand + t;
 #endif
                 if (lane == 0) {
                     ctl_[0] = t;
                     ctl_[1] = (double)kind;
                     ctl_[2] = (double)l;
-#if LSCQP_DAS_STEP_PATH & 1024
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
                     ctl_[3] = u_cand;
 #else
                     ctl_[3] += t;
@@ -1451,7 +1340,7 @@
             LSCQP_DAS_BARRIER();
             const double t = ctl_[0];
             const int kind = __builtin_amdgcn_readfirstlane((int)ctl_[1]), l = __builtin_amdgcn_readfirstlane((int)ctl_[2]);  // (uniform: scalar loop bounds)
-#if LSCQP_DAS_STEP_PATH & 256
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
             // `primal` in the same block of reads as t, kind and l, in front of the test on kind (behind it the read was a round trip of
             // its own; the decision stores ctl_[5] whatever kind it finds)
             double primal_w = ctl_[5];
@@ -1465,7 +1354,7 @@
             }
             // c += t (w_p - sum r_j w_j)   (r_ holds this step's r); a leaving row closes the gap in W on the way (the candidate moves down too)
             const int ks = __builtin_amdgcn_readfirstlane(k);  // (uniform by construction; said so: scalar loop bounds)
-#if LSCQP_DAS_STEP_PATH & 256
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
             const bool primal = __builtin_amdgcn_readfirstlane((int)primal_w) != 0;
 #else
             const bool primal = __builtin_amdgcn_readfirstlane((int)ctl_[5]) != 0;
@@ -1494,7 +1383,7 @@
             }
             DAS_T(11);  // the step itself: c, W
             if (kind == 1) {
-#if LSCQP_DAS_STEP_PATH & 4
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
                 // the joining row's descriptors, from the registers every thread holds (slot kcap keeps the copy the candidate left there --
                 // nothing has written it since -- and is not read here: eight LDS round trips of one thread in front of the barrier)
                 if (tid == 0) {

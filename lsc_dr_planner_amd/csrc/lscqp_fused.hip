@@ -28,36 +28,16 @@ namespace lscqp_das {
 constexpr bool carve_fits(int M, int dim, int kmax, int stage_rows) {
     return sizeof(double) * (size_t)Layout::make(M, dim, kmax, 1, stage_rows).total <= lscqp::kMaxLdsBytes;
 }
-// Which prologue the phase runs here (lscqp_das_body.inc, LSCQP_DAS_PROLOGUE): the rescheduled one on the kernel-argument block, except in
-// the M = 10, 3-D instance -- there the block costs scalar registers (306 SGPR spills against 292) and the form keeps the prologue it had.
+// Which of the phase's two texts runs here (lscqp_das_body.inc, LSCQP_DAS_FORM; its header says what the latency text does differently):
+// the M = 5 form and the M = 10, 2-D form run the latency text, with which they spill 161 and 220 scalar registers.  The rule of NOTES
+// section 24 decided per form: a change stays where the scalar-register spills do not grow or a timing pays for the growth.  Any other
+// shape -- the M = 10, 3-D form -- keeps the throughput text: there the kernel-argument block costs scalar registers (306 SGPR spills
+// against 292), and so did the first-step setup ahead of the first step (301 - 312 against 292); it has not been built with the rest.
 // (this unit is compiled once per instance: the shape is the preprocessor's as well as the template's)
-#if LSCQP_M == 10 && LSCQP_DIM == 3
-#define LSCQP_FUSED_PROLOGUE 0
-#else
-#define LSCQP_FUSED_PROLOGUE 1
-#endif
-// Which changes to the stepping instance's path the phase runs here (lscqp_das_body.inc, LSCQP_DAS_STEP_PATH: a set of bits, one per
-// change): the M = 5 form and the M = 10, 2-D form run the three of NOTES section 24 (bits 1, 2, 4) and the straight-line verification
-// with the objective's rounding term from one block of loads (bits 8, 32: NOTES section 31).  The rule of section 24 decides per form: an
-// item stays where the scalar-register spills do not grow or a timing pays for the growth.  With three row slots (below) the 2-D form
-// spills 242 with all of them against 245 without and the parent's 251, and c0 runs 7 % faster; the M = 10, 3-D form spilled 301 - 312
-// against 292 with the first three, has not been built with the others, and keeps the text it had.
-// Bits 64 .. 2048 (NOTES section 35) fold LDS round trips that held one or two reads: the empty-interval ballots, the pass's minimum
-// across the wavefronts, `primal` beside the step's decision, a two-sided candidate's stencil and bounds, the candidate's multiplier in
-// a register, the thread's two-sided rows in registers across the loop of steps.  With them the two forms spill 171 and 234 scalar
-// registers (174 and 242 without).  Bit 512 is kept for the headline, not for its own slot: see the section.
-// Bits 4096 and 8192 (NOTES section 40) take instructions and LDS trips the result does not need off every pass: the thread's LSC
-// rows translated once in front of the loop of steps and kept in registers (a later pass reads no staged row), and the first pass's
-// operands in one block of requests as the later pass's.  With them the two forms spill 161 and 220 scalar registers.  (Bit 32768 --
-// a quiet wavefront reducing its value alone -- paid in its slot and cost the headline all the other two gained: taken out.  Bit
-// 16384 -- the two-sided rows' decoded fields from a table -- is not built.)
-// (-DLSCQP_FUSED_STEP_PATH=<bits> builds a subset: the timing twins of one change.)
-#ifndef LSCQP_FUSED_STEP_PATH
 #if LSCQP_M == 5 || (LSCQP_M == 10 && LSCQP_DIM == 2)
-#define LSCQP_FUSED_STEP_PATH (7 | 8 | 32 | 64 | 128 | 256 | 512 | 1024 | 2048 | 4096 | 8192)
+#define LSCQP_DAS_FORM LSCQP_DAS_LATENCY
 #else
-#define LSCQP_FUSED_STEP_PATH 0
-#endif
+#define LSCQP_DAS_FORM LSCQP_DAS_THROUGHPUT
 #endif
 template <int M, int DIM, bool ES, int NSLOT, int W>
 struct FusedCarve {
@@ -77,7 +57,7 @@ __global__ __launch_bounds__(256, 1) void das_pdip_kernel(DevClass cls, int cap,
                                                           lscqp_info* __restrict__ info_out) {
     static_assert(W >= 1 && W <= 4, "the interior-point instance runs on the first W of the workgroup's four wavefronts");
     extern __shared__ __attribute__((aligned(16))) double smem[];
-#if LSCQP_FUSED_PROLOGUE
+#if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
     LSCQP_DAS_KERNARGS();  // (one block of kernel-argument reads, one wait: lscqp_das.hpp)
     const int64_t k0 = blockIdx.x;
     if (k0 >= n) return;
@@ -94,12 +74,7 @@ __global__ __launch_bounds__(256, 1) void das_pdip_kernel(DevClass cls, int cap,
         // Row slots per thread, from the carve: as many as a full instance's rows need, at most four.  The 600-row forms get three -- a
         // fourth would load, translate, stage-test and evaluate a row that cannot exist, in the prologue and in every pass; the 2 400-row
         // form keeps four and loops.  (The pass's (slack, id) minimum is lexicographic: it does not depend on which thread saw which row.)
-        // (-DLSCQP_FUSED_ROW_SLOTS=4 builds the four slots every form had: a timing twin's column)
-#ifdef LSCQP_FUSED_ROW_SLOTS
-        constexpr int kU = LSCQP_FUSED_ROW_SLOTS;
-#else
         constexpr int kU = (FC::kStage + T - 1) / T < 4 ? (FC::kStage + T - 1) / T : 4;
-#endif
         constexpr bool F32 = false, SCREEN = false, PEEL = false;
         constexpr int dim = DIM, es = ES ? 1 : 0, behind = 0;
         constexpr int kMaxNL = FC::kStage;  // (an instance beyond the launch's cap <= MAX_OBS is handed over before its rows are read)
@@ -112,11 +87,7 @@ __global__ __launch_bounds__(256, 1) void das_pdip_kernel(DevClass cls, int cap,
         goto phase_done;          \
     } while (0)
 #define LSCQP_DAS_LAYOUT Layout::make(M, DIM, FC::KMAX, 1, FC::kStage)
-#define LSCQP_DAS_PROLOGUE LSCQP_FUSED_PROLOGUE
-#define LSCQP_DAS_STEP_PATH LSCQP_FUSED_STEP_PATH
 #include "lscqp_das_body.inc"
-#undef LSCQP_DAS_STEP_PATH
-#undef LSCQP_DAS_PROLOGUE
 #undef LSCQP_DAS_LAYOUT
 #undef LSCQP_DAS_END
     }

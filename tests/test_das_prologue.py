@@ -3,9 +3,9 @@ requests with its clamped addresses, the rows asked for ahead of the header's tr
 interval -- on the inputs at which an address, a count or a flag of that code can go wrong.
 
 Small batches (at most 8 instances) of the two smallest fused shapes, M5 in 3-D and M10 in 2-D, each through four forms of the kernel: the
-fused launch (the rescheduled prologue, LSCQP_DAS_PROLOGUE 1: both shapes' fused forms have it; one test asserts that this form IS one
-launch), the two launches with 256 threads per instance, and the one- and two-wavefront forms (das_threads 64 / 128), which keep the
-prologue as it was.  Every form
+fused launch (the rescheduled prologue of the phase's latency text, LSCQP_DAS_FORM LSCQP_DAS_LATENCY: both shapes' fused forms run it; one
+test asserts that this form IS one launch), the two launches with 256 threads per instance, and the one- and two-wavefront forms
+(das_threads 64 / 128), which run the throughput text: every value read where it is used.  Every form
 must return the same bytes in x, obj, status and info; every instance the batch expects OPTIMAL is finished by the phase and held to the
 polished CPU oracle at the bars of tests/test_das_families_gpu.py (x 1e-8 m, objective 1e-8 relative); every other instance to the status
 the batch names.  Nothing is left out of the comparison.

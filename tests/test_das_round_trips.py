@@ -1,9 +1,9 @@
-"""The one-read LDS waits folded in the fused phase (csrc/lscqp_das_body.inc, LSCQP_DAS_STEP_PATH bits 64 .. 2048): the empty-interval verdict
+"""The one-read LDS waits folded in the fused phase (csrc/lscqp_das_body.inc, the latency text): the empty-interval verdict
 from one read of the four ballots, the pass's cross-wavefront minimum by selects, `primal` read with the step's decision, a two-sided
 candidate's stencil and bounds in one request, the candidate's multiplier kept in a register beside ctl_[3], and each thread's two-sided
 rows kept in registers across the loop of steps -- on the inputs at which a slot, a tie, a side or a sum of that code can go wrong.
 
-Small batches (at most 8 instances) of the two fused shapes that take the bits, M5 in 3-D and M10 in 2-D, each through the four forms of
+Small batches (at most 8 instances) of the two fused shapes that run the latency text, M5 in 3-D and M10 in 2-D, each through the four forms of
 tests/test_das_prologue.py: the fused launch (the new text; one test asserts that this form IS one launch), the two launches and the one-
 and two-wavefront forms (the text as it was).  Every form must return the same bytes in x, obj, status and info -- new text against old;
 every instance expected OPTIMAL is finished by the phase, in the step count of the CPU restatement (tests/das_reference.py) wherever that

@@ -1,8 +1,8 @@
 """Each thread's LSC rows kept in registers across the loop of steps and the first pass in one block of requests (csrc/lscqp_das_body.inc,
-LSCQP_DAS_STEP_PATH bits 4096 and 8192) -- on the inputs at which a row slot, a dropped row, a slot past the instance's last row or the
+the latency text, LSCQP_DAS_FORM LSCQP_DAS_LATENCY) -- on the inputs at which a row slot, a dropped row, a slot past the instance's last row or the
 pass's minimum over the wavefronts can go wrong.
 
-Small batches (at most 8 instances) of the two fused shapes that take the bits, M5 in 3-D and M10 in 2-D, each through the four forms of
+Small batches (at most 8 instances) of the two fused shapes that run the latency text, M5 in 3-D and M10 in 2-D, each through the four forms of
 tests/test_das_prologue.py: the fused launch (the new text; one test asserts that this form IS one launch), the two launches and the one-
 and two-wavefront forms (the text as it was).  Every form must return the same bytes in x, obj, status and info -- new text against old;
 every instance expected OPTIMAL is finished by the phase, in the step count of the CPU restatement (tests/das_reference.py) wherever that

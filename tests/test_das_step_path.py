@@ -5,10 +5,9 @@ inputs at which an index, a tail slot, a position in the list of active rows or 
 
 Small batches (at most 8 instances) of the two smallest fused shapes, M5 in 3-D and M10 in 2-D, each through four forms of the kernel: the
 fused launch (one test asserts that this form IS one launch), the two launches with 256 threads per instance, and the one- and
-two-wavefront forms.  Only the M5 fused form runs the rewritten step path (LSCQP_DAS_STEP_PATH in csrc/lscqp_fused.hip); every other form
-here, the M10 fused form included, keeps the step path as it was.  So "the same bytes in every form" compares the new text with the old
-one in the M5d3 cases only; the M10d2 cases compare old with old and are regression cases of the old text against the oracle and the
-restatement -- they do NOT cover a rewritten M10 path, which does not exist.  Every instance expected OPTIMAL is finished by the phase, in the step count of the CPU restatement
+two-wavefront forms.  The fused forms of both shapes run the phase's latency text (LSCQP_DAS_FORM in csrc/lscqp_fused.hip), which holds the
+rewritten step path; every other form here runs the throughput text, the step path as it was.  So "the same bytes in every form" compares
+the latency text with the throughput text, and both with the oracle and the restatement.  Every instance expected OPTIMAL is finished by the phase, in the step count of the CPU restatement
 (tests/das_reference.py) wherever that one decided every step by more than 1e-6 m, and held to the polished CPU oracle at the bars of
 tests/test_das_families_gpu.py (x 1e-8 m, objective 1e-8 relative).  The builders assert their premises on the CPU: the oracle calls the
 instance OPTIMAL, the restatement takes the intended steps, holds the intended rows and drops a row from the intended position."""

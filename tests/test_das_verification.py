@@ -1,5 +1,5 @@
 """The fused phase's row slots sized to its rows, and its verification as straight-line code (csrc/lscqp_fused.hip: kU; csrc/lscqp_das_body.inc:
-finish_local under LSCQP_DAS_STEP_PATH bits 8 and 32) -- on the inputs at which a slot, a clamped index or the multipliers' array can go
+finish_local in the latency text, LSCQP_DAS_FORM LSCQP_DAS_LATENCY) -- on the inputs at which a slot, a clamped index or the multipliers' array can go
 wrong: a cutting plane whose candidate rows lie in the first slot, across the boundaries between the slots (ids 255 | 256 and 511 | 512) and
 in the last rows the three slots cover; obstacle counts that fill two slots, three, the capacity and one more; an instance without rows
 between two that step; and verifications that read multipliers -- one and two rows held, a row that left, an LSC row beside a two-sided
