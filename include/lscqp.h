@@ -1215,6 +1215,58 @@ int lscqp_record_log_download(lscqp_record rec, int32_t mission, int32_t first_r
                               float* obstacles);
 int lscqp_plan_set_flight_log(lscqp_plan plan, int32_t max_replans);
 
+/* ---- the obstacle record: each mission's least agent-obstacle safety ratio over the whole flight -----------------------------------------
+ *
+ * The reference's summary line carries safety_ratio_obs, the minimum over the flight of the agent-obstacle safety ratio (MultiSyncSimulator::
+ * update, src/multi_sync_simulator.cpp:527-557, written at :658-709).  lscqp_safety_obstacles_device forms the figure of ONE replan per agent;
+ * a record that has been given those figures keeps their minimum per mission and per agent in a side buffer of its own: ONE more kernel
+ * (csrc/lscrecord.hip: record_obstacles_kernel, one workgroup per mission), enqueued in front of the flight log's kernel where there is
+ * one, otherwise in front of the record's own, on the same stream.  lscqp_mission_record itself is unchanged.
+ * The kernel reads the record's `finished` word and replan counter before the record's kernel, behind it, sets and increments them: replan
+ * r of a mission that has not finished is accumulated as r (the rule of the flight log), and a finished mission's figures are frozen with
+ * its record -- its workgroup returns after loading one word.  At replan r, for every mission not finished, from the lscqp_safety_obs
+ * [n_total] of the replan:
+ *   - per agent a: its entry takes the replan's figure, with r and the figure's closest_obstacle and sample, where the figure is STRICTLY
+ *     smaller than the entry's (an earlier replan keeps a tie; a NaN is never taken);
+ *   - compared grows by the agents whose figure is finite, below_one by those whose figure is < 1.0 (strict; 1.0 itself is not counted);
+ *   - the replan's minimum over the mission's agents, ties to the smallest agent id, replaces the mission's figure -- with r, that agent's
+ *     GLOBAL id, its closest_obstacle and sample -- where it is STRICTLY smaller: the reference's `if (safety_ratio_obs > current)` applied in
+ *     the order replan, then agent id, the order of safety_ratio_agent in the mission record.
+ * No floating-point atomics: the result does not depend on how the agents fall onto lanes.
+ * lscqp_record_set_obstacle_figures  d_safety_obs: DEVICE pointer [n_total], borrowed, read at every later lscqp_record_step_device; NULL removes
+ *                                    the obstacle record (its figures with it).  The first use allocates the side buffer, cleared.  Waits
+ *                                    for the device.  A failed call leaves the record as it was.  lscqp_record_reset clears the figures: ratios
+ *                                    +inf, replan / agent / obstacle / sample -1, counts 0.  A record without obstacle figures enqueues
+ *                                    exactly what it always did.
+ * lscqp_record_obstacles_download    out [n_missions] and, if not NULL, agents [n_total] (global id order); waits for the device.
+ *                                    LSCQP_ERR_INVALID_ARGUMENT where the record keeps no obstacle figures.
+ * lscqp_record_obstacles_raw         raw device pointer of the side buffer and its size, as lscqp_record_points (NULL without obstacle figures):
+ *                                    LSCQP_OBSREC_SPARE bytes, lscqp_mission_obstacle_record [n_missions], LSCQP_OBSREC_SPARE bytes,
+ *                                    lscqp_agent_obstacle_record [n_total], LSCQP_OBSREC_SPARE bytes.  Nothing ever writes the spare bytes.
+ * lscqp_plan_set_obstacle_record     on != 0 has the plan's record keep the obstacle figures of the plan's LSCQP_PLAN_OBS_SAFETY buffer (0: no
+ *                                    longer).  Needs a record and obstacles (LSCQP_ERR_INVALID_ARGUMENT names the one that is missing); it may
+ *                                    come before or after lscqp_plan_set_flight_log; taking the record or the obstacles away takes it away
+ *                                    with them.  Waits for the device, drops a captured graph; lscqp_plan_reset must follow (a step before
+ *                                    it is refused) and re-attaches the figures to the record of the partition in force.  The chain gains one
+ *                                    node, in front of the log's or else the record's, which stays the last.  Because missions freeze, the
+ *                                    obstacle record of a flight through lscqp_plan_run does not depend on check_every.  A plan that does not
+ *                                    ask for it enqueues the chain it always did, node for node. */
+#define LSCQP_OBSREC_SPARE 64
+typedef struct lscqp_mission_obstacle_record { /* 40 bytes */
+    double safety_ratio_obs;                 /* +inf: nothing compared (SP_INFINITY in the reference) */
+    int32_t replan, agent, obstacle, sample; /* attaining it; -1: none.  agent is a GLOBAL id */
+    int64_t below_one;                       /* agent-replans whose replan minimum was < 1.0 (strict) */
+    int64_t compared;                        /* agent-replans with a finite figure */
+} lscqp_mission_obstacle_record;
+typedef struct lscqp_agent_obstacle_record { /* 24 bytes */
+    double safety_ratio_obs;                 /* the agent's own running minimum, +inf */
+    int32_t replan, obstacle, sample, reserved;
+} lscqp_agent_obstacle_record;
+int lscqp_record_set_obstacle_figures(lscqp_record rec, const lscqp_safety_obs* d_safety_obs);
+int lscqp_record_obstacles_download(lscqp_record rec, lscqp_mission_obstacle_record* out, lscqp_agent_obstacle_record* agents);
+void* lscqp_record_obstacles_raw(lscqp_record rec, uint64_t* bytes_out);
+int lscqp_plan_set_obstacle_record(lscqp_plan plan, int32_t on);
+
 /* ---- dynamic obstacles in the chain: their motion on the device, their rows and their safety figures ------------------------------------
  *
  * The reference's missions list dynamic obstacles (mission file "obstacles": spin, straight, patrol, chasing, gaussian, real; include/
@@ -1267,7 +1319,7 @@ int lscqp_plan_set_flight_log(lscqp_plan plan, int32_t max_replans);
  *                            lscqp_safety_obstacles_device behind the agent safety figures.  A mission
  *                            partition shares the obstacles like the map; every owner of a sharded mission advances its own copy of the
  *                            same table.  The waypoint decision does not see obstacles, as in the reference.  The mission record keeps
- *                            no obstacle figure.
+ *                            no obstacle figure itself; the obstacle record beside it does (lscqp_plan_set_obstacle_record).
  * lscqp_plan_obstacle_buffer / _upload / _download   the buffers that exist only with obstacles (NULL and 0 bytes otherwise), addressed
  *                            by LSCQP_PLAN_OBS_*; copies are synchronous like lscqp_plan_upload / _download. */
 #define LSCQP_OBSTACLE_MAX_WAYPOINTS 8

@@ -244,6 +244,7 @@ EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_
                     "lscqp_record_points", "lscqp_record_unfinished", "lscqp_plan_set_record", "lscqp_plan_record", "lscqp_plan_run",
                     "lscqp_record_set_log", "lscqp_record_log_obstacles", "lscqp_record_log", "lscqp_record_log_rows", "lscqp_record_log_download",
                     "lscqp_plan_set_flight_log",
+                    "lscqp_record_set_obstacle_figures", "lscqp_record_obstacles_download", "lscqp_record_obstacles_raw", "lscqp_plan_set_obstacle_record",
                     "lscqp_obstacle_model_prepare", "lscqp_obstacles_advance_device", "lscqp_plan_set_obstacles", "lscqp_plan_obstacle_buffer",
                     "lscqp_plan_obstacle_upload", "lscqp_plan_obstacle_download",
                     "lscqp_obstacle_drive_check", "lscqp_obstacles_drive_device", "lscqp_obstacle_drive_host", "lscqp_plan_set_obstacle_drives",
@@ -621,6 +622,14 @@ MISSION_RECORD_DTYPE = np.dtype([("finished", "i4"), ("replans", "i4"), ("first_
                                  ("goal_failed", "i8"), ("sfc_kept", "i8"), ("waypoint_updates", "i8"), ("max_in_range", "i8"), ("truncated", "i8")])
 
 
+# the obstacle record (include/lscqp.h, "the obstacle record"): lscqp_mission_obstacle_record (40 bytes), lscqp_agent_obstacle_record (24 bytes)
+# and the spare bytes around the two arrays in the raw side buffer
+MISSION_OBSTACLE_RECORD_DTYPE = np.dtype([("safety_ratio_obs", "f8"), ("replan", "i4"), ("agent", "i4"), ("obstacle", "i4"), ("sample", "i4"),
+                                          ("below_one", "i8"), ("compared", "i8")])
+AGENT_OBSTACLE_RECORD_DTYPE = np.dtype([("safety_ratio_obs", "f8"), ("replan", "i4"), ("obstacle", "i4"), ("sample", "i4"), ("reserved", "i4")])
+OBSREC_SPARE = 64
+
+
 # the flight log (include/lscqp.h, "the flight log"): the buffers of lscqp_record_log and the bits of a flags word
 LOG_STATES, LOG_FLAGS, LOG_OBSTACLES = 0, 1, 2
 LOG_FLAG_QP_FAILED, LOG_FLAG_INVALID, LOG_FLAG_GOAL_FAILED, LOG_FLAG_SFC_KEPT, LOG_FLAG_WAYPOINT = 1, 2, 4, 8, 16
@@ -741,6 +750,35 @@ class Record:
         ob = np.zeros((max(n, 0), self.log_n_dyn, 4), np.float32)
         _call("lscqp_record_log_download", self._r, k, int(first_replan), n, st, fl, ob)
         return st, fl, ob
+
+
+    def set_obstacle_figures(self, d_safety_obs):
+        """lscqp_record_set_obstacle_figures: the device array (SAFETY_OBS_DTYPE records, n_total, borrowed) whose minimum the record keeps
+        per mission and per agent from the next step on; None removes the obstacle record.  Waits for the device."""
+        _call("lscqp_record_set_obstacle_figures", self._r, d_safety_obs)
+
+    def obstacles(self):
+        """lscqp_record_obstacles_download: (missions (K,) MISSION_OBSTACLE_RECORD_DTYPE, agents (n_total,) AGENT_OBSTACLE_RECORD_DTYPE);
+        waits for the device."""
+        ms = np.zeros(self.n_missions, MISSION_OBSTACLE_RECORD_DTYPE)
+        ag = np.zeros(self.n_total, AGENT_OBSTACLE_RECORD_DTYPE)
+        _call("lscqp_record_obstacles_download", self._r, ms, ag)
+        return ms, ag
+
+    def obstacles_tensor(self):
+        """The obstacle record's raw side buffer as a flat uint8 torch tensor over the device memory itself: OBSREC_SPARE bytes, the missions'
+        structs, OBSREC_SPARE bytes, the agents' structs, OBSREC_SPARE bytes (include/lscqp.h: lscqp_record_obstacles_raw)."""
+        import torch
+
+        nb = C.c_uint64()
+        ptr = lib().lscqp_record_obstacles_raw(self._r, C.byref(nb))
+        if not ptr:
+            raise LscqpError(ERR_INVALID_ARGUMENT, lib().lscqp_last_error().decode())
+
+        class _View:
+            __cuda_array_interface__ = dict(shape=(nb.value,), typestr="|u1", data=(ptr, False), version=2)
+
+        return torch.as_tensor(_View(), device="cuda")
 
 
 AGENT_PARAM_DTYPE = np.dtype([("radius", "f8"), ("downwash", "f8"), ("max_vel", "f8", 3), ("max_acc", "f8", 3), ("nominal_velocity", "f8")])
@@ -997,6 +1035,11 @@ class Plan:
         (0: none).  Needs `set_record` first; `reset` must follow."""
         _call("lscqp_plan_set_flight_log", self._p, int(max_replans))
         self._log_capacity = int(max_replans)
+
+    def set_obstacle_record(self, on=True):
+        """lscqp_plan_set_obstacle_record: the plan's record keeps each mission's least obstacle safety ratio over the flight, read with
+        `record().obstacles()`.  Needs `set_record` and `set_obstacles` first; `reset` must follow."""
+        _call("lscqp_plan_set_obstacle_record", self._p, int(bool(on)))
 
     def run(self, max_replans, check_every=1, graph=True, stream=None):
         """lscqp_plan_run: replans until every mission of the record has finished or max_replans; returns the replans enqueued."""

@@ -212,10 +212,12 @@ enum : unsigned {
     kPendWorlds = 1u << 3,
     kPendFlightLog = 1u << 4,
     kPendDrives = 1u << 5,
-    kPendPatrol = 1u << 6
+    kPendPatrol = 1u << 6,
+    kPendObstacleRecord = 1u << 7
 };
 constexpr const char* kPendSetter[] = {"lscqp_plan_set_missions", "lscqp_plan_set_record", "lscqp_plan_set_obstacles", "lscqp_plan_set_worlds",
-                                       "lscqp_plan_set_flight_log", "lscqp_plan_set_obstacle_drives", "lscqp_plan_set_patrol"};
+                                       "lscqp_plan_set_flight_log", "lscqp_plan_set_obstacle_drives", "lscqp_plan_set_patrol",
+                                       "lscqp_plan_set_obstacle_record"};
 
 }  // namespace lscplan
 
@@ -276,6 +278,7 @@ struct lscqp_plan_s {
         lscqp_record_desc desc = {0.0};
         std::unique_ptr<lscqp_record_s, lscplan::RecordDestroy> held;  // of the partition in force; empty between set_missions and the reset
         int32_t log_capacity = 0;  // the flight log's rows per mission (lscqp_plan_set_flight_log), 0 = none: given to every record made
+        bool obstacle_figures = false;  // the obstacle record (lscqp_plan_set_obstacle_record): every record made reads obs.safety
     } rec;
     // dynamic obstacles (lscqp_plan_set_obstacles): n_dyn = 0 = none, the chain as it always was.  They take row slots [0, n_dyn) of every agent
     struct Obstacles {
@@ -586,6 +589,7 @@ int make_record(lscqp_plan_s* p, const lscqp_record_desc& desc) {
                                   p->d.safety_samples, p->d.record_time_step, p->d.time_step, p->s.z_2d, &desc, &rnew));
     decltype(p->rec.held) made(rnew);
     PLAN_TRY(give_log(made.get(), p->rec.log_capacity, p->obs));
+    if (p->rec.obstacle_figures) PLAN_TRY(lscqp_record_set_obstacle_figures(made.get(), p->obs.safety.get()));
     drop_graph(p);  // (a captured chain holds the old record's buffers)
     p->rec.held = std::move(made);
     return LSCQP_OK;
@@ -1088,8 +1092,8 @@ int lscqp_plan_set_record(lscqp_plan p, const lscqp_record_desc* desc) {
     if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_record");
     if (!desc) {
         drop_graph(p);  // (a captured chain ends in the record's node)
-        p->rec = {};  // (its flight log with it)
-        p->pending &= ~(lscplan::kPendRecord | lscplan::kPendFlightLog);
+        p->rec = {};  // (its flight log and its obstacle record with it)
+        p->pending &= ~(lscplan::kPendRecord | lscplan::kPendFlightLog | lscplan::kPendObstacleRecord);
         return LSCQP_OK;
     }
     // (with the partition pending its device offsets are about to change: lscqp_plan_reset makes the record)
@@ -1116,6 +1120,23 @@ int lscqp_plan_set_flight_log(lscqp_plan p, int32_t max_replans) {
     drop_graph(p);  // (a captured chain has, or lacks, the log's node)
     p->rec.log_capacity = max_replans;
     p->pending = max_replans > 0 ? p->pending | lscplan::kPendFlightLog : p->pending & ~lscplan::kPendFlightLog;
+    return LSCQP_OK;
+}
+
+int lscqp_plan_set_obstacle_record(lscqp_plan p, int32_t on) {
+    if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
+    if (on && !p->rec.on)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacle_record: the plan has no record (lscqp_plan_set_record first): the obstacle record is part of it");
+    if (on && p->obs.n_dyn == 0)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacle_record: the plan has no obstacles (lscqp_plan_set_obstacles first)");
+    OnDevice dev(p->device);
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_obstacle_record");
+    // (without a record in hand -- the partition is pending -- lscqp_plan_reset makes one, with the figures)
+    if (p->rec.held) PLAN_TRY(lscqp_record_set_obstacle_figures(p->rec.held.get(), on ? p->obs.safety.get() : nullptr));
+    drop_graph(p);  // (a captured chain has, or lacks, the obstacle record's node)
+    p->rec.obstacle_figures = on != 0;
+    p->pending = on ? p->pending | lscplan::kPendObstacleRecord : p->pending & ~lscplan::kPendObstacleRecord;
     return LSCQP_OK;
 }
 
@@ -1158,6 +1179,12 @@ int lscqp_plan_set_obstacles(lscqp_plan p, const lscqp_obstacle_param* param, in
     }
     // (a flight log has the obstacles' columns and reads their table: a new log for the new ones, before the plan changes)
     if (p->rec.held && p->rec.log_capacity > 0) PLAN_TRY(give_log(p->rec.held.get(), p->rec.log_capacity, next));
+    // (an obstacle record reads the obstacles' safety buffer: the new one, or none -- it goes with the obstacles)
+    if (p->rec.held && p->rec.obstacle_figures) PLAN_TRY(lscqp_record_set_obstacle_figures(p->rec.held.get(), none ? nullptr : next.safety.get()));
+    if (none) {
+        p->rec.obstacle_figures = false;
+        p->pending &= ~lscplan::kPendObstacleRecord;
+    }
     drop_graph(p);  // (a captured chain holds the obstacles' nodes and the slot split)
     p->obs = std::move(next);
     p->pending = none ? p->pending & ~lscplan::kPendObstacles : p->pending | lscplan::kPendObstacles;

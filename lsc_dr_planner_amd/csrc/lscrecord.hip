@@ -7,7 +7,8 @@
 // One workgroup per mission, its threads stride over the mission's agents: sample points, distance, and the partial figures of its agents,
 // then ONE reduction across the workgroup (DPP moves within a wavefront, LDS across the four wavefronts, combined in wavefront order).  Every
 // reduced figure is a sum of integers, a maximum, or a minimum whose ties go to the lowest agent id: the result does not depend on how the
-// agents fall onto lanes.  A record may carry a flight log (include/lscqp.h, "the flight log"): a second kernel, below the record's.
+// agents fall onto lanes.  A record may carry a flight log (include/lscqp.h, "the flight log"): a second kernel, below the record's, and an
+// obstacle record (include/lscqp.h, "the obstacle record"): a third, below the log's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -257,6 +258,89 @@ __global__ __launch_bounds__(kThreads) void flight_log_kernel(Args A, LogArgs L)
     }
 }
 
+// ---- the obstacle record (include/lscqp.h, "the obstacle record"): each mission's least agent-obstacle safety ratio over the flight ----
+//   MultiSyncSimulator::update   reference src/multi_sync_simulator.cpp:527-557 (`if (safety_ratio_obs > current)`), written at :658-709
+// Enqueued IN FRONT of flight_log_kernel and record_kernel on the same stream, for the same reason as the log: it reads the replan counter
+// the record is about to increment and the `finished` word the record is about to set.  One workgroup per mission; a lane owns the
+// entries of the agents it strides over, thread 0 the mission's slot.  No atomics, nothing the other two kernels read or write is written.
+struct ObsArgs {
+    int64_t n_total;
+    const int64_t* off;  // as Args::off
+    const lscqp_mission_record* rec;
+    const lscqp_safety_obs* figures;          // [n_total], the replan's (borrowed)
+    lscqp_mission_obstacle_record* missions;  // [K]
+    lscqp_agent_obstacle_record* agents;      // [n_total]
+};
+
+struct ObsPart {
+    double ratio;                 // least ratio of the replan, +inf: none
+    int agent, obstacle, sample;  // ... the agent attaining it (lowest id on ties), its obstacle and sample; -1
+    int compared, below_one;
+};
+
+// (ids compare as unsigned, as in `combine` above: -1, "none", loses every tie; a NaN is neither smaller nor equal and is never taken)
+__device__ __forceinline__ void combine_obs(ObsPart& a, const ObsPart& b) {
+    if (b.ratio < a.ratio || (b.ratio == a.ratio && (unsigned)b.agent < (unsigned)a.agent)) {
+        a.ratio = b.ratio;
+        a.agent = b.agent;
+        a.obstacle = b.obstacle;
+        a.sample = b.sample;
+    }
+    a.compared += b.compared;
+    a.below_one += b.below_one;
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ void dpp_step_obs(ObsPart& p) {
+    ObsPart q;
+    q.ratio = dpp_f64<CTRL, ROW_MASK>(INFINITY, p.ratio);
+    q.agent = dpp_i32<CTRL, ROW_MASK>(-1, p.agent);
+    q.obstacle = dpp_i32<CTRL, ROW_MASK>(-1, p.obstacle);
+    q.sample = dpp_i32<CTRL, ROW_MASK>(-1, p.sample);
+    q.compared = dpp_i32<CTRL, ROW_MASK>(0, p.compared);
+    q.below_one = dpp_i32<CTRL, ROW_MASK>(0, p.below_one);
+    combine_obs(p, q);
+}
+
+__global__ __launch_bounds__(kThreads) void record_obstacles_kernel(ObsArgs A) {
+    __shared__ ObsPart s_part[kWaves];
+    const int k = blockIdx.x;
+    const lscqp_mission_record* R = A.rec + k;
+    if (R->finished != 0) return;  // frozen, as the record (the whole workgroup: one word, the same for every lane)
+    const int r = R->replans;      // this replan's index: the record's kernel, behind this one, increments it
+    const int64_t lo = A.off ? A.off[k] : 0, hi = A.off ? A.off[k + 1] : A.n_total;
+    ObsPart p = {INFINITY, -1, -1, -1, 0, 0};
+    for (int64_t a = lo + threadIdx.x; a < hi; a += kThreads) {
+        const lscqp_safety_obs* S = A.figures + a;
+        const double v = S->safety_ratio_obs;
+        lscqp_agent_obstacle_record* E = A.agents + a;
+        if (v < E->safety_ratio_obs) {  // strict <: an earlier replan keeps a tie, a NaN is never taken
+            E->safety_ratio_obs = v;
+            E->replan = r, E->obstacle = S->closest_obstacle, E->sample = S->sample;
+        }
+        // (ascending ids within a lane: the strict < of combine_obs keeps the lowest)
+        const ObsPart q = {v, (int)a, S->closest_obstacle, S->sample, fabs(v) < INFINITY ? 1 : 0, v < 1.0 ? 1 : 0};
+        combine_obs(p, q);
+    }
+    dpp_step_obs<0x111, 0xf>(p);  // (the steps of wave_reduce: lane 63 ends up with the wavefront's figures)
+    dpp_step_obs<0x112, 0xf>(p);
+    dpp_step_obs<0x114, 0xf>(p);
+    dpp_step_obs<0x118, 0xf>(p);
+    dpp_step_obs<0x142, 0xa>(p);
+    dpp_step_obs<0x143, 0xc>(p);
+    if ((threadIdx.x & 63) == 63) s_part[threadIdx.x >> 6] = p;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    p = s_part[0];
+    for (int w = 1; w < kWaves; w++) combine_obs(p, s_part[w]);
+    lscqp_mission_obstacle_record* O = A.missions + k;
+    if (p.ratio < O->safety_ratio_obs) {  // strict <: the reference's `if (safety_ratio_obs > current)`, replan after replan
+        O->safety_ratio_obs = p.ratio;
+        O->replan = r, O->agent = p.agent, O->obstacle = p.obstacle, O->sample = p.sample;
+    }
+    O->below_one += p.below_one;
+    O->compared += p.compared;
+}
+
 }  // namespace lscrecord
 
 struct lscqp_record_s {
@@ -271,6 +355,15 @@ struct lscqp_record_s {
         lscqp::dev_ptr<int32_t> flags;
         const lscqp_obstacle* table = nullptr;  // borrowed (lscqp_record_log_obstacles)
     } log;
+    // the obstacle record (lscqp_record_set_obstacle_figures): figures = NULL = none, the record enqueues what it always did.  ONE side
+    // allocation in the layout of include/lscqp.h (lscqp_record_obstacles_raw): spare | missions [K] | spare | agents [n_total] | spare
+    struct Obstacles {
+        const lscqp_safety_obs* figures = nullptr;  // borrowed
+        lscqp::dev_ptr<unsigned char> side;
+    } obs;
+    size_t obs_missions_at() const { return LSCQP_OBSREC_SPARE; }
+    size_t obs_agents_at() const { return 2 * (size_t)LSCQP_OBSREC_SPARE + (size_t)K * sizeof(lscqp_mission_obstacle_record); }
+    size_t obs_bytes() const { return obs_agents_at() + (size_t)a.n_total * sizeof(lscqp_agent_obstacle_record) + LSCQP_OBSREC_SPARE; }
     std::vector<int64_t> off;        // [K + 1]
     lscqp::dev_ptr<int64_t> d_off;   // own copy of the offsets, or empty where the caller's device copy is borrowed
     lscqp::dev_ptr<float> goal, points, last;
@@ -282,6 +375,25 @@ struct lscqp_record_s {
 
 using lscqp::hip_fail;
 using lscqp::OnDevice;
+
+// the obstacle record's cleared state -- +inf, -1, 0 -- copied into `side` (the spare bytes around the two arrays are not written); synchronous
+static hipError_t clear_obstacle_record(const lscqp_record_s* r, unsigned char* side) {
+    std::vector<lscqp_mission_obstacle_record> ms((size_t)r->K);
+    for (lscqp_mission_obstacle_record& m : ms) {
+        m.safety_ratio_obs = INFINITY;
+        m.replan = m.agent = m.obstacle = m.sample = -1;
+        m.below_one = m.compared = 0;
+    }
+    std::vector<lscqp_agent_obstacle_record> as((size_t)r->a.n_total);
+    for (lscqp_agent_obstacle_record& e : as) {
+        e.safety_ratio_obs = INFINITY;
+        e.replan = e.obstacle = e.sample = -1;
+        e.reserved = 0;
+    }
+    hipError_t e = hipMemcpy(side + r->obs_missions_at(), ms.data(), ms.size() * sizeof ms[0], hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(side + r->obs_agents_at(), as.data(), as.size() * sizeof as[0], hipMemcpyHostToDevice);
+    return e;
+}
 
 extern "C" int lscqp_record_create_(lscqp_handle h, int64_t n_total, int32_t n_missions, const int64_t* mission_offsets,
                                     const int64_t* d_offsets_borrowed, int32_t n_samples, double record_time_step, double time_step, double z_2d,
@@ -374,6 +486,7 @@ int lscqp_record_reset(lscqp_record r, const double* goal_points) {
     if (e == hipSuccess) e = hipMemset(r->dist.get(), 0, nt * sizeof(double));
     if (e == hipSuccess) e = hipMemset(r->last.get(), 0, nt * 3 * sizeof(float));
     if (e == hipSuccess) e = hipMemset(r->points.get(), 0, nt * (size_t)r->a.n_samples * 3 * sizeof(float));
+    if (e == hipSuccess && r->obs.side) e = clear_obstacle_record(r, r->obs.side.get());
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "lscqp_record_reset");
 }
 
@@ -386,6 +499,12 @@ int lscqp_record_step_device(lscqp_record r, const lscqp_header* d_hdr, const do
     lscrecord::Args a = r->a;
     a.hdr = d_hdr, a.x_all = d_x_all, a.status = d_status, a.goal_status = d_goal_status, a.sfc_status = d_sfc_status, a.valid = d_valid;
     a.in_range = d_in_range, a.safety = d_safety, a.waypoint_updated = d_waypoint_updated;
+    if (r->obs.figures) {  // in front of the log and the record: the replan's obstacle figures of every mission still flying
+        unsigned char* const side = r->obs.side.get();
+        const lscrecord::ObsArgs o = {a.n_total, a.off, a.rec, r->obs.figures, (lscqp_mission_obstacle_record*)(side + r->obs_missions_at()),
+                                      (lscqp_agent_obstacle_record*)(side + r->obs_agents_at())};
+        hipLaunchKernelGGL(lscrecord::record_obstacles_kernel, dim3((unsigned)r->K), dim3(lscrecord::kThreads), 0, (hipStream_t)stream, o);
+    }
     if (r->log.capacity > 0) {  // in front of the record: row `replans` of every mission still flying
         const lscqp_record_s::Log& g = r->log;
         const lscrecord::LogArgs l = {g.capacity, g.n_dyn, g.states.get(), g.flags.get(), g.obstacles.get(), g.table};
@@ -521,6 +640,46 @@ int lscqp_record_log_download(lscqp_record r, int32_t mission, int32_t first_rep
     if (e == hipSuccess && obstacles && nd > 0)
         e = hipMemcpy(obstacles, g.obstacles.get() + (((size_t)mission * C + f) * nd) * 4, n * nd * 4 * sizeof(float), hipMemcpyDeviceToHost);
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "lscqp_record_log_download");
+}
+
+int lscqp_record_set_obstacle_figures(lscqp_record r, const lscqp_safety_obs* d_safety_obs) {
+    if (!r) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null record");
+    OnDevice on(r->device);
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "lscqp_record_set_obstacle_figures");
+    if (!d_safety_obs) {
+        r->obs = {};
+        return LSCQP_OK;
+    }
+    if (!r->obs.side) {  // first use: the side allocation, cleared (everything that can fail comes before the record changes)
+        lscqp::dev_ptr<unsigned char> side;
+        if (const int rc = lscqp::dev_alloc(side, r->obs_bytes(), "lscqp_record_set_obstacle_figures", true)) return rc;
+        if ((e = clear_obstacle_record(r, side.get())) != hipSuccess) return hip_fail(e, "lscqp_record_set_obstacle_figures");
+        r->obs.side = std::move(side);
+    }
+    r->obs.figures = d_safety_obs;
+    return LSCQP_OK;
+}
+
+int lscqp_record_obstacles_download(lscqp_record r, lscqp_mission_obstacle_record* out, lscqp_agent_obstacle_record* agents) {
+    if (!r || !out) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null argument");
+    if (!r->obs.side)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_record_obstacles_download: the record keeps no obstacle figures (lscqp_record_set_obstacle_figures)");
+    OnDevice on(r->device);
+    const unsigned char* const side = r->obs.side.get();
+    hipError_t e = hipMemcpy(out, side + r->obs_missions_at(), (size_t)r->K * sizeof *out, hipMemcpyDeviceToHost);  // waits for the device
+    if (e == hipSuccess && agents) e = hipMemcpy(agents, side + r->obs_agents_at(), (size_t)r->a.n_total * sizeof *agents, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? LSCQP_OK : hip_fail(e, "lscqp_record_obstacles_download");
+}
+
+void* lscqp_record_obstacles_raw(lscqp_record r, uint64_t* bytes_out) {
+    if (bytes_out) *bytes_out = 0;
+    if (!r || !r->obs.side) {
+        lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, !r ? "null record" : "lscqp_record_obstacles_raw: the record keeps no obstacle figures (lscqp_record_set_obstacle_figures)");
+        return nullptr;
+    }
+    if (bytes_out) *bytes_out = (uint64_t)r->obs_bytes();
+    return r->obs.side.get();
 }
 
 int lscqp_record_unfinished_on_(lscqp_record r, void* stream, int32_t* unfinished_out) {

@@ -130,13 +130,21 @@ struct SimulationSummary {
 
 // The fields of the summary line a mission record holds (include/lscqp.h, "the mission record"): total_flight_time (-1 while the mission
 // has not finished), total_flight_distance, safety_ratio_agent, and the excess ratios as the reference prints them -- the float norm() of
-// the three per-axis maxima (vel_excess_ratio.norm(), :685-686).  Everything else, safety_ratio_obs included, stays the caller's.
+// the three per-axis maxima (vel_excess_ratio.norm(), :685-686).  Everything else, safety_ratio_obs included, stays the caller's -- the
+// three-argument form below takes that one from the record's obstacle record.
 inline void fillSummaryFromRecord(SimulationSummary& s, const lscqp_mission_record& r) {
     s.total_flight_time = r.flight_time;
     s.total_flight_distance = r.distance;
     s.safety_ratio_agent = r.safety_ratio_agent;
     s.vel_excess_ratio = point3d((float)r.vel_excess_ratio[0], (float)r.vel_excess_ratio[1], (float)r.vel_excess_ratio[2]).norm();
     s.acc_excess_ratio = point3d((float)r.acc_excess_ratio[0], (float)r.acc_excess_ratio[1], (float)r.acc_excess_ratio[2]).norm();
+}
+
+// ... and safety_ratio_obs from the mission's obstacle record (include/lscqp.h, "the obstacle record"): the least agent-obstacle safety
+// ratio of the flight, +inf where nothing was compared (SP_INFINITY in the reference, :527-557)
+inline void fillSummaryFromRecord(SimulationSummary& s, const lscqp_mission_record& r, const lscqp_mission_obstacle_record& o) {
+    fillSummaryFromRecord(s, r);
+    s.safety_ratio_obs = o.safety_ratio_obs;
 }
 
 class SimulationSummaryCsv {

@@ -197,7 +197,9 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     """`missions` seeded missions over one world flown by ONE lscqp_plan with a mission partition (include/lscqp.h, "many missions over one
     map"): waypoint_mode 1, closed loop, one captured graph per replan.  The summary has the figures of `run` per mission.
     until_finished = MAX: the plan keeps a mission record (include/lscqp.h, "the mission record") and lscqp_plan_run flies it until every
-    mission has finished or MAX replans, with no download in between; per mission the summary then holds the device's record.
+    mission has finished or MAX replans, with no download in between; per mission the summary then holds the device's record -- and with
+    obstacles the mission's obstacle record (include/lscqp.h, "the obstacle record"): obstacle_safety_ratio, the least agent-obstacle safety
+    ratio of the flight, with its replan, agent and obstacle, and below_one, the agent-replans whose figure was below 1.
     obstacles: api.OBSTACLE_MODEL_DTYPE records (load_obstacles) -- the dynamic obstacles every mission shares, moved by the chain itself
     (lscqp_plan_set_obstacles).  obstacle_rows "lsc": their rows are generateLSC's, so the agents' rows are LSC rows too (GEN_LSC instead
     of GEN_CLSC); "clsc": the plan stays in GEN_CLSC, the mode the reference's launch files run, and the obstacles get generateCLSC's rows
@@ -259,6 +261,8 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
         plan.set_record(goal_threshold)
         if log_csv:
             plan.set_flight_log(int(until_finished))
+        if n_dyn:  # each mission's least obstacle safety ratio over the flight, kept beside its record (include/lscqp.h, "the obstacle record")
+            plan.set_obstacle_record()
         plan.reset(starts, goals)
         enqueued = plan.run(int(until_finished), check_every=check_every, graph=graph)
         rec, _ = plan.record().download()
@@ -277,6 +281,10 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
                     max_vel_excess=float(np.linalg.norm(np.float32(r["vel_excess_ratio"]))), max_acc_excess=float(np.linalg.norm(np.float32(r["acc_excess_ratio"]))),
                     waypoints_updated=int(r["waypoint_updates"]), max_in_range=int(r["max_in_range"]), truncated_agent_steps=int(r["truncated"]),
                     walk_bound_reached=int(status[k])) for k, r in enumerate(rec)]
+        if n_dyn:
+            for m, o in zip(per, plan.record().obstacles()[0]):
+                m.update(obstacle_safety_ratio=float(o["safety_ratio_obs"]), obstacle_safety_replan=int(o["replan"]), obstacle_safety_agent=int(o["agent"]),
+                         obstacle_safety_obstacle=int(o["obstacle"]), below_one=int(o["below_one"]))
         if patrol is not None:
             legs = plan.patrol(api.PATROL_LEGS)
             for k, m in enumerate(per):
@@ -287,8 +295,8 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
                    min_safety_ratio=min(m["min_safety_ratio"] for m in per), per_mission=per)
         if patrol is not None:
             log.update(patrol_goal_threshold=float(patrol), legs=sum(sum(m["legs"]) for m in per))
-        if n_dyn:  # (the record keeps no obstacle figure: the last replan's is what the plan still holds)
-            log.update(obstacles=n_dyn, driven_obstacles=n_driven,
+        if n_dyn:  # (the flight's least figure per mission is in per_mission; the last replan's is what the plan still holds)
+            log.update(obstacles=n_dyn, driven_obstacles=n_driven, min_obstacle_safety_ratio=min(m["obstacle_safety_ratio"] for m in per),
                        last_obstacle_safety_ratio=float(plan.get_obstacles(api.PLAN_OBS_SAFETY)["safety_ratio_obs"].min()))
         if world_set:
             log["worlds"] = len(world_set)
