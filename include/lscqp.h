@@ -1066,7 +1066,8 @@ int lscqp_grid_mission_status(lscqp_grid grid, int32_t n_missions, int32_t* stat
  *                            that map drops its captured graph (and re-makes its grid) at its next step, also when this call is refused
  *                            behind it --, and the generation check in front of every step covers every member.  The set must outlive
  *                            the plan or be taken away first.  NULL: back to the one map -- such a plan, and one that never saw the call,
- *                            enqueues the chain it always did node for node.  Dynamic obstacles are shared by all missions; the record and
+ *                            enqueues the chain it always did node for node.  Dynamic obstacles given by lscqp_plan_set_obstacles are
+ *                            shared by all missions, those of lscqp_plan_set_mission_obstacles are each mission's own; the record and
  *                            lscqp_plan_run do not know.  Out of scope: worlds of different shape; sharded plans; 3-D grids. */
 typedef struct lscqp_worlds_s* lscqp_worlds;
 int lscqp_worlds_create(const lscqp_map* maps, int32_t n_worlds, lscqp_worlds* out);
@@ -1317,8 +1318,8 @@ int lscqp_plan_set_obstacle_record(lscqp_plan plan, int32_t on);
  *                            in that mode without obstacle goal points, i.e. the origin, as in the reference -- the goal LP reads the
  *                            last-segment rows of every slot, the obstacles' too), and with safety_samples > 0
  *                            lscqp_safety_obstacles_device behind the agent safety figures.  A mission
- *                            partition shares the obstacles like the map; every owner of a sharded mission advances its own copy of the
- *                            same table.  The waypoint decision does not see obstacles, as in the reference.  The mission record keeps
+ *                            partition shares THIS table like the map (a table per mission: lscqp_plan_set_mission_obstacles, "a mission's
+ *                            own obstacles" below); every owner of a sharded mission advances its own copy of the same table.  The waypoint decision does not see obstacles, as in the reference.  The mission record keeps
  *                            no obstacle figure itself; the obstacle record beside it does (lscqp_plan_set_obstacle_record).
  * lscqp_plan_obstacle_buffer / _upload / _download   the buffers that exist only with obstacles (NULL and 0 bytes otherwise), addressed
  *                            by LSCQP_PLAN_OBS_*; copies are synchronous like lscqp_plan_upload / _download. */
@@ -1348,9 +1349,10 @@ typedef struct lscqp_obstacle_model { /* 912 bytes */
 int lscqp_obstacle_model_prepare(lscqp_obstacle_model* models, int32_t n);
 int lscqp_obstacles_advance_device(lscqp_handle h, const lscqp_obstacle_model* d_models, int32_t n_dyn, double time_step, int32_t* d_clock,
                                    lscqp_obstacle* d_obstacles, void* stream);
-#define LSCQP_PLAN_OBS_TABLE 0  /* i/o  lscqp_obstacle[n_dyn]: the table as the last replan's advance left it (HELD entries: the caller's) */
+#define LSCQP_PLAN_OBS_TABLE 0  /* i/o  lscqp_obstacle[n_dyn]: the table as the last replan's advance left it (HELD entries: the caller's); a
+                                        table per mission: [n_dyn_total], mission-major */
 #define LSCQP_PLAN_OBS_SAFETY 1 /* out  lscqp_safety_obs[n_agents] of the last replan (safety_samples > 0) */
-#define LSCQP_PLAN_OBS_CLOCK 2  /* i/o  int32: the replan index the NEXT advance evaluates */
+#define LSCQP_PLAN_OBS_CLOCK 2  /* i/o  int32: the replan index the NEXT advance evaluates; a table per mission: int32[n_missions] */
 #define LSCQP_PLAN_OBS_COUNT 3
 int lscqp_plan_set_obstacles(lscqp_plan plan, const lscqp_obstacle_param* param, int32_t n_dyn, const lscqp_obstacle_model* models);
 void* lscqp_plan_obstacle_buffer(lscqp_plan plan, int32_t which, uint64_t* bytes_out);
@@ -1404,7 +1406,10 @@ int lscqp_plan_obstacle_download(lscqp_plan plan, int32_t which, void* host, uin
  *                            leaves the plan as it was; the reset puts driven entries at `start` with zero velocity and zeroes the
  *                            checkpoints.  Per replan the chain gains exactly one node, in front of the advance; a plan without drives
  *                            enqueues the chain it always did node for node.  target_agent is a global agent index: a mission partition
- *                            shares driven obstacles like any other, and every owner of a sharded mission drives its own copy. */
+ *                            shares driven obstacles like any other, and every owner of a sharded mission drives its own copy.  With a
+ *                            table per mission (below) n_dyn is the tables' total, the node is lscqp_obstacles_drive_missions_device, and
+ *                            a chaser whose target_agent (>= 0) is not an agent of the mission that owns the chaser is refused, at the call
+ *                            and again at the reset (the partition's offsets may have moved). */
 #define LSCQP_DRIVE_NONE 0
 #define LSCQP_DRIVE_CHASING 1
 #define LSCQP_DRIVE_GAUSSIAN 2
@@ -1436,6 +1441,62 @@ int lscqp_obstacle_drive_host(lscqp_handle h, const lscqp_obstacle_model* models
                               void* stream);
 int lscqp_plan_set_obstacle_drives(lscqp_plan plan, const lscqp_obstacle_drive* drives, int32_t n_dyn, const double* acc_history,
                                    int32_t n_history);
+
+/* ---- a mission's own obstacles: one obstacle table per mission of a partition -------------------------------------------------------------
+ *
+ * The reference flies one mission file at a time and every file lists its own obstacles.  A partition of K missions (lscqp_plan_set_missions)
+ * that shares one table would hand every agent the obstacles of every mission, let a chaser of one mission fly through all of them, and
+ * spend a row slot of every agent on every obstacle of every mission.  Here the table is MISSION-MAJOR: mission k owns the entries
+ * [obstacle_offsets[k], obstacle_offsets[k + 1]) of the models, the drives, the checkpoints and the table, and one clock word, clock[k].
+ * obstacle_offsets has n_missions + 1 int32 values, non-decreasing from 0 to n_dyn_total; a mission may own no obstacle.  The device entries
+ * take the list twice, like the *_missions_device entries take the partition: on the host, checked before the device is touched
+ * (LSCQP_ERR_INVALID_ARGUMENT: not from 0, decreasing, last != n_dyn_total; LSCQP_ERR_UNSUPPORTED: one mission's count above
+ * lscqp_max_obstacles(h) -- the TOTAL is not bounded by it), and on the device, where the kernels read it.  n_missions = 0 is the empty batch.
+ * lscqp_obstacles_advance_missions_device   lscqp_obstacles_advance_device with one workgroup per mission over its slice, by the same
+ *                            functions: workgroup k reads clock[k] in front of its barrier and stores clock[k] + 1 behind it (one word could
+ *                            not be read by K workgroups and counted by one of them without a race).  A mission without obstacles still
+ *                            counts its clock; with n_dyn_total = 0 the models and the table may be NULL.
+ * lscqp_obstacles_drive_missions_device     lscqp_obstacles_drive_device with one workgroup per mission, IN FRONT of the advance: it stages its
+ *                            own slice only (dynamic LDS: the largest mission's count of 32-byte records), so a chaser is repelled by the
+ *                            obstacles of its own mission and no other; target_agent stays a global index into d_state, the history table
+ *                            is one for all missions.  Reads clock[k], does not write it.
+ * lscqp_safety_obstacles_ids_device         lscqp_safety_obstacles_device in which local agent a is judged against the entries named by row a
+ *                            of d_obstacle_ids [n_agents][n_slots]: table indices, those outside [0, n_obstacles) -- -1 by convention --
+ *                            skipped, type REAL skipped as ever.  Samples, then slots, strict <: the first (sample, slot) attaining the
+ *                            minimum; closest_obstacle is the SLOT, which is the index a plan of that mission alone reports.  Nothing
+ *                            compared: +inf, -1, -1.  The arithmetic is the other entry's, bit for bit.
+ * lscqp_plan_set_mission_obstacles   gives mission k of the partition IN FORCE its own obstacles: models [obstacle_offsets[n_missions]] in
+ *                            mission order (host, prepared by the call; the caller's array is not written).  The lifecycle is
+ *                            lscqp_plan_set_obstacles': it waits for the device and drops a captured graph, lscqp_plan_reset must follow (a
+ *                            step before it is refused), the reset puts every entry at t = 0 and zeroes all K clocks, a refused call leaves
+ *                            the plan as it was.  It and lscqp_plan_set_obstacles replace each other; n_missions = 0, models = NULL or
+ *                            missions none of which owns an obstacle take the obstacles away.  Row slots: n_slot = the largest mission's
+ *                            count, n_slot <= desc.n_obs required; slot o < n_slot of an agent of mission k holds entry obstacle_offsets[k]
+ *                            + o for o < count_k and nothing (all-zero rows, which bind nothing) beyond; slots [n_slot, n_obs) hold the
+ *                            in-range agents.  Refused: n_missions other than the partition's (LSCQP_ERR_INVALID_ARGUMENT; a later
+ *                            lscqp_plan_set_missions with another count is refused while these obstacles are set, as with worlds; the reset
+ *                            makes each agent's list again from the offsets then in force); a sharded plan (n_agents != n_total);
+ *                            constraint_mode LSCQP_GEN_BVC (LSCQP_ERR_UNSUPPORTED); together with a flight log, in either order
+ *                            (LSCQP_ERR_UNSUPPORTED: the log's obstacle columns are those of one shared table).  Per replan the chain has
+ *                            exactly the nodes of a plan with a shared table, the three entries above in place of their shared forms and
+ *                            the row entries called with n_slot and the agents' own lists.  lscqp_plan_set_obstacle_drives,
+ *                            lscqp_plan_set_obstacle_record (its `obstacle` is then the slot), lscqp_plan_run, worlds and a patrol compose
+ *                            unchanged.  LSCQP_PLAN_OBS_TABLE is [n_dyn_total], LSCQP_PLAN_OBS_CLOCK int32[n_missions].  A plan that never
+ *                            makes this call enqueues the chain it always did node for node. */
+int lscqp_obstacles_advance_missions_device(lscqp_handle h, const lscqp_obstacle_model* d_models, int32_t n_missions,
+                                            const int32_t* obstacle_offsets, const int32_t* d_obstacle_offsets, int32_t n_dyn_total,
+                                            double time_step, int32_t* d_clock, lscqp_obstacle* d_obstacles, void* stream);
+int lscqp_obstacles_drive_missions_device(lscqp_handle h, const lscqp_obstacle_model* d_models, const lscqp_obstacle_drive* d_drives,
+                                          int32_t n_missions, const int32_t* obstacle_offsets, const int32_t* d_obstacle_offsets,
+                                          int32_t n_dyn_total, const double* d_acc_history, int32_t n_history, const double* d_state,
+                                          int64_t n_total, lscqp_obstacle_drive_state* d_drive_state, double time_step,
+                                          const int32_t* d_clock, lscqp_obstacle* d_obstacles, void* stream);
+int lscqp_safety_obstacles_ids_device(lscqp_handle h, int64_t n_agents, int64_t first_agent, int64_t n_total, int32_t n_samples,
+                                      double record_time_step, double z_2d, const double* d_x_all, const double* d_radius,
+                                      const double* d_downwash, int32_t n_slots, const int32_t* d_obstacle_ids, int32_t n_obstacles,
+                                      const lscqp_obstacle* d_obstacles, lscqp_safety_obs* d_out, void* stream);
+int lscqp_plan_set_mission_obstacles(lscqp_plan plan, const lscqp_obstacle_param* param, int32_t n_missions, const int32_t* obstacle_offsets,
+                                     const lscqp_obstacle_model* models);
 
 /* ---- patrol missions: start and goal swapped on arrival, on the device ------------------------------------------------------------------
  *

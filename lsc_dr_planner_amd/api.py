@@ -248,6 +248,8 @@ EXPORTED_SYMBOLS = ["lscqp_create", "lscqp_update", "lscqp_destroy", "lscqp_num_
                     "lscqp_obstacle_model_prepare", "lscqp_obstacles_advance_device", "lscqp_plan_set_obstacles", "lscqp_plan_obstacle_buffer",
                     "lscqp_plan_obstacle_upload", "lscqp_plan_obstacle_download",
                     "lscqp_obstacle_drive_check", "lscqp_obstacles_drive_device", "lscqp_obstacle_drive_host", "lscqp_plan_set_obstacle_drives",
+                    "lscqp_obstacles_advance_missions_device", "lscqp_obstacles_drive_missions_device", "lscqp_safety_obstacles_ids_device",
+                    "lscqp_plan_set_mission_obstacles",
                     "lscqp_patrol_check", "lscqp_patrol_device", "lscqp_patrol_host", "lscqp_field_exchange_device", "lscqp_plan_set_patrol",
                     "lscqp_plan_patrol_buffer",
                     "lscqp_worlds_create", "lscqp_worlds_destroy", "lscqp_worlds_prepare", "lscqp_worlds_info", "lscqp_construct_sfc_worlds_device",
@@ -952,6 +954,25 @@ class Plan:
         _call("lscqp_plan_set_obstacles", self._p, C.byref(param), len(m), m)
         self.n_dyn = len(m)
 
+    def set_mission_obstacles(self, models_per_mission, param=None):
+        """lscqp_plan_set_mission_obstacles: one OBSTACLE_MODEL_DTYPE array per mission of the partition in force (an empty one or None for a
+        mission without obstacles), each mission's own -- its agents see no other's.  None, or no obstacle in any mission, takes the obstacles
+        away; param as in set_obstacles.  `reset` must follow.  The table, the drives and PLAN_OBS_TABLE are mission-major; PLAN_OBS_CLOCK has
+        one word per mission."""
+        per = [] if models_per_mission is None else [np.zeros(0, OBSTACLE_MODEL_DTYPE) if m is None else np.ascontiguousarray(m, dtype=OBSTACLE_MODEL_DTYPE).reshape(-1)
+                                                     for m in models_per_mission]
+        off = np.zeros(len(per) + 1, np.int32)
+        off[1:] = np.cumsum([len(m) for m in per])
+        if off[-1] == 0:
+            _call("lscqp_plan_set_mission_obstacles", self._p, None, 0, None, None)
+            self.n_dyn = 0
+            return
+        m = np.ascontiguousarray(np.concatenate(per))
+        if param is None:
+            param = ObstacleParam(1.0, 0.75, 3.0, 0.1, 1, 1)
+        _call("lscqp_plan_set_mission_obstacles", self._p, C.byref(param), len(per), off, m)
+        self.n_dyn = len(m)
+
     def set_obstacle_drives(self, drives, acc_history=None):
         """lscqp_plan_set_obstacle_drives: an OBSTACLE_DRIVE_DTYPE record per obstacle of the plan and the shared [n_history][3] table of
         accelerations (obstacle_drives builds both), or None / empty to take the drives away.  `reset` must follow."""
@@ -1444,6 +1465,13 @@ class Solver:
         _call("lscqp_safety_obstacles_device", self._h, n_agents, first_agent, n_total, int(n_samples), float(record_time_step), float(z_2d), d_x_all,
               d_radius, d_downwash, int(n_obstacles), d_obstacles, d_out, stream=stream)
 
+    def safety_obstacles_ids_device(self, n_agents, first_agent, n_total, n_samples, record_time_step, d_x_all, d_radius, d_downwash, n_slots,
+                                    d_obstacle_ids, n_obstacles, d_obstacles, d_out, z_2d=1.0, stream=None):
+        """lscqp_safety_obstacles_ids_device: safety_obstacles_device with each local agent's own obstacles, row a of d_obstacle_ids
+        (int32 (n_agents, n_slots): table indices, < 0 = none); closest_obstacle is the slot."""
+        _call("lscqp_safety_obstacles_ids_device", self._h, n_agents, first_agent, n_total, int(n_samples), float(record_time_step), float(z_2d), d_x_all,
+              d_radius, d_downwash, int(n_slots), d_obstacle_ids, int(n_obstacles), d_obstacles, d_out, stream=stream)
+
     def construct_sfc_device(self, world_map, mode, n, d_points, d_radius, d_sfc, d_status, stream=None, d_order=None, d_cost=None):
         """Corridor update of n agents on the device (SFC_INIT / SFC_FROM_HULL / SFC_FROM_POINT, see include/lscqp.h).  d_order: int32
         permutation (workgroup k builds agent d_order[k]'s corridor); d_cost: uint32[n], every agent's cost of this launch."""
@@ -1527,6 +1555,21 @@ class Solver:
     def obstacles_advance_device(self, d_models, n_dyn, time_step, d_clock, d_obstacles, stream=None):
         """lscqp_obstacles_advance_device: the table moved to the clock's replan, the clock advanced; d_models PREPARED models on the device."""
         _call("lscqp_obstacles_advance_device", self._h, d_models, int(n_dyn), float(time_step), d_clock, d_obstacles, stream=stream)
+
+    def obstacles_advance_missions_device(self, d_models, obstacle_offsets, d_obstacle_offsets, time_step, d_clock, d_obstacles, stream=None):
+        """lscqp_obstacles_advance_missions_device: obstacles_advance_device over a mission-major table, one workgroup and one word of
+        d_clock (int32 (K,)) per mission.  obstacle_offsets: int32 (K + 1,) on the host, d_obstacle_offsets the same on the device."""
+        off = np.ascontiguousarray(obstacle_offsets, dtype=np.int32)
+        _call("lscqp_obstacles_advance_missions_device", self._h, d_models, len(off) - 1, off, d_obstacle_offsets, int(off[-1]), float(time_step), d_clock,
+              d_obstacles, stream=stream)
+
+    def obstacles_drive_missions_device(self, d_models, d_drives, obstacle_offsets, d_obstacle_offsets, d_acc_history, n_history, d_state, n_total,
+                                        d_drive_state, time_step, d_clock, d_obstacles, stream=None):
+        """lscqp_obstacles_drive_missions_device: obstacles_drive_device over a mission-major table, one workgroup per mission over its own
+        slice, IN FRONT of obstacles_advance_missions_device (d_clock int32 (K,) is read, not advanced)."""
+        off = np.ascontiguousarray(obstacle_offsets, dtype=np.int32)
+        _call("lscqp_obstacles_drive_missions_device", self._h, d_models, d_drives, len(off) - 1, off, d_obstacle_offsets, int(off[-1]), d_acc_history,
+              int(n_history), d_state, int(n_total), d_drive_state, float(time_step), d_clock, d_obstacles, stream=stream)
 
     def obstacles_drive_device(self, d_models, d_drives, n_dyn, d_acc_history, n_history, d_state, n_total, d_drive_state, time_step, d_clock,
                                d_obstacles, stream=None):

@@ -294,6 +294,76 @@ __global__ __launch_bounds__(kThreads) void obstacle_drive_kernel(const lscqp_ob
 
 constexpr size_t kDriveLdsMax = 64 * 1024;  // (2048 entries: far beyond lscqp_max_obstacles of any class)
 
+// ---- a table per mission (include/lscqp.h, "a mission's own obstacles"): the table is mission-major, mission k owns entries
+// [ooff[k], ooff[k + 1]) and the clock word clock[k].  One workgroup per mission does over its slice what the kernels above do over the
+// whole table, by the same functions; no workgroup reads or writes a word of another mission.
+
+// obstacle_advance_kernel over the slice of mission blockIdx.x.  A mission without obstacles still counts its clock.
+__global__ __launch_bounds__(kThreads) void obstacle_advance_missions_kernel(const lscqp_obstacle_model* __restrict__ models, const int32_t* __restrict__ ooff,
+                                                                              int64_t step_ns, int32_t* clock, lscqp_obstacle* __restrict__ table) {
+#pragma clang fp contract(off)
+    const int k = blockIdx.x;
+    const int32_t r = clock[k];
+    const int base = ooff[k], n_dyn = ooff[k + 1] - base;
+    const int64_t ns = (int64_t)r * step_ns;
+    const double t = (double)(ns / 1000000000LL) + 1e-9 * (double)(ns % 1000000000LL);
+    for (int oi = threadIdx.x; oi < n_dyn; oi += kThreads) {
+        const lscqp_obstacle_model& m = models[base + oi];
+        if (m.kind == LSCQP_OBSTACLE_HELD) continue;
+        F3 p, v;
+        if (m.kind == LSCQP_OBSTACLE_STRAIGHT) straight_at(m.leg[0], m.speed, m.max_acc, t, &p, &v);
+        else if (m.kind == LSCQP_OBSTACLE_PATROL) patrol_at(m, t, &p, &v);
+        else spin_at(m, t, &p, &v);
+        lscqp_obstacle* o = table + base + oi;
+        o->position[0] = (double)p.x, o->position[1] = (double)p.y, o->position[2] = (double)p.z;
+        o->velocity[0] = (double)v.x, o->velocity[1] = (double)v.y, o->velocity[2] = (double)v.z;
+        o->radius = m.radius, o->downwash = m.downwash, o->max_acc = m.max_acc;
+        o->type = 0;  // DYNAMICOBSTACLE (ObstacleBase::getObstacle)
+        o->reserved = 0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) clock[k] = r + 1;
+}
+
+// obstacle_drive_kernel over the slice of mission blockIdx.x: its own entries go to LDS (the largest mission's count of Staged records),
+// and drive_entry gets the slice's base pointers, count and local index -- a chaser sees the obstacles of its own mission and no other.
+// target_agent stays a global id into `state`; the history table is one for all missions.  clock[k] is read, never written.
+__global__ __launch_bounds__(kThreads) void obstacle_drive_missions_kernel(const lscqp_obstacle_model* __restrict__ models,
+                                                                            const lscqp_obstacle_drive* __restrict__ drives, const int32_t* __restrict__ ooff,
+                                                                            const double* __restrict__ hist, int n_history, const double* __restrict__ state,
+                                                                            int64_t n_total, lscqp_obstacle_drive_state* __restrict__ ckpt, int64_t step_ns,
+                                                                            const int32_t* __restrict__ clock, lscqp_obstacle* table) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) char drive_missions_lds[];
+    Staged* prev = (Staged*)drive_missions_lds;
+    const int k = blockIdx.x;
+    const int base = ooff[k], n_dyn = ooff[k + 1] - base;
+    const int32_t r = clock[k];
+    const double t = clock_seconds(r, step_ns), t_last = r > 0 ? clock_seconds(r - 1, step_ns) : 0.0;
+    lscqp_obstacle* mine = table + base;
+    for (int oi = threadIdx.x; oi < n_dyn; oi += kThreads)
+        prev[oi] = Staged{mine[oi].position[0], mine[oi].position[1], mine[oi].position[2], mine[oi].radius};
+    __syncthreads();
+    for (int oi = threadIdx.x; oi < n_dyn; oi += kThreads)
+        drive_entry(models + base, drives + base, n_dyn, hist, n_history, state, n_total, ckpt + base, t, t_last, prev, oi, mine);
+}
+
+// the offset list of a table per mission, as the host gives it: K + 1 values, non-decreasing from 0 to n_dyn_total, no mission with more
+// than lscqp_max_obstacles(h) entries.  *largest: the largest mission's count
+inline int check_obstacle_offsets(lscqp_handle h, int32_t n_missions, const int32_t* ooff, int32_t n_dyn_total, int32_t* largest) {
+    *largest = 0;
+    if (n_missions < 1 || !ooff) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "a table per mission needs n_missions >= 1 and its obstacle_offsets");
+    if (ooff[0] != 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "obstacle_offsets[0] must be 0");
+    for (int32_t k = 0; k < n_missions; k++) {
+        if (ooff[k + 1] < ooff[k]) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "obstacle_offsets must not decrease");
+        if (ooff[k + 1] - ooff[k] > *largest) *largest = ooff[k + 1] - ooff[k];
+    }
+    if (ooff[n_missions] != n_dyn_total) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "obstacle_offsets[n_missions] must be n_dyn_total");
+    if (*largest > lscqp_max_obstacles(h) || (size_t)*largest * sizeof(Staged) > kDriveLdsMax)
+        return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "a mission's obstacle count exceeds the largest compiled kernel instance of the shape (lscqp_max_obstacles)");
+    return LSCQP_OK;
+}
+
 inline int refuse_drive(int i, const char* what) {
     char msg[240];
     snprintf(msg, sizeof msg, "lscqp_obstacle_drive_check: model %d: %s", i, what);
@@ -488,4 +558,45 @@ extern "C" int lscqp_obstacle_drive_host(lscqp_handle h, const lscqp_obstacle_mo
     for (int oi = 0; oi < n_dyn; oi++) prev[(size_t)oi] = Staged{obstacles[oi].position[0], obstacles[oi].position[1], obstacles[oi].position[2], obstacles[oi].radius};
     for (int oi = 0; oi < n_dyn; oi++) drive_entry(models, drives, n_dyn, acc_history, n_history, state, n_total, drive_state, t, t_last, prev.data(), oi, obstacles);
     return LSCQP_OK;
+}
+
+extern "C" int lscqp_obstacles_advance_missions_device(lscqp_handle h, const lscqp_obstacle_model* d_models, int32_t n_missions,
+                                                       const int32_t* obstacle_offsets, const int32_t* d_obstacle_offsets, int32_t n_dyn_total,
+                                                       double time_step, int32_t* d_clock, lscqp_obstacle* d_obstacles, void* stream) {
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_missions < 0 || n_dyn_total < 0 || !(time_step > 0) || !(time_step < 1e6))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "inconsistent sizes (n_missions >= 0, n_dyn_total >= 0 and a positive, finite time_step required)");
+    if (n_missions == 0) return LSCQP_OK;
+    int32_t largest = 0;
+    if (const int rc = lscobstacle::check_obstacle_offsets(h, n_missions, obstacle_offsets, n_dyn_total, &largest)) return rc;
+    // (a partition none of whose missions has an obstacle still counts its clocks: no table is asked for)
+    if (!d_obstacle_offsets || !d_clock || (n_dyn_total > 0 && (!d_models || !d_obstacles))) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
+    const int64_t step_ns = (int64_t)llround(time_step * 1e9);  // ros::Duration(time_step): whole nanoseconds
+    hipLaunchKernelGGL(lscobstacle::obstacle_advance_missions_kernel, dim3((unsigned)n_missions), dim3(lscobstacle::kThreads), 0, (hipStream_t)stream, d_models,
+                       d_obstacle_offsets, step_ns, d_clock, d_obstacles);
+    return lscqp_launch_result_(hipGetLastError());
+}
+
+extern "C" int lscqp_obstacles_drive_missions_device(lscqp_handle h, const lscqp_obstacle_model* d_models, const lscqp_obstacle_drive* d_drives,
+                                                     int32_t n_missions, const int32_t* obstacle_offsets, const int32_t* d_obstacle_offsets,
+                                                     int32_t n_dyn_total, const double* d_acc_history, int32_t n_history, const double* d_state,
+                                                     int64_t n_total, lscqp_obstacle_drive_state* d_drive_state, double time_step,
+                                                     const int32_t* d_clock, lscqp_obstacle* d_obstacles, void* stream) {
+    if (!h) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_missions < 0 || n_dyn_total < 0 || n_history < 0 || n_total < 0 || !(time_step > 0) || !(time_step < 1e6))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
+                                "inconsistent sizes (n_missions >= 0, n_dyn_total >= 0, n_history >= 0, n_total >= 0 and a positive, finite time_step required)");
+    if (n_missions == 0) return LSCQP_OK;
+    int32_t largest = 0;
+    if (const int rc = lscobstacle::check_obstacle_offsets(h, n_missions, obstacle_offsets, n_dyn_total, &largest)) return rc;
+    if (n_dyn_total == 0) return LSCQP_OK;  // (nothing to move, and the clocks are the advance's to count)
+    if (!d_obstacle_offsets || !d_models || !d_drives || !d_drive_state || !d_clock || !d_obstacles || (n_history > 0 && !d_acc_history) || (n_total > 0 && !d_state))
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (const int rc = lscqp_need_device_()) return rc;
+    const int64_t step_ns = (int64_t)llround(time_step * 1e9);  // ros::Duration(time_step): whole nanoseconds
+    hipLaunchKernelGGL(lscobstacle::obstacle_drive_missions_kernel, dim3((unsigned)n_missions), dim3(lscobstacle::kThreads),
+                       (size_t)largest * sizeof(lscobstacle::Staged), (hipStream_t)stream, d_models, d_drives, d_obstacle_offsets, d_acc_history, (int)n_history,
+                       d_state, n_total, d_drive_state, step_ns, d_clock, d_obstacles);
+    return lscqp_launch_result_(hipGetLastError());
 }

@@ -28,6 +28,9 @@
 // rows (the non-agent branch of generateLSC or of generateCLSC, by the plan's constraint_mode; a BVC plan takes no obstacles) behind the agents'
 // rows -- they take the first row slots of every agent -- and the obstacle leg of the safety figures behind the agents'.
 // ObstacleGenerator::update(t, 0) -> obstacle_advance_kernel, src/multi_sync_simulator.cpp:311.
+// A partition whose missions have obstacles of their own (lscqp_plan_set_mission_obstacles: one mission-major table, a clock per mission) has
+// the same nodes in the same places, the motion and the safety leg in their per-mission forms (obstacle_advance_missions_kernel,
+// obstacle_drive_missions_kernel, safety_obstacles_ids_kernel) and the row entries called with every agent's own list of table indices.
 // A plan that flies a patrol (lscqp_plan_set_patrol) gains the transition node directly behind the waypoint decision -- the reference decides the
 // waypoints over the old goals, then every agent swaps start and goal on arrival at the top of its plan() -- and, with a grid, the node that
 // exchanges the turned agents' distance fields behind it (lscpatrol.hip).
@@ -213,11 +216,12 @@ enum : unsigned {
     kPendFlightLog = 1u << 4,
     kPendDrives = 1u << 5,
     kPendPatrol = 1u << 6,
-    kPendObstacleRecord = 1u << 7
+    kPendObstacleRecord = 1u << 7,
+    kPendMissionObstacles = 1u << 8
 };
 constexpr const char* kPendSetter[] = {"lscqp_plan_set_missions", "lscqp_plan_set_record", "lscqp_plan_set_obstacles", "lscqp_plan_set_worlds",
                                        "lscqp_plan_set_flight_log", "lscqp_plan_set_obstacle_drives", "lscqp_plan_set_patrol",
-                                       "lscqp_plan_set_obstacle_record"};
+                                       "lscqp_plan_set_obstacle_record", "lscqp_plan_set_mission_obstacles"};
 
 }  // namespace lscplan
 
@@ -289,12 +293,21 @@ struct lscqp_plan_s {
         dev_ptr<lscqp_obstacle> table;
         dev_ptr<int32_t> ids, clock;  // ids: 0 .. n_dyn - 1 for every local agent
         dev_ptr<lscqp_safety_obs> safety;
+        // a table per mission (lscqp_plan_set_mission_obstacles): ooff empty = one shared table, the chain as it always was.  Else the table
+        // is mission-major, n_dyn its total, n_slot = the largest mission's count the row slots [0, n_slot) of every agent, ids [n_agents][n_slot]
+        // table indices (-1: none) and clock one word per mission
+        int32_t n_slot = 0;  // row slots the obstacles take: n_dyn of a shared table
+        std::vector<int32_t> ooff;  // [K + 1]
+        dev_ptr<int32_t> d_ooff;
+        bool per_mission() const { return !ooff.empty(); }
+        int n_clocks() const { return ooff.empty() ? 1 : (int)ooff.size() - 1; }
         // the drives of chasing and gaussian obstacles (lscqp_plan_set_obstacle_drives): d_drives = NULL = none, the chain as it always was
         struct Drives {
             dev_ptr<lscqp_obstacle_drive> d_drives;
             dev_ptr<double> history;  // [n_history][3]
             int32_t n_history = 0;
             dev_ptr<lscqp_obstacle_drive_state> state;  // a checkpoint per obstacle
+            std::vector<lscqp_obstacle_drive> host;      // (a table per mission only) the drives as they were given
         } drv;
     } obs;
     // a world per mission (lscqp_plan_set_worlds): set = NULL = the one map, the chain as it always was
@@ -374,7 +387,9 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     const lscqp_plan_s::Obstacles& obs = p->obs;
     lscqp_grid grid = wp.grid.get();
     const int64_t *moff = p->mis.moff.data(), *d_moff = p->mis.d_moff.get();
-    const int32_t n_dyn = obs.n_dyn, n_nbr = s.n_obs - n_dyn;  // row slots [0, n_dyn): the obstacles, [n_dyn, n_obs): the in-range agents
+    // row slots [0, n_slot): the obstacles, [n_slot, n_obs): the in-range agents (n_slot = n_dyn unless every mission has its own table)
+    const int32_t n_dyn = obs.n_dyn, n_slot = obs.n_slot, n_nbr = s.n_obs - n_slot;
+    const bool own_tables = obs.per_mission();
     // decentralizedMAPP precedes the planning loop (src/multi_sync_simulator.cpp:101-120): the waypoints of this replan, from the plans as the
     // last replan left them (AgentManager::getTraj is desired_traj, un-shifted)
     if (grid) {
@@ -400,10 +415,17 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     }
     // obstacle_generator.update(t, 0) at the replan's start time (src/multi_sync_simulator.cpp:311); the clock is the device's.  Chasing and
     // gaussian obstacles first: they read the table as the last replan left it, and the agents' states of this replan's start
-    if (n_dyn > 0 && obs.drv.d_drives)
+    if (own_tables && obs.drv.d_drives)
+        PLAN_TRY(lscqp_obstacles_drive_missions_device(h, obs.d_models.get(), obs.drv.d_drives.get(), obs.n_clocks(), obs.ooff.data(), obs.d_ooff.get(), n_dyn,
+                                                       obs.drv.history.get(), obs.drv.n_history, state, s.n_total, obs.drv.state.get(), p->d.time_step,
+                                                       obs.clock.get(), obs.table.get(), stream));
+    else if (n_dyn > 0 && obs.drv.d_drives)
         PLAN_TRY(lscqp_obstacles_drive_device(h, obs.d_models.get(), obs.drv.d_drives.get(), n_dyn, obs.drv.history.get(), obs.drv.n_history, state, s.n_total,
                                               obs.drv.state.get(), p->d.time_step, obs.clock.get(), obs.table.get(), stream));
-    if (n_dyn > 0) PLAN_TRY(lscqp_obstacles_advance_device(h, obs.d_models.get(), n_dyn, p->d.time_step, obs.clock.get(), obs.table.get(), stream));
+    if (own_tables)
+        PLAN_TRY(lscqp_obstacles_advance_missions_device(h, obs.d_models.get(), obs.n_clocks(), obs.ooff.data(), obs.d_ooff.get(), n_dyn, p->d.time_step,
+                                                         obs.clock.get(), obs.table.get(), stream));
+    else if (n_dyn > 0) PLAN_TRY(lscqp_obstacles_advance_device(h, obs.d_models.get(), n_dyn, p->d.time_step, obs.clock.get(), obs.table.get(), stream));
     // obstaclePredictionWithPrevSol / initialTrajPlanningPrevSol for every agent of the mission (:273-310, 399-423)
     const bool from_plans = !first_replan && (s.prediction_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION || s.initial_traj_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION);
     const bool whole_shift = from_plans && fraction >= 1.0 - 1e-9;  // (done by prepare_kernel itself)
@@ -432,15 +454,16 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
                                                 stream));
     if (n_nbr > 0)
         PLAN_TRY(lscqp_generate_constraints_own_(h, p->d.constraint_mode, s.n_agents, n_nbr, s.first_agent, p->traj, p->own, p->nbr, p->radius,
-                                                 p->downwash, goal, rows, s.n_obs, n_dyn, stream));
+                                                 p->downwash, goal, rows, s.n_obs, n_slot, stream));
     // the obstacles' rows (the non-agent branch of the plan's generator) over the planning agents' INITIAL trajectories: `own`, indexed by
     // local id like the radii, goals and headers handed over here -- `traj` holds the agents' predictions as each other's obstacles by now.
     // generateCLSC's rows take no obstacle goal points: Obstacle::goal_point is the origin in the reference (include/obstacle.hpp:23, 37-49)
+    // (a table per mission: the same entries over n_slot slots, the ids naming each agent's own entries -- a slot without one gets zero rows)
     if (n_dyn > 0 && p->d.constraint_mode == LSCQP_GEN_CLSC)
-        PLAN_TRY(lscqp_generate_obstacle_rows_device(h, LSCQP_GEN_CLSC, &obs.param, s.n_agents, n_dyn, 0, p->own, obs.ids.get(), obs.table.get(), nullptr,
+        PLAN_TRY(lscqp_generate_obstacle_rows_device(h, LSCQP_GEN_CLSC, &obs.param, s.n_agents, n_slot, 0, p->own, obs.ids.get(), obs.table.get(), nullptr,
                                                      p->radius + s.first_agent, goal + s.first_agent * 3, nullptr, rows, s.n_obs, 0, stream));
     else if (n_dyn > 0)
-        PLAN_TRY(lscqp_generate_lsc_obstacles_device(h, &obs.param, s.n_agents, n_dyn, 0, p->own, obs.ids.get(), obs.table.get(), p->radius + s.first_agent,
+        PLAN_TRY(lscqp_generate_lsc_obstacles_device(h, &obs.param, s.n_agents, n_slot, 0, p->own, obs.ids.get(), obs.table.get(), p->radius + s.first_agent,
                                                      goal + s.first_agent * 3, hdr, rows, s.n_obs, 0, stream));
     if (p->d.optimize_goal) {  // (the goal LP's kernel finishes the headers itself: one node less)
         PLAN_TRY(lscqp_optimize_goal_fin_device_(h, s.n_agents, hdr, rows, p->off, p->map ? sfc : nullptr, goal_status, s.dt, stream));
@@ -473,7 +496,10 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
         PLAN_TRY(lscqp_safety_metrics_device(h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan,
                                              p->radius, p->downwash, hdr, (lscqp_safety*)p->buf[LSCQP_PLAN_BUF_SAFETY], stream));
     // the obstacle leg of the safety figures (:527-557), against the positions this replan's advance left
-    if (p->d.safety_samples > 0 && n_dyn > 0)
+    if (p->d.safety_samples > 0 && own_tables)
+        PLAN_TRY(lscqp_safety_obstacles_ids_device(h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan, p->radius,
+                                                   p->downwash, n_slot, obs.ids.get(), n_dyn, obs.table.get(), obs.safety.get(), stream));
+    else if (p->d.safety_samples > 0 && n_dyn > 0)
         PLAN_TRY(lscqp_safety_obstacles_device(h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan, p->radius,
                                                p->downwash, n_dyn, obs.table.get(), obs.safety.get(), stream));
     // the mission record: the figures of this replan and the finish test on the state it started from (hdr.p0), the chain's last node (a
@@ -519,9 +545,38 @@ int reset_obstacles(const lscqp_plan_s::Obstacles& o) {
         tab[(size_t)i].radius = m.radius, tab[(size_t)i].downwash = m.downwash, tab[(size_t)i].max_acc = m.max_acc;
     }
     hipError_t e = hipMemcpy(o.table.get(), tab.data(), tab.size() * sizeof(lscqp_obstacle), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(o.clock.get(), 0, sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemset(o.clock.get(), 0, (size_t)o.n_clocks() * sizeof(int32_t));  // (a table per mission: a clock per mission)
     if (e == hipSuccess && o.drv.d_drives) e = hipMemset(o.drv.state.get(), 0, (size_t)o.n_dyn * sizeof(lscqp_obstacle_drive_state));
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "plan reset (obstacles)");
+}
+
+// the partition in force as offsets: [0, n_total] without one
+std::vector<int64_t> mission_offsets_of(const lscqp_plan_s* p) {
+    return p->mis.moff.empty() ? std::vector<int64_t>{0, p->s.n_total} : p->mis.moff;
+}
+
+// ids [n_agents][n_slot] of a table per mission, for the partition `moff`: agent a of mission k names ooff[k] + o in slot o < count_k, -1 beyond
+int upload_mission_ids(const lscqp_plan_s::Obstacles& o, const std::vector<int64_t>& moff, int64_t n_agents) {
+    const size_t ns = (size_t)o.n_slot;
+    std::vector<int32_t> hid((size_t)(n_agents ? n_agents : 1) * ns, -1);
+    for (size_t k = 0; k + 1 < moff.size(); k++)
+        for (int64_t a = moff[k]; a < moff[k + 1]; a++)
+            for (int32_t j = 0; j < o.ooff[k + 1] - o.ooff[k]; j++) hid[(size_t)a * ns + (size_t)j] = o.ooff[k] + j;
+    const hipError_t e = hipMemcpy(o.ids.get(), hid.data(), hid.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    return e == hipSuccess ? LSCQP_OK : hip_fail(e, "lscqp_plan_set_mission_obstacles (ids)");
+}
+
+// a chaser of a table per mission follows an agent of the mission that owns it (target_agent >= 0), or a goal point
+int check_chasers_stay_home(const lscqp_plan_s::Obstacles& o, const lscqp_obstacle_drive* drives, const std::vector<int64_t>& moff) {
+    for (size_t k = 0; k + 1 < o.ooff.size() && k + 1 < moff.size(); k++)
+        for (int32_t i = o.ooff[k]; i < o.ooff[k + 1]; i++) {
+            const lscqp_obstacle_drive& d = drives[i];
+            if (d.kind == LSCQP_DRIVE_CHASING && d.target_agent >= 0 && (d.target_agent < moff[k] || d.target_agent >= moff[k + 1]))
+                return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, ("lscqp_plan_set_obstacle_drives: model " + std::to_string(i) + ": target_agent " +
+                                                                     std::to_string(d.target_agent) + " lies outside mission " + std::to_string(k) +
+                                                                     ", which owns the chaser (lscqp_plan_set_mission_obstacles)").c_str());
+        }
+    return LSCQP_OK;
 }
 
 // the plan's grid and the buffers sized by it (waypoint_mode 1): made at lscqp_plan_create, again by lscqp_plan_set_grid
@@ -817,6 +872,12 @@ int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* 
     if (p->wp.grid && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: the mission's goal points are required");
     if (p->rec.on && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: the mission's goal points are required (the desired goals of the finish test)");
     if (p->pat.on && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_patrol: the mission's goal points are required (the far end of every leg)");
+    if (p->obs.per_mission()) {  // a table per mission: of the partition in force, and every chaser after an agent of its own mission
+        if (p->obs.n_clocks() != p->n_missions())
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, ("lscqp_plan_set_mission_obstacles: " + std::to_string(p->obs.n_clocks()) + " obstacle tables for " +
+                                                                 std::to_string(p->n_missions()) + " missions: one table per mission of the partition in force required").c_str());
+        if (!p->obs.drv.host.empty()) PLAN_TRY(check_chasers_stay_home(p->obs, p->obs.drv.host.data(), mission_offsets_of(p)));
+    }
     OnDevice on(p->device);
     const lscplan::Shape& s = p->s;
     const size_t nt = (size_t)s.n_total, P = (size_t)s.M * 6;
@@ -864,6 +925,9 @@ int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* 
         // record's finish test +inf, which exceeds any threshold -- the record's kernel is the one it always was
         if (p->pat.on) std::fill(want.begin(), want.end(), (double)INFINITY);
         PLAN_TRY(lscqp_record_reset(p->rec.held.get(), want.data()));
+    }
+    if (p->obs.per_mission()) {  // the partition may have other offsets by now (never another count): each agent's own entries again
+        PLAN_TRY(upload_mission_ids(p->obs, mission_offsets_of(p), s.n_agents));
     }
     if (p->obs.n_dyn > 0) PLAN_TRY(reset_obstacles(p->obs));
     p->pending = 0;
@@ -958,6 +1022,10 @@ int lscqp_plan_set_missions(lscqp_plan p, int32_t n_missions, const int64_t* mis
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
                                 ("lscqp_plan_set_missions: the plan has " + std::to_string(lscqp_worlds_count_(p->wld.set)) +
                                  " worlds (lscqp_plan_set_worlds), one per mission: another mission count needs other worlds, or none, first").c_str());
+    if (p->obs.per_mission() && (single ? 1 : n_missions) != p->obs.n_clocks())
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
+                                ("lscqp_plan_set_missions: the plan has " + std::to_string(p->obs.n_clocks()) +
+                                 " obstacle tables (lscqp_plan_set_mission_obstacles), one per mission: another mission count needs other obstacles, or none, first").c_str());
     if (!single) {
         if (p->s.n_agents != p->s.n_total)
             return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "a mission partition needs every agent on this device (n_agents == n_total): a sharded plan flies one mission");
@@ -1112,6 +1180,8 @@ int lscqp_plan_set_flight_log(lscqp_plan p, int32_t max_replans) {
     if (max_replans < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_flight_log: max_replans >= 0 required");
     if (!p->rec.on)
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_flight_log: the plan has no record (lscqp_plan_set_record first): the log is part of it");
+    if (max_replans > 0 && p->obs.per_mission())
+        return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_plan_set_flight_log: the plan has a table of obstacles per mission (lscqp_plan_set_mission_obstacles); the log's obstacle columns are those of one shared table");
     OnDevice on(p->device);
     const hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_flight_log");
@@ -1174,7 +1244,7 @@ int lscqp_plan_set_obstacles(lscqp_plan p, const lscqp_obstacle_param* param, in
         if (e != hipSuccess) return hip_fail(e, what);
         next.models.swap(prepared);
         next.param = *param;
-        next.n_dyn = n_dyn;
+        next.n_dyn = next.n_slot = n_dyn;
         PLAN_TRY(reset_obstacles(next));  // (so that the table can be read, and HELD entries written, before the reset)
     }
     // (a flight log has the obstacles' columns and reads their table: a new log for the new ones, before the plan changes)
@@ -1188,7 +1258,68 @@ int lscqp_plan_set_obstacles(lscqp_plan p, const lscqp_obstacle_param* param, in
     drop_graph(p);  // (a captured chain holds the obstacles' nodes and the slot split)
     p->obs = std::move(next);
     p->pending = none ? p->pending & ~lscplan::kPendObstacles : p->pending | lscplan::kPendObstacles;
-    p->pending &= ~lscplan::kPendDrives;  // (the drives went with the old obstacles)
+    p->pending &= ~(lscplan::kPendDrives | lscplan::kPendMissionObstacles);  // (the drives, and a table per mission, went with the old obstacles)
+    return LSCQP_OK;
+}
+
+int lscqp_plan_set_mission_obstacles(lscqp_plan p, const lscqp_obstacle_param* param, int32_t n_missions, const int32_t* obstacle_offsets,
+                                     const lscqp_obstacle_model* models) {
+    const char* const what = "lscqp_plan_set_mission_obstacles";
+    if (!p) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null plan");
+    if (n_missions < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_mission_obstacles: negative n_missions");
+    // (no mission, no models, or missions none of which owns an obstacle: the obstacles are taken away, as lscqp_plan_set_obstacles does it)
+    bool none = n_missions == 0 || !models;
+    if (!none && obstacle_offsets) none = std::all_of(obstacle_offsets, obstacle_offsets + n_missions + 1, [](int32_t v) { return v == 0; });
+    if (none) return lscqp_plan_set_obstacles(p, nullptr, 0, nullptr);
+    if (!param) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_mission_obstacles: null param");
+    if (!obstacle_offsets) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_mission_obstacles: null obstacle_offsets");
+    if (p->d.constraint_mode != LSCQP_GEN_LSC && p->d.constraint_mode != LSCQP_GEN_CLSC)
+        return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_plan_set_mission_obstacles: constraint_mode must be LSCQP_GEN_LSC or LSCQP_GEN_CLSC (generateBVC's obstacle rows are not built)");
+    if (p->s.n_agents != p->s.n_total)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_mission_obstacles: a table per mission needs every agent on this device (n_agents == n_total): a sharded plan shares one table");
+    if (n_missions != p->n_missions())
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, (std::string(what) + ": " + std::to_string(n_missions) + " obstacle tables for " + std::to_string(p->n_missions()) +
+                                                             " missions: one table per mission of the partition in force required (lscqp_plan_set_missions first)").c_str());
+    if (p->rec.log_capacity > 0)
+        return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_plan_set_mission_obstacles: the plan has a flight log (lscqp_plan_set_flight_log), whose obstacle columns are those of one shared table");
+    int32_t n_slot = 0;
+    {   // the offsets: the device entries' own check, by the total the list itself gives once it is known not to decrease
+        for (int32_t k = 0; k < n_missions; k++)
+            if (obstacle_offsets[k + 1] < obstacle_offsets[k]) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "obstacle_offsets must not decrease");
+        PLAN_TRY(lscobstacle::check_obstacle_offsets(p->h, n_missions, obstacle_offsets, obstacle_offsets[n_missions], &n_slot));
+    }
+    if (n_slot > p->s.n_obs)
+        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_mission_obstacles: a mission's obstacle count exceeds the plan's row slots per agent (max_k count_k <= desc.n_obs required)");
+    const int32_t n_dyn = obstacle_offsets[n_missions];
+    std::vector<lscqp_obstacle_model> prepared(models, models + n_dyn);
+    PLAN_TRY(lscqp_obstacle_model_prepare(prepared.data(), n_dyn));
+    OnDevice on(p->device);
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, what);
+    lscqp_plan_s::Obstacles next;
+    {   // (everything that can fail comes before the plan changes)
+        const size_t n = (size_t)p->s.n_agents, nd = (size_t)n_dyn, K = (size_t)n_missions;
+        next.ooff.assign(obstacle_offsets, obstacle_offsets + K + 1);
+        next.n_dyn = n_dyn, next.n_slot = n_slot;
+        PLAN_TRY(lscqp::dev_alloc(next.d_models, nd, what));
+        PLAN_TRY(lscqp::dev_alloc(next.table, nd, what));
+        PLAN_TRY(lscqp::dev_alloc(next.ids, (n ? n : 1) * (size_t)n_slot, what));
+        PLAN_TRY(lscqp::dev_alloc(next.clock, K, what));
+        PLAN_TRY(lscqp::dev_alloc(next.d_ooff, K + 1, what));
+        PLAN_TRY(lscqp::dev_alloc(next.safety, n ? n : 1, what, true));
+        e = hipMemcpy(next.d_models.get(), prepared.data(), nd * sizeof(lscqp_obstacle_model), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(next.d_ooff.get(), obstacle_offsets, (K + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, what);
+        PLAN_TRY(upload_mission_ids(next, mission_offsets_of(p), p->s.n_agents));
+        next.models.swap(prepared);
+        next.param = *param;
+        PLAN_TRY(reset_obstacles(next));  // (so that the table can be read, and HELD entries written, before the reset)
+    }
+    // (an obstacle record reads the obstacles' safety buffer: the new one)
+    if (p->rec.held && p->rec.obstacle_figures) PLAN_TRY(lscqp_record_set_obstacle_figures(p->rec.held.get(), next.safety.get()));
+    drop_graph(p);  // (a captured chain holds the obstacles' nodes and the slot split)
+    p->obs = std::move(next);
+    p->pending = (p->pending | lscplan::kPendMissionObstacles) & ~(lscplan::kPendObstacles | lscplan::kPendDrives);  // (the drives went with the old obstacles)
     return LSCQP_OK;
 }
 
@@ -1203,6 +1334,7 @@ int lscqp_plan_set_obstacle_drives(lscqp_plan p, const lscqp_obstacle_drive* dri
             return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacle_drives: n_dyn is not the number of the plan's obstacles");
         if (n_history > 0 && !acc_history) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacle_drives: null acc_history");
         PLAN_TRY(lscqp_obstacle_drive_check(p->obs.models.data(), drives, n_dyn, n_history, p->s.n_total));
+        if (p->obs.per_mission()) PLAN_TRY(check_chasers_stay_home(p->obs, drives, mission_offsets_of(p)));
     }
     OnDevice on(p->device);
     hipError_t e = hipDeviceSynchronize();
@@ -1218,6 +1350,7 @@ int lscqp_plan_set_obstacle_drives(lscqp_plan p, const lscqp_obstacle_drive* dri
         if (e == hipSuccess && nh) e = hipMemcpy(next.history.get(), acc_history, nh * 3 * sizeof(double), hipMemcpyHostToDevice);
         if (e != hipSuccess) return hip_fail(e, what);
         next.n_history = n_history;
+        if (p->obs.per_mission()) next.host.assign(drives, drives + nd);  // (the reset asks again where each chaser's target flies)
     }
     drop_graph(p);  // (a captured chain has, or lacks, the drive's node)
     p->obs.drv = std::move(next);
@@ -1292,7 +1425,7 @@ void* obstacle_buffer(lscqp_plan_s* p, int32_t which, size_t* bytes) {
     switch (which) {
     case LSCQP_PLAN_OBS_TABLE: *bytes = (size_t)o.n_dyn * sizeof(lscqp_obstacle); return o.table.get();
     case LSCQP_PLAN_OBS_SAFETY: *bytes = (size_t)p->s.n_agents * sizeof(lscqp_safety_obs); return o.safety.get();
-    case LSCQP_PLAN_OBS_CLOCK: *bytes = sizeof(int32_t); return o.clock.get();
+    case LSCQP_PLAN_OBS_CLOCK: *bytes = (size_t)o.n_clocks() * sizeof(int32_t); return o.clock.get();
     }
     return nullptr;
 }

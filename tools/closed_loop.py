@@ -7,6 +7,7 @@
     python tools/closed_loop.py [--steps 40] [--world tests/golden/forest10_world.json]
     python tools/closed_loop.py --missions 25 --until-finished [MAX]      (K seeded missions in one plan, flown to the finish on the device)
     python tools/closed_loop.py --missions 4 --worlds A.csv B.csv C.csv D.csv   (mission k over world k: one plan, a world per mission)
+    python tools/closed_loop.py --missions 3 --obstacles A.json B.json C.json [--drive-obstacles] [--until-finished]   (mission k among file k's obstacles)
     python tools/closed_loop.py --patrol [--goal-threshold T] [--missions K] --steps 400   (a patrol: legs per agent, per mission)
 
 The host keeps the per-agent headers and, with --router host (the default), picks each agent's next waypoint with a stand-in
@@ -193,7 +194,8 @@ def write_flight_csv(path, states, obstacles, time_step, record_time_step, plann
 
 
 def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=0, graph=True, until_finished=None, check_every=16,
-                 goal_threshold=0.1, obstacles=None, worlds=None, obstacle_rows="lsc", log_csv=None, obstacle_specs=None, obstacle_seed=0, patrol=None):
+                 goal_threshold=0.1, obstacles=None, worlds=None, obstacle_rows="lsc", log_csv=None, obstacle_specs=None, obstacle_seed=0, patrol=None,
+                 mission_obstacles=None, mission_obstacle_specs=None):
     """`missions` seeded missions over one world flown by ONE lscqp_plan with a mission partition (include/lscqp.h, "many missions over one
     map"): waypoint_mode 1, closed loop, one captured graph per replan.  The summary has the figures of `run` per mission.
     until_finished = MAX: the plan keeps a mission record (include/lscqp.h, "the mission record") and lscqp_plan_run flies it until every
@@ -207,6 +209,10 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     obstacle_specs (with obstacles: the mission-file entries the models were made from, load_obstacle_specs): the chasing and gaussian entries
     are driven on the device (include/lscqp.h, "chasing and gaussian obstacles"; api.obstacle_drives with obstacle_seed for the gaussian
     histories, drawn for the whole flight); without it such an entry is HELD at its start.
+    mission_obstacles: instead of `obstacles`, a list of `missions` arrays of such records (an empty one or None: no obstacle) -- mission k flies
+    among its own and sees no other's (include/lscqp.h, "a mission's own obstacles"; lscqp_plan_set_mission_obstacles).  They take as many row
+    slots as the largest list has entries.  mission_obstacle_specs: the files' entries per mission, for the drives; a chaser's target_agent is
+    an agent of ITS mission, counted from that mission's first agent as the mission's own file counts it.  No flight log with them.
     worlds: one world per mission (load_worlds) in the world's box -- mission k flies over world k (include/lscqp.h, "each mission over its
     own world"; lscqp_plan_set_worlds), its seeded agents drawn from the free nodes of its own world; world 0 replaces the world's own boxes.
     log_csv (with until_finished): a directory; the plan keeps a flight log of MAX rows per mission (include/lscqp.h, "the flight log") and
@@ -237,8 +243,15 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     N = int(off[-1])
     if obstacle_rows not in ("lsc", "clsc"):
         raise ValueError("obstacle_rows must be 'lsc' or 'clsc'")
-    n_dyn = 0 if obstacles is None else len(obstacles)
-    n_obs = max(1, min((n - 1 if n_obs is None else n_obs) + n_dyn, sol.max_obstacles()))
+    if mission_obstacles is not None:
+        if obstacles is not None or len(mission_obstacles) != missions:
+            raise ValueError("mission_obstacles: one list per mission (%d for missions=%d), and no shared `obstacles` beside them" % (len(mission_obstacles), missions))
+        if log_csv:
+            raise ValueError("log_csv: the flight log's obstacle columns are those of one shared table, not of a table per mission")
+        mission_obstacles = [np.zeros(0, api.OBSTACLE_MODEL_DTYPE) if m is None else m for m in mission_obstacles]
+    n_dyn = (0 if obstacles is None else len(obstacles)) if mission_obstacles is None else sum(len(m) for m in mission_obstacles)
+    n_slot = n_dyn if mission_obstacles is None else max(len(m) for m in mission_obstacles)  # the row slots the obstacles take
+    n_obs = max(1, min((n - 1 if n_obs is None else n_obs) + n_slot, sol.max_obstacles()))
     ag = np.zeros(N, api.AGENT_PARAM_DTYPE)
     ag["radius"], ag["downwash"], ag["max_vel"], ag["max_acc"], ag["nominal_velocity"] = g["radius"], 2.0, 1.0, 2.0, 1.0
     plan = api.Plan(sol, wmap, N, n_obs, ag, constraint_mode=api.GEN_LSC if n_dyn and obstacle_rows == "lsc" else api.GEN_CLSC, sfc_mode=api.SFC_FROM_HULL, optimize_goal=True,
@@ -248,7 +261,12 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     if world_boxes:
         world_set = api.Worlds(maps)
         plan.set_worlds(world_set)
-    if n_dyn:
+    if n_dyn and mission_obstacles is not None:
+        plan.set_mission_obstacles(mission_obstacles)
+        if mission_obstacle_specs is not None:  # one list in mission order, every chaser's target made a global agent id
+            obstacle_specs = [dict(o, target_agent=int(o["target_agent"]) + int(off[k])) if int(o.get("target_agent", -1)) >= 0 else o
+                              for k, per_k in enumerate(mission_obstacle_specs) for o in (per_k or [])]
+    elif n_dyn:
         plan.set_obstacles(obstacles)
     n_driven = 0
     if n_dyn and obstacle_specs is not None:
@@ -284,7 +302,7 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
         if n_dyn:
             for m, o in zip(per, plan.record().obstacles()[0]):
                 m.update(obstacle_safety_ratio=float(o["safety_ratio_obs"]), obstacle_safety_replan=int(o["replan"]), obstacle_safety_agent=int(o["agent"]),
-                         obstacle_safety_obstacle=int(o["obstacle"]), below_one=int(o["below_one"]))
+                         obstacle_safety_obstacle=int(o["obstacle"]), below_one=int(o["below_one"]), safety_ratio_obs=float(o["safety_ratio_obs"]))
         if patrol is not None:
             legs = plan.patrol(api.PATROL_LEGS)
             for k, m in enumerate(per):
@@ -296,7 +314,8 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
         if patrol is not None:
             log.update(patrol_goal_threshold=float(patrol), legs=sum(sum(m["legs"]) for m in per))
         if n_dyn:  # (the flight's least figure per mission is in per_mission; the last replan's is what the plan still holds)
-            log.update(obstacles=n_dyn, driven_obstacles=n_driven, min_obstacle_safety_ratio=min(m["obstacle_safety_ratio"] for m in per),
+            log.update(obstacles=n_dyn, obstacle_slots=n_slot, obstacles_per_mission=mission_obstacles is not None, driven_obstacles=n_driven,
+                       min_obstacle_safety_ratio=min(m["obstacle_safety_ratio"] for m in per),
                        last_obstacle_safety_ratio=float(plan.get_obstacles(api.PLAN_OBS_SAFETY)["safety_ratio_obs"].min()))
         if world_set:
             log["worlds"] = len(world_set)
@@ -311,22 +330,25 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     plan.reset(starts, goals)
     min_obstacle_ratio = np.inf
     per = [dict(mission=k, agents=n, qp_failed=0, invalid=0, min_safety_ratio=np.inf, max_vel_excess=0.0, max_acc_excess=0.0, waypoints_updated=0,
-                truncated_agent_steps=0) for k in range(missions)]
+                truncated_agent_steps=0, **(dict(safety_ratio_obs=np.inf) if n_dyn else {})) for k in range(missions)]
     for _ in range(steps):
         plan.step(graph=graph)
         torch.cuda.synchronize()
         st, valid, saf, upd, cnt = (plan.get(b) for b in (api.PLAN_STATUS, api.PLAN_VALID, api.PLAN_SAFETY, api.PLAN_WAYPOINT_UPDATED, api.PLAN_IN_RANGE))
         if n_dyn:
-            min_obstacle_ratio = float(min(min_obstacle_ratio, plan.get_obstacles(api.PLAN_OBS_SAFETY)["safety_ratio_obs"].min()))
+            fig = plan.get_obstacles(api.PLAN_OBS_SAFETY)["safety_ratio_obs"]
+            min_obstacle_ratio = float(min(min_obstacle_ratio, fig.min()))
         for k, m in enumerate(per):
             sl = slice(int(off[k]), int(off[k + 1]))
+            if n_dyn:  # (+inf: the mission has no obstacle of its own)
+                m["safety_ratio_obs"] = float(min(m["safety_ratio_obs"], fig[sl].min()))
             m["qp_failed"] += int((st[sl] != 0).sum())
             m["invalid"] += int(((st[sl] == 0) & (valid[sl] != 1)).sum())
             m["min_safety_ratio"] = float(min(m["min_safety_ratio"], saf["safety_ratio"][sl].min()))
             m["max_vel_excess"] = float(max(m["max_vel_excess"], saf["vel_excess_ratio"][sl].max()))
             m["max_acc_excess"] = float(max(m["max_acc_excess"], saf["acc_excess_ratio"][sl].max()))
             m["waypoints_updated"] += int(upd[sl].sum())
-            m["truncated_agent_steps"] += int((cnt[sl] > n_obs - n_dyn).sum())
+            m["truncated_agent_steps"] += int((cnt[sl] > n_obs - n_slot).sum())
     state = plan.get(api.PLAN_STATE).reshape(N, 9)
     progress = np.linalg.norm(goals[:, :2] - starts[:, :2], axis=1) - np.linalg.norm(goals[:, :2] - state[:, :2], axis=1)
     status = plan.mission_status()
@@ -343,7 +365,8 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
     if patrol is not None:
         log.update(patrol_goal_threshold=float(patrol), legs=sum(sum(m["legs"]) for m in per))
     if n_dyn:
-        log.update(obstacles=n_dyn, driven_obstacles=n_driven, min_obstacle_safety_ratio=min_obstacle_ratio)
+        log.update(obstacles=n_dyn, obstacle_slots=n_slot, obstacles_per_mission=mission_obstacles is not None, driven_obstacles=n_driven,
+                   min_obstacle_safety_ratio=min_obstacle_ratio)
     if world_set:
         log["worlds"] = len(world_set)
     plan.close()
@@ -356,7 +379,7 @@ def run_missions(world_json, missions, steps=40, M=10, dt=0.2, n_obs=None, seed=
 
 def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=None, n_obs=None, script=None, router="host", missions=None,
         decision="one", until_finished=None, obstacles=None, worlds=None, obstacle_rows="lsc", log_csv=None, obstacle_specs=None, obstacle_seed=0,
-        patrol=None):
+        patrol=None, mission_obstacles=None, mission_obstacle_specs=None):
     """script (optional): {"waypoint": (K, N, 3), "state": (K, N, 9)} -- replay of a recorded mission: replan k takes every agent's
     state and waypoint from the script instead of the loop's own step / router (the plans, goal points, corridors and neighbour sets are
     still the loop's own), and the result carries every replan's solution (`x`, (K, N, nv)) and goal point (`goal`, (K, N, 3)).
@@ -365,6 +388,7 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
     decision (router "device"): "one" (lscqp_waypoints_device), "wide" (lscqp_waypoints_wide_device) or "auto" (wide from
     DECISION_AUTO_MIN_AGENTS agents on); the flight is the same whichever is chosen.
     until_finished (with missions): fly until every mission has finished, at most that many replans (run_missions).
+    mission_obstacles, mission_obstacle_specs (with missions): a list of obstacles per mission, each mission's own (run_missions).
     obstacles (with missions): dynamic obstacles flown by the plan's own chain (load_obstacles, run_missions); obstacle_rows "lsc" or "clsc":
     the generator of their rows, and with it the plan's constraint mode (run_missions).  obstacle_specs, obstacle_seed: the file's entries
     (load_obstacle_specs) -- its chasing and gaussian obstacles are then driven on the device instead of being HELD at their start.
@@ -379,6 +403,8 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
         raise ValueError("decision must be 'one', 'wide' or 'auto'")
     if until_finished and not missions:
         raise ValueError("until_finished needs missions=K (one lscqp_plan with a mission record)")
+    if mission_obstacles is not None and not missions:
+        raise ValueError("mission_obstacles need missions=K: list k belongs to mission k of an lscqp_plan (lscqp_plan_set_mission_obstacles)")
     if obstacles is not None and not missions:
         raise ValueError("obstacles need missions=K (K >= 1): they fly in the chain of an lscqp_plan (lscqp_plan_set_obstacles)")
     if worlds is not None and not missions:
@@ -388,7 +414,8 @@ def run(world_json, steps=40, M=10, dt=0.2, verbose=False, dump=None, keep_step=
     if missions:
         return run_missions(world_json, int(missions), steps=steps, M=M, dt=dt, n_obs=n_obs, until_finished=until_finished, obstacles=obstacles,
                             worlds=worlds, obstacle_rows=obstacle_rows, log_csv=log_csv, obstacle_specs=obstacle_specs, obstacle_seed=obstacle_seed,
-                            patrol=patrol, **({} if patrol is None else {"goal_threshold": float(patrol)}))
+                            patrol=patrol, mission_obstacles=mission_obstacles, mission_obstacle_specs=mission_obstacle_specs,
+                            **({} if patrol is None else {"goal_threshold": float(patrol)}))
     import torch
 
     from lsc_dr_planner_amd import api
@@ -590,9 +617,10 @@ if __name__ == "__main__":
                          "one record per mission")
     ap.add_argument("--decision", default="one", choices=("one", "wide", "auto"),
                     help="with --router device: the one-workgroup decision, lscqp_waypoints_wide_device, or wide from DECISION_AUTO_MIN_AGENTS agents on")
-    ap.add_argument("--obstacles", default=None, metavar="FILE.json",
+    ap.add_argument("--obstacles", default=None, nargs="+", metavar="FILE.json",
                     help="with --missions K: the dynamic obstacles of a reference mission file (its \"obstacles\" list, or a bare list: type, start, goal, "
-                         "waypoints, axis, size, speed, max_acc, downwash), shared by every mission and moved by the plan's chain")
+                         "waypoints, axis, size, speed, max_acc, downwash), moved by the plan's chain.  One file: shared by every mission.  K files: "
+                         "mission k flies among the obstacles of file k and sees no other's (a chaser's target_agent counts from its mission's first agent)")
     ap.add_argument("--obstacle-rows", default="lsc", choices=("lsc", "clsc"),
                     help="with --obstacles: lsc = generateLSC's rows for obstacles and agents alike (the plan flies GEN_LSC); clsc = the plan keeps "
                          "GEN_CLSC, the reference's launch mode, and the obstacles get generateCLSC's rows")
@@ -612,8 +640,13 @@ if __name__ == "__main__":
     ap.add_argument("--router", default="host", choices=("host", "device"), help="where the waypoints come from: the host stand-in or lscqp_waypoints_device")
     a = ap.parse_args()
     world = random_forest_world(a.forest) if a.forest > 0 else a.world
+    shared = a.obstacles[0] if a.obstacles and len(a.obstacles) == 1 else None
+    own = a.obstacles if a.obstacles and len(a.obstacles) > 1 else None
+    if own and len(own) != a.missions:
+        ap.error("--obstacles: one file (shared by every mission) or one per mission -- %d files for --missions %d" % (len(own), a.missions))
     print(json.dumps(run(world, steps=a.steps, verbose=a.v, dump=a.dump, n_obs=a.obs, router=a.router, missions=a.missions, decision=a.decision,
-                         until_finished=a.until_finished, obstacles=load_obstacles(a.obstacles) if a.obstacles else None, worlds=a.worlds,
+                         until_finished=a.until_finished, obstacles=load_obstacles(shared) if shared else None, worlds=a.worlds,
                          obstacle_rows=a.obstacle_rows, log_csv=a.log_csv,
-                         obstacle_specs=load_obstacle_specs(a.obstacles) if a.obstacles and a.drive_obstacles else None, obstacle_seed=a.obstacle_seed,
-                         patrol=a.goal_threshold if a.patrol else None)))
+                         obstacle_specs=load_obstacle_specs(shared) if shared and a.drive_obstacles else None, obstacle_seed=a.obstacle_seed,
+                         patrol=a.goal_threshold if a.patrol else None, mission_obstacles=[load_obstacles(f) for f in own] if own else None,
+                         mission_obstacle_specs=[load_obstacle_specs(f) for f in own] if own and a.drive_obstacles else None)))
