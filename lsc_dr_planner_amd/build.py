@@ -36,6 +36,15 @@ def fused_instances():
     return [tuple(int(v) for v in m) for m in re.findall(r"X\((\d+),\s*(\d+),\s*(\d+),\s*(\d+),\s*(\d+)\)", body)]
 
 
+def fused_flags(M, D):
+    """Optimiser options of one fused unit.  The units that compile the phase's latency text (csrc/lscqp_fused.hip: LSCQP_DAS_FORM -- M = 5,
+    and M = 10 in 2-D) are built without machine-level loop-invariant code motion: in front of the loop of steps it hoists the set-up of
+    arms the stepping instance of a small batch never enters (the polish, a leaving row, the hand-over, the proof), and what it hoists it
+    spills -- without it those units spill 150 / 196 scalar registers against 161 / 220 and the stepping instance is faster in the timing
+    twin (NOTES.md section 45).  The throughput unit keeps the default: its machine code is unchanged."""
+    return ["-mllvm", "-disable-machine-licm"] if M == 5 or (M == 10 and D == 2) else []
+
+
 def _newer(target, deps):
     if not os.path.exists(target):
         return True
@@ -70,7 +79,8 @@ def units():
     # its own fp contraction through lscqp_das.hpp's pragma), and a second time from the race test's twin of the phase for liblscqp_sync.so
     for (M, D, E, S, W) in fused_instances():
         rows.append(("lscqp_fused.hip", "fused_%d_%d_%d_%d_%d" % (M, D, E, S, W),
-                     ["-DLSCQP_M=%d" % M, "-DLSCQP_DIM=%d" % D, "-DLSCQP_ES=%d" % E, "-DLSCQP_NSLOT=%d" % S, "-DLSCQP_W=%d" % W], "LSCQP_EXTRA_F64_FLAGS", True))
+                     ["-DLSCQP_M=%d" % M, "-DLSCQP_DIM=%d" % D, "-DLSCQP_ES=%d" % E, "-DLSCQP_NSLOT=%d" % S, "-DLSCQP_W=%d" % W] + fused_flags(M, D),
+                     "LSCQP_EXTRA_F64_FLAGS", True))
     rows += [
         ("lscqp_api.hip", "api", [], "LSCQP_EXTRA_F64_FLAGS", False),
         ("lscpost.hip", "lscpost", [], None, False),

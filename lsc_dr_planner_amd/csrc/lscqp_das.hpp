@@ -119,6 +119,70 @@ __device__ __forceinline__ void wave_argmin(double& v, int& id) {  // lexicograp
     id = wave_min_i32((v == vm) ? id : 2147483647);
     v = vm;
 }
+// The latency text's reductions: the same trees on DPP steps that need no identity in the destination.  A step of lscqp::dpp_step is five
+// instructions -- two moves that put the identity into the destination for the lanes without a source, two DPP moves, the operation --
+// and on a path bound by instruction issue the two moves are time (NOTES section 45).
+//   row_shr steps of a sum or of a maximum over values >= 0: `bound_ctrl` gives a lane without a source +0.0 and the destination needs no
+//   old value.  +0.0 IS the sum's identity in dpp_step, so the sum adds what it added; fmax(v, +0.0) == v == fmax(v, -1e300) for v >= +0.0.
+//   The two row_bcast steps write some rows only: the others keep `old`, the identity, as before.
+template <class Op, int CTRL>
+__device__ __forceinline__ double dpp_step_zero(double v) {  // (a row_shr step; Op's values are >= +0.0, or Op is the sum)
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
+    return Op::ap(v, __hiloint2double(hi, lo));
+}
+struct OpMax0 {  // a maximum over values >= +0.0: the rows a row_bcast step does not write see +0.0
+    static __device__ __forceinline__ double id() { return 0.0; }
+    static __device__ __forceinline__ double ap(double a, double b) { return fmax(a, b); }
+};
+template <class OpA, class OpB, class OpC>
+__device__ __forceinline__ void wave_reduce3_zero(double& a, double& b, double& c) {  // lscqp::wave_reduce3's tree and operand order
+    a = dpp_step_zero<OpA, 0x111>(a), b = dpp_step_zero<OpB, 0x111>(b), c = dpp_step_zero<OpC, 0x111>(c);
+    a = dpp_step_zero<OpA, 0x112>(a), b = dpp_step_zero<OpB, 0x112>(b), c = dpp_step_zero<OpC, 0x112>(c);
+    a = dpp_step_zero<OpA, 0x114>(a), b = dpp_step_zero<OpB, 0x114>(b), c = dpp_step_zero<OpC, 0x114>(c);
+    a = dpp_step_zero<OpA, 0x118>(a), b = dpp_step_zero<OpB, 0x118>(b), c = dpp_step_zero<OpC, 0x118>(c);
+    a = lscqp::dpp_step<OpA, 0x142, 0xa>(a), b = lscqp::dpp_step<OpB, 0x142, 0xa>(b), c = lscqp::dpp_step<OpC, 0x142, 0xa>(c);
+    a = lscqp::dpp_step<OpA, 0x143, 0xc>(a), b = lscqp::dpp_step<OpB, 0x143, 0xc>(b), c = lscqp::dpp_step<OpC, 0x143, 0xc>(c);
+    a = lscqp::bcast63(a), b = lscqp::bcast63(b), c = lscqp::bcast63(c);
+}
+template <class Op>
+__device__ __forceinline__ double wave_reduce1_zero(double v) {
+    v = dpp_step_zero<Op, 0x111>(v);
+    v = dpp_step_zero<Op, 0x112>(v);
+    v = dpp_step_zero<Op, 0x114>(v);
+    v = dpp_step_zero<Op, 0x118>(v);
+    v = lscqp::dpp_step<Op, 0x142, 0xa>(v);
+    v = lscqp::dpp_step<Op, 0x143, 0xc>(v);
+    return lscqp::bcast63(v);
+}
+//   wave_argmin's minimum: zero is not neutral, so the four steps inside a row are rotations (row_ror), in which every lane has a source:
+//   every lane of a row ends with the row's minimum, lane 63 behind the two row_bcast steps with the wavefront's.  A minimum is exact under
+//   any association (the hardware orders -0.0 below +0.0 in every step), so it is wave_min's value, bit for bit; a NaN is dropped by
+//   fmin wherever another value stands beside it, as wave_min's fmax drops it.
+struct OpMin {
+    static __device__ __forceinline__ double id() { return 1e300; }
+    static __device__ __forceinline__ double ap(double a, double b) { return fmin(a, b); }
+};
+template <int CTRL>
+__device__ __forceinline__ double dpp_step_ror_min(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
+    return fmin(v, __hiloint2double(hi, lo));
+}
+__device__ __forceinline__ double wave_min_ror(double v) {
+    v = dpp_step_ror_min<0x121>(v);  // row_ror:1
+    v = dpp_step_ror_min<0x122>(v);  // row_ror:2
+    v = dpp_step_ror_min<0x124>(v);  // row_ror:4
+    v = dpp_step_ror_min<0x128>(v);  // row_ror:8
+    v = lscqp::dpp_step<OpMin, 0x142, 0xa>(v);
+    v = lscqp::dpp_step<OpMin, 0x143, 0xc>(v);
+    return lscqp::bcast63(v);
+}
+__device__ __forceinline__ void wave_argmin_ror(double& v, int& id) {  // wave_argmin with wave_min_ror
+    const double vm = wave_min_ror(v);
+    id = wave_min_i32((v == vm) ? id : 2147483647);
+    v = vm;
+}
 // a / b for small non-negative integers (a < 2^20, b <= 2^10) through one fp32 multiplication: exact, and a handful of instructions where an
 // integer division by a run-time value costs ~40
 __device__ __forceinline__ int fdiv(int a, float inv_b) { return (int)(((float)a + 0.5f) * inv_b); }
@@ -218,6 +282,10 @@ __device__ unsigned long long LSCQP_DAS_CYCLES[16];
 // statement takes the pointers as scalar-register inputs (they must be there at this point; they stay what they are to the optimiser)
 // and hands the class scalars, the row offsets' pointer and the boxes' back as values of unknown origin: nothing behind it can be read
 // again from the segment.
+// (kmax, max_steps, cacheC, x_init, x_out, obj_out, status_out and info_out are first read behind the first pass, and every use reads them
+// from the segment again.  Listed here they cost a second wait and twelve lane spills in front of the first load of the critical chain;
+// without them that block is 19 instructions shorter and the stepping instance 120 cycles SLOWER in the timing twin -- the reads then
+// stand, with waits of their own, in front of the loop of steps: NOTES section 45.  They stay listed.)
 // (a pointer of unknown origin is a generic one, and a load through it waits on both counters: these two say "global memory" themselves)
 #define LSCQP_DAS_GLOBAL __attribute__((address_space(1)))
 #define LSCQP_DAS_KERNARGS()                                                                                                            \

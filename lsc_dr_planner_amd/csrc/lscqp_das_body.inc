@@ -42,8 +42,17 @@
 // and the 512-QP batches 2 % slower, measured.)
 #if LSCQP_DAS_FORM == LSCQP_DAS_LATENCY
 #define DAS_CLS(f) ka_##f  // a scalar of the class: the kernel-argument block's register
+// the wavefront's reductions on DPP steps without identity moves (lscqp_das.hpp): the same trees, the same bits
+#define DAS_ARGMIN wave_argmin_ror
+#define DAS_SUM(v) wave_reduce1_zero<lscqp::OpSum>(v)
+#define DAS_MAX0(v) wave_reduce1_zero<OpMax0>(v)  // (a maximum over values >= +0.0)
+#define DAS_MAX0_MAX0_SUM(a, b, c) wave_reduce3_zero<OpMax0, OpMax0, lscqp::OpSum>(a, b, c)
 #elif LSCQP_DAS_FORM == LSCQP_DAS_THROUGHPUT
 #define DAS_CLS(f) cls.f  // a scalar of the class: the kernel argument, read where it is used
+#define DAS_ARGMIN wave_argmin
+#define DAS_SUM(v) wave_sum(v)
+#define DAS_MAX0(v) wave_max(v)
+#define DAS_MAX0_MAX0_SUM(a, b, c) lscqp::wave_reduce3<lscqp::OpMax, lscqp::OpMax, lscqp::OpSum>(a, b, c)
 #else
 #error "LSCQP_DAS_FORM is LSCQP_DAS_THROUGHPUT or LSCQP_DAS_LATENCY"
 #endif
@@ -760,7 +769,7 @@
                 }
             }
         }
-        wave_argmin(bv, bi);
+        DAS_ARGMIN(bv, bi);
         if constexpr (NW > 1) {
             double* const rb_ = red_ + 24 * par;
             par ^= 1;
@@ -831,7 +840,7 @@
             for (int t_ = 0; t_ < 8; t_++) yi += Jr[t_] * lscqp::bcast(vi, j0 + t_);  // (k <= 32: the lane index stays below 64; lanes >= k hold 0)
         }
         yi = mine ? yi : 0.0;
-        if (yy) *yy = wave_sum(yi * yi);
+        if (yy) *yy = DAS_SUM(yi * yi);
         for (int j0 = 0; j0 < k; j0 += 8) {  // r = J'y (column ll of J)
             double Jc[8];
 #pragma unroll
@@ -1082,7 +1091,7 @@
     auto finish = [&](int k, double& res_d, double& obj) {
         double rd, gs, part;
         finish_local(k, rd, gs, part);
-        lscqp::wave_reduce3<lscqp::OpMax, lscqp::OpMax, lscqp::OpSum>(rd, gs, part);
+        DAS_MAX0_MAX0_SUM(rd, gs, part);  // (rd and gs are maxima of absolute values over 0.0)
         if constexpr (NW > 1) {
             double* const rb_ = red_ + 24 * par;
             par ^= 1;
@@ -1176,8 +1185,8 @@
                 // multipliers >= 0 is the one KKT condition the passes do not look at again: a refined multiplier below zero by more than
                 // rounding is not this phase's to return -- the interior-point kernel solves the instance; rounding-size negatives are zero
                 const double un = (lane < k) ? u_[lane] + du : 0.0;
-                const double umax = wave_max(fabs(un));
-                const double neg = wave_max((lane < k && un < -1e-12 * umax) ? 1.0 : 0.0);
+                const double umax = DAS_MAX0(fabs(un));
+                const double neg = DAS_MAX0((lane < k && un < -1e-12 * umax) ? 1.0 : 0.0);
                 if (lane < k) u_[lane] = fmax(un, 0.0);
                 if (lane == 0) ctl_[7] = neg;
             }
@@ -1304,7 +1313,7 @@
                 const double t2 = (curv > 1e-12 * spp) ? -sp / curv : 1e300;
                 double t1 = (lane < k && ri > 0.0) ? u_[lane] / ri : 1e300;
                 int l = lane;
-                wave_argmin(t1, l);
+                DAS_ARGMIN(t1, l);
                 const double t = fmin(t1, t2);
                 int kind;  // 0: no step exists (hand over); 1: p joins; 2: row l leaves; 3: no step exists and the row is violated beyond what the rest of its normal can repair: no point satisfies the rows
                 if (!(t < 1e299)) kind = (sp < -1e-6) ? 3 : 0;  // (3 is a candidate proof: checked after the loop)
@@ -1464,3 +1473,7 @@
     LSCQP_DAS_END(kDasSolved);
 #undef DAS_U_CAND
 #undef DAS_CLS
+#undef DAS_ARGMIN
+#undef DAS_SUM
+#undef DAS_MAX0
+#undef DAS_MAX0_MAX0_SUM

@@ -29,7 +29,8 @@ constexpr bool carve_fits(int M, int dim, int kmax, int stage_rows) {
     return sizeof(double) * (size_t)Layout::make(M, dim, kmax, 1, stage_rows).total <= lscqp::kMaxLdsBytes;
 }
 // Which of the phase's two texts runs here (lscqp_das_body.inc, LSCQP_DAS_FORM; its header says what the latency text does differently):
-// the M = 5 form and the M = 10, 2-D form run the latency text, with which they spill 161 and 220 scalar registers.  The rule of NOTES
+// the M = 5 form and the M = 10, 2-D form run the latency text, with which they spill 150 and 196 scalar registers (their units are
+// built without machine-level hoisting -- build.py: fused_flags, NOTES section 45; 161 and 220 with it).  The rule of NOTES
 // section 24 decided per form: a change stays where the scalar-register spills do not grow or a timing pays for the growth.  Any other
 // shape -- the M = 10, 3-D form -- keeps the throughput text: there the kernel-argument block costs scalar registers (306 SGPR spills
 // against 292), and so did the first-step setup ahead of the first step (301 - 312 against 292); it has not been built with the rest.

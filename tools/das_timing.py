@@ -37,7 +37,7 @@ if "--build-only" in sys.argv:
         fo = os.path.join(td, "lscqp_fused_timing.o")
         fdefs = ["-DLSCQP_%s=%d" % (k, v) for k, v in zip(("M", "DIM", "ES", "NSLOT", "W"), FUSED)]
         extra = os.environ.get("LSCQP_EXTRA_F64_FLAGS", "").split()
-        subprocess.check_call(["/opt/rocm/bin/hipcc"] + B.FLAGS + extra + fdefs + timing + ["-c", os.path.join(CSRC, "lscqp_fused.hip"), "-o", fo])
+        subprocess.check_call(["/opt/rocm/bin/hipcc"] + B.FLAGS + extra + fdefs + B.fused_flags(*FUSED[:2]) + timing + ["-c", os.path.join(CSRC, "lscqp_fused.hip"), "-o", fo])
         skip = {"lscqp_das.o", "fused_%d_%d_%d_%d_%d.o" % FUSED}
         objs = [f for f in glob.glob(os.path.join(CSRC, "_obj", "*.o")) if os.path.basename(f) not in skip and not f.endswith("_sync.o")] + [o, fo]
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + objs + ["-ldl", "-lpthread"])
