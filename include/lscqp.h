@@ -1478,11 +1478,14 @@ int lscqp_plan_set_obstacle_drives(lscqp_plan plan, const lscqp_obstacle_drive* 
  *                            makes each agent's list again from the offsets then in force); a sharded plan (n_agents != n_total);
  *                            constraint_mode LSCQP_GEN_BVC (LSCQP_ERR_UNSUPPORTED); together with a flight log, in either order
  *                            (LSCQP_ERR_UNSUPPORTED: the log's obstacle columns are those of one shared table).  Per replan the chain has
- *                            exactly the nodes of a plan with a shared table, the three entries above in place of their shared forms and
- *                            the row entries called with n_slot and the agents' own lists.  lscqp_plan_set_obstacle_drives,
+ *                            exactly the nodes of a plan with a shared table: the three entries above and the row entries called with
+ *                            n_slot and the agents' own lists.  (A plan keeps a shared table as the one-table case of this layout --
+ *                            offsets {0, n_dyn}, one clock word, every agent's list 0 .. n_dyn - 1 -- and moves it by the same entries;
+ *                            each of the three is one kernel text with its shared form, obstacle_advance_kernel<MIS>,
+ *                            obstacle_drive_kernel<MIS> and safety_obstacles_kernel<IDS>.)  lscqp_plan_set_obstacle_drives,
  *                            lscqp_plan_set_obstacle_record (its `obstacle` is then the slot), lscqp_plan_run, worlds and a patrol compose
  *                            unchanged.  LSCQP_PLAN_OBS_TABLE is [n_dyn_total], LSCQP_PLAN_OBS_CLOCK int32[n_missions].  A plan that never
- *                            makes this call enqueues the chain it always did node for node. */
+ *                            makes this call has the nodes, buffers and results it always had. */
 int lscqp_obstacles_advance_missions_device(lscqp_handle h, const lscqp_obstacle_model* d_models, int32_t n_missions,
                                             const int32_t* obstacle_offsets, const int32_t* d_obstacle_offsets, int32_t n_dyn_total,
                                             double time_step, int32_t* d_clock, lscqp_obstacle* d_obstacles, void* stream);

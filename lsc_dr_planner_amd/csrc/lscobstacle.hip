@@ -116,15 +116,17 @@ __host__ __device__ inline void spin_at(const lscqp_obstacle_model& m, double t,
     *vel = F3{(float)(m.spin_w * p.x), (float)(m.spin_w * p.y), (float)(m.spin_w * p.z)};
 }
 
-// One workgroup; thread i takes obstacles i, i + 64, ...  The clock word is read by every thread before the barrier and written by
-// thread 0 behind it.  t: r steps of ros::Duration(time_step) -- step_ns whole nanoseconds each -- then Duration::toSec().
-__global__ __launch_bounds__(kThreads) void obstacle_advance_kernel(const lscqp_obstacle_model* __restrict__ models, int n_dyn, int64_t step_ns,
-                                                                     int32_t* clock, lscqp_obstacle* __restrict__ table) {
+// t of replan r: r steps of ros::Duration(time_step) -- step_ns whole nanoseconds each -- then Duration::toSec()
+__host__ __device__ inline double clock_seconds(int32_t r, int64_t step_ns) {
 #pragma clang fp contract(off)
-    const int32_t r = *clock;
     const int64_t ns = (int64_t)r * step_ns;
-    const double t = (double)(ns / 1000000000LL) + 1e-9 * (double)(ns % 1000000000LL);
-    for (int oi = threadIdx.x; oi < n_dyn; oi += kThreads) {
+    return (double)(ns / 1000000000LL) + 1e-9 * (double)(ns % 1000000000LL);
+}
+
+// One slice of the table at time t: thread i takes entries i, i + 64, ...  HELD entries are not written.
+__device__ __forceinline__ void advance_slice(const lscqp_obstacle_model* __restrict__ models, lscqp_obstacle* __restrict__ table, int n, double t) {
+#pragma clang fp contract(off)
+    for (int oi = threadIdx.x; oi < n; oi += kThreads) {
         const lscqp_obstacle_model& m = models[oi];
         if (m.kind == LSCQP_OBSTACLE_HELD) continue;
         F3 p, v;
@@ -138,8 +140,22 @@ __global__ __launch_bounds__(kThreads) void obstacle_advance_kernel(const lscqp_
         o->type = 0;  // DYNAMICOBSTACLE (ObstacleBase::getObstacle)
         o->reserved = 0;
     }
+}
+
+// One workgroup per table.  MIS: the table is mission-major (include/lscqp.h, "a mission's own obstacles"), workgroup k advances the slice
+// [ooff[k], ooff[k + 1]) by the clock word clock[k] and reads or writes no word of another mission; a mission without obstacles still
+// counts its clock.  Otherwise: the one table of n_dyn entries and the one clock word.  The clock word is read by every thread before the
+// barrier and written by thread 0 behind it.
+template <bool MIS>
+__global__ __launch_bounds__(kThreads) void obstacle_advance_kernel(const lscqp_obstacle_model* __restrict__ models, const int32_t* __restrict__ ooff, int n_dyn,
+                                                                     int64_t step_ns, int32_t* clock, lscqp_obstacle* __restrict__ table) {
+#pragma clang fp contract(off)
+    const int k = MIS ? blockIdx.x : 0;
+    const int32_t r = clock[k];
+    const int base = MIS ? ooff[k] : 0, n = MIS ? ooff[k + 1] - base : n_dyn;
+    advance_slice(models + base, table + base, n, clock_seconds(r, step_ns));
     __syncthreads();
-    if (threadIdx.x == 0) *clock = r + 1;
+    if (threadIdx.x == 0) clock[k] = r + 1;
 }
 
 // ---- chasing and gaussian obstacles (include/lscqp.h, "chasing and gaussian obstacles"): ChasingObstacle::getChasingObstacle :313-363,
@@ -159,13 +175,6 @@ __host__ __device__ inline double norm3(D3 v) {
 struct Staged {
     double px, py, pz, radius;
 };
-
-// t of replan r as obstacle_advance_kernel forms it
-__host__ __device__ inline double clock_seconds(int32_t r, int64_t step_ns) {
-#pragma clang fp contract(off)
-    const int64_t ns = (int64_t)r * step_ns;
-    return (double)(ns / 1000000000LL) + 1e-9 * (double)(ns % 1000000000LL);
-}
 
 // getChasingObstacle with current_state = (own staged position, `vel`) and dt = t - t_last_called; goal: the goal point as point3d
 __host__ __device__ inline void chasing_step(const lscqp_obstacle_model& m, const lscqp_obstacle_drive& d, F3 goal, const Staged* prev, int n_dyn, int self,
@@ -274,79 +283,31 @@ __host__ __device__ inline void drive_entry(const lscqp_obstacle_model* models, 
     o->reserved = flags;
 }
 
-// One workgroup; thread i takes obstacles i, i + 64, ...  Every entry's previous position and radius go to LDS first (n_dyn Staged records
-// of dynamic LDS); behind the barrier the table is only written, and an entry's own velocity is read by the one thread that writes it.
-// The clock word is read, never written: the advance behind this kernel counts it.
+// One workgroup per table, as obstacle_advance_kernel takes them; thread i takes entries i, i + 64, ... of its table.  Every entry's previous
+// position and radius go to LDS first (dynamic LDS: the largest table's count of Staged records); behind the barrier the table is only
+// written, and an entry's own velocity is read by the one thread that writes it.  drive_entry gets the table's base pointers, count and local
+// index: a chaser sees the obstacles of its own table and no other.  target_agent stays a global id into `state`; the history table is one
+// for all.  The clock word is read, never written: the advance behind this kernel counts it.
+template <bool MIS>
 __global__ __launch_bounds__(kThreads) void obstacle_drive_kernel(const lscqp_obstacle_model* __restrict__ models, const lscqp_obstacle_drive* __restrict__ drives,
-                                                                   int n_dyn, const double* __restrict__ hist, int n_history, const double* __restrict__ state,
-                                                                   int64_t n_total, lscqp_obstacle_drive_state* __restrict__ ckpt, int64_t step_ns,
-                                                                   const int32_t* __restrict__ clock, lscqp_obstacle* table) {
+                                                                   const int32_t* __restrict__ ooff, int n_dyn, const double* __restrict__ hist, int n_history,
+                                                                   const double* __restrict__ state, int64_t n_total, lscqp_obstacle_drive_state* __restrict__ ckpt,
+                                                                   int64_t step_ns, const int32_t* __restrict__ clock, lscqp_obstacle* table) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) char drive_lds[];
     Staged* prev = (Staged*)drive_lds;
-    const int32_t r = *clock;
-    const double t = clock_seconds(r, step_ns), t_last = r > 0 ? clock_seconds(r - 1, step_ns) : 0.0;
-    for (int oi = threadIdx.x; oi < n_dyn; oi += kThreads)
-        prev[oi] = Staged{table[oi].position[0], table[oi].position[1], table[oi].position[2], table[oi].radius};
-    __syncthreads();
-    for (int oi = threadIdx.x; oi < n_dyn; oi += kThreads) drive_entry(models, drives, n_dyn, hist, n_history, state, n_total, ckpt, t, t_last, prev, oi, table);
-}
-
-constexpr size_t kDriveLdsMax = 64 * 1024;  // (2048 entries: far beyond lscqp_max_obstacles of any class)
-
-// ---- a table per mission (include/lscqp.h, "a mission's own obstacles"): the table is mission-major, mission k owns entries
-// [ooff[k], ooff[k + 1]) and the clock word clock[k].  One workgroup per mission does over its slice what the kernels above do over the
-// whole table, by the same functions; no workgroup reads or writes a word of another mission.
-
-// obstacle_advance_kernel over the slice of mission blockIdx.x.  A mission without obstacles still counts its clock.
-__global__ __launch_bounds__(kThreads) void obstacle_advance_missions_kernel(const lscqp_obstacle_model* __restrict__ models, const int32_t* __restrict__ ooff,
-                                                                              int64_t step_ns, int32_t* clock, lscqp_obstacle* __restrict__ table) {
-#pragma clang fp contract(off)
-    const int k = blockIdx.x;
-    const int32_t r = clock[k];
-    const int base = ooff[k], n_dyn = ooff[k + 1] - base;
-    const int64_t ns = (int64_t)r * step_ns;
-    const double t = (double)(ns / 1000000000LL) + 1e-9 * (double)(ns % 1000000000LL);
-    for (int oi = threadIdx.x; oi < n_dyn; oi += kThreads) {
-        const lscqp_obstacle_model& m = models[base + oi];
-        if (m.kind == LSCQP_OBSTACLE_HELD) continue;
-        F3 p, v;
-        if (m.kind == LSCQP_OBSTACLE_STRAIGHT) straight_at(m.leg[0], m.speed, m.max_acc, t, &p, &v);
-        else if (m.kind == LSCQP_OBSTACLE_PATROL) patrol_at(m, t, &p, &v);
-        else spin_at(m, t, &p, &v);
-        lscqp_obstacle* o = table + base + oi;
-        o->position[0] = (double)p.x, o->position[1] = (double)p.y, o->position[2] = (double)p.z;
-        o->velocity[0] = (double)v.x, o->velocity[1] = (double)v.y, o->velocity[2] = (double)v.z;
-        o->radius = m.radius, o->downwash = m.downwash, o->max_acc = m.max_acc;
-        o->type = 0;  // DYNAMICOBSTACLE (ObstacleBase::getObstacle)
-        o->reserved = 0;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) clock[k] = r + 1;
-}
-
-// obstacle_drive_kernel over the slice of mission blockIdx.x: its own entries go to LDS (the largest mission's count of Staged records),
-// and drive_entry gets the slice's base pointers, count and local index -- a chaser sees the obstacles of its own mission and no other.
-// target_agent stays a global id into `state`; the history table is one for all missions.  clock[k] is read, never written.
-__global__ __launch_bounds__(kThreads) void obstacle_drive_missions_kernel(const lscqp_obstacle_model* __restrict__ models,
-                                                                            const lscqp_obstacle_drive* __restrict__ drives, const int32_t* __restrict__ ooff,
-                                                                            const double* __restrict__ hist, int n_history, const double* __restrict__ state,
-                                                                            int64_t n_total, lscqp_obstacle_drive_state* __restrict__ ckpt, int64_t step_ns,
-                                                                            const int32_t* __restrict__ clock, lscqp_obstacle* table) {
-#pragma clang fp contract(off)
-    extern __shared__ __attribute__((aligned(16))) char drive_missions_lds[];
-    Staged* prev = (Staged*)drive_missions_lds;
-    const int k = blockIdx.x;
-    const int base = ooff[k], n_dyn = ooff[k + 1] - base;
+    const int k = MIS ? blockIdx.x : 0;
+    const int base = MIS ? ooff[k] : 0, n = MIS ? ooff[k + 1] - base : n_dyn;
     const int32_t r = clock[k];
     const double t = clock_seconds(r, step_ns), t_last = r > 0 ? clock_seconds(r - 1, step_ns) : 0.0;
     lscqp_obstacle* mine = table + base;
-    for (int oi = threadIdx.x; oi < n_dyn; oi += kThreads)
-        prev[oi] = Staged{mine[oi].position[0], mine[oi].position[1], mine[oi].position[2], mine[oi].radius};
+    for (int oi = threadIdx.x; oi < n; oi += kThreads) prev[oi] = Staged{mine[oi].position[0], mine[oi].position[1], mine[oi].position[2], mine[oi].radius};
     __syncthreads();
-    for (int oi = threadIdx.x; oi < n_dyn; oi += kThreads)
-        drive_entry(models + base, drives + base, n_dyn, hist, n_history, state, n_total, ckpt + base, t, t_last, prev, oi, mine);
+    for (int oi = threadIdx.x; oi < n; oi += kThreads)
+        drive_entry(models + base, drives + base, n, hist, n_history, state, n_total, ckpt + base, t, t_last, prev, oi, mine);
 }
+
+constexpr size_t kDriveLdsMax = 64 * 1024;  // (2048 entries: far beyond lscqp_max_obstacles of any class)
 
 // the offset list of a table per mission, as the host gives it: K + 1 values, non-decreasing from 0 to n_dyn_total, no mission with more
 // than lscqp_max_obstacles(h) entries.  *largest: the largest mission's count
@@ -362,6 +323,34 @@ inline int check_obstacle_offsets(lscqp_handle h, int32_t n_missions, const int3
     if (*largest > lscqp_max_obstacles(h) || (size_t)*largest * sizeof(Staged) > kDriveLdsMax)
         return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "a mission's obstacle count exceeds the largest compiled kernel instance of the shape (lscqp_max_obstacles)");
     return LSCQP_OK;
+}
+
+// behind an entry's checks: the device, the step in whole nanoseconds (ros::Duration(time_step)), one workgroup per table
+template <bool MIS>
+int launch_advance(const lscqp_obstacle_model* models, int n_tables, const int32_t* ooff, int n_dyn, double time_step, int32_t* clock, lscqp_obstacle* table,
+                   void* stream) {
+    if (const int rc = lscqp_need_device_()) return rc;
+    const int64_t step_ns = (int64_t)llround(time_step * 1e9);
+    hipLaunchKernelGGL(obstacle_advance_kernel<MIS>, dim3((unsigned)n_tables), dim3(kThreads), 0, (hipStream_t)stream, models, ooff, n_dyn, step_ns, clock, table);
+    return lscqp_launch_result_(hipGetLastError());
+}
+
+// (largest: the largest table's count, the Staged records of LDS)
+template <bool MIS>
+int launch_drive(const lscqp_obstacle_model* models, const lscqp_obstacle_drive* drives, int n_tables, const int32_t* ooff, int n_dyn, int largest,
+                 const double* hist, int n_history, const double* state, int64_t n_total, lscqp_obstacle_drive_state* ckpt, double time_step, const int32_t* clock,
+                 lscqp_obstacle* table, void* stream) {
+    if (const int rc = lscqp_need_device_()) return rc;
+    const int64_t step_ns = (int64_t)llround(time_step * 1e9);
+    hipLaunchKernelGGL(obstacle_drive_kernel<MIS>, dim3((unsigned)n_tables), dim3(kThreads), (size_t)largest * sizeof(Staged), (hipStream_t)stream, models, drives, ooff,
+                       n_dyn, hist, n_history, state, n_total, ckpt, step_ns, clock, table);
+    return lscqp_launch_result_(hipGetLastError());
+}
+
+// the buffers every drive entry needs once there is an entry to move
+inline bool drive_buffer_missing(const void* models, const void* drives, const double* hist, int32_t n_history, const double* state, int64_t n_total, const void* ckpt,
+                                 const void* clock, const void* table) {
+    return !models || !drives || !ckpt || !clock || !table || (n_history > 0 && !hist) || (n_total > 0 && !state);
 }
 
 inline int refuse_drive(int i, const char* what) {
@@ -384,8 +373,7 @@ inline int drive_args(lscqp_handle h, const void* models, const void* drives, in
         *empty = true;
         return LSCQP_OK;
     }
-    if (!models || !drives || !ckpt || !clock || !table || (n_history > 0 && !hist) || (n_total > 0 && !state))
-        return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
+    if (drive_buffer_missing(models, drives, hist, n_history, state, n_total, ckpt, clock, table)) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
     return LSCQP_OK;
 }
 
@@ -489,11 +477,7 @@ extern "C" int lscqp_obstacles_advance_device(lscqp_handle h, const lscqp_obstac
         return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "n_dyn exceeds the largest compiled kernel instance of the shape (lscqp_max_obstacles)");
     if (n_dyn == 0) return LSCQP_OK;
     if (!d_models || !d_clock || !d_obstacles) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (const int rc = lscqp_need_device_()) return rc;
-    const int64_t step_ns = (int64_t)llround(time_step * 1e9);  // ros::Duration(time_step): whole nanoseconds
-    hipLaunchKernelGGL(lscobstacle::obstacle_advance_kernel, dim3(1), dim3(lscobstacle::kThreads), 0, (hipStream_t)stream, d_models, (int)n_dyn, step_ns,
-                       d_clock, d_obstacles);
-    return lscqp_launch_result_(hipGetLastError());
+    return lscobstacle::launch_advance<false>(d_models, 1, nullptr, n_dyn, time_step, d_clock, d_obstacles, stream);
 }
 
 extern "C" int lscqp_obstacle_drive_check(const lscqp_obstacle_model* models, const lscqp_obstacle_drive* drives, int32_t n, int32_t n_history,
@@ -535,11 +519,8 @@ extern "C" int lscqp_obstacles_drive_device(lscqp_handle h, const lscqp_obstacle
                                                d_obstacles, &empty))
         return rc;
     if (empty) return LSCQP_OK;
-    if (const int rc = lscqp_need_device_()) return rc;
-    const int64_t step_ns = (int64_t)llround(time_step * 1e9);  // ros::Duration(time_step): whole nanoseconds
-    hipLaunchKernelGGL(lscobstacle::obstacle_drive_kernel, dim3(1), dim3(lscobstacle::kThreads), (size_t)n_dyn * sizeof(lscobstacle::Staged), (hipStream_t)stream,
-                       d_models, d_drives, (int)n_dyn, d_acc_history, (int)n_history, d_state, n_total, d_drive_state, step_ns, d_clock, d_obstacles);
-    return lscqp_launch_result_(hipGetLastError());
+    return lscobstacle::launch_drive<false>(d_models, d_drives, 1, nullptr, n_dyn, n_dyn, d_acc_history, n_history, d_state, n_total, d_drive_state, time_step, d_clock,
+                                            d_obstacles, stream);
 }
 
 extern "C" int lscqp_obstacle_drive_host(lscqp_handle h, const lscqp_obstacle_model* models, const lscqp_obstacle_drive* drives, int32_t n_dyn,
@@ -571,11 +552,7 @@ extern "C" int lscqp_obstacles_advance_missions_device(lscqp_handle h, const lsc
     if (const int rc = lscobstacle::check_obstacle_offsets(h, n_missions, obstacle_offsets, n_dyn_total, &largest)) return rc;
     // (a partition none of whose missions has an obstacle still counts its clocks: no table is asked for)
     if (!d_obstacle_offsets || !d_clock || (n_dyn_total > 0 && (!d_models || !d_obstacles))) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (const int rc = lscqp_need_device_()) return rc;
-    const int64_t step_ns = (int64_t)llround(time_step * 1e9);  // ros::Duration(time_step): whole nanoseconds
-    hipLaunchKernelGGL(lscobstacle::obstacle_advance_missions_kernel, dim3((unsigned)n_missions), dim3(lscobstacle::kThreads), 0, (hipStream_t)stream, d_models,
-                       d_obstacle_offsets, step_ns, d_clock, d_obstacles);
-    return lscqp_launch_result_(hipGetLastError());
+    return lscobstacle::launch_advance<true>(d_models, n_missions, d_obstacle_offsets, n_dyn_total, time_step, d_clock, d_obstacles, stream);
 }
 
 extern "C" int lscqp_obstacles_drive_missions_device(lscqp_handle h, const lscqp_obstacle_model* d_models, const lscqp_obstacle_drive* d_drives,
@@ -591,12 +568,8 @@ extern "C" int lscqp_obstacles_drive_missions_device(lscqp_handle h, const lscqp
     int32_t largest = 0;
     if (const int rc = lscobstacle::check_obstacle_offsets(h, n_missions, obstacle_offsets, n_dyn_total, &largest)) return rc;
     if (n_dyn_total == 0) return LSCQP_OK;  // (nothing to move, and the clocks are the advance's to count)
-    if (!d_obstacle_offsets || !d_models || !d_drives || !d_drive_state || !d_clock || !d_obstacles || (n_history > 0 && !d_acc_history) || (n_total > 0 && !d_state))
+    if (!d_obstacle_offsets || lscobstacle::drive_buffer_missing(d_models, d_drives, d_acc_history, n_history, d_state, n_total, d_drive_state, d_clock, d_obstacles))
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "null buffer");
-    if (const int rc = lscqp_need_device_()) return rc;
-    const int64_t step_ns = (int64_t)llround(time_step * 1e9);  // ros::Duration(time_step): whole nanoseconds
-    hipLaunchKernelGGL(lscobstacle::obstacle_drive_missions_kernel, dim3((unsigned)n_missions), dim3(lscobstacle::kThreads),
-                       (size_t)largest * sizeof(lscobstacle::Staged), (hipStream_t)stream, d_models, d_drives, d_obstacle_offsets, d_acc_history, (int)n_history,
-                       d_state, n_total, d_drive_state, step_ns, d_clock, d_obstacles);
-    return lscqp_launch_result_(hipGetLastError());
+    return lscobstacle::launch_drive<true>(d_models, d_drives, n_missions, d_obstacle_offsets, n_dyn_total, largest, d_acc_history, n_history, d_state, n_total,
+                                           d_drive_state, time_step, d_clock, d_obstacles, stream);
 }

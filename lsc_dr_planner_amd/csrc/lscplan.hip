@@ -29,8 +29,10 @@
 // rows -- they take the first row slots of every agent -- and the obstacle leg of the safety figures behind the agents'.
 // ObstacleGenerator::update(t, 0) -> obstacle_advance_kernel, src/multi_sync_simulator.cpp:311.
 // A partition whose missions have obstacles of their own (lscqp_plan_set_mission_obstacles: one mission-major table, a clock per mission) has
-// the same nodes in the same places, the motion and the safety leg in their per-mission forms (obstacle_advance_missions_kernel,
-// obstacle_drive_missions_kernel, safety_obstacles_ids_kernel) and the row entries called with every agent's own list of table indices.
+// the same nodes in the same places, and the same kernels: the plan keeps its obstacles as T tables with a clock each and every agent's own list
+// of table indices, one shared table being T = 1, and enqueues obstacle_advance_kernel<true>, obstacle_drive_kernel<true> over the T tables
+// and the row entries over the lists; the safety leg is safety_obstacles_kernel<true> over the lists, <false> over the one table that is
+// everybody's (enqueue_obstacle_safety).
 // A plan that flies a patrol (lscqp_plan_set_patrol) gains the transition node directly behind the waypoint decision -- the reference decides the
 // waypoints over the old goals, then every agent swaps start and goal on arrival at the top of its plan() -- and, with a grid, the node that
 // exchanges the turned agents' distance fields behind it (lscpatrol.hip).
@@ -284,23 +286,20 @@ struct lscqp_plan_s {
         int32_t log_capacity = 0;  // the flight log's rows per mission (lscqp_plan_set_flight_log), 0 = none: given to every record made
         bool obstacle_figures = false;  // the obstacle record (lscqp_plan_set_obstacle_record): every record made reads obs.safety
     } rec;
-    // dynamic obstacles (lscqp_plan_set_obstacles): n_dyn = 0 = none, the chain as it always was.  They take row slots [0, n_dyn) of every agent
+    // dynamic obstacles (lscqp_plan_set_obstacles, lscqp_plan_set_mission_obstacles): n_dyn = 0 = none, the chain as it always was.  The table
+    // holds T tables one behind the other, table k the entries [ooff[k], ooff[k + 1]) with the clock word clock[k], n_dyn in all; the largest
+    // one's count, n_slot, is the row slots [0, n_slot) the obstacles take of every agent, and ids [n_agents][n_slot] names every local
+    // agent's entries by table index (-1: none).  One table shared by all agents is T = 1: offsets {0, n_dyn}, every agent's ids 0 .. n_dyn - 1
     struct Obstacles {
-        int32_t n_dyn = 0;
+        int32_t n_dyn = 0, n_slot = 0, n_tables = 0;  // (n_tables: T, the tables and their clocks)
         lscqp_obstacle_param param = {};
         std::vector<lscqp_obstacle_model> models;  // prepared; HELD entries start at `start`
         dev_ptr<lscqp_obstacle_model> d_models;
         dev_ptr<lscqp_obstacle> table;
-        dev_ptr<int32_t> ids, clock;  // ids: 0 .. n_dyn - 1 for every local agent
+        dev_ptr<int32_t> ids, clock, d_ooff;
         dev_ptr<lscqp_safety_obs> safety;
-        // a table per mission (lscqp_plan_set_mission_obstacles): ooff empty = one shared table, the chain as it always was.  Else the table
-        // is mission-major, n_dyn its total, n_slot = the largest mission's count the row slots [0, n_slot) of every agent, ids [n_agents][n_slot]
-        // table indices (-1: none) and clock one word per mission
-        int32_t n_slot = 0;  // row slots the obstacles take: n_dyn of a shared table
-        std::vector<int32_t> ooff;  // [K + 1]
-        dev_ptr<int32_t> d_ooff;
-        bool per_mission() const { return !ooff.empty(); }
-        int n_clocks() const { return ooff.empty() ? 1 : (int)ooff.size() - 1; }
+        std::vector<int32_t> ooff;  // [T + 1]
+        bool per_mission = false;   // table k belongs to mission k (lscqp_plan_set_mission_obstacles); else the one table is everybody's
         // the drives of chasing and gaussian obstacles (lscqp_plan_set_obstacle_drives): d_drives = NULL = none, the chain as it always was
         struct Drives {
             dev_ptr<lscqp_obstacle_drive> d_drives;
@@ -361,6 +360,20 @@ int dalloc_pub(lscqp_plan_s* p, int which, size_t count) {
         if (rc_ != LSCQP_OK) return rc_; \
     } while (0)
 
+// The obstacle leg of the safety figures.  The by-ids entry over every agent's list serves every plan, bit for bit; the one table that is
+// everybody's takes the whole-table instantiation of the same kernel text instead, here and nowhere else: with 250 agents its replan measured
+// 3 to 4 us (1 %) more by ids, a list read per lane where the one table's addresses are uniform (NOTES.md section 46).  The motion's two nodes
+// showed no such cost and take the per-mission entries over one table.
+int enqueue_obstacle_safety(const lscqp_plan_s* p, const double* x_plan, hipStream_t stream) {
+    const lscqp_plan_s::Obstacles& o = p->obs;
+    const lscplan::Shape& s = p->s;
+    if (!o.per_mission)
+        return lscqp_safety_obstacles_device(p->h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan, p->radius,
+                                             p->downwash, o.n_dyn, o.table.get(), o.safety.get(), stream);
+    return lscqp_safety_obstacles_ids_device(p->h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan, p->radius,
+                                             p->downwash, o.n_slot, o.ids.get(), o.n_dyn, o.table.get(), o.safety.get(), stream);
+}
+
 // the whole replan on `stream`; nothing here synchronises, allocates or touches host memory (capturable)
 int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     const lscplan::Shape& s = p->s;
@@ -387,9 +400,8 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     const lscqp_plan_s::Obstacles& obs = p->obs;
     lscqp_grid grid = wp.grid.get();
     const int64_t *moff = p->mis.moff.data(), *d_moff = p->mis.d_moff.get();
-    // row slots [0, n_slot): the obstacles, [n_slot, n_obs): the in-range agents (n_slot = n_dyn unless every mission has its own table)
+    // row slots [0, n_slot): the obstacles, [n_slot, n_obs): the in-range agents (n_slot: the largest table's count, n_dyn of one table)
     const int32_t n_dyn = obs.n_dyn, n_slot = obs.n_slot, n_nbr = s.n_obs - n_slot;
-    const bool own_tables = obs.per_mission();
     // decentralizedMAPP precedes the planning loop (src/multi_sync_simulator.cpp:101-120): the waypoints of this replan, from the plans as the
     // last replan left them (AgentManager::getTraj is desired_traj, un-shifted)
     if (grid) {
@@ -415,17 +427,14 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     }
     // obstacle_generator.update(t, 0) at the replan's start time (src/multi_sync_simulator.cpp:311); the clock is the device's.  Chasing and
     // gaussian obstacles first: they read the table as the last replan left it, and the agents' states of this replan's start
-    if (own_tables && obs.drv.d_drives)
-        PLAN_TRY(lscqp_obstacles_drive_missions_device(h, obs.d_models.get(), obs.drv.d_drives.get(), obs.n_clocks(), obs.ooff.data(), obs.d_ooff.get(), n_dyn,
+    // (one table is the entries' one-table case)
+    if (n_dyn > 0 && obs.drv.d_drives)
+        PLAN_TRY(lscqp_obstacles_drive_missions_device(h, obs.d_models.get(), obs.drv.d_drives.get(), obs.n_tables, obs.ooff.data(), obs.d_ooff.get(), n_dyn,
                                                        obs.drv.history.get(), obs.drv.n_history, state, s.n_total, obs.drv.state.get(), p->d.time_step,
                                                        obs.clock.get(), obs.table.get(), stream));
-    else if (n_dyn > 0 && obs.drv.d_drives)
-        PLAN_TRY(lscqp_obstacles_drive_device(h, obs.d_models.get(), obs.drv.d_drives.get(), n_dyn, obs.drv.history.get(), obs.drv.n_history, state, s.n_total,
-                                              obs.drv.state.get(), p->d.time_step, obs.clock.get(), obs.table.get(), stream));
-    if (own_tables)
-        PLAN_TRY(lscqp_obstacles_advance_missions_device(h, obs.d_models.get(), obs.n_clocks(), obs.ooff.data(), obs.d_ooff.get(), n_dyn, p->d.time_step,
+    if (n_dyn > 0)
+        PLAN_TRY(lscqp_obstacles_advance_missions_device(h, obs.d_models.get(), obs.n_tables, obs.ooff.data(), obs.d_ooff.get(), n_dyn, p->d.time_step,
                                                          obs.clock.get(), obs.table.get(), stream));
-    else if (n_dyn > 0) PLAN_TRY(lscqp_obstacles_advance_device(h, obs.d_models.get(), n_dyn, p->d.time_step, obs.clock.get(), obs.table.get(), stream));
     // obstaclePredictionWithPrevSol / initialTrajPlanningPrevSol for every agent of the mission (:273-310, 399-423)
     const bool from_plans = !first_replan && (s.prediction_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION || s.initial_traj_mode == LSCQP_TRAJ_FROM_PREVIOUS_SOLUTION);
     const bool whole_shift = from_plans && fraction >= 1.0 - 1e-9;  // (done by prepare_kernel itself)
@@ -458,13 +467,10 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
     // the obstacles' rows (the non-agent branch of the plan's generator) over the planning agents' INITIAL trajectories: `own`, indexed by
     // local id like the radii, goals and headers handed over here -- `traj` holds the agents' predictions as each other's obstacles by now.
     // generateCLSC's rows take no obstacle goal points: Obstacle::goal_point is the origin in the reference (include/obstacle.hpp:23, 37-49)
-    // (a table per mission: the same entries over n_slot slots, the ids naming each agent's own entries -- a slot without one gets zero rows)
-    if (n_dyn > 0 && p->d.constraint_mode == LSCQP_GEN_CLSC)
-        PLAN_TRY(lscqp_generate_obstacle_rows_device(h, LSCQP_GEN_CLSC, &obs.param, s.n_agents, n_slot, 0, p->own, obs.ids.get(), obs.table.get(), nullptr,
-                                                     p->radius + s.first_agent, goal + s.first_agent * 3, nullptr, rows, s.n_obs, 0, stream));
-    else if (n_dyn > 0)
-        PLAN_TRY(lscqp_generate_lsc_obstacles_device(h, &obs.param, s.n_agents, n_slot, 0, p->own, obs.ids.get(), obs.table.get(), p->radius + s.first_agent,
-                                                     goal + s.first_agent * 3, hdr, rows, s.n_obs, 0, stream));
+    // (n_slot slots, the ids naming each agent's own entries -- a slot without one gets zero rows; only the LSC rows read the headers)
+    if (n_dyn > 0)
+        PLAN_TRY(lscqp_generate_obstacle_rows_device(h, p->d.constraint_mode, &obs.param, s.n_agents, n_slot, 0, p->own, obs.ids.get(), obs.table.get(), nullptr,
+                                                     p->radius + s.first_agent, goal + s.first_agent * 3, hdr, rows, s.n_obs, 0, stream));
     if (p->d.optimize_goal) {  // (the goal LP's kernel finishes the headers itself: one node less)
         PLAN_TRY(lscqp_optimize_goal_fin_device_(h, s.n_agents, hdr, rows, p->off, p->map ? sfc : nullptr, goal_status, s.dt, stream));
     } else {
@@ -496,12 +502,7 @@ int enqueue(lscqp_plan_s* p, bool first_replan, hipStream_t stream) {
         PLAN_TRY(lscqp_safety_metrics_device(h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan,
                                              p->radius, p->downwash, hdr, (lscqp_safety*)p->buf[LSCQP_PLAN_BUF_SAFETY], stream));
     // the obstacle leg of the safety figures (:527-557), against the positions this replan's advance left
-    if (p->d.safety_samples > 0 && own_tables)
-        PLAN_TRY(lscqp_safety_obstacles_ids_device(h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan, p->radius,
-                                                   p->downwash, n_slot, obs.ids.get(), n_dyn, obs.table.get(), obs.safety.get(), stream));
-    else if (p->d.safety_samples > 0 && n_dyn > 0)
-        PLAN_TRY(lscqp_safety_obstacles_device(h, s.n_agents, s.first_agent, s.n_total, p->d.safety_samples, p->d.record_time_step, s.z_2d, x_plan, p->radius,
-                                               p->downwash, n_dyn, obs.table.get(), obs.safety.get(), stream));
+    if (p->d.safety_samples > 0 && n_dyn > 0) PLAN_TRY(enqueue_obstacle_safety(p, x_plan, stream));
     // the mission record: the figures of this replan and the finish test on the state it started from (hdr.p0), the chain's last node (a
     // record with a flight log enqueues the log's node in front of its own)
     if (p->rec.on)
@@ -545,7 +546,7 @@ int reset_obstacles(const lscqp_plan_s::Obstacles& o) {
         tab[(size_t)i].radius = m.radius, tab[(size_t)i].downwash = m.downwash, tab[(size_t)i].max_acc = m.max_acc;
     }
     hipError_t e = hipMemcpy(o.table.get(), tab.data(), tab.size() * sizeof(lscqp_obstacle), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(o.clock.get(), 0, (size_t)o.n_clocks() * sizeof(int32_t));  // (a table per mission: a clock per mission)
+    if (e == hipSuccess) e = hipMemset(o.clock.get(), 0, (size_t)o.n_tables * sizeof(int32_t));
     if (e == hipSuccess && o.drv.d_drives) e = hipMemset(o.drv.state.get(), 0, (size_t)o.n_dyn * sizeof(lscqp_obstacle_drive_state));
     return e == hipSuccess ? LSCQP_OK : hip_fail(e, "plan reset (obstacles)");
 }
@@ -555,15 +556,20 @@ std::vector<int64_t> mission_offsets_of(const lscqp_plan_s* p) {
     return p->mis.moff.empty() ? std::vector<int64_t>{0, p->s.n_total} : p->mis.moff;
 }
 
-// ids [n_agents][n_slot] of a table per mission, for the partition `moff`: agent a of mission k names ooff[k] + o in slot o < count_k, -1 beyond
-int upload_mission_ids(const lscqp_plan_s::Obstacles& o, const std::vector<int64_t>& moff, int64_t n_agents) {
+// whose table is whose, as offsets over the local agents: the partition in force where table k belongs to mission k, else [0, n_agents]
+std::vector<int64_t> table_owners_of(const lscqp_plan_s* p, bool per_mission) {
+    return per_mission ? mission_offsets_of(p) : std::vector<int64_t>{0, p->s.n_agents};
+}
+
+// ids [n_agents][n_slot]: agent a of owners' block k names ooff[k] + j in slot j < count_k, -1 beyond
+int upload_mission_ids(const lscqp_plan_s::Obstacles& o, const std::vector<int64_t>& owners, int64_t n_agents) {
     const size_t ns = (size_t)o.n_slot;
     std::vector<int32_t> hid((size_t)(n_agents ? n_agents : 1) * ns, -1);
-    for (size_t k = 0; k + 1 < moff.size(); k++)
-        for (int64_t a = moff[k]; a < moff[k + 1]; a++)
+    for (size_t k = 0; k + 1 < owners.size(); k++)
+        for (int64_t a = owners[k]; a < owners[k + 1]; a++)
             for (int32_t j = 0; j < o.ooff[k + 1] - o.ooff[k]; j++) hid[(size_t)a * ns + (size_t)j] = o.ooff[k] + j;
     const hipError_t e = hipMemcpy(o.ids.get(), hid.data(), hid.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    return e == hipSuccess ? LSCQP_OK : hip_fail(e, "lscqp_plan_set_mission_obstacles (ids)");
+    return e == hipSuccess ? LSCQP_OK : hip_fail(e, o.per_mission ? "lscqp_plan_set_mission_obstacles (ids)" : "lscqp_plan_set_obstacles");
 }
 
 // a chaser of a table per mission follows an agent of the mission that owns it (target_agent >= 0), or a goal point
@@ -647,6 +653,51 @@ int make_record(lscqp_plan_s* p, const lscqp_record_desc& desc) {
     if (p->rec.obstacle_figures) PLAN_TRY(lscqp_record_set_obstacle_figures(made.get(), p->obs.safety.get()));
     drop_graph(p);  // (a captured chain holds the old record's buffers)
     p->rec.held = std::move(made);
+    return LSCQP_OK;
+}
+
+// The plan's obstacles, new: n_tables tables by their offsets (n_tables = 0: none), `prepared` their models, table k mission k's own
+// (per_mission) or the one table everybody's.  `what` names the setter.  Everything that can fail comes before the plan changes
+int set_obstacle_tables(lscqp_plan_s* p, const char* what, const lscqp_obstacle_param* param, int32_t n_tables, const int32_t* offsets,
+                        std::vector<lscqp_obstacle_model>& prepared, bool per_mission) {
+    OnDevice on(p->device);
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, what);
+    const bool none = n_tables == 0;
+    lscqp_plan_s::Obstacles next;  // (none: empty)
+    if (!none) {
+        const size_t n = (size_t)p->s.n_agents, T = (size_t)n_tables;
+        next.ooff.assign(offsets, offsets + T + 1);
+        next.n_tables = n_tables, next.n_dyn = offsets[T], next.per_mission = per_mission;
+        for (size_t k = 0; k < T; k++) next.n_slot = std::max(next.n_slot, offsets[k + 1] - offsets[k]);
+        const size_t nd = (size_t)next.n_dyn;
+        PLAN_TRY(lscqp::dev_alloc(next.d_models, nd, what));
+        PLAN_TRY(lscqp::dev_alloc(next.table, nd, what));
+        PLAN_TRY(lscqp::dev_alloc(next.ids, (n ? n : 1) * (size_t)next.n_slot, what));
+        PLAN_TRY(lscqp::dev_alloc(next.clock, T, what));
+        PLAN_TRY(lscqp::dev_alloc(next.d_ooff, T + 1, what));
+        PLAN_TRY(lscqp::dev_alloc(next.safety, n ? n : 1, what, true));
+        e = hipMemcpy(next.d_models.get(), prepared.data(), nd * sizeof(lscqp_obstacle_model), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(next.d_ooff.get(), offsets, (T + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, what);
+        PLAN_TRY(upload_mission_ids(next, table_owners_of(p, per_mission), p->s.n_agents));
+        next.models.swap(prepared);
+        next.param = *param;
+        PLAN_TRY(reset_obstacles(next));  // (so that the table can be read, and HELD entries written, before the reset)
+    }
+    // (a flight log has the obstacles' columns and reads their table: a new log for the new ones, before the plan changes)
+    if (p->rec.held && p->rec.log_capacity > 0) PLAN_TRY(give_log(p->rec.held.get(), p->rec.log_capacity, next));
+    // (an obstacle record reads the obstacles' safety buffer: the new one, or none -- it goes with the obstacles)
+    if (p->rec.held && p->rec.obstacle_figures) PLAN_TRY(lscqp_record_set_obstacle_figures(p->rec.held.get(), none ? nullptr : next.safety.get()));
+    if (none) {
+        p->rec.obstacle_figures = false;
+        p->pending &= ~lscplan::kPendObstacleRecord;
+    }
+    drop_graph(p);  // (a captured chain holds the obstacles' nodes and the slot split)
+    p->obs = std::move(next);
+    // (the drives, and the other setter's obstacles, went with the old ones)
+    p->pending &= ~(lscplan::kPendObstacles | lscplan::kPendMissionObstacles | lscplan::kPendDrives);
+    if (!none) p->pending |= per_mission ? lscplan::kPendMissionObstacles : lscplan::kPendObstacles;
     return LSCQP_OK;
 }
 
@@ -872,9 +923,9 @@ int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* 
     if (p->wp.grid && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "waypoint_mode = LSCQP_WAYPOINT_GRID_PIBT: the mission's goal points are required");
     if (p->rec.on && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_record: the mission's goal points are required (the desired goals of the finish test)");
     if (p->pat.on && !goal_points) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_patrol: the mission's goal points are required (the far end of every leg)");
-    if (p->obs.per_mission()) {  // a table per mission: of the partition in force, and every chaser after an agent of its own mission
-        if (p->obs.n_clocks() != p->n_missions())
-            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, ("lscqp_plan_set_mission_obstacles: " + std::to_string(p->obs.n_clocks()) + " obstacle tables for " +
+    if (p->obs.per_mission) {  // a table per mission: of the partition in force, and every chaser after an agent of its own mission
+        if (p->obs.n_tables != p->n_missions())
+            return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, ("lscqp_plan_set_mission_obstacles: " + std::to_string(p->obs.n_tables) + " obstacle tables for " +
                                                                  std::to_string(p->n_missions()) + " missions: one table per mission of the partition in force required").c_str());
         if (!p->obs.drv.host.empty()) PLAN_TRY(check_chasers_stay_home(p->obs, p->obs.drv.host.data(), mission_offsets_of(p)));
     }
@@ -926,10 +977,10 @@ int lscqp_plan_reset(lscqp_plan p, const double* start_positions, const double* 
         if (p->pat.on) std::fill(want.begin(), want.end(), (double)INFINITY);
         PLAN_TRY(lscqp_record_reset(p->rec.held.get(), want.data()));
     }
-    if (p->obs.per_mission()) {  // the partition may have other offsets by now (never another count): each agent's own entries again
-        PLAN_TRY(upload_mission_ids(p->obs, mission_offsets_of(p), s.n_agents));
+    if (p->obs.n_dyn > 0) {  // the partition may have other offsets by now (never another count): each agent's own entries again
+        PLAN_TRY(upload_mission_ids(p->obs, table_owners_of(p, p->obs.per_mission), s.n_agents));
+        PLAN_TRY(reset_obstacles(p->obs));
     }
-    if (p->obs.n_dyn > 0) PLAN_TRY(reset_obstacles(p->obs));
     p->pending = 0;
     p->first = true;
     p->steps = 0;
@@ -1022,9 +1073,9 @@ int lscqp_plan_set_missions(lscqp_plan p, int32_t n_missions, const int64_t* mis
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
                                 ("lscqp_plan_set_missions: the plan has " + std::to_string(lscqp_worlds_count_(p->wld.set)) +
                                  " worlds (lscqp_plan_set_worlds), one per mission: another mission count needs other worlds, or none, first").c_str());
-    if (p->obs.per_mission() && (single ? 1 : n_missions) != p->obs.n_clocks())
+    if (p->obs.per_mission && (single ? 1 : n_missions) != p->obs.n_tables)
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT,
-                                ("lscqp_plan_set_missions: the plan has " + std::to_string(p->obs.n_clocks()) +
+                                ("lscqp_plan_set_missions: the plan has " + std::to_string(p->obs.n_tables) +
                                  " obstacle tables (lscqp_plan_set_mission_obstacles), one per mission: another mission count needs other obstacles, or none, first").c_str());
     if (!single) {
         if (p->s.n_agents != p->s.n_total)
@@ -1180,7 +1231,7 @@ int lscqp_plan_set_flight_log(lscqp_plan p, int32_t max_replans) {
     if (max_replans < 0) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_flight_log: max_replans >= 0 required");
     if (!p->rec.on)
         return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_flight_log: the plan has no record (lscqp_plan_set_record first): the log is part of it");
-    if (max_replans > 0 && p->obs.per_mission())
+    if (max_replans > 0 && p->obs.per_mission)
         return lscqp_set_error_(LSCQP_ERR_UNSUPPORTED, "lscqp_plan_set_flight_log: the plan has a table of obstacles per mission (lscqp_plan_set_mission_obstacles); the log's obstacle columns are those of one shared table");
     OnDevice on(p->device);
     const hipError_t e = hipDeviceSynchronize();
@@ -1224,42 +1275,8 @@ int lscqp_plan_set_obstacles(lscqp_plan p, const lscqp_obstacle_param* param, in
         prepared.assign(models, models + n_dyn);
         PLAN_TRY(lscqp_obstacle_model_prepare(prepared.data(), n_dyn));
     }
-    OnDevice on(p->device);
-    hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, "lscqp_plan_set_obstacles");
-    lscqp_plan_s::Obstacles next;  // (none: empty)
-    if (!none) {  // (everything that can fail comes before the plan changes)
-        const size_t n = (size_t)p->s.n_agents, nd = (size_t)n_dyn;
-        std::vector<int32_t> hid((n ? n : 1) * nd);
-        for (size_t a = 0; a < n; a++)
-            for (size_t o = 0; o < nd; o++) hid[a * nd + o] = (int32_t)o;
-        const char* const what = "lscqp_plan_set_obstacles";
-        PLAN_TRY(lscqp::dev_alloc(next.d_models, nd, what));
-        PLAN_TRY(lscqp::dev_alloc(next.table, nd, what));
-        PLAN_TRY(lscqp::dev_alloc(next.ids, hid.size(), what));
-        PLAN_TRY(lscqp::dev_alloc(next.clock, 1, what));
-        PLAN_TRY(lscqp::dev_alloc(next.safety, n ? n : 1, what, true));
-        e = hipMemcpy(next.d_models.get(), prepared.data(), nd * sizeof(lscqp_obstacle_model), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(next.ids.get(), hid.data(), hid.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_fail(e, what);
-        next.models.swap(prepared);
-        next.param = *param;
-        next.n_dyn = next.n_slot = n_dyn;
-        PLAN_TRY(reset_obstacles(next));  // (so that the table can be read, and HELD entries written, before the reset)
-    }
-    // (a flight log has the obstacles' columns and reads their table: a new log for the new ones, before the plan changes)
-    if (p->rec.held && p->rec.log_capacity > 0) PLAN_TRY(give_log(p->rec.held.get(), p->rec.log_capacity, next));
-    // (an obstacle record reads the obstacles' safety buffer: the new one, or none -- it goes with the obstacles)
-    if (p->rec.held && p->rec.obstacle_figures) PLAN_TRY(lscqp_record_set_obstacle_figures(p->rec.held.get(), none ? nullptr : next.safety.get()));
-    if (none) {
-        p->rec.obstacle_figures = false;
-        p->pending &= ~lscplan::kPendObstacleRecord;
-    }
-    drop_graph(p);  // (a captured chain holds the obstacles' nodes and the slot split)
-    p->obs = std::move(next);
-    p->pending = none ? p->pending & ~lscplan::kPendObstacles : p->pending | lscplan::kPendObstacles;
-    p->pending &= ~(lscplan::kPendDrives | lscplan::kPendMissionObstacles);  // (the drives, and a table per mission, went with the old obstacles)
-    return LSCQP_OK;
+    const int32_t offsets[2] = {0, n_dyn};  // (one table, everybody's)
+    return set_obstacle_tables(p, "lscqp_plan_set_obstacles", param, none ? 0 : 1, offsets, prepared, false);
 }
 
 int lscqp_plan_set_mission_obstacles(lscqp_plan p, const lscqp_obstacle_param* param, int32_t n_missions, const int32_t* obstacle_offsets,
@@ -1293,34 +1310,7 @@ int lscqp_plan_set_mission_obstacles(lscqp_plan p, const lscqp_obstacle_param* p
     const int32_t n_dyn = obstacle_offsets[n_missions];
     std::vector<lscqp_obstacle_model> prepared(models, models + n_dyn);
     PLAN_TRY(lscqp_obstacle_model_prepare(prepared.data(), n_dyn));
-    OnDevice on(p->device);
-    hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) return hip_fail(e, what);
-    lscqp_plan_s::Obstacles next;
-    {   // (everything that can fail comes before the plan changes)
-        const size_t n = (size_t)p->s.n_agents, nd = (size_t)n_dyn, K = (size_t)n_missions;
-        next.ooff.assign(obstacle_offsets, obstacle_offsets + K + 1);
-        next.n_dyn = n_dyn, next.n_slot = n_slot;
-        PLAN_TRY(lscqp::dev_alloc(next.d_models, nd, what));
-        PLAN_TRY(lscqp::dev_alloc(next.table, nd, what));
-        PLAN_TRY(lscqp::dev_alloc(next.ids, (n ? n : 1) * (size_t)n_slot, what));
-        PLAN_TRY(lscqp::dev_alloc(next.clock, K, what));
-        PLAN_TRY(lscqp::dev_alloc(next.d_ooff, K + 1, what));
-        PLAN_TRY(lscqp::dev_alloc(next.safety, n ? n : 1, what, true));
-        e = hipMemcpy(next.d_models.get(), prepared.data(), nd * sizeof(lscqp_obstacle_model), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(next.d_ooff.get(), obstacle_offsets, (K + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_fail(e, what);
-        PLAN_TRY(upload_mission_ids(next, mission_offsets_of(p), p->s.n_agents));
-        next.models.swap(prepared);
-        next.param = *param;
-        PLAN_TRY(reset_obstacles(next));  // (so that the table can be read, and HELD entries written, before the reset)
-    }
-    // (an obstacle record reads the obstacles' safety buffer: the new one)
-    if (p->rec.held && p->rec.obstacle_figures) PLAN_TRY(lscqp_record_set_obstacle_figures(p->rec.held.get(), next.safety.get()));
-    drop_graph(p);  // (a captured chain holds the obstacles' nodes and the slot split)
-    p->obs = std::move(next);
-    p->pending = (p->pending | lscplan::kPendMissionObstacles) & ~(lscplan::kPendObstacles | lscplan::kPendDrives);  // (the drives went with the old obstacles)
-    return LSCQP_OK;
+    return set_obstacle_tables(p, what, param, n_missions, obstacle_offsets, prepared, true);
 }
 
 int lscqp_plan_set_obstacle_drives(lscqp_plan p, const lscqp_obstacle_drive* drives, int32_t n_dyn, const double* acc_history, int32_t n_history) {
@@ -1334,7 +1324,7 @@ int lscqp_plan_set_obstacle_drives(lscqp_plan p, const lscqp_obstacle_drive* dri
             return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacle_drives: n_dyn is not the number of the plan's obstacles");
         if (n_history > 0 && !acc_history) return lscqp_set_error_(LSCQP_ERR_INVALID_ARGUMENT, "lscqp_plan_set_obstacle_drives: null acc_history");
         PLAN_TRY(lscqp_obstacle_drive_check(p->obs.models.data(), drives, n_dyn, n_history, p->s.n_total));
-        if (p->obs.per_mission()) PLAN_TRY(check_chasers_stay_home(p->obs, drives, mission_offsets_of(p)));
+        if (p->obs.per_mission) PLAN_TRY(check_chasers_stay_home(p->obs, drives, mission_offsets_of(p)));
     }
     OnDevice on(p->device);
     hipError_t e = hipDeviceSynchronize();
@@ -1350,7 +1340,7 @@ int lscqp_plan_set_obstacle_drives(lscqp_plan p, const lscqp_obstacle_drive* dri
         if (e == hipSuccess && nh) e = hipMemcpy(next.history.get(), acc_history, nh * 3 * sizeof(double), hipMemcpyHostToDevice);
         if (e != hipSuccess) return hip_fail(e, what);
         next.n_history = n_history;
-        if (p->obs.per_mission()) next.host.assign(drives, drives + nd);  // (the reset asks again where each chaser's target flies)
+        if (p->obs.per_mission) next.host.assign(drives, drives + nd);  // (the reset asks again where each chaser's target flies)
     }
     drop_graph(p);  // (a captured chain has, or lacks, the drive's node)
     p->obs.drv = std::move(next);
@@ -1425,7 +1415,7 @@ void* obstacle_buffer(lscqp_plan_s* p, int32_t which, size_t* bytes) {
     switch (which) {
     case LSCQP_PLAN_OBS_TABLE: *bytes = (size_t)o.n_dyn * sizeof(lscqp_obstacle); return o.table.get();
     case LSCQP_PLAN_OBS_SAFETY: *bytes = (size_t)p->s.n_agents * sizeof(lscqp_safety_obs); return o.safety.get();
-    case LSCQP_PLAN_OBS_CLOCK: *bytes = (size_t)o.n_clocks() * sizeof(int32_t); return o.clock.get();
+    case LSCQP_PLAN_OBS_CLOCK: *bytes = (size_t)o.n_tables * sizeof(int32_t); return o.clock.get();
     }
     return nullptr;
 }

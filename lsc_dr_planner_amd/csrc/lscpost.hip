@@ -256,11 +256,16 @@ __global__ __launch_bounds__(kSafT) void safety_metrics_kernel(int M, int dim, d
 // up to thousands of agents: one lane per agent, every lane walks the samples of its own plan and the obstacle table (uniform
 // addresses: scalar loads).  IEEE division and square root (few pairs: the agent-agent kernel's fast
 // reciprocals buy nothing here), so the figures are bit-for-bit the double arithmetic of the reference's expression.
+// IDS: every agent has its own obstacles (a table per mission).  Agent a walks row a of ids [n_agents][n_slots], table indices of which
+// those outside [0, n_obstacles) stand for "no obstacle" and are skipped like a REAL entry; closest_obstacle is the SLOT -- the index a plan
+// of that mission alone reports.  Otherwise every agent walks the whole table.  Samples, then entries, strict <: the first pair attaining
+// the minimum.
 constexpr int kObsT = 256;
+template <bool IDS>
 __global__ __launch_bounds__(kObsT) void safety_obstacles_kernel(int M, int dim, double dt, int64_t n_agents, int64_t first_agent, int n_samples,
                                                                  double record_time_step, double z_2d, const double* __restrict__ x_all,
-                                                                 const double* __restrict__ radius, const double* __restrict__ downwash,
-                                                                 int n_obstacles, const lscqp_obstacle* __restrict__ obs,
+                                                                 const double* __restrict__ radius, const double* __restrict__ downwash, int n_slots,
+                                                                 const int32_t* __restrict__ ids, int n_obstacles, const lscqp_obstacle* __restrict__ obs,
                                                                  lscqp_safety_obs* __restrict__ out) {
     const int64_t a = (int64_t)blockIdx.x * kObsT + threadIdx.x;
     if (a >= n_agents) return;
@@ -272,7 +277,9 @@ __global__ __launch_bounds__(kObsT) void safety_obstacles_kernel(int M, int dim,
     for (int s = 0; s < n_samples; s++) {
         float pi[3];
         position_at(M, dim, dt, s * record_time_step, z_2d, x_all + gi * nv, pi);
-        for (int o = 0; o < n_obstacles; o++) {
+        for (int slot = 0; slot < (IDS ? n_slots : n_obstacles); slot++) {
+            const int o = IDS ? ids[a * n_slots + slot] : slot;
+            if (IDS && (o < 0 || o >= n_obstacles)) continue;
             if (obs[o].type == LSCQP_OBSTACLE_REAL) continue;  // :531-532
             const double ro = obs[o].radius;
             const double dwn = (ro * obs[o].downwash + dri) / (ri + ro);  // :538-540
@@ -285,54 +292,6 @@ __global__ __launch_bounds__(kObsT) void safety_obstacles_kernel(int M, int dim,
             }
             const double ratio = sqrt((double)nsq) / (ri + ro);
             if (ratio < best) {  // the reference's strict <: first (sample, obstacle) attaining the minimum
-                best = ratio;
-                bo = o;
-                bs = s;
-            }
-        }
-    }
-    lscqp_safety_obs R;
-    R.safety_ratio_obs = best;
-    R.closest_obstacle = bo;
-    R.sample = bs;
-    out[a] = R;
-}
-
-// The same leg where every agent has its own obstacles (a table per mission): agent a walks row a of ids [n_agents][n_slots], table
-// indices of which those outside [0, n_obstacles) stand for "no obstacle" and are skipped like a REAL entry.  Samples, then slots, strict <:
-// the first (sample, slot) attaining the minimum, and closest_obstacle is the SLOT -- the index a plan of that mission alone reports.
-// The arithmetic is safety_obstacles_kernel's, expression for expression.
-__global__ __launch_bounds__(kObsT) void safety_obstacles_ids_kernel(int M, int dim, double dt, int64_t n_agents, int64_t first_agent, int n_samples,
-                                                                     double record_time_step, double z_2d, const double* __restrict__ x_all,
-                                                                     const double* __restrict__ radius, const double* __restrict__ downwash,
-                                                                     int n_slots, const int32_t* __restrict__ ids, int n_obstacles,
-                                                                     const lscqp_obstacle* __restrict__ obs, lscqp_safety_obs* __restrict__ out) {
-    const int64_t a = (int64_t)blockIdx.x * kObsT + threadIdx.x;
-    if (a >= n_agents) return;
-    const int64_t gi = first_agent + a;
-    const int nv = dim * 6 * M;
-    const double ri = radius[gi], dri = ri * downwash[gi];
-    const int32_t* mine = ids + a * n_slots;
-    double best = INFINITY;
-    int bo = -1, bs = -1;
-    for (int s = 0; s < n_samples; s++) {
-        float pi[3];
-        position_at(M, dim, dt, s * record_time_step, z_2d, x_all + gi * nv, pi);
-        for (int slot = 0; slot < n_slots; slot++) {
-            const int o = mine[slot];
-            if (o < 0 || o >= n_obstacles) continue;
-            if (obs[o].type == LSCQP_OBSTACLE_REAL) continue;  // :531-532
-            const double ro = obs[o].radius;
-            const double dwn = (ro * obs[o].downwash + dri) / (ri + ro);  // :538-540
-            const float dx = pi[0] - (float)obs[o].position[0], dy = pi[1] - (float)obs[o].position[1];
-            const float dz = (float)((double)(pi[2] - (float)obs[o].position[2]) / dwn);
-            float nsq;
-            {
-#pragma clang fp contract(off)
-                nsq = dx * dx + dy * dy + dz * dz;
-            }
-            const double ratio = sqrt((double)nsq) / (ri + ro);
-            if (ratio < best) {
                 best = ratio;
                 bo = slot;
                 bs = s;
@@ -379,8 +338,9 @@ extern "C" int lscqp_safety_obstacles_device(lscqp_handle h, int64_t n_agents, i
     if (const int rc = lscqp_need_device_()) return rc;
     const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
     const unsigned blocks = (unsigned)((n_agents + lscpost::kObsT - 1) / lscpost::kObsT);
-    hipLaunchKernelGGL(lscpost::safety_obstacles_kernel, dim3(blocks), dim3(lscpost::kObsT), 0, (hipStream_t)stream, cd->M, cd->dim, cd->dt, n_agents,
-                       first_agent, (int)n_samples, record_time_step, z_2d, d_x_all, d_radius, d_downwash, (int)n_obstacles, d_obstacles, d_out);
+    hipLaunchKernelGGL(lscpost::safety_obstacles_kernel<false>, dim3(blocks), dim3(lscpost::kObsT), 0, (hipStream_t)stream, cd->M, cd->dim, cd->dt, n_agents,
+                       first_agent, (int)n_samples, record_time_step, z_2d, d_x_all, d_radius, d_downwash, 0, (const int32_t*)nullptr, (int)n_obstacles,
+                       d_obstacles, d_out);
     return lscqp_launch_result_(hipGetLastError());
 }
 
@@ -397,7 +357,7 @@ extern "C" int lscqp_safety_obstacles_ids_device(lscqp_handle h, int64_t n_agent
     if (const int rc = lscqp_need_device_()) return rc;
     const lscqp_class_desc* cd = lscqp_class_desc_of_(h);
     const unsigned blocks = (unsigned)((n_agents + lscpost::kObsT - 1) / lscpost::kObsT);
-    hipLaunchKernelGGL(lscpost::safety_obstacles_ids_kernel, dim3(blocks), dim3(lscpost::kObsT), 0, (hipStream_t)stream, cd->M, cd->dim, cd->dt, n_agents,
+    hipLaunchKernelGGL(lscpost::safety_obstacles_kernel<true>, dim3(blocks), dim3(lscpost::kObsT), 0, (hipStream_t)stream, cd->M, cd->dim, cd->dt, n_agents,
                        first_agent, (int)n_samples, record_time_step, z_2d, d_x_all, d_radius, d_downwash, (int)n_slots, d_obstacle_ids, (int)n_obstacles,
                        d_obstacles, d_out);
     return lscqp_launch_result_(hipGetLastError());

@@ -1,8 +1,10 @@
 """The three kernels of a mission's own obstacles alone (include/lscqp.h, "a mission's own obstacles"; csrc/lscobstacle.hip:
-obstacle_advance_missions_kernel, obstacle_drive_missions_kernel; csrc/lscpost.hip: safety_obstacles_ids_kernel), each against the entry it
-is the per-mission form of, run on one mission's slice (one agent's gathered sub-table) alone.  Every comparison is exact equality of bytes;
-every byte that must not be written holds a sentinel, guard entries behind the buffers included.  The shapes are
-tests/mission_obstacles_cases.py's."""
+obstacle_advance_kernel<true>, obstacle_drive_kernel<true>; csrc/lscpost.hip: safety_obstacles_kernel<true>), each against the entry of one
+shared table (the <false> instantiation of the same text), run on one mission's slice (one agent's gathered sub-table) alone.  The single-table
+entries are pinned on their own against tests/obstacle_reference.py, the oracle and lscqp_obstacle_drive_host.  A plan with one shared table
+runs the <true> instantiations over one table and identity ids: the one-table cases here -- SHAPES' (65,) and the identity rows of the
+safety leg -- hold them to what such a plan ran before.  Every comparison is exact equality of bytes; every byte that must not be written
+holds a sentinel, guard entries behind the buffers included.  The shapes are tests/mission_obstacles_cases.py's."""
 import numpy as np
 import pytest
 
@@ -229,3 +231,29 @@ def test_the_safety_figures_by_ids_are_the_single_entrys_on_each_agents_gathered
         assert (got["closest_obstacle"][rows == 2] == 0).any() and not (got["closest_obstacle"][rows == 2] == 1).any()
         assert not (got["closest_obstacle"][rows == 3] == 4).any()
         assert (got["closest_obstacle"] != c["ids"][np.arange(n), np.maximum(got["closest_obstacle"], 0)])[~nothing].any()  # (not the table index)
+
+
+def test_one_table_of_65_entries_is_among_the_shapes_of_the_advance_and_the_drive():
+    """What a plan with one shared table launches: K = 1.  Both parametrisations above run MC.SHAPES."""
+    assert (65,) in MC.SHAPES and len(MC.offsets((65,))) == 2
+
+
+@pytest.mark.parametrize("n", (1, 65, 257))
+def test_the_safety_figures_by_identity_ids_are_the_single_entrys_on_the_same_table(api, torch_cuda, sol, n):
+    """Every agent's row 0 .. 6 over the seven entries of MC.safety_case (the REAL entry, the tied twins): what a plan with one shared table
+    enqueues.  Byte for byte lscqp_safety_obstacles_device on that table -- the slot is the table index, the lower twin wins the tie."""
+    torch = torch_cuda
+    c = MC.safety_case(api, n)
+    R, T = api.SAFETY_OBS_DTYPE.itemsize, len(c["table"])
+    assert T == 7
+    ids = np.ascontiguousarray(np.tile(np.arange(T, dtype=np.int32), (n, 1)))
+    d_x, d_r, d_w, d_table = _dev(torch, c["x"]), _dev(torch, c["radius"]), _dev(torch, c["downwash"]), _dev(torch, c["table"])
+    d_want = torch.zeros(n * R, dtype=torch.uint8, device="cuda")
+    d_out = torch.full(((n + 1) * R,), GUARD, dtype=torch.uint8, device="cuda")
+    sol.safety_obstacles_device(n, 0, n, 3, 0.07, d_x, d_r, d_w, T, d_table, d_want)
+    sol.safety_obstacles_ids_device(n, 0, n, 3, 0.07, d_x, d_r, d_w, T, _dev(torch, ids), T, d_table, d_out)
+    torch.cuda.synchronize()
+    raw, want = d_out.cpu().numpy(), _host(d_want, api.SAFETY_OBS_DTYPE)
+    assert raw[:n * R].tobytes() == want.tobytes(), [a for a in range(n) if raw[a * R:(a + 1) * R].tobytes() != want[a:a + 1].tobytes()][:8]
+    assert (raw[n * R:] == GUARD).all()
+    assert np.isfinite(want["safety_ratio_obs"]).all() and (want["closest_obstacle"] != MC.REAL).all() and (want["closest_obstacle"] != MC.TWIN_B).all()

@@ -408,3 +408,41 @@ def test_a_plane_mission_with_one_straight_obstacle_eager_equals_graph(api, torc
     rows = np.frombuffer(out[0][-1][api.PLAN_ROWS], api.ROW_DTYPE).reshape(4, 4, M, 6)
     assert (rows["nz"][:, 0] == 0).all() and np.abs(rows["nx"][:, 0]).max() > 0
     sol.close()
+
+
+def test_a_shared_table_is_the_one_table_case_of_the_tables_per_mission(api, torch_cuda):
+    """The plane mission above, three replans eager and by graph.  A plan with one shared table keeps it as one table of the per-mission
+    layout and moves it by the per-mission entries: as many graph nodes as a plan of one mission that owns the same obstacle, one clock
+    word, a table of n_dyn entries, every buffer of every replan that plan's, and safety figures that are lscqp_safety_obstacles_device's
+    on the plans and the table the chain left."""
+    torch, z = torch_cuda, 1.0
+    starts = np.array([[-2.0, -2.0, z], [2.0, -2.0, z], [2.0, 2.0, z], [-2.0, 2.0, z]])
+    goals = -starts
+    goals[:, 2] = z
+    sol = api.Solver(api.make_desc(M=M, dim=2, dt=DT, comm_range=0.0, use_sfc=False))
+    models = api.obstacle_models([dict(type="straight", start=[-1.5, 0.2, z], goal=[1.5, -0.2, z], size=0.3, speed=0.3, max_acc=0.5, downwash=1.0)])
+    ag = agents(api, 4)
+    d_radius, d_downwash = torch.from_numpy(ag["radius"].copy()).cuda(), torch.from_numpy(ag["downwash"].copy()).cuda()
+    flights, nodes = {}, {}
+    for owned in (False, True):
+        for graph in (False, True):
+            plan = api.Plan(sol, None, 4, 4, ag, constraint_mode=api.GEN_LSC, optimize_goal=False, closed_loop=True, safety_samples=2, record_time_step=0.1,
+                            z_2d=z)
+            plan.set_mission_obstacles([models]) if owned else plan.set_obstacles(models)
+            assert plan.obstacle_pointer(api.PLAN_OBS_CLOCK)[1] == 4 and plan.obstacle_pointer(api.PLAN_OBS_TABLE)[1] == len(models) * api.OBSTACLE_DTYPE.itemsize
+            flights[owned, graph] = fly(api, torch, plan, starts, goals, 3, graph=graph)
+            nodes[owned, graph] = plan.graph_nodes()
+            assert plan.get_obstacles(api.PLAN_OBS_CLOCK).tolist() == [3]
+            if not owned and not graph:
+                for k, s in enumerate(flights[owned, graph]):
+                    d_want = torch.zeros(4 * api.SAFETY_OBS_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+                    up = lambda b: torch.from_numpy(np.frombuffer(b, np.uint8).copy()).cuda()  # noqa: E731
+                    sol.safety_obstacles_device(4, 0, 4, 2, 0.1, up(s[api.PLAN_PLAN]), d_radius, d_downwash, len(models), up(s[16 + api.PLAN_OBS_TABLE]), d_want,
+                                                z_2d=z)
+                    torch.cuda.synchronize()
+                    assert s[16 + api.PLAN_OBS_SAFETY] == d_want.cpu().numpy().tobytes(), k
+                    assert np.isfinite(np.frombuffer(s[16 + api.PLAN_OBS_SAFETY], api.SAFETY_OBS_DTYPE)["safety_ratio_obs"]).all()
+            plan.close()
+    assert flights[False, False] == flights[False, True] == flights[True, False] == flights[True, True]
+    assert nodes[False, True] == nodes[True, True] > 0 and nodes[False, False] == nodes[True, False] == 0
+    sol.close()
