@@ -791,7 +791,7 @@ __global__ __launch_bounds__(64) void select_neighbours_kernel(int64_t n_agents,
         total += __popcll(m);
     }
     __syncthreads();
-    if (total <= kCap) {
+    if (__builtin_expect(total <= kCap, 1)) {  // (the case of every swarm with a range; profiles/r38_neighbour_ties.txt on what the hint is for)
         // everything in range is in LDS.  No overflow: copy the first `total`.  Overflow: an entry stays if fewer than n_obs
         // entries precede it in (distance, id) order -- a rank count over at most kCap candidates -- and the survivors are
         // compacted in id order (the list is in id order already)
@@ -822,32 +822,39 @@ __global__ __launch_bounds__(64) void select_neighbours_kernel(int64_t n_agents,
     int n_strict = 0;  // overflow: keep everything nearer than `limit`, then the smallest ids at exactly `limit`
     bool capped = false;
     if (total > n_obs && n_obs > 0) {
-        // the n_obs-th smallest distance, by bisection on the float-valued distances (they are exact in double)
-        double lo = 0, hi = range > 0 ? range : 3.0e38;
-        if (!(range > 0)) {
-            double mx = 0;
+        // the n_obs-th smallest distance.  The distances are non-negative float values, and those are ordered as their bit patterns are:
+        // a bisection over the pattern ends on a value that some agent has, in at most 31 counting passes, however far below the range
+        // it lies.  (A bisection of the value in doubles, 64 rounds at the most, is not: below about hi 2^-11 it ends ABOVE the distance,
+        // nobody is at `limit`, and the agents tied there are taken for strictly nearer ones, smallest ids first -- NOTES.md section 47.)
+        auto bits_of = [&](int64_t j) -> int32_t { return __float_as_int((float)dist_of(j)); };
+        int32_t lo = -1, hi = 0x7f800000;  // (lo: fewer than n_obs at or below it; hi: at least n_obs)
+        if (range > 0) {
+            float fr = (float)range;  // the largest float <= range
+            if ((double)fr > range) fr = __int_as_float(__float_as_int(fr) - 1);
+            hi = __float_as_int(fr);
+        } else {
+            int32_t mx = 0;
             for (int64_t base = m_lo; base < m_hi; base += 64) {
                 const int64_t j = base + lane;
-                double d = (j < m_hi && j != gi) ? dist_of(j) : 0.0;
-                for (int o = 32; o > 0; o >>= 1) d = fmax(d, __shfl_xor(d, o));
-                mx = fmax(mx, d);
+                int32_t b = (j < m_hi && j != gi) ? bits_of(j) : 0;
+                for (int o = 32; o > 0; o >>= 1) b = max(b, __shfl_xor(b, o));
+                mx = max(mx, b);
             }
             hi = mx;
         }
-        for (int it = 0; it < 64 && lo < hi; it++) {
-            const double mid = 0.5 * (lo + hi);
-            if (mid <= lo || mid >= hi) break;
+        while (hi - lo > 1) {
+            const int32_t mid = lo + (hi - lo) / 2;
             int c = 0;
             for (int64_t base = m_lo; base < m_hi; base += 64) {
                 const int64_t j = base + lane;
-                c += __popcll(__ballot(j < m_hi && j != gi && dist_of(j) <= mid));
+                c += __popcll(__ballot(j < m_hi && j != gi && bits_of(j) <= mid));
             }
             if (c >= n_obs)
                 hi = mid;
             else
                 lo = mid;
         }
-        limit = hi;  // smallest distance value with at least n_obs agents at or below it
+        limit = (double)__int_as_float(hi);  // smallest distance with at least n_obs agents at or below it: the n_obs-th smallest
         for (int64_t base = m_lo; base < m_hi; base += 64) {
             const int64_t j = base + lane;
             n_strict += __popcll(__ballot(j < m_hi && j != gi && dist_of(j) < limit));

@@ -1,6 +1,6 @@
 """Measurement of the kernels either side of the QP: constraint generation in the three planner modes,
 safety metrics, voxel-map construction and corridor construction.
-    python tools/bench_next_rows.py [N] [--cpu]
+    python tools/bench_next_rows.py [N] [--cpu] [--dim2] [--neighbours]
 Kernel times are HIP-event averages on the launch stream; --cpu also times the OpenMP oracle on the same inputs."""
 import json
 import os
@@ -43,6 +43,22 @@ goal_all = np.ascontiguousarray(sw.pos + 0.5, dtype=np.float64)
 sol = api.Solver(api.make_desc(M=M, dim=dim, world_min=sw.world_min, world_max=sw.world_max))
 up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
 d_traj, d_nbr = up(init), up(nbr)
+
+
+def neighbour_lines():
+    """Neighbour selection at the launch file's range (the in-range agents fit the kernel's LDS list: a rank count) and with the range
+    unbounded (N - 1 in range: above 1024 the threshold distance is found by bisection).  --neighbours: these lines alone."""
+    d_nb2 = torch.zeros(N * n_obs, dtype=torch.int32, device=dev)
+    d_cnt = torch.zeros(N, dtype=torch.int32, device=dev)
+    d_pos = up(np.float32(sw.pos).astype(np.float64))
+    for name, rng_ in (("select_neighbours (broadcastMsgs range filter)", 3.0), ("select_neighbours, range unbounded", 0.0)):
+        ms = timed(lambda: sol.select_neighbours_device(N, 0, N, n_obs, rng_, d_pos, d_nb2, d_cnt), reps=100)
+        print(json.dumps({"kernel": name, "agents": N, "kernel_ms": ms, "pairs": N * (N - 1), "in_range_max": int(d_cnt.max())}))
+
+
+if "--neighbours" in sys.argv:
+    neighbour_lines()
+    sys.exit(0)
 d_r = torch.full((N,), sw.radius, dtype=torch.float64, device=dev)
 d_dw = torch.full((N,), sw.downwash, dtype=torch.float64, device=dev)
 d_goal = up(goal_all)
@@ -78,11 +94,7 @@ if CPU and N <= 4096:
 print(json.dumps(rec))
 
 # the small per-agent kernels of a replan step: neighbour selection, shift of the previous plans, goal LP, validity / next state
-d_nb2 = torch.zeros(N * n_obs, dtype=torch.int32, device=dev)
-d_cnt = torch.zeros(N, dtype=torch.int32, device=dev)
-d_pos = up(np.float32(sw.pos).astype(np.float64))
-ms = timed(lambda: sol.select_neighbours_device(N, 0, N, n_obs, 3.0, d_pos, d_nb2, d_cnt), reps=100)
-print(json.dumps({"kernel": "select_neighbours (broadcastMsgs range filter)", "agents": N, "kernel_ms": ms, "pairs": N * (N - 1)}))
+neighbour_lines()
 ms = timed(lambda: sol.shift_traj_device(N, d_x, d_traj, z_2d=1.0, shift=1), reps=100)
 print(json.dumps({"kernel": "shift_traj (initialTrajPlanningPrevSol)", "agents": N, "kernel_ms": ms}))
 d_off = up((np.arange(N + 1) * n_obs * M * 6).astype(np.int64))
